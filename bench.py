@@ -18,10 +18,13 @@ A *step* is one pass of the hot path over the device-resident batches of the con
                            over the ranks (strong scaling: the same corpus at every N), walked in waves of
                            <= 24576 files that fit one GPU; a step is one pass over the rank's whole shard.
 
-Rank 0 prints ONE JSON line with `roofline` (per-kernel event times measured on the launch stream
-inside the timed region; the dominant kernel at the top level) and `cpu_baseline` (the CPU oracle, a
-scalar C port of the reference algorithms -- the D reference cannot be built here -- timed by a native
-thread pool on this box's host cores on a bounded sample of the same workload).
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if `--dump-outputs DIR` is
+given and prints ONE JSON line: `value`, `ms_per_step` and `roofline` (per-kernel event times measured on the
+launch stream inside the timed region; the dominant kernel at the top level).  `--full` adds everything
+else, after the timed steps: parity against the CPU oracle, `cpu_baseline` (the oracle, a scalar C port
+of the reference algorithms -- the D reference cannot be built here -- timed by a native thread pool on
+this box's host cores on a bounded sample of the same workload), the full-fetch and side-by-side legs,
+the copy probe, `other_workloads`, the PMC traffic passes and the full record file.
 """
 import argparse
 import json
@@ -38,6 +41,8 @@ for p in (os.path.join(ROOT, "audio-formats_amd"), os.path.join(ROOT, "tests")):
 
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 METRIC = "decoded samples/sec (batched MP3+OGG+FLAC) at 1/2/4/8 MI355X vs CPU ref"
+DUMP_BYTES = 48 << 20            # --dump-outputs: bytes written in all, at most
+DUMP_SEED = 0x0D0D               # ... and the seed of the sample taken from a larger plane
 
 
 def parse_args(argv=None):
@@ -49,6 +54,13 @@ def parse_args(argv=None):
     ap.add_argument("--files", type=int, default=1024, help="C2/C3 files per GPU (C4 has 4x as many); BASELINE: 1024")
     ap.add_argument("--c5-files", type=int, default=65536, help="files of the mixed corpus (BASELINE: 65536)")
     ap.add_argument("--seg", type=int, default=0, help="MP3 granules per wavefront segment (0 = library default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything besides the headline figure: parity against the CPU oracle, the CPU baseline, "
+                         "the full-fetch legs, the side-by-side step, the copy probe, `other_workloads`, the PMC traffic passes and the full "
+                         "record file (the --no-* options below trim such a run); off: set up, warm up, time, print the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<codec>.npy (float32 PCM; FLAC's int32 samples "
+                         "as float64): each output plane whole, or a fixed, seeded sample of it, %d MiB at most in all (rank 0 only)" % (DUMP_BYTES >> 20))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-full-fetch", action="store_true", help="skip the MP3 leg that fetches all 32 subbands")
@@ -58,7 +70,7 @@ def parse_args(argv=None):
                     help="skip `other_workloads` (the side-by-side step; the C5 corpus, dense CELT, QOA and the end-to-end batches, each in "
                          "a child process after the headline measurement; only at N = 1 with the default config)")
     ap.add_argument("--measure-traffic", action="store_true", default=None,
-                    help="N = 1, default config (where it is the default when rocprofv3 is on the PATH): before the run, measure `roofline.traffic` of "
+                    help="N = 1, default config (where it is the default of a --full run when rocprofv3 is on the PATH): before the run, measure `roofline.traffic` of "
                          "the three headline kernels in child processes (separate `rocprofv3 --pmc FETCH_SIZE` / `WRITE_SIZE` passes over bench.py "
                          "--config c2 / c3 / c4, FLAC's counters calibrated on its access pattern: tools/pmc_collect.sh) instead of reading the "
                          "committed passes under profiles/; adds about half a minute")
@@ -297,7 +309,7 @@ def other_workloads(args):
             return None, f"exit code {r.returncode}: {r.stderr.decode()[-400:]}", time.perf_counter() - t0
         return json.loads(lines[-1]), (None if r.returncode == 0 else f"exit code {r.returncode}"), time.perf_counter() - t0
 
-    d, err, wall = child([os.path.abspath(__file__), "--config", "c5", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full-line",
+    d, err, wall = child([os.path.abspath(__file__), "--config", "c5", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--full-line",
                           "--c5-files", str(args.c5_files)], 420)
     if d is None:
         out["c5"] = {"error": err}
@@ -313,7 +325,7 @@ def other_workloads(args):
     env32 = dict(env, AFG_FLAC_RES32="1")
     t0 = time.perf_counter()
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", "c4", "--steps", "5", "--warmup", "1", "--no-cpu-baseline",
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", "c4", "--steps", "5", "--warmup", "1", "--full", "--no-cpu-baseline",
                             "--no-others", "--full-line", "--files", str(args.files)], env=env32, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
         lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
         d = json.loads(lines[-1]) if lines else None
@@ -488,6 +500,9 @@ def emit(args, full):
     if args.full_line:
         print(json.dumps(full), flush=True)
         return
+    if not (args.full or args.full_record):
+        print(compact_line(full), flush=True)           # a plain run: the line alone, no record file
+        return
     path = args.full_record or os.path.join(ROOT, "gpurun_out", "bench_full.json")
     rel = None
     try:
@@ -510,6 +525,20 @@ def load_traffic(name):
             return json.load(fh)
     except Exception:
         return None
+
+
+def output_sample(plane, quota, seed):
+    """--dump-outputs: a host copy of the 1-D device tensor `plane` -- whole when it holds at most `quota` elements, else at
+    `quota` distinct positions drawn by a generator seeded with `seed`, in ascending order -- as float32, or float64 for integer
+    planes (FLAC's int32 samples, exactly)."""
+    import numpy as np
+    import torch
+    n = plane.numel()
+    if n > quota:
+        idx = np.sort(np.random.default_rng(seed).choice(n, quota, replace=False)).astype(np.int64)
+        plane = plane.index_select(0, torch.from_numpy(idx).to(plane.device))
+    a = plane.cpu().numpy()
+    return a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
 
 
 def run_rank(args, world, rank, local_rank):
@@ -573,9 +602,30 @@ def run_rank(args, world, rank, local_rank):
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
         return float(t.item())
 
-    def measure_c5(steps, warmup, want_cpu):
+    dump = {}                                         # --dump-outputs: codec -> [sample of its output plane per workload]
+
+    def take_outputs(wl, n_sets):
+        """--dump-outputs, rank 0: sample every part's output plane as its last timed step left it; `n_sets` workloads (the
+        waves of C5) share DUMP_BYTES."""
+        if not args.dump_outputs or rank != 0:
+            return
+        for i, p in enumerate(wl.parts):
+            plane = p.out_plane().view(-1)
+            quota = DUMP_BYTES // (n_sets * len(wl.parts)) // (4 if plane.dtype == torch.float32 else 8)
+            got = dump.setdefault(p.name, [])
+            got.append(output_sample(plane, quota, [DUMP_SEED, len(got), i]))
+
+    def write_outputs():
+        if not args.dump_outputs or rank != 0:
+            return
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arrs in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.concatenate(arrs))
+
+    def measure_c5(steps, warmup, want_cpu, full, dump_waves):
         """BASELINE configs[4] on this rank's shard: (elapsed s of this rank, samples of this rank, per-codec kernel records,
-        parity of rank 0's first wave, cpu baseline or None, extras, number of waves, the manifest)."""
+        parity of rank 0's first wave (`full` only), cpu baseline or None, extras, number of waves, the manifest).
+        dump_waves: keep every wave's outputs for --dump-outputs."""
         kern5, parity5, cpu5, extra5 = {}, {}, None, {}
         man = corpus.c5_manifest(args.c5_files)
         waves = corpus.c5_shard_waves(man, rank, world, args.c5_wave_files or corpus.C5_WAVE_FILES)
@@ -585,6 +635,8 @@ def run_rank(args, world, rank, local_rank):
             if args.only:
                 wl.parts = [p for p in wl.parts if p.name in args.only.split(",")]
             e, per_part = timed_steps(wl, steps, warmup)
+            if dump_waves:
+                take_outputs(wl, len(waves))
             elapsed5 += e
             my5 += wl.samples
             for p, ms in zip(wl.parts, per_part):
@@ -593,7 +645,7 @@ def run_rank(args, world, rank, local_rank):
                 k["samples"] += p.samples; k["alg_bytes"] += p.alg_bytes; k["units"] += p.units
             # the Opus members on their own (in the step they run on a second stream beside the other codecs' kernels, so
             # their event span there is the overlapped one)
-            for p in wl.parts:
+            for p in (wl.parts if full else ()):
                 if p.name == "celt":
                     ms = []
                     for i in range(3):
@@ -604,7 +656,7 @@ def run_rank(args, world, rank, local_rank):
                             ms.append(e0.elapsed_time(e1))
                     extra5["celt_alone_ms"] = extra5.get("celt_alone_ms", 0.0) + sum(ms) / len(ms)
                     extra5["celt_alone_bytes"] = extra5.get("celt_alone_bytes", 0) + p.alg_bytes
-            if rank == 0 and wi == 0:
+            if rank == 0 and wi == 0 and full:
                 import oraclelib
                 parity5 = {p.name: p.check(oraclelib) for p in wl.parts}
                 if want_cpu:
@@ -618,7 +670,8 @@ def run_rank(args, world, rank, local_rank):
     kern = {}                                         # name -> dict(ms list, samples, alg_bytes, units)
     parity, cpu, extra = {}, None, {}
     if args.config == "c5":
-        elapsed, my_samples, kern, parity, cpu, extra, waves, man = measure_c5(args.steps, args.warmup, not args.no_cpu_baseline)
+        elapsed, my_samples, kern, parity, cpu, extra, waves, man = measure_c5(args.steps, args.warmup, not args.no_cpu_baseline, args.full, True)
+        write_outputs()
         total_samples = reduce_sum(float(my_samples))
         scaling = "strong"
         workload = (f"{args.c5_files}-file mixed corpus (40% MP3 / 25% Ogg Vorbis / 25% FLAC / 10% Opus-CELT, durations "
@@ -631,6 +684,8 @@ def run_rank(args, world, rank, local_rank):
         which = {"c234": ("mp3", "vorbis", "flac"), "c2": ("mp3",), "c3": ("vorbis",), "c4": ("flac",)}[args.config]
         wl = corpus.build_c234(dev, rank, which, args.files, args.seg)
         elapsed, per_part = timed_steps(wl, args.steps, args.warmup)
+        take_outputs(wl, 1)
+        write_outputs()
         my_samples = wl.samples
         for p, ms in zip(wl.parts, per_part):
             kern[p.name] = {"kernel": p.kernel, "ms": ms, "samples": p.samples, "alg_bytes": p.alg_bytes, "units": p.units,
@@ -642,7 +697,7 @@ def run_rank(args, world, rank, local_rank):
                          + ("; residual rows int32" if os.environ.get("AFG_FLAC_RES32") else "; residual rows int16, as the host parser packs 16-bit material") + ")"}
         workload = " + ".join(names[w] for w in which) + " per GPU, resident together; device-resident transform-stage records -> PCM"
         cfg_extra = {"files_per_gpu": {w: (4 * args.files if w == "flac" else args.files) for w in which}}
-        if rank == 0:
+        if rank == 0 and args.full:
             import oraclelib
             parity = {p.name: p.check(oraclelib, 2) for p in wl.parts}
             # MP3 with every subband fetched (no AFG_MP3_NZ_BANDS declaration): the same kernel moving all algorithmic bytes
@@ -719,13 +774,13 @@ def run_rank(args, world, rank, local_rank):
     elapsed = reduce_max(elapsed)
     # ---- N > 1, default config: the scaling configuration itself (BASELINE configs[4], strong scaling) on the same ranks ----
     c5_tail = None
-    if world > 1 and args.config == "c234" and not args.no_others:
+    if world > 1 and args.config == "c234" and args.full and not args.no_others:
         wl = mp3 = p = None                              # release the headline batches: the C5 waves need the room
         import gc
         gc.collect()
         torch.cuda.empty_cache()
         barrier()
-        e5, my5, kern5, parity5, _, extra5, waves5, man5 = measure_c5(3, 1, False)
+        e5, my5, kern5, parity5, _, extra5, waves5, man5 = measure_c5(3, 1, False, True, False)
         e5_max, e5_min = reduce_max(e5), reduce_min(e5)
         tot5 = reduce_sum(float(my5))
         if rank == 0:
@@ -816,7 +871,7 @@ def run_rank(args, world, rank, local_rank):
     if args.oversubscribe and world > ndev:
         line["oversubscribed"] = f"{world} ranks on {ndev} device(s): a launcher test, not a scaling point"
     failed = [n for n, p in parity.items() if p["mismatches"]]
-    if world == 1 and args.config == "c234" and not args.no_others:
+    if world == 1 and args.config == "c234" and args.full and not args.no_others:
         # release the headline batches (148 GB) first: the C5 waves need the room
         wl = mp3 = p = None
         import gc
@@ -848,7 +903,7 @@ def main():
             return launch_ranks(args)                  # before anything in this process touches a GPU
         world, rank, local_rank = 1, 0, 0
         # (by default only in the full default run -- the one the driver times -- and never inside this script's own children)
-        want = args.measure_traffic if args.measure_traffic is not None else (not args.no_others and not os.environ.get("AFG_BENCH_NESTED"))
+        want = args.measure_traffic if args.measure_traffic is not None else (args.full and not args.no_others and not os.environ.get("AFG_BENCH_NESTED"))
         if want and args.config == "c234" and args.files == 1024:
             args.live_traffic = measure_traffic()      # child processes: this one has not touched a GPU yet
     else:

@@ -85,3 +85,26 @@ def test_notes_land_on_their_own_codec():
     src = open(os.path.join(ROOT, "bench.py")).read()
     i = src.index('kernels[-1]["input_rows"] = "int16 residual rows')
     assert 'if name == "flac":' in src[i - 700:i]
+
+
+def test_plain_run_is_the_default():
+    bench = _bench()
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_output_sample_is_fixed_and_exact():
+    """--dump-outputs: a plane that fits is written whole; a larger one as the same seeded sample every time; int32 samples
+    as float64 without loss, float32 as float32."""
+    import numpy as np
+    import torch
+    bench = _bench()
+    f = torch.randn(1000, generator=torch.Generator().manual_seed(1))
+    assert np.array_equal(bench.output_sample(f, 1000, [1]), f.numpy()) and bench.output_sample(f, 1000, [1]).dtype == np.float32
+    i = torch.arange(-(1 << 31), -(1 << 31) + 50000, dtype=torch.int32) * 3 + 7
+    a, b = bench.output_sample(i, 4000, [bench.DUMP_SEED, 0, 2]), bench.output_sample(i, 4000, [bench.DUMP_SEED, 0, 2])
+    assert a.dtype == np.float64 and a.size == 4000 and np.array_equal(a, b) and len(np.unique(a)) == 4000
+    assert np.all(np.isin(a.astype(np.int64), i.numpy().astype(np.int64)))
+    assert not np.array_equal(a, bench.output_sample(i, 4000, [bench.DUMP_SEED, 1, 2]))

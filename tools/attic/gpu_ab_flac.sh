@@ -3,7 +3,7 @@
 # (audio-formats_amd/lib/libafg_<variant>.so), int16 rows; "<variant>:32" runs that variant with int32 rows
 R="$GRAFT_REPO_ROOT"; [ -z "$R" ] && R=/root/repo
 cd "$R"
-run() { python bench.py --config c4 --steps 5 --warmup 1 --no-cpu-baseline --no-others 2>/dev/null | python -c "
+run() { python bench.py --config c4 --steps 5 --warmup 1 --full --no-cpu-baseline --no-others 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,7 +3,7 @@
 R="$GRAFT_REPO_ROOT"; [ -z "$R" ] && R=/root/repo
 cd "$R"
 for seg in "$@"; do
-AFG_CELT_SEG_RECS=$seg python bench.py --config c5 --only celt --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
+AFG_CELT_SEG_RECS=$seg python bench.py --config c5 --only celt --steps 3 --warmup 1 --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,7 +2,7 @@
 # tools/gpu_c5_order.sh: BASELINE configs[4] on one GPU with the Opus members overlapped / serial and different launch orders
 R="$GRAFT_REPO_ROOT"; [ -z "$R" ] && R=/root/repo
 cd "$R"; mkdir -p gpurun_out
-run() { python bench.py --config c5 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
+run() { python bench.py --config c5 --steps 3 --warmup 1 --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,7 +3,7 @@
 R="$GRAFT_REPO_ROOT"; [ -z "$R" ] && R=/root/repo
 cd "$R"; export TMPDIR=/tmp
 ( timeout 1500 python -m pytest tests/test_vorbis_walk_gpu.py tests/test_vorbis_gpu.py -m gpu -x -q -n 4 2>&1 | tail -5 )
-run() { python bench.py --config c3 --steps 10 --warmup 2 --no-cpu-baseline --no-others --no-full-fetch 2>/dev/null | python -c "
+run() { python bench.py --config c3 --steps 10 --warmup 2 --full --no-cpu-baseline --no-others --no-full-fetch 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

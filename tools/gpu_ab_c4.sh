@@ -2,7 +2,7 @@
 # tools/gpu_ab_c4.sh [variant...]: C4 (bench.py --config c4) for the product build and each named library variant
 R="$GRAFT_REPO_ROOT"; [ -z "$R" ] && R=/root/repo
 cd "$R"; export TMPDIR=/tmp
-run() { python bench.py --config c4 --steps 10 --warmup 2 --no-cpu-baseline --no-others 2>/dev/null | python -c "
+run() { python bench.py --config c4 --steps 10 --warmup 2 --full --no-cpu-baseline --no-others 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

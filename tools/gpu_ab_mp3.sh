@@ -3,7 +3,7 @@
 R="$GRAFT_REPO_ROOT"; [ -z "$R" ] && R=/root/repo
 cd "$R"
 ( timeout 900 python -m pytest tests/test_mp3_gpu.py tests/test_mp3_layer12_gpu.py tests/test_mp3_requant_gpu.py -m gpu -x -q 2>&1 | tail -3 )
-run() { python bench.py --config c2 --steps 5 --warmup 1 --no-cpu-baseline --no-others --no-full-fetch 2>/dev/null | python -c "
+run() { python bench.py --config c2 --steps 5 --warmup 1 --full --no-cpu-baseline --no-others --no-full-fetch 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,13 +3,13 @@
 # (run on the GPU box; the small results are copied into profiles/ afterwards)
 R="$GRAFT_REPO_ROOT"; [ -z "$R" ] && R=/root/repo
 cd "$R"; export TMPDIR=/tmp; P=gpurun_out/r06_prof; mkdir -p $P
-( timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 2> $P/bench.err ) > $P/bench_line.json
+( timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full 2> $P/bench.err ) > $P/bench_line.json
 cp gpurun_out/bench_full.json $P/bench_full.json
-( timeout 900 python3 bench.py --config c5 --steps 3 --warmup 1 --cpu-seconds 8 --full-record $P/c5_full.json 2> $P/c5.err ) > $P/c5_line.json
+( timeout 900 python3 bench.py --config c5 --steps 3 --warmup 1 --full --cpu-seconds 8 --full-record $P/c5_full.json 2> $P/c5.err ) > $P/c5_line.json
 cd /tmp
-rocprofv3 --kernel-trace --stats -d "$R/$P/stats" -- python3 "$R/bench.py" --steps 10 --warmup 2 --no-cpu-baseline --no-others > /dev/null 2> "$R/$P/stats.err"
+rocprofv3 --kernel-trace --stats -d "$R/$P/stats" -- python3 "$R/bench.py" --steps 10 --warmup 2 --full --no-cpu-baseline --no-others > /dev/null 2> "$R/$P/stats.err"
 cd "$R"
-python3 tools/export_kernel_stats.py $P/stats $P/r06_kernel_stats.csv "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-others" > /dev/null
+python3 tools/export_kernel_stats.py $P/stats $P/r06_kernel_stats.csv "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-others" > /dev/null
 find $P/stats -name "*.db" -delete
 bash tools/pmc_collect.sh r06_pmc_mp3_tolerance_kernel mp3_tolerance_kernel bench.py --config c2 --steps 3 --warmup 1 --no-cpu-baseline --no-full-fetch --no-others > /dev/null
 bash tools/pmc_collect.sh r06_pmc_vorbis_walk_kernel vorbis_walk_kernel bench.py --config c3 --steps 3 --warmup 1 --no-cpu-baseline --no-full-fetch --no-others > /dev/null
