@@ -71,6 +71,8 @@ ABI_SYMBOLS = [
     "afg_copy_probe_hip", "afg_lds_fill_probe_hip",
     "afg_qoa_encoded_size", "afg_qoa_encode_hip", "afg_wav_encoded_size", "afg_wav_encode", "afg_wav_encode_dithered",
     "afg_opus_output_hip",
+    "afg_mod_render_hip", "afg_mod_parse", "afg_mod_parsed_free", "afg_is_module", "afg_module_pattern_count",
+    "afg_module_length", "afg_module_rows_in_pattern", "afg_module_tell_pattern", "afg_module_tell_row", "afg_module_seek",
 ]
 
 
@@ -127,6 +129,26 @@ class OpusParsed(C.Structure):
                 ("gain", C.c_float), ("pad", C.c_int32), ("declared_frames", C.c_int64), ("pcm_frames", C.c_uint64),
                 ("n_frames", C.c_uint64), ("n_coeffs", C.c_uint64), ("frames", C.c_void_p), ("coeffs", C.c_void_p),
                 ("owner", C.c_void_p)]
+
+
+# ProTracker MOD records (afg.h)
+MOD_MAX_FRAMES = 30 * 60 * 44100
+MOD_SONG_DTYPE = np.dtype([("out_frame", np.uint64), ("tick_base", np.uint64), ("seg_base", np.uint64), ("sample_base", np.uint64),
+                           ("n_ticks", np.uint32), ("sample_bytes", np.uint32), ("reserved", np.uint64)])
+assert MOD_SONG_DTYPE.itemsize == 48
+MOD_TICK_DTYPE = np.dtype([("frame", np.uint32), ("frames", np.uint32), ("seg", np.uint32), ("n_seg", np.uint32),
+                           ("pattern", np.int16), ("line", np.int16), ("pad", np.uint32)])
+assert MOD_TICK_DTYPE.itemsize == 24
+MOD_SEGMENT_DTYPE = np.dtype([("frame", np.uint32), ("frames", np.uint32), ("position", np.float32), ("increment", np.float32),
+                              ("level_l", np.float32), ("level_r", np.float32), ("sample_off", np.uint32), ("loop_start", np.int32),
+                              ("loop_length", np.int32), ("loop_end", np.int32), ("length", np.int32), ("channel", np.uint32)])
+assert MOD_SEGMENT_DTYPE.itemsize == 48
+
+
+class ModParsed(C.Structure):
+    _fields_ = [("channels", C.c_uint32), ("capped", C.c_uint32), ("n_frames", C.c_uint64), ("n_ticks", C.c_uint64),
+                ("n_segments", C.c_uint64), ("n_sample_bytes", C.c_uint64), ("ticks", C.c_void_p), ("segments", C.c_void_p),
+                ("sample_bytes", C.c_void_p), ("owner", C.c_void_p)]
 
 
 class BatchItem(C.Structure):
@@ -289,6 +311,14 @@ def lib():
     L.afg_copy_probe_hip.argtypes = [vp, vp, C.c_size_t, vp]
     L.afg_lds_fill_probe_hip.argtypes = [C.c_uint32, vp]
     L.afg_dev_option.argtypes = [C.c_char_p, C.c_int]
+    L.afg_mod_render_hip.argtypes = [u32, vp, vp, vp, vp, vp, vp]
+    L.afg_mod_parse.argtypes = [vp, C.c_size_t, C.POINTER(ModParsed)]
+    L.afg_mod_parsed_free.argtypes = [C.POINTER(ModParsed)]
+    L.afg_mod_parsed_free.restype = None
+    for fn in (L.afg_is_module, L.afg_module_pattern_count, L.afg_module_length, L.afg_module_tell_pattern, L.afg_module_tell_row):
+        fn.argtypes = [vp]
+    L.afg_module_rows_in_pattern.argtypes = [vp, C.c_int]
+    L.afg_module_seek.argtypes = [vp, C.c_int, C.c_int]
     _lib = L
     _sync_dev_options(L)
     return L
@@ -673,6 +703,52 @@ def qoa_parse(file_bytes):
     return frames, ch.value, sr.value, smp.value
 
 
+def mod_parse(file_bytes):
+    """Host front-end only (afg_mod_parse): the batch path's control layer for one MOD file.  Returns a dict: channels,
+    capped, frames, ticks (MOD_TICK_DTYPE), segments (MOD_SEGMENT_DTYPE), plane (uint8 sample area + padding).  Needs no
+    device."""
+    buf = bytes(file_bytes)
+    out = ModParsed()
+    check(lib().afg_mod_parse(buf, len(buf), C.byref(out)))
+    try:
+        def view(ptr, count, dtype):
+            if not count:
+                return np.zeros(0, dtype)
+            raw = (C.c_uint8 * (count * np.dtype(dtype).itemsize)).from_address(ptr)
+            return np.frombuffer(raw, dtype=dtype, count=count).copy()
+        return {"channels": int(out.channels), "capped": bool(out.capped), "frames": int(out.n_frames),
+                "ticks": view(out.ticks, int(out.n_ticks), MOD_TICK_DTYPE),
+                "segments": view(out.segments, int(out.n_segments), MOD_SEGMENT_DTYPE),
+                "plane": view(out.sample_bytes, int(out.n_sample_bytes), np.uint8)}
+    finally:
+        lib().afg_mod_parsed_free(C.byref(out))
+
+
+def mod_render(n_songs, d_songs, d_segments, d_ticks, d_sample_bytes, d_out, stream=None):
+    """Enqueue the MOD mixer (afg_mod_render_hip) on device arrays."""
+    check(lib().afg_mod_render_hip(int(n_songs), _ptr(d_songs), _ptr(d_segments), _ptr(d_ticks), _ptr(d_sample_bytes),
+                                   _ptr(d_out), _stream(stream)))
+
+
+def mod_layout(parsed_songs):
+    """Concatenate afg_mod_parse results (dicts of mod_parse) into one launch: (songs, ticks, segments, plane, total
+    frames) as numpy arrays, songs back to back in the output."""
+    songs = np.zeros(len(parsed_songs), MOD_SONG_DTYPE)
+    frames = ticks = segs = plane = 0
+    for i, p in enumerate(parsed_songs):
+        songs[i] = (frames, ticks, segs, plane, len(p["ticks"]), len(p["plane"]), 0)
+        frames += p["frames"]
+        ticks += len(p["ticks"])
+        segs += len(p["segments"])
+        plane += (len(p["plane"]) + 15) & ~15
+    plane_arr = np.zeros(max(plane, 16), np.uint8)
+    for i, p in enumerate(parsed_songs):
+        plane_arr[int(songs[i]["sample_base"]):int(songs[i]["sample_base"]) + len(p["plane"])] = p["plane"]
+    tick_arr = np.concatenate([p["ticks"] for p in parsed_songs]) if parsed_songs else np.zeros(0, MOD_TICK_DTYPE)
+    seg_arr = np.concatenate([p["segments"] for p in parsed_songs] + [np.zeros(1, MOD_SEGMENT_DTYPE)])
+    return songs, tick_arr, seg_arr, plane_arr, frames
+
+
 class AudioStream:
     """The reading half of the reference's AudioStream (stream.d:102-637) over afg_open_from_memory: same method
     names, same never-throw / error-state contract (stream.d:31-33)."""
@@ -715,11 +791,36 @@ class AudioStream:
     def canSeek(self):
         return bool(lib().afg_can_seek(self._h))
 
-    def seekPosition(self, frame):
+    def seekPosition(self, frame, row=None):
+        """seekPosition(frame), or on a module seekPosition(pattern, row) (stream.d:1059)."""
+        if row is not None:
+            return self.seekModulePosition(frame, row)
         return bool(lib().afg_seek_position(self._h, int(frame)))
 
     def tellPosition(self):
         return int(lib().afg_tell_position(self._h))
+
+    # the module functions (stream.d:330-345, :906-1080); seekPosition(pattern, row) is the module form of seekPosition
+    def isModule(self):
+        return bool(lib().afg_is_module(self._h))
+
+    def countModulePatterns(self):
+        return int(lib().afg_module_pattern_count(self._h))
+
+    def getModuleLength(self):
+        return int(lib().afg_module_length(self._h))
+
+    def rowsInPattern(self, pattern):
+        return int(lib().afg_module_rows_in_pattern(self._h, int(pattern)))
+
+    def tellModulePattern(self):
+        return int(lib().afg_module_tell_pattern(self._h))
+
+    def tellModuleRow(self):
+        return int(lib().afg_module_tell_row(self._h))
+
+    def seekModulePosition(self, pattern, row):
+        return bool(lib().afg_module_seek(self._h, int(pattern), int(row)))
 
     def readSamplesFloat(self, out):
         """out: float32 numpy array whose size is a multiple of the channel count; returns frames read."""

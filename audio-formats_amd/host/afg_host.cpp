@@ -11,6 +11,7 @@
 // samples on the device, serve interleaved floats.
 #include "../csrc/afg_common.h"
 #include "afg_flac_front.h"
+#include "afg_mod_front.h"
 #include "afg_mp3_front.h"
 #include "afg_opus_front.h"
 #include "afg_vorbis_front.h"
@@ -115,7 +116,11 @@ public:
     void give_back(void *p, size_t cap)
     {
         int dev = 0;
-        const bool known = hipGetDevice(&dev) == hipSuccess;
+        give_back_on(hipGetDevice(&dev) == hipSuccess ? dev : -1, p, cap);
+    }
+    void give_back_on(int dev, void *p, size_t cap)      // dev: the device the buffer was taken on (-1: unknown)
+    {
+        const bool known = dev >= 0;
         {
             std::lock_guard<std::mutex> lk(mu_);
             if (known && free_.size() < 128 && held_ + cap <= ((size_t)64 << 30)) {
@@ -145,6 +150,9 @@ private:
     size_t held_ = 0;
 };
 DevicePool g_devpool;
+}  // namespace
+
+namespace {
 
 struct DeviceBuf {
     void *p = nullptr;
@@ -303,6 +311,25 @@ private:
     std::vector<Pair> free_;
 };
 StreamPool g_streams;
+}  // namespace
+
+// the pools as the MOD stage (afg_mod_stage.cpp) uses them
+namespace afg_front {
+int devpool_take(size_t bytes, void **out, size_t *cap_out) { return g_devpool.take(bytes, out, cap_out); }
+void devpool_give(void *p, size_t cap, int dev) { g_devpool.give_back_on(dev, p, cap); }
+// a page-locked staging lease; the buffer goes back to the pool when the last owner lets go
+std::shared_ptr<void> staging_lease(size_t bytes, void **p)
+{
+    auto lease = std::make_shared<StagingPool::Lease>();
+    if (g_staging.take(bytes, *lease)) return nullptr;
+    *p = lease->p;
+    return lease;
+}
+hipError_t streams_take(hipStream_t *up, hipStream_t *down) { return g_streams.take(up, down); }
+void streams_give(hipStream_t up, hipStream_t down) { g_streams.give(up, down); }
+}  // namespace afg_front
+
+namespace {
 
 // AFG_TRACE=1: wall-clock of the host stages on stderr (development aid)
 struct StageTimer {
@@ -408,6 +435,7 @@ struct BatchOut {
     StagingPool::Lease mp3_plane;       // batch path: the MP3 PCM in staging layout, served in place
     StagingPool::Lease opus_plane;      // batch path: the Opus PCM, files back to back
     std::unique_ptr<BatchOut> early;    // batch path: the FLAC / QOA files, decoded on a second host thread meanwhile
+    std::shared_ptr<void> mod_plane;    // batch path: the MOD files' PCM (afg_mod_stage.cpp)
 };
 
 // Device stage for a set of parsed files: every FLAC record of the batch in one launch, every QOA frame
@@ -1329,6 +1357,7 @@ struct afg_stream {
     std::unique_ptr<afg_mp3::Reader> mp3;
     std::unique_ptr<afg_vorbis::Reader> ogg;
     std::unique_ptr<afg_opus::Reader> opus;
+    std::unique_ptr<afg_mod::StreamMix> mod;
     Mp3Carry carry;
     OpusCarry opus_carry;
     int opus_gain_i = 0;
@@ -1504,6 +1533,11 @@ afg_stream *afg_open_from_memory(const uint8_t *data, size_t length)
             s->channels = m3.channels;
             s->samplerate = (float)m3.hz;
             s->declared_frames = (int64_t)(m3.declared_samples / (uint64_t)std::max(1, m3.channels));   // stream.d:1737
+        } else if ((s->mod.reset(new afg_mod::StreamMix), afg_mod::probe(d, length, &s->mod->song))) {   // tried last (stream.d:1796-1830)
+            s->format = AFG_FORMAT_MOD;
+            s->channels = 2;
+            s->samplerate = 44100.0f;
+            s->declared_frames = AFG_UNKNOWN_LENGTH;
         } else {
             s->error = kErrorUnknownFormat;
             return s;
@@ -1535,6 +1569,12 @@ int afg_read_samples_float(afg_stream *s, float *out, int frames)
     // declares 0 samples therefore reads nothing); the check is made on entry only, like the reference's.
     if (s->format == AFG_FORMAT_FLAC && s->position == s->declared_frames) return 0;
     try {
+        if (s->format == AFG_FORMAT_MOD) {
+            const int n = s->mod->read(out, frames);
+            if (n < 0) { s->error = kErrorDecodingError; return 0; }
+            s->position += n;
+            return n;
+        }
         const size_t C = (size_t)std::max(1, s->channels);
         int done = 0;
         while (done < frames) {
@@ -1559,6 +1599,7 @@ int afg_can_seek(const afg_stream *s) { return s && !s->error; }
 int afg_seek_position(afg_stream *s, int frame)
 {
     if (!s || s->error) return 0;
+    if (s->format == AFG_FORMAT_MOD) return 0;          // a module seeks by pattern and row (afg_module_seek; stream.d:1097)
     // the reference bounds a seek by the declared length (stream.d:1104, :1113, :1137); what can actually be reached is
     // bounded by what decodes.  Backwards: the readers start over; forwards: chunks are decoded and dropped (a chunk
     // is ~1.5 s of audio and takes about a millisecond on the device).
@@ -1594,6 +1635,21 @@ int afg_seek_position(afg_stream *s, int frame)
 int afg_tell_position(const afg_stream *s) { return (s && !s->error) ? (int)s->position : -1; }
 
 void afg_close(afg_stream *s) { delete s; }
+
+// the module functions of AudioStream (stream.d:330-345, :906-1080)
+static const afg_mod::Song *module_of(const afg_stream *s) { return (s && !s->error && s->mod) ? &s->mod->song : nullptr; }
+int afg_is_module(const afg_stream *s) { return module_of(s) ? 1 : 0; }
+int afg_module_pattern_count(const afg_stream *s) { const afg_mod::Song *m = module_of(s); return m ? m->num_patterns() : -1; }
+int afg_module_length(const afg_stream *s) { const afg_mod::Song *m = module_of(s); return m ? m->length() : -1; }
+int afg_module_rows_in_pattern(const afg_stream *s, int) { return module_of(s) ? 64 : -1; }   // stream.d:971-975
+int afg_module_tell_pattern(const afg_stream *s) { const afg_mod::Song *m = module_of(s); return m ? m->pattern() : -1; }
+int afg_module_tell_row(const afg_stream *s) { const afg_mod::Song *m = module_of(s); return m ? m->line() : -1; }
+int afg_module_seek(afg_stream *s, int pattern, int row)
+{
+    if (!module_of(s)) return 0;
+    s->mod->song.seek(pattern, row, 0);                 // stream.d:1075
+    return 1;
+}
 
 namespace {
 struct FlacParsedOwner {
@@ -2370,6 +2426,13 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
                                  : d.in_opus_plane ? (const float *)owner->opus_plane.p : (const float *)src->plane.p;
             items[i].pcm = (d.status == AFG_OK && d.frames > 0) ? (float *)plane + d.pcm_off : nullptr;
         }
+        // MOD is probed last (stream.d:1796): files no other front-end took go to its stage
+        std::vector<int> unknown;
+        for (int i = 0; i < n_files; i++)
+            if (items[i].status == AFG_ERR_UNSUPPORTED && items[i].message == kErrorUnknownFormat) unknown.push_back(i);
+        if (int mrc = afg_mod::batch_stage(data, length, unknown, [&](size_t n, const std::function<void(size_t)> &fn) { parallel_for(n, nt, fn); },
+                                           items, owner->mod_plane)) return mrc;
+        tm.lap("mod stage");
         keep = std::move(guard);
         tm.lap("items filled");
         return AFG_OK;

@@ -1,0 +1,265 @@
+// afg_mod_stage.cpp -- the device side of MOD decoding: a stream's reads and the batch path's MOD stage.
+//
+// Both hand the mixer (csrc/mod_mix.hip) what the control layer (afg_mod_front.cpp) wrote down: the file's sample area,
+// per song one afg_mod_song, and its ticks and segments.  Records are small next to the output (a 4-channel tick of
+// 882 frames is 24 + 4 x 48 bytes against 7 KB of PCM), so the transfers that matter are the PCM coming back.
+#include "afg_mod_front.h"
+#include "../csrc/afg_common.h"
+
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <new>
+
+namespace afg_front {
+// the library's device-memory pool (afg_host.cpp)
+int devpool_take(size_t bytes, void **out, size_t *cap_out);
+void devpool_give(void *p, size_t cap, int dev);
+// page-locked staging (afg_host.cpp's pool: pinning memory costs about as much as moving it) and the kept stream pair
+std::shared_ptr<void> staging_lease(size_t bytes, void **p);
+hipError_t streams_take(hipStream_t *up, hipStream_t *down);
+void streams_give(hipStream_t up, hipStream_t down);
+}  // namespace afg_front
+
+namespace afg_mod {
+
+const char *const kMessageCapped = "MOD: the song does not end; cut at AFG_MOD_MAX_FRAMES (30 minutes)";
+
+int DevBuf::alloc(size_t bytes)
+{
+    int cur = 0;
+    if (hipGetDevice(&cur) != hipSuccess) cur = 0;
+    if (p && cap >= bytes && dev == cur) return AFG_OK;
+    release();
+    if (int rc = afg_front::devpool_take(bytes, &p, &cap)) { p = nullptr; cap = 0; return rc; }
+    dev = cur;
+    return AFG_OK;
+}
+
+void DevBuf::release()
+{
+    if (p) afg_front::devpool_give(p, cap, dev);
+    p = nullptr; cap = 0; dev = -1;
+}
+
+namespace {
+
+size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// Records of one launch in one buffer: songs, then ticks, then segments (each 16-byte aligned)
+struct RecLayout {
+    size_t songs = 0, ticks = 0, segs = 0, bytes = 0;
+    RecLayout(size_t n_songs, size_t n_ticks, size_t n_segs)
+    {
+        songs = 0;
+        ticks = align16(n_songs * sizeof(afg_mod_song));
+        segs = ticks + align16(n_ticks * sizeof(afg_mod_tick));
+        bytes = segs + align16(std::max<size_t>(n_segs, 1) * sizeof(afg_mod_segment));
+    }
+};
+
+}  // namespace
+
+StreamMix::~StreamMix()
+{
+    if (stream_) {
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        if (cur != stream_dev_) (void)hipSetDevice(stream_dev_);
+        (void)hipStreamDestroy(stream_);
+        if (cur != stream_dev_ && cur >= 0) (void)hipSetDevice(cur);
+    }
+}
+
+int StreamMix::read(float *out, int frames)
+{
+    if (frames <= 0 || song.loop_count() >= 1) return 0;           // stream.d:614: the song has ended
+    ticks_.clear();
+    segs_.clear();
+    const int n = song.render(frames, 0, 0, ticks_, segs_);
+    if (n <= 0) return 0;
+    int dev = 0;
+    AFG_HIP_CHECK(hipGetDevice(&dev));
+    if (stream_ && stream_dev_ != dev) {
+        // the caller changed devices between reads: the buffers follow, the plane is uploaded again
+        (void)hipSetDevice(stream_dev_);
+        (void)hipStreamDestroy(stream_);
+        (void)hipSetDevice(dev);
+        stream_ = nullptr;
+        uploaded_ = false;
+    }
+    if (!stream_) {
+        AFG_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+        stream_dev_ = dev;
+    }
+    const std::vector<uint8_t> &plane = song.plane();
+    if (!uploaded_ || plane_.dev != dev) {
+        if (plane_.alloc(plane.size())) return -1;
+        AFG_HIP_CHECK(hipMemcpyAsync(plane_.p, plane.data(), plane.size(), hipMemcpyHostToDevice, stream_));
+        uploaded_ = true;
+    }
+    const RecLayout L(1, ticks_.size(), segs_.size());
+    staging_.assign(L.bytes, 0);
+    afg_mod_song sg;
+    std::memset(&sg, 0, sizeof(sg));
+    sg.n_ticks = (uint32_t)ticks_.size();
+    sg.sample_bytes = (uint32_t)plane.size();
+    std::memcpy(staging_.data() + L.songs, &sg, sizeof(sg));
+    std::memcpy(staging_.data() + L.ticks, ticks_.data(), ticks_.size() * sizeof(afg_mod_tick));
+    if (!segs_.empty()) std::memcpy(staging_.data() + L.segs, segs_.data(), segs_.size() * sizeof(afg_mod_segment));
+    const size_t out_bytes = (size_t)n * 2 * sizeof(float);
+    if (recs_.alloc(L.bytes) || out_.alloc(out_bytes)) return -1;
+    AFG_HIP_CHECK(hipMemcpyAsync(recs_.p, staging_.data(), L.bytes, hipMemcpyHostToDevice, stream_));
+    uint8_t *r = (uint8_t *)recs_.p;
+    if (afg_mod_render_hip(1, (const afg_mod_song *)(r + L.songs), (const afg_mod_segment *)(r + L.segs),
+                           (const afg_mod_tick *)(r + L.ticks), (const uint8_t *)plane_.p, (float *)out_.p, stream_))
+        return -1;
+    float *dst = out;
+    if (!dst) { bounce_.resize((size_t)n * 2); dst = bounce_.data(); }
+    AFG_HIP_CHECK(hipMemcpyAsync(dst, out_.p, out_bytes, hipMemcpyDeviceToHost, stream_));
+    AFG_HIP_CHECK(hipStreamSynchronize(stream_));
+    return n;
+}
+
+int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
+                const std::function<void(size_t, const std::function<void(size_t)> &)> &run_parallel,
+                afg_batch_item *items, std::shared_ptr<void> &keep)
+{
+    if (which.empty()) return AFG_OK;
+    // ---- the control layer, one file per helper-thread job ----
+    // (the records go to per-file vectors first: their sizes are known only once a song has played, and they are small next
+    // to the PCM -- a 4-channel tick is 24 + 4 x 48 bytes against 7 KB of output; the helper threads then gather them)
+    struct Sim {
+        bool ok = false, capped = false;
+        uint64_t frames = 0;
+        Song song;                                      // holds the sample plane
+        std::vector<afg_mod_tick> ticks;
+        std::vector<afg_mod_segment> segs;
+    };
+    std::vector<Sim> sims(which.size());
+    std::atomic<bool> oom{ false };
+    run_parallel(which.size(), [&](size_t k) {
+        const int i = which[k];
+        try {
+            Sim &s = sims[k];
+            if (!data[i] || !probe(data[i], length[i], &s.song)) return;
+            s.frames = render_song(s.song, s.ticks, s.segs, &s.capped);
+            s.ok = true;
+        } catch (...) {
+            oom = true;
+        }
+    });
+    if (oom) { afg::set_error("MOD stage: out of host memory"); return AFG_ERR_OOM; }
+    std::vector<size_t> mods;
+    for (size_t k = 0; k < sims.size(); k++) if (sims[k].ok) mods.push_back(k);
+    if (mods.empty()) return AFG_OK;
+
+    // ---- layout: per song its output frame, ticks, segments and plane bytes in the batch ----
+    const size_t M = mods.size();
+    std::vector<afg_mod_song> songs(M);
+    uint64_t frames = 0, n_ticks = 0, n_segs = 0, plane_bytes = 0;
+    for (size_t j = 0; j < M; j++) {
+        const Sim &s = sims[mods[j]];
+        afg_mod_song &g = songs[j];
+        std::memset(&g, 0, sizeof(g));
+        g.out_frame = frames; g.tick_base = n_ticks; g.seg_base = n_segs; g.sample_base = plane_bytes;
+        g.n_ticks = (uint32_t)s.ticks.size();
+        g.sample_bytes = (uint32_t)s.song.plane().size();
+        frames += s.frames; n_ticks += s.ticks.size(); n_segs += s.segs.size(); plane_bytes += align16(s.song.plane().size());
+    }
+    // page-locked: the PCM plane the items point into (owned by `keep`), and the inputs staged for one upload
+    void *pcm = nullptr, *in = nullptr;
+    const size_t pcm_bytes = std::max<uint64_t>(frames, 1) * 2 * sizeof(float);
+    const size_t tick_bytes = align16(n_ticks * sizeof(afg_mod_tick)), seg_bytes = align16(std::max<uint64_t>(n_segs, 1) * sizeof(afg_mod_segment));
+    const size_t in_bytes = tick_bytes + seg_bytes + align16(plane_bytes);
+    std::shared_ptr<void> pcm_owner = afg_front::staging_lease(pcm_bytes, &pcm);
+    if (!pcm_owner) return AFG_ERR_OOM;
+    std::shared_ptr<void> in_owner = afg_front::staging_lease(in_bytes, &in);
+    if (!in_owner) return AFG_ERR_OOM;
+    uint8_t *hin = (uint8_t *)in;
+    run_parallel(M, [&](size_t j) {
+        const Sim &s = sims[mods[j]];
+        const afg_mod_song &g = songs[j];
+        if (!s.ticks.empty()) std::memcpy(hin + g.tick_base * sizeof(afg_mod_tick), s.ticks.data(), s.ticks.size() * sizeof(afg_mod_tick));
+        if (!s.segs.empty()) std::memcpy(hin + tick_bytes + g.seg_base * sizeof(afg_mod_segment), s.segs.data(), s.segs.size() * sizeof(afg_mod_segment));
+        std::memcpy(hin + tick_bytes + seg_bytes + g.sample_base, s.song.plane().data(), s.song.plane().size());
+    });
+
+    // ---- chunks of songs, about kChunkFrames of output each: mix chunk c+1 while chunk c comes back ----
+    constexpr uint64_t kChunkFrames = (uint64_t)16 << 20;                   // 128 MB of PCM
+    std::vector<size_t> first{ 0 };
+    for (size_t j = 0; j < M; j++) {
+        const uint64_t end = songs[j].out_frame + sims[mods[j]].frames;
+        if (j + 1 < M && end - songs[first.back()].out_frame >= kChunkFrames) first.push_back(j + 1);
+    }
+    first.push_back(M);
+    const size_t C = first.size() - 1;
+    // chunk-relative song records: output frame and tick base count from the chunk's first song
+    std::vector<afg_mod_song> rel(songs);
+    uint64_t max_chunk = 1;
+    for (size_t c = 0; c < C; c++) {
+        const afg_mod_song &f = songs[first[c]];
+        for (size_t j = first[c]; j < first[c + 1]; j++) { rel[j].out_frame -= f.out_frame; rel[j].tick_base -= f.tick_base; }
+        const size_t last = first[c + 1] - 1;
+        max_chunk = std::max<uint64_t>(max_chunk, songs[last].out_frame + sims[mods[last]].frames - f.out_frame);
+    }
+    DevBuf d_in, d_songs, d_out[2];
+    if (int rc = d_in.alloc(in_bytes)) return rc;
+    if (int rc = d_songs.alloc(M * sizeof(afg_mod_song))) return rc;
+    for (DevBuf &b : d_out) if (int rc = b.alloc(max_chunk * 2 * sizeof(float))) return rc;
+    // the kept upload / download pair, given back drained on every way out
+    struct Pair {
+        hipStream_t up = nullptr, down = nullptr;
+        ~Pair()
+        {
+            for (hipStream_t st : { up, down }) if (st) (void)hipStreamSynchronize(st);
+            if (up && down) afg_front::streams_give(up, down);
+        }
+    } pair;
+    AFG_HIP_CHECK(afg_front::streams_take(&pair.up, &pair.down));
+    hipStream_t up = pair.up, down = pair.down;
+    // two output buffers in turn: chunk c waits for chunk c - 2's download (events in a ring of two: a wait takes the event's
+    // state when it is queued)
+    hipEvent_t mixed[2] = { nullptr, nullptr }, fetched[2] = { nullptr, nullptr };
+    struct EventGuard { hipEvent_t *e; ~EventGuard() { for (int k = 0; k < 4; k++) if (e[k]) (void)hipEventDestroy(e[k]); } };
+    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+    EventGuard g_ev{ ev };
+    for (int k = 0; k < 4; k++) AFG_HIP_CHECK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+    mixed[0] = ev[0]; mixed[1] = ev[1]; fetched[0] = ev[2]; fetched[1] = ev[3];
+    AFG_HIP_CHECK(hipMemcpyAsync(d_in.p, in, in_bytes, hipMemcpyHostToDevice, up));
+    AFG_HIP_CHECK(hipMemcpyAsync(d_songs.p, rel.data(), M * sizeof(afg_mod_song), hipMemcpyHostToDevice, up));
+    const uint8_t *din = (const uint8_t *)d_in.p;
+    for (size_t c = 0; c < C; c++) {
+        const afg_mod_song &f = songs[first[c]];
+        const size_t last = first[c + 1] - 1;
+        const uint64_t chunk_frames = songs[last].out_frame + sims[mods[last]].frames - f.out_frame;
+        DevBuf &o = d_out[c & 1];
+        if (c >= 2) AFG_HIP_CHECK(hipStreamWaitEvent(up, fetched[c & 1], 0));  // its buffer has come back (chunk c - 2)
+        if (int rc = afg_mod_render_hip((uint32_t)(first[c + 1] - first[c]), (const afg_mod_song *)d_songs.p + first[c],
+                                        (const afg_mod_segment *)(din + tick_bytes),
+                                        (const afg_mod_tick *)din + f.tick_base, din + tick_bytes + seg_bytes, (float *)o.p, up))
+            return rc;
+        AFG_HIP_CHECK(hipEventRecord(mixed[c & 1], up));
+        AFG_HIP_CHECK(hipStreamWaitEvent(down, mixed[c & 1], 0));
+        if (chunk_frames)
+            AFG_HIP_CHECK(hipMemcpyAsync((float *)pcm + 2 * f.out_frame, o.p, chunk_frames * 2 * sizeof(float), hipMemcpyDeviceToHost, down));
+        AFG_HIP_CHECK(hipEventRecord(fetched[c & 1], down));
+    }
+    AFG_HIP_CHECK(hipStreamSynchronize(down));
+    AFG_HIP_CHECK(hipStreamSynchronize(up));
+    for (size_t j = 0; j < M; j++) {
+        const Sim &s = sims[mods[j]];
+        afg_batch_item &it = items[which[mods[j]]];
+        it.status = AFG_OK;
+        it.message = s.capped ? kMessageCapped : nullptr;
+        it.format = AFG_FORMAT_MOD;
+        it.channels = 2;
+        it.samplerate = (float)kRate;
+        it.frames = (int64_t)s.frames;
+        it.pcm = s.frames ? (float *)pcm + 2 * songs[j].out_frame : nullptr;
+    }
+    keep = pcm_owner;
+    return AFG_OK;
+}
+
+}  // namespace afg_mod

@@ -322,6 +322,39 @@ int afg_mp3_parse_q(const(ubyte)* data, size_t length, afg_mp3_parsed_q* parsed)
 void afg_mp3_parsed_q_free(afg_mp3_parsed_q* parsed);
 void afg_mp3_qtables(ubyte* band_of_line /* [24][576] */, ushort* dst_of_src /* [24][576] */, float* pow43 /* [145] */);
 int afg_lds_fill_probe_hip(uint word, void* hip_stream);   // test aid: fills the LDS of every CU with `word`
+
+// ProTracker MOD (afg.h): records of the device mixer, the host front-end, the module functions of AudioStream
+enum AFG_MOD_MAX_FRAMES = 30 * 60 * 44100;
+struct afg_mod_song { ulong out_frame, tick_base, seg_base, sample_base; uint n_ticks, sample_bytes; ulong reserved; }
+struct afg_mod_tick { uint frame, frames, seg, n_seg; short pattern, line; uint pad; }
+struct afg_mod_segment
+{
+    uint frame, frames;
+    float position, increment, level_l, level_r;
+    uint sample_off;
+    int loop_start, loop_length, loop_end, length;
+    uint channel;
+}
+struct afg_mod_parsed
+{
+    uint channels, capped;
+    ulong n_frames, n_ticks, n_segments, n_sample_bytes;
+    afg_mod_tick* ticks;
+    afg_mod_segment* segments;
+    ubyte* sample_bytes;
+    void* owner;
+}
+int afg_mod_render_hip(uint n_songs, const(afg_mod_song)* d_songs, const(afg_mod_segment)* d_segments,
+                       const(afg_mod_tick)* d_ticks, const(ubyte)* d_sample_bytes, float* d_out, void* hip_stream);
+int afg_mod_parse(const(ubyte)* data, size_t length, afg_mod_parsed* parsed);
+void afg_mod_parsed_free(afg_mod_parsed* parsed);
+int afg_is_module(const(afg_stream)* s);
+int afg_module_pattern_count(const(afg_stream)* s);
+int afg_module_length(const(afg_stream)* s);
+int afg_module_rows_in_pattern(const(afg_stream)* s, int pattern);
+int afg_module_tell_pattern(const(afg_stream)* s);
+int afg_module_tell_row(const(afg_stream)* s);
+int afg_module_seek(afg_stream* s, int pattern, int row);
 int afg_celt_transform_streams_hip(uint n_chan, const(ulong)* d_rec_base, const(afg_celt_frame)* d_recs, const(float)* d_coeffs,
                                    float* d_out, float* d_states, void* hip_stream, void* hip_tail_stream);
 alias afg_rand_fn = extern(C) int function(void* user) nothrow @nogc;
@@ -362,6 +395,13 @@ nothrow @nogc:
     bool canSeek() { return afg_can_seek(_h) != 0; }
     bool seekPosition(int frame) { return afg_seek_position(_h, frame) != 0; }
     int tellPosition() { return afg_tell_position(_h); }
+    bool isModule() { return afg_is_module(_h) != 0; }
+    int countModulePatterns() { return afg_module_pattern_count(_h); }
+    int getModuleLength() { return afg_module_length(_h); }
+    int rowsInPattern(int pattern) { return afg_module_rows_in_pattern(_h, pattern); }
+    int tellModulePattern() { return afg_module_tell_pattern(_h); }
+    int tellModuleRow() { return afg_module_tell_row(_h); }
+    bool seekPosition(int pattern, int row) { return afg_module_seek(_h, pattern, row) != 0; }
     int readSamplesFloat(float* outData, int frames) { return afg_read_samples_float(_h, outData, frames); }
     int readSamplesFloat(float[] outData)
     {

@@ -371,10 +371,14 @@ int afg_opus_output_gain_hip(uint64_t n_samples, const float *d_in, float gain, 
  *  Outer surface: the AudioStream subset (stream.d:102-637) over the host front-ends
  *  -- FLAC (native container, drflac.d:680-1695, :1887-2153), QOA (qoa.d:413-486, :703-851), MP3 Layer I / II / III
  *  (minimp3.d, minimp3_ex.d), Ogg Vorbis (stb_vorbis2.d) and Ogg Opus with CELT-only packets (dopus.d; a file that holds
- *  SILK / hybrid packets is refused at open with this library's own message).  WAV, MOD and XM report "unrecognized
- *  encoding".  Like the reference the stream decodes as the caller pulls: afg_open_from_memory parses the container only,
- *  a read that finds the FIFO empty decodes the next chunk (64 MP3 frames / Vorbis or Opus packets, 16 FLAC or QOA frames)
- *  on the device; afg_batch_decode parses whole files into transform-stage records and decodes them in one pass.
+ *  SILK / hybrid packets is refused at open with this library's own message) and ProTracker MOD (pocketmod.d: below).
+ *  WAV and XM report "unrecognized encoding".  Like the reference the stream decodes as the caller pulls:
+ *  afg_open_from_memory parses the container only, a read that finds the FIFO empty decodes the next chunk (64 MP3 frames /
+ *  Vorbis or Opus packets, 16 FLAC or QOA frames) on the device; afg_batch_decode parses whole files into transform-stage
+ *  records and decodes them in one pass.  A MOD stream has no FIFO: each read runs the module's control layer on the host
+ *  up to the read's end and mixes exactly those frames on the device (pocketmod_render(..., frames * 8), stream.d:611-620),
+ *  so a read stops early at every pattern boundary, as the reference's does, and the first read after the song has come
+ *  back to an order index it already played returns 0.
  * ========================================================================== */
 
 typedef enum afg_format {          /* AudioFileFormat, stream.d:36-47 */
@@ -621,6 +625,81 @@ uint64_t afg_wav_encode(const float *samples, uint64_t frames, uint32_t channels
 typedef int (*afg_rand_fn)(void *user);        /* a draw in [0, rng_max] */
 uint64_t afg_wav_encode_dithered(const float *samples, uint64_t frames, uint32_t channels, uint32_t samplerate, int format,
                                  afg_rand_fn rng, void *rng_user, uint32_t rng_max, uint8_t *out, uint64_t cap);
+
+/* ========================================================================== *
+ *  ProTracker MOD (pocketmod.d; stream.d:1796-1830): 2 channels at 44100 Hz, length AFG_UNKNOWN_LENGTH, one numeric mode
+ *  (both AFG_NUMERIC settings give the same bits).  The control layer -- pattern lines, effects, LFOs, tempo, once per tick
+ *  (pocketmod.d:354-662) -- runs on the host and describes the mix as segment records: a run of output frames over which
+ *  one channel steps through one sample with a fixed increment (one pass of the loop at pocketmod.d:684-720).  The device
+ *  mixer (afg_mod_render_hip) resamples, scales and adds them in channel order, bit-identical to pocketmod_render.
+ *  Probe: MOD is tried last, after every other format; files that begin like a RIFF/WAVE file or pass the XM header check
+ *  (libxm.d:360-380) are left to those formats and stay refused.
+ *  The batch path's output (afg_batch_decode, afg_mod_parse) is the reference's read loop with requests as long as the
+ *  frames left below AFG_MOD_MAX_FRAMES: every read runs to its pattern boundary, so reads cut the mix at tick boundaries
+ *  only; the loop ends at the first read after the song returns to a visited order index (stream.d:614).  A song that never
+ *  does is cut at AFG_MOD_MAX_FRAMES (30 minutes): the item is AFG_OK, with frames == AFG_MOD_MAX_FRAMES and a message.
+ * ========================================================================== */
+#define AFG_MOD_MAX_FRAMES (30 * 60 * 44100)
+
+typedef struct afg_mod_song {      /* one song of a launch (48 bytes) */
+    uint64_t out_frame;            /* first stereo frame of the song in d_out */
+    uint64_t tick_base;            /* first afg_mod_tick of the song */
+    uint64_t seg_base;             /* first afg_mod_segment of the song */
+    uint64_t sample_base;          /* first byte of the song's sample plane in d_sample_bytes */
+    uint32_t n_ticks;
+    uint32_t sample_bytes;         /* bytes of the plane (sample area of the file, then zero padding) */
+    uint64_t reserved;             /* 0 */
+} afg_mod_song;
+
+typedef struct afg_mod_tick {      /* a run of output frames mixed with one set of channel states (24 bytes) */
+    uint32_t frame, frames;        /* first output frame (relative to the song) and count */
+    uint32_t seg, n_seg;           /* its segments: song seg_base + seg ..., channels in index order */
+    int16_t pattern, line;         /* song position when the run was mixed */
+    uint32_t pad;
+} afg_mod_tick;
+
+typedef struct afg_mod_segment {   /* one channel stepping through one sample (48 bytes) */
+    uint32_t frame, frames;        /* output frames (relative to the song) */
+    float position, increment;     /* position at `frame`; position += increment per frame */
+    float level_l, level_r;        /* output += level * data[(int)position] */
+    uint32_t sample_off;           /* byte offset of the sample in the song's plane */
+    int32_t loop_start, loop_length, loop_end, length;
+    uint32_t channel;
+} afg_mod_segment;
+
+/* Mixes every tick of n_songs songs into d_out (interleaved float pairs): each frame of a tick starts at +0.0f and takes
+ * level_l * s, level_r * s of every segment that covers it, segments in record order.  s = (float)(int8)byte at
+ * sample_off + (int)position of the song's plane; an index outside [0, sample_bytes) reads 0.  Positions are
+ * position + increment added sequentially (exactly: mod_chain.h), as pocketmod.d:691-705 does.  Songs, ticks and segments
+ * are device arrays; the songs' ticks follow one another in song order (tick_base ascending), and the ticks of a song cover
+ * its frames once.  d_out is 16-byte aligned. */
+int afg_mod_render_hip(uint32_t n_songs, const afg_mod_song *d_songs, const afg_mod_segment *d_segments,
+                       const afg_mod_tick *d_ticks, const uint8_t *d_sample_bytes, float *d_out, void *hip_stream);
+
+/* Host front-end on its own (no device needed): the batch path's control layer for one file (definition above). */
+typedef struct afg_mod_parsed {
+    uint32_t channels;             /* the module's channels (1..32) */
+    uint32_t capped;               /* 1: cut at AFG_MOD_MAX_FRAMES */
+    uint64_t n_frames, n_ticks, n_segments, n_sample_bytes;
+    afg_mod_tick *ticks;           /* song-relative: seg indexes into segments */
+    afg_mod_segment *segments;
+    uint8_t *sample_bytes;         /* the plane the segments' sample_off point into */
+    void *owner;                   /* internal */
+} afg_mod_parsed;
+int  afg_mod_parse(const uint8_t *data, size_t length, afg_mod_parsed *out);    /* AFG_ERR_UNSUPPORTED: not a MOD */
+void afg_mod_parsed_free(afg_mod_parsed *p);
+
+/* The module half of AudioStream (stream.d:330-345, :906-1080) for a MOD stream; 0 / -1 on any other stream.
+ * afg_can_seek is 1 for a MOD (stream.d:366); afg_seek_position(frame) refuses it (the reference asserts, stream.d:1097).
+ * afg_module_seek is pocketmod_seek (pocketmod.d:954-962) as written: it sets the order index and line, tick 0, and
+ * checks nothing. */
+int afg_is_module(const afg_stream *s);
+int afg_module_pattern_count(const afg_stream *s);           /* countModulePatterns: num_patterns */
+int afg_module_length(const afg_stream *s);                  /* getModuleLength: patterns in the order */
+int afg_module_rows_in_pattern(const afg_stream *s, int pattern);   /* 64 */
+int afg_module_tell_pattern(const afg_stream *s);
+int afg_module_tell_row(const afg_stream *s);
+int afg_module_seek(afg_stream *s, int pattern, int row);    /* 1 = done */
 
 /* Streaming device-to-device copy (16-byte aligned) used by bench.py to measure the copy rate this device
  * actually sustains, the practical ceiling the HBM-bound kernels are compared with next to the 8 TB/s spec. */
