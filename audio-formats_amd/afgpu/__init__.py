@@ -73,6 +73,7 @@ ABI_SYMBOLS = [
     "afg_opus_output_hip",
     "afg_mod_render_hip", "afg_mod_parse", "afg_mod_parsed_free", "afg_is_module", "afg_module_pattern_count",
     "afg_module_length", "afg_module_rows_in_pattern", "afg_module_tell_pattern", "afg_module_tell_row", "afg_module_seek",
+    "afg_xm_render_hip", "afg_xm_parse", "afg_xm_parsed_free",
 ]
 
 
@@ -143,6 +144,27 @@ MOD_SEGMENT_DTYPE = np.dtype([("frame", np.uint32), ("frames", np.uint32), ("pos
                               ("level_l", np.float32), ("level_r", np.float32), ("sample_off", np.uint32), ("loop_start", np.int32),
                               ("loop_length", np.int32), ("loop_end", np.int32), ("length", np.int32), ("channel", np.uint32)])
 assert MOD_SEGMENT_DTYPE.itemsize == 48
+
+
+XM_SONG_DTYPE = np.dtype([("out_frame", np.uint64), ("tick_base", np.uint64), ("seg_base", np.uint64), ("sample_base", np.uint64),
+                          ("aux_base", np.uint64), ("n_ticks", np.uint32), ("sample_bytes", np.uint32), ("reserved", np.uint64, (2,))])
+assert XM_SONG_DTYPE.itemsize == 64
+XM_TICK_DTYPE = np.dtype([("frame", np.uint32), ("frames", np.uint32), ("seg", np.uint32), ("n_seg", np.uint32), ("scale", np.float32),
+                          ("table_index", np.int16), ("row", np.int16), ("loop_count", np.uint32), ("pad", np.uint32)])
+assert XM_TICK_DTYPE.itemsize == 32
+XM_SEGMENT_DTYPE = np.dtype([("frame", np.uint32), ("frames", np.uint32), ("sample_off", np.uint32), ("last", np.uint32),
+                             ("flags", np.uint32), ("channel", np.uint32), ("position", np.float32), ("step", np.float32),
+                             ("vol_l", np.float32), ("vol_r", np.float32), ("aux_vol", np.uint32), ("aux_fade", np.uint32),
+                             ("aux_pos", np.uint32), ("fade_count", np.uint32), ("pad", np.uint32, (2,))])
+assert XM_SEGMENT_DTYPE.itemsize == 64
+XM_SEG_16BIT, XM_SEG_BACK, XM_SEG_TABLE, XM_SEG_RAMP, XM_SEG_FADE = 1, 2, 4, 8, 16
+
+
+class XmParsed(C.Structure):
+    _fields_ = [("channels", C.c_uint32), ("capped", C.c_uint32), ("length", C.c_uint32), ("patterns", C.c_uint32),
+                ("instruments", C.c_uint32), ("restart", C.c_uint32), ("n_frames", C.c_uint64), ("n_ticks", C.c_uint64),
+                ("n_segments", C.c_uint64), ("n_sample_bytes", C.c_uint64), ("n_aux", C.c_uint64), ("ticks", C.c_void_p),
+                ("segments", C.c_void_p), ("sample_bytes", C.c_void_p), ("aux", C.c_void_p), ("owner", C.c_void_p)]
 
 
 class ModParsed(C.Structure):
@@ -315,6 +337,10 @@ def lib():
     L.afg_mod_parse.argtypes = [vp, C.c_size_t, C.POINTER(ModParsed)]
     L.afg_mod_parsed_free.argtypes = [C.POINTER(ModParsed)]
     L.afg_mod_parsed_free.restype = None
+    L.afg_xm_render_hip.argtypes = [u32, vp, vp, vp, vp, vp, vp, vp]
+    L.afg_xm_parse.argtypes = [vp, C.c_size_t, C.POINTER(XmParsed)]
+    L.afg_xm_parsed_free.argtypes = [C.POINTER(XmParsed)]
+    L.afg_xm_parsed_free.restype = None
     for fn in (L.afg_is_module, L.afg_module_pattern_count, L.afg_module_length, L.afg_module_tell_pattern, L.afg_module_tell_row):
         fn.argtypes = [vp]
     L.afg_module_rows_in_pattern.argtypes = [vp, C.c_int]
@@ -747,6 +773,57 @@ def mod_layout(parsed_songs):
     tick_arr = np.concatenate([p["ticks"] for p in parsed_songs]) if parsed_songs else np.zeros(0, MOD_TICK_DTYPE)
     seg_arr = np.concatenate([p["segments"] for p in parsed_songs] + [np.zeros(1, MOD_SEGMENT_DTYPE)])
     return songs, tick_arr, seg_arr, plane_arr, frames
+
+
+def xm_parse(file_bytes):
+    """Host front-end only (afg_xm_parse): the batch path's loader and control layer for one XM file.  Returns a dict:
+    channels, length, patterns, instruments, restart, capped, frames, ticks (XM_TICK_DTYPE), segments (XM_SEGMENT_DTYPE),
+    data (uint8: the delta-decoded samples), aux (float32 side table).  Needs no device."""
+    buf = bytes(file_bytes)
+    out = XmParsed()
+    check(lib().afg_xm_parse(buf, len(buf), C.byref(out)))
+    try:
+        def view(ptr, count, dtype):
+            if not count:
+                return np.zeros(0, dtype)
+            raw = (C.c_uint8 * (count * np.dtype(dtype).itemsize)).from_address(ptr)
+            return np.frombuffer(raw, dtype=dtype, count=count).copy()
+        return {"channels": int(out.channels), "length": int(out.length), "patterns": int(out.patterns),
+                "instruments": int(out.instruments), "restart": int(out.restart), "capped": bool(out.capped),
+                "frames": int(out.n_frames),
+                "ticks": view(out.ticks, int(out.n_ticks), XM_TICK_DTYPE),
+                "segments": view(out.segments, int(out.n_segments), XM_SEGMENT_DTYPE),
+                "data": view(out.sample_bytes, int(out.n_sample_bytes), np.uint8),
+                "aux": view(out.aux, int(out.n_aux), np.float32)}
+    finally:
+        lib().afg_xm_parsed_free(C.byref(out))
+
+
+def xm_render(n_songs, d_songs, d_segments, d_ticks, d_sample_bytes, d_aux, d_out, stream=None):
+    """Enqueue the XM mixer (afg_xm_render_hip) on device arrays."""
+    check(lib().afg_xm_render_hip(int(n_songs), _ptr(d_songs), _ptr(d_segments), _ptr(d_ticks), _ptr(d_sample_bytes),
+                                  _ptr(d_aux), _ptr(d_out), _stream(stream)))
+
+
+def xm_layout(parsed_songs, align=16):
+    """Concatenate afg_xm_parse results (dicts of xm_parse) into one launch: (songs, ticks, segments, data, aux, total
+    frames) as numpy arrays; every song starts on a multiple of `align` output frames."""
+    songs = np.zeros(len(parsed_songs), XM_SONG_DTYPE)
+    frames = ticks = segs = data = aux = 0
+    for i, p in enumerate(parsed_songs):
+        songs[i] = (frames, ticks, segs, data, aux, len(p["ticks"]), len(p["data"]), (0, 0))
+        frames += -(-p["frames"] // align) * align
+        ticks += len(p["ticks"])
+        segs += len(p["segments"])
+        data += (len(p["data"]) + 15) & ~15
+        aux += len(p["aux"])
+    data_arr = np.zeros(max(data, 16), np.uint8)
+    for i, p in enumerate(parsed_songs):
+        data_arr[int(songs[i]["sample_base"]):int(songs[i]["sample_base"]) + len(p["data"])] = p["data"]
+    tick_arr = np.concatenate([p["ticks"] for p in parsed_songs]) if parsed_songs else np.zeros(0, XM_TICK_DTYPE)
+    seg_arr = np.concatenate([p["segments"] for p in parsed_songs] + [np.zeros(1, XM_SEGMENT_DTYPE)])
+    aux_arr = np.concatenate([p["aux"] for p in parsed_songs] + [np.zeros(1, np.float32)])
+    return songs, tick_arr, seg_arr, data_arr, aux_arr, frames
 
 
 class AudioStream:

@@ -12,6 +12,7 @@
 #include "../csrc/afg_common.h"
 #include "afg_flac_front.h"
 #include "afg_mod_front.h"
+#include "afg_xm_front.h"
 #include "afg_mp3_front.h"
 #include "afg_opus_front.h"
 #include "afg_vorbis_front.h"
@@ -436,6 +437,7 @@ struct BatchOut {
     StagingPool::Lease opus_plane;      // batch path: the Opus PCM, files back to back
     std::unique_ptr<BatchOut> early;    // batch path: the FLAC / QOA files, decoded on a second host thread meanwhile
     std::shared_ptr<void> mod_plane;    // batch path: the MOD files' PCM (afg_mod_stage.cpp)
+    std::shared_ptr<void> xm_plane;     // batch path: the XM files' PCM (afg_xm_stage.cpp)
 };
 
 // Device stage for a set of parsed files: every FLAC record of the batch in one launch, every QOA frame
@@ -1358,6 +1360,7 @@ struct afg_stream {
     std::unique_ptr<afg_vorbis::Reader> ogg;
     std::unique_ptr<afg_opus::Reader> opus;
     std::unique_ptr<afg_mod::StreamMix> mod;
+    std::unique_ptr<afg_xm::StreamMix> xm;
     Mp3Carry carry;
     OpusCarry opus_carry;
     int opus_gain_i = 0;
@@ -1533,7 +1536,12 @@ afg_stream *afg_open_from_memory(const uint8_t *data, size_t length)
             s->channels = m3.channels;
             s->samplerate = (float)m3.hz;
             s->declared_frames = (int64_t)(m3.declared_samples / (uint64_t)std::max(1, m3.channels));   // stream.d:1737
-        } else if ((s->mod.reset(new afg_mod::StreamMix), afg_mod::probe(d, length, &s->mod->song))) {   // tried last (stream.d:1796-1830)
+        } else if ((s->xm.reset(new afg_xm::StreamMix), afg_xm::probe(d, length, &s->xm->song))) {   // stream.d:1751-1793
+            s->format = AFG_FORMAT_XM;
+            s->channels = 2;
+            s->samplerate = 44100.0f;
+            s->declared_frames = AFG_UNKNOWN_LENGTH;
+        } else if ((s->xm.reset(), s->mod.reset(new afg_mod::StreamMix), afg_mod::probe(d, length, &s->mod->song))) {   // tried last (stream.d:1796-1830)
             s->format = AFG_FORMAT_MOD;
             s->channels = 2;
             s->samplerate = 44100.0f;
@@ -1569,8 +1577,8 @@ int afg_read_samples_float(afg_stream *s, float *out, int frames)
     // declares 0 samples therefore reads nothing); the check is made on entry only, like the reference's.
     if (s->format == AFG_FORMAT_FLAC && s->position == s->declared_frames) return 0;
     try {
-        if (s->format == AFG_FORMAT_MOD) {
-            const int n = s->mod->read(out, frames);
+        if (s->format == AFG_FORMAT_MOD || s->format == AFG_FORMAT_XM) {
+            const int n = s->format == AFG_FORMAT_XM ? s->xm->read(out, frames) : s->mod->read(out, frames);
             if (n < 0) { s->error = kErrorDecodingError; return 0; }
             s->position += n;
             return n;
@@ -1599,7 +1607,7 @@ int afg_can_seek(const afg_stream *s) { return s && !s->error; }
 int afg_seek_position(afg_stream *s, int frame)
 {
     if (!s || s->error) return 0;
-    if (s->format == AFG_FORMAT_MOD) return 0;          // a module seeks by pattern and row (afg_module_seek; stream.d:1097)
+    if (s->format == AFG_FORMAT_MOD || s->format == AFG_FORMAT_XM) return 0;   // a module seeks by pattern and row (afg_module_seek; stream.d:1097)
     // the reference bounds a seek by the declared length (stream.d:1104, :1113, :1137); what can actually be reached is
     // bounded by what decodes.  Backwards: the readers start over; forwards: chunks are decoded and dropped (a chunk
     // is ~1.5 s of audio and takes about a millisecond on the device).
@@ -1637,15 +1645,41 @@ int afg_tell_position(const afg_stream *s) { return (s && !s->error) ? (int)s->p
 void afg_close(afg_stream *s) { delete s; }
 
 // the module functions of AudioStream (stream.d:330-345, :906-1080)
-static const afg_mod::Song *module_of(const afg_stream *s) { return (s && !s->error && s->mod) ? &s->mod->song : nullptr; }
-int afg_is_module(const afg_stream *s) { return module_of(s) ? 1 : 0; }
-int afg_module_pattern_count(const afg_stream *s) { const afg_mod::Song *m = module_of(s); return m ? m->num_patterns() : -1; }
-int afg_module_length(const afg_stream *s) { const afg_mod::Song *m = module_of(s); return m ? m->length() : -1; }
-int afg_module_rows_in_pattern(const afg_stream *s, int) { return module_of(s) ? 64 : -1; }   // stream.d:971-975
-int afg_module_tell_pattern(const afg_stream *s) { const afg_mod::Song *m = module_of(s); return m ? m->pattern() : -1; }
-int afg_module_tell_row(const afg_stream *s) { const afg_mod::Song *m = module_of(s); return m ? m->line() : -1; }
+static const afg_mod::Song *module_of(const afg_stream *s) { return (s && !s->error && s->format == AFG_FORMAT_MOD && s->mod) ? &s->mod->song : nullptr; }
+static afg_xm::Song *xm_of(const afg_stream *s) { return (s && !s->error && s->format == AFG_FORMAT_XM && s->xm) ? &s->xm->song : nullptr; }
+int afg_is_module(const afg_stream *s) { return (module_of(s) || xm_of(s)) ? 1 : 0; }
+int afg_module_pattern_count(const afg_stream *s)
+{
+    if (const afg_xm::Song *x = xm_of(s)) return x->num_patterns();
+    const afg_mod::Song *m = module_of(s);
+    return m ? m->num_patterns() : -1;
+}
+int afg_module_length(const afg_stream *s)
+{
+    if (const afg_xm::Song *x = xm_of(s)) return x->length();
+    const afg_mod::Song *m = module_of(s);
+    return m ? m->length() : -1;
+}
+int afg_module_rows_in_pattern(const afg_stream *s, int pattern)
+{
+    if (const afg_xm::Song *x = xm_of(s)) return x->rows(pattern);   // stream.d:977-984
+    return module_of(s) ? 64 : -1;                                    // stream.d:971-975
+}
+int afg_module_tell_pattern(const afg_stream *s)
+{
+    if (const afg_xm::Song *x = xm_of(s)) return x->table_index();
+    const afg_mod::Song *m = module_of(s);
+    return m ? m->pattern() : -1;
+}
+int afg_module_tell_row(const afg_stream *s)
+{
+    if (const afg_xm::Song *x = xm_of(s)) return x->row();
+    const afg_mod::Song *m = module_of(s);
+    return m ? m->line() : -1;
+}
 int afg_module_seek(afg_stream *s, int pattern, int row)
 {
+    if (afg_xm::Song *x = xm_of(s)) return x->seek(pattern, row) ? 1 : 0;   // stream.d:1078
     if (!module_of(s)) return 0;
     s->mod->song.seek(pattern, row, 0);                 // stream.d:1075
     return 1;
@@ -2430,6 +2464,11 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
         std::vector<int> unknown;
         for (int i = 0; i < n_files; i++)
             if (items[i].status == AFG_ERR_UNSUPPORTED && items[i].message == kErrorUnknownFormat) unknown.push_back(i);
+        // ... and XM directly before it (stream.d:1751)
+        if (int xrc = afg_xm::batch_stage(data, length, unknown, [&](size_t n, const std::function<void(size_t)> &fn) { parallel_for(n, nt, fn); },
+                                          items, owner->xm_plane)) return xrc;
+        tm.lap("xm stage");
+        unknown.erase(std::remove_if(unknown.begin(), unknown.end(), [&](int i) { return items[i].status == AFG_OK || items[i].message != kErrorUnknownFormat; }), unknown.end());
         if (int mrc = afg_mod::batch_stage(data, length, unknown, [&](size_t n, const std::function<void(size_t)> &fn) { parallel_for(n, nt, fn); },
                                            items, owner->mod_plane)) return mrc;
         tm.lap("mod stage");

@@ -1,0 +1,291 @@
+// afg_xm_stage.cpp -- the device side of XM decoding: a stream's reads, the batch path's XM stage and afg_xm_parse.
+//
+// A sibling of afg_mod_stage.cpp: the same pools (afg_mod::DevBuf, the page-locked staging and the kept stream pair of
+// afg_host.cpp), the same chunks of about 128 MB of PCM with chunk c + 1 mixed while chunk c comes back.  What differs is
+// the record set: XM adds the side table of floats and its own song, tick and segment records.
+#include "afg_xm_front.h"
+#include "../csrc/afg_common.h"
+
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <new>
+
+namespace afg_front {
+std::shared_ptr<void> staging_lease(size_t bytes, void **p);
+hipError_t streams_take(hipStream_t *up, hipStream_t *down);
+void streams_give(hipStream_t up, hipStream_t down);
+}  // namespace afg_front
+
+namespace afg_xm {
+
+namespace {
+
+size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// The inputs of one launch in one buffer: ticks, segments, side table, sample data (each 16-byte aligned)
+struct InLayout {
+    size_t ticks = 0, segs = 0, aux = 0, data = 0, bytes = 0;
+    InLayout(size_t n_ticks, size_t n_segs, size_t n_aux, size_t data_bytes)
+    {
+        segs = align16(n_ticks * sizeof(afg_xm_tick));
+        aux = segs + align16(std::max<size_t>(n_segs, 1) * sizeof(afg_xm_segment));
+        data = aux + align16(std::max<size_t>(n_aux, 1) * sizeof(float));
+        bytes = data + align16(std::max<size_t>(data_bytes, 16));
+    }
+};
+
+}  // namespace
+
+StreamMix::~StreamMix()
+{
+    if (stream_) {
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        if (cur != stream_dev_) (void)hipSetDevice(stream_dev_);
+        (void)hipStreamDestroy(stream_);
+        if (cur != stream_dev_ && cur >= 0) (void)hipSetDevice(cur);
+    }
+}
+
+int StreamMix::read(float *out, int frames)
+{
+    if (frames <= 0 || song.loop_count() >= 1) return 0;            // stream.d:600: the song is finished
+    rec_.clear();
+    const int n = (int)song.render((uint64_t)frames, false, rec_);  // exactly `frames`: zeros once the loop count is raised
+    if (rec_.overflow) { afg::set_error(kMessageTooManyRecords); return -1; }
+    int dev = 0;
+    AFG_HIP_CHECK(hipGetDevice(&dev));
+    if (stream_ && stream_dev_ != dev) {
+        (void)hipSetDevice(stream_dev_);
+        (void)hipStreamDestroy(stream_);
+        (void)hipSetDevice(dev);
+        stream_ = nullptr;
+        uploaded_ = false;
+    }
+    if (!stream_) {
+        AFG_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+        stream_dev_ = dev;
+    }
+    const std::vector<uint8_t> &data = song.sample_data();
+    if (!uploaded_ || data_.dev != dev) {
+        if (data_.alloc(data.size())) return -1;
+        AFG_HIP_CHECK(hipMemcpyAsync(data_.p, data.data(), data.size(), hipMemcpyHostToDevice, stream_));
+        uploaded_ = true;
+    }
+    const InLayout L(rec_.ticks.size(), rec_.segs.size(), rec_.aux.size(), 0);
+    const size_t song_at = L.data;                                   // the song record rides in the (unused) data slot
+    staging_.assign(L.bytes + sizeof(afg_xm_song), 0);
+    afg_xm_song sg;
+    std::memset(&sg, 0, sizeof(sg));
+    sg.n_ticks = (uint32_t)rec_.ticks.size();
+    sg.sample_bytes = (uint32_t)data.size();
+    std::memcpy(staging_.data() + song_at, &sg, sizeof(sg));
+    std::memcpy(staging_.data() + L.ticks, rec_.ticks.data(), rec_.ticks.size() * sizeof(afg_xm_tick));
+    if (!rec_.segs.empty()) std::memcpy(staging_.data() + L.segs, rec_.segs.data(), rec_.segs.size() * sizeof(afg_xm_segment));
+    if (!rec_.aux.empty()) std::memcpy(staging_.data() + L.aux, rec_.aux.data(), rec_.aux.size() * sizeof(float));
+    const size_t out_bytes = (size_t)n * 2 * sizeof(float);
+    if (recs_.alloc(staging_.size()) || out_.alloc(out_bytes)) return -1;
+    AFG_HIP_CHECK(hipMemcpyAsync(recs_.p, staging_.data(), staging_.size(), hipMemcpyHostToDevice, stream_));
+    const uint8_t *r = (const uint8_t *)recs_.p;
+    if (afg_xm_render_hip(1, (const afg_xm_song *)(r + song_at), (const afg_xm_segment *)(r + L.segs), (const afg_xm_tick *)(r + L.ticks),
+                          (const uint8_t *)data_.p, (const float *)(r + L.aux), (float *)out_.p, stream_))
+        return -1;
+    float *dst = out;
+    if (!dst) { bounce_.resize((size_t)n * 2); dst = bounce_.data(); }
+    AFG_HIP_CHECK(hipMemcpyAsync(dst, out_.p, out_bytes, hipMemcpyDeviceToHost, stream_));
+    AFG_HIP_CHECK(hipStreamSynchronize(stream_));
+    return n;
+}
+
+int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
+                const std::function<void(size_t, const std::function<void(size_t)> &)> &run_parallel,
+                afg_batch_item *items, std::shared_ptr<void> &keep)
+{
+    if (which.empty()) return AFG_OK;
+    struct Sim {
+        bool ok = false, capped = false, refused = false;
+        uint64_t frames = 0;
+        Song song;
+        Records rec;
+    };
+    std::vector<Sim> sims(which.size());
+    std::atomic<bool> oom{ false };
+    run_parallel(which.size(), [&](size_t k) {
+        const int i = which[k];
+        try {
+            Sim &s = sims[k];
+            if (!data[i] || !probe(data[i], length[i], &s.song)) return;
+            s.frames = render_song(s.song, s.rec, &s.capped);
+            if (s.rec.overflow) { s.refused = true; s.rec = Records(); return; }
+            s.ok = true;
+        } catch (...) {
+            oom = true;
+        }
+    });
+    if (oom) { afg::set_error("XM stage: out of host memory"); return AFG_ERR_OOM; }
+    std::vector<size_t> mods;
+    for (size_t k = 0; k < sims.size(); k++) {
+        if (sims[k].ok) mods.push_back(k);
+        if (sims[k].refused) {                                       // an XM, but not one this library will mix
+            afg_batch_item &it = items[which[k]];
+            it.status = AFG_ERR_UNSUPPORTED;
+            it.message = kMessageTooManyRecords;
+            it.format = AFG_FORMAT_XM;
+        }
+    }
+    if (mods.empty()) return AFG_OK;
+
+    // ---- layout: songs start on 16-frame boundaries of the PCM plane, so that every lane stores whole lines ----
+    const size_t M = mods.size();
+    std::vector<afg_xm_song> songs(M);
+    uint64_t frames = 0, n_ticks = 0, n_segs = 0, n_aux = 0, data_bytes = 0;
+    for (size_t j = 0; j < M; j++) {
+        const Sim &s = sims[mods[j]];
+        afg_xm_song &g = songs[j];
+        std::memset(&g, 0, sizeof(g));
+        g.out_frame = frames; g.tick_base = n_ticks; g.seg_base = n_segs; g.aux_base = n_aux; g.sample_base = data_bytes;
+        g.n_ticks = (uint32_t)s.rec.ticks.size();
+        g.sample_bytes = (uint32_t)s.song.sample_data().size();
+        frames += (s.frames + 15) & ~(uint64_t)15;
+        n_ticks += s.rec.ticks.size(); n_segs += s.rec.segs.size(); n_aux += s.rec.aux.size();
+        data_bytes += align16(s.song.sample_data().size());
+    }
+    void *pcm = nullptr, *in = nullptr;
+    const size_t pcm_bytes = std::max<uint64_t>(frames, 1) * 2 * sizeof(float);
+    const InLayout L(n_ticks, n_segs, n_aux, data_bytes);
+    std::shared_ptr<void> pcm_owner = afg_front::staging_lease(pcm_bytes, &pcm);
+    if (!pcm_owner) return AFG_ERR_OOM;
+    std::shared_ptr<void> in_owner = afg_front::staging_lease(L.bytes, &in);
+    if (!in_owner) return AFG_ERR_OOM;
+    uint8_t *hin = (uint8_t *)in;
+    run_parallel(M, [&](size_t j) {
+        const Sim &s = sims[mods[j]];
+        const afg_xm_song &g = songs[j];
+        if (!s.rec.ticks.empty()) std::memcpy(hin + L.ticks + g.tick_base * sizeof(afg_xm_tick), s.rec.ticks.data(), s.rec.ticks.size() * sizeof(afg_xm_tick));
+        if (!s.rec.segs.empty()) std::memcpy(hin + L.segs + g.seg_base * sizeof(afg_xm_segment), s.rec.segs.data(), s.rec.segs.size() * sizeof(afg_xm_segment));
+        if (!s.rec.aux.empty()) std::memcpy(hin + L.aux + g.aux_base * sizeof(float), s.rec.aux.data(), s.rec.aux.size() * sizeof(float));
+        std::memcpy(hin + L.data + g.sample_base, s.song.sample_data().data(), s.song.sample_data().size());
+    });
+
+    // ---- chunks of songs, about kChunkFrames of output each: mix chunk c + 1 while chunk c comes back ----
+    constexpr uint64_t kChunkFrames = (uint64_t)16 << 20;
+    auto end_of = [&](size_t j) { return songs[j].out_frame + ((sims[mods[j]].frames + 15) & ~(uint64_t)15); };
+    std::vector<size_t> first{ 0 };
+    for (size_t j = 0; j + 1 < M; j++)
+        if (end_of(j) - songs[first.back()].out_frame >= kChunkFrames) first.push_back(j + 1);
+    first.push_back(M);
+    const size_t C = first.size() - 1;
+    std::vector<afg_xm_song> rel(songs);
+    uint64_t max_chunk = 1;
+    for (size_t c = 0; c < C; c++) {
+        const afg_xm_song &f = songs[first[c]];
+        for (size_t j = first[c]; j < first[c + 1]; j++) { rel[j].out_frame -= f.out_frame; rel[j].tick_base -= f.tick_base; }
+        max_chunk = std::max<uint64_t>(max_chunk, end_of(first[c + 1] - 1) - f.out_frame);
+    }
+    afg_mod::DevBuf d_in, d_songs, d_out[2];
+    if (int rc = d_in.alloc(L.bytes)) return rc;
+    if (int rc = d_songs.alloc(M * sizeof(afg_xm_song))) return rc;
+    for (afg_mod::DevBuf &b : d_out) if (int rc = b.alloc(max_chunk * 2 * sizeof(float))) return rc;
+    struct Pair {
+        hipStream_t up = nullptr, down = nullptr;
+        ~Pair()
+        {
+            for (hipStream_t st : { up, down }) if (st) (void)hipStreamSynchronize(st);
+            if (up && down) afg_front::streams_give(up, down);
+        }
+    } pair;
+    AFG_HIP_CHECK(afg_front::streams_take(&pair.up, &pair.down));
+    hipStream_t up = pair.up, down = pair.down;
+    struct EventGuard { hipEvent_t *e; ~EventGuard() { for (int k = 0; k < 4; k++) if (e[k]) (void)hipEventDestroy(e[k]); } };
+    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+    EventGuard g_ev{ ev };
+    for (int k = 0; k < 4; k++) AFG_HIP_CHECK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+    hipEvent_t *mixed = ev, *fetched = ev + 2;
+    AFG_HIP_CHECK(hipMemcpyAsync(d_in.p, in, L.bytes, hipMemcpyHostToDevice, up));
+    AFG_HIP_CHECK(hipMemcpyAsync(d_songs.p, rel.data(), M * sizeof(afg_xm_song), hipMemcpyHostToDevice, up));
+    const uint8_t *din = (const uint8_t *)d_in.p;
+    for (size_t c = 0; c < C; c++) {
+        const afg_xm_song &f = songs[first[c]];
+        const uint64_t chunk_frames = end_of(first[c + 1] - 1) - f.out_frame;
+        afg_mod::DevBuf &o = d_out[c & 1];
+        if (c >= 2) AFG_HIP_CHECK(hipStreamWaitEvent(up, fetched[c & 1], 0));
+        // the padding frames between songs are never mixed; the items do not reach them
+        if (int rc = afg_xm_render_hip((uint32_t)(first[c + 1] - first[c]), (const afg_xm_song *)d_songs.p + first[c],
+                                       (const afg_xm_segment *)(din + L.segs), (const afg_xm_tick *)(din + L.ticks) + f.tick_base,
+                                       din + L.data, (const float *)(din + L.aux), (float *)o.p, up))
+            return rc;
+        AFG_HIP_CHECK(hipEventRecord(mixed[c & 1], up));
+        AFG_HIP_CHECK(hipStreamWaitEvent(down, mixed[c & 1], 0));
+        if (chunk_frames)
+            AFG_HIP_CHECK(hipMemcpyAsync((float *)pcm + 2 * f.out_frame, o.p, chunk_frames * 2 * sizeof(float), hipMemcpyDeviceToHost, down));
+        AFG_HIP_CHECK(hipEventRecord(fetched[c & 1], down));
+    }
+    AFG_HIP_CHECK(hipStreamSynchronize(down));
+    AFG_HIP_CHECK(hipStreamSynchronize(up));
+    for (size_t j = 0; j < M; j++) {
+        const Sim &s = sims[mods[j]];
+        afg_batch_item &it = items[which[mods[j]]];
+        it.status = AFG_OK;
+        it.message = s.capped ? afg_mod::kMessageCapped : nullptr;
+        it.format = AFG_FORMAT_XM;
+        it.channels = 2;
+        it.samplerate = (float)kRate;
+        it.frames = (int64_t)s.frames;
+        it.pcm = s.frames ? (float *)pcm + 2 * songs[j].out_frame : nullptr;
+    }
+    keep = pcm_owner;
+    return AFG_OK;
+}
+
+}  // namespace afg_xm
+
+namespace {
+struct XmParsedOwner {
+    afg_xm::Song song;
+    afg_xm::Records rec;
+};
+}  // namespace
+
+extern "C" int afg_xm_parse(const uint8_t *data, size_t length, afg_xm_parsed *out)
+{
+    if (!out) { afg::set_error("afg_xm_parse: NULL argument"); return AFG_ERR_INVALID; }
+    std::memset(out, 0, sizeof(*out));
+    if (!data) { afg::set_error("afg_xm_parse: NULL argument"); return AFG_ERR_INVALID; }
+    try {
+        std::unique_ptr<XmParsedOwner> o(new XmParsedOwner);
+        if (!afg_xm::probe(data, length, &o->song)) { afg::set_error("afg_xm_parse: not an XM module"); return AFG_ERR_UNSUPPORTED; }
+        out->channels = (uint32_t)o->song.num_channels();
+        out->length = (uint32_t)o->song.length();
+        out->patterns = (uint32_t)o->song.num_patterns();
+        out->instruments = (uint32_t)o->song.num_instruments();
+        out->restart = (uint32_t)o->song.restart();
+        bool capped = false;
+        out->n_frames = afg_xm::render_song(o->song, o->rec, &capped);
+        if (o->rec.overflow) { std::memset(out, 0, sizeof(*out)); afg::set_error(afg_xm::kMessageTooManyRecords); return AFG_ERR_UNSUPPORTED; }
+        out->capped = capped;
+        if (o->rec.segs.empty()) o->rec.segs.resize(1), std::memset(o->rec.segs.data(), 0, sizeof(afg_xm_segment)), out->n_segments = 0;
+        else out->n_segments = o->rec.segs.size();
+        out->n_aux = o->rec.aux.size();
+        if (o->rec.aux.empty()) o->rec.aux.push_back(0.0f);
+        out->n_ticks = o->rec.ticks.size();
+        out->n_sample_bytes = o->song.sample_data().size();
+        out->ticks = o->rec.ticks.data();
+        out->segments = o->rec.segs.data();
+        out->sample_bytes = const_cast<uint8_t *>(o->song.sample_data().data());
+        out->aux = o->rec.aux.data();
+        out->owner = o.release();
+        return AFG_OK;
+    } catch (...) {
+        std::memset(out, 0, sizeof(*out));
+        afg::set_error("afg_xm_parse: out of host memory");
+        return AFG_ERR_OOM;
+    }
+}
+
+extern "C" void afg_xm_parsed_free(afg_xm_parsed *p)
+{
+    if (!p) return;
+    delete (XmParsedOwner *)p->owner;
+    std::memset(p, 0, sizeof(*p));
+}

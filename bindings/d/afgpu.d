@@ -348,6 +348,30 @@ int afg_mod_render_hip(uint n_songs, const(afg_mod_song)* d_songs, const(afg_mod
                        const(afg_mod_tick)* d_ticks, const(ubyte)* d_sample_bytes, float* d_out, void* hip_stream);
 int afg_mod_parse(const(ubyte)* data, size_t length, afg_mod_parsed* parsed);
 void afg_mod_parsed_free(afg_mod_parsed* parsed);
+struct afg_xm_song { ulong out_frame, tick_base, seg_base, sample_base, aux_base; uint n_ticks, sample_bytes; ulong[2] reserved; }
+struct afg_xm_tick { uint frame, frames, seg, n_seg; float scale; short table_index, row; uint loop_count, pad; }
+struct afg_xm_segment
+{
+    uint frame, frames, sample_off, last, flags, channel;
+    float position, step, vol_l, vol_r;
+    uint aux_vol, aux_fade, aux_pos, fade_count;
+    uint[2] pad;
+}
+struct afg_xm_parsed
+{
+    uint channels, capped, length, patterns, instruments, restart;
+    ulong n_frames, n_ticks, n_segments, n_sample_bytes, n_aux;
+    afg_xm_tick* ticks;
+    afg_xm_segment* segments;
+    ubyte* sample_bytes;
+    float* aux;
+    void* owner;
+}
+int afg_xm_render_hip(uint n_songs, const(afg_xm_song)* d_songs, const(afg_xm_segment)* d_segments,
+                      const(afg_xm_tick)* d_ticks, const(ubyte)* d_sample_bytes, const(float)* d_aux, float* d_out,
+                      void* hip_stream);
+int afg_xm_parse(const(ubyte)* data, size_t length, afg_xm_parsed* parsed);
+void afg_xm_parsed_free(afg_xm_parsed* parsed);
 int afg_is_module(const(afg_stream)* s);
 int afg_module_pattern_count(const(afg_stream)* s);
 int afg_module_length(const(afg_stream)* s);

@@ -371,8 +371,8 @@ int afg_opus_output_gain_hip(uint64_t n_samples, const float *d_in, float gain, 
  *  Outer surface: the AudioStream subset (stream.d:102-637) over the host front-ends
  *  -- FLAC (native container, drflac.d:680-1695, :1887-2153), QOA (qoa.d:413-486, :703-851), MP3 Layer I / II / III
  *  (minimp3.d, minimp3_ex.d), Ogg Vorbis (stb_vorbis2.d) and Ogg Opus with CELT-only packets (dopus.d; a file that holds
- *  SILK / hybrid packets is refused at open with this library's own message) and ProTracker MOD (pocketmod.d: below).
- *  WAV and XM report "unrecognized encoding".  Like the reference the stream decodes as the caller pulls:
+ *  SILK / hybrid packets is refused at open with this library's own message), ProTracker MOD (pocketmod.d: below) and
+ *  FastTracker II XM (libxm.d: below).  WAV reports "unrecognized encoding".  Like the reference the stream decodes as the caller pulls:
  *  afg_open_from_memory parses the container only, a read that finds the FIFO empty decodes the next chunk (64 MP3 frames /
  *  Vorbis or Opus packets, 16 FLAC or QOA frames) on the device; afg_batch_decode parses whole files into transform-stage
  *  records and decodes them in one pass.  A MOD stream has no FIFO: each read runs the module's control layer on the host
@@ -689,7 +689,88 @@ typedef struct afg_mod_parsed {
 int  afg_mod_parse(const uint8_t *data, size_t length, afg_mod_parsed *out);    /* AFG_ERR_UNSUPPORTED: not a MOD */
 void afg_mod_parsed_free(afg_mod_parsed *p);
 
-/* The module half of AudioStream (stream.d:330-345, :906-1080) for a MOD stream; 0 / -1 on any other stream.
+/* ========================================================================== *
+ *  FastTracker II XM (libxm.d; stream.d:595-605, :1751-1793): 2 channels at 44100 Hz, xm_set_max_loop_count(ctx, 1),
+ *  length AFG_UNKNOWN_LENGTH, one numeric mode.  The loader and the control layer (xm_row, xm_tick, envelopes, effects:
+ *  libxm.d:1154-2311) run on the host once per tick and describe the mix as records; the device mixer (afg_xm_render_hip)
+ *  does the per-frame layer (xm_next_of_sample, xm_sample: libxm.d:2313-2475), bit-identical float32.
+ *  A segment is one channel stepping through one sample in one direction: no loop wrap, ping-pong turn or sample end
+ *  falls inside it (the host does those itself, with the reference's float operations), and it is of one kind: its
+ *  volumes are steady or ramping (XM_SLIDE_TOWARDS per frame), and it is inside the 32-frame cross-fade after a trigger
+ *  or not.  What cannot be computed in closed form travels in a side table of floats (`aux`): the ramp's volumes per
+ *  frame, the cross-fade's stored values per frame, and for a segment that runs backwards (or whose step is not a finite
+ *  number >= 0) the position at the first frame of each group of 16 song-relative frames.
+ *  Probe: XM is tried directly before MOD (stream.d:1751).  A file with the XM header that the loader refuses stays
+ *  refused.  A read returns 0 once the loop count is >= 1, else exactly the frames asked for; ticks that start with a loop
+ *  count >= 1 are zeros (libxm.d:2438).  The batch path's output is the frames before the tick that raises the loop count
+ *  to 1, cut at AFG_MOD_MAX_FRAMES like a MOD.
+ * ========================================================================== */
+#define AFG_XM_SEG_16BIT    1u     /* int16 samples (scaled by 1/32768), else int8 (1/128) */
+#define AFG_XM_SEG_BACK     2u     /* position -= step per frame */
+#define AFG_XM_SEG_TABLE    4u     /* lane start positions from aux_pos (else the closed form of mod_chain.h) */
+#define AFG_XM_SEG_RAMP     8u     /* volumes per frame from aux_vol (left, right pairs), else vol_l / vol_r */
+#define AFG_XM_SEG_FADE     16u    /* XM_LERP(aux_fade[k], s, (fade_count + k) / 32) */
+
+typedef struct afg_xm_song {       /* one song of a launch (64 bytes) */
+    uint64_t out_frame;            /* first stereo frame of the song in d_out */
+    uint64_t tick_base;            /* first afg_xm_tick of the song */
+    uint64_t seg_base;             /* first afg_xm_segment of the song */
+    uint64_t sample_base;          /* first byte of the song's sample data in d_sample_bytes (a multiple of 2) */
+    uint64_t aux_base;             /* first float of the song's side table in d_aux */
+    uint32_t n_ticks;
+    uint32_t sample_bytes;
+    uint64_t reserved[2];          /* 0 */
+} afg_xm_song;
+
+/* A tick, or a piece of one: a read's end cuts a tick, and a tick longer than 4096 frames is written as several records. */
+typedef struct afg_xm_tick {       /* a run of output frames mixed with one set of channel states (32 bytes) */
+    uint32_t frame, frames;        /* first output frame (relative to the song) and count */
+    uint32_t seg, n_seg;           /* its segments: song seg_base + seg ..., channels in index order */
+    float scale;                   /* global_volume * amplification, applied to the channel sum */
+    int16_t table_index, row;      /* song position when the run was mixed */
+    uint32_t loop_count;           /* >= 1: the frames are zeros and no channel steps */
+    uint32_t pad;
+} afg_xm_tick;
+
+typedef struct afg_xm_segment {    /* 64 bytes */
+    uint32_t frame, frames;        /* output frames (relative to the song) */
+    uint32_t sample_off;           /* byte offset of the sample in the song's sample data */
+    uint32_t last;                 /* sample length - 1, in samples: an index above it reads this one */
+    uint32_t flags;                /* AFG_XM_SEG_* */
+    uint32_t channel;
+    float position, step;          /* position at `frame` */
+    float vol_l, vol_r;            /* steady volumes */
+    uint32_t aux_vol, aux_fade, aux_pos;   /* song-relative float indexes into the side table */
+    uint32_t fade_count;           /* frame_count at `frame` */
+    uint32_t pad[2];
+} afg_xm_segment;
+
+/* Mixes every tick of n_songs songs into d_out (interleaved float pairs), as afg_mod_render_hip does for MOD records:
+ * each frame starts at +0.0f, takes s * vol of every segment that covers it in record order (separate multiply and add),
+ * and is then multiplied by the tick's scale.  All arrays are device arrays; d_out is 16-byte aligned. */
+int afg_xm_render_hip(uint32_t n_songs, const afg_xm_song *d_songs, const afg_xm_segment *d_segments,
+                      const afg_xm_tick *d_ticks, const uint8_t *d_sample_bytes, const float *d_aux, float *d_out,
+                      void *hip_stream);
+
+/* Host front-end on its own (no device needed): the batch path's loader and control layer for one file. */
+typedef struct afg_xm_parsed {
+    uint32_t channels;
+    uint32_t capped;               /* 1: cut at AFG_MOD_MAX_FRAMES */
+    uint32_t length, patterns, instruments, restart;
+    uint64_t n_frames, n_ticks, n_segments, n_sample_bytes, n_aux;
+    afg_xm_tick *ticks;
+    afg_xm_segment *segments;
+    uint8_t *sample_bytes;         /* delta-decoded sample data (int8, or int16 in host order at even offsets) */
+    float *aux;
+    void *owner;                   /* internal */
+} afg_xm_parsed;
+int  afg_xm_parse(const uint8_t *data, size_t length, afg_xm_parsed *out);      /* AFG_ERR_UNSUPPORTED: not an XM */
+void afg_xm_parsed_free(afg_xm_parsed *p);
+
+/* The module half of AudioStream (stream.d:330-345, :906-1080) for a MOD or XM stream; 0 / -1 on any other stream.
+ * For an XM: pattern count and length are xm_get_number_of_patterns / xm_get_module_length, rows are per pattern (-1 out
+ * of range, stream.d:979-983), tell is current_table_index / current_row, and afg_module_seek is xm_seek (libxm.d:951-959:
+ * index, row, tick 0, remaining_samples_in_tick = 0, channels untouched) for an index inside the order and a row below 256.
  * afg_can_seek is 1 for a MOD (stream.d:366); afg_seek_position(frame) refuses it (the reference asserts, stream.d:1097).
  * afg_module_seek is pocketmod_seek (pocketmod.d:954-962) as written: it sets the order index and line, tick 0, and
  * checks nothing. */
