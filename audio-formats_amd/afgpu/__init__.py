@@ -74,6 +74,7 @@ ABI_SYMBOLS = [
     "afg_mod_render_hip", "afg_mod_parse", "afg_mod_parsed_free", "afg_is_module", "afg_module_pattern_count",
     "afg_module_length", "afg_module_rows_in_pattern", "afg_module_tell_pattern", "afg_module_tell_row", "afg_module_seek",
     "afg_xm_render_hip", "afg_xm_parse", "afg_xm_parsed_free",
+    "afg_wav_layout", "afg_wav_convert_hip", "afg_wav_parse",
 ]
 
 
@@ -165,6 +166,20 @@ class XmParsed(C.Structure):
                 ("instruments", C.c_uint32), ("restart", C.c_uint32), ("n_frames", C.c_uint64), ("n_ticks", C.c_uint64),
                 ("n_segments", C.c_uint64), ("n_sample_bytes", C.c_uint64), ("n_aux", C.c_uint64), ("ticks", C.c_void_p),
                 ("segments", C.c_void_p), ("sample_bytes", C.c_void_p), ("aux", C.c_void_p), ("owner", C.c_void_p)]
+
+
+# WAV (afg.h): span records of afg_wav_convert_hip and what afg_wav_parse returns
+WAV_KIND_U8, WAV_KIND_S16, WAV_KIND_S24, WAV_KIND_S32, WAV_KIND_F32, WAV_KIND_F64 = range(6)
+WAV_KIND_BYTES = (1, 2, 3, 4, 4, 8)
+WAV_TILE_SAMPLES = 4096
+WAV_SPAN_DTYPE = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), ("count", np.uint64), ("tile_first", np.uint64),
+                           ("kind", np.uint32), ("pad", np.uint32)])
+assert WAV_SPAN_DTYPE.itemsize == 40
+
+
+class WavParsed(C.Structure):
+    _fields_ = [("tag", C.c_uint32), ("channels", C.c_uint32), ("bits", C.c_uint32), ("sample_rate", C.c_uint32),
+                ("frames", C.c_uint32), ("kind", C.c_int32), ("samples_offset", C.c_uint64), ("present_samples", C.c_uint64)]
 
 
 class ModParsed(C.Structure):
@@ -339,6 +354,10 @@ def lib():
     L.afg_mod_parsed_free.restype = None
     L.afg_xm_render_hip.argtypes = [u32, vp, vp, vp, vp, vp, vp, vp]
     L.afg_xm_parse.argtypes = [vp, C.c_size_t, C.POINTER(XmParsed)]
+    L.afg_wav_layout.argtypes = [vp, u64]
+    L.afg_wav_layout.restype = u64
+    L.afg_wav_convert_hip.argtypes = [u64, vp, u64, vp, u64, vp, u64, vp]
+    L.afg_wav_parse.argtypes = [vp, C.c_size_t, C.POINTER(WavParsed)]
     L.afg_xm_parsed_free.argtypes = [C.POINTER(XmParsed)]
     L.afg_xm_parsed_free.restype = None
     for fn in (L.afg_is_module, L.afg_module_pattern_count, L.afg_module_length, L.afg_module_tell_pattern, L.afg_module_tell_row):
@@ -824,6 +843,28 @@ def xm_layout(parsed_songs, align=16):
     seg_arr = np.concatenate([p["segments"] for p in parsed_songs] + [np.zeros(1, XM_SEGMENT_DTYPE)])
     aux_arr = np.concatenate([p["aux"] for p in parsed_songs] + [np.zeros(1, np.float32)])
     return songs, tick_arr, seg_arr, data_arr, aux_arr, frames
+
+
+def wav_parse(file_bytes):
+    """Host front-end only (afg_wav_parse): WAVDecoder.scan on one file.  Returns a dict: tag, channels, bits, sample_rate,
+    frames (declared), kind (WAV_KIND_*, -1: the first read fails), samples_offset, present_samples.  Raises AfgError with
+    the scan's reason when the file is refused.  Needs no device."""
+    buf = bytes(file_bytes)
+    out = WavParsed()
+    check(lib().afg_wav_parse(buf, len(buf), C.byref(out)))
+    return {name: int(getattr(out, name)) for name, _ in WavParsed._fields_}
+
+
+def wav_layout(spans):
+    """afg_wav_layout: fills tile_first of a WAV_SPAN_DTYPE array in place; returns the launch's tile count."""
+    assert spans.dtype == WAV_SPAN_DTYPE and spans.flags.c_contiguous
+    return int(lib().afg_wav_layout(spans.ctypes.data, len(spans)))
+
+
+def wav_convert(n_spans, d_spans, n_tiles, d_in, in_bytes, d_out, out_floats, stream=None):
+    """Enqueue the WAV sample conversion (afg_wav_convert_hip) on device arrays."""
+    check(lib().afg_wav_convert_hip(int(n_spans), _ptr(d_spans), int(n_tiles), _ptr(d_in), int(in_bytes), _ptr(d_out),
+                                    int(out_floats), _stream(stream)))
 
 
 class AudioStream:

@@ -12,6 +12,7 @@
 #include "../csrc/afg_common.h"
 #include "afg_flac_front.h"
 #include "afg_mod_front.h"
+#include "afg_wav_front.h"
 #include "afg_xm_front.h"
 #include "afg_mp3_front.h"
 #include "afg_opus_front.h"
@@ -437,6 +438,7 @@ struct BatchOut {
     StagingPool::Lease opus_plane;      // batch path: the Opus PCM, files back to back
     std::unique_ptr<BatchOut> early;    // batch path: the FLAC / QOA files, decoded on a second host thread meanwhile
     std::shared_ptr<void> mod_plane;    // batch path: the MOD files' PCM (afg_mod_stage.cpp)
+    std::shared_ptr<void> wav_plane;    // batch path: the WAV files' PCM (afg_wav_stage.cpp)
     std::shared_ptr<void> xm_plane;     // batch path: the XM files' PCM (afg_xm_stage.cpp)
 };
 
@@ -1361,6 +1363,8 @@ struct afg_stream {
     std::unique_ptr<afg_opus::Reader> opus;
     std::unique_ptr<afg_mod::StreamMix> mod;
     std::unique_ptr<afg_xm::StreamMix> xm;
+    std::unique_ptr<afg_wav::StreamConv> wav;
+    bool wav_failed = false;            // a WAV read has failed: the stream is in error state and still tells its position
     Mp3Carry carry;
     OpusCarry opus_carry;
     int opus_gain_i = 0;
@@ -1521,7 +1525,12 @@ afg_stream *afg_open_from_memory(const uint8_t *data, size_t length)
             s->channels = (int)s->fi.channels;
             s->samplerate = (float)s->fi.sample_rate;
             s->declared_frames = (int64_t)s->fi.total_samples;            // totalSampleCount / channels, stream.d:1631
-        } else if (qoa_parse(d, length, s->qi, s->qoa)) {
+        } else if ((s->wav.reset(new afg_wav::StreamConv), afg_wav::scan(d, length, &s->wav->info) == nullptr)) {   // stream.d:1638-1655
+            s->format = AFG_FORMAT_WAV;
+            s->channels = s->wav->info.channels;
+            s->samplerate = (float)s->wav->info.sample_rate;
+            s->declared_frames = (int64_t)s->wav->info.frames;
+        } else if ((s->wav.reset(), qoa_parse(d, length, s->qi, s->qoa))) {
             s->format = AFG_FORMAT_QOA;
             s->channels = (int)s->qi.channels;
             s->samplerate = (float)s->qi.samplerate;
@@ -1577,6 +1586,13 @@ int afg_read_samples_float(afg_stream *s, float *out, int frames)
     // declares 0 samples therefore reads nothing); the check is made on entry only, like the reference's.
     if (s->format == AFG_FORMAT_FLAC && s->position == s->declared_frames) return 0;
     try {
+        if (s->format == AFG_FORMAT_WAV) {                       // stream.d:557-570
+            bool failed = false;
+            const int n = s->wav->read(s->bytes.data(), s->bytes.size(), out, frames, &failed);
+            s->position = s->wav->tell();
+            if (n < 0 || failed) { s->error = kErrorDecodingError; s->wav_failed = true; return 0; }
+            return n;
+        }
         if (s->format == AFG_FORMAT_MOD || s->format == AFG_FORMAT_XM) {
             const int n = s->format == AFG_FORMAT_XM ? s->xm->read(out, frames) : s->mod->read(out, frames);
             if (n < 0) { s->error = kErrorDecodingError; return 0; }
@@ -1608,6 +1624,11 @@ int afg_seek_position(afg_stream *s, int frame)
 {
     if (!s || s->error) return 0;
     if (s->format == AFG_FORMAT_MOD || s->format == AFG_FORMAT_XM) return 0;   // a module seeks by pattern and row (afg_module_seek; stream.d:1097)
+    if (s->format == AFG_FORMAT_WAV) {                           // stream.d:1197-1199
+        if (!s->wav->seek(frame)) return 0;
+        s->position = frame;
+        return 1;
+    }
     // the reference bounds a seek by the declared length (stream.d:1104, :1113, :1137); what can actually be reached is
     // bounded by what decodes.  Backwards: the readers start over; forwards: chunks are decoded and dropped (a chunk
     // is ~1.5 s of audio and takes about a millisecond on the device).
@@ -1640,7 +1661,11 @@ int afg_seek_position(afg_stream *s, int frame)
     }
 }
 
-int afg_tell_position(const afg_stream *s) { return (s && !s->error) ? (int)s->position : -1; }
+int afg_tell_position(const afg_stream *s)
+{
+    if (s && s->wav_failed && s->wav) return s->wav->tell();    // wav.d:253: the failed read has moved the position
+    return (s && !s->error) ? (int)s->position : -1;
+}
 
 void afg_close(afg_stream *s) { delete s; }
 
@@ -2464,6 +2489,12 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
         std::vector<int> unknown;
         for (int i = 0; i < n_files; i++)
             if (items[i].status == AFG_ERR_UNSUPPORTED && items[i].message == kErrorUnknownFormat) unknown.push_back(i);
+        // WAV comes well before either (stream.d:1638); no probe between it and them takes a file its scan accepts (QOA and
+        // Ogg have their own magic, looks_like_mp3 declines RIFF), so its stage can run here, on the files nothing took
+        if (int wrc = afg_wav::batch_stage(data, length, unknown, [&](size_t n, const std::function<void(size_t)> &fn) { parallel_for(n, nt, fn); },
+                                           items, owner->wav_plane)) return wrc;
+        tm.lap("wav stage");
+        unknown.erase(std::remove_if(unknown.begin(), unknown.end(), [&](int i) { return items[i].status == AFG_OK || items[i].message != kErrorUnknownFormat; }), unknown.end());
         // ... and XM directly before it (stream.d:1751)
         if (int xrc = afg_xm::batch_stage(data, length, unknown, [&](size_t n, const std::function<void(size_t)> &fn) { parallel_for(n, nt, fn); },
                                           items, owner->xm_plane)) return xrc;

@@ -1,0 +1,270 @@
+// afg_wav_stage.cpp -- the device side of WAV decoding: a stream's reads and the batch path's WAV stage.
+//
+// Both hand csrc/wav_pcm.hip the sample bytes as they are in the file -- 1 to 8 bytes per sample, nothing converted on the
+// host -- and bring float32 back.  End to end this is bound by the bus (1-8 bytes up, 4 down per sample), not by the
+// kernel; it runs on the device because the library has no CPU path, and so that a WAV in a batch rides the same upload /
+// kernel / download pipeline as its neighbours.
+#include "afg_wav_front.h"
+#include "../csrc/afg_common.h"
+
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+
+namespace afg_front {
+// page-locked staging and the kept stream pair (afg_host.cpp)
+std::shared_ptr<void> staging_lease(size_t bytes, void **p);
+hipError_t streams_take(hipStream_t *up, hipStream_t *down);
+void streams_give(hipStream_t up, hipStream_t down);
+}  // namespace afg_front
+
+namespace afg_wav {
+
+const char *const kMessageDecodingError = "Decoder encountered an error";
+
+namespace {
+size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
+constexpr uint64_t kStreamChunkSamples = (uint64_t)1 << 18;               // a stream's FIFO refill: 1 MB of floats
+constexpr uint64_t kBatchChunkSamples = (uint64_t)8 << 20;                // a batch chunk: 32 MB of floats, 8-64 MB of input
+static_assert(kBatchChunkSamples % AFG_WAV_TILE_SAMPLES == 0, "files are cut at tile boundaries");
+}  // namespace
+
+StreamConv::~StreamConv()
+{
+    if (stream_) {
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        if (cur != stream_dev_) (void)hipSetDevice(stream_dev_);
+        (void)hipStreamDestroy(stream_);
+        if (cur != stream_dev_ && cur >= 0) (void)hipSetDevice(cur);
+    }
+}
+
+bool StreamConv::seek(int frame)
+{
+    if (frame < 0 || (uint32_t)frame > info.frames) return false;
+    position_ = (uint32_t)frame;
+    return true;
+}
+
+// frames [frame0, frame0 + frames) of the file into the FIFO; all of their samples are in the file
+int StreamConv::decode(const uint8_t *file, uint64_t frame0, uint64_t frames)
+{
+    const uint64_t C = (uint64_t)info.channels, B = (uint64_t)bytes_per_sample(info);
+    const uint64_t count = frames * C, bytes = count * B;
+    int dev = 0;
+    AFG_HIP_CHECK(hipGetDevice(&dev));
+    if (stream_ && stream_dev_ != dev) {
+        // the caller changed devices between reads: the stream is made again there (the buffers follow by themselves)
+        (void)hipSetDevice(stream_dev_);
+        (void)hipStreamDestroy(stream_);
+        (void)hipSetDevice(dev);
+        stream_ = nullptr;
+    }
+    if (!stream_) {
+        AFG_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+        stream_dev_ = dev;
+    }
+    afg_wav_span span;
+    std::memset(&span, 0, sizeof(span));
+    span.count = count;
+    span.kind = (uint32_t)kind_of(info);
+    const uint64_t tiles = afg_wav_layout(&span, 1);
+    const size_t in_bytes = align16(bytes), out_floats = (size_t)((count + 3) & ~(uint64_t)3);
+    if (in_.alloc(in_bytes) || out_.alloc(out_floats * sizeof(float)) || spans_.alloc(sizeof(span))) return AFG_ERR_OOM;
+    fifo_.resize((size_t)count);
+    fifo_frame_ = frame0;
+    AFG_HIP_CHECK(hipMemcpyAsync(spans_.p, &span, sizeof(span), hipMemcpyHostToDevice, stream_));
+    AFG_HIP_CHECK(hipMemcpyAsync(in_.p, file + info.samples_off + frame0 * C * B, bytes, hipMemcpyHostToDevice, stream_));
+    if (int rc = afg_wav_convert_hip(1, (const afg_wav_span *)spans_.p, tiles, (const uint8_t *)in_.p, in_bytes, (float *)out_.p,
+                                     out_floats, stream_)) {
+        fifo_.clear();
+        return rc;
+    }
+    hipError_t e = hipMemcpyAsync(fifo_.data(), out_.p, count * sizeof(float), hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    if (e != hipSuccess) {
+        fifo_.clear();
+        afg::set_error("WAV stream: %s", hipGetErrorString(e));
+        return AFG_ERR_HIP;
+    }
+    return AFG_OK;
+}
+
+int StreamConv::read(const uint8_t *file, size_t size, float *out, int frames, bool *failed)
+{
+    (void)size;
+    *failed = false;
+    if (frames <= 0) return 0;
+    // wav.d:247-255: the request is clamped to what the header declares and the position moves before anything is read
+    const uint32_t n = std::min<uint32_t>((uint32_t)frames, info.frames - position_);
+    const uint64_t first = position_, C = (uint64_t)info.channels;
+    position_ += n;
+    if (kind_of(info) < 0) { *failed = true; return 0; }                  // wav.d:282-286, :332-337
+    if (n == 0) return 0;
+    // the reference reads sample by sample and gives the whole read up at the first one that is not there
+    if ((first + n) * C > info.present) { *failed = true; return 0; }
+    const uint64_t chunk = std::max<uint64_t>(1, kStreamChunkSamples / C), valid_end = std::min<uint64_t>(info.frames, info.present / C);
+    uint64_t f = first, done = 0;
+    while (done < n) {
+        uint64_t held = fifo_.size() / C;
+        if (f < fifo_frame_ || f >= fifo_frame_ + held) {
+            if (decode(file, f, std::min(valid_end - f, chunk)) != AFG_OK) return -1;
+            held = fifo_.size() / C;
+        }
+        const uint64_t take = std::min<uint64_t>(n - done, fifo_frame_ + held - f);
+        if (out) std::memcpy(out + done * C, fifo_.data() + (f - fifo_frame_) * C, (size_t)(take * C) * sizeof(float));
+        f += take;
+        done += take;
+    }
+    return (int)n;
+}
+
+int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
+                const std::function<void(size_t, const std::function<void(size_t)> &)> &run_parallel,
+                afg_batch_item *items, std::shared_ptr<void> &keep)
+{
+    if (which.empty()) return AFG_OK;
+    // ---- the scan, one file per helper-thread job ----
+    struct File { bool ok = false; Info info; int kind = -1; uint64_t out_off = 0; };
+    std::vector<File> files(which.size());
+    run_parallel(which.size(), [&](size_t k) {
+        const int i = which[k];
+        File &f = files[k];
+        if (!data[i] || scan(data[i], length[i], &f.info) != nullptr) return;
+        f.ok = true;
+        f.kind = kind_of(f.info);
+    });
+    // ---- layout: a file's floats start on a 16-byte boundary of the PCM plane; files are cut into pieces at tile
+    //      boundaries where a chunk is full, so that a file of any length goes through buffers of one chunk ----
+    struct Piece { size_t file; uint64_t src_byte; };
+    std::vector<Piece> pieces;
+    std::vector<afg_wav_span> spans;                     // chunk-relative offsets
+    std::vector<size_t> first{ 0 };                      // chunk c owns pieces [first[c], first[c + 1])
+    std::vector<uint64_t> chunk_out0{ 0 };               // its first float in the PCM plane
+    uint64_t plane_floats = 0, in_at = 0, chunk_samples = 0, max_in = 16, max_out = 4;
+    bool any = false;
+    auto close_chunk = [&] {
+        if (first.back() == pieces.size()) return;
+        first.push_back(pieces.size());
+        chunk_out0.push_back(0);
+        in_at = 0; chunk_samples = 0;
+    };
+    for (size_t k = 0; k < files.size(); k++) {
+        File &f = files[k];
+        if (!f.ok) continue;
+        afg_batch_item &it = items[which[k]];
+        it.format = AFG_FORMAT_WAV;
+        it.channels = f.info.channels;
+        it.samplerate = (float)f.info.sample_rate;
+        it.frames = 0;
+        it.pcm = nullptr;
+        const uint64_t count = (uint64_t)f.info.frames * (uint64_t)f.info.channels, B = (uint64_t)bytes_per_sample(f.info);
+        if (f.kind < 0 || f.info.present != count) {     // one read of the whole declared length fails (stream.d:563-567)
+            it.status = AFG_ERR_INVALID;
+            it.message = kMessageDecodingError;
+            f.ok = false;
+            continue;
+        }
+        it.status = AFG_OK;
+        it.message = nullptr;
+        any = true;
+        plane_floats = (plane_floats + 3) & ~(uint64_t)3;
+        f.out_off = plane_floats;
+        for (uint64_t done = 0; done < count;) {
+            if (kBatchChunkSamples - chunk_samples < AFG_WAV_TILE_SAMPLES) close_chunk();
+            const uint64_t room = (kBatchChunkSamples - chunk_samples) & ~(uint64_t)(AFG_WAV_TILE_SAMPLES - 1);
+            const uint64_t take = std::min(count - done, room);
+            if (first.back() == pieces.size()) chunk_out0.back() = f.out_off + done;
+            afg_wav_span sp;
+            std::memset(&sp, 0, sizeof(sp));
+            sp.in_off = in_at;
+            sp.out_off = f.out_off + done - chunk_out0.back();
+            sp.count = take;
+            sp.kind = (uint32_t)f.kind;
+            spans.push_back(sp);
+            pieces.push_back({ k, f.info.samples_off + done * B });
+            in_at += align16(take * B);
+            chunk_samples += take;
+            done += take;
+            max_in = std::max(max_in, in_at);
+            max_out = std::max(max_out, (sp.out_off + take + 3) & ~(uint64_t)3);
+        }
+        plane_floats += count;
+    }
+    if (!any) return AFG_OK;
+    close_chunk();
+    const size_t C = first.size() - 1;
+    std::vector<uint64_t> tiles(C, 0);
+    for (size_t c = 0; c < C; c++) tiles[c] = afg_wav_layout(spans.data() + first[c], first[c + 1] - first[c]);
+
+    // page-locked: the PCM plane the items point into (owned by `keep`) and two input stagings that take turns
+    void *pcm = nullptr, *stage[2] = { nullptr, nullptr };
+    std::shared_ptr<void> pcm_owner = afg_front::staging_lease(std::max<uint64_t>(plane_floats, 4) * sizeof(float), &pcm);
+    if (!pcm_owner) return AFG_ERR_OOM;
+    std::shared_ptr<void> stage_owner[2];
+    for (int b = 0; b < (C > 1 ? 2 : 1); b++)
+        if (!(stage_owner[b] = afg_front::staging_lease((size_t)max_in, &stage[b]))) return AFG_ERR_OOM;
+    afg_mod::DevBuf d_spans, d_in[2], d_out[2];
+    if (int rc = d_spans.alloc(std::max<size_t>(spans.size(), 1) * sizeof(afg_wav_span))) return rc;
+    for (int b = 0; b < (C > 1 ? 2 : 1); b++) {
+        if (int rc = d_in[b].alloc((size_t)max_in)) return rc;
+        if (int rc = d_out[b].alloc((size_t)max_out * sizeof(float))) return rc;
+    }
+    // the kept upload / download pair, given back drained on every way out
+    struct Pair {
+        hipStream_t up = nullptr, down = nullptr;
+        ~Pair()
+        {
+            for (hipStream_t st : { up, down }) if (st) (void)hipStreamSynchronize(st);
+            if (up && down) afg_front::streams_give(up, down);
+        }
+    } pair;
+    AFG_HIP_CHECK(afg_front::streams_take(&pair.up, &pair.down));
+    hipStream_t up = pair.up, down = pair.down;
+    // rings of two: chunk c's staging is free once chunk c - 2 has gone up (the host waits), its output buffer once
+    // chunk c - 2 has come back (the upload stream waits)
+    struct EventGuard { hipEvent_t *e; ~EventGuard() { for (int k = 0; k < 6; k++) if (e[k]) (void)hipEventDestroy(e[k]); } };
+    hipEvent_t ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    EventGuard g_ev{ ev };
+    for (int k = 0; k < 6; k++) AFG_HIP_CHECK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+    hipEvent_t *uploaded = ev, *converted = ev + 2, *fetched = ev + 4;
+    AFG_HIP_CHECK(hipMemcpyAsync(d_spans.p, spans.data(), spans.size() * sizeof(afg_wav_span), hipMemcpyHostToDevice, up));
+    for (size_t c = 0; c < C; c++) {
+        const int b = (int)(c & 1);
+        const size_t p0 = first[c], p1 = first[c + 1];
+        const uint64_t in_bytes = spans[p1 - 1].in_off + align16(spans[p1 - 1].count * (uint64_t)bytes_per_sample(files[pieces[p1 - 1].file].info));
+        const uint64_t out_floats = spans[p1 - 1].out_off + spans[p1 - 1].count;
+        if (c >= 2) AFG_HIP_CHECK(hipEventSynchronize(uploaded[b]));
+        uint8_t *hin = (uint8_t *)stage[b];
+        run_parallel(p1 - p0, [&](size_t j) {
+            const Piece &pc = pieces[p0 + j];
+            const afg_wav_span &sp = spans[p0 + j];
+            std::memcpy(hin + sp.in_off, data[which[pc.file]] + pc.src_byte,
+                        (size_t)(sp.count * (uint64_t)bytes_per_sample(files[pc.file].info)));
+        });
+        AFG_HIP_CHECK(hipMemcpyAsync(d_in[b].p, hin, (size_t)in_bytes, hipMemcpyHostToDevice, up));
+        AFG_HIP_CHECK(hipEventRecord(uploaded[b], up));
+        if (c >= 2) AFG_HIP_CHECK(hipStreamWaitEvent(up, fetched[b], 0));
+        if (int rc = afg_wav_convert_hip(p1 - p0, (const afg_wav_span *)d_spans.p + p0, tiles[c], (const uint8_t *)d_in[b].p, in_bytes,
+                                         (float *)d_out[b].p, (out_floats + 3) & ~(uint64_t)3, up))
+            return rc;
+        AFG_HIP_CHECK(hipEventRecord(converted[b], up));
+        AFG_HIP_CHECK(hipStreamWaitEvent(down, converted[b], 0));
+        AFG_HIP_CHECK(hipMemcpyAsync((float *)pcm + chunk_out0[c], d_out[b].p, (size_t)out_floats * sizeof(float), hipMemcpyDeviceToHost, down));
+        AFG_HIP_CHECK(hipEventRecord(fetched[b], down));
+    }
+    AFG_HIP_CHECK(hipStreamSynchronize(down));
+    AFG_HIP_CHECK(hipStreamSynchronize(up));
+    for (size_t k = 0; k < files.size(); k++) {
+        const File &f = files[k];
+        if (!f.ok) continue;
+        afg_batch_item &it = items[which[k]];
+        it.frames = (int64_t)f.info.frames;
+        it.pcm = f.info.frames ? (float *)pcm + f.out_off : nullptr;
+    }
+    keep = pcm_owner;
+    return AFG_OK;
+}
+
+}  // namespace afg_wav

@@ -372,6 +372,20 @@ int afg_xm_render_hip(uint n_songs, const(afg_xm_song)* d_songs, const(afg_xm_se
                       void* hip_stream);
 int afg_xm_parse(const(ubyte)* data, size_t length, afg_xm_parsed* parsed);
 void afg_xm_parsed_free(afg_xm_parsed* parsed);
+// WAV (afg.h): span records of the device conversion, the host front-end
+enum { AFG_WAV_KIND_U8 = 0, AFG_WAV_KIND_S16 = 1, AFG_WAV_KIND_S24 = 2, AFG_WAV_KIND_S32 = 3, AFG_WAV_KIND_F32 = 4, AFG_WAV_KIND_F64 = 5 }
+enum AFG_WAV_TILE_SAMPLES = 4096;
+struct afg_wav_span { ulong in_off, out_off, count, tile_first; uint kind, pad; }
+struct afg_wav_parsed
+{
+    uint tag, channels, bits, sample_rate, frames;
+    int kind;
+    ulong samples_offset, present_samples;
+}
+ulong afg_wav_layout(afg_wav_span* spans, ulong n_spans);
+int afg_wav_convert_hip(ulong n_spans, const(afg_wav_span)* d_spans, ulong n_tiles, const(ubyte)* d_in, ulong in_bytes,
+                        float* d_out, ulong out_floats, void* hip_stream);
+int afg_wav_parse(const(ubyte)* data, size_t length, afg_wav_parsed* parsed);
 int afg_is_module(const(afg_stream)* s);
 int afg_module_pattern_count(const(afg_stream)* s);
 int afg_module_length(const(afg_stream)* s);

@@ -371,14 +371,15 @@ int afg_opus_output_gain_hip(uint64_t n_samples, const float *d_in, float gain, 
  *  Outer surface: the AudioStream subset (stream.d:102-637) over the host front-ends
  *  -- FLAC (native container, drflac.d:680-1695, :1887-2153), QOA (qoa.d:413-486, :703-851), MP3 Layer I / II / III
  *  (minimp3.d, minimp3_ex.d), Ogg Vorbis (stb_vorbis2.d) and Ogg Opus with CELT-only packets (dopus.d; a file that holds
- *  SILK / hybrid packets is refused at open with this library's own message), ProTracker MOD (pocketmod.d: below) and
- *  FastTracker II XM (libxm.d: below).  WAV reports "unrecognized encoding".  Like the reference the stream decodes as the caller pulls:
+ *  SILK / hybrid packets is refused at open with this library's own message), ProTracker MOD (pocketmod.d: below) ,
+ *  FastTracker II XM (libxm.d: below) and WAV (wav.d: below; probed after FLAC and before QOA, stream.d:1638-1655).  Like the reference the stream decodes as the caller pulls:
  *  afg_open_from_memory parses the container only, a read that finds the FIFO empty decodes the next chunk (64 MP3 frames /
  *  Vorbis or Opus packets, 16 FLAC or QOA frames) on the device; afg_batch_decode parses whole files into transform-stage
  *  records and decodes them in one pass.  A MOD stream has no FIFO: each read runs the module's control layer on the host
  *  up to the read's end and mixes exactly those frames on the device (pocketmod_render(..., frames * 8), stream.d:611-620),
  *  so a read stops early at every pattern boundary, as the reference's does, and the first read after the song has come
- *  back to an order index it already played returns 0.
+ *  back to an order index it already played returns 0.  A WAV stream converts its sample bytes on the device, a chunk of
+ *  about 2^18 samples at a time; a read that needs a sample the file does not hold returns 0 and sets the error state.
  * ========================================================================== */
 
 typedef enum afg_format {          /* AudioFileFormat, stream.d:36-47 */
@@ -406,7 +407,8 @@ int         afg_read_samples_float(afg_stream *s, float *out, int frames);
  * [0, length] fails and leaves the position alone (the invariants of examples/transcode's additionalTests). */
 int         afg_can_seek(const afg_stream *s);
 int         afg_seek_position(afg_stream *s, int frame);     /* 1 = done, 0 = refused */
-int         afg_tell_position(const afg_stream *s);          /* -1 on an invalid stream */
+int         afg_tell_position(const afg_stream *s);          /* -1 on an invalid stream (a WAV stream whose read failed
+                                                                 * still tells: see the WAV section) */
 void        afg_close(afg_stream *s);
 
 /* Host front-ends on their own (no device needed): what the stream and batch entry points run
@@ -781,6 +783,57 @@ int afg_module_rows_in_pattern(const afg_stream *s, int pattern);   /* 64 */
 int afg_module_tell_pattern(const afg_stream *s);
 int afg_module_tell_row(const afg_stream *s);
 int afg_module_seek(afg_stream *s, int pattern, int row);    /* 1 = done */
+
+/* ========================================================================== *
+ *  WAV (wav.d:21-358; stream.d:557-570, :1197-1199, :1249-1251, :1638-1655): RIFF/WAVE with PCM of 8 / 16 / 24 / 32 bits
+ *  or IEEE float of 32 / 64 bits, any channel count up to 65535, length = the frames the 'data' chunk declares.
+ *  The host walks the chunks the way WAVDecoder.scan does (afg_wav_parse; its habits and the two refusals that are this
+ *  library's own are listed in INTEGRATION.md); the device converts the sample bytes, as they are in the file, to
+ *  float32 with readSamples!float's arithmetic (afg_wav_convert_hip), bit-identical; f64 NaNs stay NaNs.
+ *  Stream: afg_seek_position(frame) succeeds for 0 <= frame <= length; a read returns min(frames, length - position)
+ *  frames; when the file does not hold all the samples of that read (a 'data' chunk cut short), or the format is one the
+ *  scan lets through and readSamples refuses (PCM of 64 bits, float of 8 / 16 / 24), the read returns 0 and the stream
+ *  is in error state with the reference's decoding-error message.  As in the reference (wav.d:253) the position has
+ *  advanced by the clamped request all the same, and afg_tell_position still reports it.
+ *  Batch: one read of the whole declared length; a file for which that read fails is an error item (AFG_ERR_INVALID,
+ *  the decoding-error message, format AFG_FORMAT_WAV).
+ * ========================================================================== */
+#define AFG_WAV_KIND_U8   0      /* (b - 128) / 127.0           wav.d:297 */
+#define AFG_WAV_KIND_S16  1      /* s / 32767.0                 wav.d:307 */
+#define AFG_WAV_KIND_S24  2      /* sign-extended / 8388607.0   wav.d:318-319 */
+#define AFG_WAV_KIND_S32  3      /* s / 2147483648.0            wav.d:329 */
+#define AFG_WAV_KIND_F32  4      /* the bits as they are        wav.d:266-269 */
+#define AFG_WAV_KIND_F64  5      /* narrowed to float           wav.d:276-279 */
+#define AFG_WAV_TILE_SAMPLES 4096u
+
+typedef struct afg_wav_span {      /* a run of samples of one kind (40 bytes) */
+    uint64_t in_off;               /* first byte in d_in; 16-byte aligned for the fast path (any offset is converted) */
+    uint64_t out_off;              /* first float in d_out; a multiple of 4 for the fast path */
+    uint64_t count;                /* samples (little-endian, interleaved as in the file) */
+    uint64_t tile_first;           /* first tile of the span in the launch: afg_wav_layout fills it in */
+    uint32_t kind;                 /* AFG_WAV_KIND_* */
+    uint32_t pad;
+} afg_wav_span;
+
+/* Host: gives every span its tiles of AFG_WAV_TILE_SAMPLES samples (tile_first) and returns the launch's tile count. */
+uint64_t afg_wav_layout(afg_wav_span *spans, uint64_t n_spans);
+/* Converts every span in one launch, one workgroup per tile.  d_spans is the device copy of spans laid out by
+ * afg_wav_layout, n_tiles what it returned.  A span that does not lie inside [0, in_bytes) / [0, out_floats) is not
+ * converted at all.  Input and output must not overlap. */
+int afg_wav_convert_hip(uint64_t n_spans, const afg_wav_span *d_spans, uint64_t n_tiles, const uint8_t *d_in, uint64_t in_bytes,
+                        float *d_out, uint64_t out_floats, void *hip_stream);
+
+/* Host front-end on its own (no device needed): WAVDecoder.scan.  AFG_ERR_UNSUPPORTED: the scan refuses the file
+ * (afg_last_error carries the reference's reason). */
+typedef struct afg_wav_parsed {
+    uint32_t tag;                  /* 1 PCM, 3 IEEE float (an extensible header with the float GUID has become 3) */
+    uint32_t channels, bits, sample_rate;
+    uint32_t frames;               /* declared by the 'data' chunk */
+    int32_t  kind;                 /* AFG_WAV_KIND_*, or -1: opens, and the first read fails */
+    uint64_t samples_offset;       /* byte offset of the first sample */
+    uint64_t present_samples;      /* whole samples the file holds from there, at most frames * channels */
+} afg_wav_parsed;
+int afg_wav_parse(const uint8_t *data, size_t length, afg_wav_parsed *out);
 
 /* Streaming device-to-device copy (16-byte aligned) used by bench.py to measure the copy rate this device
  * actually sustains, the practical ceiling the HBM-bound kernels are compared with next to the 8 TB/s spec. */

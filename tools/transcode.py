@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""transcode [--format s24|s16|s8|f32] [--no-dither | --dither-seed N] input.{mp3|flac|ogg|qoa|mod|xm} output.{wav|qoa}
+"""transcode [--format s24|s16|s8|f32] [--no-dither | --dither-seed N] input.{mp3|flac|ogg|qoa|mod|xm|wav} output.{wav|qoa}
 
 The reference's examples/transcode flow (main.d:12-84) over the device library: open, report format / rate /
 channels / length, read 1024-frame chunks, write them out with the library's own writers (afg_wav_encode[_dithered] /
@@ -27,7 +27,7 @@ def lcg(seed):
 
 def main(argv):
     import argparse
-    ap = argparse.ArgumentParser(prog="transcode", usage="transcode [options] input.{mp3|flac|ogg|qoa|mod|xm} output.{wav|qoa}")
+    ap = argparse.ArgumentParser(prog="transcode", usage="transcode [options] input.{mp3|flac|ogg|qoa|mod|xm|wav} output.{wav|qoa}")
     ap.add_argument("--format", default="s24", choices=["s24", "s16", "s8", "f32"])
     ap.add_argument("--no-dither", action="store_true")
     ap.add_argument("--dither-seed", type=int, default=None)
