@@ -48,6 +48,12 @@ QOA_ENC_STREAM_DTYPE = np.dtype([("pcm_off", np.uint64), ("out_off", np.uint64),
                                  ("samplerate", np.uint32), ("channels", np.uint8), ("pad", np.uint8, 7)])
 assert QOA_ENC_STREAM_DTYPE.itemsize == 32
 WAV_S8, WAV_S16LE, WAV_S24LE, WAV_FP32LE, WAV_FP64LE = range(5)
+WAV_FORMAT_BYTES = (1, 2, 3, 4, 8)
+DITHER_OFF, DITHER_LIBC, DITHER_LCG31 = range(3)
+WAV_PACK_SPAN_DTYPE = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), ("count", np.uint64), ("first_tile", np.uint64),
+                                ("draw0", np.uint64), ("seed", np.uint32), ("format", np.uint8), ("dither", np.uint8),
+                                ("pad", np.uint8, (2,))])
+assert WAV_PACK_SPAN_DTYPE.itemsize == 48
 
 # every symbol include/afg.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -75,6 +81,10 @@ ABI_SYMBOLS = [
     "afg_module_length", "afg_module_rows_in_pattern", "afg_module_tell_pattern", "afg_module_tell_row", "afg_module_seek",
     "afg_xm_render_hip", "afg_xm_parse", "afg_xm_parsed_free",
     "afg_wav_layout", "afg_wav_convert_hip", "afg_wav_parse",
+    "afg_lcg31_jump", "afg_wav_pack_layout", "afg_wav_pack_hip",
+    "afg_open_to_buffer", "afg_open_to_memory", "afg_is_open_for_reading", "afg_is_open_for_writing",
+    "afg_write_samples_float", "afg_write_samples_double", "afg_finalize_encoding", "afg_finalize_and_get_encoded",
+    "afg_batch_encode", "afg_encode_free",
 ]
 
 
@@ -195,6 +205,23 @@ class BatchItem(C.Structure):
 
 class BatchOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_threads", C.c_int), ("n_devices", C.c_int), ("devices", C.POINTER(C.c_int))]
+
+
+class EncodingOptions(C.Structure):
+    """afg_encoding_options (EncodingOptions, stream.d:59-67)."""
+    _fields_ = [("struct_size", C.c_uint32), ("sample_format", C.c_int), ("dither", C.c_int), ("dither_seed", C.c_uint32)]
+
+
+class EncodeInput(C.Structure):
+    _fields_ = [("pcm", C.c_void_p), ("frames", C.c_uint64), ("channels", C.c_uint32), ("samplerate", C.c_float)]
+
+
+class EncodedItem(C.Structure):
+    _fields_ = [("status", C.c_int), ("message", C.c_char_p), ("bytes", C.POINTER(C.c_uint8)), ("size", C.c_uint64)]
+
+
+class EncodeResult(C.Structure):
+    _fields_ = [("n_files", C.c_int), ("items", C.POINTER(EncodedItem)), ("owner", C.c_void_p)]
 
 
 class BatchResult(C.Structure):
@@ -364,6 +391,25 @@ def lib():
         fn.argtypes = [vp]
     L.afg_module_rows_in_pattern.argtypes = [vp, C.c_int]
     L.afg_module_seek.argtypes = [vp, C.c_int, C.c_int]
+    L.afg_lcg31_jump.argtypes = [u32, u64]
+    L.afg_lcg31_jump.restype = u32
+    L.afg_wav_pack_layout.argtypes = [vp, u64]
+    L.afg_wav_pack_layout.restype = u64
+    L.afg_wav_pack_hip.argtypes = [u64, vp, u64, vp, u64, vp, u64, vp]
+    L.afg_open_to_buffer.argtypes = [C.c_int, C.c_float, C.c_int, C.POINTER(EncodingOptions)]
+    L.afg_open_to_buffer.restype = vp
+    L.afg_open_to_memory.argtypes = [vp, C.c_size_t, C.c_int, C.c_float, C.c_int, C.POINTER(EncodingOptions)]
+    L.afg_open_to_memory.restype = vp
+    L.afg_is_open_for_reading.argtypes = [vp]
+    L.afg_is_open_for_writing.argtypes = [vp]
+    L.afg_write_samples_float.argtypes = [vp, vp, C.c_int]
+    L.afg_write_samples_double.argtypes = [vp, vp, C.c_int]
+    L.afg_finalize_encoding.argtypes = [vp]
+    L.afg_finalize_and_get_encoded.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
+    L.afg_batch_encode.argtypes = [C.POINTER(EncodeInput), C.c_int, C.c_int, C.POINTER(EncodingOptions), C.c_int,
+                                   C.POINTER(EncodeResult)]
+    L.afg_encode_free.argtypes = [C.POINTER(EncodeResult)]
+    L.afg_encode_free.restype = None
     _lib = L
     _sync_dev_options(L)
     return L
@@ -867,9 +913,62 @@ def wav_convert(n_spans, d_spans, n_tiles, d_in, in_bytes, d_out, out_floats, st
                                     int(out_floats), _stream(stream)))
 
 
+def lcg31_jump(seed, n_draws):
+    """afg_lcg31_jump: state of the dither generator after n_draws steps from seed.  Needs no device."""
+    return int(lib().afg_lcg31_jump(int(seed) & 0xffffffff, int(n_draws)))
+
+
+def wav_pack_layout(spans):
+    """afg_wav_pack_layout: fills first_tile of a WAV_PACK_SPAN_DTYPE array in place; returns the launch's tile count."""
+    assert spans.dtype == WAV_PACK_SPAN_DTYPE and spans.flags.c_contiguous
+    return int(lib().afg_wav_pack_layout(spans.ctypes.data, len(spans)))
+
+
+def wav_pack(n_spans, d_spans, n_tiles, d_in, in_floats, d_out, out_bytes, stream=None):
+    """Enqueue the WAV sample packing (afg_wav_pack_hip) on device arrays."""
+    check(lib().afg_wav_pack_hip(int(n_spans), _ptr(d_spans), int(n_tiles), _ptr(d_in), int(in_floats), _ptr(d_out),
+                                 int(out_bytes), _stream(stream)))
+
+
+def encoding_options(sample_format=WAV_FP32LE, dither=DITHER_LIBC, dither_seed=0):
+    return EncodingOptions(C.sizeof(EncodingOptions), int(sample_format), int(dither), int(dither_seed) & 0xffffffff)
+
+
+def batch_encode(inputs, fmt=FORMAT_WAV, options=None, n_threads=0):
+    """afg_batch_encode: inputs = [(float32 array [frames, channels] or [frames], samplerate), ...]; an input may also be a
+    dict(pcm=, frames=, channels=, samplerate=) to describe an item as it is (pcm None = NULL).  Returns a list of dicts
+    (status, message, bytes: the file as a bytes object, None on error)."""
+    n = len(inputs)
+    arr = (EncodeInput * max(n, 1))()
+    keep = []
+    for i, item in enumerate(inputs):
+        if isinstance(item, dict):
+            x = None if item.get("pcm") is None else np.ascontiguousarray(item["pcm"], np.float32)
+            frames, ch, rate = item["frames"], item["channels"], item["samplerate"]
+        else:
+            x, rate = item
+            x = np.ascontiguousarray(x, np.float32)
+            if x.ndim == 1:
+                x = x[:, None]
+            frames, ch = x.shape
+        keep.append(x)
+        arr[i] = EncodeInput(None if x is None else x.ctypes.data, int(frames), int(ch), float(rate))
+    res = EncodeResult()
+    check(lib().afg_batch_encode(arr, n, int(fmt), None if options is None else C.byref(options), int(n_threads), C.byref(res)))
+    try:
+        out = []
+        for i in range(res.n_files):
+            it = res.items[i]
+            out.append({"status": it.status, "message": None if it.message is None else it.message.decode(),
+                        "bytes": C.string_at(it.bytes, it.size) if it.status == 0 else None})
+        return out
+    finally:
+        lib().afg_encode_free(C.byref(res))
+
+
 class AudioStream:
-    """The reading half of the reference's AudioStream (stream.d:102-637) over afg_open_from_memory: same method
-    names, same never-throw / error-state contract (stream.d:31-33)."""
+    """The reference's AudioStream (stream.d:102-902) over afg_open_from_memory and afg_open_to_buffer / _to_memory:
+    same method names, same never-throw / error-state contract (stream.d:31-33)."""
 
     def __init__(self):
         self._h = None
@@ -879,6 +978,48 @@ class AudioStream:
         self.cleanUp()
         self._keep = bytes(data)
         self._h = lib().afg_open_from_memory(self._keep, len(self._keep))
+
+    def openToBuffer(self, fmt, samplerate, channels, options=None):
+        """options: encoding_options(...) or None for the reference's defaults."""
+        self.cleanUp()
+        self._h = lib().afg_open_to_buffer(int(fmt), float(samplerate), int(channels), None if options is None else C.byref(options))
+
+    def openToMemory(self, out, fmt, samplerate, channels, options=None):
+        """out: a writable uint8 numpy array the file is written into; it must outlive the stream."""
+        self.cleanUp()
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable
+        self._keep = out
+        self._h = lib().afg_open_to_memory(out.ctypes.data, out.size, int(fmt), float(samplerate), int(channels),
+                                           None if options is None else C.byref(options))
+
+    def isOpenForReading(self):
+        return bool(lib().afg_is_open_for_reading(self._h))
+
+    def isOpenForWriting(self):
+        return bool(lib().afg_is_open_for_writing(self._h))
+
+    def _write(self, fn, data, dtype, frames):
+        x = np.ascontiguousarray(data, dtype)
+        if frames is None:
+            frames = x.shape[0] if x.ndim == 2 else x.size // max(1, self.getNumChannels())
+        return int(fn(self._h, x.ctypes.data, int(frames)))
+
+    def writeSamplesFloat(self, data, frames=None):
+        """data: float32 [frames, channels] or interleaved; returns the frames written."""
+        return self._write(lib().afg_write_samples_float, data, np.float32, frames)
+
+    def writeSamplesDouble(self, data, frames=None):
+        return self._write(lib().afg_write_samples_double, data, np.float64, frames)
+
+    def finalizeEncoding(self):
+        return bool(lib().afg_finalize_encoding(self._h))
+
+    def finalizeAndGetEncodedResult(self):
+        """The encoded file of a buffer stream as bytes (may be called again); None when it failed."""
+        p, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+        if not lib().afg_finalize_and_get_encoded(self._h, C.byref(p), C.byref(n)):
+            return None
+        return C.string_at(p, n.value)
 
     def cleanUp(self):
         if self._h:

@@ -1,0 +1,344 @@
+// afg_encode_stage.cpp -- afg_batch_encode: interleaved float PCM in host memory to WAV or QOA files in host memory.
+//
+// Built like the WAV stage of the batch decoder (afg_wav_stage.cpp) turned round: helper threads copy the PCM into leased
+// page-locked staging (that copy puts every piece on a 4-float boundary), chunks go through two stagings and two pairs of
+// device buffers with upload, kernel and download on the kept stream pair, and the bytes come back into one page-locked
+// plane that the items point into.  The plane has the device buffers' layout, so a chunk is one download: a WAV file
+// starts 4 bytes past a 16-byte boundary, which puts its samples -- 44 bytes on -- on one; headers are written by the
+// host once the last chunk is back.
+// WAV: one afg_wav_pack_hip launch per chunk, whatever it holds; a long file is cut at tile boundaries and draw0 carries
+// its dither position across the cuts.  QOA: afg_qoa_encode_hip over the streams of a chunk; the encoder's LMS state runs
+// through a stream, so a file is never cut.
+#include "afg_mod_front.h"
+#include "afg_write_stream.h"
+#include "../csrc/afg_common.h"
+
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <vector>
+
+namespace afg_front {
+// page-locked staging and the kept stream pair (afg_host.cpp)
+std::shared_ptr<void> staging_lease(size_t bytes, void **p);
+hipError_t streams_take(hipStream_t *up, hipStream_t *down);
+void streams_give(hipStream_t up, hipStream_t down);
+}  // namespace afg_front
+
+namespace {
+
+const char *const kMessageChannels = "Encoder: unsupported channel count";
+const char *const kMessageRate = "Encoder: sample rate out of range";
+const char *const kMessageNoPcm = "Encoder: no samples given";
+const char *const kMessageTooLong = "Encoder: too many frames for the format";
+
+constexpr uint64_t kChunkSamples = (uint64_t)8 << 20;          // a chunk: 32 MB of floats up, 8-64 MB of file bytes down
+static_assert(kChunkSamples % AFG_WAV_TILE_SAMPLES == 0, "files are cut at tile boundaries");
+constexpr uint64_t kWavHeader = 44;
+
+uint64_t align16(uint64_t n) { return (n + 15) & ~(uint64_t)15; }
+int sample_size(int format) { return format == AFG_WAV_S8 ? 1 : format == AFG_WAV_S16LE ? 2 : format == AFG_WAV_S24LE ? 3 : format == AFG_WAV_FP32LE ? 4 : 8; }
+
+struct EncodeOwner {
+    std::vector<afg_encoded_item> items;
+    std::shared_ptr<void> plane;
+};
+
+struct File {
+    bool ok = false;
+    uint32_t rate = 0;
+    uint64_t count = 0;        // samples
+    uint64_t at = 0;           // first byte of the file in the plane
+    uint64_t size = 0;
+};
+
+// a piece of one file inside a chunk: `src` is its first sample in the file's PCM, `in_off` / `count` its place in the staging
+struct Piece { size_t file; uint64_t src, in_off, count; };
+
+struct Pair {
+    hipStream_t up = nullptr, down = nullptr;
+    ~Pair()
+    {
+        for (hipStream_t st : { up, down }) if (st) (void)hipStreamSynchronize(st);
+        if (up && down) afg_front::streams_give(up, down);
+    }
+};
+struct Events {
+    hipEvent_t e[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    ~Events() { for (hipEvent_t ev : e) if (ev) (void)hipEventDestroy(ev); }
+};
+
+// The pipeline both formats share.  Chunk c owns pieces [first[c], first[c + 1]), uploads in_floats[c] floats, runs
+// launch(c, d_in, d_out, stream) and brings out_bytes[c] bytes back to plane + plane_at[c].
+template <typename Launch>
+int run_chunks(const afg_encode_input *in, int n_threads, const std::vector<Piece> &pieces, const std::vector<size_t> &first,
+               const std::vector<uint64_t> &in_floats, const std::vector<uint64_t> &out_bytes, const std::vector<uint64_t> &plane_at,
+               uint8_t *plane, const Launch &launch)
+{
+    const size_t C = first.size() - 1;
+    const int bufs = C > 1 ? 2 : 1;
+    const uint64_t max_in = std::max<uint64_t>(4, *std::max_element(in_floats.begin(), in_floats.end()));
+    const uint64_t max_out = std::max<uint64_t>(16, *std::max_element(out_bytes.begin(), out_bytes.end()));
+    void *stage[2] = { nullptr, nullptr };
+    std::shared_ptr<void> stage_owner[2];
+    afg_mod::DevBuf d_in[2], d_out[2];
+    for (int b = 0; b < bufs; b++) {
+        if (!(stage_owner[b] = afg_front::staging_lease((size_t)max_in * sizeof(float), &stage[b]))) return AFG_ERR_OOM;
+        if (int rc = d_in[b].alloc((size_t)max_in * sizeof(float))) return rc;
+        if (int rc = d_out[b].alloc((size_t)align16(max_out))) return rc;
+    }
+    Pair pair;                                           // the kept upload / download pair, given back drained on every way out
+    AFG_HIP_CHECK(afg_front::streams_take(&pair.up, &pair.down));
+    hipStream_t up = pair.up, down = pair.down;
+    // rings of two: chunk c's staging is free once chunk c - 2 has gone up (the host waits), its output buffer once
+    // chunk c - 2 has come back (the upload stream waits)
+    Events ev;
+    for (hipEvent_t &e : ev.e) AFG_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    hipEvent_t *uploaded = ev.e, *packed = ev.e + 2, *fetched = ev.e + 4;
+    for (size_t c = 0; c < C; c++) {
+        const int b = (int)(c & 1);
+        const size_t p0 = first[c], p1 = first[c + 1];
+        if (c >= 2) AFG_HIP_CHECK(hipEventSynchronize(uploaded[b]));
+        float *hin = (float *)stage[b];
+        afg_front::parallel_run(p1 - p0, n_threads, [&](size_t j) {
+            const Piece &pc = pieces[p0 + j];
+            if (pc.count) std::memcpy(hin + pc.in_off, in[pc.file].pcm + pc.src, (size_t)pc.count * sizeof(float));
+        });
+        if (in_floats[c]) AFG_HIP_CHECK(hipMemcpyAsync(d_in[b].p, hin, (size_t)in_floats[c] * sizeof(float), hipMemcpyHostToDevice, up));
+        AFG_HIP_CHECK(hipEventRecord(uploaded[b], up));
+        if (c >= 2) AFG_HIP_CHECK(hipStreamWaitEvent(up, fetched[b], 0));
+        if (int rc = launch(c, (const float *)d_in[b].p, (uint8_t *)d_out[b].p, up)) return rc;
+        AFG_HIP_CHECK(hipEventRecord(packed[b], up));
+        AFG_HIP_CHECK(hipStreamWaitEvent(down, packed[b], 0));
+        if (out_bytes[c]) AFG_HIP_CHECK(hipMemcpyAsync(plane + plane_at[c], d_out[b].p, (size_t)out_bytes[c], hipMemcpyDeviceToHost, down));
+        AFG_HIP_CHECK(hipEventRecord(fetched[b], down));
+    }
+    AFG_HIP_CHECK(hipStreamSynchronize(down));
+    AFG_HIP_CHECK(hipStreamSynchronize(up));
+    return AFG_OK;
+}
+
+void wav_header(uint8_t *p, uint64_t frames, uint32_t channels, uint32_t rate, int format)
+{
+    // afg_wav.cpp's header, through the host writer itself: a file of no frames is the header alone, the two lengths follow
+    (void)afg_wav_encode(nullptr, 0, channels, rate, format, p, kWavHeader);
+    const uint64_t data_bytes = (uint64_t)((uint32_t)sample_size(format) * channels) * frames;
+    const uint32_t riff = (uint32_t)(4 + (4 + 4 + 16) + (4 + 4 + data_bytes)), data = (uint32_t)data_bytes;
+    std::memcpy(p + 4, &riff, 4);                       // (little-endian hosts only, like the rest of the library)
+    std::memcpy(p + 40, &data, 4);
+}
+
+int encode_wav(const afg_encode_input *in, int n_threads, std::vector<File> &files, int sample_format, bool dither, uint32_t seed,
+               EncodeOwner &owner)
+{
+    const uint64_t B = (uint64_t)sample_size(sample_format);
+    std::vector<Piece> pieces;
+    std::vector<afg_wav_pack_span> spans;                // chunk-relative offsets
+    std::vector<size_t> first{ 0 };
+    std::vector<uint64_t> in_floats, out_bytes, plane_at, tiles;
+    uint64_t plane_bytes = 0, in_at = 0, chunk_samples = 0, chunk_at = 0, chunk_end = 0;
+    auto close_chunk = [&] {
+        if (first.back() == pieces.size()) return;
+        first.push_back(pieces.size());
+        in_floats.push_back(in_at);
+        out_bytes.push_back(chunk_end - chunk_at);
+        plane_at.push_back(chunk_at);
+        in_at = 0; chunk_samples = 0;
+    };
+    for (size_t k = 0; k < files.size(); k++) {
+        File &f = files[k];
+        if (!f.ok) continue;
+        const uint64_t data_at = align16(plane_bytes + kWavHeader);        // the samples start on a 16-byte boundary
+        f.at = data_at - kWavHeader;
+        f.size = kWavHeader + f.count * B;
+        plane_bytes = data_at + f.count * B;
+        for (uint64_t done = 0; done < f.count;) {
+            if (kChunkSamples - chunk_samples < AFG_WAV_TILE_SAMPLES) close_chunk();
+            const uint64_t room = (kChunkSamples - chunk_samples) & ~(uint64_t)(AFG_WAV_TILE_SAMPLES - 1);
+            const uint64_t take = std::min(f.count - done, room);
+            if (first.back() == pieces.size()) chunk_at = data_at + done * B;     // (done is a multiple of the tile: aligned)
+            afg_wav_pack_span sp;
+            std::memset(&sp, 0, sizeof(sp));
+            sp.in_off = in_at;
+            sp.out_off = data_at + done * B - chunk_at;
+            sp.count = take;
+            sp.draw0 = 2 * done;
+            sp.seed = seed;
+            sp.format = (uint8_t)sample_format;
+            sp.dither = dither ? 1 : 0;
+            spans.push_back(sp);
+            pieces.push_back({ k, done, in_at, take });
+            in_at += (take + 3) & ~(uint64_t)3;
+            chunk_samples += take;
+            chunk_end = data_at + (done + take) * B;
+            done += take;
+        }
+    }
+    close_chunk();
+    void *plane = nullptr;
+    owner.plane = afg_front::staging_lease((size_t)std::max<uint64_t>(plane_bytes, 16), &plane);
+    if (!owner.plane) return AFG_ERR_OOM;
+    if (!pieces.empty()) {
+        const size_t C = first.size() - 1;
+        tiles.resize(C);
+        for (size_t c = 0; c < C; c++) tiles[c] = afg_wav_pack_layout(spans.data() + first[c], first[c + 1] - first[c]);
+        afg_mod::DevBuf d_spans;
+        if (int rc = d_spans.alloc(spans.size() * sizeof(afg_wav_pack_span))) return rc;
+        // (synchronous: the table is in place before the pipeline's streams start)
+        AFG_HIP_CHECK(hipMemcpy(d_spans.p, spans.data(), spans.size() * sizeof(afg_wav_pack_span), hipMemcpyHostToDevice));
+        const int rc = run_chunks(in, n_threads, pieces, first, in_floats, out_bytes, plane_at, (uint8_t *)plane,
+                                  [&](size_t c, const float *d_in, uint8_t *d_out, hipStream_t st) {
+                                      return afg_wav_pack_hip(first[c + 1] - first[c], (const afg_wav_pack_span *)d_spans.p + first[c], tiles[c],
+                                                              d_in, in_floats[c], d_out, align16(out_bytes[c]), st);
+                                  });
+        if (rc) return rc;
+    }
+    afg_front::parallel_run(files.size(), n_threads, [&](size_t k) {
+        const File &f = files[k];
+        if (!f.ok) return;
+        wav_header((uint8_t *)plane + f.at, in[k].frames, in[k].channels, f.rate, sample_format);
+        owner.items[k].bytes = (uint8_t *)plane + f.at;
+        owner.items[k].size = f.size;
+    });
+    return AFG_OK;
+}
+
+int encode_qoa(const afg_encode_input *in, int n_threads, std::vector<File> &files, EncodeOwner &owner)
+{
+    std::vector<Piece> pieces;
+    std::vector<afg_qoa_enc_stream> recs;                // chunk-relative offsets
+    std::vector<size_t> first{ 0 };
+    std::vector<uint64_t> in_floats, out_bytes, plane_at;
+    uint64_t plane_bytes = 0, in_at = 0, chunk_at = 0;
+    auto close_chunk = [&] {
+        if (first.back() == pieces.size()) return;
+        first.push_back(pieces.size());
+        in_floats.push_back(in_at);
+        out_bytes.push_back(plane_bytes - chunk_at);
+        plane_at.push_back(chunk_at);
+        in_at = 0;
+    };
+    for (size_t k = 0; k < files.size(); k++) {
+        File &f = files[k];
+        if (!f.ok) continue;
+        if (in_at && in_at + f.count > kChunkSamples) close_chunk();
+        plane_bytes = (plane_bytes + 7) & ~(uint64_t)7;
+        if (first.back() == pieces.size()) chunk_at = plane_bytes;
+        f.at = plane_bytes;
+        f.size = afg_qoa_encoded_size((uint32_t)in[k].frames, in[k].channels);
+        afg_qoa_enc_stream r;
+        std::memset(&r, 0, sizeof(r));
+        r.pcm_off = in_at;
+        r.out_off = f.at - chunk_at;
+        r.samples = (uint32_t)in[k].frames;
+        r.samplerate = f.rate;
+        r.channels = (uint8_t)in[k].channels;
+        recs.push_back(r);
+        pieces.push_back({ k, 0, in_at, f.count });
+        in_at += (f.count + 3) & ~(uint64_t)3;
+        plane_bytes += f.size;
+    }
+    close_chunk();
+    void *plane = nullptr;
+    owner.plane = afg_front::staging_lease((size_t)std::max<uint64_t>(plane_bytes, 16), &plane);
+    if (!owner.plane) return AFG_ERR_OOM;
+    if (!pieces.empty()) {
+        afg_mod::DevBuf d_recs;
+        if (int rc = d_recs.alloc(recs.size() * sizeof(afg_qoa_enc_stream))) return rc;
+        AFG_HIP_CHECK(hipMemcpy(d_recs.p, recs.data(), recs.size() * sizeof(afg_qoa_enc_stream), hipMemcpyHostToDevice));
+        const int rc = run_chunks(in, n_threads, pieces, first, in_floats, out_bytes, plane_at, (uint8_t *)plane,
+                                  [&](size_t c, const float *d_in, uint8_t *d_out, hipStream_t st) {
+                                      return afg_qoa_encode_hip((uint32_t)(first[c + 1] - first[c]), (const afg_qoa_enc_stream *)d_recs.p + first[c],
+                                                                nullptr, d_in, d_out, st);
+                                  });
+        if (rc) return rc;
+    }
+    for (size_t k = 0; k < files.size(); k++) {
+        if (!files[k].ok) continue;
+        owner.items[k].bytes = (uint8_t *)plane + files[k].at;
+        owner.items[k].size = files[k].size;
+    }
+    return AFG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int afg_batch_encode(const afg_encode_input *in, int n_files, int format, const afg_encoding_options *opts, int n_threads,
+                     afg_encode_result *out)
+{
+    if (out) { out->n_files = 0; out->items = nullptr; out->owner = nullptr; }
+    if (!out || n_files < 0 || (n_files > 0 && !in) || n_threads < 0) {
+        afg::set_error("afg_batch_encode: bad arguments");
+        return AFG_ERR_INVALID;
+    }
+    if (opts && opts->struct_size != sizeof(afg_encoding_options)) {
+        afg::set_error("afg_batch_encode: afg_encoding_options.struct_size does not match this library");
+        return AFG_ERR_INVALID;
+    }
+    if (format != AFG_FORMAT_WAV && format != AFG_FORMAT_QOA) {
+        afg::set_error("afg_batch_encode: only WAV and QOA are written");
+        return AFG_ERR_UNSUPPORTED;
+    }
+    const int sample_format = opts ? opts->sample_format : AFG_WAV_FP32LE;
+    const int dither = opts ? opts->dither : AFG_DITHER_LIBC;
+    const bool wav = format == AFG_FORMAT_WAV, integer = sample_format <= AFG_WAV_S24LE;
+    if (wav && (sample_format < AFG_WAV_S8 || sample_format > AFG_WAV_FP64LE || dither < AFG_DITHER_OFF || dither > AFG_DITHER_LCG31)) {
+        afg::set_error("afg_batch_encode: unknown sample format or dither");
+        return AFG_ERR_INVALID;
+    }
+    if (wav && integer && dither == AFG_DITHER_LIBC) {
+        afg::set_error("afg_batch_encode: libc rand() dither has no defined draw order across files; use AFG_DITHER_LCG31 or AFG_DITHER_OFF");
+        return AFG_ERR_UNSUPPORTED;
+    }
+    if (int rc = afg::require_device()) return rc;
+    try {
+        std::unique_ptr<EncodeOwner> owner(new EncodeOwner);
+        owner->items.resize((size_t)n_files);
+        std::vector<File> files((size_t)n_files);
+        for (int i = 0; i < n_files; i++) {
+            afg_encoded_item &it = owner->items[(size_t)i];
+            File &f = files[(size_t)i];
+            it.status = AFG_ERR_INVALID;
+            it.bytes = nullptr;
+            it.size = 0;
+            const float biased = in[i].samplerate + 0.5f;                      // stream.d:1852
+            const bool rate_ok = wav ? (biased >= 0.0f && biased < 2147483648.0f) : (biased >= 1.0f && biased < 16777216.0f);
+            const uint64_t max_frames = ~(uint64_t)0 / 8 / std::max<uint32_t>(1, in[i].channels);
+            if (in[i].channels == 0 || in[i].channels > (wav ? 1024u : 8u)) it.message = kMessageChannels;
+            else if (!rate_ok) it.message = kMessageRate;
+            else if (!in[i].pcm && in[i].frames) it.message = kMessageNoPcm;
+            else if (in[i].frames > (wav ? max_frames : (uint64_t)0xffffffffu)) it.message = kMessageTooLong;
+            else {
+                it.status = AFG_OK;
+                it.message = nullptr;
+                f.ok = true;
+                f.rate = (uint32_t)(int)biased;
+                f.count = in[i].frames * in[i].channels;
+            }
+        }
+        const int rc = wav ? encode_wav(in, n_threads, files, sample_format, integer && dither == AFG_DITHER_LCG31, opts ? opts->dither_seed : 0, *owner)
+                           : encode_qoa(in, n_threads, files, *owner);
+        if (rc) return rc;
+        out->n_files = n_files;
+        out->items = owner->items.data();
+        out->owner = owner.release();
+        return AFG_OK;
+    } catch (const std::bad_alloc &) {
+        afg::set_error("afg_batch_encode: out of memory");
+        return AFG_ERR_OOM;
+    }
+}
+
+void afg_encode_free(afg_encode_result *r)
+{
+    if (!r) return;
+    delete (EncodeOwner *)r->owner;
+    r->n_files = 0;
+    r->items = nullptr;
+    r->owner = nullptr;
+}
+
+}  // extern "C"

@@ -17,6 +17,7 @@
 #include "afg_mp3_front.h"
 #include "afg_opus_front.h"
 #include "afg_vorbis_front.h"
+#include "afg_write_stream.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1376,6 +1377,8 @@ struct afg_stream {
     size_t fifo_at = 0;                 // floats of `fifo` already handed out
     int64_t position = 0;               // frames handed out so far (tellPosition)
     bool ended = false;                 // nothing further can be decoded
+    afg_write::Writer *writer = nullptr;    // opened for writing (afg_write_stream.cpp): nothing above is in use
+    ~afg_stream() { if (writer) afg_write::destroy(writer); }
 
     static constexpr int kMp3Frames = 64, kOggPackets = 64, kFlacFrames = 16, kQoaFrames = 16, kOpusPackets = 64;
 
@@ -1581,7 +1584,7 @@ int64_t afg_get_length_in_frames(const afg_stream *s)
 
 int afg_read_samples_float(afg_stream *s, float *out, int frames)
 {
-    if (!s || s->error || frames <= 0) return 0;
+    if (!s || s->error || s->writer || frames <= 0) return 0;
     // stream.d:498: a FLAC stream stops once the position equals the declared length (a STREAMINFO that
     // declares 0 samples therefore reads nothing); the check is made on entry only, like the reference's.
     if (s->format == AFG_FORMAT_FLAC && s->position == s->declared_frames) return 0;
@@ -1618,11 +1621,11 @@ int afg_read_samples_float(afg_stream *s, float *out, int frames)
     }
 }
 
-int afg_can_seek(const afg_stream *s) { return s && !s->error; }
+int afg_can_seek(const afg_stream *s) { return s && !s->error && !s->writer; }
 
 int afg_seek_position(afg_stream *s, int frame)
 {
-    if (!s || s->error) return 0;
+    if (!s || s->error || s->writer) return 0;
     if (s->format == AFG_FORMAT_MOD || s->format == AFG_FORMAT_XM) return 0;   // a module seeks by pattern and row (afg_module_seek; stream.d:1097)
     if (s->format == AFG_FORMAT_WAV) {                           // stream.d:1197-1199
         if (!s->wav->seek(frame)) return 0;
@@ -1668,6 +1671,8 @@ int afg_tell_position(const afg_stream *s)
 }
 
 void afg_close(afg_stream *s) { delete s; }
+int afg_is_open_for_reading(const afg_stream *s) { return s && !s->writer && s->error != kErrorNotInitialized; }   // stream.d:377-391
+int afg_is_open_for_writing(const afg_stream *s) { return s && s->writer; }
 
 // the module functions of AudioStream (stream.d:330-345, :906-1080)
 static const afg_mod::Song *module_of(const afg_stream *s) { return (s && !s->error && s->format == AFG_FORMAT_MOD && s->mod) ? &s->mod->song : nullptr; }
@@ -1709,6 +1714,27 @@ int afg_module_seek(afg_stream *s, int pattern, int row)
     s->mod->song.seek(pattern, row, 0);                 // stream.d:1075
     return 1;
 }
+
+}  // extern "C"
+
+// the handle's side of a write stream, and the helper threads for the batch encoder (afg_write_stream.h)
+namespace afg_front {
+afg_stream *stream_for_writing(afg_write::Writer *w, int format, int channels, float samplerate, const char *error)
+{
+    afg_stream *s = new (std::nothrow) afg_stream;
+    if (!s) return nullptr;
+    s->writer = w;
+    s->format = format;
+    s->channels = channels;
+    s->samplerate = samplerate;
+    s->error = error;
+    return s;
+}
+afg_write::Writer *stream_writer(const afg_stream *s) { return s ? s->writer : nullptr; }
+void stream_set_error(afg_stream *s, const char *message) { if (s) s->error = message; }
+}  // namespace afg_front
+
+extern "C" {
 
 namespace {
 struct FlacParsedOwner {
@@ -2510,6 +2536,13 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
 }
 
 }  // namespace
+
+namespace afg_front {
+void parallel_run(size_t n, int n_threads, const std::function<void(size_t)> &fn)
+{
+    parallel_for(n, n_threads > 0 ? (unsigned)n_threads : default_threads(), fn);
+}
+}  // namespace afg_front
 
 extern "C" {
 

@@ -400,6 +400,30 @@ ulong afg_wav_encode_dithered(const(float)* samples, ulong frames, uint channels
                               afg_rand_fn rng, void* rng_user, uint rng_max, ubyte* outData, ulong cap);
 void afg_batch_free(afg_batch_result* result);
 
+/// Encode side: device WAV sample packing, the writing half of AudioStream, the batch encoder (afg.h has the contracts).
+enum { AFG_DITHER_OFF = 0, AFG_DITHER_LIBC = 1, AFG_DITHER_LCG31 = 2 }
+struct afg_wav_pack_span { ulong in_off, out_off, count, first_tile, draw0; uint seed; ubyte format, dither; ubyte[2] pad; }
+uint afg_lcg31_jump(uint seed, ulong n_draws);
+ulong afg_wav_pack_layout(afg_wav_pack_span* spans, ulong n_spans);
+int afg_wav_pack_hip(ulong n_spans, const(afg_wav_pack_span)* d_spans, ulong n_tiles, const(float)* d_in, ulong in_floats,
+                     ubyte* d_out, ulong out_bytes, void* hip_stream);
+struct afg_encoding_options { uint struct_size; int sample_format; int dither; uint dither_seed; }
+afg_stream* afg_open_to_buffer(int format, float samplerate, int channels, const(afg_encoding_options)* opts);
+afg_stream* afg_open_to_memory(ubyte* data, size_t max_length, int format, float samplerate, int channels,
+                               const(afg_encoding_options)* opts);
+int afg_is_open_for_reading(const(afg_stream)* s);
+int afg_is_open_for_writing(const(afg_stream)* s);
+int afg_write_samples_float(afg_stream* s, const(float)* inData, int frames);
+int afg_write_samples_double(afg_stream* s, const(double)* inData, int frames);
+int afg_finalize_encoding(afg_stream* s);
+int afg_finalize_and_get_encoded(afg_stream* s, const(ubyte)** bytes, size_t* length);
+struct afg_encode_input { const(float)* pcm; ulong frames; uint channels; float samplerate; }
+struct afg_encoded_item { int status; const(char)* message; ubyte* bytes; ulong size; }
+struct afg_encode_result { int n_files; afg_encoded_item* items; void* owner; }
+int afg_batch_encode(const(afg_encode_input)* inputs, int n_files, int format, const(afg_encoding_options)* opts, int n_threads,
+                     afg_encode_result* result);
+void afg_encode_free(afg_encode_result* result);
+
 /// Drop-in for the decoding use of `AudioStream` (stream.d:102): same member names and error-state contract
 /// (never throws, `isError` + `errorMessage`), backed by the device library.  Not thread-safe per instance,
 /// like the original (stream.d:31-33).
@@ -415,6 +439,29 @@ nothrow @nogc:
     {
         cleanUp();
         _h = afg_open_from_memory(inputData.ptr, inputData.length);
+    }
+    /// The writing half (stream.d:216-286, :762-902, :1282-1349): WAV and QOA.
+    void openToBuffer(afg_format format, float sampleRate, int numChannels, const(afg_encoding_options)* options = null)
+    {
+        cleanUp();
+        _h = afg_open_to_buffer(format, sampleRate, numChannels, options);
+    }
+    void openToMemory(ubyte* data, size_t maxLength, afg_format format, float sampleRate, int numChannels,
+                      const(afg_encoding_options)* options = null)
+    {
+        cleanUp();
+        _h = afg_open_to_memory(data, maxLength, format, sampleRate, numChannels, options);
+    }
+    bool isOpenForReading() { return afg_is_open_for_reading(_h) != 0; }
+    bool isOpenForWriting() { return afg_is_open_for_writing(_h) != 0; }
+    int writeSamplesFloat(const(float)* inData, int frames) { return afg_write_samples_float(_h, inData, frames); }
+    int writeSamplesDouble(const(double)* inData, int frames) { return afg_write_samples_double(_h, inData, frames); }
+    bool finalizeEncoding() { return afg_finalize_encoding(_h) != 0; }
+    const(ubyte)[] finalizeAndGetEncodedResult()
+    {
+        const(ubyte)* p;
+        size_t n;
+        return afg_finalize_and_get_encoded(_h, &p, &n) ? p[0 .. n] : null;
     }
     void cleanUp() { if (_h !is null) { afg_close(_h); _h = null; } }
 

@@ -628,6 +628,94 @@ typedef int (*afg_rand_fn)(void *user);        /* a draw in [0, rng_max] */
 uint64_t afg_wav_encode_dithered(const float *samples, uint64_t frames, uint32_t channels, uint32_t samplerate, int format,
                                  afg_rand_fn rng, void *rng_user, uint32_t rng_max, uint8_t *out, uint64_t cap);
 
+/* WAV sample packing on the device: float32 to the sample bytes WAVEncoder.writeSamples produces (wav.d:482-547), with
+ * TPDFDither.process (wav.d:679-700) in front of the integer formats when asked for.  The mirror image of
+ * afg_wav_convert_hip: spans, tiles of AFG_WAV_TILE_SAMPLES samples, one workgroup per tile.  The reference draws its
+ * dither from libc rand(), one process-wide serial sequence that cannot be spread over lanes; the device draws from the
+ * 31-bit generator  state = (state * 1103515245 + 12345) & 0x7fffffff  (the draw is the new state, rng_max = 0x7fffffff),
+ * and sample n of a file -- counted over its interleaved samples -- uses draws 2n and 2n + 1 of the file's seed: the bytes
+ * are those of afg_wav_encode_dithered with that generator as its callback. */
+#define AFG_DITHER_OFF    0
+#define AFG_DITHER_LIBC   1      /* EncodingOptions.enableDither = true with the reference's rand(): host only */
+#define AFG_DITHER_LCG31  2
+
+typedef struct afg_wav_pack_span { /* one run of samples of one output file (48 bytes) */
+    uint64_t in_off;               /* first float in d_in, a multiple of 4 */
+    uint64_t out_off;              /* first byte in d_out, a multiple of 16 */
+    uint64_t count;                /* samples */
+    uint64_t first_tile;           /* first tile of the span in the launch: afg_wav_pack_layout fills it in */
+    uint64_t draw0;                /* index of the span's first dither draw = 2 x (samples of the file before it) */
+    uint32_t seed;                 /* the file's generator starts from this state */
+    uint8_t  format;               /* AFG_WAV_S8 .. AFG_WAV_FP64LE */
+    uint8_t  dither;               /* 0 off, 1 the 31-bit generator (integer formats only; the float formats never dither) */
+    uint8_t  pad[2];
+} afg_wav_pack_span;
+
+/* Host: the generator's state after n_draws steps from `seed` (taken modulo 2^31) -- the n-th draw itself for
+ * n_draws >= 1.  The generator is an affine map modulo 2^31, so this takes 31 steps for any n_draws. */
+uint32_t afg_lcg31_jump(uint32_t seed, uint64_t n_draws);
+/* Host: gives every span its tiles (first_tile) and returns the launch's tile count. */
+uint64_t afg_wav_pack_layout(afg_wav_pack_span *spans, uint64_t n_spans);
+/* Packs every span in one launch.  d_spans is the device copy of spans laid out by afg_wav_pack_layout, n_tiles what
+ * it returned; d_in and d_out are 16-byte aligned and do not overlap.  A span that does not lie inside [0, in_floats) /
+ * [0, out_bytes), or whose offsets are not aligned as stated, is not touched at all.  The integer formats are defined
+ * for inputs in [-1, 1] (the reference asserts). */
+int afg_wav_pack_hip(uint64_t n_spans, const afg_wav_pack_span *d_spans, uint64_t n_tiles, const float *d_in,
+                     uint64_t in_floats, uint8_t *d_out, uint64_t out_bytes, void *hip_stream);
+
+/* The writing half of AudioStream (stream.d:216-286 openToBuffer / openToMemory, :762-902 writeSamplesFloat /
+ * writeSamplesDouble, :1282-1349 finalizeEncoding / finalizeAndGetEncodedResult) for WAV and QOA, on the same handle
+ * type: afg_is_error, afg_error_message, afg_get_format, afg_get_num_channels, afg_get_samplerate and afg_close work
+ * on it; reads and seeks return 0.  Any other format puts the stream in error state with the reference's
+ * unsupported-encoding-format message (internals.d:17), every failure with its encoder-error message (:22).
+ *   WAV  the 44-byte header is written at open; writes queue floats, and whenever about 2^18 samples are queued, and at
+ *        finalize, one upload, one afg_wav_pack_hip launch and one download append their bytes; the dither's draw index
+ *        runs on across writes.  AFG_DITHER_LIBC with an integer format is the one case that stays on the host writer's
+ *        loop (afg_wav_encode_dithered): its draws are a serial, process-global sequence.  afg_write_samples_double to
+ *        an fp64 stream stores the doubles as they are (wav.d:538-546), to any other it narrows to float first
+ *        (stream.d:886-894).  Finalize patches the two length fields (wav.d:572-603) and reports 1: the reference
+ *        reports every WAV finalize as failed (wav.d:604); this library does not.
+ *   QOA  writes queue frames; finalize encodes the whole stream with one afg_qoa_encode_hip call -- the bytes of the
+ *        reference's frame-by-frame writes, since the LMS state runs through the stream either way.  Doubles are
+ *        converted in double (qoa.d:632-634).
+ * afg_open_to_memory: the first write whose bytes would pass max_length writes nothing, returns 0 and sets the error
+ * state; for QOA the bound is checked at finalize.  A write after finalize returns 0 and sets the error state (the
+ * reference asserts). */
+typedef struct afg_encoding_options {          /* EncodingOptions, stream.d:59-67 */
+    uint32_t struct_size;     /* sizeof(afg_encoding_options) */
+    int      sample_format;   /* AFG_WAV_*; NULL options = the reference's defaults: AFG_WAV_FP32LE, AFG_DITHER_LIBC */
+    int      dither;          /* AFG_DITHER_* */
+    uint32_t dither_seed;     /* AFG_DITHER_LCG31 only */
+} afg_encoding_options;
+/* The integer sample rate is (int)(samplerate + 0.5f) (stream.d:1852).  Return NULL only when out of memory. */
+afg_stream *afg_open_to_buffer(int format, float samplerate, int channels, const afg_encoding_options *opts);
+afg_stream *afg_open_to_memory(uint8_t *data, size_t max_length, int format, float samplerate, int channels,
+                               const afg_encoding_options *opts);
+int  afg_is_open_for_reading(const afg_stream *s);           /* stream.d:377-391 */
+int  afg_is_open_for_writing(const afg_stream *s);
+int  afg_write_samples_float(afg_stream *s, const float *in, int frames);     /* frames written */
+int  afg_write_samples_double(afg_stream *s, const double *in, int frames);
+int  afg_finalize_encoding(afg_stream *s);                   /* 1 = done */
+/* Buffer streams only: finalizes if that has not happened and hands out the file, owned by the stream and valid until
+ * afg_close; may be called again.  1 = done. */
+int  afg_finalize_and_get_encoded(afg_stream *s, const uint8_t **bytes, size_t *length);
+
+/* Batch encode (no reference counterpart: the throughput path outward, the mirror of afg_batch_decode).  Interleaved
+ * float PCM in host memory becomes file bytes in host memory, on the current device: pooled threads copy the PCM into
+ * page-locked staging, chunks go through two staging and two pairs of device buffers with upload, kernel and download
+ * overlapped, and the files land in a page-locked plane owned by the result.  format is AFG_FORMAT_WAV (opts as above;
+ * every file's dither starts at draw 0 of dither_seed, so a file's bytes depend on nothing but the file) or
+ * AFG_FORMAT_QOA.  A bad item -- no or too many channels (WAV 1..1024, QOA 1..8), a sample rate out of range, NULL pcm
+ * with frames > 0, a QOA of 2^32 frames or more -- carries its own status and never poisons the batch.
+ * AFG_DITHER_LIBC with an integer WAV format is refused for the whole call (AFG_ERR_UNSUPPORTED): there is no defined
+ * draw order across files. */
+typedef struct afg_encode_input { const float *pcm; uint64_t frames; uint32_t channels; float samplerate; } afg_encode_input;
+typedef struct afg_encoded_item { int status; const char *message; uint8_t *bytes; uint64_t size; } afg_encoded_item;
+typedef struct afg_encode_result { int n_files; afg_encoded_item *items; void *owner; } afg_encode_result;
+int  afg_batch_encode(const afg_encode_input *in, int n_files, int format, const afg_encoding_options *opts,
+                      int n_threads, afg_encode_result *out);
+void afg_encode_free(afg_encode_result *r);
+
 /* ========================================================================== *
  *  ProTracker MOD (pocketmod.d; stream.d:1796-1830): 2 channels at 44100 Hz, length AFG_UNKNOWN_LENGTH, one numeric mode
  *  (both AFG_NUMERIC settings give the same bits).  The control layer -- pattern lines, effects, LFOs, tempo, once per tick
