@@ -1,15 +1,14 @@
 // afg_encode_stage.cpp -- afg_batch_encode: interleaved float PCM in host memory to WAV or QOA files in host memory.
 //
-// Built like the WAV stage of the batch decoder (afg_wav_stage.cpp) turned round: helper threads copy the PCM into leased
-// page-locked staging (that copy puts every piece on a 4-float boundary), chunks go through two stagings and two pairs of
-// device buffers with upload, kernel and download on the kept stream pair, and the bytes come back into one page-locked
-// plane that the items point into.  The plane has the device buffers' layout, so a chunk is one download: a WAV file
-// starts 4 bytes past a 16-byte boundary, which puts its samples -- 44 bytes on -- on one; headers are written by the
-// host once the last chunk is back.
+// Helper threads copy the PCM into leased page-locked staging (that copy puts every piece on a 4-float boundary),
+// chunks go through two stagings and two pairs of device buffers with upload, kernel and download on the kept stream
+// pair (afg_front::run_chunks), and the bytes come back into one page-locked plane that the items point into.  The plane
+// has the device buffers' layout, so a chunk is one download: a WAV file starts 4 bytes past a 16-byte boundary, which
+// puts its samples -- 44 bytes on -- on one; headers are written by the host once the last chunk is back.
 // WAV: one afg_wav_pack_hip launch per chunk, whatever it holds; a long file is cut at tile boundaries and draw0 carries
 // its dither position across the cuts.  QOA: afg_qoa_encode_hip over the streams of a chunk; the encoder's LMS state runs
 // through a stream, so a file is never cut.
-#include "afg_mod_front.h"
+#include "afg_stage.h"
 #include "afg_write_stream.h"
 #include "../csrc/afg_common.h"
 
@@ -19,14 +18,12 @@
 #include <new>
 #include <vector>
 
-namespace afg_front {
-// page-locked staging and the kept stream pair (afg_host.cpp)
-std::shared_ptr<void> staging_lease(size_t bytes, void **p);
-hipError_t streams_take(hipStream_t *up, hipStream_t *down);
-void streams_give(hipStream_t up, hipStream_t down);
-}  // namespace afg_front
-
 namespace {
+
+using afg_front::align16;
+using afg_front::DevBuf;
+using afg_write::kWavHeader;
+using afg_write::sample_size;
 
 const char *const kMessageChannels = "Encoder: unsupported channel count";
 const char *const kMessageRate = "Encoder: sample rate out of range";
@@ -35,10 +32,6 @@ const char *const kMessageTooLong = "Encoder: too many frames for the format";
 
 constexpr uint64_t kChunkSamples = (uint64_t)8 << 20;          // a chunk: 32 MB of floats up, 8-64 MB of file bytes down
 static_assert(kChunkSamples % AFG_WAV_TILE_SAMPLES == 0, "files are cut at tile boundaries");
-constexpr uint64_t kWavHeader = 44;
-
-uint64_t align16(uint64_t n) { return (n + 15) & ~(uint64_t)15; }
-int sample_size(int format) { return format == AFG_WAV_S8 ? 1 : format == AFG_WAV_S16LE ? 2 : format == AFG_WAV_S24LE ? 3 : format == AFG_WAV_FP32LE ? 4 : 8; }
 
 struct EncodeOwner {
     std::vector<afg_encoded_item> items;
@@ -56,23 +49,10 @@ struct File {
 // a piece of one file inside a chunk: `src` is its first sample in the file's PCM, `in_off` / `count` its place in the staging
 struct Piece { size_t file; uint64_t src, in_off, count; };
 
-struct Pair {
-    hipStream_t up = nullptr, down = nullptr;
-    ~Pair()
-    {
-        for (hipStream_t st : { up, down }) if (st) (void)hipStreamSynchronize(st);
-        if (up && down) afg_front::streams_give(up, down);
-    }
-};
-struct Events {
-    hipEvent_t e[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    ~Events() { for (hipEvent_t ev : e) if (ev) (void)hipEventDestroy(ev); }
-};
-
 // The pipeline both formats share.  Chunk c owns pieces [first[c], first[c + 1]), uploads in_floats[c] floats, runs
 // launch(c, d_in, d_out, stream) and brings out_bytes[c] bytes back to plane + plane_at[c].
 template <typename Launch>
-int run_chunks(const afg_encode_input *in, int n_threads, const std::vector<Piece> &pieces, const std::vector<size_t> &first,
+int run_pieces(const afg_encode_input *in, int n_threads, const std::vector<Piece> &pieces, const std::vector<size_t> &first,
                const std::vector<uint64_t> &in_floats, const std::vector<uint64_t> &out_bytes, const std::vector<uint64_t> &plane_at,
                uint8_t *plane, const Launch &launch)
 {
@@ -82,41 +62,29 @@ int run_chunks(const afg_encode_input *in, int n_threads, const std::vector<Piec
     const uint64_t max_out = std::max<uint64_t>(16, *std::max_element(out_bytes.begin(), out_bytes.end()));
     void *stage[2] = { nullptr, nullptr };
     std::shared_ptr<void> stage_owner[2];
-    afg_mod::DevBuf d_in[2], d_out[2];
+    DevBuf d_in[2], d_out[2];
     for (int b = 0; b < bufs; b++) {
         if (!(stage_owner[b] = afg_front::staging_lease((size_t)max_in * sizeof(float), &stage[b]))) return AFG_ERR_OOM;
         if (int rc = d_in[b].alloc((size_t)max_in * sizeof(float))) return rc;
         if (int rc = d_out[b].alloc((size_t)align16(max_out))) return rc;
     }
-    Pair pair;                                           // the kept upload / download pair, given back drained on every way out
-    AFG_HIP_CHECK(afg_front::streams_take(&pair.up, &pair.down));
-    hipStream_t up = pair.up, down = pair.down;
-    // rings of two: chunk c's staging is free once chunk c - 2 has gone up (the host waits), its output buffer once
-    // chunk c - 2 has come back (the upload stream waits)
-    Events ev;
-    for (hipEvent_t &e : ev.e) AFG_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    hipEvent_t *uploaded = ev.e, *packed = ev.e + 2, *fetched = ev.e + 4;
-    for (size_t c = 0; c < C; c++) {
-        const int b = (int)(c & 1);
-        const size_t p0 = first[c], p1 = first[c + 1];
-        if (c >= 2) AFG_HIP_CHECK(hipEventSynchronize(uploaded[b]));
-        float *hin = (float *)stage[b];
-        afg_front::parallel_run(p1 - p0, n_threads, [&](size_t j) {
-            const Piece &pc = pieces[p0 + j];
-            if (pc.count) std::memcpy(hin + pc.in_off, in[pc.file].pcm + pc.src, (size_t)pc.count * sizeof(float));
+    return afg_front::run_chunks(
+        C, /* before */ nullptr,
+        [&](size_t c, int b, hipStream_t up) -> int {
+            const size_t p0 = first[c];
+            float *hin = (float *)stage[b];
+            afg_front::parallel_run(first[c + 1] - p0, n_threads, [&](size_t j) {
+                const Piece &pc = pieces[p0 + j];
+                if (pc.count) std::memcpy(hin + pc.in_off, in[pc.file].pcm + pc.src, (size_t)pc.count * sizeof(float));
+            });
+            if (in_floats[c]) AFG_HIP_CHECK(hipMemcpyAsync(d_in[b].p, hin, (size_t)in_floats[c] * sizeof(float), hipMemcpyHostToDevice, up));
+            return AFG_OK;
+        },
+        [&](size_t c, int b, hipStream_t up) -> int { return launch(c, (const float *)d_in[b].p, (uint8_t *)d_out[b].p, up); },
+        [&](size_t c, int b, hipStream_t down) -> int {
+            if (out_bytes[c]) AFG_HIP_CHECK(hipMemcpyAsync(plane + plane_at[c], d_out[b].p, (size_t)out_bytes[c], hipMemcpyDeviceToHost, down));
+            return AFG_OK;
         });
-        if (in_floats[c]) AFG_HIP_CHECK(hipMemcpyAsync(d_in[b].p, hin, (size_t)in_floats[c] * sizeof(float), hipMemcpyHostToDevice, up));
-        AFG_HIP_CHECK(hipEventRecord(uploaded[b], up));
-        if (c >= 2) AFG_HIP_CHECK(hipStreamWaitEvent(up, fetched[b], 0));
-        if (int rc = launch(c, (const float *)d_in[b].p, (uint8_t *)d_out[b].p, up)) return rc;
-        AFG_HIP_CHECK(hipEventRecord(packed[b], up));
-        AFG_HIP_CHECK(hipStreamWaitEvent(down, packed[b], 0));
-        if (out_bytes[c]) AFG_HIP_CHECK(hipMemcpyAsync(plane + plane_at[c], d_out[b].p, (size_t)out_bytes[c], hipMemcpyDeviceToHost, down));
-        AFG_HIP_CHECK(hipEventRecord(fetched[b], down));
-    }
-    AFG_HIP_CHECK(hipStreamSynchronize(down));
-    AFG_HIP_CHECK(hipStreamSynchronize(up));
-    return AFG_OK;
 }
 
 void wav_header(uint8_t *p, uint64_t frames, uint32_t channels, uint32_t rate, int format)
@@ -183,11 +151,11 @@ int encode_wav(const afg_encode_input *in, int n_threads, std::vector<File> &fil
         const size_t C = first.size() - 1;
         tiles.resize(C);
         for (size_t c = 0; c < C; c++) tiles[c] = afg_wav_pack_layout(spans.data() + first[c], first[c + 1] - first[c]);
-        afg_mod::DevBuf d_spans;
+        DevBuf d_spans;
         if (int rc = d_spans.alloc(spans.size() * sizeof(afg_wav_pack_span))) return rc;
         // (synchronous: the table is in place before the pipeline's streams start)
         AFG_HIP_CHECK(hipMemcpy(d_spans.p, spans.data(), spans.size() * sizeof(afg_wav_pack_span), hipMemcpyHostToDevice));
-        const int rc = run_chunks(in, n_threads, pieces, first, in_floats, out_bytes, plane_at, (uint8_t *)plane,
+        const int rc = run_pieces(in, n_threads, pieces, first, in_floats, out_bytes, plane_at, (uint8_t *)plane,
                                   [&](size_t c, const float *d_in, uint8_t *d_out, hipStream_t st) {
                                       return afg_wav_pack_hip(first[c + 1] - first[c], (const afg_wav_pack_span *)d_spans.p + first[c], tiles[c],
                                                               d_in, in_floats[c], d_out, align16(out_bytes[c]), st);
@@ -244,10 +212,10 @@ int encode_qoa(const afg_encode_input *in, int n_threads, std::vector<File> &fil
     owner.plane = afg_front::staging_lease((size_t)std::max<uint64_t>(plane_bytes, 16), &plane);
     if (!owner.plane) return AFG_ERR_OOM;
     if (!pieces.empty()) {
-        afg_mod::DevBuf d_recs;
+        DevBuf d_recs;
         if (int rc = d_recs.alloc(recs.size() * sizeof(afg_qoa_enc_stream))) return rc;
         AFG_HIP_CHECK(hipMemcpy(d_recs.p, recs.data(), recs.size() * sizeof(afg_qoa_enc_stream), hipMemcpyHostToDevice));
-        const int rc = run_chunks(in, n_threads, pieces, first, in_floats, out_bytes, plane_at, (uint8_t *)plane,
+        const int rc = run_pieces(in, n_threads, pieces, first, in_floats, out_bytes, plane_at, (uint8_t *)plane,
                                   [&](size_t c, const float *d_in, uint8_t *d_out, hipStream_t st) {
                                       return afg_qoa_encode_hip((uint32_t)(first[c + 1] - first[c]), (const afg_qoa_enc_stream *)d_recs.p + first[c],
                                                                 nullptr, d_in, d_out, st);

@@ -16,6 +16,7 @@
 #include "afg_xm_front.h"
 #include "afg_mp3_front.h"
 #include "afg_opus_front.h"
+#include "afg_stage.h"
 #include "afg_vorbis_front.h"
 #include "afg_write_stream.h"
 
@@ -316,9 +317,17 @@ private:
 StreamPool g_streams;
 }  // namespace
 
-// the pools as the MOD stage (afg_mod_stage.cpp) uses them
+// the pools as the stages beside this file use them (declared in afg_stage.h)
 namespace afg_front {
-int devpool_take(size_t bytes, void **out, size_t *cap_out) { return g_devpool.take(bytes, out, cap_out); }
+int devpool_take(size_t bytes, void **out, size_t *cap_out)
+{
+    if (int rc = g_devpool.take(bytes, out, cap_out)) return rc;
+    if (bytes && g_poison_alloc) {                       // (tests: see DeviceBuf::alloc)
+        (void)hipMemset(*out, 0xff, bytes);
+        (void)hipStreamSynchronize(nullptr);
+    }
+    return AFG_OK;
+}
 void devpool_give(void *p, size_t cap, int dev) { g_devpool.give_back_on(dev, p, cap); }
 // a page-locked staging lease; the buffer goes back to the pool when the last owner lets go
 std::shared_ptr<void> staging_lease(size_t bytes, void **p)
@@ -2517,17 +2526,14 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
             if (items[i].status == AFG_ERR_UNSUPPORTED && items[i].message == kErrorUnknownFormat) unknown.push_back(i);
         // WAV comes well before either (stream.d:1638); no probe between it and them takes a file its scan accepts (QOA and
         // Ogg have their own magic, looks_like_mp3 declines RIFF), so its stage can run here, on the files nothing took
-        if (int wrc = afg_wav::batch_stage(data, length, unknown, [&](size_t n, const std::function<void(size_t)> &fn) { parallel_for(n, nt, fn); },
-                                           items, owner->wav_plane)) return wrc;
+        if (int wrc = afg_wav::batch_stage(data, length, unknown, (int)nt, items, owner->wav_plane)) return wrc;
         tm.lap("wav stage");
         unknown.erase(std::remove_if(unknown.begin(), unknown.end(), [&](int i) { return items[i].status == AFG_OK || items[i].message != kErrorUnknownFormat; }), unknown.end());
         // ... and XM directly before it (stream.d:1751)
-        if (int xrc = afg_xm::batch_stage(data, length, unknown, [&](size_t n, const std::function<void(size_t)> &fn) { parallel_for(n, nt, fn); },
-                                          items, owner->xm_plane)) return xrc;
+        if (int xrc = afg_xm::batch_stage(data, length, unknown, (int)nt, items, owner->xm_plane)) return xrc;
         tm.lap("xm stage");
         unknown.erase(std::remove_if(unknown.begin(), unknown.end(), [&](int i) { return items[i].status == AFG_OK || items[i].message != kErrorUnknownFormat; }), unknown.end());
-        if (int mrc = afg_mod::batch_stage(data, length, unknown, [&](size_t n, const std::function<void(size_t)> &fn) { parallel_for(n, nt, fn); },
-                                           items, owner->mod_plane)) return mrc;
+        if (int mrc = afg_mod::batch_stage(data, length, unknown, (int)nt, items, owner->mod_plane)) return mrc;
         tm.lap("mod stage");
         keep = std::move(guard);
         tm.lap("items filled");

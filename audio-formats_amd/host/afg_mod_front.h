@@ -2,13 +2,10 @@
 // machine that emits the mixer's work as afg_mod_tick / afg_mod_segment records (include/afg.h).  The device mixer is
 // csrc/mod_mix.hip; the position chain both sides share is csrc/mod_chain.h.
 #pragma once
-#include "../../include/afg.h"
-
-#include <hip/hip_runtime.h>
+#include "afg_stage.h"
 
 #include <cstddef>
 #include <cstdint>
-#include <functional>
 #include <memory>
 #include <vector>
 
@@ -97,31 +94,16 @@ uint64_t render_song(Song &song, std::vector<afg_mod_tick> &ticks, std::vector<a
 // ---------------------------------------------------------------------------------------------
 namespace afg_mod {
 
-// Device memory from the library's pool (afg_host.cpp), returned to the device it was taken on.
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int dev = -1;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    int alloc(size_t bytes);                                // keeps the buffer when it is large enough
-    void release();
-};
-
 // A MOD stream: each read runs the control layer for exactly the read's frames and mixes them on the device.
 class StreamMix {
 public:
-    ~StreamMix();
     // pocketmod_render(c, out, frames * 8) behind stream.d:611-620; -1: device error (afg_last_error says which)
     int read(float *out, int frames);
     Song song;
 private:
-    DevBuf plane_, recs_, out_;
+    afg_front::DevBuf plane_, recs_, out_;
     bool uploaded_ = false;
-    hipStream_t stream_ = nullptr;
-    int stream_dev_ = -1;
+    afg_front::HandleStream stream_;
     std::vector<afg_mod_tick> ticks_;
     std::vector<afg_mod_segment> segs_;
     std::vector<uint8_t> staging_;
@@ -129,11 +111,10 @@ private:
 };
 
 // The batch path's MOD stage: the files listed in `which` that pass the probe are simulated on the helper threads
-// (run_parallel(n, fn) calls fn(0..n-1)), mixed on the current device in chunks with upload, mix and download overlapped,
+// (n_threads as afg_front::parallel_run takes it), mixed on the current device in chunks with upload, mix and download overlapped,
 // and their items filled in (2-channel float PCM in page-locked memory that `keep` owns).  Other files are left alone.
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                const std::function<void(size_t, const std::function<void(size_t)> &)> &run_parallel,
-                afg_batch_item *items, std::shared_ptr<void> &keep);
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep);
 
 // What the stage reports on a song cut at AFG_MOD_MAX_FRAMES (status AFG_OK)
 extern const char *const kMessageCapped;

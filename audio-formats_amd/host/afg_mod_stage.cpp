@@ -11,40 +11,14 @@
 #include <cstring>
 #include <new>
 
-namespace afg_front {
-// the library's device-memory pool (afg_host.cpp)
-int devpool_take(size_t bytes, void **out, size_t *cap_out);
-void devpool_give(void *p, size_t cap, int dev);
-// page-locked staging (afg_host.cpp's pool: pinning memory costs about as much as moving it) and the kept stream pair
-std::shared_ptr<void> staging_lease(size_t bytes, void **p);
-hipError_t streams_take(hipStream_t *up, hipStream_t *down);
-void streams_give(hipStream_t up, hipStream_t down);
-}  // namespace afg_front
-
 namespace afg_mod {
+
+using afg_front::align16;
+using afg_front::DevBuf;
 
 const char *const kMessageCapped = "MOD: the song does not end; cut at AFG_MOD_MAX_FRAMES (30 minutes)";
 
-int DevBuf::alloc(size_t bytes)
-{
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess) cur = 0;
-    if (p && cap >= bytes && dev == cur) return AFG_OK;
-    release();
-    if (int rc = afg_front::devpool_take(bytes, &p, &cap)) { p = nullptr; cap = 0; return rc; }
-    dev = cur;
-    return AFG_OK;
-}
-
-void DevBuf::release()
-{
-    if (p) afg_front::devpool_give(p, cap, dev);
-    p = nullptr; cap = 0; dev = -1;
-}
-
 namespace {
-
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 // Records of one launch in one buffer: songs, then ticks, then segments (each 16-byte aligned)
 struct RecLayout {
@@ -60,17 +34,6 @@ struct RecLayout {
 
 }  // namespace
 
-StreamMix::~StreamMix()
-{
-    if (stream_) {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (cur != stream_dev_) (void)hipSetDevice(stream_dev_);
-        (void)hipStreamDestroy(stream_);
-        if (cur != stream_dev_ && cur >= 0) (void)hipSetDevice(cur);
-    }
-}
-
 int StreamMix::read(float *out, int frames)
 {
     if (frames <= 0 || song.loop_count() >= 1) return 0;           // stream.d:614: the song has ended
@@ -78,24 +41,15 @@ int StreamMix::read(float *out, int frames)
     segs_.clear();
     const int n = song.render(frames, 0, 0, ticks_, segs_);
     if (n <= 0) return 0;
-    int dev = 0;
-    AFG_HIP_CHECK(hipGetDevice(&dev));
-    if (stream_ && stream_dev_ != dev) {
-        // the caller changed devices between reads: the buffers follow, the plane is uploaded again
-        (void)hipSetDevice(stream_dev_);
-        (void)hipStreamDestroy(stream_);
-        (void)hipSetDevice(dev);
-        stream_ = nullptr;
-        uploaded_ = false;
-    }
-    if (!stream_) {
-        AFG_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-        stream_dev_ = dev;
-    }
+    hipStream_t st = nullptr;
+    bool moved = false;
+    const int rc = stream_.current(&st, &moved);
+    if (moved) uploaded_ = false;     // the caller changed devices between reads: the buffers follow, the plane is uploaded again
+    if (rc) return rc;
     const std::vector<uint8_t> &plane = song.plane();
-    if (!uploaded_ || plane_.dev != dev) {
+    if (!uploaded_ || plane_.dev != stream_.dev) {
         if (plane_.alloc(plane.size())) return -1;
-        AFG_HIP_CHECK(hipMemcpyAsync(plane_.p, plane.data(), plane.size(), hipMemcpyHostToDevice, stream_));
+        AFG_HIP_CHECK(hipMemcpyAsync(plane_.p, plane.data(), plane.size(), hipMemcpyHostToDevice, st));
         uploaded_ = true;
     }
     const RecLayout L(1, ticks_.size(), segs_.size());
@@ -109,21 +63,20 @@ int StreamMix::read(float *out, int frames)
     if (!segs_.empty()) std::memcpy(staging_.data() + L.segs, segs_.data(), segs_.size() * sizeof(afg_mod_segment));
     const size_t out_bytes = (size_t)n * 2 * sizeof(float);
     if (recs_.alloc(L.bytes) || out_.alloc(out_bytes)) return -1;
-    AFG_HIP_CHECK(hipMemcpyAsync(recs_.p, staging_.data(), L.bytes, hipMemcpyHostToDevice, stream_));
+    AFG_HIP_CHECK(hipMemcpyAsync(recs_.p, staging_.data(), L.bytes, hipMemcpyHostToDevice, st));
     uint8_t *r = (uint8_t *)recs_.p;
     if (afg_mod_render_hip(1, (const afg_mod_song *)(r + L.songs), (const afg_mod_segment *)(r + L.segs),
-                           (const afg_mod_tick *)(r + L.ticks), (const uint8_t *)plane_.p, (float *)out_.p, stream_))
+                           (const afg_mod_tick *)(r + L.ticks), (const uint8_t *)plane_.p, (float *)out_.p, st))
         return -1;
     float *dst = out;
     if (!dst) { bounce_.resize((size_t)n * 2); dst = bounce_.data(); }
-    AFG_HIP_CHECK(hipMemcpyAsync(dst, out_.p, out_bytes, hipMemcpyDeviceToHost, stream_));
-    AFG_HIP_CHECK(hipStreamSynchronize(stream_));
+    AFG_HIP_CHECK(hipMemcpyAsync(dst, out_.p, out_bytes, hipMemcpyDeviceToHost, st));
+    AFG_HIP_CHECK(hipStreamSynchronize(st));
     return n;
 }
 
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                const std::function<void(size_t, const std::function<void(size_t)> &)> &run_parallel,
-                afg_batch_item *items, std::shared_ptr<void> &keep)
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep)
 {
     if (which.empty()) return AFG_OK;
     // ---- the control layer, one file per helper-thread job ----
@@ -138,7 +91,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
     };
     std::vector<Sim> sims(which.size());
     std::atomic<bool> oom{ false };
-    run_parallel(which.size(), [&](size_t k) {
+    afg_front::parallel_run(which.size(), n_threads, [&](size_t k) {
         const int i = which[k];
         try {
             Sim &s = sims[k];
@@ -157,6 +110,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
     // ---- layout: per song its output frame, ticks, segments and plane bytes in the batch ----
     const size_t M = mods.size();
     std::vector<afg_mod_song> songs(M);
+    std::vector<uint64_t> start(M), end(M);
     uint64_t frames = 0, n_ticks = 0, n_segs = 0, plane_bytes = 0;
     for (size_t j = 0; j < M; j++) {
         const Sim &s = sims[mods[j]];
@@ -165,6 +119,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
         g.out_frame = frames; g.tick_base = n_ticks; g.seg_base = n_segs; g.sample_base = plane_bytes;
         g.n_ticks = (uint32_t)s.ticks.size();
         g.sample_bytes = (uint32_t)s.song.plane().size();
+        start[j] = frames; end[j] = frames + s.frames;
         frames += s.frames; n_ticks += s.ticks.size(); n_segs += s.segs.size(); plane_bytes += align16(s.song.plane().size());
     }
     // page-locked: the PCM plane the items point into (owned by `keep`), and the inputs staged for one upload
@@ -177,7 +132,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
     std::shared_ptr<void> in_owner = afg_front::staging_lease(in_bytes, &in);
     if (!in_owner) return AFG_ERR_OOM;
     uint8_t *hin = (uint8_t *)in;
-    run_parallel(M, [&](size_t j) {
+    afg_front::parallel_run(M, n_threads, [&](size_t j) {
         const Sim &s = sims[mods[j]];
         const afg_mod_song &g = songs[j];
         if (!s.ticks.empty()) std::memcpy(hin + g.tick_base * sizeof(afg_mod_tick), s.ticks.data(), s.ticks.size() * sizeof(afg_mod_tick));
@@ -185,68 +140,35 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
         std::memcpy(hin + tick_bytes + seg_bytes + g.sample_base, s.song.plane().data(), s.song.plane().size());
     });
 
-    // ---- chunks of songs, about kChunkFrames of output each: mix chunk c+1 while chunk c comes back ----
-    constexpr uint64_t kChunkFrames = (uint64_t)16 << 20;                   // 128 MB of PCM
-    std::vector<size_t> first{ 0 };
-    for (size_t j = 0; j < M; j++) {
-        const uint64_t end = songs[j].out_frame + sims[mods[j]].frames;
-        if (j + 1 < M && end - songs[first.back()].out_frame >= kChunkFrames) first.push_back(j + 1);
-    }
-    first.push_back(M);
-    const size_t C = first.size() - 1;
-    // chunk-relative song records: output frame and tick base count from the chunk's first song
-    std::vector<afg_mod_song> rel(songs);
-    uint64_t max_chunk = 1;
-    for (size_t c = 0; c < C; c++) {
-        const afg_mod_song &f = songs[first[c]];
-        for (size_t j = first[c]; j < first[c + 1]; j++) { rel[j].out_frame -= f.out_frame; rel[j].tick_base -= f.tick_base; }
-        const size_t last = first[c + 1] - 1;
-        max_chunk = std::max<uint64_t>(max_chunk, songs[last].out_frame + sims[mods[last]].frames - f.out_frame);
-    }
+    // ---- chunks of songs, about 128 MB of output each: chunk c + 1 is mixed while chunk c comes back ----
+    const afg_front::SongChunks chunks(start, end);
+    const std::vector<size_t> &first = chunks.first;
+    const std::vector<afg_mod_song> rel = chunks.relative(songs);
     DevBuf d_in, d_songs, d_out[2];
     if (int rc = d_in.alloc(in_bytes)) return rc;
     if (int rc = d_songs.alloc(M * sizeof(afg_mod_song))) return rc;
-    for (DevBuf &b : d_out) if (int rc = b.alloc(max_chunk * 2 * sizeof(float))) return rc;
-    // the kept upload / download pair, given back drained on every way out
-    struct Pair {
-        hipStream_t up = nullptr, down = nullptr;
-        ~Pair()
-        {
-            for (hipStream_t st : { up, down }) if (st) (void)hipStreamSynchronize(st);
-            if (up && down) afg_front::streams_give(up, down);
-        }
-    } pair;
-    AFG_HIP_CHECK(afg_front::streams_take(&pair.up, &pair.down));
-    hipStream_t up = pair.up, down = pair.down;
-    // two output buffers in turn: chunk c waits for chunk c - 2's download (events in a ring of two: a wait takes the event's
-    // state when it is queued)
-    hipEvent_t mixed[2] = { nullptr, nullptr }, fetched[2] = { nullptr, nullptr };
-    struct EventGuard { hipEvent_t *e; ~EventGuard() { for (int k = 0; k < 4; k++) if (e[k]) (void)hipEventDestroy(e[k]); } };
-    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-    EventGuard g_ev{ ev };
-    for (int k = 0; k < 4; k++) AFG_HIP_CHECK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
-    mixed[0] = ev[0]; mixed[1] = ev[1]; fetched[0] = ev[2]; fetched[1] = ev[3];
-    AFG_HIP_CHECK(hipMemcpyAsync(d_in.p, in, in_bytes, hipMemcpyHostToDevice, up));
-    AFG_HIP_CHECK(hipMemcpyAsync(d_songs.p, rel.data(), M * sizeof(afg_mod_song), hipMemcpyHostToDevice, up));
+    for (DevBuf &b : d_out) if (int rc = b.alloc(chunks.max_frames * 2 * sizeof(float))) return rc;
     const uint8_t *din = (const uint8_t *)d_in.p;
-    for (size_t c = 0; c < C; c++) {
-        const afg_mod_song &f = songs[first[c]];
-        const size_t last = first[c + 1] - 1;
-        const uint64_t chunk_frames = songs[last].out_frame + sims[mods[last]].frames - f.out_frame;
-        DevBuf &o = d_out[c & 1];
-        if (c >= 2) AFG_HIP_CHECK(hipStreamWaitEvent(up, fetched[c & 1], 0));  // its buffer has come back (chunk c - 2)
-        if (int rc = afg_mod_render_hip((uint32_t)(first[c + 1] - first[c]), (const afg_mod_song *)d_songs.p + first[c],
-                                        (const afg_mod_segment *)(din + tick_bytes),
-                                        (const afg_mod_tick *)din + f.tick_base, din + tick_bytes + seg_bytes, (float *)o.p, up))
-            return rc;
-        AFG_HIP_CHECK(hipEventRecord(mixed[c & 1], up));
-        AFG_HIP_CHECK(hipStreamWaitEvent(down, mixed[c & 1], 0));
-        if (chunk_frames)
-            AFG_HIP_CHECK(hipMemcpyAsync((float *)pcm + 2 * f.out_frame, o.p, chunk_frames * 2 * sizeof(float), hipMemcpyDeviceToHost, down));
-        AFG_HIP_CHECK(hipEventRecord(fetched[c & 1], down));
-    }
-    AFG_HIP_CHECK(hipStreamSynchronize(down));
-    AFG_HIP_CHECK(hipStreamSynchronize(up));
+    const int rc = afg_front::run_chunks(
+        chunks.count(),
+        [&](hipStream_t up) -> int {                       // everything the mixer reads goes up once
+            AFG_HIP_CHECK(hipMemcpyAsync(d_in.p, in, in_bytes, hipMemcpyHostToDevice, up));
+            AFG_HIP_CHECK(hipMemcpyAsync(d_songs.p, rel.data(), M * sizeof(afg_mod_song), hipMemcpyHostToDevice, up));
+            return AFG_OK;
+        },
+        /* upload */ nullptr,                              // no per-chunk upload: nothing waits on the host
+        [&](size_t c, int slot, hipStream_t up) -> int {
+            return afg_mod_render_hip((uint32_t)(first[c + 1] - first[c]), (const afg_mod_song *)d_songs.p + first[c],
+                                      (const afg_mod_segment *)(din + tick_bytes), (const afg_mod_tick *)din + songs[first[c]].tick_base,
+                                      din + tick_bytes + seg_bytes, (float *)d_out[slot].p, up);
+        },
+        [&](size_t c, int slot, hipStream_t down) -> int {
+            if (chunks.frames[c])
+                AFG_HIP_CHECK(hipMemcpyAsync((float *)pcm + 2 * start[first[c]], d_out[slot].p, chunks.frames[c] * 2 * sizeof(float),
+                                             hipMemcpyDeviceToHost, down));
+            return AFG_OK;
+        });
+    if (rc) return rc;
     for (size_t j = 0; j < M; j++) {
         const Sim &s = sims[mods[j]];
         afg_batch_item &it = items[which[mods[j]]];

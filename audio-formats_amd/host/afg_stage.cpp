@@ -1,0 +1,115 @@
+// afg_stage.cpp -- the shared half of the host stages (afg_stage.h).
+#include "afg_stage.h"
+#include "../csrc/afg_common.h"
+
+#include <algorithm>
+
+namespace afg_front {
+
+int DevBuf::alloc(size_t bytes)
+{
+    int cur = 0;
+    if (hipGetDevice(&cur) != hipSuccess) cur = 0;
+    if (p && cap >= bytes && dev == cur) return AFG_OK;
+    release();
+    if (int rc = devpool_take(bytes, &p, &cap)) { p = nullptr; cap = 0; return rc; }
+    dev = cur;
+    return AFG_OK;
+}
+
+void DevBuf::release()
+{
+    if (p) devpool_give(p, cap, dev);
+    p = nullptr; cap = 0; dev = -1;
+}
+
+namespace {
+void destroy_on(int dev, hipStream_t st)
+{
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    if (cur != dev) (void)hipSetDevice(dev);
+    (void)hipStreamDestroy(st);
+    if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
+}
+}  // namespace
+
+HandleStream::~HandleStream() { if (stream) destroy_on(dev, stream); }
+
+int HandleStream::current(hipStream_t *st, bool *moved)
+{
+    int cur = 0;
+    AFG_HIP_CHECK(hipGetDevice(&cur));
+    if (stream && dev != cur) {
+        destroy_on(dev, stream);
+        stream = nullptr;
+        if (moved) *moved = true;
+    }
+    if (!stream) {
+        AFG_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        dev = cur;
+    }
+    *st = stream;
+    return AFG_OK;
+}
+
+namespace {
+// the kept upload / download pair, given back drained on every way out
+struct StreamPair {
+    hipStream_t up = nullptr, down = nullptr;
+    ~StreamPair()
+    {
+        for (hipStream_t st : { up, down }) if (st) (void)hipStreamSynchronize(st);
+        if (up && down) streams_give(up, down);
+    }
+};
+struct Events {
+    hipEvent_t e[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    ~Events() { for (hipEvent_t ev : e) if (ev) (void)hipEventDestroy(ev); }
+};
+}  // namespace
+
+int run_chunks(size_t n_chunks, const std::function<int(hipStream_t up)> &before, const ChunkStep &upload, const ChunkStep &launch,
+               const ChunkStep &download)
+{
+    StreamPair pair;
+    AFG_HIP_CHECK(streams_take(&pair.up, &pair.down));
+    const hipStream_t up = pair.up, down = pair.down;
+    // Rings of two events, one per slot.  A wait takes the event's state when it is queued, so at chunk c `uploaded[slot]`
+    // and `fetched[slot]` still stand for chunk c - 2: the last chunk that used the slot.
+    Events ev;
+    for (hipEvent_t &e : ev.e) AFG_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    hipEvent_t *uploaded = ev.e, *done = ev.e + 2, *fetched = ev.e + 4;
+    if (before) if (int rc = before(up)) return rc;
+    for (size_t c = 0; c < n_chunks; c++) {
+        const int slot = (int)(c & 1);
+        if (upload) {
+            if (c >= 2) AFG_HIP_CHECK(hipEventSynchronize(uploaded[slot]));    // the staging is free: chunk c - 2 has gone up
+            if (int rc = upload(c, slot, up)) return rc;
+            AFG_HIP_CHECK(hipEventRecord(uploaded[slot], up));
+        }
+        if (c >= 2) AFG_HIP_CHECK(hipStreamWaitEvent(up, fetched[slot], 0));  // the output buffer is free: chunk c - 2 has come back
+        if (int rc = launch(c, slot, up)) return rc;
+        AFG_HIP_CHECK(hipEventRecord(done[slot], up));
+        AFG_HIP_CHECK(hipStreamWaitEvent(down, done[slot], 0));
+        if (int rc = download(c, slot, down)) return rc;
+        AFG_HIP_CHECK(hipEventRecord(fetched[slot], down));
+    }
+    AFG_HIP_CHECK(hipStreamSynchronize(down));
+    AFG_HIP_CHECK(hipStreamSynchronize(up));
+    return AFG_OK;
+}
+
+SongChunks::SongChunks(const std::vector<uint64_t> &start, const std::vector<uint64_t> &end) : first{ 0 }
+{
+    const size_t M = start.size();
+    for (size_t j = 0; j + 1 < M; j++)
+        if (end[j] - start[first.back()] >= kSongChunkFrames) first.push_back(j + 1);
+    first.push_back(M);
+    for (size_t c = 0; c < count(); c++) {
+        frames.push_back(end[first[c + 1] - 1] - start[first[c]]);
+        max_frames = std::max(max_frames, frames.back());
+    }
+}
+
+}  // namespace afg_front

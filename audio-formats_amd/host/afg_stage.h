@@ -1,0 +1,93 @@
+// afg_stage.h -- what the host stages beside afg_host.cpp share (MOD, XM and WAV decoding, the batch encoder, the write
+// stream): the library's pools, a pooled device buffer, a handle's own stream, and the chunk pipeline of the batch stages.
+#pragma once
+#include "../../include/afg.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <functional>
+#include <memory>
+#include <vector>
+
+namespace afg_front {
+
+// ---- the pools and helper threads of afg_host.cpp ----
+int devpool_take(size_t bytes, void **out, size_t *cap_out);   // device memory, kept between calls
+void devpool_give(void *p, size_t cap, int dev);               // dev: the device it was taken on
+// a page-locked staging lease (pinning memory costs about as much as moving it); the buffer goes back to the pool when
+// the last owner lets go.  NULL: out of memory.
+std::shared_ptr<void> staging_lease(size_t bytes, void **p);
+hipError_t streams_take(hipStream_t *up, hipStream_t *down);   // the kept upload / download pair of the current device
+void streams_give(hipStream_t up, hipStream_t down);           // ... given back drained
+// fn(0) .. fn(n - 1) on the library's pooled host threads; n_threads 0 = the library's choice (afg_batch_decode)
+void parallel_run(size_t n, int n_threads, const std::function<void(size_t)> &fn);
+
+constexpr uint64_t align16(uint64_t n) { return (n + 15) & ~(uint64_t)15; }
+
+// Device memory from the pool, returned to the device it was taken on.
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    int dev = -1;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    int alloc(size_t bytes);                                    // keeps the buffer when it is large enough and on the current device
+    void release();
+};
+
+// The stream of one handle (a stream being read or written): non-blocking, on the device that was current at the last
+// call, destroyed on that device.
+struct HandleStream {
+    hipStream_t stream = nullptr;
+    int dev = -1;
+    HandleStream() = default;
+    HandleStream(const HandleStream &) = delete;
+    HandleStream &operator=(const HandleStream &) = delete;
+    ~HandleStream();
+    // *st: the stream on the caller's current device (`dev` from then on).  When the caller changed devices since the last
+    // call the stream is made again there and *moved (optional) is set: what the handle keeps in device memory is stale.
+    int current(hipStream_t *st, bool *moved = nullptr);
+};
+
+// ---- the chunk pipeline of a batch stage ----
+// Chunks 0 .. n_chunks - 1 go through two slots in turn (chunk c uses slot c & 1) on the kept stream pair: uploads and
+// kernels on `up`, downloads on `down`, so that chunk c + 1 is worked on while chunk c comes back.  The caller keeps the
+// slots' device buffers and stagings; run_chunks owns the pair, the events and the order:
+//   before(up)             (optional) what every chunk needs, queued once ahead of chunk 0
+//   upload(c, slot, up)    (optional) fills the slot's host staging and queues its upload; the host first waits until the
+//                          upload of chunk c - 2 has left that staging.  Without it nothing ever waits on the host.
+//   launch(c, slot, up)    the kernels, writing the slot's output buffer; they wait until chunk c - 2 has come back from it
+//   download(c, slot, down) queued behind the chunk's kernels
+// A step returns AFG_OK or the status run_chunks returns at once; on every way out both streams are drained before the
+// pair goes back, so no buffer of the caller is still in use when run_chunks has returned.
+using ChunkStep = std::function<int(size_t c, int slot, hipStream_t st)>;
+int run_chunks(size_t n_chunks, const std::function<int(hipStream_t up)> &before, const ChunkStep &upload, const ChunkStep &launch,
+               const ChunkStep &download);
+
+// The chunks of the MOD and XM stages: song j fills output frames [start[j], end[j]) of the batch's PCM plane, and a chunk
+// is closed behind the song that brings it to kSongChunkFrames.  Chunk c is songs [first[c], first[c + 1]).
+constexpr uint64_t kSongChunkFrames = (uint64_t)16 << 20;          // 128 MB of PCM
+struct SongChunks {
+    std::vector<size_t> first;
+    std::vector<uint64_t> frames;                                   // per chunk: from its first song's start to its last song's end
+    uint64_t max_frames = 1;                                        // of the longest chunk
+    SongChunks(const std::vector<uint64_t> &start, const std::vector<uint64_t> &end);
+    size_t count() const { return first.size() - 1; }
+    // the song records as the mixer takes them: output frame and tick base count from the chunk's first song
+    template <typename Song> std::vector<Song> relative(const std::vector<Song> &songs) const
+    {
+        std::vector<Song> rel(songs);
+        for (size_t c = 0; c < count(); c++)
+            for (size_t j = first[c]; j < first[c + 1]; j++) {
+                rel[j].out_frame -= songs[first[c]].out_frame;
+                rel[j].tick_base -= songs[first[c]].tick_base;
+            }
+        return rel;
+    }
+};
+
+}  // namespace afg_front

@@ -5,7 +5,7 @@
 // finalizeEncoding computes them (:571-606).  Sample conversions are writeSamples' (:482-527); the TPDF dither of
 // :674-701 (on by default in the reference, EncodingOptions.enableDither stream.d:66) draws from libc rand() there:
 // afg_wav_encode_dithered takes the generator as a callback so that the result is reproducible and testable.
-#include "../../include/afg.h"
+#include "afg_write_stream.h"                               // sample_size
 
 #include <cmath>
 #include <cstdint>
@@ -14,17 +14,7 @@
 
 namespace {
 
-int sample_size(int format)
-{
-    switch (format) {
-    case AFG_WAV_S8: return 1;
-    case AFG_WAV_S16LE: return 2;
-    case AFG_WAV_S24LE: return 3;
-    case AFG_WAV_FP32LE: return 4;
-    case AFG_WAV_FP64LE: return 8;
-    default: return 0;
-    }
-}
+using afg_write::sample_size;
 
 void put16(uint8_t *&p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p += 2; }
 void put32(uint8_t *&p, uint32_t v) { put16(p, v & 0xffff); put16(p, v >> 16); }

@@ -2,14 +2,10 @@
 // of WAV decoding (afg_wav_stage.cpp): a stream's reads and the batch path's WAV stage.  The sample conversion itself
 // (readSamples!float, wav.d:242-344) is csrc/wav_pcm.hip; afg_wav.cpp is the writer.
 #pragma once
-#include "../../include/afg.h"
-#include "afg_mod_front.h"                                  // DevBuf
-
-#include <hip/hip_runtime.h>
+#include "afg_stage.h"
 
 #include <cstddef>
 #include <cstdint>
-#include <functional>
 #include <memory>
 #include <vector>
 
@@ -42,7 +38,6 @@ inline int bytes_per_sample(const Info &info) { return info.bits / 8; }
 // samples at a time through a FIFO.
 class StreamConv {
 public:
-    ~StreamConv();
     Info info;
     // readSamples!float behind stream.d:557-570: the frames read; *failed set when the reference's read sets its error
     // (the position has advanced by the clamped request all the same, wav.d:253).  -1: device error.
@@ -54,9 +49,8 @@ private:
     uint32_t position_ = 0;                                 // _framePosition
     std::vector<float> fifo_;                               // frames [fifo_frame_, fifo_frame_ + fifo_.size() / channels)
     uint64_t fifo_frame_ = 0;
-    afg_mod::DevBuf in_, out_, spans_;                      // device memory from the library's pool
-    hipStream_t stream_ = nullptr;
-    int stream_dev_ = -1;
+    afg_front::DevBuf in_, out_, spans_;                    // device memory from the library's pool
+    afg_front::HandleStream stream_;
 };
 
 // The batch path's WAV stage: the files listed in `which` that pass scan() have their sample bytes staged as they are in
@@ -65,8 +59,7 @@ private:
 // or whose format readSamples refuses, becomes an error item with the reference's decoding-error message.  Files that do
 // not pass the scan are left alone.
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                const std::function<void(size_t, const std::function<void(size_t)> &)> &run_parallel,
-                afg_batch_item *items, std::shared_ptr<void> &keep);
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep);
 
 extern const char *const kMessageDecodingError;             // internals.d: kErrorDecodingError
 

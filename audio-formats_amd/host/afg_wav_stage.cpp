@@ -11,34 +11,17 @@
 #include <atomic>
 #include <cstring>
 
-namespace afg_front {
-// page-locked staging and the kept stream pair (afg_host.cpp)
-std::shared_ptr<void> staging_lease(size_t bytes, void **p);
-hipError_t streams_take(hipStream_t *up, hipStream_t *down);
-void streams_give(hipStream_t up, hipStream_t down);
-}  // namespace afg_front
-
 namespace afg_wav {
+
+using afg_front::align16;
 
 const char *const kMessageDecodingError = "Decoder encountered an error";
 
 namespace {
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 constexpr uint64_t kStreamChunkSamples = (uint64_t)1 << 18;               // a stream's FIFO refill: 1 MB of floats
 constexpr uint64_t kBatchChunkSamples = (uint64_t)8 << 20;                // a batch chunk: 32 MB of floats, 8-64 MB of input
 static_assert(kBatchChunkSamples % AFG_WAV_TILE_SAMPLES == 0, "files are cut at tile boundaries");
 }  // namespace
-
-StreamConv::~StreamConv()
-{
-    if (stream_) {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (cur != stream_dev_) (void)hipSetDevice(stream_dev_);
-        (void)hipStreamDestroy(stream_);
-        if (cur != stream_dev_ && cur >= 0) (void)hipSetDevice(cur);
-    }
-}
 
 bool StreamConv::seek(int frame)
 {
@@ -52,19 +35,8 @@ int StreamConv::decode(const uint8_t *file, uint64_t frame0, uint64_t frames)
 {
     const uint64_t C = (uint64_t)info.channels, B = (uint64_t)bytes_per_sample(info);
     const uint64_t count = frames * C, bytes = count * B;
-    int dev = 0;
-    AFG_HIP_CHECK(hipGetDevice(&dev));
-    if (stream_ && stream_dev_ != dev) {
-        // the caller changed devices between reads: the stream is made again there (the buffers follow by themselves)
-        (void)hipSetDevice(stream_dev_);
-        (void)hipStreamDestroy(stream_);
-        (void)hipSetDevice(dev);
-        stream_ = nullptr;
-    }
-    if (!stream_) {
-        AFG_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-        stream_dev_ = dev;
-    }
+    hipStream_t st = nullptr;                                             // (after a change of device the buffers follow by themselves)
+    if (int rc = stream_.current(&st)) return rc;
     afg_wav_span span;
     std::memset(&span, 0, sizeof(span));
     span.count = count;
@@ -74,15 +46,15 @@ int StreamConv::decode(const uint8_t *file, uint64_t frame0, uint64_t frames)
     if (in_.alloc(in_bytes) || out_.alloc(out_floats * sizeof(float)) || spans_.alloc(sizeof(span))) return AFG_ERR_OOM;
     fifo_.resize((size_t)count);
     fifo_frame_ = frame0;
-    AFG_HIP_CHECK(hipMemcpyAsync(spans_.p, &span, sizeof(span), hipMemcpyHostToDevice, stream_));
-    AFG_HIP_CHECK(hipMemcpyAsync(in_.p, file + info.samples_off + frame0 * C * B, bytes, hipMemcpyHostToDevice, stream_));
+    AFG_HIP_CHECK(hipMemcpyAsync(spans_.p, &span, sizeof(span), hipMemcpyHostToDevice, st));
+    AFG_HIP_CHECK(hipMemcpyAsync(in_.p, file + info.samples_off + frame0 * C * B, bytes, hipMemcpyHostToDevice, st));
     if (int rc = afg_wav_convert_hip(1, (const afg_wav_span *)spans_.p, tiles, (const uint8_t *)in_.p, in_bytes, (float *)out_.p,
-                                     out_floats, stream_)) {
+                                     out_floats, st)) {
         fifo_.clear();
         return rc;
     }
-    hipError_t e = hipMemcpyAsync(fifo_.data(), out_.p, count * sizeof(float), hipMemcpyDeviceToHost, stream_);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    hipError_t e = hipMemcpyAsync(fifo_.data(), out_.p, count * sizeof(float), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         fifo_.clear();
         afg::set_error("WAV stream: %s", hipGetErrorString(e));
@@ -121,14 +93,13 @@ int StreamConv::read(const uint8_t *file, size_t size, float *out, int frames, b
 }
 
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                const std::function<void(size_t, const std::function<void(size_t)> &)> &run_parallel,
-                afg_batch_item *items, std::shared_ptr<void> &keep)
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep)
 {
     if (which.empty()) return AFG_OK;
     // ---- the scan, one file per helper-thread job ----
     struct File { bool ok = false; Info info; int kind = -1; uint64_t out_off = 0; };
     std::vector<File> files(which.size());
-    run_parallel(which.size(), [&](size_t k) {
+    afg_front::parallel_run(which.size(), n_threads, [&](size_t k) {
         const int i = which[k];
         File &f = files[k];
         if (!data[i] || scan(data[i], length[i], &f.info) != nullptr) return;
@@ -205,57 +176,45 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
     std::shared_ptr<void> stage_owner[2];
     for (int b = 0; b < (C > 1 ? 2 : 1); b++)
         if (!(stage_owner[b] = afg_front::staging_lease((size_t)max_in, &stage[b]))) return AFG_ERR_OOM;
-    afg_mod::DevBuf d_spans, d_in[2], d_out[2];
+    afg_front::DevBuf d_spans, d_in[2], d_out[2];
     if (int rc = d_spans.alloc(std::max<size_t>(spans.size(), 1) * sizeof(afg_wav_span))) return rc;
     for (int b = 0; b < (C > 1 ? 2 : 1); b++) {
         if (int rc = d_in[b].alloc((size_t)max_in)) return rc;
         if (int rc = d_out[b].alloc((size_t)max_out * sizeof(float))) return rc;
     }
-    // the kept upload / download pair, given back drained on every way out
-    struct Pair {
-        hipStream_t up = nullptr, down = nullptr;
-        ~Pair()
-        {
-            for (hipStream_t st : { up, down }) if (st) (void)hipStreamSynchronize(st);
-            if (up && down) afg_front::streams_give(up, down);
-        }
-    } pair;
-    AFG_HIP_CHECK(afg_front::streams_take(&pair.up, &pair.down));
-    hipStream_t up = pair.up, down = pair.down;
-    // rings of two: chunk c's staging is free once chunk c - 2 has gone up (the host waits), its output buffer once
-    // chunk c - 2 has come back (the upload stream waits)
-    struct EventGuard { hipEvent_t *e; ~EventGuard() { for (int k = 0; k < 6; k++) if (e[k]) (void)hipEventDestroy(e[k]); } };
-    hipEvent_t ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    EventGuard g_ev{ ev };
-    for (int k = 0; k < 6; k++) AFG_HIP_CHECK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
-    hipEvent_t *uploaded = ev, *converted = ev + 2, *fetched = ev + 4;
-    AFG_HIP_CHECK(hipMemcpyAsync(d_spans.p, spans.data(), spans.size() * sizeof(afg_wav_span), hipMemcpyHostToDevice, up));
-    for (size_t c = 0; c < C; c++) {
-        const int b = (int)(c & 1);
-        const size_t p0 = first[c], p1 = first[c + 1];
-        const uint64_t in_bytes = spans[p1 - 1].in_off + align16(spans[p1 - 1].count * (uint64_t)bytes_per_sample(files[pieces[p1 - 1].file].info));
-        const uint64_t out_floats = spans[p1 - 1].out_off + spans[p1 - 1].count;
-        if (c >= 2) AFG_HIP_CHECK(hipEventSynchronize(uploaded[b]));
-        uint8_t *hin = (uint8_t *)stage[b];
-        run_parallel(p1 - p0, [&](size_t j) {
-            const Piece &pc = pieces[p0 + j];
-            const afg_wav_span &sp = spans[p0 + j];
-            std::memcpy(hin + sp.in_off, data[which[pc.file]] + pc.src_byte,
-                        (size_t)(sp.count * (uint64_t)bytes_per_sample(files[pc.file].info)));
+    // what chunk c takes up and brings back: both end with its last piece
+    auto in_bytes = [&](size_t c) {
+        const size_t p = first[c + 1] - 1;
+        return spans[p].in_off + align16(spans[p].count * (uint64_t)bytes_per_sample(files[pieces[p].file].info));
+    };
+    auto out_floats = [&](size_t c) { return spans[first[c + 1] - 1].out_off + spans[first[c + 1] - 1].count; };
+    const int rc = afg_front::run_chunks(
+        C,
+        [&](hipStream_t up) -> int {
+            AFG_HIP_CHECK(hipMemcpyAsync(d_spans.p, spans.data(), spans.size() * sizeof(afg_wav_span), hipMemcpyHostToDevice, up));
+            return AFG_OK;
+        },
+        [&](size_t c, int b, hipStream_t up) -> int {
+            const size_t p0 = first[c];
+            uint8_t *hin = (uint8_t *)stage[b];
+            afg_front::parallel_run(first[c + 1] - p0, n_threads, [&](size_t j) {
+                const Piece &pc = pieces[p0 + j];
+                const afg_wav_span &sp = spans[p0 + j];
+                std::memcpy(hin + sp.in_off, data[which[pc.file]] + pc.src_byte,
+                            (size_t)(sp.count * (uint64_t)bytes_per_sample(files[pc.file].info)));
+            });
+            AFG_HIP_CHECK(hipMemcpyAsync(d_in[b].p, hin, (size_t)in_bytes(c), hipMemcpyHostToDevice, up));
+            return AFG_OK;
+        },
+        [&](size_t c, int b, hipStream_t up) -> int {
+            return afg_wav_convert_hip(first[c + 1] - first[c], (const afg_wav_span *)d_spans.p + first[c], tiles[c], (const uint8_t *)d_in[b].p,
+                                       in_bytes(c), (float *)d_out[b].p, (out_floats(c) + 3) & ~(uint64_t)3, up);
+        },
+        [&](size_t c, int b, hipStream_t down) -> int {
+            AFG_HIP_CHECK(hipMemcpyAsync((float *)pcm + chunk_out0[c], d_out[b].p, (size_t)out_floats(c) * sizeof(float), hipMemcpyDeviceToHost, down));
+            return AFG_OK;
         });
-        AFG_HIP_CHECK(hipMemcpyAsync(d_in[b].p, hin, (size_t)in_bytes, hipMemcpyHostToDevice, up));
-        AFG_HIP_CHECK(hipEventRecord(uploaded[b], up));
-        if (c >= 2) AFG_HIP_CHECK(hipStreamWaitEvent(up, fetched[b], 0));
-        if (int rc = afg_wav_convert_hip(p1 - p0, (const afg_wav_span *)d_spans.p + p0, tiles[c], (const uint8_t *)d_in[b].p, in_bytes,
-                                         (float *)d_out[b].p, (out_floats + 3) & ~(uint64_t)3, up))
-            return rc;
-        AFG_HIP_CHECK(hipEventRecord(converted[b], up));
-        AFG_HIP_CHECK(hipStreamWaitEvent(down, converted[b], 0));
-        AFG_HIP_CHECK(hipMemcpyAsync((float *)pcm + chunk_out0[c], d_out[b].p, (size_t)out_floats * sizeof(float), hipMemcpyDeviceToHost, down));
-        AFG_HIP_CHECK(hipEventRecord(fetched[b], down));
-    }
-    AFG_HIP_CHECK(hipStreamSynchronize(down));
-    AFG_HIP_CHECK(hipStreamSynchronize(up));
+    if (rc) return rc;
     for (size_t k = 0; k < files.size(); k++) {
         const File &f = files[k];
         if (!f.ok) continue;

@@ -8,7 +8,7 @@
 // lane can enter in the middle.  Doubles written to an fp64 stream are stored as they are (wav.d:538-546).
 // QOA: writes queue frames and finalize encodes the stream with one afg_qoa_encode_hip call: the encoder's LMS state
 // runs through the whole stream, so there is nothing to win by encoding earlier.
-#include "afg_mod_front.h"
+#include "afg_stage.h"
 #include "afg_write_stream.h"
 #include "../csrc/afg_common.h"
 
@@ -23,19 +23,6 @@ namespace {
 const char *const kErrorUnsupportedEncodingFormat = "Unsupported encoding format, maybe check your audio-formats configuration";
 const char *const kErrorEncodingError = "Encoder encountered an error";
 constexpr size_t kFlushSamples = (size_t)1 << 18;
-constexpr size_t kWavHeader = 44;
-
-int sample_size(int format)
-{
-    switch (format) {
-    case AFG_WAV_S8: return 1;
-    case AFG_WAV_S16LE: return 2;
-    case AFG_WAV_S24LE: return 3;
-    case AFG_WAV_FP32LE: return 4;
-    case AFG_WAV_FP64LE: return 8;
-    default: return 0;
-    }
-}
 void put32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
 }  // namespace
 
@@ -57,21 +44,9 @@ struct Writer {
     std::vector<int16_t> qoa_i16;
     bool qoa_int = false;
     uint64_t qoa_frames = 0;
-    afg_mod::DevBuf d_in, d_out, d_recs;
+    afg_front::DevBuf d_in, d_out, d_recs;
     std::vector<uint8_t> scratch;
-    hipStream_t stream = nullptr;
-    int stream_dev = -1;
-
-    ~Writer()
-    {
-        if (stream) {
-            int cur = -1;
-            (void)hipGetDevice(&cur);
-            if (cur != stream_dev) (void)hipSetDevice(stream_dev);
-            (void)hipStreamDestroy(stream);
-            if (cur != stream_dev && cur >= 0) (void)hipSetDevice(cur);
-        }
-    }
+    afg_front::HandleStream own_stream;     // follows the caller's device from write to write
 
     size_t size() const { return to_memory ? mem_pos : buf.size(); }
     uint8_t *data() { return to_memory ? mem : buf.data(); }
@@ -87,23 +62,6 @@ struct Writer {
             buf.insert(buf.end(), p, p + n);
         }
         return true;
-    }
-
-    int device_stream()
-    {
-        int dev = 0;
-        AFG_HIP_CHECK(hipGetDevice(&dev));
-        if (stream && stream_dev != dev) {              // the caller changed devices between writes
-            (void)hipSetDevice(stream_dev);
-            (void)hipStreamDestroy(stream);
-            (void)hipSetDevice(dev);
-            stream = nullptr;
-        }
-        if (!stream) {
-            AFG_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-            stream_dev = dev;
-        }
-        return AFG_OK;
     }
 
     // packs the queued samples and appends their bytes
@@ -122,7 +80,8 @@ struct Writer {
                 return AFG_ERR_INVALID;
             append(scratch.data() + kWavHeader, bytes);
         } else {
-            if (int rc = device_stream()) return rc;
+            hipStream_t stream = nullptr;
+            if (int rc = own_stream.current(&stream)) return rc;
             afg_wav_pack_span span;
             std::memset(&span, 0, sizeof(span));
             span.count = count;
@@ -166,7 +125,8 @@ struct Writer {
         if (qoa_frames > 0xffffffffull) return AFG_ERR_INVALID;                 // qoa.d:660: the frame count is 32 bits
         const uint64_t size = afg_qoa_encoded_size((uint32_t)qoa_frames, (uint32_t)channels);
         if (to_memory && size > mem_cap) return AFG_ERR_INVALID;
-        if (int rc = device_stream()) return rc;
+        hipStream_t stream = nullptr;
+        if (int rc = own_stream.current(&stream)) return rc;
         afg_qoa_enc_stream rec;
         std::memset(&rec, 0, sizeof(rec));
         rec.samples = (uint32_t)qoa_frames;

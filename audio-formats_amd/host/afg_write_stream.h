@@ -1,14 +1,21 @@
-// afg_write_stream.h -- what the write stream (afg_write_stream.cpp), the batch encoder (afg_encode_stage.cpp) and the
-// handle (afg_host.cpp) know of each other.
+// afg_write_stream.h -- what the write stream (afg_write_stream.cpp), the batch encoder (afg_encode_stage.cpp), the host
+// WAV writer (afg_wav.cpp) and the handle (afg_host.cpp) know of each other.
 #pragma once
 #include "../../include/afg.h"
 
 #include <cstddef>
-#include <functional>
 
 namespace afg_write {
 struct Writer;                          // the state of a stream opened for writing (afg_write_stream.cpp)
 void destroy(Writer *w);
+
+// what every WAV writer puts out: the header's length and a sample's bytes (0: not a sample format)
+constexpr size_t kWavHeader = 44;
+constexpr int sample_size(int format)
+{
+    return format == AFG_WAV_S8 ? 1 : format == AFG_WAV_S16LE ? 2 : format == AFG_WAV_S24LE ? 3 : format == AFG_WAV_FP32LE ? 4
+           : format == AFG_WAV_FP64LE ? 8 : 0;
+}
 }  // namespace afg_write
 
 namespace afg_front {
@@ -17,6 +24,4 @@ namespace afg_front {
 afg_stream *stream_for_writing(afg_write::Writer *w, int format, int channels, float samplerate, const char *error);
 afg_write::Writer *stream_writer(const afg_stream *s);         // NULL: not opened for writing
 void stream_set_error(afg_stream *s, const char *message);
-// fn(0) .. fn(n - 1) on the library's pooled host threads; n_threads 0 = the library's choice (afg_batch_decode)
-void parallel_run(size_t n, int n_threads, const std::function<void(size_t)> &fn);
 }  // namespace afg_front

@@ -2,11 +2,11 @@
 // as a tick-by-tick state machine that emits the mixer's work as afg_xm_tick / afg_xm_segment records and a side table of
 // floats (include/afg.h).  The device mixer is csrc/xm_mix.hip; forward position chains are jumped with csrc/mod_chain.h.
 #pragma once
-#include "afg_mod_front.h"
+#include "afg_mod_front.h"                                  // kMessageCapped
+#include "afg_stage.h"
 
 #include <cstddef>
 #include <cstdint>
-#include <functional>
 #include <memory>
 #include <vector>
 
@@ -174,14 +174,12 @@ uint64_t render_song(Song &song, Records &rec, bool *capped);
 // An XM stream: each read runs the control layer for exactly the read's frames and mixes them on the device.
 class StreamMix {
 public:
-    ~StreamMix();
     int read(float *out, int frames);                       // -1: device error (afg_last_error says which)
     Song song;
 private:
-    afg_mod::DevBuf data_, recs_, out_;
+    afg_front::DevBuf data_, recs_, out_;
     bool uploaded_ = false;
-    hipStream_t stream_ = nullptr;
-    int stream_dev_ = -1;
+    afg_front::HandleStream stream_;
     Records rec_;
     std::vector<uint8_t> staging_;
     std::vector<float> bounce_;
@@ -190,7 +188,6 @@ private:
 // The batch path's XM stage, shaped like afg_mod::batch_stage: the files of `which` that pass the probe are simulated on
 // the helper threads, mixed in chunks with mix and download overlapped, and their items filled in.
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                const std::function<void(size_t, const std::function<void(size_t)> &)> &run_parallel,
-                afg_batch_item *items, std::shared_ptr<void> &keep);
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep);
 
 }  // namespace afg_xm

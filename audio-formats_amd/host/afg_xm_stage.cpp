@@ -1,8 +1,8 @@
 // afg_xm_stage.cpp -- the device side of XM decoding: a stream's reads, the batch path's XM stage and afg_xm_parse.
 //
-// A sibling of afg_mod_stage.cpp: the same pools (afg_mod::DevBuf, the page-locked staging and the kept stream pair of
-// afg_host.cpp), the same chunks of about 128 MB of PCM with chunk c + 1 mixed while chunk c comes back.  What differs is
-// the record set: XM adds the side table of floats and its own song, tick and segment records.
+// Like the MOD stage it runs on what afg_stage.h gives every stage: pooled device buffers, page-locked staging, and chunks
+// of about 128 MB of PCM with chunk c + 1 mixed while chunk c comes back.  Its record set is its own: the side table of
+// floats and XM's song, tick and segment records.
 #include "afg_xm_front.h"
 #include "../csrc/afg_common.h"
 
@@ -11,17 +11,12 @@
 #include <cstring>
 #include <new>
 
-namespace afg_front {
-std::shared_ptr<void> staging_lease(size_t bytes, void **p);
-hipError_t streams_take(hipStream_t *up, hipStream_t *down);
-void streams_give(hipStream_t up, hipStream_t down);
-}  // namespace afg_front
-
 namespace afg_xm {
 
-namespace {
+using afg_front::align16;
+using afg_front::DevBuf;
 
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
+namespace {
 
 // The inputs of one launch in one buffer: ticks, segments, side table, sample data (each 16-byte aligned)
 struct InLayout {
@@ -37,40 +32,21 @@ struct InLayout {
 
 }  // namespace
 
-StreamMix::~StreamMix()
-{
-    if (stream_) {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (cur != stream_dev_) (void)hipSetDevice(stream_dev_);
-        (void)hipStreamDestroy(stream_);
-        if (cur != stream_dev_ && cur >= 0) (void)hipSetDevice(cur);
-    }
-}
-
 int StreamMix::read(float *out, int frames)
 {
     if (frames <= 0 || song.loop_count() >= 1) return 0;            // stream.d:600: the song is finished
     rec_.clear();
     const int n = (int)song.render((uint64_t)frames, false, rec_);  // exactly `frames`: zeros once the loop count is raised
     if (rec_.overflow) { afg::set_error(kMessageTooManyRecords); return -1; }
-    int dev = 0;
-    AFG_HIP_CHECK(hipGetDevice(&dev));
-    if (stream_ && stream_dev_ != dev) {
-        (void)hipSetDevice(stream_dev_);
-        (void)hipStreamDestroy(stream_);
-        (void)hipSetDevice(dev);
-        stream_ = nullptr;
-        uploaded_ = false;
-    }
-    if (!stream_) {
-        AFG_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-        stream_dev_ = dev;
-    }
+    hipStream_t st = nullptr;
+    bool moved = false;
+    const int rc = stream_.current(&st, &moved);
+    if (moved) uploaded_ = false;     // the caller changed devices between reads: the sample data is uploaded again
+    if (rc) return rc;
     const std::vector<uint8_t> &data = song.sample_data();
-    if (!uploaded_ || data_.dev != dev) {
+    if (!uploaded_ || data_.dev != stream_.dev) {
         if (data_.alloc(data.size())) return -1;
-        AFG_HIP_CHECK(hipMemcpyAsync(data_.p, data.data(), data.size(), hipMemcpyHostToDevice, stream_));
+        AFG_HIP_CHECK(hipMemcpyAsync(data_.p, data.data(), data.size(), hipMemcpyHostToDevice, st));
         uploaded_ = true;
     }
     const InLayout L(rec_.ticks.size(), rec_.segs.size(), rec_.aux.size(), 0);
@@ -86,21 +62,20 @@ int StreamMix::read(float *out, int frames)
     if (!rec_.aux.empty()) std::memcpy(staging_.data() + L.aux, rec_.aux.data(), rec_.aux.size() * sizeof(float));
     const size_t out_bytes = (size_t)n * 2 * sizeof(float);
     if (recs_.alloc(staging_.size()) || out_.alloc(out_bytes)) return -1;
-    AFG_HIP_CHECK(hipMemcpyAsync(recs_.p, staging_.data(), staging_.size(), hipMemcpyHostToDevice, stream_));
+    AFG_HIP_CHECK(hipMemcpyAsync(recs_.p, staging_.data(), staging_.size(), hipMemcpyHostToDevice, st));
     const uint8_t *r = (const uint8_t *)recs_.p;
     if (afg_xm_render_hip(1, (const afg_xm_song *)(r + song_at), (const afg_xm_segment *)(r + L.segs), (const afg_xm_tick *)(r + L.ticks),
-                          (const uint8_t *)data_.p, (const float *)(r + L.aux), (float *)out_.p, stream_))
+                          (const uint8_t *)data_.p, (const float *)(r + L.aux), (float *)out_.p, st))
         return -1;
     float *dst = out;
     if (!dst) { bounce_.resize((size_t)n * 2); dst = bounce_.data(); }
-    AFG_HIP_CHECK(hipMemcpyAsync(dst, out_.p, out_bytes, hipMemcpyDeviceToHost, stream_));
-    AFG_HIP_CHECK(hipStreamSynchronize(stream_));
+    AFG_HIP_CHECK(hipMemcpyAsync(dst, out_.p, out_bytes, hipMemcpyDeviceToHost, st));
+    AFG_HIP_CHECK(hipStreamSynchronize(st));
     return n;
 }
 
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                const std::function<void(size_t, const std::function<void(size_t)> &)> &run_parallel,
-                afg_batch_item *items, std::shared_ptr<void> &keep)
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep)
 {
     if (which.empty()) return AFG_OK;
     struct Sim {
@@ -111,7 +86,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
     };
     std::vector<Sim> sims(which.size());
     std::atomic<bool> oom{ false };
-    run_parallel(which.size(), [&](size_t k) {
+    afg_front::parallel_run(which.size(), n_threads, [&](size_t k) {
         const int i = which[k];
         try {
             Sim &s = sims[k];
@@ -139,6 +114,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
     // ---- layout: songs start on 16-frame boundaries of the PCM plane, so that every lane stores whole lines ----
     const size_t M = mods.size();
     std::vector<afg_xm_song> songs(M);
+    std::vector<uint64_t> start(M), end(M);
     uint64_t frames = 0, n_ticks = 0, n_segs = 0, n_aux = 0, data_bytes = 0;
     for (size_t j = 0; j < M; j++) {
         const Sim &s = sims[mods[j]];
@@ -147,7 +123,9 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
         g.out_frame = frames; g.tick_base = n_ticks; g.seg_base = n_segs; g.aux_base = n_aux; g.sample_base = data_bytes;
         g.n_ticks = (uint32_t)s.rec.ticks.size();
         g.sample_bytes = (uint32_t)s.song.sample_data().size();
+        start[j] = frames;
         frames += (s.frames + 15) & ~(uint64_t)15;
+        end[j] = frames;
         n_ticks += s.rec.ticks.size(); n_segs += s.rec.segs.size(); n_aux += s.rec.aux.size();
         data_bytes += align16(s.song.sample_data().size());
     }
@@ -159,7 +137,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
     std::shared_ptr<void> in_owner = afg_front::staging_lease(L.bytes, &in);
     if (!in_owner) return AFG_ERR_OOM;
     uint8_t *hin = (uint8_t *)in;
-    run_parallel(M, [&](size_t j) {
+    afg_front::parallel_run(M, n_threads, [&](size_t j) {
         const Sim &s = sims[mods[j]];
         const afg_xm_song &g = songs[j];
         if (!s.rec.ticks.empty()) std::memcpy(hin + L.ticks + g.tick_base * sizeof(afg_xm_tick), s.rec.ticks.data(), s.rec.ticks.size() * sizeof(afg_xm_tick));
@@ -168,61 +146,36 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
         std::memcpy(hin + L.data + g.sample_base, s.song.sample_data().data(), s.song.sample_data().size());
     });
 
-    // ---- chunks of songs, about kChunkFrames of output each: mix chunk c + 1 while chunk c comes back ----
-    constexpr uint64_t kChunkFrames = (uint64_t)16 << 20;
-    auto end_of = [&](size_t j) { return songs[j].out_frame + ((sims[mods[j]].frames + 15) & ~(uint64_t)15); };
-    std::vector<size_t> first{ 0 };
-    for (size_t j = 0; j + 1 < M; j++)
-        if (end_of(j) - songs[first.back()].out_frame >= kChunkFrames) first.push_back(j + 1);
-    first.push_back(M);
-    const size_t C = first.size() - 1;
-    std::vector<afg_xm_song> rel(songs);
-    uint64_t max_chunk = 1;
-    for (size_t c = 0; c < C; c++) {
-        const afg_xm_song &f = songs[first[c]];
-        for (size_t j = first[c]; j < first[c + 1]; j++) { rel[j].out_frame -= f.out_frame; rel[j].tick_base -= f.tick_base; }
-        max_chunk = std::max<uint64_t>(max_chunk, end_of(first[c + 1] - 1) - f.out_frame);
-    }
-    afg_mod::DevBuf d_in, d_songs, d_out[2];
+    // ---- chunks of songs, about 128 MB of output each: chunk c + 1 is mixed while chunk c comes back ----
+    const afg_front::SongChunks chunks(start, end);
+    const std::vector<size_t> &first = chunks.first;
+    const std::vector<afg_xm_song> rel = chunks.relative(songs);
+    DevBuf d_in, d_songs, d_out[2];
     if (int rc = d_in.alloc(L.bytes)) return rc;
     if (int rc = d_songs.alloc(M * sizeof(afg_xm_song))) return rc;
-    for (afg_mod::DevBuf &b : d_out) if (int rc = b.alloc(max_chunk * 2 * sizeof(float))) return rc;
-    struct Pair {
-        hipStream_t up = nullptr, down = nullptr;
-        ~Pair()
-        {
-            for (hipStream_t st : { up, down }) if (st) (void)hipStreamSynchronize(st);
-            if (up && down) afg_front::streams_give(up, down);
-        }
-    } pair;
-    AFG_HIP_CHECK(afg_front::streams_take(&pair.up, &pair.down));
-    hipStream_t up = pair.up, down = pair.down;
-    struct EventGuard { hipEvent_t *e; ~EventGuard() { for (int k = 0; k < 4; k++) if (e[k]) (void)hipEventDestroy(e[k]); } };
-    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-    EventGuard g_ev{ ev };
-    for (int k = 0; k < 4; k++) AFG_HIP_CHECK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
-    hipEvent_t *mixed = ev, *fetched = ev + 2;
-    AFG_HIP_CHECK(hipMemcpyAsync(d_in.p, in, L.bytes, hipMemcpyHostToDevice, up));
-    AFG_HIP_CHECK(hipMemcpyAsync(d_songs.p, rel.data(), M * sizeof(afg_xm_song), hipMemcpyHostToDevice, up));
+    for (DevBuf &b : d_out) if (int rc = b.alloc(chunks.max_frames * 2 * sizeof(float))) return rc;
     const uint8_t *din = (const uint8_t *)d_in.p;
-    for (size_t c = 0; c < C; c++) {
-        const afg_xm_song &f = songs[first[c]];
-        const uint64_t chunk_frames = end_of(first[c + 1] - 1) - f.out_frame;
-        afg_mod::DevBuf &o = d_out[c & 1];
-        if (c >= 2) AFG_HIP_CHECK(hipStreamWaitEvent(up, fetched[c & 1], 0));
-        // the padding frames between songs are never mixed; the items do not reach them
-        if (int rc = afg_xm_render_hip((uint32_t)(first[c + 1] - first[c]), (const afg_xm_song *)d_songs.p + first[c],
-                                       (const afg_xm_segment *)(din + L.segs), (const afg_xm_tick *)(din + L.ticks) + f.tick_base,
-                                       din + L.data, (const float *)(din + L.aux), (float *)o.p, up))
-            return rc;
-        AFG_HIP_CHECK(hipEventRecord(mixed[c & 1], up));
-        AFG_HIP_CHECK(hipStreamWaitEvent(down, mixed[c & 1], 0));
-        if (chunk_frames)
-            AFG_HIP_CHECK(hipMemcpyAsync((float *)pcm + 2 * f.out_frame, o.p, chunk_frames * 2 * sizeof(float), hipMemcpyDeviceToHost, down));
-        AFG_HIP_CHECK(hipEventRecord(fetched[c & 1], down));
-    }
-    AFG_HIP_CHECK(hipStreamSynchronize(down));
-    AFG_HIP_CHECK(hipStreamSynchronize(up));
+    const int rc = afg_front::run_chunks(
+        chunks.count(),
+        [&](hipStream_t up) -> int {                       // everything the mixer reads goes up once
+            AFG_HIP_CHECK(hipMemcpyAsync(d_in.p, in, L.bytes, hipMemcpyHostToDevice, up));
+            AFG_HIP_CHECK(hipMemcpyAsync(d_songs.p, rel.data(), M * sizeof(afg_xm_song), hipMemcpyHostToDevice, up));
+            return AFG_OK;
+        },
+        /* upload */ nullptr,                              // no per-chunk upload: nothing waits on the host
+        [&](size_t c, int slot, hipStream_t up) -> int {
+            // the padding frames between songs are never mixed; the items do not reach them
+            return afg_xm_render_hip((uint32_t)(first[c + 1] - first[c]), (const afg_xm_song *)d_songs.p + first[c],
+                                     (const afg_xm_segment *)(din + L.segs), (const afg_xm_tick *)(din + L.ticks) + songs[first[c]].tick_base,
+                                     din + L.data, (const float *)(din + L.aux), (float *)d_out[slot].p, up);
+        },
+        [&](size_t c, int slot, hipStream_t down) -> int {
+            if (chunks.frames[c])
+                AFG_HIP_CHECK(hipMemcpyAsync((float *)pcm + 2 * start[first[c]], d_out[slot].p, chunks.frames[c] * 2 * sizeof(float),
+                                             hipMemcpyDeviceToHost, down));
+            return AFG_OK;
+        });
+    if (rc) return rc;
     for (size_t j = 0; j < M; j++) {
         const Sim &s = sims[mods[j]];
         afg_batch_item &it = items[which[mods[j]]];
