@@ -81,6 +81,7 @@ ABI_SYMBOLS = [
     "afg_module_length", "afg_module_rows_in_pattern", "afg_module_tell_pattern", "afg_module_tell_row", "afg_module_seek",
     "afg_xm_render_hip", "afg_xm_parse", "afg_xm_parsed_free",
     "afg_wav_layout", "afg_wav_convert_hip", "afg_wav_parse",
+    "afg_pcm_to_f64_hip", "afg_read_samples_double",
     "afg_lcg31_jump", "afg_wav_pack_layout", "afg_wav_pack_hip",
     "afg_open_to_buffer", "afg_open_to_memory", "afg_is_open_for_reading", "afg_is_open_for_writing",
     "afg_write_samples_float", "afg_write_samples_double", "afg_finalize_encoding", "afg_finalize_and_get_encoded",
@@ -181,6 +182,8 @@ class XmParsed(C.Structure):
 # WAV (afg.h): span records of afg_wav_convert_hip and what afg_wav_parse returns
 WAV_KIND_U8, WAV_KIND_S16, WAV_KIND_S24, WAV_KIND_S32, WAV_KIND_F32, WAV_KIND_F64 = range(6)
 WAV_KIND_BYTES = (1, 2, 3, 4, 4, 8)
+F64_KIND_FLAC_S32 = 6                     # afg_pcm_to_f64_hip only: the int32 plane of the FLAC restore
+F64_KIND_BYTES = WAV_KIND_BYTES + (4,)
 WAV_TILE_SAMPLES = 4096
 WAV_SPAN_DTYPE = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), ("count", np.uint64), ("tile_first", np.uint64),
                            ("kind", np.uint32), ("pad", np.uint32)])
@@ -204,7 +207,12 @@ class BatchItem(C.Structure):
 
 
 class BatchOpts(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("n_threads", C.c_int), ("n_devices", C.c_int), ("devices", C.POINTER(C.c_int))]
+    _fields_ = [("struct_size", C.c_uint32), ("n_threads", C.c_int), ("n_devices", C.c_int), ("devices", C.POINTER(C.c_int)),
+                ("sample_type", C.c_uint32)]
+
+
+SAMPLE_F32, SAMPLE_F64 = 0, 1             # afg_batch_opts.sample_type
+BATCH_OPTS_SIZE_V1 = BatchOpts.sample_type.offset        # the struct before sample_type was appended
 
 
 class EncodingOptions(C.Structure):
@@ -384,6 +392,8 @@ def lib():
     L.afg_wav_layout.argtypes = [vp, u64]
     L.afg_wav_layout.restype = u64
     L.afg_wav_convert_hip.argtypes = [u64, vp, u64, vp, u64, vp, u64, vp]
+    L.afg_pcm_to_f64_hip.argtypes = [u64, vp, u64, vp, u64, vp, u64, vp]
+    L.afg_read_samples_double.argtypes = [vp, vp, C.c_int]
     L.afg_wav_parse.argtypes = [vp, C.c_size_t, C.POINTER(WavParsed)]
     L.afg_xm_parsed_free.argtypes = [C.POINTER(XmParsed)]
     L.afg_xm_parsed_free.restype = None
@@ -913,6 +923,13 @@ def wav_convert(n_spans, d_spans, n_tiles, d_in, in_bytes, d_out, out_floats, st
                                     int(out_floats), _stream(stream)))
 
 
+def pcm_to_f64(n_spans, d_spans, n_tiles, d_in, in_bytes, d_out, out_doubles, stream=None):
+    """Enqueue the conversion to float64 (afg_pcm_to_f64_hip) on device arrays: WAV_SPAN_DTYPE records laid out by
+    wav_layout, out_off / count in doubles, kinds WAV_KIND_* and F64_KIND_FLAC_S32."""
+    check(lib().afg_pcm_to_f64_hip(int(n_spans), _ptr(d_spans), int(n_tiles), _ptr(d_in), int(in_bytes), _ptr(d_out),
+                                   int(out_doubles), _stream(stream)))
+
+
 def lcg31_jump(seed, n_draws):
     """afg_lcg31_jump: state of the dither generator after n_draws steps from seed.  Needs no device."""
     return int(lib().afg_lcg31_jump(int(seed) & 0xffffffff, int(n_draws)))
@@ -1087,13 +1104,23 @@ class AudioStream:
         assert out.dtype == np.float32 and out.flags.c_contiguous and out.size % ch == 0
         return int(lib().afg_read_samples_float(self._h, out.ctypes.data, out.size // ch))
 
+    def readSamplesDouble(self, out):
+        """out: float64 numpy array whose size is a multiple of the channel count; returns frames read."""
+        ch = max(1, self.getNumChannels())
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.size % ch == 0
+        return int(lib().afg_read_samples_double(self._h, out.ctypes.data, out.size // ch))
+
 
 class BatchDecoded:
     """Result of afg_batch_decode kept in the library's (page-locked) result plane: ``items[i]`` are dicts whose
     ``pcm`` arrays are views, valid until ``close()`` (or the end of a ``with`` block)."""
 
-    def __init__(self, files, n_threads=0, devices=None):
-        """devices: None = the current device; "all" = every visible device; or a list of device indices."""
+    def __init__(self, files, n_threads=0, devices=None, dtype=np.float32):
+        """devices: None = the current device; "all" = every visible device; or a list of device indices.
+        dtype: np.float32, or np.float64 for the doubles of readSamplesDouble (afg_batch_opts.sample_type)."""
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("batch_decode delivers float32 or float64")
         self.devices = devices
         self._bufs = [bytes(f) for f in files]
         n = len(self._bufs)
@@ -1108,7 +1135,7 @@ class BatchDecoded:
         """The timed part: host parse + device restore + copy back -- the C call and nothing else (the per-file views of
         `items` are made when they are first asked for: two thousand numpy views cost more than some of these calls)."""
         self.close()
-        opts = BatchOpts(C.sizeof(BatchOpts), self.n_threads, 0, None)
+        opts = BatchOpts(C.sizeof(BatchOpts), self.n_threads, 0, None, SAMPLE_F64 if self.dtype == np.float64 else SAMPLE_F32)
         if self.devices == "all":
             opts.n_devices = -1
         elif self.devices is not None:
@@ -1127,7 +1154,8 @@ class BatchDecoded:
                 for i in range(self._res.n_files):
                     it = self._res.items[i]
                     cnt = it.frames * it.channels
-                    pcm = (np.ctypeslib.as_array(it.pcm, shape=(cnt,)).reshape(-1, max(1, it.channels))
+                    ptr = it.pcm if self.dtype == np.float32 else C.cast(it.pcm, C.POINTER(C.c_double))
+                    pcm = (np.ctypeslib.as_array(ptr, shape=(cnt,)).reshape(-1, max(1, it.channels))
                            if cnt and it.pcm else None)
                     self._items.append({"status": it.status, "message": None if it.message is None else it.message.decode(),
                                         "format": it.format, "channels": it.channels, "samplerate": it.samplerate,
@@ -1166,9 +1194,10 @@ def get_device():
     return d
 
 
-def batch_decode(files, n_threads=0, devices=None):
-    """afg_batch_decode(_ex): list of dicts (status, message, format, channels, samplerate, frames, pcm ndarray copy)."""
-    with BatchDecoded(files, n_threads, devices) as res:
+def batch_decode(files, n_threads=0, devices=None, dtype=np.float32):
+    """afg_batch_decode(_ex): list of dicts (status, message, format, channels, samplerate, frames, pcm ndarray copy of
+    `dtype`: np.float32, or np.float64 for the doubles afg_read_samples_double returns)."""
+    with BatchDecoded(files, n_threads, devices, dtype) as res:
         return [dict(it, pcm=None if it["pcm"] is None else it["pcm"].copy()) for it in res.items]
 
 

@@ -450,6 +450,7 @@ struct BatchOut {
     std::shared_ptr<void> mod_plane;    // batch path: the MOD files' PCM (afg_mod_stage.cpp)
     std::shared_ptr<void> wav_plane;    // batch path: the WAV files' PCM (afg_wav_stage.cpp)
     std::shared_ptr<void> xm_plane;     // batch path: the XM files' PCM (afg_xm_stage.cpp)
+    bool f64 = false;                   // a stream's double reads: `plane` holds plane_floats doubles
 };
 
 // Device stage for a set of parsed files: every FLAC record of the batch in one launch, every QOA frame
@@ -466,7 +467,9 @@ struct Mp3Stage {
     const uint32_t *flags = nullptr;
     size_t blocks = 0;
     const size_t *base = nullptr;
-    float *plane = nullptr;             // host PCM plane, blocks * 576 floats (page-locked)
+    float *plane = nullptr;             // host PCM plane, blocks * 576 floats (page-locked) ...
+    bool f64 = false;                   // ... or as many doubles (afg_batch_opts.sample_type): the transform's floats are widened on the device
+    size_t es() const { return f64 ? sizeof(double) : sizeof(float); }
 };
 
 // Where the batch path parsed its Ogg Vorbis files: file i's spectra at float base[i] of one page-locked buffer
@@ -487,7 +490,8 @@ struct FlacStage {
 // k's PCM goes back (PCIe is full duplex) -- and while the host threads parse chunk k+2.
 struct Mp3Pipe {
     const Mp3Stage *st = nullptr;
-    DeviceBuf d_in, d_pcm;
+    DeviceBuf d_in, d_pcm, d_pcm64;
+    std::vector<std::unique_ptr<F64Plane>> widen;          // one per chunk, alive until close() has drained the streams
     uint32_t *d_flags = nullptr;
     hipStream_t up = nullptr, down = nullptr;
     std::vector<afg_mp3_plan *> plans;
@@ -512,6 +516,7 @@ struct Mp3Pipe {
         const size_t coef_bytes = stage.blocks * 576 * sizeof(float), flag_bytes = (stage.blocks * 4 + 15) & ~(size_t)15;
         if (int r = d_in.alloc(coef_bytes + flag_bytes)) return r;
         if (int r = d_pcm.alloc(coef_bytes)) return r;
+        if (stage.f64) if (int r = d_pcm64.alloc(coef_bytes * 2)) return r;
         if (stage.q) {
             const size_t q_bytes = (stage.blocks * 576 * sizeof(int16_t) + 15) & ~(size_t)15;
             const size_t rec_bytes = stage.blocks * sizeof(afg_mp3_qgranule);
@@ -593,10 +598,16 @@ struct Mp3Pipe {
         }
         rc = afg_mp3_transform_hip(plan, (const float *)d_in.p, d_flags, (float *)d_pcm.p, nullptr, up);
         if (rc) return;
+        if (st->f64) {
+            widen.emplace_back(new F64Plane);
+            rc = widen.back()->launch(AFG_WAV_KIND_F32, (const float *)d_pcm.p + b0 * 576, nb * 576, (double *)d_pcm64.p + b0 * 576, up);
+            if (rc) return;
+        }
+        const size_t es = st->es();
         e = hipEventRecord(done, up);
         if (e == hipSuccess) e = hipStreamWaitEvent(down, done, 0);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(st->plane + b0 * 576, (const float *)d_pcm.p + b0 * 576, nb * 576 * sizeof(float), hipMemcpyDeviceToHost, down);
+            e = hipMemcpyAsync((uint8_t *)st->plane + b0 * 576 * es, (const uint8_t *)(st->f64 ? d_pcm64.p : d_pcm.p) + b0 * 576 * es, nb * 576 * es, hipMemcpyDeviceToHost, down);
     }
     int close()
     {
@@ -604,7 +615,7 @@ struct Mp3Pipe {
         if (down) { hipError_t e2 = hipStreamSynchronize(down); if (e == hipSuccess) e = e2; }
         for (afg_mp3_plan *p : plans) afg_mp3_plan_destroy(p);
         for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
-        plans.clear(); events.clear();
+        plans.clear(); events.clear(); widen.clear();
         g_streams.give(up, down);
         up = down = nullptr;
         if (rc) return rc;
@@ -632,8 +643,14 @@ struct OpusCarry {
 int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const size_t *len, unsigned threads, BatchOut &out,
                   const Mp3Stage *stage = nullptr, const OggStage *ogg_stage = nullptr, const FlacStage *flac_stage = nullptr,
                   const uint8_t *own = nullptr, Mp3Carry *carry = nullptr, OpusCarry *opus_carry = nullptr,
-                  const size_t *opus_done_at = nullptr)
+                  const size_t *opus_done_at = nullptr, bool f64 = false)
 {
+    // f64 (afg_read_samples_double, afg_batch_opts.sample_type): the result plane holds doubles.  Every stage's device plane
+    // -- int32 for FLAC, float for the others -- is widened by afg_pcm_to_f64_hip behind the stage's kernels, on their
+    // stream, and the doubles are what comes back.  The batch path's MP3 and Opus planes were widened by their own pipelines.
+    if (stage && stage->blocks && stage->f64 != f64) { afg::set_error("decode_parsed: the MP3 stage's sample type differs"); return AFG_ERR_INVALID; }
+    const size_t es = f64 ? sizeof(double) : sizeof(float);
+    out.f64 = f64;
     // opus_done_at (batch path): the Opus files are already decoded, file i's PCM at float opus_done_at[i] of the batch's
     // Opus plane; only their metadata is filled in here
     // `own` (optional, one byte per file): the files this call is responsible for.  The batch path decodes its FLAC /
@@ -804,11 +821,11 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
         parallel_for(broken.size(), threads, [&](size_t bi) {
             const size_t i = broken[bi];
             const Parsed &p = parsed[i];
-            float *file_plane = stage->plane + stage->base[i] * 576;
-            float *dst = file_plane + p.mp3.copies[0].src;
+            uint8_t *file_plane = (uint8_t *)stage->plane + stage->base[i] * 576 * es;
+            uint8_t *dst = file_plane + p.mp3.copies[0].src * es;
             for (const afg_mp3::Copy &c : p.mp3.copies) {
-                if (dst != file_plane + c.src) std::memmove(dst, file_plane + c.src, (size_t)c.count * sizeof(float));
-                dst += c.count;
+                if (dst != file_plane + c.src * es) std::memmove(dst, file_plane + c.src * es, (size_t)c.count * es);
+                dst += c.count * es;
             }
         });
         tm.lap("mp3 delivery (in place)");
@@ -839,10 +856,19 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
     out.plane_floats = flac_out + qoa_out + mp3_out + ogg_out + opus_out;
     if (out.plane_floats == 0) goto metadata;
     {
-        if (int rc = g_staging.take(out.plane_floats * sizeof(float), out.plane)) return rc;
+        if (int rc = g_staging.take(out.plane_floats * es, out.plane)) return rc;
         tm.lap("layout + plane alloc");
-        DeviceBuf d_out;
+        // (the widened planes and the conversion records are declared out here: on an early way out of a stage they are let
+        //  go only after the device has drained, below them)
+        DeviceBuf d_out, d_out64, d_mp3_64, d_ogg_64, d_opus_64;
         if (int rc = d_out.alloc(out.plane_floats * sizeof(float))) return rc;
+        if (f64) if (int rc = d_out64.alloc(std::max<size_t>(flac_out + qoa_out, 2) * sizeof(double))) return rc;   // FLAC and QOA are widened in place of the plane
+        std::vector<std::unique_ptr<F64Plane>> widen;        // one per conversion launch, alive until the stages have drained
+        struct Drain { bool on; ~Drain() { if (on) (void)hipDeviceSynchronize(); } } drain{ f64 };
+        auto to_f64 = [&](uint32_t kind, const void *src, uint64_t n, void *dst, hipStream_t st) -> int {
+            widen.emplace_back(new F64Plane);
+            return widen.back()->launch(kind, src, n, (double *)dst, st);
+        };
         hipStream_t stream = nullptr;
         // ---- FLAC ----
         if (flac_out) {
@@ -922,9 +948,10 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                 if (e == hipSuccess) e = hipStreamWaitEvent(mid, landed, 0);
                 if (e != hipSuccess) break;
                 // (the records are still here in host memory: only the populated instantiations are launched)
-                rc = afg_flac_transform_variants_hip(fr1 - fr0, df + fr0, ds, dr, nullptr, (float *)d_out.p,
+                rc = afg_flac_transform_variants_hip(fr1 - fr0, df + fr0, ds, dr, f64 ? (int32_t *)d_out.p : nullptr, f64 ? nullptr : (float *)d_out.p,
                                                      afg_flac_variants(fr1 - fr0, hf + fr0, hs), mid);
                 if (rc) break;
+                if (f64 && (rc = to_f64(AFG_F64_KIND_FLAC_S32, (const int32_t *)d_out.p + o0, o1 - o0, (double *)d_out64.p + o0, mid)) != AFG_OK) break;
                 if (g_trace) ct.e_k1 = mark(mid);
                 e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
                 if (e != hipSuccess) break;
@@ -933,7 +960,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                 if (e == hipSuccess) e = hipStreamWaitEvent(down, done, 0);
                 if (g_trace) ct.e_d0 = mark(down);
                 if (e == hipSuccess)
-                    e = hipMemcpyAsync((float *)out.plane.p + o0, (const float *)d_out.p + o0, (o1 - o0) * sizeof(float), hipMemcpyDeviceToHost, down);
+                    e = hipMemcpyAsync((uint8_t *)out.plane.p + o0 * es, (const uint8_t *)(f64 ? d_out64.p : d_out.p) + o0 * es, (o1 - o0) * es, hipMemcpyDeviceToHost, down);
                 if (g_trace) { ct.e_d1 = mark(down); ct.t_queued = since(); ctrace.push_back(ct); }
                 f0 = f1;
             }
@@ -985,10 +1012,11 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
             if (int rc = afg_qoa_transform_hip(qframes, (const afg_qoa_frame *)d_in.p, (const uint8_t *)d_in.p + rec_pad, nullptr,
                                                (float *)d_out.p, stream))
                 return rc;
+            if (f64) if (int rc = to_f64(AFG_WAV_KIND_F32, (const float *)d_out.p + flac_out, qoa_out, (double *)d_out64.p + flac_out, stream)) return rc;
             AFG_HIP_CHECK(hipStreamSynchronize(stream));
         }
         if (qoa_out) {                                       // (the FLAC part came back chunk by chunk)
-            AFG_HIP_CHECK(hipMemcpyAsync((float *)out.plane.p + flac_out, (const float *)d_out.p + flac_out, qoa_out * sizeof(float),
+            AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)out.plane.p + flac_out * es, (const uint8_t *)(f64 ? d_out64.p : d_out.p) + flac_out * es, qoa_out * es,
                                          hipMemcpyDeviceToHost, stream));
             AFG_HIP_CHECK(hipStreamSynchronize(stream));
         }
@@ -997,8 +1025,10 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
         if (mp3_blocks && !staged) {
             const size_t coef_bytes = mp3_blocks * 576 * sizeof(float), flag_bytes = (mp3_blocks * 4 + 15) & ~(size_t)15;
             DeviceBuf d_in, d_pcm;
+            DeviceBuf &d_pcm64 = d_mp3_64;
             if (int rc = d_in.alloc(coef_bytes + flag_bytes)) return rc;
             if (int rc = d_pcm.alloc(coef_bytes)) return rc;
+            if (f64) if (int rc = d_pcm64.alloc(coef_bytes * 2)) return rc;
             // The files are cut into a few chunks of similar size, each with its own plan: the upload and kernel of
             // chunk k+1 (stream `up`) run while chunk k's PCM goes back (stream `down`) -- PCIe is full duplex.
             struct Chunk { size_t f0, f1, blk0, blocks; afg_mp3_plan *plan; hipEvent_t done; size_t runs = 0; };
@@ -1079,6 +1109,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                     if (e != hipSuccess) break;
                     carry->valid = true;
                 }
+                if (f64 && (rc = to_f64(AFG_WAV_KIND_F32, (const float *)d_pcm.p + c.blk0 * 576, c.blocks * 576, (double *)d_pcm64.p + c.blk0 * 576, up)) != AFG_OK) break;
                 e = hipEventRecord(c.done, up);
                 if (e == hipSuccess) e = hipStreamWaitEvent(down, c.done, 0);
                 // delivery: the copy plan of each file, merged into maximal contiguous pieces (one per undamaged file),
@@ -1086,15 +1117,15 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                 for (size_t i = c.f0; i < c.f1 && e == hipSuccess; i++) {
                     const Parsed &p = parsed[i];
                     if (fmt_of(p) != AFG_FORMAT_MP3) continue;
-                    const float *src = (const float *)d_pcm.p + mp3_blk_base[i] * 576;
-                    float *dst = (float *)out.plane.p + out.files[i].pcm_off;
+                    const uint8_t *src = (const uint8_t *)(f64 ? d_pcm64.p : d_pcm.p) + mp3_blk_base[i] * 576 * es;
+                    uint8_t *dst = (uint8_t *)out.plane.p + out.files[i].pcm_off * es;
                     const std::vector<afg_mp3::Copy> &cp = p.mp3.copies;
                     for (size_t k = 0; k < cp.size() && e == hipSuccess;) {
                         uint64_t from = cp[k].src, cnt = cp[k].count;
                         size_t j = k + 1;
                         while (j < cp.size() && cp[j].src == from + cnt) cnt += cp[j++].count;
-                        e = hipMemcpyAsync(dst, src + from, (size_t)cnt * sizeof(float), hipMemcpyDeviceToHost, down);
-                        dst += cnt;
+                        e = hipMemcpyAsync(dst, src + from * es, (size_t)cnt * es, hipMemcpyDeviceToHost, down);
+                        dst += cnt * es;
                         k = j;
                     }
                 }
@@ -1115,11 +1146,13 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
         if (!ogg.v.empty()) {
             StagingPool::Lease h_spec;
             DeviceBuf d_spec, d_pcm;
+            DeviceBuf &d_pcm64 = d_ogg_64;
+            if (f64) if (int rc = d_pcm64.alloc(ogg_out * sizeof(double))) return rc;
             if (!ogg_staged)
                 if (int rc = g_staging.take(ogg_spec * sizeof(float), h_spec)) return rc;
             if (int rc = d_spec.alloc((ogg_staged ? ogg_stage->floats : ogg_spec) * sizeof(float))) return rc;
             if (int rc = d_pcm.alloc(ogg_out * sizeof(float))) return rc;
-            float *ogg_plane = (float *)out.plane.p + flac_out + qoa_out + mp3_out;
+            uint8_t *ogg_plane = (uint8_t *)out.plane.p + (flac_out + qoa_out + mp3_out) * es;
             hipStream_t up = nullptr, down = nullptr;
             hipError_t e = g_streams.take(&up, &down);
             int rc = AFG_OK;
@@ -1208,11 +1241,12 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                 // a staged plan addresses the staging layout from float 0; a gathered one is packed from its chunk's start
                 rc = afg_vorbis_transform_hip(c.plan, (const float *)d_spec.p + (ogg_staged ? 0 : c.spec0), (float *)d_pcm.p + c.out0, up);
                 if (rc) break;
+                if (f64 && (rc = to_f64(AFG_WAV_KIND_F32, (const float *)d_pcm.p + c.out0, c.out_n, (double *)d_pcm64.p + c.out0, up)) != AFG_OK) break;
                 e = hipEventCreateWithFlags(&c.done, hipEventDisableTiming);
                 if (e == hipSuccess) e = hipEventRecord(c.done, up);
                 if (e == hipSuccess) e = hipStreamWaitEvent(down, c.done, 0);
                 if (e == hipSuccess)
-                    e = hipMemcpyAsync(ogg_plane + c.out0, (const float *)d_pcm.p + c.out0, c.out_n * sizeof(float), hipMemcpyDeviceToHost, down);
+                    e = hipMemcpyAsync(ogg_plane + c.out0 * es, (const uint8_t *)(f64 ? d_pcm64.p : d_pcm.p) + c.out0 * es, c.out_n * es, hipMemcpyDeviceToHost, down);
             }
             if (up) { hipError_t e2 = hipStreamSynchronize(up); if (e == hipSuccess) e = e2; }
             if (down) { hipError_t e2 = hipStreamSynchronize(down); if (e == hipSuccess) e = e2; }
@@ -1223,11 +1257,11 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
             for (size_t bi = 0, at = 0; bi < ogg_broken.size(); bi++) {
                 const size_t i = ogg_broken[bi];
                 while (at < ogg_pieces.size() && ogg_pieces[at].file != i) at++;
-                float *dst = (float *)out.plane.p + out.files[i].pcm_off;
+                uint8_t *dst = (uint8_t *)out.plane.p + out.files[i].pcm_off * es;
                 for (; at < ogg_pieces.size() && ogg_pieces[at].file == i; at++) {
-                    const float *src = ogg_plane + ogg_pieces[at].from;
-                    if (dst != src) std::memmove(dst, src, (size_t)ogg_pieces[at].count * sizeof(float));
-                    dst += ogg_pieces[at].count;
+                    const uint8_t *src = ogg_plane + ogg_pieces[at].from * es;
+                    if (dst != src) std::memmove(dst, src, (size_t)ogg_pieces[at].count * es);
+                    dst += ogg_pieces[at].count * es;
                 }
             }
             tm.lap("vorbis gather | h2d | kernel | d2h (chunks overlapped)");
@@ -1239,6 +1273,8 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
             const size_t rec_bytes = (opus_recs * sizeof(afg_celt_frame) + 15) & ~(size_t)15;
             StagingPool::Lease h_in;
             DeviceBuf d_in, d_pcm;
+            DeviceBuf &d_pcm64 = d_opus_64;
+            if (f64) if (int rc = d_pcm64.alloc(opus_out * sizeof(double))) return rc;
             if (int rc = g_staging.take(base_bytes + rec_bytes + opus_coefs * sizeof(float), h_in)) return rc;
             if (int rc = d_in.alloc(base_bytes + rec_bytes + opus_coefs * sizeof(float))) return rc;
             if (int rc = d_pcm.alloc(opus_out * sizeof(float))) return rc;
@@ -1301,11 +1337,13 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                     if (rc) return rc;
                 }
             }
-            AFG_HIP_CHECK(hipMemcpyAsync((float *)out.plane.p + flac_out + qoa_out + mp3_out + ogg_out, d_pcm.p, opus_out * sizeof(float),
+            if (f64) if (int rc = to_f64(AFG_WAV_KIND_F32, d_pcm.p, opus_out, d_pcm64.p, stream)) return rc;
+            AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)out.plane.p + (flac_out + qoa_out + mp3_out + ogg_out) * es, f64 ? d_pcm64.p : d_pcm.p, opus_out * es,
                                          hipMemcpyDeviceToHost, stream));
             AFG_HIP_CHECK(hipStreamSynchronize(stream));
             tm.lap("opus gather | h2d | kernel | d2h");
         }
+        drain.on = false;                                    // every stage has drained its own streams
     }
 metadata:
     for (size_t i = 0; i < nf; i++) {
@@ -1382,8 +1420,11 @@ struct afg_stream {
     int64_t opus_decoded = 0;           // frames decoded so far (the declared length cuts the delivery, stream.d:439-442)
     bool opus_failed = false;           // a packet could not be framed: the next refill reports it (stream.d:452-456)
     // delivered samples not yet read
-    std::vector<float> fifo;
-    size_t fifo_at = 0;                 // floats of `fifo` already handed out
+    std::vector<uint8_t> fifo;          // samples of fifo_es bytes: floats, or doubles once afg_read_samples_double is in use
+    size_t fifo_es = sizeof(float);
+    size_t fifo_at = 0;                 // samples of `fifo` already handed out
+    bool decoded = false;               // a chunk has been decoded since the readers were (re)started
+    size_t fifo_samples() const { return fifo.size() / fifo_es; }
     int64_t position = 0;               // frames handed out so far (tellPosition)
     bool ended = false;                 // nothing further can be decoded
     afg_write::Writer *writer = nullptr;    // opened for writing (afg_write_stream.cpp): nothing above is in use
@@ -1398,6 +1439,7 @@ struct afg_stream {
         fifo_at = 0;
         position = 0;
         ended = false;
+        decoded = false;
         flac_pos = 0;
         qoa_next = 0;
         carry.valid = carry.continues = false;
@@ -1426,7 +1468,8 @@ struct afg_stream {
     bool refill()
     {
         if (ended) return false;
-        if (fifo_at == fifo.size()) { fifo.clear(); fifo_at = 0; }
+        if (fifo_at == fifo_samples()) { fifo.clear(); fifo_at = 0; }
+        decoded = true;
         std::vector<Parsed> parsed(1);
         Parsed &p = parsed[0];
         const uint8_t *dp[1] = { bytes.data() };
@@ -1485,7 +1528,8 @@ struct afg_stream {
             return false;
         }
         BatchOut out;
-        if (decode_parsed(parsed, dp, lp, 1, out, nullptr, nullptr, nullptr, nullptr, cr, ocr) != AFG_OK || out.files[0].status != AFG_OK) {
+        if (decode_parsed(parsed, dp, lp, 1, out, nullptr, nullptr, nullptr, nullptr, cr, ocr, nullptr, fifo_es == sizeof(double)) != AFG_OK ||
+            out.files[0].status != AFG_OK) {
             error = kErrorDecodingError;
             ended = true;
             return false;
@@ -1494,10 +1538,40 @@ struct afg_stream {
         const size_t want = (size_t)std::max<int64_t>(d.frames, 0) * (size_t)channels;
         if (want) {
             if (d.pcm_off + want > out.plane_floats) { error = kErrorDecodingError; ended = true; return false; }
-            const float *src = (const float *)out.plane.p + d.pcm_off;
-            fifo.insert(fifo.end(), src, src + want);
+            const uint8_t *src = (const uint8_t *)out.plane.p + d.pcm_off * fifo_es;
+            fifo.insert(fifo.end(), src, src + want * fifo_es);
         }
         return true;
+    }
+
+    // decode and drop until `frame` (or the end of what decodes)
+    void skip_to(int64_t frame)
+    {
+        const size_t C = (size_t)std::max(1, channels);
+        while (position < frame) {
+            if (fifo_at == fifo_samples() && !refill()) break;
+            const size_t avail = (fifo_samples() - fifo_at) / C;
+            const size_t n = std::min<size_t>(avail, (size_t)(frame - position));
+            fifo_at += n * C;
+            position += (int64_t)n;
+        }
+    }
+
+    // Reads of the other sample type from here on.  A change of type is a seek to the current position: what the FIFO
+    // holds was decoded in the old type and is dropped, the readers start over and the chunks up to the position are
+    // decoded again, so that the next read returns what a handle that only ever used the new type returns there.
+    bool set_sample_bytes(size_t es)
+    {
+        if (fifo_es == es) return true;
+        const int64_t at = position;
+        const bool start_over = decoded;
+        fifo.clear();
+        fifo_at = 0;
+        fifo_es = es;
+        if (!start_over) return true;
+        if (!rewind()) return false;
+        skip_to(at);
+        return !error && position == at;
     }
 };
 
@@ -1591,33 +1665,38 @@ int64_t afg_get_length_in_frames(const afg_stream *s)
     return s->declared_frames;         // stream.d:404-407: whatever the container declares (FLAC: may be 0)
 }
 
-int afg_read_samples_float(afg_stream *s, float *out, int frames)
+static int read_samples(afg_stream *s, void *out, int frames, bool f64)
 {
     if (!s || s->error || s->writer || frames <= 0) return 0;
-    // stream.d:498: a FLAC stream stops once the position equals the declared length (a STREAMINFO that
+    // stream.d:498 / :705: a FLAC stream stops once the position equals the declared length (a STREAMINFO that
     // declares 0 samples therefore reads nothing); the check is made on entry only, like the reference's.
     if (s->format == AFG_FORMAT_FLAC && s->position == s->declared_frames) return 0;
+    const size_t es = f64 ? sizeof(double) : sizeof(float);
     try {
-        if (s->format == AFG_FORMAT_WAV) {                       // stream.d:557-570
+        if (s->format == AFG_FORMAT_WAV) {                       // stream.d:557-570, :719-730
             bool failed = false;
-            const int n = s->wav->read(s->bytes.data(), s->bytes.size(), out, frames, &failed);
+            const int n = s->wav->read(s->bytes.data(), s->bytes.size(), out, frames, &failed, f64);
             s->position = s->wav->tell();
             if (n < 0 || failed) { s->error = kErrorDecodingError; s->wav_failed = true; return 0; }
             return n;
         }
         if (s->format == AFG_FORMAT_MOD || s->format == AFG_FORMAT_XM) {
-            const int n = s->format == AFG_FORMAT_XM ? s->xm->read(out, frames) : s->mod->read(out, frames);
+            const int n = s->format == AFG_FORMAT_XM ? s->xm->read(out, frames, f64) : s->mod->read(out, frames, f64);
             if (n < 0) { s->error = kErrorDecodingError; return 0; }
             s->position += n;
             return n;
         }
+        if (!s->set_sample_bytes(es)) {
+            if (!s->error) s->error = kErrorDecodingError;
+            return 0;
+        }
         const size_t C = (size_t)std::max(1, s->channels);
         int done = 0;
         while (done < frames) {
-            if (s->fifo_at == s->fifo.size() && !s->refill()) break;
-            const size_t avail = (s->fifo.size() - s->fifo_at) / C;
+            if (s->fifo_at == s->fifo_samples() && !s->refill()) break;
+            const size_t avail = (s->fifo_samples() - s->fifo_at) / C;
             const size_t n = std::min<size_t>(avail, (size_t)(frames - done));
-            if (out && n) std::memcpy(out + (size_t)done * C, s->fifo.data() + s->fifo_at, n * C * sizeof(float));
+            if (out && n) std::memcpy((uint8_t *)out + (size_t)done * C * es, s->fifo.data() + s->fifo_at * es, n * C * es);
             s->fifo_at += n * C;
             done += (int)n;
         }
@@ -1629,6 +1708,9 @@ int afg_read_samples_float(afg_stream *s, float *out, int frames)
         return 0;
     }
 }
+
+int afg_read_samples_float(afg_stream *s, float *out, int frames) { return read_samples(s, out, frames, false); }
+int afg_read_samples_double(afg_stream *s, double *out, int frames) { return read_samples(s, out, frames, true); }
 
 int afg_can_seek(const afg_stream *s) { return s && !s->error && !s->writer; }
 
@@ -1658,14 +1740,7 @@ int afg_seek_position(afg_stream *s, int frame)
             }
             if (!s->rewind()) { s->error = kErrorDecodingError; return 0; }
         }
-        const size_t C = (size_t)std::max(1, s->channels);
-        while (s->position < frame) {
-            if (s->fifo_at == s->fifo.size() && !s->refill()) break;
-            const size_t avail = (s->fifo.size() - s->fifo_at) / C;
-            const size_t n = std::min<size_t>(avail, (size_t)(frame - s->position));
-            s->fifo_at += n * C;
-            s->position += (int64_t)n;
-        }
+        s->skip_to(frame);
         return s->error ? 0 : 1;
     } catch (...) {
         s->error = kErrorDecodingError;
@@ -2103,8 +2178,10 @@ struct BatchOwner {
 // `parse_done` (optional) is called once, when the host passes that keep every helper thread busy are over and what remains is
 // the device stages of decode_parsed: a grouped batch lets its next group start parsing then.
 int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_files, int n_threads, afg_batch_item *items,
-                        std::unique_ptr<BatchOut> &keep, const std::function<void()> *parse_done = nullptr)
+                        std::unique_ptr<BatchOut> &keep, const std::function<void()> *parse_done = nullptr, bool f64 = false)
 {
+    // f64 (afg_batch_opts.sample_type == AFG_SAMPLE_F64): every plane the items point into holds doubles, widened on the device
+    const size_t es = f64 ? sizeof(double) : sizeof(float);
     {
         if (int rc = afg::require_device()) return rc;
         int cur_dev = 0;
@@ -2226,9 +2303,11 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
                 const size_t base_bytes = ((seqs_total + 1) * sizeof(uint64_t) + 15) & ~(size_t)15;
                 const size_t rec_bytes = (recs_total * sizeof(afg_celt_frame) + 15) & ~(size_t)15;
                 StagingPool::Lease h_in;
-                DeviceBuf d_in, d_pcm;
+                DeviceBuf d_in, d_pcm, d_pcm64;
+                std::vector<std::unique_ptr<F64Plane>> widen;     // one per chunk; the streams are drained before the stage returns
                 if (int rc = g_staging.take(base_bytes + rec_bytes + coefs_total * sizeof(float), h_in)) return rc;
-                if (int rc = g_staging.take(std::max<size_t>(coefs_total, 1) * sizeof(float), owner->opus_plane)) return rc;
+                if (int rc = g_staging.take(std::max<size_t>(coefs_total, 1) * es, owner->opus_plane)) return rc;
+                if (f64) if (int rc = d_pcm64.alloc(std::max<size_t>(coefs_total, 2) * sizeof(double))) return rc;
                 if (int rc = d_in.alloc(base_bytes + rec_bytes + coefs_total * sizeof(float))) return rc;
                 if (int rc = d_pcm.alloc(std::max<size_t>(coefs_total, 1) * sizeof(float))) return rc;
                 uint64_t *hb = (uint64_t *)h_in.p;
@@ -2314,6 +2393,11 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
                             }
                         }
                         if (rc) break;
+                        if (f64) {
+                            widen.emplace_back(new F64Plane);
+                            rc = widen.back()->launch(AFG_WAV_KIND_F32, (const float *)d_pcm.p + c0, c1 - c0, (double *)d_pcm64.p + c0, up);
+                            if (rc) break;
+                        }
                         hipEvent_t done = nullptr;
                         e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
                         if (e != hipSuccess) break;
@@ -2321,7 +2405,7 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
                         e = hipEventRecord(done, up);
                         if (e == hipSuccess) e = hipStreamWaitEvent(down, done, 0);
                         if (e == hipSuccess)
-                            e = hipMemcpyAsync((float *)owner->opus_plane.p + c0, (const float *)d_pcm.p + c0, (c1 - c0) * sizeof(float), hipMemcpyDeviceToHost, down);
+                            e = hipMemcpyAsync((uint8_t *)owner->opus_plane.p + c0 * es, (const uint8_t *)(f64 ? d_pcm64.p : d_pcm.p) + c0 * es, (c1 - c0) * es, hipMemcpyDeviceToHost, down);
                     }
                     f0 = f1;
                 }
@@ -2360,7 +2444,7 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
                     // HIP's current device is per host thread and starts at 0: this thread works for the caller's device
                     if (hipSetDevice(cur_dev) != hipSuccess) { afg::set_error("hipSetDevice(%d) failed", cur_dev); early_job.rc = AFG_ERR_HIP; return; }
                     early_job.rc = decode_parsed(parsed, data, length, 1 /* no helpers: they are parsing */, *eo, nullptr, nullptr, fs,
-                                                 own_early.data());
+                                                 own_early.data(), nullptr, nullptr, nullptr, f64);
                 } catch (...) {
                     afg::set_error("out of host memory");
                     early_job.rc = AFG_ERR_OOM;
@@ -2379,7 +2463,7 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
             const size_t per_block = qmode ? 576 * sizeof(int16_t) + sizeof(afg_mp3_qgranule) + sizeof(uint32_t)
                                            : 576 * sizeof(float) + sizeof(uint32_t);
             if (int rc = g_staging.take(total_bound * per_block + 64, mp3_stage)) return rc;
-            if (int rc = g_staging.take(total_bound * 576 * sizeof(float), owner->mp3_plane)) return rc;
+            if (int rc = g_staging.take(total_bound * 576 * es, owner->mp3_plane)) return rc;
             float *coef0 = nullptr;
             int16_t *q0 = nullptr;
             afg_mp3_qgranule *recs0 = nullptr;
@@ -2396,6 +2480,7 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
             }
             stage.flags = flags0; stage.blocks = total_bound; stage.base = base.data();
             stage.plane = (float *)owner->mp3_plane.p;
+            stage.f64 = f64;
             if (int rc = pipe.open(stage)) return rc;
             tm.lap("mp3 pipeline set-up (device planes, streams, table arena)");
             // pass 2, chunk by chunk: all host threads parse a chunk of files, its device work is queued, and they go on
@@ -2499,7 +2584,7 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
         if (parse_done) (*parse_done)();
         int rc = decode_parsed(parsed, data, length, nt, *owner, stage.blocks ? &stage : nullptr, ogg_stage.floats ? &ogg_stage : nullptr,
                                split ? nullptr : (flac_stage.words ? &flac_stage : nullptr), split ? own_late.data() : nullptr, nullptr, nullptr,
-                               opus_staged ? opus_pcm_at.data() : nullptr);
+                               opus_staged ? opus_pcm_at.data() : nullptr, f64);
         tm.lap("decode_parsed total");
         if (split) {
             early_job.th.join();
@@ -2516,9 +2601,9 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
             items[i].channels = d.channels;
             items[i].samplerate = d.samplerate;
             items[i].frames = d.frames;
-            const float *plane = d.in_mp3_plane ? (const float *)owner->mp3_plane.p
-                                 : d.in_opus_plane ? (const float *)owner->opus_plane.p : (const float *)src->plane.p;
-            items[i].pcm = (d.status == AFG_OK && d.frames > 0) ? (float *)plane + d.pcm_off : nullptr;
+            const uint8_t *plane = d.in_mp3_plane ? (const uint8_t *)owner->mp3_plane.p
+                                   : d.in_opus_plane ? (const uint8_t *)owner->opus_plane.p : (const uint8_t *)src->plane.p;
+            items[i].pcm = (d.status == AFG_OK && d.frames > 0) ? (float *)(plane + d.pcm_off * es) : nullptr;
         }
         // MOD is probed last (stream.d:1796): files no other front-end took go to its stage
         std::vector<int> unknown;
@@ -2526,14 +2611,14 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
             if (items[i].status == AFG_ERR_UNSUPPORTED && items[i].message == kErrorUnknownFormat) unknown.push_back(i);
         // WAV comes well before either (stream.d:1638); no probe between it and them takes a file its scan accepts (QOA and
         // Ogg have their own magic, looks_like_mp3 declines RIFF), so its stage can run here, on the files nothing took
-        if (int wrc = afg_wav::batch_stage(data, length, unknown, (int)nt, items, owner->wav_plane)) return wrc;
+        if (int wrc = afg_wav::batch_stage(data, length, unknown, (int)nt, items, owner->wav_plane, f64)) return wrc;
         tm.lap("wav stage");
         unknown.erase(std::remove_if(unknown.begin(), unknown.end(), [&](int i) { return items[i].status == AFG_OK || items[i].message != kErrorUnknownFormat; }), unknown.end());
         // ... and XM directly before it (stream.d:1751)
-        if (int xrc = afg_xm::batch_stage(data, length, unknown, (int)nt, items, owner->xm_plane)) return xrc;
+        if (int xrc = afg_xm::batch_stage(data, length, unknown, (int)nt, items, owner->xm_plane, f64)) return xrc;
         tm.lap("xm stage");
         unknown.erase(std::remove_if(unknown.begin(), unknown.end(), [&](int i) { return items[i].status == AFG_OK || items[i].message != kErrorUnknownFormat; }), unknown.end());
-        if (int mrc = afg_mod::batch_stage(data, length, unknown, (int)nt, items, owner->mod_plane)) return mrc;
+        if (int mrc = afg_mod::batch_stage(data, length, unknown, (int)nt, items, owner->mod_plane, f64)) return mrc;
         tm.lap("mod stage");
         keep = std::move(guard);
         tm.lap("items filled");
@@ -2586,7 +2671,15 @@ int afg_batch_decode_ex(const uint8_t *const *data, const size_t *length, int n_
     try {
         if (!out || n_files < 0 || (n_files && (!data || !length))) return AFG_ERR_INVALID;
         out->n_files = 0; out->items = nullptr; out->owner = nullptr;
-        if (opts && opts->struct_size < sizeof(afg_batch_opts)) { afg::set_error("afg_batch_opts.struct_size too small"); return AFG_ERR_INVALID; }
+        // (a caller built before sample_type was appended hands in the struct up to `devices`: it gets float, as it always did)
+        if (opts && opts->struct_size < offsetof(afg_batch_opts, sample_type)) { afg::set_error("afg_batch_opts.struct_size too small"); return AFG_ERR_INVALID; }
+        uint32_t sample_type = AFG_SAMPLE_F32;
+        if (opts && opts->struct_size >= offsetof(afg_batch_opts, sample_type) + sizeof(uint32_t)) sample_type = opts->sample_type;
+        if (sample_type != AFG_SAMPLE_F32 && sample_type != AFG_SAMPLE_F64) {
+            afg::set_error("afg_batch_opts.sample_type %u: AFG_SAMPLE_F32 (0) or AFG_SAMPLE_F64 (1)", sample_type);
+            return AFG_ERR_INVALID;
+        }
+        const bool f64 = sample_type == AFG_SAMPLE_F64;
         if (n_files == 0) return AFG_OK;
         // ---- which devices ----
         std::vector<int> devs;
@@ -2644,7 +2737,7 @@ int afg_batch_decode_ex(const uint8_t *const *data, const size_t *length, int n_
             int rc = AFG_OK;
             if (groups <= 1) {
                 owner->parts.emplace_back();
-                rc = batch_decode_device(data, length, n_files, n_threads, items, owner->parts.back());
+                rc = batch_decode_device(data, length, n_files, n_threads, items, owner->parts.back(), nullptr, f64);
             } else {
                 const size_t G = (size_t)groups;
                 owner->parts.resize(G);
@@ -2674,7 +2767,7 @@ int afg_batch_decode_ex(const uint8_t *const *data, const size_t *length, int n_
                             std::unique_lock<std::mutex> lk(token);
                             bool released = false;
                             const std::function<void()> done = [&] { if (!released) { released = true; lk.unlock(); } };
-                            const int r = batch_decode_device(data + f0, length + f0, f1 - f0, n_threads, items + f0, owner->parts[g], &done);
+                            const int r = batch_decode_device(data + f0, length + f0, f1 - f0, n_threads, items + f0, owner->parts[g], &done, f64);
                             done();
                             if (r) { jobs[w].rc = r; jobs[w].error = afg_last_error(); failed = true; }
                         }
@@ -2731,7 +2824,7 @@ int afg_batch_decode_ex(const uint8_t *const *data, const size_t *length, int n_
                     if (mine[k].empty()) return;
                     if (hipSetDevice(devs[k]) != hipSuccess) { p.rc = AFG_ERR_HIP; p.error = "hipSetDevice failed"; return; }
                     tl_helpers = &g_device_helpers[k];
-                    p.rc = batch_decode_device(p.data.data(), p.len.data(), (int)mine[k].size(), per_dev_threads, p.items.data(), owner->parts[k]);
+                    p.rc = batch_decode_device(p.data.data(), p.len.data(), (int)mine[k].size(), per_dev_threads, p.items.data(), owner->parts[k], nullptr, f64);
                     tl_helpers = nullptr;
                     if (p.rc) p.error = afg_last_error();
                 } catch (...) {

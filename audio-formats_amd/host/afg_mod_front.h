@@ -98,7 +98,7 @@ namespace afg_mod {
 class StreamMix {
 public:
     // pocketmod_render(c, out, frames * 8) behind stream.d:611-620; -1: device error (afg_last_error says which)
-    int read(float *out, int frames);
+    int read(void *out, int frames, bool f64 = false);   // f64: doubles, widened on the device (stream.d:732-739)
     Song song;
 private:
     afg_front::DevBuf plane_, recs_, out_;
@@ -107,14 +107,14 @@ private:
     std::vector<afg_mod_tick> ticks_;
     std::vector<afg_mod_segment> segs_;
     std::vector<uint8_t> staging_;
-    std::vector<float> bounce_;
+    afg_front::PlaneFetch fetch_;
 };
 
 // The batch path's MOD stage: the files listed in `which` that pass the probe are simulated on the helper threads
 // (n_threads as afg_front::parallel_run takes it), mixed on the current device in chunks with upload, mix and download overlapped,
 // and their items filled in (2-channel float PCM in page-locked memory that `keep` owns).  Other files are left alone.
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep);
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, bool f64 = false);   // f64: items point at doubles (afg_batch_opts.sample_type)
 
 // What the stage reports on a song cut at AFG_MOD_MAX_FRAMES (status AFG_OK)
 extern const char *const kMessageCapped;

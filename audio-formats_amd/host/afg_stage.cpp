@@ -3,6 +3,7 @@
 #include "../csrc/afg_common.h"
 
 #include <algorithm>
+#include <cstring>
 
 namespace afg_front {
 
@@ -50,6 +51,46 @@ int HandleStream::current(hipStream_t *st, bool *moved)
         dev = cur;
     }
     *st = stream;
+    return AFG_OK;
+}
+
+int F64Plane::launch(uint32_t kind, const void *d_in, uint64_t count, double *d_out, hipStream_t st)
+{
+    if (count == 0) return AFG_OK;
+    afg_wav_span &sp = rec;                                  // the upload's source lives as long as the object
+    std::memset(&sp, 0, sizeof(sp));
+    sp.count = count;
+    sp.kind = kind;
+    const uint64_t tiles = afg_wav_layout(&sp, 1);
+    if (int rc = span.alloc(sizeof(sp))) return rc;
+    AFG_HIP_CHECK(hipMemcpyAsync(span.p, &sp, sizeof(sp), hipMemcpyHostToDevice, st));
+    return afg_pcm_to_f64_hip(1, (const afg_wav_span *)span.p, tiles, (const uint8_t *)d_in, count * f64_kind_bytes(kind), d_out, count, st);
+}
+
+int F64Slots::alloc(size_t samples)
+{
+    for (DevBuf &b : wide) if (int rc = b.alloc(std::max<size_t>(samples, 2) * sizeof(double))) return rc;
+    return AFG_OK;
+}
+
+int F64Slots::launch(int slot, uint32_t kind, const void *d_in, uint64_t count, hipStream_t st)
+{
+    conv.emplace_back(new F64Plane);
+    return conv.back()->launch(kind, d_in, count, (double *)wide[slot].p, st);
+}
+
+int PlaneFetch::run(const void *d_plane, uint32_t kind, uint64_t count, void *out, bool f64, hipStream_t st)
+{
+    const size_t bytes = (size_t)count * (f64 ? sizeof(double) : (size_t)f64_kind_bytes(kind));
+    const void *src = d_plane;
+    if (f64) {
+        if (int rc = wide.alloc(std::max<size_t>(bytes, 16))) return rc;
+        if (int rc = conv.launch(kind, d_plane, count, (double *)wide.p, st)) return rc;
+        src = wide.p;
+    }
+    if (!out) { bounce.resize(bytes); out = bounce.data(); }
+    AFG_HIP_CHECK(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, st));
+    AFG_HIP_CHECK(hipStreamSynchronize(st));
     return AFG_OK;
 }
 

@@ -53,6 +53,40 @@ struct HandleStream {
     int current(hipStream_t *st, bool *moved = nullptr);
 };
 
+// ---- float64 output (afg_read_samples_double) ----
+// One plane of `count` samples of one kind (AFG_WAV_KIND_*, AFG_F64_KIND_FLAC_S32) to doubles on the device
+// (csrc/pcm_f64.hip): makes the plane's span, keeps it in a pooled buffer of its own and queues one afg_pcm_to_f64_hip
+// launch on `st` behind whatever wrote the plane there.  d_in and d_out are 16-byte aligned for the fast path.  The
+// object -- it holds the record the upload reads -- lives until the launch has run.
+inline uint64_t f64_kind_bytes(uint32_t kind)
+{
+    return kind == AFG_WAV_KIND_U8 ? 1 : kind == AFG_WAV_KIND_S16 ? 2 : kind == AFG_WAV_KIND_S24 ? 3 : kind == AFG_WAV_KIND_F64 ? 8 : 4;
+}
+struct F64Plane {
+    afg_wav_span rec;
+    DevBuf span;
+    int launch(uint32_t kind, const void *d_in, uint64_t count, double *d_out, hipStream_t st);
+};
+
+// The end of a stream's read: the plane its kernels left on the device (`count` samples of `kind`, queued on st) comes to
+// `out` as it is, or -- f64 -- as doubles through one conversion launch; out NULL: the samples are skipped.  Waits for st.
+struct PlaneFetch {
+    F64Plane conv;
+    DevBuf wide;
+    std::vector<uint8_t> bounce;
+    int run(const void *d_plane, uint32_t kind, uint64_t count, void *out, bool f64, hipStream_t st);
+};
+
+// The float64 side of a batch stage's two output slots (afg_batch_opts.sample_type): the chunk in `slot` is widened from the
+// stage's float plane into wide[slot] on the kernel stream, between the stage's kernels and the download.  One F64Plane per
+// launch, kept until the stage has drained (run_chunks drains on every way out).
+struct F64Slots {
+    DevBuf wide[2];
+    std::vector<std::unique_ptr<F64Plane>> conv;
+    int alloc(size_t samples);
+    int launch(int slot, uint32_t kind, const void *d_in, uint64_t count, hipStream_t st);
+};
+
 // ---- the chunk pipeline of a batch stage ----
 // Chunks 0 .. n_chunks - 1 go through two slots in turn (chunk c uses slot c & 1) on the kept stream pair: uploads and
 // kernels on `up`, downloads on `down`, so that chunk c + 1 is worked on while chunk c comes back.  The caller keeps the

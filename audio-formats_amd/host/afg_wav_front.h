@@ -41,13 +41,16 @@ public:
     Info info;
     // readSamples!float behind stream.d:557-570: the frames read; *failed set when the reference's read sets its error
     // (the position has advanced by the clamped request all the same, wav.d:253).  -1: device error.
-    int read(const uint8_t *file, size_t size, float *out, int frames, bool *failed);
+    // f64: readSamples!double -- `out` takes doubles, made by csrc/pcm_f64.hip from the same bytes.  The FIFO holds one
+    // type; a read of the other type drops it (the position is the stream's, not the FIFO's).
+    int read(const uint8_t *file, size_t size, void *out, int frames, bool *failed, bool f64 = false);
     bool seek(int frame);                                   // wav.d:220-231
     int tell() const { return (int)position_; }
 private:
     int decode(const uint8_t *file, uint64_t frame0, uint64_t frames);
     uint32_t position_ = 0;                                 // _framePosition
-    std::vector<float> fifo_;                               // frames [fifo_frame_, fifo_frame_ + fifo_.size() / channels)
+    std::vector<uint8_t> fifo_;                             // frames [fifo_frame_, fifo_frame_ + fifo_.size() / (es_ * channels))
+    size_t es_ = sizeof(float);                             // bytes per sample of the FIFO: float, or double
     uint64_t fifo_frame_ = 0;
     afg_front::DevBuf in_, out_, spans_;                    // device memory from the library's pool
     afg_front::HandleStream stream_;
@@ -59,7 +62,7 @@ private:
 // or whose format readSamples refuses, becomes an error item with the reference's decoding-error message.  Files that do
 // not pass the scan are left alone.
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep);
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, bool f64 = false);   // f64: afg_pcm_to_f64_hip, items point at doubles
 
 extern const char *const kMessageDecodingError;             // internals.d: kErrorDecodingError
 

@@ -42,18 +42,20 @@ int StreamConv::decode(const uint8_t *file, uint64_t frame0, uint64_t frames)
     span.count = count;
     span.kind = (uint32_t)kind_of(info);
     const uint64_t tiles = afg_wav_layout(&span, 1);
-    const size_t in_bytes = align16(bytes), out_floats = (size_t)((count + 3) & ~(uint64_t)3);
-    if (in_.alloc(in_bytes) || out_.alloc(out_floats * sizeof(float)) || spans_.alloc(sizeof(span))) return AFG_ERR_OOM;
-    fifo_.resize((size_t)count);
+    const size_t in_bytes = align16(bytes), out_samples = (size_t)((count + 3) & ~(uint64_t)3);
+    if (in_.alloc(in_bytes) || out_.alloc(out_samples * es_) || spans_.alloc(sizeof(span))) return AFG_ERR_OOM;
+    fifo_.resize((size_t)count * es_);
     fifo_frame_ = frame0;
     AFG_HIP_CHECK(hipMemcpyAsync(spans_.p, &span, sizeof(span), hipMemcpyHostToDevice, st));
     AFG_HIP_CHECK(hipMemcpyAsync(in_.p, file + info.samples_off + frame0 * C * B, bytes, hipMemcpyHostToDevice, st));
-    if (int rc = afg_wav_convert_hip(1, (const afg_wav_span *)spans_.p, tiles, (const uint8_t *)in_.p, in_bytes, (float *)out_.p,
-                                     out_floats, st)) {
+    const int rc = es_ == sizeof(double)
+                       ? afg_pcm_to_f64_hip(1, (const afg_wav_span *)spans_.p, tiles, (const uint8_t *)in_.p, in_bytes, (double *)out_.p, out_samples, st)
+                       : afg_wav_convert_hip(1, (const afg_wav_span *)spans_.p, tiles, (const uint8_t *)in_.p, in_bytes, (float *)out_.p, out_samples, st);
+    if (rc) {
         fifo_.clear();
         return rc;
     }
-    hipError_t e = hipMemcpyAsync(fifo_.data(), out_.p, count * sizeof(float), hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemcpyAsync(fifo_.data(), out_.p, count * es_, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         fifo_.clear();
@@ -63,10 +65,14 @@ int StreamConv::decode(const uint8_t *file, uint64_t frame0, uint64_t frames)
     return AFG_OK;
 }
 
-int StreamConv::read(const uint8_t *file, size_t size, float *out, int frames, bool *failed)
+int StreamConv::read(const uint8_t *file, size_t size, void *out, int frames, bool *failed, bool f64)
 {
     (void)size;
     *failed = false;
+    if (es_ != (f64 ? sizeof(double) : sizeof(float))) {                  // a change of type: what is held is of the other one
+        fifo_.clear();
+        es_ = f64 ? sizeof(double) : sizeof(float);
+    }
     if (frames <= 0) return 0;
     // wav.d:247-255: the request is clamped to what the header declares and the position moves before anything is read
     const uint32_t n = std::min<uint32_t>((uint32_t)frames, info.frames - position_);
@@ -79,13 +85,13 @@ int StreamConv::read(const uint8_t *file, size_t size, float *out, int frames, b
     const uint64_t chunk = std::max<uint64_t>(1, kStreamChunkSamples / C), valid_end = std::min<uint64_t>(info.frames, info.present / C);
     uint64_t f = first, done = 0;
     while (done < n) {
-        uint64_t held = fifo_.size() / C;
+        uint64_t held = fifo_.size() / (es_ * C);
         if (f < fifo_frame_ || f >= fifo_frame_ + held) {
             if (decode(file, f, std::min(valid_end - f, chunk)) != AFG_OK) return -1;
-            held = fifo_.size() / C;
+            held = fifo_.size() / (es_ * C);
         }
         const uint64_t take = std::min<uint64_t>(n - done, fifo_frame_ + held - f);
-        if (out) std::memcpy(out + done * C, fifo_.data() + (f - fifo_frame_) * C, (size_t)(take * C) * sizeof(float));
+        if (out) std::memcpy((uint8_t *)out + done * C * es_, fifo_.data() + (f - fifo_frame_) * C * es_, (size_t)(take * C) * es_);
         f += take;
         done += take;
     }
@@ -93,9 +99,10 @@ int StreamConv::read(const uint8_t *file, size_t size, float *out, int frames, b
 }
 
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep)
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, bool f64)
 {
     if (which.empty()) return AFG_OK;
+    const size_t es = f64 ? sizeof(double) : sizeof(float);       // bytes per sample of the PCM plane (span offsets count samples)
     // ---- the scan, one file per helper-thread job ----
     struct File { bool ok = false; Info info; int kind = -1; uint64_t out_off = 0; };
     std::vector<File> files(which.size());
@@ -171,7 +178,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
 
     // page-locked: the PCM plane the items point into (owned by `keep`) and two input stagings that take turns
     void *pcm = nullptr, *stage[2] = { nullptr, nullptr };
-    std::shared_ptr<void> pcm_owner = afg_front::staging_lease(std::max<uint64_t>(plane_floats, 4) * sizeof(float), &pcm);
+    std::shared_ptr<void> pcm_owner = afg_front::staging_lease(std::max<uint64_t>(plane_floats, 4) * es, &pcm);
     if (!pcm_owner) return AFG_ERR_OOM;
     std::shared_ptr<void> stage_owner[2];
     for (int b = 0; b < (C > 1 ? 2 : 1); b++)
@@ -180,7 +187,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
     if (int rc = d_spans.alloc(std::max<size_t>(spans.size(), 1) * sizeof(afg_wav_span))) return rc;
     for (int b = 0; b < (C > 1 ? 2 : 1); b++) {
         if (int rc = d_in[b].alloc((size_t)max_in)) return rc;
-        if (int rc = d_out[b].alloc((size_t)max_out * sizeof(float))) return rc;
+        if (int rc = d_out[b].alloc((size_t)max_out * es)) return rc;
     }
     // what chunk c takes up and brings back: both end with its last piece
     auto in_bytes = [&](size_t c) {
@@ -207,11 +214,14 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
             return AFG_OK;
         },
         [&](size_t c, int b, hipStream_t up) -> int {
+            if (f64)
+                return afg_pcm_to_f64_hip(first[c + 1] - first[c], (const afg_wav_span *)d_spans.p + first[c], tiles[c], (const uint8_t *)d_in[b].p,
+                                          in_bytes(c), (double *)d_out[b].p, (out_floats(c) + 3) & ~(uint64_t)3, up);
             return afg_wav_convert_hip(first[c + 1] - first[c], (const afg_wav_span *)d_spans.p + first[c], tiles[c], (const uint8_t *)d_in[b].p,
                                        in_bytes(c), (float *)d_out[b].p, (out_floats(c) + 3) & ~(uint64_t)3, up);
         },
         [&](size_t c, int b, hipStream_t down) -> int {
-            AFG_HIP_CHECK(hipMemcpyAsync((float *)pcm + chunk_out0[c], d_out[b].p, (size_t)out_floats(c) * sizeof(float), hipMemcpyDeviceToHost, down));
+            AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)pcm + chunk_out0[c] * es, d_out[b].p, (size_t)out_floats(c) * es, hipMemcpyDeviceToHost, down));
             return AFG_OK;
         });
     if (rc) return rc;
@@ -220,7 +230,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
         if (!f.ok) continue;
         afg_batch_item &it = items[which[k]];
         it.frames = (int64_t)f.info.frames;
-        it.pcm = f.info.frames ? (float *)pcm + f.out_off : nullptr;
+        it.pcm = f.info.frames ? (float *)((uint8_t *)pcm + f.out_off * es) : nullptr;
     }
     keep = pcm_owner;
     return AFG_OK;

@@ -174,7 +174,7 @@ uint64_t render_song(Song &song, Records &rec, bool *capped);
 // An XM stream: each read runs the control layer for exactly the read's frames and mixes them on the device.
 class StreamMix {
 public:
-    int read(float *out, int frames);                       // -1: device error (afg_last_error says which)
+    int read(void *out, int frames, bool f64 = false);      // -1: device error (afg_last_error says which); f64: doubles (stream.d:732-739)
     Song song;
 private:
     afg_front::DevBuf data_, recs_, out_;
@@ -182,12 +182,12 @@ private:
     afg_front::HandleStream stream_;
     Records rec_;
     std::vector<uint8_t> staging_;
-    std::vector<float> bounce_;
+    afg_front::PlaneFetch fetch_;
 };
 
 // The batch path's XM stage, shaped like afg_mod::batch_stage: the files of `which` that pass the probe are simulated on
 // the helper threads, mixed in chunks with mix and download overlapped, and their items filled in.
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep);
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, bool f64 = false);   // f64: items point at doubles (afg_batch_opts.sample_type)
 
 }  // namespace afg_xm

@@ -32,7 +32,7 @@ struct InLayout {
 
 }  // namespace
 
-int StreamMix::read(float *out, int frames)
+int StreamMix::read(void *out, int frames, bool f64)
 {
     if (frames <= 0 || song.loop_count() >= 1) return 0;            // stream.d:600: the song is finished
     rec_.clear();
@@ -67,16 +67,14 @@ int StreamMix::read(float *out, int frames)
     if (afg_xm_render_hip(1, (const afg_xm_song *)(r + song_at), (const afg_xm_segment *)(r + L.segs), (const afg_xm_tick *)(r + L.ticks),
                           (const uint8_t *)data_.p, (const float *)(r + L.aux), (float *)out_.p, st))
         return -1;
-    float *dst = out;
-    if (!dst) { bounce_.resize((size_t)n * 2); dst = bounce_.data(); }
-    AFG_HIP_CHECK(hipMemcpyAsync(dst, out_.p, out_bytes, hipMemcpyDeviceToHost, st));
-    AFG_HIP_CHECK(hipStreamSynchronize(st));
+    if (fetch_.run(out_.p, AFG_WAV_KIND_F32, (uint64_t)n * 2, out, f64, st)) return -1;
     return n;
 }
 
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep)
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, bool f64)
 {
+    const size_t es = f64 ? sizeof(double) : sizeof(float);       // bytes per sample of the PCM plane the items point into
     if (which.empty()) return AFG_OK;
     struct Sim {
         bool ok = false, capped = false, refused = false;
@@ -130,7 +128,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
         data_bytes += align16(s.song.sample_data().size());
     }
     void *pcm = nullptr, *in = nullptr;
-    const size_t pcm_bytes = std::max<uint64_t>(frames, 1) * 2 * sizeof(float);
+    const size_t pcm_bytes = std::max<uint64_t>(frames, 1) * 2 * es;
     const InLayout L(n_ticks, n_segs, n_aux, data_bytes);
     std::shared_ptr<void> pcm_owner = afg_front::staging_lease(pcm_bytes, &pcm);
     if (!pcm_owner) return AFG_ERR_OOM;
@@ -154,6 +152,8 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
     if (int rc = d_in.alloc(L.bytes)) return rc;
     if (int rc = d_songs.alloc(M * sizeof(afg_xm_song))) return rc;
     for (DevBuf &b : d_out) if (int rc = b.alloc(chunks.max_frames * 2 * sizeof(float))) return rc;
+    afg_front::F64Slots wide;                              // f64: the mixed floats stay on the device and are widened there
+    if (f64) if (int rc = wide.alloc(chunks.max_frames * 2)) return rc;
     const uint8_t *din = (const uint8_t *)d_in.p;
     const int rc = afg_front::run_chunks(
         chunks.count(),
@@ -165,13 +165,15 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
         /* upload */ nullptr,                              // no per-chunk upload: nothing waits on the host
         [&](size_t c, int slot, hipStream_t up) -> int {
             // the padding frames between songs are never mixed; the items do not reach them
-            return afg_xm_render_hip((uint32_t)(first[c + 1] - first[c]), (const afg_xm_song *)d_songs.p + first[c],
-                                     (const afg_xm_segment *)(din + L.segs), (const afg_xm_tick *)(din + L.ticks) + songs[first[c]].tick_base,
-                                     din + L.data, (const float *)(din + L.aux), (float *)d_out[slot].p, up);
+            if (int rc = afg_xm_render_hip((uint32_t)(first[c + 1] - first[c]), (const afg_xm_song *)d_songs.p + first[c],
+                                           (const afg_xm_segment *)(din + L.segs), (const afg_xm_tick *)(din + L.ticks) + songs[first[c]].tick_base,
+                                           din + L.data, (const float *)(din + L.aux), (float *)d_out[slot].p, up))
+                return rc;
+            return f64 ? wide.launch(slot, AFG_WAV_KIND_F32, d_out[slot].p, chunks.frames[c] * 2, up) : AFG_OK;
         },
         [&](size_t c, int slot, hipStream_t down) -> int {
             if (chunks.frames[c])
-                AFG_HIP_CHECK(hipMemcpyAsync((float *)pcm + 2 * start[first[c]], d_out[slot].p, chunks.frames[c] * 2 * sizeof(float),
+                AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)pcm + 2 * start[first[c]] * es, f64 ? wide.wide[slot].p : d_out[slot].p, chunks.frames[c] * 2 * es,
                                              hipMemcpyDeviceToHost, down));
             return AFG_OK;
         });
@@ -185,7 +187,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
         it.channels = 2;
         it.samplerate = (float)kRate;
         it.frames = (int64_t)s.frames;
-        it.pcm = s.frames ? (float *)pcm + 2 * songs[j].out_frame : nullptr;
+        it.pcm = s.frames ? (float *)((uint8_t *)pcm + 2 * songs[j].out_frame * es) : nullptr;
     }
     keep = pcm_owner;
     return AFG_OK;

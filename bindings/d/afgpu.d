@@ -204,6 +204,7 @@ int afg_get_num_channels(const(afg_stream)* s);
 long afg_get_length_in_frames(const(afg_stream)* s);
 float afg_get_samplerate(const(afg_stream)* s);
 int afg_read_samples_float(afg_stream* s, float* outData, int frames);
+int afg_read_samples_double(afg_stream* s, double* outData, int frames);   // readSamplesDouble, stream.d:656-747
 int afg_can_seek(const(afg_stream)* s);
 int afg_seek_position(afg_stream* s, int frame);
 int afg_tell_position(const(afg_stream)* s);
@@ -297,7 +298,8 @@ struct afg_batch_result
 int afg_batch_decode(const(ubyte*)* data, const(size_t)* length, int n_files, int n_threads, afg_batch_result* result);
 
 // ---- round 2: device selection, multi-device batches, MP3 quantised upload, CELT on two streams, dithered WAV ----
-struct afg_batch_opts { uint struct_size; int n_threads; int n_devices; const(int)* devices; }
+enum uint AFG_SAMPLE_F32 = 0, AFG_SAMPLE_F64 = 1;   // AFG_SAMPLE_F64: an item's pcm points at frames * channels doubles (readSamplesDouble's)
+struct afg_batch_opts { uint struct_size; int n_threads; int n_devices; const(int)* devices; uint sample_type; }
 int afg_set_device(int device);
 int afg_get_device();
 int afg_batch_decode_ex(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_batch_opts)* opts, afg_batch_result* result);
@@ -385,6 +387,9 @@ struct afg_wav_parsed
 ulong afg_wav_layout(afg_wav_span* spans, ulong n_spans);
 int afg_wav_convert_hip(ulong n_spans, const(afg_wav_span)* d_spans, ulong n_tiles, const(ubyte)* d_in, ulong in_bytes,
                         float* d_out, ulong out_floats, void* hip_stream);
+enum uint AFG_F64_KIND_FLAC_S32 = 6;
+int afg_pcm_to_f64_hip(ulong n_spans, const(afg_wav_span)* d_spans, ulong n_tiles, const(ubyte)* d_in, ulong in_bytes,
+                       double* d_out, ulong out_doubles, void* hip_stream);
 int afg_wav_parse(const(ubyte)* data, size_t length, afg_wav_parsed* parsed);
 int afg_is_module(const(afg_stream)* s);
 int afg_module_pattern_count(const(afg_stream)* s);
@@ -492,5 +497,11 @@ nothrow @nogc:
     {
         const int ch = getNumChannels();
         return ch > 0 ? readSamplesFloat(outData.ptr, cast(int)(outData.length / ch)) : 0;
+    }
+    int readSamplesDouble(double* outData, int frames) { return afg_read_samples_double(_h, outData, frames); }
+    int readSamplesDouble(double[] outData)
+    {
+        const int ch = getNumChannels();
+        return ch > 0 ? readSamplesDouble(outData.ptr, cast(int)(outData.length / ch)) : 0;
     }
 }

@@ -403,6 +403,16 @@ int64_t     afg_get_length_in_frames(const afg_stream *s);     /* AFG_UNKNOWN_LE
 float       afg_get_samplerate(const afg_stream *s);
 /* readSamplesFloat (stream.d:429-637): interleaved, returns frames read (< frames: end or error). */
 int         afg_read_samples_float(afg_stream *s, float *out, int frames);
+/* readSamplesDouble (stream.d:656-747): the same contract with float64 samples -- 0 on NULL, an errored or writing handle
+ * or frames <= 0; the FLAC entry check, the WAV and Opus failure rules, out == NULL skipping frames, and one position
+ * shared with the float read, seek and tell.  The doubles are the reference's: WAV samples converted directly
+ * (wav.d:242-344: the double quotient, all 32 bits of s32, f64 as stored), FLAC the int32 sample times 1.0 / int.max
+ * without narrowing (stream.d:707-717), every other format the float read widened (stream.d:732-739; QOA: qoa.d:831-838).
+ * They are made on the device (afg_pcm_to_f64_hip) from the file's sample bytes (WAV), the int32 plane (FLAC) or the
+ * float plane of the chunk; neither floats nor ints come to the host.  Float and double reads may be mixed on one
+ * handle: each returns what a handle that only ever used its type returns at that position (a change of type is a seek
+ * to the current position: what was decoded ahead in the other type is dropped and decoded again). */
+int         afg_read_samples_double(afg_stream *s, double *out, int frames);
 /* canSeek / seekPosition / tellPosition (stream.d:352-369, :1095-1189, :1208-1261): positions are frames; a seek outside
  * [0, length] fails and leaves the position alone (the invariants of examples/transcode's additionalTests). */
 int         afg_can_seek(const afg_stream *s);
@@ -537,7 +547,8 @@ typedef struct afg_batch_item {
     int         channels;
     float       samplerate;
     int64_t     frames;
-    float      *pcm;           /* frames * channels floats, NULL on error */
+    float      *pcm;           /* frames * channels floats, NULL on error; with afg_batch_opts.sample_type ==
+                                  AFG_SAMPLE_F64 it points at frames * channels doubles (cast it) */
 } afg_batch_item;
 
 typedef struct afg_batch_result {
@@ -561,11 +572,18 @@ void afg_batch_free(afg_batch_result *result);
  *                    longest-first to the least loaded device; every device gets its own host thread, helper
  *                    threads (n_threads in total, 0 = one per physical core) and stream set.  Per-file results do
  *                    not depend on the number of devices. */
+/*   sample_type      AFG_SAMPLE_F32: the items' pcm are floats, as afg_batch_decode delivers them.  AFG_SAMPLE_F64: they
+ *                    are the doubles of afg_read_samples_double (stream.d:656-747), made on the device in every stage
+ *                    between the codec's kernels and the download -- WAV from the file's bytes, FLAC from the int32
+ *                    plane, every other format from its float plane.  Any other value: AFG_ERR_INVALID, before any work. */
+#define AFG_SAMPLE_F32 0
+#define AFG_SAMPLE_F64 1
 typedef struct afg_batch_opts {
     uint32_t   struct_size;    /* sizeof(afg_batch_opts) */
     int        n_threads;
     int        n_devices;
     const int *devices;
+    uint32_t   sample_type;    /* AFG_SAMPLE_*; a struct_size that does not reach this field means AFG_SAMPLE_F32 */
 } afg_batch_opts;
 
 int  afg_set_device(int device);
@@ -910,6 +928,20 @@ uint64_t afg_wav_layout(afg_wav_span *spans, uint64_t n_spans);
  * converted at all.  Input and output must not overlap. */
 int afg_wav_convert_hip(uint64_t n_spans, const afg_wav_span *d_spans, uint64_t n_tiles, const uint8_t *d_in, uint64_t in_bytes,
                         float *d_out, uint64_t out_floats, void *hip_stream);
+
+/* The same spans to float64: readSamples!double (wav.d:242-344) for the six WAV kinds, and what AudioStream.
+ * readSamplesDouble does to the other decoders' output (stream.d:656-747).  out_off and count are in doubles; the fast
+ * path needs in_off 16-byte aligned and out_off even.  Bit-identical to IEEE float64 arithmetic:
+ *   U8 / S16 / S24  the correctly rounded quotient of the integer by 127.0 / 32767.0 / 8388607.0   wav.d:297-319
+ *   S32             s / 2147483648.0, exact                                                         wav.d:329
+ *   F32             widened: denormals kept, a quiet NaN keeps sign and payload, a signalling NaN comes out a NaN with
+ *                   its sign (stream.d:732-739 for the float decoders' planes)                      wav.d:266-269
+ *   F64             the 64 bits as they are                                                         wav.d:276-279
+ *   FLAC_S32        (double)s * (1.0 / 2147483647.0), one rounding: drflac_read_s32's int32          stream.d:713-716
+ * A span that does not lie inside [0, in_bytes) / [0, out_doubles) is not converted at all. */
+#define AFG_F64_KIND_FLAC_S32 6
+int afg_pcm_to_f64_hip(uint64_t n_spans, const afg_wav_span *d_spans, uint64_t n_tiles, const uint8_t *d_in, uint64_t in_bytes,
+                       double *d_out, uint64_t out_doubles, void *hip_stream);
 
 /* Host front-end on its own (no device needed): WAVDecoder.scan.  AFG_ERR_UNSUPPORTED: the scan refuses the file
  * (afg_last_error carries the reference's reason). */
