@@ -54,6 +54,7 @@ WAV_PACK_SPAN_DTYPE = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), (
                                 ("draw0", np.uint64), ("seed", np.uint32), ("format", np.uint8), ("dither", np.uint8),
                                 ("pad", np.uint8, (2,))])
 assert WAV_PACK_SPAN_DTYPE.itemsize == 48
+PCM_PACK_SPAN_DTYPE = WAV_PACK_SPAN_DTYPE        # afg_pcm_pack_span: the same fields; in_off and out_off are free, format <= WAV_S24LE
 
 # every symbol include/afg.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -86,6 +87,7 @@ ABI_SYMBOLS = [
     "afg_open_to_buffer", "afg_open_to_memory", "afg_is_open_for_reading", "afg_is_open_for_writing",
     "afg_write_samples_float", "afg_write_samples_double", "afg_finalize_encoding", "afg_finalize_and_get_encoded",
     "afg_batch_encode", "afg_encode_free",
+    "afg_pcm_pack_layout", "afg_pcm_pack_hip", "afg_batch_transcode",
 ]
 
 
@@ -208,11 +210,15 @@ class BatchItem(C.Structure):
 
 class BatchOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_threads", C.c_int), ("n_devices", C.c_int), ("devices", C.POINTER(C.c_int)),
-                ("sample_type", C.c_uint32)]
+                ("sample_type", C.c_uint32), ("dither", C.c_int), ("dither_seed", C.c_uint32)]
 
 
-SAMPLE_F32, SAMPLE_F64 = 0, 1             # afg_batch_opts.sample_type
+SAMPLE_F32, SAMPLE_F64, SAMPLE_PCM_S8, SAMPLE_PCM_S16, SAMPLE_PCM_S24 = range(5)     # afg_batch_opts.sample_type
 BATCH_OPTS_SIZE_V1 = BatchOpts.sample_type.offset        # the struct before sample_type was appended
+BATCH_OPTS_SIZE_V2 = BatchOpts.dither.offset             # ... up to sample_type, before dither and dither_seed were
+# what an item's pcm is viewed as, per sample type: (numpy dtype, trailing shape)
+_SAMPLE_VIEW = {SAMPLE_F32: (np.float32, ()), SAMPLE_F64: (np.float64, ()), SAMPLE_PCM_S8: (np.uint8, ()),
+                SAMPLE_PCM_S16: (np.int16, ()), SAMPLE_PCM_S24: (np.uint8, (3,))}
 
 
 class EncodingOptions(C.Structure):
@@ -252,7 +258,8 @@ _DEV_ENV = {"AFG_CELT_PATH": ("celt_path", {"stream": 1, "split": 2, "walk": 3})
             "AFG_CELT_WHOLE_FRAMES": ("celt_whole_frames", None), "AFG_VORBIS_SINGLE": ("vorbis_single", None),
             "AFG_MP3_CHUNKS": ("mp3_chunks", None), "AFG_MP3_FLOAT_UPLOAD": ("mp3_float_upload", None),
             "AFG_VORBIS_HOST_FLOOR": ("vorbis_host_floor", None), "AFG_FLAC_HOST_RES32": ("flac_host_res32", None),
-            "AFG_VORBIS_SEG_PACKETS": ("vorbis_seg_packets", None), "AFG_BATCH_GROUPS": ("batch_groups", None)}
+            "AFG_VORBIS_SEG_PACKETS": ("vorbis_seg_packets", None), "AFG_BATCH_GROUPS": ("batch_groups", None),
+            "AFG_STAGE_CHUNK_SAMPLES": ("stage_chunk_samples", None)}
 _dev_seen = {}
 
 
@@ -420,6 +427,11 @@ def lib():
                                    C.POINTER(EncodeResult)]
     L.afg_encode_free.argtypes = [C.POINTER(EncodeResult)]
     L.afg_encode_free.restype = None
+    L.afg_pcm_pack_layout.argtypes = [vp, u64]
+    L.afg_pcm_pack_layout.restype = u64
+    L.afg_pcm_pack_hip.argtypes = [u64, vp, u64, vp, u64, vp, u64, vp]
+    L.afg_batch_transcode.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(EncodingOptions), C.POINTER(BatchOpts),
+                                      C.POINTER(EncodeResult)]
     _lib = L
     _sync_dev_options(L)
     return L
@@ -947,6 +959,19 @@ def wav_pack(n_spans, d_spans, n_tiles, d_in, in_floats, d_out, out_bytes, strea
                                  int(out_bytes), _stream(stream)))
 
 
+def pcm_pack_layout(spans):
+    """afg_pcm_pack_layout: fills first_tile of a PCM_PACK_SPAN_DTYPE array in place; returns the launch's tile count.
+    Needs no device."""
+    assert spans.dtype == PCM_PACK_SPAN_DTYPE and spans.flags.c_contiguous
+    return int(lib().afg_pcm_pack_layout(spans.ctypes.data, len(spans)))
+
+
+def pcm_pack(n_spans, d_spans, n_tiles, d_in, in_floats, d_out, out_bytes, stream=None):
+    """Enqueue the decode stages' packer (afg_pcm_pack_hip) on device arrays: spans at any float / any byte."""
+    check(lib().afg_pcm_pack_hip(int(n_spans), _ptr(d_spans), int(n_tiles), _ptr(d_in), int(in_floats), _ptr(d_out),
+                                 int(out_bytes), _stream(stream)))
+
+
 def encoding_options(sample_format=WAV_FP32LE, dither=DITHER_LIBC, dither_seed=0):
     return EncodingOptions(C.sizeof(EncodingOptions), int(sample_format), int(dither), int(dither_seed) & 0xffffffff)
 
@@ -1115,12 +1140,16 @@ class BatchDecoded:
     """Result of afg_batch_decode kept in the library's (page-locked) result plane: ``items[i]`` are dicts whose
     ``pcm`` arrays are views, valid until ``close()`` (or the end of a ``with`` block)."""
 
-    def __init__(self, files, n_threads=0, devices=None, dtype=np.float32):
+    def __init__(self, files, n_threads=0, devices=None, dtype=np.float32, sample_type=None, dither=DITHER_OFF, dither_seed=0):
         """devices: None = the current device; "all" = every visible device; or a list of device indices.
-        dtype: np.float32, or np.float64 for the doubles of readSamplesDouble (afg_batch_opts.sample_type)."""
+        dtype: np.float32, or np.float64 for the doubles of readSamplesDouble (afg_batch_opts.sample_type).
+        sample_type (overrides dtype): SAMPLE_*; the SAMPLE_PCM_* types deliver uint8 (s8), int16 or uint8[..., 3] (s24)
+        arrays, dithered as `dither` / `dither_seed` say (DITHER_OFF or DITHER_LCG31)."""
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise ValueError("batch_decode delivers float32 or float64")
+        self.sample_type = (SAMPLE_F64 if self.dtype == np.float64 else SAMPLE_F32) if sample_type is None else int(sample_type)
+        self.dither, self.dither_seed = int(dither), int(dither_seed) & 0xffffffff
         self.devices = devices
         self._bufs = [bytes(f) for f in files]
         n = len(self._bufs)
@@ -1135,7 +1164,7 @@ class BatchDecoded:
         """The timed part: host parse + device restore + copy back -- the C call and nothing else (the per-file views of
         `items` are made when they are first asked for: two thousand numpy views cost more than some of these calls)."""
         self.close()
-        opts = BatchOpts(C.sizeof(BatchOpts), self.n_threads, 0, None, SAMPLE_F64 if self.dtype == np.float64 else SAMPLE_F32)
+        opts = BatchOpts(C.sizeof(BatchOpts), self.n_threads, 0, None, self.sample_type, self.dither, self.dither_seed)
         if self.devices == "all":
             opts.n_devices = -1
         elif self.devices is not None:
@@ -1154,9 +1183,12 @@ class BatchDecoded:
                 for i in range(self._res.n_files):
                     it = self._res.items[i]
                     cnt = it.frames * it.channels
-                    ptr = it.pcm if self.dtype == np.float32 else C.cast(it.pcm, C.POINTER(C.c_double))
-                    pcm = (np.ctypeslib.as_array(ptr, shape=(cnt,)).reshape(-1, max(1, it.channels))
-                           if cnt and it.pcm else None)
+                    dt, tail = _SAMPLE_VIEW[self.sample_type]
+                    pcm = None
+                    if cnt and it.pcm:
+                        nbytes = cnt * np.dtype(dt).itemsize * (tail[0] if tail else 1)
+                        raw = np.ctypeslib.as_array(C.cast(it.pcm, C.POINTER(C.c_uint8)), shape=(nbytes,))
+                        pcm = raw.view(dt).reshape((-1, max(1, it.channels)) + tail)
                     self._items.append({"status": it.status, "message": None if it.message is None else it.message.decode(),
                                         "format": it.format, "channels": it.channels, "samplerate": it.samplerate,
                                         "frames": it.frames, "pcm": pcm})
@@ -1194,11 +1226,39 @@ def get_device():
     return d
 
 
-def batch_decode(files, n_threads=0, devices=None, dtype=np.float32):
+def batch_decode(files, n_threads=0, devices=None, dtype=np.float32, sample_type=None, dither=DITHER_OFF, dither_seed=0):
     """afg_batch_decode(_ex): list of dicts (status, message, format, channels, samplerate, frames, pcm ndarray copy of
-    `dtype`: np.float32, or np.float64 for the doubles afg_read_samples_double returns)."""
-    with BatchDecoded(files, n_threads, devices, dtype) as res:
+    `dtype`: np.float32, or np.float64 for the doubles afg_read_samples_double returns).  sample_type = SAMPLE_PCM_S8 /
+    _S16 / _S24: pcm is the WAV body made on the device, uint8 / int16 [frames, channels] or uint8 [frames, channels, 3]."""
+    with BatchDecoded(files, n_threads, devices, dtype, sample_type, dither, dither_seed) as res:
         return [dict(it, pcm=None if it["pcm"] is None else it["pcm"].copy()) for it in res.items]
+
+
+def batch_transcode(files, options=None, n_threads=0, devices=None):
+    """afg_batch_transcode to WAV: options = encoding_options(...) (None: fp32).  devices as for batch_decode.  Returns a
+    list of dicts (status, message, bytes: the complete WAV file, None for a file that did not decode)."""
+    bufs = [bytes(f) for f in files]
+    n = len(bufs)
+    ptrs = (C.c_char_p * max(n, 1))(*bufs)
+    lens = (C.c_size_t * max(n, 1))(*[len(b) for b in bufs])
+    opts = BatchOpts(C.sizeof(BatchOpts), int(n_threads), 0, None, SAMPLE_F32, DITHER_OFF, 0)
+    if devices == "all":
+        opts.n_devices = -1
+    elif devices is not None:
+        devs = (C.c_int * len(devices))(*[int(d) for d in devices])
+        opts.n_devices, opts.devices = len(devices), devs
+    res = EncodeResult()
+    check(lib().afg_batch_transcode(ptrs, lens, n, FORMAT_WAV, None if options is None else C.byref(options), C.byref(opts),
+                                    C.byref(res)))
+    try:
+        out = []
+        for i in range(res.n_files):
+            it = res.items[i]
+            out.append({"status": it.status, "message": None if it.message is None else it.message.decode(),
+                        "bytes": C.string_at(it.bytes, it.size) if it.status == 0 else None})
+        return out
+    finally:
+        lib().afg_encode_free(C.byref(res))
 
 
 def copy_probe(d_dst, d_src, nbytes, stream=None):

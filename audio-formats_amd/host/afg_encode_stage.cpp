@@ -1,4 +1,5 @@
-// afg_encode_stage.cpp -- afg_batch_encode: interleaved float PCM in host memory to WAV or QOA files in host memory.
+// afg_encode_stage.cpp -- afg_batch_encode: interleaved float PCM in host memory to WAV or QOA files in host memory; and
+// afg_batch_transcode: compressed files in host memory to WAV files in host memory (at the end of this file).
 //
 // Helper threads copy the PCM into leased page-locked staging (that copy puts every piece on a 4-float boundary),
 // chunks go through two stagings and two pairs of device buffers with upload, kernel and download on the kept stream
@@ -13,6 +14,8 @@
 #include "../csrc/afg_common.h"
 
 #include <algorithm>
+#include <cstddef>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -296,6 +299,108 @@ int afg_batch_encode(const afg_encode_input *in, int n_files, int format, const 
         return AFG_OK;
     } catch (const std::bad_alloc &) {
         afg::set_error("afg_batch_encode: out of memory");
+        return AFG_ERR_OOM;
+    }
+}
+
+// Decode with the sample type the WAV format asks for -- the body of every file is made on the device and comes down at
+// its own width -- then one host copy per file on the pooled threads puts header and body side by side in the result's
+// plane.  (The other way, reserving 44 bytes in front of every file inside the decode stages' planes, would have every
+// stage lay its plane out for this one caller.)
+int afg_batch_transcode(const uint8_t *const *data, const size_t *length, int n_files, int out_format, const afg_encoding_options *enc,
+                        const afg_batch_opts *opts, afg_encode_result *out)
+{
+    if (out) { out->n_files = 0; out->items = nullptr; out->owner = nullptr; }
+    if (!out || n_files < 0 || (n_files > 0 && (!data || !length))) {
+        afg::set_error("afg_batch_transcode: bad arguments");
+        return AFG_ERR_INVALID;
+    }
+    if (enc && enc->struct_size != sizeof(afg_encoding_options)) {
+        afg::set_error("afg_batch_transcode: afg_encoding_options.struct_size does not match this library");
+        return AFG_ERR_INVALID;
+    }
+    if (opts && opts->struct_size < offsetof(afg_batch_opts, sample_type)) {
+        afg::set_error("afg_batch_transcode: afg_batch_opts.struct_size too small");
+        return AFG_ERR_INVALID;
+    }
+    if (out_format == AFG_FORMAT_QOA) {
+        afg::set_error("afg_batch_transcode: QOA output is not provided: the encoder's state runs through a whole file and the decode stages cut files at chunk borders; decode, then afg_batch_encode");
+        return AFG_ERR_UNSUPPORTED;
+    }
+    if (out_format != AFG_FORMAT_WAV) {
+        afg::set_error("afg_batch_transcode: only WAV is written");
+        return AFG_ERR_UNSUPPORTED;
+    }
+    const int sample_format = enc ? enc->sample_format : AFG_WAV_FP32LE;
+    const int dither = enc ? enc->dither : AFG_DITHER_OFF;
+    if (sample_format < AFG_WAV_S8 || sample_format > AFG_WAV_FP64LE) {
+        afg::set_error("afg_batch_transcode: unknown sample_format %d", sample_format);
+        return AFG_ERR_INVALID;
+    }
+    if (dither < AFG_DITHER_OFF || dither > AFG_DITHER_LCG31) {
+        afg::set_error("afg_batch_transcode: unknown dither %d", dither);
+        return AFG_ERR_INVALID;
+    }
+    const bool integer = sample_format <= AFG_WAV_S24LE;
+    if (integer && dither == AFG_DITHER_LIBC) {
+        afg::set_error("afg_batch_transcode: dither: libc rand() has no defined draw order across files; use AFG_DITHER_LCG31 or AFG_DITHER_OFF");
+        return AFG_ERR_INVALID;
+    }
+    try {
+        afg_batch_opts o;
+        std::memset(&o, 0, sizeof(o));
+        o.struct_size = sizeof(o);
+        if (opts) { o.n_threads = opts->n_threads; o.n_devices = opts->n_devices; o.devices = opts->devices; }
+        o.sample_type = integer ? (uint32_t)(AFG_SAMPLE_PCM_S8 + (sample_format - AFG_WAV_S8)) : sample_format == AFG_WAV_FP64LE ? AFG_SAMPLE_F64 : AFG_SAMPLE_F32;
+        o.dither = integer ? dither : AFG_DITHER_OFF;           // (the float formats never dither)
+        o.dither_seed = enc ? enc->dither_seed : 0;
+        afg_batch_result dec;
+        if (int rc = afg_batch_decode_ex(data, length, n_files, &o, &dec)) return rc;
+        struct FreeDecoded { afg_batch_result *r; ~FreeDecoded() { afg_batch_free(r); } } free_decoded{ &dec };
+        std::unique_ptr<EncodeOwner> owner(new EncodeOwner);
+        owner->items.resize((size_t)n_files);
+        const uint64_t B = (uint64_t)sample_size(sample_format);
+        std::vector<File> files((size_t)n_files);
+        uint64_t plane_bytes = 0;
+        for (int i = 0; i < n_files; i++) {
+            const afg_batch_item &d = dec.items[i];
+            afg_encoded_item &it = owner->items[(size_t)i];
+            File &f = files[(size_t)i];
+            it.status = d.status;
+            it.message = d.message;
+            it.bytes = nullptr;
+            it.size = 0;
+            if (d.status != AFG_OK) continue;
+            const float biased = d.samplerate + 0.5f;                          // stream.d:1852
+            if (d.channels < 1 || d.channels > 1024) { it.status = AFG_ERR_INVALID; it.message = kMessageChannels; continue; }
+            if (!(biased >= 0.0f && biased < 2147483648.0f)) { it.status = AFG_ERR_INVALID; it.message = kMessageRate; continue; }
+            f.ok = true;
+            f.rate = (uint32_t)(int)biased;
+            f.count = (uint64_t)std::max<int64_t>(d.frames, 0) * (uint64_t)d.channels;
+            f.at = plane_bytes;
+            f.size = kWavHeader + f.count * B;
+            plane_bytes = align16(plane_bytes + f.size);
+        }
+        // (pageable: nothing is copied from the device into this plane, and pinning costs about as much as a copy)
+        uint8_t *plane = (uint8_t *)std::malloc((size_t)std::max<uint64_t>(plane_bytes, 16));
+        if (!plane) throw std::bad_alloc();
+        owner->plane = std::shared_ptr<void>(plane, [](void *q) { std::free(q); });
+        afg_front::parallel_run((size_t)n_files, o.n_threads, [&](size_t k) {
+            const File &f = files[k];
+            if (!f.ok) return;
+            const afg_batch_item &d = dec.items[k];
+            uint8_t *p = plane + f.at;
+            wav_header(p, (uint64_t)std::max<int64_t>(d.frames, 0), (uint32_t)d.channels, f.rate, sample_format);
+            if (f.count) std::memcpy(p + kWavHeader, d.pcm, (size_t)(f.count * B));
+            owner->items[k].bytes = p;
+            owner->items[k].size = f.size;
+        });
+        out->n_files = n_files;
+        out->items = owner->items.data();
+        out->owner = owner.release();
+        return AFG_OK;
+    } catch (const std::bad_alloc &) {
+        afg::set_error("afg_batch_transcode: out of memory");
         return AFG_ERR_OOM;
     }
 }

@@ -468,8 +468,8 @@ struct Mp3Stage {
     size_t blocks = 0;
     const size_t *base = nullptr;
     float *plane = nullptr;             // host PCM plane, blocks * 576 floats (page-locked) ...
-    bool f64 = false;                   // ... or as many doubles (afg_batch_opts.sample_type): the transform's floats are widened on the device
-    size_t es() const { return f64 ? sizeof(double) : sizeof(float); }
+    SampleOut so;                       // ... or as many doubles / packed integer samples (afg_batch_opts.sample_type): made of the transform's floats on the device
+    size_t es() const { return so.es(); }
 };
 
 // Where the batch path parsed its Ogg Vorbis files: file i's spectra at float base[i] of one page-locked buffer
@@ -492,6 +492,7 @@ struct Mp3Pipe {
     const Mp3Stage *st = nullptr;
     DeviceBuf d_in, d_pcm, d_pcm64;
     std::vector<std::unique_ptr<F64Plane>> widen;          // one per chunk, alive until close() has drained the streams
+    std::vector<std::unique_ptr<PackPlane>> packs;         // likewise (AFG_SAMPLE_PCM_*)
     uint32_t *d_flags = nullptr;
     hipStream_t up = nullptr, down = nullptr;
     std::vector<afg_mp3_plan *> plans;
@@ -516,7 +517,7 @@ struct Mp3Pipe {
         const size_t coef_bytes = stage.blocks * 576 * sizeof(float), flag_bytes = (stage.blocks * 4 + 15) & ~(size_t)15;
         if (int r = d_in.alloc(coef_bytes + flag_bytes)) return r;
         if (int r = d_pcm.alloc(coef_bytes)) return r;
-        if (stage.f64) if (int r = d_pcm64.alloc(coef_bytes * 2)) return r;
+        if (stage.so.wide()) if (int r = d_pcm64.alloc(std::max<size_t>(stage.blocks * 576 * stage.es(), 16))) return r;
         if (stage.q) {
             const size_t q_bytes = (stage.blocks * 576 * sizeof(int16_t) + 15) & ~(size_t)15;
             const size_t rec_bytes = stage.blocks * sizeof(afg_mp3_qgranule);
@@ -598,16 +599,29 @@ struct Mp3Pipe {
         }
         rc = afg_mp3_transform_hip(plan, (const float *)d_in.p, d_flags, (float *)d_pcm.p, nullptr, up);
         if (rc) return;
-        if (st->f64) {
+        if (st->so.f64()) {
             widen.emplace_back(new F64Plane);
             rc = widen.back()->launch(AFG_WAV_KIND_F32, (const float *)d_pcm.p + b0 * 576, nb * 576, (double *)d_pcm64.p + b0 * 576, up);
+            if (rc) return;
+        } else if (st->so.pcm()) {
+            // a file's samples are the pieces of its copy plan, in order (with dither a sample's draws follow its index)
+            std::vector<PackRun> runs;
+            for (size_t i = f0; i < f1 && st->so.dither; i++) {
+                const Parsed &p = parsed[i];
+                if (p.format != AFG_FORMAT_MP3 || !p.mp3.blocks()) continue;
+                uint64_t at = 0;
+                for (const afg_mp3::Copy &c : p.mp3.copies) { runs.push_back(PackRun{ st->base[i] * 576 + c.src, c.count, at }); at += c.count; }
+            }
+            sort_runs(runs);
+            packs.emplace_back(new PackPlane);
+            rc = packs.back()->launch(st->so, (const float *)d_pcm.p, (uint8_t *)d_pcm64.p, 0, b0 * 576, nb * 576, runs, up);
             if (rc) return;
         }
         const size_t es = st->es();
         e = hipEventRecord(done, up);
         if (e == hipSuccess) e = hipStreamWaitEvent(down, done, 0);
         if (e == hipSuccess)
-            e = hipMemcpyAsync((uint8_t *)st->plane + b0 * 576 * es, (const uint8_t *)(st->f64 ? d_pcm64.p : d_pcm.p) + b0 * 576 * es, nb * 576 * es, hipMemcpyDeviceToHost, down);
+            e = hipMemcpyAsync((uint8_t *)st->plane + b0 * 576 * es, (const uint8_t *)(st->so.wide() ? d_pcm64.p : d_pcm.p) + b0 * 576 * es, nb * 576 * es, hipMemcpyDeviceToHost, down);
     }
     int close()
     {
@@ -615,7 +629,7 @@ struct Mp3Pipe {
         if (down) { hipError_t e2 = hipStreamSynchronize(down); if (e == hipSuccess) e = e2; }
         for (afg_mp3_plan *p : plans) afg_mp3_plan_destroy(p);
         for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
-        plans.clear(); events.clear(); widen.clear();
+        plans.clear(); events.clear(); widen.clear(); packs.clear();
         g_streams.give(up, down);
         up = down = nullptr;
         if (rc) return rc;
@@ -643,14 +657,19 @@ struct OpusCarry {
 int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const size_t *len, unsigned threads, BatchOut &out,
                   const Mp3Stage *stage = nullptr, const OggStage *ogg_stage = nullptr, const FlacStage *flac_stage = nullptr,
                   const uint8_t *own = nullptr, Mp3Carry *carry = nullptr, OpusCarry *opus_carry = nullptr,
-                  const size_t *opus_done_at = nullptr, bool f64 = false)
+                  const size_t *opus_done_at = nullptr, SampleOut so = SampleOut())
 {
     // f64 (afg_read_samples_double, afg_batch_opts.sample_type): the result plane holds doubles.  Every stage's device plane
     // -- int32 for FLAC, float for the others -- is widened by afg_pcm_to_f64_hip behind the stage's kernels, on their
     // stream, and the doubles are what comes back.  The batch path's MP3 and Opus planes were widened by their own pipelines.
-    if (stage && stage->blocks && stage->f64 != f64) { afg::set_error("decode_parsed: the MP3 stage's sample type differs"); return AFG_ERR_INVALID; }
-    const size_t es = f64 ? sizeof(double) : sizeof(float);
+    // AFG_SAMPLE_PCM_* (afg_batch_opts.sample_type): the result plane holds samples of 1, 2 or 3 bytes, packed from every
+    // stage's float plane by afg_pcm_pack_hip at the same place; FLAC restores to float as for a float read.
+    if (stage && stage->blocks && stage->so != so) { afg::set_error("decode_parsed: the MP3 stage's sample type differs"); return AFG_ERR_INVALID; }
+    const bool f64 = so.f64(), wide = so.wide();
+    const size_t es = so.es();
     out.f64 = f64;
+    // dither: where each file's samples lie in the stages' device planes (afg_stage.h: PackRun)
+    std::vector<PackRun> runs_main, runs_mp3, runs_ogg, runs_opus;
     // opus_done_at (batch path): the Opus files are already decoded, file i's PCM at float opus_done_at[i] of the batch's
     // Opus plane; only their metadata is filled in here
     // `own` (optional, one byte per file): the files this call is responsible for.  The batch path decodes its FLAC /
@@ -670,6 +689,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
         if (!flac_staged) res_total = (res_total + 3) & ~(size_t)3;     // 16-byte aligned planes (int16 rows: afg_flac_frame.res16)
         res_base[i] = flac_staged ? flac_stage->base[i] : res_total; fr_base[i] = fr_total; sf_base[i] = sf_total;
         out.files[i].pcm_off = flac_out;
+        if (so.dither) runs_main.push_back(PackRun{ flac_out, p.flac.out_samples, 0 });
         res_total += p.flac.res_size(); fr_total += p.flac.frames.size(); sf_total += p.flac.subframes.size();
         flac_out += p.flac.out_samples;
     }
@@ -681,7 +701,9 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
         out.files[i].pcm_off = flac_out + qoa_out;
         qbytes += (len[i] + 15) & ~(size_t)15;
         qframes += p.qoa.size();
-        qoa_out += p.qoa.back().out_off + (size_t)p.qoa.back().samples * p.qoa.back().channels;
+        const size_t q_samples = p.qoa.back().out_off + (size_t)p.qoa.back().samples * p.qoa.back().channels;
+        if (so.dither) runs_main.push_back(PackRun{ flac_out + qoa_out, q_samples, 0 });
+        qoa_out += q_samples;
     }
     std::vector<size_t> mp3_blk_base(nf, 0);
     size_t mp3_blocks = 0, mp3_out = 0;
@@ -689,6 +711,10 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
         Parsed &p = parsed[i];
         if (fmt_of(p) != AFG_FORMAT_MP3) continue;
         mp3_blk_base[i] = mp3_blocks;
+        if (so.dither) {
+            uint64_t at = 0;
+            for (const afg_mp3::Copy &c : p.mp3.copies) { runs_mp3.push_back(PackRun{ mp3_blocks * 576 + c.src, c.count, at }); at += c.count; }
+        }
         out.files[i].pcm_off = flac_out + qoa_out + mp3_out;
         mp3_blocks += p.mp3.blocks();
         mp3_out += (size_t)p.mp3.pcm_samples;
@@ -732,7 +758,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
         size_t total = 0;
         for (size_t i = 0; i < nf; i++)
             if (fmt_of(parsed[i]) == AFG_FORMAT_OGG) { total += parsed[i].ogg.n_spec; ogg_packets += parsed[i].ogg.pflags.size(); }
-        const size_t target = std::max<size_t>((total + tl_stage_chunks - 1) / tl_stage_chunks, (size_t)4 << 20);
+        const size_t target = std::max<size_t>((total + tl_stage_chunks - 1) / tl_stage_chunks, (size_t)stage_chunk_samples((size_t)4 << 20));
         for (size_t f0 = 0; f0 < nf && ogg_packets;) {
             size_t f1 = f0, acc = 0;
             while (f1 < nf && acc < target) { if (fmt_of(parsed[f1]) == AFG_FORMAT_OGG) acc += parsed[f1].ogg.n_spec; f1++; }
@@ -799,6 +825,10 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                     ogg_pieces.push_back(OggPiece{ i, ogg_out + from, cnt });
                     q = j;
                 }
+                if (so.dither) {
+                    uint64_t at = 0;
+                    for (size_t k = first_piece; k < ogg_pieces.size(); k++) { runs_ogg.push_back(PackRun{ ogg_pieces[k].from, ogg_pieces[k].count, at }); at += ogg_pieces[k].count; }
+                }
                 out.files[i].pcm_off = flac_out + qoa_out + mp3_out + (ogg_pieces.size() > first_piece ? (size_t)ogg_pieces[first_piece].from : ogg_out);
                 if (ogg_pieces.size() - first_piece > 1) ogg_broken.push_back(i);
                 else if (ogg_pieces.size() > first_piece) ogg_pieces.pop_back();          // one run: nothing to move
@@ -842,6 +872,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
             continue;
         }
         opus_rec_base[i] = opus_recs; opus_coef_base[i] = opus_coefs; opus_pcm_base[i] = opus_out;
+        if (so.dither) runs_opus.push_back(PackRun{ opus_out, (uint64_t)p.opus.pcm_frames * (uint64_t)p.opus.channels, 0 });
         out.files[i].pcm_off = flac_out + qoa_out + mp3_out + ogg_out + opus_out;
         opus_recs += p.opus.frames.size() * (size_t)p.opus.channels;
         opus_coefs += p.opus.coeffs.size();
@@ -862,12 +893,20 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
         //  go only after the device has drained, below them)
         DeviceBuf d_out, d_out64, d_mp3_64, d_ogg_64, d_opus_64;
         if (int rc = d_out.alloc(out.plane_floats * sizeof(float))) return rc;
-        if (f64) if (int rc = d_out64.alloc(std::max<size_t>(flac_out + qoa_out, 2) * sizeof(double))) return rc;   // FLAC and QOA are widened in place of the plane
+        if (wide) if (int rc = d_out64.alloc(std::max<size_t>((flac_out + qoa_out) * es, 16))) return rc;   // FLAC and QOA are converted in place of the plane
         std::vector<std::unique_ptr<F64Plane>> widen;        // one per conversion launch, alive until the stages have drained
-        struct Drain { bool on; ~Drain() { if (on) (void)hipDeviceSynchronize(); } } drain{ f64 };
-        auto to_f64 = [&](uint32_t kind, const void *src, uint64_t n, void *dst, hipStream_t st) -> int {
+        std::vector<std::unique_ptr<PackPlane>> packs;
+        struct Drain { bool on; ~Drain() { if (on) (void)hipDeviceSynchronize(); } } drain{ wide };
+        for (std::vector<PackRun> *r : { &runs_main, &runs_mp3, &runs_ogg, &runs_opus }) sort_runs(*r);
+        // samples [c0, c0 + n) of a stage's plane `src` (4-byte elements of `kind`) to the same samples of its converted
+        // plane `dst`: doubles, or packed integers
+        auto convert = [&](uint32_t kind, const void *src, uint64_t c0, uint64_t n, void *dst, const std::vector<PackRun> &runs, hipStream_t st) -> int {
+            if (so.pcm()) {
+                packs.emplace_back(new PackPlane);
+                return packs.back()->launch(so, (const float *)src, (uint8_t *)dst, 0, c0, n, runs, st);
+            }
             widen.emplace_back(new F64Plane);
-            return widen.back()->launch(kind, src, n, (double *)dst, st);
+            return widen.back()->launch(kind, (const uint8_t *)src + c0 * 4, n, (double *)dst + c0, st);
         };
         hipStream_t stream = nullptr;
         // ---- FLAC ----
@@ -893,7 +932,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
             std::vector<hipEvent_t> events;
             hipError_t e = g_streams.take(&up, &down, &mid);
             int rc = AFG_OK;
-            const size_t target = std::max<size_t>((res_total + tl_stage_chunks - 1) / tl_stage_chunks, (size_t)4 << 20);
+            const size_t target = std::max<size_t>((res_total + tl_stage_chunks - 1) / tl_stage_chunks, (size_t)stage_chunk_samples((size_t)4 << 20));
             // AFG_TRACE: host wall-clock of every chunk's gather and submission, device time of its upload, kernel and download
             struct ChunkTrace { double t_begin, t_gathered, t_queued; hipEvent_t e_up0, e_up1, e_k1, e_d0, e_d1; };
             std::vector<ChunkTrace> ctrace;
@@ -951,7 +990,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                 rc = afg_flac_transform_variants_hip(fr1 - fr0, df + fr0, ds, dr, f64 ? (int32_t *)d_out.p : nullptr, f64 ? nullptr : (float *)d_out.p,
                                                      afg_flac_variants(fr1 - fr0, hf + fr0, hs), mid);
                 if (rc) break;
-                if (f64 && (rc = to_f64(AFG_F64_KIND_FLAC_S32, (const int32_t *)d_out.p + o0, o1 - o0, (double *)d_out64.p + o0, mid)) != AFG_OK) break;
+                if (wide && (rc = convert(f64 ? AFG_F64_KIND_FLAC_S32 : AFG_WAV_KIND_F32, d_out.p, o0, o1 - o0, d_out64.p, runs_main, mid)) != AFG_OK) break;
                 if (g_trace) ct.e_k1 = mark(mid);
                 e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
                 if (e != hipSuccess) break;
@@ -960,7 +999,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                 if (e == hipSuccess) e = hipStreamWaitEvent(down, done, 0);
                 if (g_trace) ct.e_d0 = mark(down);
                 if (e == hipSuccess)
-                    e = hipMemcpyAsync((uint8_t *)out.plane.p + o0 * es, (const uint8_t *)(f64 ? d_out64.p : d_out.p) + o0 * es, (o1 - o0) * es, hipMemcpyDeviceToHost, down);
+                    e = hipMemcpyAsync((uint8_t *)out.plane.p + o0 * es, (const uint8_t *)(wide ? d_out64.p : d_out.p) + o0 * es, (o1 - o0) * es, hipMemcpyDeviceToHost, down);
                 if (g_trace) { ct.e_d1 = mark(down); ct.t_queued = since(); ctrace.push_back(ct); }
                 f0 = f1;
             }
@@ -1012,11 +1051,11 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
             if (int rc = afg_qoa_transform_hip(qframes, (const afg_qoa_frame *)d_in.p, (const uint8_t *)d_in.p + rec_pad, nullptr,
                                                (float *)d_out.p, stream))
                 return rc;
-            if (f64) if (int rc = to_f64(AFG_WAV_KIND_F32, (const float *)d_out.p + flac_out, qoa_out, (double *)d_out64.p + flac_out, stream)) return rc;
+            if (wide) if (int rc = convert(AFG_WAV_KIND_F32, d_out.p, flac_out, qoa_out, d_out64.p, runs_main, stream)) return rc;
             AFG_HIP_CHECK(hipStreamSynchronize(stream));
         }
         if (qoa_out) {                                       // (the FLAC part came back chunk by chunk)
-            AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)out.plane.p + flac_out * es, (const uint8_t *)(f64 ? d_out64.p : d_out.p) + flac_out * es, qoa_out * es,
+            AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)out.plane.p + flac_out * es, (const uint8_t *)(wide ? d_out64.p : d_out.p) + flac_out * es, qoa_out * es,
                                          hipMemcpyDeviceToHost, stream));
             AFG_HIP_CHECK(hipStreamSynchronize(stream));
         }
@@ -1028,7 +1067,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
             DeviceBuf &d_pcm64 = d_mp3_64;
             if (int rc = d_in.alloc(coef_bytes + flag_bytes)) return rc;
             if (int rc = d_pcm.alloc(coef_bytes)) return rc;
-            if (f64) if (int rc = d_pcm64.alloc(coef_bytes * 2)) return rc;
+            if (wide) if (int rc = d_pcm64.alloc(std::max<size_t>(mp3_blocks * 576 * es, 16))) return rc;
             // The files are cut into a few chunks of similar size, each with its own plan: the upload and kernel of
             // chunk k+1 (stream `up`) run while chunk k's PCM goes back (stream `down`) -- PCIe is full duplex.
             struct Chunk { size_t f0, f1, blk0, blocks; afg_mp3_plan *plan; hipEvent_t done; size_t runs = 0; };
@@ -1109,7 +1148,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                     if (e != hipSuccess) break;
                     carry->valid = true;
                 }
-                if (f64 && (rc = to_f64(AFG_WAV_KIND_F32, (const float *)d_pcm.p + c.blk0 * 576, c.blocks * 576, (double *)d_pcm64.p + c.blk0 * 576, up)) != AFG_OK) break;
+                if (wide && (rc = convert(AFG_WAV_KIND_F32, d_pcm.p, c.blk0 * 576, c.blocks * 576, d_pcm64.p, runs_mp3, up)) != AFG_OK) break;
                 e = hipEventRecord(c.done, up);
                 if (e == hipSuccess) e = hipStreamWaitEvent(down, c.done, 0);
                 // delivery: the copy plan of each file, merged into maximal contiguous pieces (one per undamaged file),
@@ -1117,7 +1156,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                 for (size_t i = c.f0; i < c.f1 && e == hipSuccess; i++) {
                     const Parsed &p = parsed[i];
                     if (fmt_of(p) != AFG_FORMAT_MP3) continue;
-                    const uint8_t *src = (const uint8_t *)(f64 ? d_pcm64.p : d_pcm.p) + mp3_blk_base[i] * 576 * es;
+                    const uint8_t *src = (const uint8_t *)(wide ? d_pcm64.p : d_pcm.p) + mp3_blk_base[i] * 576 * es;
                     uint8_t *dst = (uint8_t *)out.plane.p + out.files[i].pcm_off * es;
                     const std::vector<afg_mp3::Copy> &cp = p.mp3.copies;
                     for (size_t k = 0; k < cp.size() && e == hipSuccess;) {
@@ -1147,7 +1186,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
             StagingPool::Lease h_spec;
             DeviceBuf d_spec, d_pcm;
             DeviceBuf &d_pcm64 = d_ogg_64;
-            if (f64) if (int rc = d_pcm64.alloc(ogg_out * sizeof(double))) return rc;
+            if (wide) if (int rc = d_pcm64.alloc(std::max<size_t>(ogg_out * es, 16))) return rc;
             if (!ogg_staged)
                 if (int rc = g_staging.take(ogg_spec * sizeof(float), h_spec)) return rc;
             if (int rc = d_spec.alloc((ogg_staged ? ogg_stage->floats : ogg_spec) * sizeof(float))) return rc;
@@ -1241,12 +1280,12 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                 // a staged plan addresses the staging layout from float 0; a gathered one is packed from its chunk's start
                 rc = afg_vorbis_transform_hip(c.plan, (const float *)d_spec.p + (ogg_staged ? 0 : c.spec0), (float *)d_pcm.p + c.out0, up);
                 if (rc) break;
-                if (f64 && (rc = to_f64(AFG_WAV_KIND_F32, (const float *)d_pcm.p + c.out0, c.out_n, (double *)d_pcm64.p + c.out0, up)) != AFG_OK) break;
+                if (wide && (rc = convert(AFG_WAV_KIND_F32, d_pcm.p, c.out0, c.out_n, d_pcm64.p, runs_ogg, up)) != AFG_OK) break;
                 e = hipEventCreateWithFlags(&c.done, hipEventDisableTiming);
                 if (e == hipSuccess) e = hipEventRecord(c.done, up);
                 if (e == hipSuccess) e = hipStreamWaitEvent(down, c.done, 0);
                 if (e == hipSuccess)
-                    e = hipMemcpyAsync(ogg_plane + c.out0 * es, (const uint8_t *)(f64 ? d_pcm64.p : d_pcm.p) + c.out0 * es, c.out_n * es, hipMemcpyDeviceToHost, down);
+                    e = hipMemcpyAsync(ogg_plane + c.out0 * es, (const uint8_t *)(wide ? d_pcm64.p : d_pcm.p) + c.out0 * es, c.out_n * es, hipMemcpyDeviceToHost, down);
             }
             if (up) { hipError_t e2 = hipStreamSynchronize(up); if (e == hipSuccess) e = e2; }
             if (down) { hipError_t e2 = hipStreamSynchronize(down); if (e == hipSuccess) e = e2; }
@@ -1274,7 +1313,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
             StagingPool::Lease h_in;
             DeviceBuf d_in, d_pcm;
             DeviceBuf &d_pcm64 = d_opus_64;
-            if (f64) if (int rc = d_pcm64.alloc(opus_out * sizeof(double))) return rc;
+            if (wide) if (int rc = d_pcm64.alloc(std::max<size_t>(opus_out * es, 16))) return rc;
             if (int rc = g_staging.take(base_bytes + rec_bytes + opus_coefs * sizeof(float), h_in)) return rc;
             if (int rc = d_in.alloc(base_bytes + rec_bytes + opus_coefs * sizeof(float))) return rc;
             if (int rc = d_pcm.alloc(opus_out * sizeof(float))) return rc;
@@ -1337,8 +1376,8 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                     if (rc) return rc;
                 }
             }
-            if (f64) if (int rc = to_f64(AFG_WAV_KIND_F32, d_pcm.p, opus_out, d_pcm64.p, stream)) return rc;
-            AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)out.plane.p + (flac_out + qoa_out + mp3_out + ogg_out) * es, f64 ? d_pcm64.p : d_pcm.p, opus_out * es,
+            if (wide) if (int rc = convert(AFG_WAV_KIND_F32, d_pcm.p, 0, opus_out, d_pcm64.p, runs_opus, stream)) return rc;
+            AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)out.plane.p + (flac_out + qoa_out + mp3_out + ogg_out) * es, wide ? d_pcm64.p : d_pcm.p, opus_out * es,
                                          hipMemcpyDeviceToHost, stream));
             AFG_HIP_CHECK(hipStreamSynchronize(stream));
             tm.lap("opus gather | h2d | kernel | d2h");
@@ -2178,10 +2217,12 @@ struct BatchOwner {
 // `parse_done` (optional) is called once, when the host passes that keep every helper thread busy are over and what remains is
 // the device stages of decode_parsed: a grouped batch lets its next group start parsing then.
 int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_files, int n_threads, afg_batch_item *items,
-                        std::unique_ptr<BatchOut> &keep, const std::function<void()> *parse_done = nullptr, bool f64 = false)
+                        std::unique_ptr<BatchOut> &keep, const std::function<void()> *parse_done = nullptr, SampleOut so = SampleOut())
 {
-    // f64 (afg_batch_opts.sample_type == AFG_SAMPLE_F64): every plane the items point into holds doubles, widened on the device
-    const size_t es = f64 ? sizeof(double) : sizeof(float);
+    // so (afg_batch_opts.sample_type, dither, dither_seed): every plane the items point into holds doubles or packed integer
+    // samples, made on the device
+    const bool f64 = so.f64(), wide = so.wide();
+    const size_t es = so.es();
     {
         if (int rc = afg::require_device()) return rc;
         int cur_dev = 0;
@@ -2283,7 +2324,7 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
             // an empty sequence goes in front of it after an odd number of mono files, and in front of a chunk (a launch, below)
             // that would start on an odd one.  Without it such a file is walked one channel at a time -- slower, and in
             // AFG_NUMERIC_TOLERANCE to samples that depend on what else is in the batch (tools/soak_damaged.py found one).
-            const size_t target = std::max<size_t>((coefs_total + 7) / 8, (size_t)4 << 20);      // coefficients per chunk
+            const size_t target = std::max<size_t>((coefs_total + 7) / 8, (size_t)stage_chunk_samples((size_t)4 << 20));      // coefficients per chunk
             std::vector<uint8_t> seq_pad((size_t)n_files, 0);
             for (size_t f0 = 0; f0 < (size_t)n_files;) {
                 size_t f1 = f0, acc = 0;
@@ -2305,9 +2346,13 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
                 StagingPool::Lease h_in;
                 DeviceBuf d_in, d_pcm, d_pcm64;
                 std::vector<std::unique_ptr<F64Plane>> widen;     // one per chunk; the streams are drained before the stage returns
+                std::vector<std::unique_ptr<PackPlane>> packs;
+                std::vector<PackRun> runs;                        // (ascending: the files lie in the plane in order)
+                for (size_t i = 0; i < (size_t)n_files && so.dither; i++)
+                    if (opus_open[i]) runs.push_back(PackRun{ opus_pcm_at[i], parsed[i].opus.bound_coeffs, 0 });
                 if (int rc = g_staging.take(base_bytes + rec_bytes + coefs_total * sizeof(float), h_in)) return rc;
                 if (int rc = g_staging.take(std::max<size_t>(coefs_total, 1) * es, owner->opus_plane)) return rc;
-                if (f64) if (int rc = d_pcm64.alloc(std::max<size_t>(coefs_total, 2) * sizeof(double))) return rc;
+                if (wide) if (int rc = d_pcm64.alloc(std::max<size_t>(coefs_total * es, 16))) return rc;
                 if (int rc = d_in.alloc(base_bytes + rec_bytes + coefs_total * sizeof(float))) return rc;
                 if (int rc = d_pcm.alloc(std::max<size_t>(coefs_total, 1) * sizeof(float))) return rc;
                 uint64_t *hb = (uint64_t *)h_in.p;
@@ -2397,6 +2442,10 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
                             widen.emplace_back(new F64Plane);
                             rc = widen.back()->launch(AFG_WAV_KIND_F32, (const float *)d_pcm.p + c0, c1 - c0, (double *)d_pcm64.p + c0, up);
                             if (rc) break;
+                        } else if (so.pcm()) {
+                            packs.emplace_back(new PackPlane);
+                            rc = packs.back()->launch(so, (const float *)d_pcm.p, (uint8_t *)d_pcm64.p, 0, c0, c1 - c0, runs, up);
+                            if (rc) break;
                         }
                         hipEvent_t done = nullptr;
                         e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
@@ -2405,7 +2454,7 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
                         e = hipEventRecord(done, up);
                         if (e == hipSuccess) e = hipStreamWaitEvent(down, done, 0);
                         if (e == hipSuccess)
-                            e = hipMemcpyAsync((uint8_t *)owner->opus_plane.p + c0 * es, (const uint8_t *)(f64 ? d_pcm64.p : d_pcm.p) + c0 * es, (c1 - c0) * es, hipMemcpyDeviceToHost, down);
+                            e = hipMemcpyAsync((uint8_t *)owner->opus_plane.p + c0 * es, (const uint8_t *)(wide ? d_pcm64.p : d_pcm.p) + c0 * es, (c1 - c0) * es, hipMemcpyDeviceToHost, down);
                     }
                     f0 = f1;
                 }
@@ -2444,7 +2493,7 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
                     // HIP's current device is per host thread and starts at 0: this thread works for the caller's device
                     if (hipSetDevice(cur_dev) != hipSuccess) { afg::set_error("hipSetDevice(%d) failed", cur_dev); early_job.rc = AFG_ERR_HIP; return; }
                     early_job.rc = decode_parsed(parsed, data, length, 1 /* no helpers: they are parsing */, *eo, nullptr, nullptr, fs,
-                                                 own_early.data(), nullptr, nullptr, nullptr, f64);
+                                                 own_early.data(), nullptr, nullptr, nullptr, so);
                 } catch (...) {
                     afg::set_error("out of host memory");
                     early_job.rc = AFG_ERR_OOM;
@@ -2480,7 +2529,7 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
             }
             stage.flags = flags0; stage.blocks = total_bound; stage.base = base.data();
             stage.plane = (float *)owner->mp3_plane.p;
-            stage.f64 = f64;
+            stage.so = so;
             if (int rc = pipe.open(stage)) return rc;
             tm.lap("mp3 pipeline set-up (device planes, streams, table arena)");
             // pass 2, chunk by chunk: all host threads parse a chunk of files, its device work is queued, and they go on
@@ -2584,7 +2633,7 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
         if (parse_done) (*parse_done)();
         int rc = decode_parsed(parsed, data, length, nt, *owner, stage.blocks ? &stage : nullptr, ogg_stage.floats ? &ogg_stage : nullptr,
                                split ? nullptr : (flac_stage.words ? &flac_stage : nullptr), split ? own_late.data() : nullptr, nullptr, nullptr,
-                               opus_staged ? opus_pcm_at.data() : nullptr, f64);
+                               opus_staged ? opus_pcm_at.data() : nullptr, so);
         tm.lap("decode_parsed total");
         if (split) {
             early_job.th.join();
@@ -2611,14 +2660,14 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
             if (items[i].status == AFG_ERR_UNSUPPORTED && items[i].message == kErrorUnknownFormat) unknown.push_back(i);
         // WAV comes well before either (stream.d:1638); no probe between it and them takes a file its scan accepts (QOA and
         // Ogg have their own magic, looks_like_mp3 declines RIFF), so its stage can run here, on the files nothing took
-        if (int wrc = afg_wav::batch_stage(data, length, unknown, (int)nt, items, owner->wav_plane, f64)) return wrc;
+        if (int wrc = afg_wav::batch_stage(data, length, unknown, (int)nt, items, owner->wav_plane, so)) return wrc;
         tm.lap("wav stage");
         unknown.erase(std::remove_if(unknown.begin(), unknown.end(), [&](int i) { return items[i].status == AFG_OK || items[i].message != kErrorUnknownFormat; }), unknown.end());
         // ... and XM directly before it (stream.d:1751)
-        if (int xrc = afg_xm::batch_stage(data, length, unknown, (int)nt, items, owner->xm_plane, f64)) return xrc;
+        if (int xrc = afg_xm::batch_stage(data, length, unknown, (int)nt, items, owner->xm_plane, so)) return xrc;
         tm.lap("xm stage");
         unknown.erase(std::remove_if(unknown.begin(), unknown.end(), [&](int i) { return items[i].status == AFG_OK || items[i].message != kErrorUnknownFormat; }), unknown.end());
-        if (int mrc = afg_mod::batch_stage(data, length, unknown, (int)nt, items, owner->mod_plane, f64)) return mrc;
+        if (int mrc = afg_mod::batch_stage(data, length, unknown, (int)nt, items, owner->mod_plane, so)) return mrc;
         tm.lap("mod stage");
         keep = std::move(guard);
         tm.lap("items filled");
@@ -2675,11 +2724,26 @@ int afg_batch_decode_ex(const uint8_t *const *data, const size_t *length, int n_
         if (opts && opts->struct_size < offsetof(afg_batch_opts, sample_type)) { afg::set_error("afg_batch_opts.struct_size too small"); return AFG_ERR_INVALID; }
         uint32_t sample_type = AFG_SAMPLE_F32;
         if (opts && opts->struct_size >= offsetof(afg_batch_opts, sample_type) + sizeof(uint32_t)) sample_type = opts->sample_type;
-        if (sample_type != AFG_SAMPLE_F32 && sample_type != AFG_SAMPLE_F64) {
-            afg::set_error("afg_batch_opts.sample_type %u: AFG_SAMPLE_F32 (0) or AFG_SAMPLE_F64 (1)", sample_type);
+        if (sample_type > AFG_SAMPLE_PCM_S24) {
+            afg::set_error("afg_batch_opts.sample_type %u: AFG_SAMPLE_F32 (0), AFG_SAMPLE_F64 (1) or AFG_SAMPLE_PCM_S8 / _S16 / _S24 (2 - 4)", sample_type);
             return AFG_ERR_INVALID;
         }
-        const bool f64 = sample_type == AFG_SAMPLE_F64;
+        // (dither and dither_seed were appended together: a struct that ends before dither_seed means no dither)
+        int dither = AFG_DITHER_OFF;
+        uint32_t dither_seed = 0;
+        if (opts && opts->struct_size >= offsetof(afg_batch_opts, dither_seed) + sizeof(uint32_t)) { dither = opts->dither; dither_seed = opts->dither_seed; }
+        if (dither == AFG_DITHER_LIBC) {
+            afg::set_error("afg_batch_opts.dither: libc rand() dither has no defined draw order across files; use AFG_DITHER_LCG31 or AFG_DITHER_OFF");
+            return AFG_ERR_INVALID;
+        }
+        if (dither != AFG_DITHER_OFF && dither != AFG_DITHER_LCG31) {
+            afg::set_error("afg_batch_opts.dither %d: AFG_DITHER_OFF (0) or AFG_DITHER_LCG31 (2)", dither);
+            return AFG_ERR_INVALID;
+        }
+        SampleOut so;
+        so.type = sample_type;
+        so.dither = so.pcm() && dither == AFG_DITHER_LCG31;       // (the float types never dither)
+        so.seed = so.dither ? dither_seed : 0;
         if (n_files == 0) return AFG_OK;
         // ---- which devices ----
         std::vector<int> devs;
@@ -2737,7 +2801,7 @@ int afg_batch_decode_ex(const uint8_t *const *data, const size_t *length, int n_
             int rc = AFG_OK;
             if (groups <= 1) {
                 owner->parts.emplace_back();
-                rc = batch_decode_device(data, length, n_files, n_threads, items, owner->parts.back(), nullptr, f64);
+                rc = batch_decode_device(data, length, n_files, n_threads, items, owner->parts.back(), nullptr, so);
             } else {
                 const size_t G = (size_t)groups;
                 owner->parts.resize(G);
@@ -2767,7 +2831,7 @@ int afg_batch_decode_ex(const uint8_t *const *data, const size_t *length, int n_
                             std::unique_lock<std::mutex> lk(token);
                             bool released = false;
                             const std::function<void()> done = [&] { if (!released) { released = true; lk.unlock(); } };
-                            const int r = batch_decode_device(data + f0, length + f0, f1 - f0, n_threads, items + f0, owner->parts[g], &done, f64);
+                            const int r = batch_decode_device(data + f0, length + f0, f1 - f0, n_threads, items + f0, owner->parts[g], &done, so);
                             done();
                             if (r) { jobs[w].rc = r; jobs[w].error = afg_last_error(); failed = true; }
                         }
@@ -2824,7 +2888,7 @@ int afg_batch_decode_ex(const uint8_t *const *data, const size_t *length, int n_
                     if (mine[k].empty()) return;
                     if (hipSetDevice(devs[k]) != hipSuccess) { p.rc = AFG_ERR_HIP; p.error = "hipSetDevice failed"; return; }
                     tl_helpers = &g_device_helpers[k];
-                    p.rc = batch_decode_device(p.data.data(), p.len.data(), (int)mine[k].size(), per_dev_threads, p.items.data(), owner->parts[k], nullptr, f64);
+                    p.rc = batch_decode_device(p.data.data(), p.len.data(), (int)mine[k].size(), per_dev_threads, p.items.data(), owner->parts[k], nullptr, so);
                     tl_helpers = nullptr;
                     if (p.rc) p.error = afg_last_error();
                 } catch (...) {

@@ -114,7 +114,7 @@ private:
 // (n_threads as afg_front::parallel_run takes it), mixed on the current device in chunks with upload, mix and download overlapped,
 // and their items filled in (2-channel float PCM in page-locked memory that `keep` owns).  Other files are left alone.
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, bool f64 = false);   // f64: items point at doubles (afg_batch_opts.sample_type)
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, afg_front::SampleOut so = afg_front::SampleOut());   // f64: items point at doubles (afg_batch_opts.sample_type)
 
 // What the stage reports on a song cut at AFG_MOD_MAX_FRAMES (status AFG_OK)
 extern const char *const kMessageCapped;

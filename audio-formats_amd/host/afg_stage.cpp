@@ -79,6 +79,64 @@ int F64Slots::launch(int slot, uint32_t kind, const void *d_in, uint64_t count, 
     return conv.back()->launch(kind, d_in, count, (double *)wide[slot].p, st);
 }
 
+uint64_t stage_chunk_samples(uint64_t dflt)
+{
+    const long v = afg::dev_option(afg::kDevStageChunkSamples);
+    return v > 0 ? (uint64_t)v : dflt;
+}
+
+void sort_runs(std::vector<PackRun> &runs)
+{
+    std::sort(runs.begin(), runs.end(), [](const PackRun &x, const PackRun &y) { return x.at < y.at; });
+}
+
+int PackPlane::launch(const SampleOut &out, const float *d_in, uint8_t *d_out, uint64_t origin, uint64_t c0, uint64_t n,
+                      const std::vector<PackRun> &runs, hipStream_t st)
+{
+    if (n == 0) return AFG_OK;
+    const uint64_t B = out.es(), c1 = c0 + n;
+    recs.clear();                                            // the upload's source lives as long as the object
+    auto add = [&](uint64_t at, uint64_t count, uint64_t sample0) {
+        afg_pcm_pack_span sp;
+        std::memset(&sp, 0, sizeof(sp));
+        sp.in_off = at - origin;
+        sp.out_off = (at - origin) * B;
+        sp.count = count;
+        sp.draw0 = 2 * sample0;
+        sp.seed = out.seed;
+        sp.format = out.wav_format();
+        sp.dither = out.dither ? 1 : 0;
+        recs.push_back(sp);
+    };
+    if (!out.dither) {
+        add(c0, n, 0);
+    } else {
+        // the first run that ends behind c0, then every run that starts before c1
+        auto it = std::upper_bound(runs.begin(), runs.end(), c0, [](uint64_t v, const PackRun &r) { return v < r.at + r.count; });
+        for (; it != runs.end() && it->at < c1; ++it) {
+            const uint64_t a = std::max(it->at, c0), b = std::min(it->at + it->count, c1);
+            if (a < b) add(a, b - a, it->sample0 + (a - it->at));
+        }
+        if (recs.empty()) return AFG_OK;
+    }
+    const uint64_t tiles = afg_pcm_pack_layout(recs.data(), recs.size());
+    if (int rc = spans.alloc(recs.size() * sizeof(afg_pcm_pack_span))) return rc;
+    AFG_HIP_CHECK(hipMemcpyAsync(spans.p, recs.data(), recs.size() * sizeof(afg_pcm_pack_span), hipMemcpyHostToDevice, st));
+    return afg_pcm_pack_hip(recs.size(), (const afg_pcm_pack_span *)spans.p, tiles, d_in, c1 - origin, d_out, (c1 - origin) * B, st);
+}
+
+int PackSlots::alloc(size_t samples, size_t es)
+{
+    for (DevBuf &b : bytes) if (int rc = b.alloc(std::max<size_t>(samples * es, 16))) return rc;
+    return AFG_OK;
+}
+
+int PackSlots::launch(int slot, const SampleOut &out, const void *d_in, uint64_t origin, uint64_t n, const std::vector<PackRun> &runs, hipStream_t st)
+{
+    conv.emplace_back(new PackPlane);
+    return conv.back()->launch(out, (const float *)d_in, (uint8_t *)bytes[slot].p, origin, origin, n, runs, st);
+}
+
 int PlaneFetch::run(const void *d_plane, uint32_t kind, uint64_t count, void *out, bool f64, hipStream_t st)
 {
     const size_t bytes = (size_t)count * (f64 ? sizeof(double) : (size_t)f64_kind_bytes(kind));
@@ -145,7 +203,7 @@ SongChunks::SongChunks(const std::vector<uint64_t> &start, const std::vector<uin
 {
     const size_t M = start.size();
     for (size_t j = 0; j + 1 < M; j++)
-        if (end[j] - start[first.back()] >= kSongChunkFrames) first.push_back(j + 1);
+        if (end[j] - start[first.back()] >= (stage_chunk_samples(2 * kSongChunkFrames) + 1) / 2) first.push_back(j + 1);
     first.push_back(M);
     for (size_t c = 0; c < count(); c++) {
         frames.push_back(end[first[c + 1] - 1] - start[first[c]]);

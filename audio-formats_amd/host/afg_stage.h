@@ -87,7 +87,50 @@ struct F64Slots {
     int launch(int slot, uint32_t kind, const void *d_in, uint64_t count, hipStream_t st);
 };
 
+// ---- packed integer PCM output (afg_batch_opts.sample_type AFG_SAMPLE_PCM_*, afg_batch_transcode) ----
+// What a batch stage delivers per sample.  A bool converts to it (true: doubles), which is all a stream's reads ask for.
+struct SampleOut {
+    uint32_t type = AFG_SAMPLE_F32;
+    bool dither = false;                                         // AFG_DITHER_LCG31, the integer types only
+    uint32_t seed = 0;
+    SampleOut() = default;
+    SampleOut(bool f64) : type(f64 ? AFG_SAMPLE_F64 : AFG_SAMPLE_F32) {}
+    bool f64() const { return type == AFG_SAMPLE_F64; }
+    bool pcm() const { return type >= AFG_SAMPLE_PCM_S8; }
+    bool wide() const { return type != AFG_SAMPLE_F32; }         // a conversion launch follows the stage's kernels
+    size_t es() const { return type == AFG_SAMPLE_F64 ? 8 : type == AFG_SAMPLE_F32 ? 4 : type - AFG_SAMPLE_PCM_S8 + 1; }   // bytes per sample
+    uint8_t wav_format() const { return (uint8_t)(type - AFG_SAMPLE_PCM_S8 + AFG_WAV_S8); }
+    bool operator!=(const SampleOut &o) const { return type != o.type || dither != o.dither || seed != o.seed; }
+};
+// A run of one file's samples inside a stage's float plane: floats [at, at + count) are samples sample0 ... of the file.
+// A stage lists its runs (sorted by `at`) from the offsets it knows; they matter with dither only, where a sample's
+// draws follow from its index in the file.  Floats outside every run are never delivered.
+struct PackRun { uint64_t at, count, sample0; };
+void sort_runs(std::vector<PackRun> &runs);
+// One launch of afg_pcm_pack_hip (csrc/pcm_pack.hip): floats [c0, c0 + n) of a stage's plane to the bytes at the same
+// sample index of a byte plane that mirrors it (the sample at float i lives at byte i * es).  d_in[0] is float `origin` of
+// the plane and d_out[0] its byte.  Without dither that is one span; with it one span per run-and-chunk intersection,
+// draw0 taken from the run, and nothing for floats outside the runs.  The object holds the records its upload reads and lives until the
+// launch has run: the rule F64Plane follows.
+struct PackPlane {
+    std::vector<afg_pcm_pack_span> recs;
+    DevBuf spans;
+    int launch(const SampleOut &out, const float *d_in, uint8_t *d_out, uint64_t origin, uint64_t c0, uint64_t n,
+               const std::vector<PackRun> &runs, hipStream_t st);
+};
+// The packed side of a batch stage's two output slots, beside F64Slots.
+struct PackSlots {
+    DevBuf bytes[2];
+    std::vector<std::unique_ptr<PackPlane>> conv;
+    int alloc(size_t samples, size_t es);
+    int launch(int slot, const SampleOut &out, const void *d_in, uint64_t origin, uint64_t n, const std::vector<PackRun> &runs, hipStream_t st);
+};
+
 // ---- the chunk pipeline of a batch stage ----
+// How much a stage puts into a chunk at least, or at most: `dflt`, unless afg_dev_option("stage_chunk_samples", n) says n.
+// The stages' own figures are millions of samples; tests set a few thousand, so that small files span several chunks.
+uint64_t stage_chunk_samples(uint64_t dflt);
+
 // Chunks 0 .. n_chunks - 1 go through two slots in turn (chunk c uses slot c & 1) on the kept stream pair: uploads and
 // kernels on `up`, downloads on `down`, so that chunk c + 1 is worked on while chunk c comes back.  The caller keeps the
 // slots' device buffers and stagings; run_chunks owns the pair, the events and the order:
@@ -104,7 +147,7 @@ int run_chunks(size_t n_chunks, const std::function<int(hipStream_t up)> &before
 
 // The chunks of the MOD and XM stages: song j fills output frames [start[j], end[j]) of the batch's PCM plane, and a chunk
 // is closed behind the song that brings it to kSongChunkFrames.  Chunk c is songs [first[c], first[c + 1]).
-constexpr uint64_t kSongChunkFrames = (uint64_t)16 << 20;          // 128 MB of PCM
+constexpr uint64_t kSongChunkFrames = (uint64_t)16 << 20;          // 128 MB of PCM (afg_dev_option("stage_chunk_samples") / 2 in tests)
 struct SongChunks {
     std::vector<size_t> first;
     std::vector<uint64_t> frames;                                   // per chunk: from its first song's start to its last song's end

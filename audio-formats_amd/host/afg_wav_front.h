@@ -62,7 +62,7 @@ private:
 // or whose format readSamples refuses, becomes an error item with the reference's decoding-error message.  Files that do
 // not pass the scan are left alone.
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, bool f64 = false);   // f64: afg_pcm_to_f64_hip, items point at doubles
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, afg_front::SampleOut so = afg_front::SampleOut());   // f64: afg_pcm_to_f64_hip, items point at doubles
 
 extern const char *const kMessageDecodingError;             // internals.d: kErrorDecodingError
 

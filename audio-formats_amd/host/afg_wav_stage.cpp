@@ -99,10 +99,14 @@ int StreamConv::read(const uint8_t *file, size_t size, void *out, int frames, bo
 }
 
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, bool f64)
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, afg_front::SampleOut so)
 {
     if (which.empty()) return AFG_OK;
-    const size_t es = f64 ? sizeof(double) : sizeof(float);       // bytes per sample of the PCM plane (span offsets count samples)
+    const bool f64 = so.f64();
+    const size_t es = so.es();                                    // bytes per sample of the PCM plane (span offsets count samples)
+    // (tests make small files span several chunks: afg_dev_option("stage_chunk_samples"))
+    const uint64_t chunk_cap = (afg_front::stage_chunk_samples(kBatchChunkSamples) + AFG_WAV_TILE_SAMPLES - 1) & ~(uint64_t)(AFG_WAV_TILE_SAMPLES - 1);
+    std::vector<afg_front::PackRun> runs;                         // AFG_SAMPLE_PCM_* with dither: a file is one run of its own samples
     // ---- the scan, one file per helper-thread job ----
     struct File { bool ok = false; Info info; int kind = -1; uint64_t out_off = 0; };
     std::vector<File> files(which.size());
@@ -149,9 +153,10 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
         any = true;
         plane_floats = (plane_floats + 3) & ~(uint64_t)3;
         f.out_off = plane_floats;
+        if (so.dither) runs.push_back(afg_front::PackRun{ f.out_off, count, 0 });
         for (uint64_t done = 0; done < count;) {
-            if (kBatchChunkSamples - chunk_samples < AFG_WAV_TILE_SAMPLES) close_chunk();
-            const uint64_t room = (kBatchChunkSamples - chunk_samples) & ~(uint64_t)(AFG_WAV_TILE_SAMPLES - 1);
+            if (chunk_cap - chunk_samples < AFG_WAV_TILE_SAMPLES) close_chunk();
+            const uint64_t room = (chunk_cap - chunk_samples) & ~(uint64_t)(AFG_WAV_TILE_SAMPLES - 1);
             const uint64_t take = std::min(count - done, room);
             if (first.back() == pieces.size()) chunk_out0.back() = f.out_off + done;
             afg_wav_span sp;
@@ -187,8 +192,10 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
     if (int rc = d_spans.alloc(std::max<size_t>(spans.size(), 1) * sizeof(afg_wav_span))) return rc;
     for (int b = 0; b < (C > 1 ? 2 : 1); b++) {
         if (int rc = d_in[b].alloc((size_t)max_in)) return rc;
-        if (int rc = d_out[b].alloc((size_t)max_out * es)) return rc;
+        if (int rc = d_out[b].alloc((size_t)max_out * (so.pcm() ? sizeof(float) : es))) return rc;
     }
+    afg_front::PackSlots packed;                         // AFG_SAMPLE_PCM_*: the converted floats stay on the device and are packed there
+    if (so.pcm()) if (int rc = packed.alloc((size_t)max_out, es)) return rc;
     // what chunk c takes up and brings back: both end with its last piece
     auto in_bytes = [&](size_t c) {
         const size_t p = first[c + 1] - 1;
@@ -217,11 +224,14 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
             if (f64)
                 return afg_pcm_to_f64_hip(first[c + 1] - first[c], (const afg_wav_span *)d_spans.p + first[c], tiles[c], (const uint8_t *)d_in[b].p,
                                           in_bytes(c), (double *)d_out[b].p, (out_floats(c) + 3) & ~(uint64_t)3, up);
-            return afg_wav_convert_hip(first[c + 1] - first[c], (const afg_wav_span *)d_spans.p + first[c], tiles[c], (const uint8_t *)d_in[b].p,
-                                       in_bytes(c), (float *)d_out[b].p, (out_floats(c) + 3) & ~(uint64_t)3, up);
+            if (int rc = afg_wav_convert_hip(first[c + 1] - first[c], (const afg_wav_span *)d_spans.p + first[c], tiles[c], (const uint8_t *)d_in[b].p,
+                                             in_bytes(c), (float *)d_out[b].p, (out_floats(c) + 3) & ~(uint64_t)3, up))
+                return rc;
+            // (without dither the alignment gaps between files are packed too: their floats are whatever the buffer held)
+            return so.pcm() ? packed.launch(b, so, d_out[b].p, chunk_out0[c], out_floats(c), runs, up) : AFG_OK;
         },
         [&](size_t c, int b, hipStream_t down) -> int {
-            AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)pcm + chunk_out0[c] * es, d_out[b].p, (size_t)out_floats(c) * es, hipMemcpyDeviceToHost, down));
+            AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)pcm + chunk_out0[c] * es, so.pcm() ? packed.bytes[b].p : d_out[b].p, (size_t)out_floats(c) * es, hipMemcpyDeviceToHost, down));
             return AFG_OK;
         });
     if (rc) return rc;

@@ -188,6 +188,6 @@ private:
 // The batch path's XM stage, shaped like afg_mod::batch_stage: the files of `which` that pass the probe are simulated on
 // the helper threads, mixed in chunks with mix and download overlapped, and their items filled in.
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, bool f64 = false);   // f64: items point at doubles (afg_batch_opts.sample_type)
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, afg_front::SampleOut so = afg_front::SampleOut());   // f64: items point at doubles (afg_batch_opts.sample_type)
 
 }  // namespace afg_xm

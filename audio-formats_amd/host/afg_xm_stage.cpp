@@ -72,9 +72,10 @@ int StreamMix::read(void *out, int frames, bool f64)
 }
 
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
-                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, bool f64)
+                int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, afg_front::SampleOut so)
 {
-    const size_t es = f64 ? sizeof(double) : sizeof(float);       // bytes per sample of the PCM plane the items point into
+    const bool f64 = so.f64();
+    const size_t es = so.es();                                    // bytes per sample of the PCM plane the items point into
     if (which.empty()) return AFG_OK;
     struct Sim {
         bool ok = false, capped = false, refused = false;
@@ -154,6 +155,12 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
     for (DevBuf &b : d_out) if (int rc = b.alloc(chunks.max_frames * 2 * sizeof(float))) return rc;
     afg_front::F64Slots wide;                              // f64: the mixed floats stay on the device and are widened there
     if (f64) if (int rc = wide.alloc(chunks.max_frames * 2)) return rc;
+    afg_front::PackSlots packed;                           // AFG_SAMPLE_PCM_*: ... or packed there; a song is one run of its own samples
+    std::vector<afg_front::PackRun> runs;
+    if (so.pcm()) {
+        if (int rc = packed.alloc(chunks.max_frames * 2, es)) return rc;
+        for (size_t j = 0; j < M && so.dither; j++) runs.push_back(afg_front::PackRun{ 2 * start[j], 2 * sims[mods[j]].frames, 0 });
+    }
     const uint8_t *din = (const uint8_t *)d_in.p;
     const int rc = afg_front::run_chunks(
         chunks.count(),
@@ -169,11 +176,12 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
                                            (const afg_xm_segment *)(din + L.segs), (const afg_xm_tick *)(din + L.ticks) + songs[first[c]].tick_base,
                                            din + L.data, (const float *)(din + L.aux), (float *)d_out[slot].p, up))
                 return rc;
+            if (so.pcm()) return packed.launch(slot, so, d_out[slot].p, 2 * start[first[c]], chunks.frames[c] * 2, runs, up);
             return f64 ? wide.launch(slot, AFG_WAV_KIND_F32, d_out[slot].p, chunks.frames[c] * 2, up) : AFG_OK;
         },
         [&](size_t c, int slot, hipStream_t down) -> int {
             if (chunks.frames[c])
-                AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)pcm + 2 * start[first[c]] * es, f64 ? wide.wide[slot].p : d_out[slot].p, chunks.frames[c] * 2 * es,
+                AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)pcm + 2 * start[first[c]] * es, so.pcm() ? packed.bytes[slot].p : f64 ? wide.wide[slot].p : d_out[slot].p, chunks.frames[c] * 2 * es,
                                              hipMemcpyDeviceToHost, down));
             return AFG_OK;
         });

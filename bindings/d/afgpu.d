@@ -299,7 +299,11 @@ int afg_batch_decode(const(ubyte*)* data, const(size_t)* length, int n_files, in
 
 // ---- round 2: device selection, multi-device batches, MP3 quantised upload, CELT on two streams, dithered WAV ----
 enum uint AFG_SAMPLE_F32 = 0, AFG_SAMPLE_F64 = 1;   // AFG_SAMPLE_F64: an item's pcm points at frames * channels doubles (readSamplesDouble's)
-struct afg_batch_opts { uint struct_size; int n_threads; int n_devices; const(int)* devices; uint sample_type; }
+// AFG_SAMPLE_PCM_*: an item's pcm points at frames * channels samples of 1, 2 or 3 bytes, the body of the WAV file that
+// readSamplesFloat + writeSamplesFloat would write, packed on the device (afg_pcm_pack_hip); dither: AFG_DITHER_OFF or
+// AFG_DITHER_LCG31 (every file from draw 0 of dither_seed), AFG_DITHER_LIBC is refused
+enum uint AFG_SAMPLE_PCM_S8 = 2, AFG_SAMPLE_PCM_S16 = 3, AFG_SAMPLE_PCM_S24 = 4;
+struct afg_batch_opts { uint struct_size; int n_threads; int n_devices; const(int)* devices; uint sample_type; int dither; uint dither_seed; }
 int afg_set_device(int device);
 int afg_get_device();
 int afg_batch_decode_ex(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_batch_opts)* opts, afg_batch_result* result);
@@ -428,6 +432,14 @@ struct afg_encode_result { int n_files; afg_encoded_item* items; void* owner; }
 int afg_batch_encode(const(afg_encode_input)* inputs, int n_files, int format, const(afg_encoding_options)* opts, int n_threads,
                      afg_encode_result* result);
 void afg_encode_free(afg_encode_result* result);
+// the packer of the decode stages: afg_wav_pack_hip's integer formats for spans at any float / any byte; inputs are clamped to [-1, 1], NaN -> 0
+struct afg_pcm_pack_span { ulong in_off, out_off, count, first_tile, draw0; uint seed; ubyte format, dither; ubyte[2] pad; }
+ulong afg_pcm_pack_layout(afg_pcm_pack_span* spans, ulong n_spans);
+int afg_pcm_pack_hip(ulong n_spans, const(afg_pcm_pack_span)* d_spans, ulong n_tiles, const(float)* d_in, ulong in_floats,
+                     ubyte* d_out, ulong out_bytes, void* hip_stream);
+// the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
+int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
+                        const(afg_batch_opts)* opts, afg_encode_result* result);
 
 /// Drop-in for the decoding use of `AudioStream` (stream.d:102): same member names and error-state contract
 /// (never throws, `isError` + `errorMessage`), backed by the device library.  Not thread-safe per instance,

@@ -76,7 +76,9 @@ int         afg_set_numeric_mode(int mode);
  * "mp3_chunks", "mp3_float_upload" (1: float spectra instead of quantised values cross the bus), "vorbis_host_floor"
  * (1: floor curves on the host), "flac_host_res32" (1: int32 residual rows only), "vorbis_seg_packets" (packets per walk
  * item of plans created with seg_packets = 0, instead of the library's choice), "batch_groups" (groups of files a batch call
- * pipelines: 1 = none; default 4 for batches of FLAC / Ogg Vorbis files from 512 files up, else 1).  AFG_ERR_INVALID: no such name. */
+ * pipelines: 1 = none; default 4 for batches of FLAC / Ogg Vorbis files from 512 files up, else 1), "stage_chunk_samples" (samples per chunk of
+ * the FLAC, Vorbis, Opus, WAV, MOD and XM batch stages in place of their own millions, so that small files span several
+ * chunks).  AFG_ERR_INVALID: no such name. */
 int         afg_dev_option(const char *name, int value);
 int         afg_get_numeric_mode(void);
 int         afg_device_name(int device, char *buf, size_t buflen);
@@ -548,7 +550,8 @@ typedef struct afg_batch_item {
     float       samplerate;
     int64_t     frames;
     float      *pcm;           /* frames * channels floats, NULL on error; with afg_batch_opts.sample_type ==
-                                  AFG_SAMPLE_F64 it points at frames * channels doubles (cast it) */
+                                  AFG_SAMPLE_F64 it points at frames * channels doubles, with AFG_SAMPLE_PCM_* at as many
+                                  samples of 1, 2 or 3 bytes (cast it) */
 } afg_batch_item;
 
 typedef struct afg_batch_result {
@@ -576,14 +579,29 @@ void afg_batch_free(afg_batch_result *result);
  *                    are the doubles of afg_read_samples_double (stream.d:656-747), made on the device in every stage
  *                    between the codec's kernels and the download -- WAV from the file's bytes, FLAC from the int32
  *                    plane, every other format from its float plane.  Any other value: AFG_ERR_INVALID, before any work. */
+/*                    AFG_SAMPLE_PCM_S8 / _S16 / _S24: the items' pcm are the sample bytes WAVEncoder.writeSamples
+ *                    (wav.d:482-527) makes of those floats in AFG_WAV_S8 / _S16LE / _S24LE -- the body of the WAV file
+ *                    that `transcode` (readSamplesFloat, then writeSamplesFloat) writes -- made on the device
+ *                    (afg_pcm_pack_hip) between the codec's kernels and the download, so that 1, 2 or 3 bytes per sample
+ *                    cross the bus.  The float is the one AFG_SAMPLE_F32 delivers for that sample, for FLAC too; WAV input
+ *                    is converted to float first.  Floats outside [-1, 1] are clamped and NaN becomes 0 (afg_pcm_pack_hip).
+ *   dither           AFG_SAMPLE_PCM_* only.  AFG_DITHER_OFF, or AFG_DITHER_LCG31: TPDFDither.process (wav.d:679-700) with
+ *                    the 31-bit generator, every file starting at draw 0 of dither_seed, so that a file's bytes depend on
+ *                    nothing but the file: not on its neighbours, the stages' chunks or the devices.  AFG_DITHER_LIBC:
+ *                    AFG_ERR_INVALID for the whole call, before any work -- rand() has no draw order across files. */
 #define AFG_SAMPLE_F32 0
 #define AFG_SAMPLE_F64 1
+#define AFG_SAMPLE_PCM_S8  2
+#define AFG_SAMPLE_PCM_S16 3
+#define AFG_SAMPLE_PCM_S24 4
 typedef struct afg_batch_opts {
     uint32_t   struct_size;    /* sizeof(afg_batch_opts) */
     int        n_threads;
     int        n_devices;
     const int *devices;
     uint32_t   sample_type;    /* AFG_SAMPLE_*; a struct_size that does not reach this field means AFG_SAMPLE_F32 */
+    int        dither;         /* AFG_DITHER_OFF / AFG_DITHER_LCG31; a struct_size that does not reach these two fields */
+    uint32_t   dither_seed;    /* means AFG_DITHER_OFF */
 } afg_batch_opts;
 
 int  afg_set_device(int device);
@@ -681,6 +699,33 @@ uint64_t afg_wav_pack_layout(afg_wav_pack_span *spans, uint64_t n_spans);
 int afg_wav_pack_hip(uint64_t n_spans, const afg_wav_pack_span *d_spans, uint64_t n_tiles, const float *d_in,
                      uint64_t in_floats, uint8_t *d_out, uint64_t out_bytes, void *hip_stream);
 
+/* The packer of the batch decode stages (afg_batch_opts.sample_type AFG_SAMPLE_PCM_*, afg_batch_transcode): the integer
+ * formats of afg_wav_pack_hip -- the bytes of WAVEncoder.writeSamples (wav.d:482-527) and TPDFDither.process
+ * (wav.d:679-700), the same generator, the same draw numbering -- for spans that start at any float of d_in and any byte
+ * of d_out: a file's samples start wherever its decode stage left them in the plane.  Tiles are AFG_WAV_TILE_SAMPLES
+ * samples, one workgroup per tile.  The interior of a tile is written as 16-byte words aligned in d_out's address space,
+ * what lies before and behind them one byte at a time; no byte outside a span is written or read back, so spans may abut
+ * inside one dword.  One difference from the host writer, which asserts |x| <= 1 (wav.d:485): decoded audio does leave
+ * the range (MP3 overshoot, float WAV), so every input is clamped to [-1, 1] first and NaN becomes 0; for inputs in range
+ * the bytes are afg_wav_encode's / afg_wav_encode_dithered's. */
+typedef struct afg_pcm_pack_span {   /* one run of samples of one file inside a decode plane (48 bytes) */
+    uint64_t in_off;     /* first float in d_in: any index */
+    uint64_t out_off;    /* first byte in d_out: any offset */
+    uint64_t count;      /* samples */
+    uint64_t first_tile; /* filled in by afg_pcm_pack_layout */
+    uint64_t draw0;      /* 2 x (samples of the file before this run) */
+    uint32_t seed;       /* the file's generator starts from this state */
+    uint8_t  format;     /* AFG_WAV_S8, AFG_WAV_S16LE, AFG_WAV_S24LE only */
+    uint8_t  dither;     /* 0 off, 1 the 31-bit generator */
+    uint8_t  pad[2];
+} afg_pcm_pack_span;
+/* Host: gives every span its tiles (first_tile) and returns the launch's tile count. */
+uint64_t afg_pcm_pack_layout(afg_pcm_pack_span *spans, uint64_t n_spans);
+/* Packs every span in one launch.  d_in is 4-byte aligned, d_out any address; the planes do not overlap.  A span that
+ * does not lie inside [0, in_floats) / [0, out_bytes), or whose format is not one of the three, is not touched at all. */
+int afg_pcm_pack_hip(uint64_t n_spans, const afg_pcm_pack_span *d_spans, uint64_t n_tiles, const float *d_in,
+                     uint64_t in_floats, uint8_t *d_out, uint64_t out_bytes, void *hip_stream);
+
 /* The writing half of AudioStream (stream.d:216-286 openToBuffer / openToMemory, :762-902 writeSamplesFloat /
  * writeSamplesDouble, :1282-1349 finalizeEncoding / finalizeAndGetEncodedResult) for WAV and QOA, on the same handle
  * type: afg_is_error, afg_error_message, afg_get_format, afg_get_num_channels, afg_get_samplerate and afg_close work
@@ -733,6 +778,22 @@ typedef struct afg_encode_result { int n_files; afg_encoded_item *items; void *o
 int  afg_batch_encode(const afg_encode_input *in, int n_files, int format, const afg_encoding_options *opts,
                       int n_threads, afg_encode_result *out);
 void afg_encode_free(afg_encode_result *r);
+
+/* Batch transcode: the reference's example program `transcode` (open, readSamplesFloat, writeSamplesFloat to a WAV,
+ * finalize: stream.d:480-570, :762-832, wav.d:365-603) for a batch of files in one call.  Every file goes through
+ * afg_batch_decode_ex with the sample type that enc->sample_format asks for -- AFG_SAMPLE_PCM_* for the integer formats,
+ * AFG_SAMPLE_F32 / AFG_SAMPLE_F64 for the float ones -- so the body of each WAV file is made on the device and crosses
+ * the bus once, at its own width; the pooled host threads then put the 44-byte header in front (one host copy per file).
+ * Item i is a complete WAV file: the bytes of afg_wav_encode[_dithered] over the floats afg_batch_decode_ex returns for
+ * file i, with its channel count and (int)(samplerate + 0.5f) (stream.d:1852); floats outside [-1, 1] are clamped and NaN
+ * becomes 0 for the integer formats (afg_pcm_pack_hip).  enc NULL: AFG_WAV_FP32LE.  enc->dither follows afg_batch_opts.dither
+ * (AFG_DITHER_LIBC with an integer format: AFG_ERR_INVALID); the float formats never dither.  opts (may be NULL) supplies
+ * threads and devices; its sample_type and dither are ignored.  A file that does not decode is an item with the decoder's
+ * status and message and no bytes.  out_format: AFG_FORMAT_WAV.  AFG_FORMAT_QOA is refused (AFG_ERR_UNSUPPORTED): the QOA
+ * encoder's LMS state runs through a whole file and the decode stages cut files at chunk borders.  Free the result with
+ * afg_encode_free. */
+int  afg_batch_transcode(const uint8_t *const *data, const size_t *length, int n_files, int out_format,
+                         const afg_encoding_options *enc, const afg_batch_opts *opts, afg_encode_result *out);
 
 /* ========================================================================== *
  *  ProTracker MOD (pocketmod.d; stream.d:1796-1830): 2 channels at 44100 Hz, length AFG_UNKNOWN_LENGTH, one numeric mode
