@@ -55,6 +55,11 @@ WAV_PACK_SPAN_DTYPE = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), (
                                 ("pad", np.uint8, (2,))])
 assert WAV_PACK_SPAN_DTYPE.itemsize == 48
 PCM_PACK_SPAN_DTYPE = WAV_PACK_SPAN_DTYPE        # afg_pcm_pack_span: the same fields; in_off and out_off are free, format <= WAV_S24LE
+# afg_collate_span: a run of interleaved samples to planar rows (channels 0: a run of zeros from out_off + sample0 on)
+COLLATE_SPAN_DTYPE = np.dtype([("in_off", np.uint64), ("count", np.uint64), ("sample0", np.uint64), ("out_off", np.uint64),
+                               ("first_frame", np.int64), ("first_tile", np.uint64), ("frames", np.uint32), ("channels", np.uint16),
+                               ("out_channels", np.uint16)])
+assert COLLATE_SPAN_DTYPE.itemsize == 56
 
 # every symbol include/afg.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -88,6 +93,7 @@ ABI_SYMBOLS = [
     "afg_write_samples_float", "afg_write_samples_double", "afg_finalize_encoding", "afg_finalize_and_get_encoded",
     "afg_batch_encode", "afg_encode_free",
     "afg_pcm_pack_layout", "afg_pcm_pack_hip", "afg_batch_transcode",
+    "afg_collate_layout", "afg_collate_hip", "afg_batch_decode_to_device",
 ]
 
 
@@ -211,6 +217,12 @@ class BatchItem(C.Structure):
 class BatchOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_threads", C.c_int), ("n_devices", C.c_int), ("devices", C.POINTER(C.c_int)),
                 ("sample_type", C.c_uint32), ("dither", C.c_int), ("dither_seed", C.c_uint32)]
+
+
+class CollateOpts(C.Structure):
+    """afg_collate_opts (afg_batch_decode_to_device)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_threads", C.c_int), ("channels", C.c_uint32), ("frames", C.c_uint32),
+                ("first_frame", C.POINTER(C.c_int64))]
 
 
 SAMPLE_F32, SAMPLE_F64, SAMPLE_PCM_S8, SAMPLE_PCM_S16, SAMPLE_PCM_S24 = range(5)     # afg_batch_opts.sample_type
@@ -432,6 +444,10 @@ def lib():
     L.afg_pcm_pack_hip.argtypes = [u64, vp, u64, vp, u64, vp, u64, vp]
     L.afg_batch_transcode.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(EncodingOptions), C.POINTER(BatchOpts),
                                       C.POINTER(EncodeResult)]
+    L.afg_collate_layout.argtypes = [vp, u64]
+    L.afg_collate_layout.restype = u64
+    L.afg_collate_hip.argtypes = [u64, vp, u64, vp, u64, vp, u64, vp]
+    L.afg_batch_decode_to_device.argtypes = [vp, vp, C.c_int, C.POINTER(CollateOpts), vp, C.POINTER(BatchResult)]
     _lib = L
     _sync_dev_options(L)
     return L
@@ -1232,6 +1248,71 @@ def batch_decode(files, n_threads=0, devices=None, dtype=np.float32, sample_type
     _S16 / _S24: pcm is the WAV body made on the device, uint8 / int16 [frames, channels] or uint8 [frames, channels, 3]."""
     with BatchDecoded(files, n_threads, devices, dtype, sample_type, dither, dither_seed) as res:
         return [dict(it, pcm=None if it["pcm"] is None else it["pcm"].copy()) for it in res.items]
+
+
+def collate_layout(spans):
+    """afg_collate_layout: fills first_tile of a COLLATE_SPAN_DTYPE array in place; returns the launch's tile count."""
+    assert spans.dtype == COLLATE_SPAN_DTYPE and spans.flags.c_contiguous
+    return int(lib().afg_collate_layout(spans.ctypes.data, len(spans)))
+
+
+def collate(n_spans, d_spans, n_tiles, d_in, in_floats, d_out, out_floats, stream=None):
+    """Enqueue the collate kernel (afg_collate_hip) on device arrays: interleaved runs to planar, padded rows.  The spans
+    are checked first (the call waits for `stream` to read them): AfgError, and nothing written, when one leaves a plane."""
+    check(lib().afg_collate_hip(int(n_spans), _ptr(d_spans), int(n_tiles), _ptr(d_in), int(in_floats), _ptr(d_out),
+                                int(out_floats), _stream(stream)))
+
+
+def batch_decode_tensor(files, frames, channels, first_frame=None, out=None, n_threads=0):
+    """afg_batch_decode_to_device: (tensor, meta).  tensor is a torch.float32 CUDA tensor [len(files), channels, frames] on
+    the current device -- element [i, k, t] is sample (first_frame[i] + t) * channels_i + k of what batch_decode delivers for
+    file i, 0 past the file's end, for a channel it does not have, and for a file that failed -- made on the device with no
+    download; `out` (optional) is written in place of a new one.  meta: batch_decode's per-file dicts without pcm.
+    The library works on HIP's current device of the calling thread, which must be torch's (afgpu.set_device keeps the two in
+    step): ValueError otherwise.  torch's current stream is synchronised before the call, for a new tensor too -- torch's
+    allocator hands a freed block out again at once and relies on stream order, which the library's own streams are not part of."""
+    import torch
+    bufs = [bytes(f) for f in files]
+    n = len(bufs)
+    frames, channels = int(frames), int(channels)
+    if frames < 1 or channels < 1:
+        raise ValueError("batch_decode_tensor: frames and channels must be at least 1")
+    shape = (n, channels, frames)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+    else:
+        if tuple(out.shape) != shape or out.dtype != torch.float32:
+            raise ValueError(f"batch_decode_tensor: out must be a float32 tensor of shape {shape}")
+        if not out.is_cuda or out.device.index != torch.cuda.current_device():
+            raise ValueError("batch_decode_tensor: out must live on the current device")
+        if not out.is_contiguous():
+            raise ValueError("batch_decode_tensor: out must be contiguous")
+    if n == 0:
+        return out, []
+    if get_device() != torch.cuda.current_device():
+        raise ValueError(f"batch_decode_tensor: HIP's current device is {get_device()}, torch's {torch.cuda.current_device()}")
+    # Whatever is queued on `out` -- or, for a new tensor, on the block the allocator has just handed out again -- is over
+    # before the library's streams, which torch's stream order does not cover, write it.
+    torch.cuda.current_stream().synchronize()
+    ff = None
+    if first_frame is not None:
+        if len(first_frame) != n:
+            raise ValueError("batch_decode_tensor: one first_frame per file")
+        ff = (C.c_int64 * n)(*[int(v) for v in first_frame])
+    ptrs = (C.c_char_p * n)(*bufs)
+    lens = (C.c_size_t * n)(*[len(b) for b in bufs])
+    opts = CollateOpts(C.sizeof(CollateOpts), int(n_threads), channels, frames, ff)
+    res = BatchResult()
+    check(lib().afg_batch_decode_to_device(ptrs, lens, n, C.byref(opts), out.data_ptr(), C.byref(res)))
+    try:
+        meta = []
+        for i in range(res.n_files):
+            it = res.items[i]
+            meta.append({"status": it.status, "message": None if it.message is None else it.message.decode(),
+                         "format": it.format, "channels": it.channels, "samplerate": it.samplerate, "frames": it.frames})
+        return out, meta
+    finally:
+        lib().afg_batch_free(C.byref(res))
 
 
 def batch_transcode(files, options=None, n_threads=0, devices=None):

@@ -63,6 +63,11 @@ int vorbis_plan_create_at(afg_vorbis_plan **plan, uint32_t n_streams, const uint
                           const uint16_t *blocksize0, const uint16_t *blocksize1, const uint8_t *pflags,
                           const uint64_t *spec_base, uint32_t seg_packets);
 
+// afg_collate_hip for a caller that still has the spans in host memory (h_spans: what d_spans was uploaded from, on
+// `stream`): the checks run on them and nothing waits for the device (collate.hip)
+int collate_launch(const afg_collate_span *h_spans, uint64_t n_spans, const afg_collate_span *d_spans, uint64_t n_tiles,
+                   const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats, hipStream_t stream);
+
 // Owns a device buffer filled from a host array at plan creation.
 struct DeviceArray {
     void *ptr = nullptr;

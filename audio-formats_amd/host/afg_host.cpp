@@ -493,6 +493,7 @@ struct Mp3Pipe {
     DeviceBuf d_in, d_pcm, d_pcm64;
     std::vector<std::unique_ptr<F64Plane>> widen;          // one per chunk, alive until close() has drained the streams
     std::vector<std::unique_ptr<PackPlane>> packs;         // likewise (AFG_SAMPLE_PCM_*)
+    std::vector<std::unique_ptr<CollatePlane>> collated;   // likewise (collate mode)
     uint32_t *d_flags = nullptr;
     hipStream_t up = nullptr, down = nullptr;
     std::vector<afg_mp3_plan *> plans;
@@ -517,7 +518,7 @@ struct Mp3Pipe {
         const size_t coef_bytes = stage.blocks * 576 * sizeof(float), flag_bytes = (stage.blocks * 4 + 15) & ~(size_t)15;
         if (int r = d_in.alloc(coef_bytes + flag_bytes)) return r;
         if (int r = d_pcm.alloc(coef_bytes)) return r;
-        if (stage.so.wide()) if (int r = d_pcm64.alloc(std::max<size_t>(stage.blocks * 576 * stage.es(), 16))) return r;
+        if (stage.so.wide() && stage.so.fetch()) if (int r = d_pcm64.alloc(std::max<size_t>(stage.blocks * 576 * stage.es(), 16))) return r;
         if (stage.q) {
             const size_t q_bytes = (stage.blocks * 576 * sizeof(int16_t) + 15) & ~(size_t)15;
             const size_t rec_bytes = stage.blocks * sizeof(afg_mp3_qgranule);
@@ -603,24 +604,30 @@ struct Mp3Pipe {
             widen.emplace_back(new F64Plane);
             rc = widen.back()->launch(AFG_WAV_KIND_F32, (const float *)d_pcm.p + b0 * 576, nb * 576, (double *)d_pcm64.p + b0 * 576, up);
             if (rc) return;
-        } else if (st->so.pcm()) {
-            // a file's samples are the pieces of its copy plan, in order (with dither a sample's draws follow its index)
+        } else if (st->so.pcm() || st->so.collate()) {
+            // a file's samples are the pieces of its copy plan, in order (with dither a sample's draws follow its index, in
+            // collate mode its place does)
             std::vector<PackRun> runs;
-            for (size_t i = f0; i < f1 && st->so.dither; i++) {
+            for (size_t i = f0; i < f1 && st->so.runs(); i++) {
                 const Parsed &p = parsed[i];
                 if (p.format != AFG_FORMAT_MP3 || !p.mp3.blocks()) continue;
                 uint64_t at = 0;
-                for (const afg_mp3::Copy &c : p.mp3.copies) { runs.push_back(PackRun{ st->base[i] * 576 + c.src, c.count, at }); at += c.count; }
+                for (const afg_mp3::Copy &c : p.mp3.copies) { runs.push_back(PackRun{ st->base[i] * 576 + c.src, c.count, at, (uint32_t)i, (uint32_t)p.mp3.channels }); at += c.count; }
             }
             sort_runs(runs);
-            packs.emplace_back(new PackPlane);
-            rc = packs.back()->launch(st->so, (const float *)d_pcm.p, (uint8_t *)d_pcm64.p, 0, b0 * 576, nb * 576, runs, up);
+            if (st->so.collate()) {
+                collated.emplace_back(new CollatePlane);
+                rc = collated.back()->launch(st->so, (const float *)d_pcm.p, 0, b0 * 576, nb * 576, runs, up);
+            } else {
+                packs.emplace_back(new PackPlane);
+                rc = packs.back()->launch(st->so, (const float *)d_pcm.p, (uint8_t *)d_pcm64.p, 0, b0 * 576, nb * 576, runs, up);
+            }
             if (rc) return;
         }
         const size_t es = st->es();
         e = hipEventRecord(done, up);
         if (e == hipSuccess) e = hipStreamWaitEvent(down, done, 0);
-        if (e == hipSuccess)
+        if (e == hipSuccess && st->so.fetch())
             e = hipMemcpyAsync((uint8_t *)st->plane + b0 * 576 * es, (const uint8_t *)(st->so.wide() ? d_pcm64.p : d_pcm.p) + b0 * 576 * es, nb * 576 * es, hipMemcpyDeviceToHost, down);
     }
     int close()
@@ -629,7 +636,7 @@ struct Mp3Pipe {
         if (down) { hipError_t e2 = hipStreamSynchronize(down); if (e == hipSuccess) e = e2; }
         for (afg_mp3_plan *p : plans) afg_mp3_plan_destroy(p);
         for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
-        plans.clear(); events.clear(); widen.clear(); packs.clear();
+        plans.clear(); events.clear(); widen.clear(); packs.clear(); collated.clear();
         g_streams.give(up, down);
         up = down = nullptr;
         if (rc) return rc;
@@ -664,8 +671,10 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
     // stream, and the doubles are what comes back.  The batch path's MP3 and Opus planes were widened by their own pipelines.
     // AFG_SAMPLE_PCM_* (afg_batch_opts.sample_type): the result plane holds samples of 1, 2 or 3 bytes, packed from every
     // stage's float plane by afg_pcm_pack_hip at the same place; FLAC restores to float as for a float read.
+    // Collate mode (afg_batch_decode_to_device): there is no result plane.  afg_collate_hip scatters every stage's float plane
+    // into the caller's tensor where the other types convert, and the downloads are left out; parsed[i] is batch file i.
     if (stage && stage->blocks && stage->so != so) { afg::set_error("decode_parsed: the MP3 stage's sample type differs"); return AFG_ERR_INVALID; }
-    const bool f64 = so.f64(), wide = so.wide();
+    const bool f64 = so.f64(), wide = so.wide(), fetch = so.fetch();
     const size_t es = so.es();
     out.f64 = f64;
     // dither: where each file's samples lie in the stages' device planes (afg_stage.h: PackRun)
@@ -689,7 +698,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
         if (!flac_staged) res_total = (res_total + 3) & ~(size_t)3;     // 16-byte aligned planes (int16 rows: afg_flac_frame.res16)
         res_base[i] = flac_staged ? flac_stage->base[i] : res_total; fr_base[i] = fr_total; sf_base[i] = sf_total;
         out.files[i].pcm_off = flac_out;
-        if (so.dither) runs_main.push_back(PackRun{ flac_out, p.flac.out_samples, 0 });
+        if (so.runs()) runs_main.push_back(PackRun{ flac_out, p.flac.out_samples, 0, (uint32_t)i, (uint32_t)p.fi.channels });
         res_total += p.flac.res_size(); fr_total += p.flac.frames.size(); sf_total += p.flac.subframes.size();
         flac_out += p.flac.out_samples;
     }
@@ -702,7 +711,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
         qbytes += (len[i] + 15) & ~(size_t)15;
         qframes += p.qoa.size();
         const size_t q_samples = p.qoa.back().out_off + (size_t)p.qoa.back().samples * p.qoa.back().channels;
-        if (so.dither) runs_main.push_back(PackRun{ flac_out + qoa_out, q_samples, 0 });
+        if (so.runs()) runs_main.push_back(PackRun{ flac_out + qoa_out, q_samples, 0, (uint32_t)i, (uint32_t)p.qi.channels });
         qoa_out += q_samples;
     }
     std::vector<size_t> mp3_blk_base(nf, 0);
@@ -711,9 +720,9 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
         Parsed &p = parsed[i];
         if (fmt_of(p) != AFG_FORMAT_MP3) continue;
         mp3_blk_base[i] = mp3_blocks;
-        if (so.dither) {
+        if (so.runs()) {
             uint64_t at = 0;
-            for (const afg_mp3::Copy &c : p.mp3.copies) { runs_mp3.push_back(PackRun{ mp3_blocks * 576 + c.src, c.count, at }); at += c.count; }
+            for (const afg_mp3::Copy &c : p.mp3.copies) { runs_mp3.push_back(PackRun{ mp3_blocks * 576 + c.src, c.count, at, (uint32_t)i, (uint32_t)p.mp3.channels }); at += c.count; }
         }
         out.files[i].pcm_off = flac_out + qoa_out + mp3_out;
         mp3_blocks += p.mp3.blocks();
@@ -825,9 +834,9 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                     ogg_pieces.push_back(OggPiece{ i, ogg_out + from, cnt });
                     q = j;
                 }
-                if (so.dither) {
+                if (so.runs()) {
                     uint64_t at = 0;
-                    for (size_t k = first_piece; k < ogg_pieces.size(); k++) { runs_ogg.push_back(PackRun{ ogg_pieces[k].from, ogg_pieces[k].count, at }); at += ogg_pieces[k].count; }
+                    for (size_t k = first_piece; k < ogg_pieces.size(); k++) { runs_ogg.push_back(PackRun{ ogg_pieces[k].from, ogg_pieces[k].count, at, (uint32_t)i, (uint32_t)p.ogg.channels }); at += ogg_pieces[k].count; }
                 }
                 out.files[i].pcm_off = flac_out + qoa_out + mp3_out + (ogg_pieces.size() > first_piece ? (size_t)ogg_pieces[first_piece].from : ogg_out);
                 if (ogg_pieces.size() - first_piece > 1) ogg_broken.push_back(i);
@@ -838,7 +847,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
             ogg_out += k.out_n;
         }
     }
-    if (staged) {
+    if (staged && fetch) {
         // delivery in place: a file whose copy plan is one piece (every undamaged file) is served where it landed;
         // the pieces of a damaged file are closed up towards its first piece (ascending, so memmove order is safe)
         std::vector<size_t> broken;                          // files whose pieces are not already back to back
@@ -873,6 +882,9 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
         }
         opus_rec_base[i] = opus_recs; opus_coef_base[i] = opus_coefs; opus_pcm_base[i] = opus_out;
         if (so.dither) runs_opus.push_back(PackRun{ opus_out, (uint64_t)p.opus.pcm_frames * (uint64_t)p.opus.channels, 0 });
+        else if (so.collate())                                   // (what is delivered: the declared length cuts it, below)
+            runs_opus.push_back(PackRun{ opus_out, (uint64_t)std::min<int64_t>((int64_t)p.opus.pcm_frames, std::max<int64_t>(p.opus.declared_frames, 0)) * (uint64_t)p.opus.channels,
+                                         0, (uint32_t)i, (uint32_t)p.opus.channels });
         out.files[i].pcm_off = flac_out + qoa_out + mp3_out + ogg_out + opus_out;
         opus_recs += p.opus.frames.size() * (size_t)p.opus.channels;
         opus_coefs += p.opus.coeffs.size();
@@ -887,20 +899,25 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
     out.plane_floats = flac_out + qoa_out + mp3_out + ogg_out + opus_out;
     if (out.plane_floats == 0) goto metadata;
     {
-        if (int rc = g_staging.take(out.plane_floats * es, out.plane)) return rc;
+        if (fetch) if (int rc = g_staging.take(out.plane_floats * es, out.plane)) return rc;
         tm.lap("layout + plane alloc");
         // (the widened planes and the conversion records are declared out here: on an early way out of a stage they are let
         //  go only after the device has drained, below them)
         DeviceBuf d_out, d_out64, d_mp3_64, d_ogg_64, d_opus_64;
         if (int rc = d_out.alloc(out.plane_floats * sizeof(float))) return rc;
-        if (wide) if (int rc = d_out64.alloc(std::max<size_t>((flac_out + qoa_out) * es, 16))) return rc;   // FLAC and QOA are converted in place of the plane
+        if (wide && fetch) if (int rc = d_out64.alloc(std::max<size_t>((flac_out + qoa_out) * es, 16))) return rc;   // FLAC and QOA are converted in place of the plane
         std::vector<std::unique_ptr<F64Plane>> widen;        // one per conversion launch, alive until the stages have drained
         std::vector<std::unique_ptr<PackPlane>> packs;
+        std::vector<std::unique_ptr<CollatePlane>> collated;
         struct Drain { bool on; ~Drain() { if (on) (void)hipDeviceSynchronize(); } } drain{ wide };
         for (std::vector<PackRun> *r : { &runs_main, &runs_mp3, &runs_ogg, &runs_opus }) sort_runs(*r);
         // samples [c0, c0 + n) of a stage's plane `src` (4-byte elements of `kind`) to the same samples of its converted
-        // plane `dst`: doubles, or packed integers
+        // plane `dst`: doubles, or packed integers; collate mode: to the tensor (dst is not used)
         auto convert = [&](uint32_t kind, const void *src, uint64_t c0, uint64_t n, void *dst, const std::vector<PackRun> &runs, hipStream_t st) -> int {
+            if (so.collate()) {
+                collated.emplace_back(new CollatePlane);
+                return collated.back()->launch(so, (const float *)src, 0, c0, n, runs, st);
+            }
             if (so.pcm()) {
                 packs.emplace_back(new PackPlane);
                 return packs.back()->launch(so, (const float *)src, (uint8_t *)dst, 0, c0, n, runs, st);
@@ -998,7 +1015,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                 e = hipEventRecord(done, mid);
                 if (e == hipSuccess) e = hipStreamWaitEvent(down, done, 0);
                 if (g_trace) ct.e_d0 = mark(down);
-                if (e == hipSuccess)
+                if (e == hipSuccess && fetch)
                     e = hipMemcpyAsync((uint8_t *)out.plane.p + o0 * es, (const uint8_t *)(wide ? d_out64.p : d_out.p) + o0 * es, (o1 - o0) * es, hipMemcpyDeviceToHost, down);
                 if (g_trace) { ct.e_d1 = mark(down); ct.t_queued = since(); ctrace.push_back(ct); }
                 f0 = f1;
@@ -1054,7 +1071,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
             if (wide) if (int rc = convert(AFG_WAV_KIND_F32, d_out.p, flac_out, qoa_out, d_out64.p, runs_main, stream)) return rc;
             AFG_HIP_CHECK(hipStreamSynchronize(stream));
         }
-        if (qoa_out) {                                       // (the FLAC part came back chunk by chunk)
+        if (qoa_out && fetch) {                              // (the FLAC part came back chunk by chunk)
             AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)out.plane.p + flac_out * es, (const uint8_t *)(wide ? d_out64.p : d_out.p) + flac_out * es, qoa_out * es,
                                          hipMemcpyDeviceToHost, stream));
             AFG_HIP_CHECK(hipStreamSynchronize(stream));
@@ -1067,7 +1084,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
             DeviceBuf &d_pcm64 = d_mp3_64;
             if (int rc = d_in.alloc(coef_bytes + flag_bytes)) return rc;
             if (int rc = d_pcm.alloc(coef_bytes)) return rc;
-            if (wide) if (int rc = d_pcm64.alloc(std::max<size_t>(mp3_blocks * 576 * es, 16))) return rc;
+            if (wide && fetch) if (int rc = d_pcm64.alloc(std::max<size_t>(mp3_blocks * 576 * es, 16))) return rc;
             // The files are cut into a few chunks of similar size, each with its own plan: the upload and kernel of
             // chunk k+1 (stream `up`) run while chunk k's PCM goes back (stream `down`) -- PCIe is full duplex.
             struct Chunk { size_t f0, f1, blk0, blocks; afg_mp3_plan *plan; hipEvent_t done; size_t runs = 0; };
@@ -1153,7 +1170,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                 if (e == hipSuccess) e = hipStreamWaitEvent(down, c.done, 0);
                 // delivery: the copy plan of each file, merged into maximal contiguous pieces (one per undamaged file),
                 // straight from the device PCM plane into the page-locked result plane
-                for (size_t i = c.f0; i < c.f1 && e == hipSuccess; i++) {
+                for (size_t i = c.f0; i < c.f1 && e == hipSuccess && fetch; i++) {
                     const Parsed &p = parsed[i];
                     if (fmt_of(p) != AFG_FORMAT_MP3) continue;
                     const uint8_t *src = (const uint8_t *)(wide ? d_pcm64.p : d_pcm.p) + mp3_blk_base[i] * 576 * es;
@@ -1186,7 +1203,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
             StagingPool::Lease h_spec;
             DeviceBuf d_spec, d_pcm;
             DeviceBuf &d_pcm64 = d_ogg_64;
-            if (wide) if (int rc = d_pcm64.alloc(std::max<size_t>(ogg_out * es, 16))) return rc;
+            if (wide && fetch) if (int rc = d_pcm64.alloc(std::max<size_t>(ogg_out * es, 16))) return rc;
             if (!ogg_staged)
                 if (int rc = g_staging.take(ogg_spec * sizeof(float), h_spec)) return rc;
             if (int rc = d_spec.alloc((ogg_staged ? ogg_stage->floats : ogg_spec) * sizeof(float))) return rc;
@@ -1284,7 +1301,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                 e = hipEventCreateWithFlags(&c.done, hipEventDisableTiming);
                 if (e == hipSuccess) e = hipEventRecord(c.done, up);
                 if (e == hipSuccess) e = hipStreamWaitEvent(down, c.done, 0);
-                if (e == hipSuccess)
+                if (e == hipSuccess && fetch)
                     e = hipMemcpyAsync(ogg_plane + c.out0 * es, (const uint8_t *)(wide ? d_pcm64.p : d_pcm.p) + c.out0 * es, c.out_n * es, hipMemcpyDeviceToHost, down);
             }
             if (up) { hipError_t e2 = hipStreamSynchronize(up); if (e == hipSuccess) e = e2; }
@@ -1293,7 +1310,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
             if (rc) return rc;
             if (e != hipSuccess) { afg::set_error("Vorbis stage failed: %s", hipGetErrorString(e)); return AFG_ERR_HIP; }
             // files delivered as several runs (seek-style trims, damaged streams): close the runs up, in place
-            for (size_t bi = 0, at = 0; bi < ogg_broken.size(); bi++) {
+            for (size_t bi = 0, at = 0; bi < ogg_broken.size() && fetch; bi++) {
                 const size_t i = ogg_broken[bi];
                 while (at < ogg_pieces.size() && ogg_pieces[at].file != i) at++;
                 uint8_t *dst = (uint8_t *)out.plane.p + out.files[i].pcm_off * es;
@@ -1313,7 +1330,7 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
             StagingPool::Lease h_in;
             DeviceBuf d_in, d_pcm;
             DeviceBuf &d_pcm64 = d_opus_64;
-            if (wide) if (int rc = d_pcm64.alloc(std::max<size_t>(opus_out * es, 16))) return rc;
+            if (wide && fetch) if (int rc = d_pcm64.alloc(std::max<size_t>(opus_out * es, 16))) return rc;
             if (int rc = g_staging.take(base_bytes + rec_bytes + opus_coefs * sizeof(float), h_in)) return rc;
             if (int rc = d_in.alloc(base_bytes + rec_bytes + opus_coefs * sizeof(float))) return rc;
             if (int rc = d_pcm.alloc(opus_out * sizeof(float))) return rc;
@@ -1377,8 +1394,9 @@ int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const
                 }
             }
             if (wide) if (int rc = convert(AFG_WAV_KIND_F32, d_pcm.p, 0, opus_out, d_pcm64.p, runs_opus, stream)) return rc;
-            AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)out.plane.p + (flac_out + qoa_out + mp3_out + ogg_out) * es, wide ? d_pcm64.p : d_pcm.p, opus_out * es,
-                                         hipMemcpyDeviceToHost, stream));
+            if (fetch)
+                AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)out.plane.p + (flac_out + qoa_out + mp3_out + ogg_out) * es, wide ? d_pcm64.p : d_pcm.p, opus_out * es,
+                                             hipMemcpyDeviceToHost, stream));
             AFG_HIP_CHECK(hipStreamSynchronize(stream));
             tm.lap("opus gather | h2d | kernel | d2h");
         }
@@ -2221,7 +2239,9 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
 {
     // so (afg_batch_opts.sample_type, dither, dither_seed): every plane the items point into holds doubles or packed integer
     // samples, made on the device
-    const bool f64 = so.f64(), wide = so.wide();
+    // Collate mode: nothing comes back.  Every stage scatters its chunks into so.d_out; what the files did not fill is written
+    // as zero runs at the end, when every file's delivered length is known, and the items point at the slabs.
+    const bool f64 = so.f64(), wide = so.wide(), fetch = so.fetch();
     const size_t es = so.es();
     {
         if (int rc = afg::require_device()) return rc;
@@ -2347,12 +2367,13 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
                 DeviceBuf d_in, d_pcm, d_pcm64;
                 std::vector<std::unique_ptr<F64Plane>> widen;     // one per chunk; the streams are drained before the stage returns
                 std::vector<std::unique_ptr<PackPlane>> packs;
+                std::vector<std::unique_ptr<CollatePlane>> collated;
                 std::vector<PackRun> runs;                        // (ascending: the files lie in the plane in order)
                 for (size_t i = 0; i < (size_t)n_files && so.dither; i++)
                     if (opus_open[i]) runs.push_back(PackRun{ opus_pcm_at[i], parsed[i].opus.bound_coeffs, 0 });
                 if (int rc = g_staging.take(base_bytes + rec_bytes + coefs_total * sizeof(float), h_in)) return rc;
-                if (int rc = g_staging.take(std::max<size_t>(coefs_total, 1) * es, owner->opus_plane)) return rc;
-                if (wide) if (int rc = d_pcm64.alloc(std::max<size_t>(coefs_total * es, 16))) return rc;
+                if (fetch) if (int rc = g_staging.take(std::max<size_t>(coefs_total, 1) * es, owner->opus_plane)) return rc;
+                if (wide && fetch) if (int rc = d_pcm64.alloc(std::max<size_t>(coefs_total * es, 16))) return rc;
                 if (int rc = d_in.alloc(base_bytes + rec_bytes + coefs_total * sizeof(float))) return rc;
                 if (int rc = d_pcm.alloc(std::max<size_t>(coefs_total, 1) * sizeof(float))) return rc;
                 uint64_t *hb = (uint64_t *)h_in.p;
@@ -2446,6 +2467,19 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
                             packs.emplace_back(new PackPlane);
                             rc = packs.back()->launch(so, (const float *)d_pcm.p, (uint8_t *)d_pcm64.p, 0, c0, c1 - c0, runs, up);
                             if (rc) break;
+                        } else if (so.collate()) {
+                            // the chunk's files have just been decoded: a file's run is what it delivers, not its bound
+                            // (the declared length cuts the delivery, stream.d:439-442); a failed file has none
+                            std::vector<PackRun> delivered;
+                            for (size_t i = first; i <= last; i++) {
+                                if (!opus_open[i] || parsed[i].opus.error) continue;
+                                const afg_opus::File &m = parsed[i].opus;
+                                const uint64_t frames = (uint64_t)std::min<int64_t>((int64_t)m.pcm_frames, std::max<int64_t>(m.declared_frames, 0));
+                                delivered.push_back(PackRun{ opus_pcm_at[i], std::min<uint64_t>(frames * (uint64_t)m.channels, m.bound_coeffs), 0, (uint32_t)i, (uint32_t)m.channels });
+                            }
+                            collated.emplace_back(new CollatePlane);
+                            rc = collated.back()->launch(so, (const float *)d_pcm.p, 0, c0, c1 - c0, delivered, up);
+                            if (rc) break;
                         }
                         hipEvent_t done = nullptr;
                         e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
@@ -2453,7 +2487,7 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
                         events.push_back(done);
                         e = hipEventRecord(done, up);
                         if (e == hipSuccess) e = hipStreamWaitEvent(down, done, 0);
-                        if (e == hipSuccess)
+                        if (e == hipSuccess && fetch)
                             e = hipMemcpyAsync((uint8_t *)owner->opus_plane.p + c0 * es, (const uint8_t *)(wide ? d_pcm64.p : d_pcm.p) + c0 * es, (c1 - c0) * es, hipMemcpyDeviceToHost, down);
                     }
                     f0 = f1;
@@ -2512,7 +2546,7 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
             const size_t per_block = qmode ? 576 * sizeof(int16_t) + sizeof(afg_mp3_qgranule) + sizeof(uint32_t)
                                            : 576 * sizeof(float) + sizeof(uint32_t);
             if (int rc = g_staging.take(total_bound * per_block + 64, mp3_stage)) return rc;
-            if (int rc = g_staging.take(total_bound * 576 * es, owner->mp3_plane)) return rc;
+            if (fetch) if (int rc = g_staging.take(total_bound * 576 * es, owner->mp3_plane)) return rc;
             float *coef0 = nullptr;
             int16_t *q0 = nullptr;
             afg_mp3_qgranule *recs0 = nullptr;
@@ -2652,7 +2686,7 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
             items[i].frames = d.frames;
             const uint8_t *plane = d.in_mp3_plane ? (const uint8_t *)owner->mp3_plane.p
                                    : d.in_opus_plane ? (const uint8_t *)owner->opus_plane.p : (const uint8_t *)src->plane.p;
-            items[i].pcm = (d.status == AFG_OK && d.frames > 0) ? (float *)(plane + d.pcm_off * es) : nullptr;
+            items[i].pcm = (d.status == AFG_OK && d.frames > 0 && fetch) ? (float *)(plane + d.pcm_off * es) : nullptr;
         }
         // MOD is probed last (stream.d:1796): files no other front-end took go to its stage
         std::vector<int> unknown;
@@ -2669,6 +2703,22 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
         unknown.erase(std::remove_if(unknown.begin(), unknown.end(), [&](int i) { return items[i].status == AFG_OK || items[i].message != kErrorUnknownFormat; }), unknown.end());
         if (int mrc = afg_mod::batch_stage(data, length, unknown, (int)nt, items, owner->mod_plane, so)) return mrc;
         tm.lap("mod stage");
+        if (so.collate()) {
+            // Every stage has drained its streams.  The padding: tails, the rows a file has no channel for, and the whole slab
+            // of a file that failed or starts past its end -- whatever a stage may have written there (an Opus file whose
+            // last packet failed) is overwritten.
+            std::vector<int64_t> frames((size_t)n_files, 0);
+            std::vector<int> channels((size_t)n_files, 0);
+            for (int i = 0; i < n_files; i++) {
+                const bool ok = items[i].status == AFG_OK;
+                if (ok) { frames[(size_t)i] = items[i].frames; channels[(size_t)i] = items[i].channels; }
+                items[i].pcm = ok ? so.d_out + (size_t)i * so.C * so.T : nullptr;
+            }
+            CollatePlane padding;
+            if (int rc2 = padding.pad(so, frames, channels, nullptr)) return rc2;
+            AFG_HIP_CHECK(hipStreamSynchronize(nullptr));
+            tm.lap("collate padding");
+        }
         keep = std::move(guard);
         tm.lap("items filled");
         return AFG_OK;
@@ -2931,6 +2981,54 @@ int afg_batch_decode(const uint8_t *const *data, const size_t *length, int n_fil
     o.struct_size = (uint32_t)sizeof(o);
     o.n_threads = n_threads;
     return afg_batch_decode_ex(data, length, n_files, &o, out);
+}
+
+int afg_batch_decode_to_device(const uint8_t *const *data, const size_t *length, int n_files, const afg_collate_opts *opts,
+                               float *d_out, afg_batch_result *out)
+{
+    try {
+        // (all of this before any device call: it holds on a machine without a GPU too)
+        if (!opts || !d_out || !out) { afg::set_error("afg_batch_decode_to_device: NULL %s", !opts ? "opts" : !d_out ? "d_out" : "out"); return AFG_ERR_INVALID; }
+        out->n_files = 0; out->items = nullptr; out->owner = nullptr;
+        if (opts->struct_size < offsetof(afg_collate_opts, first_frame) + sizeof(const int64_t *)) {
+            afg::set_error("afg_collate_opts.struct_size too small");
+            return AFG_ERR_INVALID;
+        }
+        if (opts->channels == 0 || opts->frames == 0) {
+            afg::set_error("afg_collate_opts: channels and frames must be at least 1 (%u, %u)", opts->channels, opts->frames);
+            return AFG_ERR_INVALID;
+        }
+        if (n_files < 0 || (n_files && (!data || !length))) { afg::set_error("afg_batch_decode_to_device: n_files %d, or no file list", n_files); return AFG_ERR_INVALID; }
+        for (int i = 0; i < n_files && opts->first_frame; i++)
+            if (opts->first_frame[i] < 0) { afg::set_error("afg_collate_opts.first_frame[%d] is negative", i); return AFG_ERR_INVALID; }
+        if (n_files == 0) return AFG_OK;
+        if ((uint64_t)opts->channels * opts->frames > (((uint64_t)1 << 62) / (uint64_t)n_files)) {
+            afg::set_error("afg_batch_decode_to_device: a tensor of %d x %u x %u floats", n_files, opts->channels, opts->frames);
+            return AFG_ERR_INVALID;
+        }
+        SampleOut so;
+        so.type = afg_front::kSampleCollate;
+        so.d_out = d_out;
+        so.C = opts->channels;
+        so.T = opts->frames;
+        so.n_files = (uint64_t)n_files;
+        so.first_frame = opts->first_frame;
+        auto owner = std::unique_ptr<BatchOwner>(new BatchOwner);
+        afg_batch_item *items = (afg_batch_item *)std::calloc((size_t)n_files, sizeof(afg_batch_item));
+        if (!items) return AFG_ERR_OOM;
+        struct ItemsGuard { afg_batch_item *p; ~ItemsGuard() { std::free(p); } } items_guard{ items };
+        // one pass over the whole list on the current device: a slab's place follows from the file's index in it
+        owner->parts.emplace_back();
+        if (int rc = batch_decode_device(data, length, n_files, opts->n_threads, items, owner->parts.back(), nullptr, so)) return rc;
+        items_guard.p = nullptr;
+        out->n_files = n_files;
+        out->items = items;
+        out->owner = owner.release();
+        return AFG_OK;
+    } catch (...) {
+        afg::set_error("out of host memory");
+        return AFG_ERR_OOM;
+    }
 }
 
 void afg_batch_free(afg_batch_result *r)

@@ -126,8 +126,8 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
     const size_t pcm_bytes = std::max<uint64_t>(frames, 1) * 2 * es;
     const size_t tick_bytes = align16(n_ticks * sizeof(afg_mod_tick)), seg_bytes = align16(std::max<uint64_t>(n_segs, 1) * sizeof(afg_mod_segment));
     const size_t in_bytes = tick_bytes + seg_bytes + align16(plane_bytes);
-    std::shared_ptr<void> pcm_owner = afg_front::staging_lease(pcm_bytes, &pcm);
-    if (!pcm_owner) return AFG_ERR_OOM;
+    std::shared_ptr<void> pcm_owner;                       // (collate: the floats go on to the tensor, nothing comes back)
+    if (so.fetch() && !(pcm_owner = afg_front::staging_lease(pcm_bytes, &pcm))) return AFG_ERR_OOM;
     std::shared_ptr<void> in_owner = afg_front::staging_lease(in_bytes, &in);
     if (!in_owner) return AFG_ERR_OOM;
     uint8_t *hin = (uint8_t *)in;
@@ -151,10 +151,9 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
     if (f64) if (int rc = wide.alloc(chunks.max_frames * 2)) return rc;
     afg_front::PackSlots packed;                           // AFG_SAMPLE_PCM_*: ... or packed there; a song is one run of its own samples
     std::vector<afg_front::PackRun> runs;
-    if (so.pcm()) {
-        if (int rc = packed.alloc(chunks.max_frames * 2, es)) return rc;
-        for (size_t j = 0; j < M && so.dither; j++) runs.push_back(afg_front::PackRun{ 2 * start[j], 2 * sims[mods[j]].frames, 0 });
-    }
+    if (so.pcm()) if (int rc = packed.alloc(chunks.max_frames * 2, es)) return rc;
+    for (size_t j = 0; j < M && so.runs(); j++) runs.push_back(afg_front::PackRun{ 2 * start[j], 2 * sims[mods[j]].frames, 0, (uint32_t)which[mods[j]], 2 });
+    std::vector<std::unique_ptr<afg_front::CollatePlane>> collated;   // collate: one per chunk, alive until run_chunks has drained
     const uint8_t *din = (const uint8_t *)d_in.p;
     const int rc = afg_front::run_chunks(
         chunks.count(),
@@ -170,10 +169,14 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
                                             din + tick_bytes + seg_bytes, (float *)d_out[slot].p, up))
                 return rc;
             if (so.pcm()) return packed.launch(slot, so, d_out[slot].p, 2 * start[first[c]], chunks.frames[c] * 2, runs, up);
+            if (so.collate()) {
+                collated.emplace_back(new afg_front::CollatePlane);
+                return collated.back()->launch(so, (const float *)d_out[slot].p, 2 * start[first[c]], 2 * start[first[c]], chunks.frames[c] * 2, runs, up);
+            }
             return f64 ? wide.launch(slot, AFG_WAV_KIND_F32, d_out[slot].p, chunks.frames[c] * 2, up) : AFG_OK;
         },
         [&](size_t c, int slot, hipStream_t down) -> int {
-            if (chunks.frames[c])
+            if (chunks.frames[c] && so.fetch())
                 AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)pcm + 2 * start[first[c]] * es, so.pcm() ? packed.bytes[slot].p : f64 ? wide.wide[slot].p : d_out[slot].p, chunks.frames[c] * 2 * es,
                                              hipMemcpyDeviceToHost, down));
             return AFG_OK;
@@ -188,7 +191,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
         it.channels = 2;
         it.samplerate = (float)kRate;
         it.frames = (int64_t)s.frames;
-        it.pcm = s.frames ? (float *)((uint8_t *)pcm + 2 * songs[j].out_frame * es) : nullptr;
+        it.pcm = s.frames && pcm ? (float *)((uint8_t *)pcm + 2 * songs[j].out_frame * es) : nullptr;
     }
     keep = pcm_owner;
     return AFG_OK;

@@ -125,6 +125,72 @@ int PackPlane::launch(const SampleOut &out, const float *d_in, uint8_t *d_out, u
     return afg_pcm_pack_hip(recs.size(), (const afg_pcm_pack_span *)spans.p, tiles, d_in, c1 - origin, d_out, (c1 - origin) * B, st);
 }
 
+int CollatePlane::submit(const SampleOut &out, const float *d_in, uint64_t in_floats, hipStream_t st)
+{
+    if (recs.empty()) return AFG_OK;
+    const uint64_t tiles = afg_collate_layout(recs.data(), recs.size());
+    if (int rc = spans.alloc(recs.size() * sizeof(afg_collate_span))) return rc;
+    AFG_HIP_CHECK(hipMemcpyAsync(spans.p, recs.data(), recs.size() * sizeof(afg_collate_span), hipMemcpyHostToDevice, st));
+    return afg::collate_launch(recs.data(), recs.size(), (const afg_collate_span *)spans.p, tiles, d_in, in_floats, out.d_out,
+                               out.n_files * out.C * out.T, st);
+}
+
+int CollatePlane::launch(const SampleOut &out, const float *d_in, uint64_t origin, uint64_t c0, uint64_t n, const std::vector<PackRun> &runs, hipStream_t st)
+{
+    if (n == 0) return AFG_OK;
+    const uint64_t c1 = c0 + n;
+    recs.clear();                                            // the upload's source lives as long as the object
+    // the first run that ends behind c0, then every run that starts before c1
+    auto it = std::upper_bound(runs.begin(), runs.end(), c0, [](uint64_t v, const PackRun &r) { return v < r.at + r.count; });
+    for (; it != runs.end() && it->at < c1; ++it) {
+        uint64_t a = std::max(it->at, c0), b = std::min(it->at + it->count, c1);
+        if (a >= b || it->channels == 0 || it->channels > 0xffff || it->file >= out.n_files) continue;
+        // only the samples of frames [first_frame, first_frame + T) get a tile: a crop of a long file launches the crop
+        const uint64_t ff = out.first_frame ? (uint64_t)out.first_frame[it->file] : 0;
+        const unsigned __int128 w0 = (unsigned __int128)ff * it->channels, w1 = w0 + (unsigned __int128)out.T * it->channels;
+        const uint64_t s_a = it->sample0 + (a - it->at), s_b = it->sample0 + (b - it->at);    // the piece, in file samples
+        if (w0 >= s_b || w1 <= s_a) continue;
+        if (w0 > s_a) a += (uint64_t)w0 - s_a;
+        if (w1 < s_b) b -= s_b - (uint64_t)w1;
+        afg_collate_span sp;
+        std::memset(&sp, 0, sizeof(sp));
+        sp.in_off = a - origin;
+        sp.count = b - a;
+        sp.sample0 = it->sample0 + (a - it->at);
+        sp.out_off = (uint64_t)it->file * out.C * out.T;
+        sp.first_frame = (int64_t)ff;
+        sp.frames = out.T;
+        sp.channels = (uint16_t)it->channels;
+        sp.out_channels = (uint16_t)std::min<uint32_t>(out.C, 0xffff);   // (a file has 65535 channels at the most: the rows behind are padding)
+        recs.push_back(sp);
+    }
+    return submit(out, d_in, c1 - origin, st);
+}
+
+int CollatePlane::pad(const SampleOut &out, const std::vector<int64_t> &frames, const std::vector<int> &channels, hipStream_t st)
+{
+    recs.clear();
+    const uint64_t C = out.C, T = out.T;
+    auto zero = [&](uint64_t at, uint64_t count) {
+        if (!count) return;
+        afg_collate_span sp;
+        std::memset(&sp, 0, sizeof(sp));
+        sp.out_off = at;
+        sp.count = count;
+        recs.push_back(sp);
+    };
+    for (uint64_t i = 0; i < out.n_files; i++) {
+        const uint64_t slab = i * C * T;
+        const int64_t ff = out.first_frame ? out.first_frame[i] : 0;
+        const uint64_t rows = std::min<uint64_t>((uint64_t)std::max(channels[i], 0), C);
+        const uint64_t filled = rows && frames[i] > ff ? std::min<uint64_t>((uint64_t)(frames[i] - ff), T) : 0;   // per row
+        if (filled == 0) { zero(slab, C * T); continue; }
+        for (uint64_t k = 0; k < rows && filled < T; k++) zero(slab + k * T + filled, T - filled);
+        zero(slab + rows * T, (C - rows) * T);
+    }
+    return submit(out, nullptr, 0, st);
+}
+
 int PackSlots::alloc(size_t samples, size_t es)
 {
     for (DevBuf &b : bytes) if (int rc = b.alloc(std::max<size_t>(samples * es, 16))) return rc;

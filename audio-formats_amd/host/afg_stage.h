@@ -89,23 +89,35 @@ struct F64Slots {
 
 // ---- packed integer PCM output (afg_batch_opts.sample_type AFG_SAMPLE_PCM_*, afg_batch_transcode) ----
 // What a batch stage delivers per sample.  A bool converts to it (true: doubles), which is all a stream's reads ask for.
+// Collate mode (afg_batch_decode_to_device) is a sample type of its own, known to the stages only: the stage's floats
+// stay on the device, afg_collate_hip scatters each chunk into the caller's tensor, and the download -- with the host
+// plane it would fill -- is left out.  Batch file i has its slab at d_out + i * C * T and starts at first_frame[i].
+constexpr uint32_t kSampleCollate = 0x100;
 struct SampleOut {
     uint32_t type = AFG_SAMPLE_F32;
     bool dither = false;                                         // AFG_DITHER_LCG31, the integer types only
     uint32_t seed = 0;
+    float *d_out = nullptr;                                      // collate: the tensor, n_files * C * T floats ...
+    uint32_t C = 0, T = 0;
+    uint64_t n_files = 0;
+    const int64_t *first_frame = nullptr;                        // ... and the file frame at t = 0, per batch file (NULL: 0)
     SampleOut() = default;
     SampleOut(bool f64) : type(f64 ? AFG_SAMPLE_F64 : AFG_SAMPLE_F32) {}
     bool f64() const { return type == AFG_SAMPLE_F64; }
-    bool pcm() const { return type >= AFG_SAMPLE_PCM_S8; }
+    bool pcm() const { return type >= AFG_SAMPLE_PCM_S8 && type <= AFG_SAMPLE_PCM_S24; }
+    bool collate() const { return type == kSampleCollate; }
     bool wide() const { return type != AFG_SAMPLE_F32; }         // a conversion launch follows the stage's kernels
-    size_t es() const { return type == AFG_SAMPLE_F64 ? 8 : type == AFG_SAMPLE_F32 ? 4 : type - AFG_SAMPLE_PCM_S8 + 1; }   // bytes per sample
+    bool runs() const { return dither || collate(); }            // the stage lists where each file's samples lie (PackRun)
+    bool fetch() const { return !collate(); }                    // the result comes back to host memory
+    size_t es() const { return type == AFG_SAMPLE_F64 ? 8 : (type == AFG_SAMPLE_F32 || collate()) ? 4 : type - AFG_SAMPLE_PCM_S8 + 1; }   // bytes per sample
     uint8_t wav_format() const { return (uint8_t)(type - AFG_SAMPLE_PCM_S8 + AFG_WAV_S8); }
     bool operator!=(const SampleOut &o) const { return type != o.type || dither != o.dither || seed != o.seed; }
 };
 // A run of one file's samples inside a stage's float plane: floats [at, at + count) are samples sample0 ... of the file.
 // A stage lists its runs (sorted by `at`) from the offsets it knows; they matter with dither only, where a sample's
-// draws follow from its index in the file.  Floats outside every run are never delivered.
-struct PackRun { uint64_t at, count, sample0; };
+// draws follow from its index in the file, and in collate mode, where a sample's place follows from it.  Floats outside
+// every run are never delivered.  file, channels (collate mode): the file's index in the batch and its channel count.
+struct PackRun { uint64_t at, count, sample0; uint32_t file = 0, channels = 0; };
 void sort_runs(std::vector<PackRun> &runs);
 // One launch of afg_pcm_pack_hip (csrc/pcm_pack.hip): floats [c0, c0 + n) of a stage's plane to the bytes at the same
 // sample index of a byte plane that mirrors it (the sample at float i lives at byte i * es).  d_in[0] is float `origin` of
@@ -117,6 +129,18 @@ struct PackPlane {
     DevBuf spans;
     int launch(const SampleOut &out, const float *d_in, uint8_t *d_out, uint64_t origin, uint64_t c0, uint64_t n,
                const std::vector<PackRun> &runs, hipStream_t st);
+};
+// One launch of afg_collate_hip (csrc/collate.hip) beside PackPlane: the runs' intersections with floats [c0, c0 + n) of
+// a stage's plane -- d_in[0] is float `origin` of it -- become copy spans into the tensor of `out`; floats outside the
+// runs go nowhere.  The same lifetime rule: the object holds the records its upload reads and lives until the launch has run.
+struct CollatePlane {
+    std::vector<afg_collate_span> recs;
+    DevBuf spans;
+    int launch(const SampleOut &out, const float *d_in, uint64_t origin, uint64_t c0, uint64_t n, const std::vector<PackRun> &runs, hipStream_t st);
+    // what the files did not fill, as zero runs: file i delivered frames[i] frames of channels[i] channels (0, 0: it failed)
+    int pad(const SampleOut &out, const std::vector<int64_t> &frames, const std::vector<int> &channels, hipStream_t st);
+private:
+    int submit(const SampleOut &out, const float *d_in, uint64_t in_floats, hipStream_t st);
 };
 // The packed side of a batch stage's two output slots, beside F64Slots.
 struct PackSlots {

@@ -106,7 +106,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
     const size_t es = so.es();                                    // bytes per sample of the PCM plane (span offsets count samples)
     // (tests make small files span several chunks: afg_dev_option("stage_chunk_samples"))
     const uint64_t chunk_cap = (afg_front::stage_chunk_samples(kBatchChunkSamples) + AFG_WAV_TILE_SAMPLES - 1) & ~(uint64_t)(AFG_WAV_TILE_SAMPLES - 1);
-    std::vector<afg_front::PackRun> runs;                         // AFG_SAMPLE_PCM_* with dither: a file is one run of its own samples
+    std::vector<afg_front::PackRun> runs;                         // AFG_SAMPLE_PCM_* with dither, collate: a file is one run of its own samples
     // ---- the scan, one file per helper-thread job ----
     struct File { bool ok = false; Info info; int kind = -1; uint64_t out_off = 0; };
     std::vector<File> files(which.size());
@@ -153,7 +153,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
         any = true;
         plane_floats = (plane_floats + 3) & ~(uint64_t)3;
         f.out_off = plane_floats;
-        if (so.dither) runs.push_back(afg_front::PackRun{ f.out_off, count, 0 });
+        if (so.runs()) runs.push_back(afg_front::PackRun{ f.out_off, count, 0, (uint32_t)which[k], (uint32_t)f.info.channels });
         for (uint64_t done = 0; done < count;) {
             if (chunk_cap - chunk_samples < AFG_WAV_TILE_SAMPLES) close_chunk();
             const uint64_t room = (chunk_cap - chunk_samples) & ~(uint64_t)(AFG_WAV_TILE_SAMPLES - 1);
@@ -183,8 +183,8 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
 
     // page-locked: the PCM plane the items point into (owned by `keep`) and two input stagings that take turns
     void *pcm = nullptr, *stage[2] = { nullptr, nullptr };
-    std::shared_ptr<void> pcm_owner = afg_front::staging_lease(std::max<uint64_t>(plane_floats, 4) * es, &pcm);
-    if (!pcm_owner) return AFG_ERR_OOM;
+    std::shared_ptr<void> pcm_owner;                     // (collate: the floats go on to the tensor, nothing comes back)
+    if (so.fetch() && !(pcm_owner = afg_front::staging_lease(std::max<uint64_t>(plane_floats, 4) * es, &pcm))) return AFG_ERR_OOM;
     std::shared_ptr<void> stage_owner[2];
     for (int b = 0; b < (C > 1 ? 2 : 1); b++)
         if (!(stage_owner[b] = afg_front::staging_lease((size_t)max_in, &stage[b]))) return AFG_ERR_OOM;
@@ -194,6 +194,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
         if (int rc = d_in[b].alloc((size_t)max_in)) return rc;
         if (int rc = d_out[b].alloc((size_t)max_out * (so.pcm() ? sizeof(float) : es))) return rc;
     }
+    std::vector<std::unique_ptr<afg_front::CollatePlane>> collated;   // one per chunk, alive until run_chunks has drained
     afg_front::PackSlots packed;                         // AFG_SAMPLE_PCM_*: the converted floats stay on the device and are packed there
     if (so.pcm()) if (int rc = packed.alloc((size_t)max_out, es)) return rc;
     // what chunk c takes up and brings back: both end with its last piece
@@ -228,9 +229,14 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
                                              in_bytes(c), (float *)d_out[b].p, (out_floats(c) + 3) & ~(uint64_t)3, up))
                 return rc;
             // (without dither the alignment gaps between files are packed too: their floats are whatever the buffer held)
+            if (so.collate()) {
+                collated.emplace_back(new afg_front::CollatePlane);
+                return collated.back()->launch(so, (const float *)d_out[b].p, chunk_out0[c], chunk_out0[c], out_floats(c), runs, up);
+            }
             return so.pcm() ? packed.launch(b, so, d_out[b].p, chunk_out0[c], out_floats(c), runs, up) : AFG_OK;
         },
         [&](size_t c, int b, hipStream_t down) -> int {
+            if (!so.fetch()) return AFG_OK;
             AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)pcm + chunk_out0[c] * es, so.pcm() ? packed.bytes[b].p : d_out[b].p, (size_t)out_floats(c) * es, hipMemcpyDeviceToHost, down));
             return AFG_OK;
         });
@@ -240,7 +246,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
         if (!f.ok) continue;
         afg_batch_item &it = items[which[k]];
         it.frames = (int64_t)f.info.frames;
-        it.pcm = f.info.frames ? (float *)((uint8_t *)pcm + f.out_off * es) : nullptr;
+        it.pcm = f.info.frames && pcm ? (float *)((uint8_t *)pcm + f.out_off * es) : nullptr;
     }
     keep = pcm_owner;
     return AFG_OK;

@@ -437,6 +437,15 @@ struct afg_pcm_pack_span { ulong in_off, out_off, count, first_tile, draw0; uint
 ulong afg_pcm_pack_layout(afg_pcm_pack_span* spans, ulong n_spans);
 int afg_pcm_pack_hip(ulong n_spans, const(afg_pcm_pack_span)* d_spans, ulong n_tiles, const(float)* d_in, ulong in_floats,
                      ubyte* d_out, ulong out_bytes, void* hip_stream);
+// collate on the device: runs of interleaved floats to planar, padded rows (channels 0: `count` zeros from out_off + sample0 on)
+struct afg_collate_span { ulong in_off, count, sample0, out_off; long first_frame; ulong first_tile; uint frames; ushort channels, out_channels; }
+ulong afg_collate_layout(afg_collate_span* spans, ulong n_spans);
+int afg_collate_hip(ulong n_spans, const(afg_collate_span)* d_spans, ulong n_tiles, const(float)* d_in, ulong in_floats,
+                    float* d_out, ulong out_floats, void* hip_stream);
+// batch decode into a [files, channels, frames] float tensor in device memory: the floats of readSamplesFloat, no download
+struct afg_collate_opts { uint struct_size; int n_threads; uint channels; uint frames; const(long)* first_frame; }
+int afg_batch_decode_to_device(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_collate_opts)* opts,
+                               float* d_out, afg_batch_result* result);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

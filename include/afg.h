@@ -726,6 +726,64 @@ uint64_t afg_pcm_pack_layout(afg_pcm_pack_span *spans, uint64_t n_spans);
 int afg_pcm_pack_hip(uint64_t n_spans, const afg_pcm_pack_span *d_spans, uint64_t n_tiles, const float *d_in,
                      uint64_t in_floats, uint8_t *d_out, uint64_t out_bytes, void *hip_stream);
 
+/* Collate on the device: runs of interleaved float samples inside a decode plane to planar, padded rows -- the
+ * [files, channels, frames] float32 tensor a training or feature-extraction job on the same GPU wants, with no download.
+ * A copy span: sample s = sample0 + i of its run (i < count) is frame f = s / channels, channel k = s % channels of its
+ * file, and is stored at d_out[out_off + k * frames + (f - first_frame)] when k < out_channels and
+ * 0 <= f - first_frame < frames; otherwise it is dropped.  The stored word is the input word (NaN payloads included).
+ * A zero run (channels == 0): `count` zero floats from d_out[out_off + sample0] on -- how padding is written; the tensor is
+ * never cleared as a whole.  Tiles are AFG_WAV_TILE_SAMPLES input samples (or zero floats), one workgroup per tile.  No
+ * word of d_out is read back and nothing outside the stated elements is written, so spans may write neighbouring floats
+ * of one row and a slab's neighbours may be foreign data.  The fields need 48 bytes; the tile table of the sibling spans
+ * (first_tile) makes it 56. */
+typedef struct afg_collate_span {   /* one run of one file's interleaved samples (56 bytes) */
+    uint64_t in_off;      /* float index in d_in of the run's first sample: any value */
+    uint64_t count;       /* samples in the run (not frames: a run may begin and end mid-frame) */
+    uint64_t sample0;     /* index of that first sample in its file */
+    uint64_t out_off;     /* float index in d_out of element [file, 0, 0] */
+    int64_t  first_frame; /* file frame that lands at t = 0 */
+    uint64_t first_tile;  /* filled in by afg_collate_layout */
+    uint32_t frames;      /* T: row length, >= 1 */
+    uint16_t channels;    /* of the file, 1 .. 65535; 0 = a zero run */
+    uint16_t out_channels;/* C: rows of the slab, >= 1 */
+} afg_collate_span;
+/* Host: gives every span its tiles (first_tile) and returns the launch's tile count. */
+uint64_t afg_collate_layout(afg_collate_span *spans, uint64_t n_spans);
+/* Runs every span in one launch.  d_spans is the device copy of spans laid out by afg_collate_layout, n_tiles what it
+ * returned; d_in (4-byte aligned; may be NULL when in_floats is 0: zero runs only) and d_out do not overlap.  Every span
+ * is checked before the launch (the entry fetches d_spans on hip_stream and waits for it): a copy span must lie inside
+ * [0, in_floats) and its whole slab -- out_channels * frames floats from out_off -- inside [0, out_floats), a zero run
+ * inside [0, out_floats); sample0 and count are below 2^62, |first_frame| below 2^61.  Otherwise AFG_ERR_INVALID and nothing is
+ * written. */
+int afg_collate_hip(uint64_t n_spans, const afg_collate_span *d_spans, uint64_t n_tiles, const float *d_in, uint64_t in_floats,
+                    float *d_out, uint64_t out_floats, void *hip_stream);
+
+/* Batch decode into a padded planar device tensor: afg_batch_decode_ex without the download.  d_out is n_files * channels *
+ * frames floats on the current device, and element [i, k, t] is the float AudioStream.readSamplesFloat (stream.d:429-637)
+ * -- afg_batch_decode_ex with AFG_SAMPLE_F32 in the same numeric mode -- delivers as sample (first_frame[i] + t) *
+ * channels_i + k of file i, for every format (FLAC and WAV go to float first, as for packed PCM); 0 where k >= channels_i,
+ * where the frame is past the file's delivered end, and for a file that failed.  Every stage keeps its float plane on the
+ * device and afg_collate_hip scatters each chunk into the tensor behind the stage's kernels; padding is written as zero
+ * runs, once.  No decoded sample is downloaded and no host staging is taken for output.  Synchronous: when the call returns
+ * every element of d_out has been written.  The current device only (one tensor lives on one device), and the whole list as
+ * one pass: a slab's place follows from the file's index in the list, so the pipeline of groups of files in which
+ * afg_batch_decode_ex runs large FLAC / Ogg Vorbis batches (one group parsed while the previous one's device stages run) is
+ * not used here.  d_out must not be in use by work queued on another stream: the library's streams are ordered with nobody's.
+ * items[i].pcm is the device address of file i's slab (NULL when the file failed; afg_batch_free does not free it);
+ * frames and channels are the file's own, uncropped; status and message as afg_batch_decode_ex: a bad file never poisons
+ * the batch.  Checked before any device call, AFG_ERR_INVALID with afg_last_error set: NULL opts, d_out or out; a
+ * struct_size that does not reach first_frame; channels == 0 or frames == 0; a negative first_frame entry; n_files < 0.
+ * n_files == 0 is AFG_OK and touches nothing. */
+typedef struct afg_collate_opts {
+    uint32_t       struct_size;   /* sizeof(afg_collate_opts) */
+    int            n_threads;     /* as afg_batch_opts */
+    uint32_t       channels;      /* C >= 1 */
+    uint32_t       frames;        /* T >= 1 */
+    const int64_t *first_frame;   /* per file, >= 0; NULL: 0 for every file */
+} afg_collate_opts;
+int afg_batch_decode_to_device(const uint8_t *const *data, const size_t *length, int n_files, const afg_collate_opts *opts,
+                               float *d_out, afg_batch_result *out);
+
 /* The writing half of AudioStream (stream.d:216-286 openToBuffer / openToMemory, :762-902 writeSamplesFloat /
  * writeSamplesDouble, :1282-1349 finalizeEncoding / finalizeAndGetEncodedResult) for WAV and QOA, on the same handle
  * type: afg_is_error, afg_error_message, afg_get_format, afg_get_num_channels, afg_get_samplerate and afg_close work
