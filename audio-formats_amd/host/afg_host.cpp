@@ -16,6 +16,7 @@
 #include "afg_xm_front.h"
 #include "afg_mp3_front.h"
 #include "afg_opus_front.h"
+#include "afg_batch.h"
 #include "afg_stage.h"
 #include "afg_vorbis_front.h"
 #include "afg_write_stream.h"
@@ -35,51 +36,16 @@
 
 using namespace afg_front;
 
+// debugging aids, read ONCE when the library is loaded (set them before that): a trace of the host stages and the staging
+// pool, and poisoned allocations (the test-suite runs with it: an output byte the library forgets to write shows up as NaN)
+namespace afg_front {
+const bool g_trace = std::getenv("AFG_TRACE") != nullptr;
+}  // namespace afg_front
+
 namespace {
 
-// error strings of the reference (internals.d:16-23; stream.d:1379)
-const char *const kErrorUnknownFormat = "Cannot decode stream: unrecognized encoding.";
-const char *const kErrorDecodingError = "Decoder encountered an error";
-const char *const kErrorDecoderInitializationFailed = "Decoder initialization failed";
-const char *const kErrorNotInitialized = "Stream not initialized";
-// this library's own: the reference decodes such files, the device path does not (out of scope)
-const char *const kErrorOpusMode = "Cannot decode stream: Opus SILK / hybrid packets are not supported (CELT-only).";
-
-// ---------------------------------------------------------------------------------------------
-// decoded files: one result plane for a whole batch
-// ---------------------------------------------------------------------------------------------
-struct Decoded {
-    int status = AFG_OK;
-    const char *message = nullptr;
-    int format = AFG_FORMAT_UNKNOWN;
-    int channels = 0;
-    float samplerate = 0;
-    int64_t frames = 0;                 // frames actually decoded
-    int64_t declared_frames = AFG_UNKNOWN_LENGTH;
-    size_t pcm_off = 0;                 // float offset of this file's interleaved PCM in the result plane
-    bool in_mp3_plane = false;          // ... or in the batch's MP3 plane (staging layout, afg_batch_decode)
-    bool in_opus_plane = false;         // ... or in the batch's Opus plane (decoded by the pipelined stage of afg_batch_decode)
-};
-
-struct Parsed {
-    int format = AFG_FORMAT_UNKNOWN;
-    FlacInfo fi;
-    FlacRecords flac;
-    QoaInfo qi;
-    std::vector<afg_qoa_frame> qoa;
-    afg_mp3::File mp3;
-    afg_vorbis::File ogg;
-    afg_opus::File opus;
-    bool opus_mode = false;               // an Ogg Opus file with SILK / hybrid packets: reported, not decoded
-    const float *mp3_coef() const { return mp3.ext_coef ? mp3.ext_coef : mp3.coef.data(); }
-    const uint32_t *mp3_flags() const { return mp3.ext_flags ? mp3.ext_flags : mp3.flags.data(); }
-};
-
-// Vorbis: inverse coupling and floor curves on the device (default) or in the host parser (AFG_VORBIS_HOST_FLOOR=1)
-// debugging aids, read ONCE when the library is loaded (set them before that): poisoned allocations (the test-suite runs
-// with it: an output byte the library forgets to write shows up as NaN) and a trace of the staging pool
 static const bool g_poison_alloc = std::getenv("AFG_POISON_ALLOC") != nullptr;
-static const bool g_trace = std::getenv("AFG_TRACE") != nullptr;
+// Vorbis: inverse coupling and floor curves on the device (default) or in the host parser (AFG_VORBIS_HOST_FLOOR=1)
 static bool vorbis_floor_on_device() { return afg::dev_option(afg::kDevVorbisHostFloor) <= 0; }
 
 // FLAC: residual rows that fit 16 bits are packed as int16 (default) or left as int32 (AFG_FLAC_HOST_RES32=1)
@@ -117,11 +83,6 @@ public:
         *out = p; *cap_out = want;
         return AFG_OK;
     }
-    void give_back(void *p, size_t cap)
-    {
-        int dev = 0;
-        give_back_on(hipGetDevice(&dev) == hipSuccess ? dev : -1, p, cap);
-    }
     void give_back_on(int dev, void *p, size_t cap)      // dev: the device the buffer was taken on (-1: unknown)
     {
         const bool known = dev >= 0;
@@ -158,24 +119,6 @@ DevicePool g_devpool;
 
 namespace {
 
-struct DeviceBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    ~DeviceBuf() { if (p) g_devpool.give_back(p, cap); }
-    int alloc(size_t bytes)
-    {
-        if (int rc = g_devpool.take(bytes, &p, &cap)) { p = nullptr; return rc; }
-        // AFG_POISON_ALLOC=1 (tests): device buffers start out holding NaN patterns, so that a stage that reads what nobody wrote
-        // shows (hipMemset runs on the null stream and returns early; the stages copy on non-blocking streams, which do not wait
-        // for it: without the synchronisation the fill can land on top of an upload)
-        if (bytes && g_poison_alloc) {
-            (void)hipMemset(p, 0xff, bytes);
-            (void)hipStreamSynchronize(nullptr);
-        }
-        return AFG_OK;
-    }
-};
-
 // page-locked host memory: H2D / D2H run at PCIe rate without a staging copy
 struct PinnedBuf {
     void *p = nullptr;
@@ -193,16 +136,7 @@ struct PinnedBuf {
 // much as moving it.  The pool keeps the few largest buffers it has seen, bounded in count and bytes.
 class StagingPool {
 public:
-    struct Lease {
-        StagingPool *pool = nullptr;
-        void *p = nullptr;
-        size_t cap = 0;
-        Lease() = default;
-        Lease(const Lease &) = delete;
-        Lease &operator=(const Lease &) = delete;
-        ~Lease() { if (pool && p) pool->give_back(p, cap); }
-    };
-    int take(size_t bytes, Lease &out)
+    int take(size_t bytes, StagingLease &out)
     {
         {
             std::lock_guard<std::mutex> lk(mu_);
@@ -210,10 +144,10 @@ public:
             for (size_t i = 0; i < free_.size(); i++)
                 if (free_[i].second >= bytes && (best == free_.size() || free_[i].second < free_[best].second)) best = i;
             if (best != free_.size()) {
-                out.pool = this; out.p = free_[best].first; out.cap = free_[best].second;
+                out.p = free_[best].first; out.cap = free_[best].second;
                 held_ -= out.cap;
                 free_.erase(free_.begin() + (long)best);
-                if (g_poison_alloc) std::memset(out.p, 0xff, out.cap);     // (tests: see DeviceBuf::alloc)
+                if (g_poison_alloc) std::memset(out.p, 0xff, out.cap);     // (tests: see DevBuf)
                 return AFG_OK;
             }
         }
@@ -222,7 +156,7 @@ public:
         if (g_trace) fprintf(stderr, "[afg] staging pool miss: pinning %.1f MB\n", cap / 1e6);
         hipError_t e = hipHostMalloc(&p, cap, hipHostMallocPortable);
         if (e != hipSuccess) { afg::set_error("hipHostMalloc(%zu) failed: %s", cap, hipGetErrorString(e)); return AFG_ERR_OOM; }
-        out.pool = this; out.p = p; out.cap = cap;
+        out.p = p; out.cap = cap;
         if (g_poison_alloc) std::memset(out.p, 0xff, out.cap);
         return AFG_OK;
     }
@@ -239,8 +173,7 @@ public:
         for (auto &b : drop) { (void)hipHostFree(b.first); bytes += b.second; }
         return bytes;
     }
-private:
-    void give_back(void *p, size_t cap)
+    void give_back(void *p, size_t cap)                  // (the end of a StagingLease)
     {
         std::lock_guard<std::mutex> lk(mu_);
         if (free_.size() < 128 && held_ + cap <= ((size_t)24 << 30)) {      // (a grouped batch leases a set of buffers per group)
@@ -250,6 +183,7 @@ private:
             (void)hipHostFree(p);
         }
     }
+private:
     std::mutex mu_;
     std::vector<std::pair<void *, size_t>> free_;
     size_t held_ = 0;
@@ -317,44 +251,27 @@ private:
 StreamPool g_streams;
 }  // namespace
 
-// the pools as the stages beside this file use them (declared in afg_stage.h)
+// the pools as the stages use them (declared in afg_stage.h and afg_batch.h)
 namespace afg_front {
-int devpool_take(size_t bytes, void **out, size_t *cap_out)
-{
-    if (int rc = g_devpool.take(bytes, out, cap_out)) return rc;
-    if (bytes && g_poison_alloc) {                       // (tests: see DeviceBuf::alloc)
-        (void)hipMemset(*out, 0xff, bytes);
-        (void)hipStreamSynchronize(nullptr);
-    }
-    return AFG_OK;
-}
+bool poison_alloc() { return g_poison_alloc; }
+int devpool_take(size_t bytes, void **out, size_t *cap_out) { return g_devpool.take(bytes, out, cap_out); }
 void devpool_give(void *p, size_t cap, int dev) { g_devpool.give_back_on(dev, p, cap); }
+StagingLease::~StagingLease() { if (p) g_staging.give_back(p, cap); }
+int staging_take(size_t bytes, StagingLease &out) { return g_staging.take(bytes, out); }
 // a page-locked staging lease; the buffer goes back to the pool when the last owner lets go
 std::shared_ptr<void> staging_lease(size_t bytes, void **p)
 {
-    auto lease = std::make_shared<StagingPool::Lease>();
+    auto lease = std::make_shared<StagingLease>();
     if (g_staging.take(bytes, *lease)) return nullptr;
     *p = lease->p;
     return lease;
 }
-hipError_t streams_take(hipStream_t *up, hipStream_t *down) { return g_streams.take(up, down); }
-void streams_give(hipStream_t up, hipStream_t down) { g_streams.give(up, down); }
+hipError_t streams_take(hipStream_t *up, hipStream_t *down, hipStream_t *mid) { return g_streams.take(up, down, mid); }
+void streams_give(hipStream_t up, hipStream_t down, hipStream_t mid) { g_streams.give(up, down, mid); }
 }  // namespace afg_front
 
 namespace {
 
-// AFG_TRACE=1: wall-clock of the host stages on stderr (development aid)
-struct StageTimer {
-    bool on = g_trace;
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void lap(const char *what)
-    {
-        if (!on) return;
-        const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[afg] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
-        t = now;
-    }
-};
 
 // Helper threads are kept between calls: the batch path runs one parallel_for per chunk of files, and creating a
 // few hundred threads each time cost more than the parsing they did.
@@ -421,1008 +338,48 @@ HelperPool g_device_helpers[16];
 // group's parse pass must not find it taken by the other group's small gather jobs (it would run on one thread)
 HelperPool g_group_helpers[16];
 thread_local HelperPool *tl_helpers = nullptr;
-// chunks a device stage cuts its files into (8; a group of a grouped batch -- below -- is itself a piece of a pipeline and takes 2)
+}  // namespace
+
+namespace afg_front {
+void helpers_run(unsigned helpers, const std::function<void()> &work) { (tl_helpers ? *tl_helpers : g_helpers).run(helpers, work); }
+}  // namespace afg_front
+
+namespace {
+
+
+// chunks a device stage cuts its files into (8; a group of a grouped batch -- below -- is itself a piece of a pipeline and takes 2).
+// Per host thread: the second thread of a batch, which decodes the FLAC / QOA files, has always cut into 8.
 thread_local unsigned tl_stage_chunks = 8;
 
-template <typename F>
-void parallel_for(size_t n, unsigned threads, F fn)
+StageCtx stage_ctx(std::vector<Parsed> &parsed, const uint8_t *const *data, const size_t *len, const uint8_t *own, unsigned threads,
+                   SampleOut so, BatchOut &out)
 {
-    if (n == 0) return;
-    threads = (unsigned)std::min<size_t>(std::max(1u, threads), n);
-    std::atomic<size_t> next{ 0 };
-    const std::function<void()> work = [&]() {
-        for (;;) {
-            const size_t i = next.fetch_add(1);
-            if (i >= n) return;
-            fn(i);
-        }
-    };
-    (tl_helpers ? *tl_helpers : g_helpers).run(threads - 1, work);
+    return StageCtx{ parsed, data, len, own, threads, so, tl_stage_chunks, out, StageTimer() };
 }
 
-struct BatchOut {
-    std::vector<Decoded> files;
-    StagingPool::Lease plane;           // all PCM of the batch: FLAC files, then QOA files, then MP3 files; page-locked,
-    size_t plane_floats = 0;            // returned to the pool by afg_batch_free / afg_close
-    StagingPool::Lease mp3_plane;       // batch path: the MP3 PCM in staging layout, served in place
-    StagingPool::Lease opus_plane;      // batch path: the Opus PCM, files back to back
-    std::unique_ptr<BatchOut> early;    // batch path: the FLAC / QOA files, decoded on a second host thread meanwhile
-    std::shared_ptr<void> mod_plane;    // batch path: the MOD files' PCM (afg_mod_stage.cpp)
-    std::shared_ptr<void> wav_plane;    // batch path: the WAV files' PCM (afg_wav_stage.cpp)
-    std::shared_ptr<void> xm_plane;     // batch path: the XM files' PCM (afg_xm_stage.cpp)
-    bool f64 = false;                   // a stream's double reads: `plane` holds plane_floats doubles
-};
-
-// Device stage for a set of parsed files: every FLAC record of the batch in one launch, every QOA frame
-// in another; inputs are gathered (by `threads` host threads) into one page-locked buffer per kind and
-// the results come back as one plane.
-// Where the batch path parsed its MP3 files: one page-locked buffer, file i at block base[i] (gaps between files).
-// The device planes and the MP3 result plane mirror that layout, so a chunk of files moves in ONE copy each way and
-// a file's PCM is served where it lands (a per-file copy costs ~20 us of submission: 2 x 2048 of them were the whole
-// end-to-end time of a 2048-file batch).
-struct Mp3Stage {
-    const float *coef = nullptr;        // float upload: dequantised spectra, blocks * 576 ...
-    const int16_t *q = nullptr;         // ... or quantised upload: Huffman values, blocks * 576, and one record slot
-    const afg_mp3_qgranule *recs = nullptr;   // per block (the slot of a granule's first block is used, nch = 0 elsewhere)
-    const uint32_t *flags = nullptr;
-    size_t blocks = 0;
-    const size_t *base = nullptr;
-    float *plane = nullptr;             // host PCM plane, blocks * 576 floats (page-locked) ...
-    SampleOut so;                       // ... or as many doubles / packed integer samples (afg_batch_opts.sample_type): made of the transform's floats on the device
-    size_t es() const { return so.es(); }
-};
-
-// Where the batch path parsed its Ogg Vorbis files: file i's spectra at float base[i] of one page-locked buffer
-struct OggStage {
-    const float *spec = nullptr;
-    size_t floats = 0;
-    const size_t *base = nullptr;
-};
-
-// Where the batch path parsed its FLAC files: file i's residual plane at word base[i] of one page-locked buffer
-struct FlacStage {
-    const int32_t *res = nullptr;
-    size_t words = 0;
-    const size_t *base = nullptr;
-};
-
-// H2D -> kernel on stream `up`, D2H on stream `down` behind an event: chunk k+1 uploads and transforms while chunk
-// k's PCM goes back (PCIe is full duplex) -- and while the host threads parse chunk k+2.
-struct Mp3Pipe {
-    const Mp3Stage *st = nullptr;
-    DeviceBuf d_in, d_pcm, d_pcm64;
-    std::vector<std::unique_ptr<F64Plane>> widen;          // one per chunk, alive until close() has drained the streams
-    std::vector<std::unique_ptr<PackPlane>> packs;         // likewise (AFG_SAMPLE_PCM_*)
-    std::vector<std::unique_ptr<CollatePlane>> collated;   // likewise (collate mode)
-    uint32_t *d_flags = nullptr;
-    hipStream_t up = nullptr, down = nullptr;
-    std::vector<afg_mp3_plan *> plans;
-    std::vector<hipEvent_t> events;
-    DeviceBuf d_tables;                 // plan tables: at most one 16-byte segment and stream record per block
-    StagingPool::Lease h_tables;
-    afg::PlanArena arena;
-    int rc = AFG_OK;
-    hipError_t e = hipSuccess;
-
-    DeviceBuf d_qin;                    // quantised upload: int16 plane, record slots, stereo descriptors
-    int16_t *d_q = nullptr;
-    afg_mp3_qgranule *d_recs = nullptr;
-    afg_mp3_sdesc *d_sdesc = nullptr;
-    StagingPool::Lease h_sdesc;
-    size_t sdesc_cap = 0, sdesc_used = 0;
-    uint64_t h2d_bytes = 0;
-
-    int open(const Mp3Stage &stage)
-    {
-        st = &stage;
-        const size_t coef_bytes = stage.blocks * 576 * sizeof(float), flag_bytes = (stage.blocks * 4 + 15) & ~(size_t)15;
-        if (int r = d_in.alloc(coef_bytes + flag_bytes)) return r;
-        if (int r = d_pcm.alloc(coef_bytes)) return r;
-        if (stage.so.wide() && stage.so.fetch()) if (int r = d_pcm64.alloc(std::max<size_t>(stage.blocks * 576 * stage.es(), 16))) return r;
-        if (stage.q) {
-            const size_t q_bytes = (stage.blocks * 576 * sizeof(int16_t) + 15) & ~(size_t)15;
-            const size_t rec_bytes = stage.blocks * sizeof(afg_mp3_qgranule);
-            sdesc_cap = 4096;                            // intensity-stereo granules of the whole batch (grown on demand: rare)
-            if (int r = d_qin.alloc(q_bytes + rec_bytes + sdesc_cap * sizeof(afg_mp3_sdesc))) return r;
-            d_q = (int16_t *)d_qin.p;
-            d_recs = (afg_mp3_qgranule *)((uint8_t *)d_qin.p + q_bytes);
-            d_sdesc = (afg_mp3_sdesc *)((uint8_t *)d_recs + rec_bytes);
-            if (int r = g_staging.take(sdesc_cap * sizeof(afg_mp3_sdesc), h_sdesc)) return r;
-        }
-        d_flags = (uint32_t *)((uint8_t *)d_in.p + coef_bytes);
-        e = g_streams.take(&up, &down);
-        if (e != hipSuccess) { afg::set_error("hipStreamCreate failed: %s", hipGetErrorString(e)); return AFG_ERR_HIP; }
-        const size_t tab_bytes = stage.blocks * 32 + 4096;
-        if (int r = d_tables.alloc(tab_bytes)) return r;
-        if (int r = g_staging.take(tab_bytes, h_tables)) return r;
-        arena.host = (uint8_t *)h_tables.p; arena.dev = (uint8_t *)d_tables.p; arena.cap = tab_bytes; arena.stream = up;
-        return AFG_OK;
-    }
-    // files [f0, f1) have been parsed into the stage: plan, upload, transform, download
-    void submit(const std::vector<Parsed> &parsed, size_t f0, size_t f1)
-    {
-        if (rc || e != hipSuccess) return;
-        std::vector<uint32_t> granules;
-        std::vector<uint8_t> channels;
-        std::vector<uint64_t> bases;
-        size_t b0 = 0, b1 = 0;
-        for (size_t i = f0; i < f1; i++) {
-            const Parsed &p = parsed[i];
-            if (p.format != AFG_FORMAT_MP3 || !p.mp3.blocks()) continue;
-            if (granules.empty()) b0 = st->base[i];
-            uint64_t at = st->base[i];
-            for (uint32_t g : p.mp3.run_granules) {
-                granules.push_back(g);
-                channels.push_back((uint8_t)p.mp3.channels);
-                bases.push_back(at);
-                at += (uint64_t)g * (uint64_t)p.mp3.channels;
-            }
-            b1 = st->base[i] + p.mp3.blocks();
-        }
-        if (granules.empty()) return;
-        afg_mp3_plan *plan = nullptr;
-        rc = afg::mp3_plan_create_at(&plan, (uint32_t)granules.size(), granules.data(), channels.data(), bases.data(), 0, &arena);
-        if (rc) return;
-        plans.push_back(plan);
-        hipEvent_t done = nullptr;
-        e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
-        if (e != hipSuccess) return;
-        events.push_back(done);
-        const size_t nb = b1 - b0;
-        if (st->q) {
-            // quantised upload: 2 bytes per line + a record per granule, requantised on the device into the plane the
-            // transform reads (afg_mp3_requant_hip); the stereo descriptors of intensity frames are gathered per chunk
-            afg_mp3_qgranule *hrecs = const_cast<afg_mp3_qgranule *>(st->recs);
-            const size_t sd0 = sdesc_used;
-            for (size_t i = f0; i < f1; i++) {
-                const Parsed &p = parsed[i];
-                if (p.format != AFG_FORMAT_MP3 || p.mp3.sdesc.empty()) continue;
-                if (sdesc_used + p.mp3.sdesc.size() > sdesc_cap) { afg::set_error("MP3 stage: more than %zu intensity-stereo granules in one batch", sdesc_cap); rc = AFG_ERR_UNSUPPORTED; return; }
-                std::memcpy((afg_mp3_sdesc *)h_sdesc.p + sdesc_used, p.mp3.sdesc.data(), p.mp3.sdesc.size() * sizeof(afg_mp3_sdesc));
-                for (size_t k = st->base[i]; k < st->base[i] + p.mp3.blocks(); k++)
-                    if (hrecs[k].nch && hrecs[k].sdesc != AFG_MP3_NO_SDESC) hrecs[k].sdesc += (uint32_t)sdesc_used;
-                sdesc_used += p.mp3.sdesc.size();
-            }
-            e = hipMemcpyAsync(d_q + b0 * 576, st->q + b0 * 576, nb * 576 * sizeof(int16_t), hipMemcpyHostToDevice, up);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_recs + b0, st->recs + b0, nb * sizeof(afg_mp3_qgranule), hipMemcpyHostToDevice, up);
-            if (e == hipSuccess && sdesc_used > sd0)
-                e = hipMemcpyAsync(d_sdesc + sd0, (afg_mp3_sdesc *)h_sdesc.p + sd0, (sdesc_used - sd0) * sizeof(afg_mp3_sdesc), hipMemcpyHostToDevice, up);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_flags + b0, st->flags + b0, nb * sizeof(uint32_t), hipMemcpyHostToDevice, up);
-            if (e != hipSuccess) return;
-            h2d_bytes += nb * (576 * sizeof(int16_t) + sizeof(afg_mp3_qgranule) + sizeof(uint32_t));
-            rc = afg_mp3_requant_hip(nb, d_recs + b0, d_q, d_sdesc, (float *)d_in.p, up);
-            if (rc) return;
-        } else {
-            e = hipMemcpyAsync((float *)d_in.p + b0 * 576, st->coef + b0 * 576, nb * 576 * sizeof(float), hipMemcpyHostToDevice, up);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_flags + b0, st->flags + b0, nb * sizeof(uint32_t), hipMemcpyHostToDevice, up);
-            if (e != hipSuccess) return;
-            h2d_bytes += nb * (576 * sizeof(float) + sizeof(uint32_t));
-        }
-        rc = afg_mp3_transform_hip(plan, (const float *)d_in.p, d_flags, (float *)d_pcm.p, nullptr, up);
-        if (rc) return;
-        if (st->so.f64()) {
-            widen.emplace_back(new F64Plane);
-            rc = widen.back()->launch(AFG_WAV_KIND_F32, (const float *)d_pcm.p + b0 * 576, nb * 576, (double *)d_pcm64.p + b0 * 576, up);
-            if (rc) return;
-        } else if (st->so.pcm() || st->so.collate()) {
-            // a file's samples are the pieces of its copy plan, in order (with dither a sample's draws follow its index, in
-            // collate mode its place does)
-            std::vector<PackRun> runs;
-            for (size_t i = f0; i < f1 && st->so.runs(); i++) {
-                const Parsed &p = parsed[i];
-                if (p.format != AFG_FORMAT_MP3 || !p.mp3.blocks()) continue;
-                uint64_t at = 0;
-                for (const afg_mp3::Copy &c : p.mp3.copies) { runs.push_back(PackRun{ st->base[i] * 576 + c.src, c.count, at, (uint32_t)i, (uint32_t)p.mp3.channels }); at += c.count; }
-            }
-            sort_runs(runs);
-            if (st->so.collate()) {
-                collated.emplace_back(new CollatePlane);
-                rc = collated.back()->launch(st->so, (const float *)d_pcm.p, 0, b0 * 576, nb * 576, runs, up);
-            } else {
-                packs.emplace_back(new PackPlane);
-                rc = packs.back()->launch(st->so, (const float *)d_pcm.p, (uint8_t *)d_pcm64.p, 0, b0 * 576, nb * 576, runs, up);
-            }
-            if (rc) return;
-        }
-        const size_t es = st->es();
-        e = hipEventRecord(done, up);
-        if (e == hipSuccess) e = hipStreamWaitEvent(down, done, 0);
-        if (e == hipSuccess && st->so.fetch())
-            e = hipMemcpyAsync((uint8_t *)st->plane + b0 * 576 * es, (const uint8_t *)(st->so.wide() ? d_pcm64.p : d_pcm.p) + b0 * 576 * es, nb * 576 * es, hipMemcpyDeviceToHost, down);
-    }
-    int close()
-    {
-        if (up) { hipError_t e2 = hipStreamSynchronize(up); if (e == hipSuccess) e = e2; }
-        if (down) { hipError_t e2 = hipStreamSynchronize(down); if (e == hipSuccess) e = e2; }
-        for (afg_mp3_plan *p : plans) afg_mp3_plan_destroy(p);
-        for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
-        plans.clear(); events.clear(); widen.clear(); packs.clear(); collated.clear();
-        g_streams.give(up, down);
-        up = down = nullptr;
-        if (rc) return rc;
-        if (e != hipSuccess) { afg::set_error("MP3 stage failed: %s", hipGetErrorString(e)); return AFG_ERR_HIP; }
-        return AFG_OK;
-    }
-    ~Mp3Pipe() { (void)close(); }
-};
-
-// Decoder state an MP3 stream carries from one chunk of frames to the next (chunked AudioStream reads): the overlap and
-// polyphase history of the run that was open when the previous chunk ended, as the transform kernel left it.
-struct Mp3Carry {
-    DeviceBuf state;                    // AFG_MP3_STATE_FLOATS floats
-    bool valid = false;                 // `state` holds the end of the previous chunk
-    bool continues = false;             // this chunk's first run goes on from it
-};
-
-// What an Opus stream carries from one chunk of packets to the next on the device: the transform stage's per-channel
-// memory (overlap, post-filter history, de-emphasis), as afg_celt_transform_hip reads and rewrites it.
-struct OpusCarry {
-    DeviceBuf states;                   // channels * AFG_CELT_STATE_FLOATS floats
-    bool valid = false;
-};
-
-int decode_parsed(std::vector<Parsed> &parsed, const uint8_t *const *data, const size_t *len, unsigned threads, BatchOut &out,
-                  const Mp3Stage *stage = nullptr, const OggStage *ogg_stage = nullptr, const FlacStage *flac_stage = nullptr,
-                  const uint8_t *own = nullptr, Mp3Carry *carry = nullptr, OpusCarry *opus_carry = nullptr,
-                  const size_t *opus_done_at = nullptr, SampleOut so = SampleOut())
+// what the caller is told of every file (the PCM offsets are the layouts')
+void fill_metadata(StageCtx &ctx)
 {
-    // f64 (afg_read_samples_double, afg_batch_opts.sample_type): the result plane holds doubles.  Every stage's device plane
-    // -- int32 for FLAC, float for the others -- is widened by afg_pcm_to_f64_hip behind the stage's kernels, on their
-    // stream, and the doubles are what comes back.  The batch path's MP3 and Opus planes were widened by their own pipelines.
-    // AFG_SAMPLE_PCM_* (afg_batch_opts.sample_type): the result plane holds samples of 1, 2 or 3 bytes, packed from every
-    // stage's float plane by afg_pcm_pack_hip at the same place; FLAC restores to float as for a float read.
-    // Collate mode (afg_batch_decode_to_device): there is no result plane.  afg_collate_hip scatters every stage's float plane
-    // into the caller's tensor where the other types convert, and the downloads are left out; parsed[i] is batch file i.
-    if (stage && stage->blocks && stage->so != so) { afg::set_error("decode_parsed: the MP3 stage's sample type differs"); return AFG_ERR_INVALID; }
-    const bool f64 = so.f64(), wide = so.wide(), fetch = so.fetch();
-    const size_t es = so.es();
-    out.f64 = f64;
-    // dither: where each file's samples lie in the stages' device planes (afg_stage.h: PackRun)
-    std::vector<PackRun> runs_main, runs_mp3, runs_ogg, runs_opus;
-    // opus_done_at (batch path): the Opus files are already decoded, file i's PCM at float opus_done_at[i] of the batch's
-    // Opus plane; only their metadata is filled in here
-    // `own` (optional, one byte per file): the files this call is responsible for.  The batch path decodes its FLAC /
-    // QOA files on a second host thread while the first still parses MP3 / Ogg files: a call never looks at (not even
-    // the format of) a file it does not own.
-    auto fmt_of = [&](const Parsed &q) -> int { return (!own || own[&q - parsed.data()]) ? q.format : -1; };
-    const size_t nf = parsed.size();
-    out.files.assign(nf, Decoded());
-    StageTimer tm;
-    // ---- layout ----
-    std::vector<size_t> res_base(nf, 0), fr_base(nf, 0), sf_base(nf, 0), qbyte_base(nf, 0), qfr_base(nf, 0);
-    size_t res_total = 0, fr_total = 0, sf_total = 0, flac_out = 0, qbytes = 0, qframes = 0, qoa_out = 0;
-    const bool flac_staged = flac_stage && flac_stage->words;
-    for (size_t i = 0; i < nf; i++) {
-        Parsed &p = parsed[i];
-        if (fmt_of(p) != AFG_FORMAT_FLAC) continue;
-        if (!flac_staged) res_total = (res_total + 3) & ~(size_t)3;     // 16-byte aligned planes (int16 rows: afg_flac_frame.res16)
-        res_base[i] = flac_staged ? flac_stage->base[i] : res_total; fr_base[i] = fr_total; sf_base[i] = sf_total;
-        out.files[i].pcm_off = flac_out;
-        if (so.runs()) runs_main.push_back(PackRun{ flac_out, p.flac.out_samples, 0, (uint32_t)i, (uint32_t)p.fi.channels });
-        res_total += p.flac.res_size(); fr_total += p.flac.frames.size(); sf_total += p.flac.subframes.size();
-        flac_out += p.flac.out_samples;
-    }
-    if (flac_staged) res_total = flac_stage->words;          // the device plane mirrors the staging layout (gaps and all)
-    for (size_t i = 0; i < nf; i++) {
-        Parsed &p = parsed[i];
-        if (fmt_of(p) != AFG_FORMAT_QOA) continue;
-        qbyte_base[i] = qbytes; qfr_base[i] = qframes;
-        out.files[i].pcm_off = flac_out + qoa_out;
-        qbytes += (len[i] + 15) & ~(size_t)15;
-        qframes += p.qoa.size();
-        const size_t q_samples = p.qoa.back().out_off + (size_t)p.qoa.back().samples * p.qoa.back().channels;
-        if (so.runs()) runs_main.push_back(PackRun{ flac_out + qoa_out, q_samples, 0, (uint32_t)i, (uint32_t)p.qi.channels });
-        qoa_out += q_samples;
-    }
-    std::vector<size_t> mp3_blk_base(nf, 0);
-    size_t mp3_blocks = 0, mp3_out = 0;
-    for (size_t i = 0; i < nf; i++) {
-        Parsed &p = parsed[i];
-        if (fmt_of(p) != AFG_FORMAT_MP3) continue;
-        mp3_blk_base[i] = mp3_blocks;
-        if (so.runs()) {
-            uint64_t at = 0;
-            for (const afg_mp3::Copy &c : p.mp3.copies) { runs_mp3.push_back(PackRun{ mp3_blocks * 576 + c.src, c.count, at, (uint32_t)i, (uint32_t)p.mp3.channels }); at += c.count; }
-        }
-        out.files[i].pcm_off = flac_out + qoa_out + mp3_out;
-        mp3_blocks += p.mp3.blocks();
-        mp3_out += (size_t)p.mp3.pcm_samples;
-    }
-    // Staged batch (afg_batch_decode): the MP3 files are already decoded, in staging layout, in stage->plane
-    const bool staged = stage && stage->blocks && mp3_blocks;
-    if (staged) {
-        mp3_out = 0;
-        for (size_t i = 0; i < nf; i++) {
-            Parsed &p = parsed[i];
-            if (fmt_of(p) != AFG_FORMAT_MP3) continue;
-            const uint64_t first = p.mp3.copies.empty() ? 0 : p.mp3.copies[0].src;
-            out.files[i].pcm_off = stage->base[i] * 576 + (size_t)first;
-            out.files[i].in_mp3_plane = true;
-        }
-    }
-    // Vorbis: chunks of files, one plan each; the Vorbis part of the result plane is the plans' output planes back to
-    // back, so a chunk's PCM comes back in one copy and a file is served where it lands (first piece onwards)
-    struct OggChunk {
-        size_t f0 = 0, f1 = 0, spec0 = 0, spec_n = 0, out0 = 0, out_n = 0;
-        afg_vorbis_plan *plan = nullptr;
-        hipEvent_t done = nullptr;
-        std::vector<size_t> spec_at;                         // per file of the chunk: float offset of its spectra in the chunk
-    };
-    struct OggChunks {
-        std::vector<OggChunk> v;
-        ~OggChunks()
-        {
-            for (OggChunk &c : v) {
-                if (c.plan) afg_vorbis_plan_destroy(c.plan);
-                if (c.done) (void)hipEventDestroy(c.done);
-            }
-        }
-    } ogg;
-    struct OggPiece { size_t file; uint64_t from, count; };  // pieces of files that are not served as one run
-    std::vector<OggPiece> ogg_pieces;
-    std::vector<size_t> ogg_broken;
-    size_t ogg_out = 0, ogg_packets = 0, ogg_spec = 0;
-    const bool ogg_staged = ogg_stage && ogg_stage->floats;
-    {
-        size_t total = 0;
-        for (size_t i = 0; i < nf; i++)
-            if (fmt_of(parsed[i]) == AFG_FORMAT_OGG) { total += parsed[i].ogg.n_spec; ogg_packets += parsed[i].ogg.pflags.size(); }
-        const size_t target = std::max<size_t>((total + tl_stage_chunks - 1) / tl_stage_chunks, (size_t)stage_chunk_samples((size_t)4 << 20));
-        for (size_t f0 = 0; f0 < nf && ogg_packets;) {
-            size_t f1 = f0, acc = 0;
-            while (f1 < nf && acc < target) { if (fmt_of(parsed[f1]) == AFG_FORMAT_OGG) acc += parsed[f1].ogg.n_spec; f1++; }
-            OggChunk c;
-            c.f0 = f0; c.f1 = f1; c.spec0 = ogg_spec; c.out0 = ogg_out;
-            std::vector<uint32_t> npk;
-            std::vector<uint8_t> chans, pflags;
-            std::vector<uint16_t> b0, b1;
-            std::vector<uint64_t> sbase;                     // staged: where each stream's spectra sit in the staging buffer
-            c.spec_at.assign(f1 - f0, 0);
-            size_t at = 0, span0 = 0, span1 = 0;
-            for (size_t i = f0; i < f1; i++) {
-                const Parsed &p = parsed[i];
-                if (fmt_of(p) != AFG_FORMAT_OGG) continue;
-                c.spec_at[i - f0] = at;
-                at += p.ogg.n_spec;
-                if (p.ogg.pflags.empty()) continue;
-                if (ogg_staged) {
-                    if (sbase.empty()) span0 = ogg_stage->base[i];
-                    span1 = ogg_stage->base[i] + p.ogg.n_spec;
-                    sbase.push_back(ogg_stage->base[i]);
-                }
-                npk.push_back((uint32_t)p.ogg.pflags.size());
-                chans.push_back((uint8_t)p.ogg.channels);
-                b0.push_back((uint16_t)p.ogg.blocksize0);
-                b1.push_back((uint16_t)p.ogg.blocksize1);
-                pflags.insert(pflags.end(), p.ogg.pflags.begin(), p.ogg.pflags.end());
-            }
-            f0 = f1;
-            if (npk.empty()) continue;
-            if (int rc = afg::vorbis_plan_create_at(&c.plan, (uint32_t)npk.size(), npk.data(), chans.data(), b0.data(), b1.data(),
-                                                    pflags.data(), ogg_staged ? sbase.data() : nullptr, 0))
-                return rc;
-            ogg.v.push_back(std::move(c));
-            OggChunk &k = ogg.v.back();
-            k.spec_n = (size_t)afg_vorbis_plan_spec_floats(k.plan);
-            k.out_n = (size_t)afg_vorbis_plan_out_floats(k.plan);
-            if (ogg_staged) {                                // the plan addresses the staging layout: the chunk is a span of it
-                if (k.spec_n != span1) {
-                    afg::set_error("Vorbis stage: spectrum layout mismatch (%zu vs %zu floats)", k.spec_n, span1);
-                    return AFG_ERR_INVALID;
-                }
-                k.spec0 = span0;
-                k.spec_n = span1 - span0;
-            } else if (k.spec_n != at) {
-                afg::set_error("Vorbis stage: spectrum layout mismatch (%zu vs %zu floats)", k.spec_n, at);
-                return AFG_ERR_INVALID;
-            }
-            std::vector<uint64_t> out_off(pflags.size());
-            if (int rc = afg_vorbis_plan_offsets(k.plan, nullptr, out_off.data())) return rc;
-            // delivery = the pull API's share of every packet's output: normally one run from the first packet on
-            size_t pk = 0;
-            for (size_t i = k.f0; i < k.f1; i++) {
-                const Parsed &p = parsed[i];
-                if (fmt_of(p) != AFG_FORMAT_OGG) continue;
-                const size_t n = p.ogg.pflags.size(), C = (size_t)p.ogg.channels;
-                const size_t first_piece = ogg_pieces.size();
-                for (size_t q = 0; q < n;) {
-                    if (p.ogg.take_count[q] <= 0) { q++; continue; }
-                    uint64_t from = out_off[pk + q] + (uint64_t)p.ogg.take_from[q] * C, cnt = (uint64_t)p.ogg.take_count[q] * C;
-                    size_t j = q + 1;
-                    while (j < n && p.ogg.take_count[j] > 0 && out_off[pk + j] + (uint64_t)p.ogg.take_from[j] * C == from + cnt)
-                        cnt += (uint64_t)p.ogg.take_count[j++] * C;
-                    ogg_pieces.push_back(OggPiece{ i, ogg_out + from, cnt });
-                    q = j;
-                }
-                if (so.runs()) {
-                    uint64_t at = 0;
-                    for (size_t k = first_piece; k < ogg_pieces.size(); k++) { runs_ogg.push_back(PackRun{ ogg_pieces[k].from, ogg_pieces[k].count, at, (uint32_t)i, (uint32_t)p.ogg.channels }); at += ogg_pieces[k].count; }
-                }
-                out.files[i].pcm_off = flac_out + qoa_out + mp3_out + (ogg_pieces.size() > first_piece ? (size_t)ogg_pieces[first_piece].from : ogg_out);
-                if (ogg_pieces.size() - first_piece > 1) ogg_broken.push_back(i);
-                else if (ogg_pieces.size() > first_piece) ogg_pieces.pop_back();          // one run: nothing to move
-                pk += n;
-            }
-            if (!ogg_staged) ogg_spec += k.spec_n;
-            ogg_out += k.out_n;
-        }
-    }
-    if (staged && fetch) {
-        // delivery in place: a file whose copy plan is one piece (every undamaged file) is served where it landed;
-        // the pieces of a damaged file are closed up towards its first piece (ascending, so memmove order is safe)
-        std::vector<size_t> broken;                          // files whose pieces are not already back to back
-        for (size_t i = 0; i < nf; i++) {
-            const Parsed &p = parsed[i];
-            if (fmt_of(p) != AFG_FORMAT_MP3) continue;
-            for (size_t k = 1; k < p.mp3.copies.size(); k++)
-                if (p.mp3.copies[k].src != p.mp3.copies[k - 1].src + p.mp3.copies[k - 1].count) { broken.push_back(i); break; }
-        }
-        parallel_for(broken.size(), threads, [&](size_t bi) {
-            const size_t i = broken[bi];
-            const Parsed &p = parsed[i];
-            uint8_t *file_plane = (uint8_t *)stage->plane + stage->base[i] * 576 * es;
-            uint8_t *dst = file_plane + p.mp3.copies[0].src * es;
-            for (const afg_mp3::Copy &c : p.mp3.copies) {
-                if (dst != file_plane + c.src * es) std::memmove(dst, file_plane + c.src * es, (size_t)c.count * es);
-                dst += c.count * es;
-            }
-        });
-        tm.lap("mp3 delivery (in place)");
-    }
-    // Opus: one channel sequence per output channel of every file; the PCM plane holds the files back to back, interleaved
-    std::vector<size_t> opus_rec_base(nf, 0), opus_coef_base(nf, 0), opus_pcm_base(nf, 0);
-    size_t opus_out = 0, opus_recs = 0, opus_coefs = 0, opus_seqs = 0;
-    for (size_t i = 0; i < nf; i++) {
-        const Parsed &p = parsed[i];
-        if (fmt_of(p) != AFG_FORMAT_OPUS) continue;
-        if (opus_done_at) {
-            out.files[i].pcm_off = opus_done_at[i];
-            out.files[i].in_opus_plane = true;
-            continue;
-        }
-        opus_rec_base[i] = opus_recs; opus_coef_base[i] = opus_coefs; opus_pcm_base[i] = opus_out;
-        if (so.dither) runs_opus.push_back(PackRun{ opus_out, (uint64_t)p.opus.pcm_frames * (uint64_t)p.opus.channels, 0 });
-        else if (so.collate())                                   // (what is delivered: the declared length cuts it, below)
-            runs_opus.push_back(PackRun{ opus_out, (uint64_t)std::min<int64_t>((int64_t)p.opus.pcm_frames, std::max<int64_t>(p.opus.declared_frames, 0)) * (uint64_t)p.opus.channels,
-                                         0, (uint32_t)i, (uint32_t)p.opus.channels });
-        out.files[i].pcm_off = flac_out + qoa_out + mp3_out + ogg_out + opus_out;
-        opus_recs += p.opus.frames.size() * (size_t)p.opus.channels;
-        opus_coefs += p.opus.coeffs.size();
-        opus_out += (size_t)p.opus.pcm_frames * (size_t)p.opus.channels;
-        // The transform stage walks sequences 2p and 2p + 1 together when they are the two channels of a stream (one
-        // wavefront, half each: afg.h).  A stereo file behind an odd number of mono files would sit across two such
-        // slots -- walked one channel at a time, and, in AFG_NUMERIC_TOLERANCE, to samples that depend on what else is
-        // in the batch -- so an empty sequence goes in front of it.
-        if (p.opus.channels == 2 && (opus_seqs & 1)) opus_seqs++;
-        opus_seqs += (size_t)p.opus.channels;
-    }
-    out.plane_floats = flac_out + qoa_out + mp3_out + ogg_out + opus_out;
-    if (out.plane_floats == 0) goto metadata;
-    {
-        if (fetch) if (int rc = g_staging.take(out.plane_floats * es, out.plane)) return rc;
-        tm.lap("layout + plane alloc");
-        // (the widened planes and the conversion records are declared out here: on an early way out of a stage they are let
-        //  go only after the device has drained, below them)
-        DeviceBuf d_out, d_out64, d_mp3_64, d_ogg_64, d_opus_64;
-        if (int rc = d_out.alloc(out.plane_floats * sizeof(float))) return rc;
-        if (wide && fetch) if (int rc = d_out64.alloc(std::max<size_t>((flac_out + qoa_out) * es, 16))) return rc;   // FLAC and QOA are converted in place of the plane
-        std::vector<std::unique_ptr<F64Plane>> widen;        // one per conversion launch, alive until the stages have drained
-        std::vector<std::unique_ptr<PackPlane>> packs;
-        std::vector<std::unique_ptr<CollatePlane>> collated;
-        struct Drain { bool on; ~Drain() { if (on) (void)hipDeviceSynchronize(); } } drain{ wide };
-        for (std::vector<PackRun> *r : { &runs_main, &runs_mp3, &runs_ogg, &runs_opus }) sort_runs(*r);
-        // samples [c0, c0 + n) of a stage's plane `src` (4-byte elements of `kind`) to the same samples of its converted
-        // plane `dst`: doubles, or packed integers; collate mode: to the tensor (dst is not used)
-        auto convert = [&](uint32_t kind, const void *src, uint64_t c0, uint64_t n, void *dst, const std::vector<PackRun> &runs, hipStream_t st) -> int {
-            if (so.collate()) {
-                collated.emplace_back(new CollatePlane);
-                return collated.back()->launch(so, (const float *)src, 0, c0, n, runs, st);
-            }
-            if (so.pcm()) {
-                packs.emplace_back(new PackPlane);
-                return packs.back()->launch(so, (const float *)src, (uint8_t *)dst, 0, c0, n, runs, st);
-            }
-            widen.emplace_back(new F64Plane);
-            return widen.back()->launch(kind, (const uint8_t *)src + c0 * 4, n, (double *)dst + c0, st);
-        };
-        hipStream_t stream = nullptr;
-        // ---- FLAC ----
-        if (flac_out) {
-            const size_t rec_bytes = fr_total * sizeof(afg_flac_frame) + sf_total * sizeof(afg_flac_subframe);
-            const size_t rec_pad = (rec_bytes + 15) & ~(size_t)15;
-            StagingPool::Lease h_in;
-            DeviceBuf d_in;
-            if (int rc = g_staging.take(rec_pad + (flac_staged ? 0 : res_total * 4), h_in)) return rc;
-            if (int rc = d_in.alloc(rec_pad + res_total * 4)) return rc;
-            afg_flac_frame *hf = (afg_flac_frame *)h_in.p;
-            afg_flac_subframe *hs = (afg_flac_subframe *)(hf + fr_total);
-            int32_t *hr = (int32_t *)((uint8_t *)h_in.p + rec_pad);           // (not staged: the residuals are gathered here)
-            const int32_t *hres = flac_staged ? flac_stage->res : hr;
-            // Chunks of files: gather (host threads) -> upload + kernel on `up` -> download on `down` behind an event,
-            // so the gather of chunk k+1, the upload of chunk k and the download of chunk k-1 overlap.
-            const afg_flac_frame *df = (const afg_flac_frame *)d_in.p;
-            const afg_flac_subframe *ds = (const afg_flac_subframe *)(df + fr_total);
-            const int32_t *dr = (const int32_t *)((const uint8_t *)d_in.p + rec_pad);
-            // three streams: uploads only on `up` (the next chunk's never waits behind this chunk's kernel), kernels on `mid`
-            // behind the upload's event, downloads on `down` behind the kernel's
-            hipStream_t up = nullptr, down = nullptr, mid = nullptr;
-            std::vector<hipEvent_t> events;
-            hipError_t e = g_streams.take(&up, &down, &mid);
-            int rc = AFG_OK;
-            const size_t target = std::max<size_t>((res_total + tl_stage_chunks - 1) / tl_stage_chunks, (size_t)stage_chunk_samples((size_t)4 << 20));
-            // AFG_TRACE: host wall-clock of every chunk's gather and submission, device time of its upload, kernel and download
-            struct ChunkTrace { double t_begin, t_gathered, t_queued; hipEvent_t e_up0, e_up1, e_k1, e_d0, e_d1; };
-            std::vector<ChunkTrace> ctrace;
-            const auto t_stage = std::chrono::steady_clock::now();
-            auto since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_stage).count(); };
-            hipEvent_t e_stage = nullptr;
-            if (g_trace && e == hipSuccess) { (void)hipEventCreate(&e_stage); (void)hipEventRecord(e_stage, up); }
-            auto mark = [&](hipStream_t st) { hipEvent_t ev = nullptr; (void)hipEventCreate(&ev); (void)hipEventRecord(ev, st); return ev; };
-            for (size_t f0 = 0; f0 < nf && !rc && e == hipSuccess;) {
-                size_t f1 = f0, acc = 0;
-                while (f1 < nf && acc < target) { if (fmt_of(parsed[f1]) == AFG_FORMAT_FLAC) acc += parsed[f1].flac.res_size(); f1++; }
-                size_t first = nf, last = nf;                // first / last FLAC file of the chunk
-                for (size_t i = f0; i < f1; i++)
-                    if (fmt_of(parsed[i]) == AFG_FORMAT_FLAC) { if (first == nf) first = i; last = i; }
-                if (first == nf) { f0 = f1; continue; }
-                ChunkTrace ct{};
-                ct.t_begin = since();
-                parallel_for(f1 - f0, threads, [&](size_t k) {
-                    const size_t i = f0 + k;
-                    Parsed &p = parsed[i];
-                    if (fmt_of(p) != AFG_FORMAT_FLAC) return;
-                    for (size_t q = 0; q < p.flac.frames.size(); q++) {
-                        afg_flac_frame f = p.flac.frames[q];
-                        f.in_off += (f.res16 ? 2 : 1) * (uint64_t)res_base[i]; f.out_off += out.files[i].pcm_off; f.sf_index += (uint32_t)sf_base[i];
-                        hf[fr_base[i] + q] = f;
-                    }
-                    std::memcpy(hs + sf_base[i], p.flac.subframes.data(), p.flac.subframes.size() * sizeof(afg_flac_subframe));
-                    if (!flac_staged) {
-                        std::memcpy(hr + res_base[i], p.flac.res_data(), p.flac.res_size() * 4);
-                        std::vector<int32_t>().swap(p.flac.res);       // the residual plane is the big one: drop it early
-                    }
-                });
-                const size_t fr0 = fr_base[first], fr1 = fr_base[last] + parsed[last].flac.frames.size();
-                const size_t sf0 = sf_base[first], sf1 = sf_base[last] + parsed[last].flac.subframes.size();
-                const size_t r0 = res_base[first];
-                size_t r1 = r0;
-                for (size_t q = fr0; q < fr1; q++)                           // (a packed frame keeps the words it was parsed into)
-                    r1 = std::max<size_t>(r1, (size_t)(hf[q].res16 ? hf[q].in_off / 2 : hf[q].in_off) + (size_t)hf[q].channels * hf[q].block_size);
-                const size_t o0 = out.files[first].pcm_off, o1 = out.files[last].pcm_off + parsed[last].flac.out_samples;
-                ct.t_gathered = since();
-                if (g_trace) ct.e_up0 = mark(up);
-                e = hipMemcpyAsync((void *)(df + fr0), hf + fr0, (fr1 - fr0) * sizeof(afg_flac_frame), hipMemcpyHostToDevice, up);
-                if (e == hipSuccess) e = hipMemcpyAsync((void *)(ds + sf0), hs + sf0, (sf1 - sf0) * sizeof(afg_flac_subframe), hipMemcpyHostToDevice, up);
-                if (e == hipSuccess) e = hipMemcpyAsync((void *)(dr + r0), hres + r0, (r1 - r0) * 4, hipMemcpyHostToDevice, up);
-                if (e != hipSuccess) break;
-                if (g_trace) ct.e_up1 = mark(up);
-                hipEvent_t landed = nullptr, done = nullptr;
-                e = hipEventCreateWithFlags(&landed, hipEventDisableTiming);
-                if (e != hipSuccess) break;
-                events.push_back(landed);
-                e = hipEventRecord(landed, up);
-                if (e == hipSuccess) e = hipStreamWaitEvent(mid, landed, 0);
-                if (e != hipSuccess) break;
-                // (the records are still here in host memory: only the populated instantiations are launched)
-                rc = afg_flac_transform_variants_hip(fr1 - fr0, df + fr0, ds, dr, f64 ? (int32_t *)d_out.p : nullptr, f64 ? nullptr : (float *)d_out.p,
-                                                     afg_flac_variants(fr1 - fr0, hf + fr0, hs), mid);
-                if (rc) break;
-                if (wide && (rc = convert(f64 ? AFG_F64_KIND_FLAC_S32 : AFG_WAV_KIND_F32, d_out.p, o0, o1 - o0, d_out64.p, runs_main, mid)) != AFG_OK) break;
-                if (g_trace) ct.e_k1 = mark(mid);
-                e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
-                if (e != hipSuccess) break;
-                events.push_back(done);
-                e = hipEventRecord(done, mid);
-                if (e == hipSuccess) e = hipStreamWaitEvent(down, done, 0);
-                if (g_trace) ct.e_d0 = mark(down);
-                if (e == hipSuccess && fetch)
-                    e = hipMemcpyAsync((uint8_t *)out.plane.p + o0 * es, (const uint8_t *)(wide ? d_out64.p : d_out.p) + o0 * es, (o1 - o0) * es, hipMemcpyDeviceToHost, down);
-                if (g_trace) { ct.e_d1 = mark(down); ct.t_queued = since(); ctrace.push_back(ct); }
-                f0 = f1;
-            }
-            const double t_loop = since();
-            if (up) { hipError_t e2 = hipStreamSynchronize(up); if (e == hipSuccess) e = e2; }
-            if (mid) { hipError_t e2 = hipStreamSynchronize(mid); if (e == hipSuccess) e = e2; }
-            const double t_up = since();
-            if (down) { hipError_t e2 = hipStreamSynchronize(down); if (e == hipSuccess) e = e2; }
-            if (g_trace) {
-                std::fprintf(stderr, "[afg] flac stage: loop done %.2f ms, up drained %.2f, down drained %.2f\n", t_loop, t_up, since());
-                for (size_t k = 0; k < ctrace.size(); k++) {
-                    const ChunkTrace &c = ctrace[k];
-                    float u0 = 0, u1 = 0, k1 = 0, d0 = 0, d1 = 0;
-                    (void)hipEventElapsedTime(&u0, e_stage, c.e_up0); (void)hipEventElapsedTime(&u1, e_stage, c.e_up1);
-                    (void)hipEventElapsedTime(&k1, e_stage, c.e_k1); (void)hipEventElapsedTime(&d0, e_stage, c.e_d0);
-                    (void)hipEventElapsedTime(&d1, e_stage, c.e_d1);
-                    std::fprintf(stderr, "[afg]   chunk %zu: host begin %.2f gathered %.2f queued %.2f | device up %.2f-%.2f kernel -%.2f down %.2f-%.2f\n",
-                                 k, c.t_begin, c.t_gathered, c.t_queued, u0, u1, k1, d0, d1);
-                    for (hipEvent_t ev : { c.e_up0, c.e_up1, c.e_k1, c.e_d0, c.e_d1 }) (void)hipEventDestroy(ev);
-                }
-                if (e_stage) (void)hipEventDestroy(e_stage);
-            }
-            for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
-            g_streams.give(up, down, mid);
-            if (rc) return rc;
-            if (e != hipSuccess) { afg::set_error("FLAC stage failed: %s", hipGetErrorString(e)); return AFG_ERR_HIP; }
-            tm.lap("flac gather | h2d | kernel | d2h (chunks overlapped)");
-        }
-        // ---- QOA ----
-        if (qoa_out) {
-            const size_t rec_pad = (qframes * sizeof(afg_qoa_frame) + 15) & ~(size_t)15;
-            StagingPool::Lease h_in;
-            DeviceBuf d_in;
-            if (int rc = g_staging.take(rec_pad + qbytes, h_in)) return rc;
-            if (int rc = d_in.alloc(rec_pad + qbytes)) return rc;
-            afg_qoa_frame *hq = (afg_qoa_frame *)h_in.p;
-            uint8_t *hb = (uint8_t *)h_in.p + rec_pad;
-            parallel_for(nf, threads, [&](size_t i) {
-                Parsed &p = parsed[i];
-                if (fmt_of(p) != AFG_FORMAT_QOA) return;
-                for (size_t k = 0; k < p.qoa.size(); k++) {
-                    afg_qoa_frame f = p.qoa[k];
-                    f.byte_off += qbyte_base[i]; f.out_off += out.files[i].pcm_off;
-                    hq[qfr_base[i] + k] = f;
-                }
-                std::memcpy(hb + qbyte_base[i], data[i], len[i]);
-            });
-            AFG_HIP_CHECK(hipMemcpyAsync(d_in.p, h_in.p, rec_pad + qbytes, hipMemcpyHostToDevice, stream));
-            if (int rc = afg_qoa_transform_hip(qframes, (const afg_qoa_frame *)d_in.p, (const uint8_t *)d_in.p + rec_pad, nullptr,
-                                               (float *)d_out.p, stream))
-                return rc;
-            if (wide) if (int rc = convert(AFG_WAV_KIND_F32, d_out.p, flac_out, qoa_out, d_out64.p, runs_main, stream)) return rc;
-            AFG_HIP_CHECK(hipStreamSynchronize(stream));
-        }
-        if (qoa_out && fetch) {                              // (the FLAC part came back chunk by chunk)
-            AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)out.plane.p + flac_out * es, (const uint8_t *)(wide ? d_out64.p : d_out.p) + flac_out * es, qoa_out * es,
-                                         hipMemcpyDeviceToHost, stream));
-            AFG_HIP_CHECK(hipStreamSynchronize(stream));
-        }
-        tm.lap("qoa stage");
-        // ---- MP3: spectra of every decoded granule -> PCM plane -> the samples mp3dec_ex_read would deliver ----
-        if (mp3_blocks && !staged) {
-            const size_t coef_bytes = mp3_blocks * 576 * sizeof(float), flag_bytes = (mp3_blocks * 4 + 15) & ~(size_t)15;
-            DeviceBuf d_in, d_pcm;
-            DeviceBuf &d_pcm64 = d_mp3_64;
-            if (int rc = d_in.alloc(coef_bytes + flag_bytes)) return rc;
-            if (int rc = d_pcm.alloc(coef_bytes)) return rc;
-            if (wide && fetch) if (int rc = d_pcm64.alloc(std::max<size_t>(mp3_blocks * 576 * es, 16))) return rc;
-            // The files are cut into a few chunks of similar size, each with its own plan: the upload and kernel of
-            // chunk k+1 (stream `up`) run while chunk k's PCM goes back (stream `down`) -- PCIe is full duplex.
-            struct Chunk { size_t f0, f1, blk0, blocks; afg_mp3_plan *plan; hipEvent_t done; size_t runs = 0; };
-            std::vector<Chunk> chunks;
-            {
-                size_t want = 8;
-                if (afg::dev_option(afg::kDevMp3Chunks) > 0) want = (size_t)afg::dev_option(afg::kDevMp3Chunks);
-                const size_t target = std::max<size_t>((mp3_blocks + want - 1) / want, 8192);
-                Chunk c{ 0, 0, 0, 0, nullptr, nullptr, 0 };
-                for (size_t i = 0; i < nf; i++) {
-                    if (fmt_of(parsed[i]) != AFG_FORMAT_MP3) continue;
-                    if (c.blocks == 0) { c.f0 = i; c.blk0 = mp3_blk_base[i]; }
-                    c.blocks += parsed[i].mp3.blocks();
-                    c.f1 = i + 1;
-                    if (c.blocks >= target) { chunks.push_back(c); c = Chunk{ 0, 0, 0, 0, nullptr, nullptr, 0 }; }
-                }
-                if (c.blocks) chunks.push_back(c);
-            }
-            StagingPool::Lease hfl_lease;                    // page-locked: the flag words travel asynchronously too
-            if (int rc = g_staging.take(mp3_blocks * sizeof(uint32_t), hfl_lease)) return rc;
-            uint32_t *hfl = (uint32_t *)hfl_lease.p;
-            hipStream_t up = nullptr, down = nullptr;
-            hipError_t e = g_streams.take(&up, &down);
-            int rc = AFG_OK;
-            for (Chunk &c : chunks) {                        // plans first: their tables are uploaded synchronously
-                if (rc || e != hipSuccess) break;
-                std::vector<uint32_t> granules;
-                std::vector<uint8_t> channels;
-                for (size_t i = c.f0; i < c.f1; i++) {
-                    const Parsed &p = parsed[i];
-                    if (fmt_of(p) != AFG_FORMAT_MP3) continue;
-                    for (uint32_t g : p.mp3.run_granules) {
-                        granules.push_back(g);
-                        channels.push_back((uint8_t)p.mp3.channels);
-                    }
-                    if (p.mp3.blocks()) std::memcpy(hfl + mp3_blk_base[i], p.mp3_flags(), p.mp3.blocks() * sizeof(uint32_t));
-                }
-                rc = afg_mp3_plan_create(&c.plan, (uint32_t)granules.size(), granules.data(), channels.data(), 0);
-                if (!rc) e = hipEventCreateWithFlags(&c.done, hipEventDisableTiming);
-                c.runs = granules.size();
-            }
-            tm.lap("mp3 plans");
-            uint32_t *d_flags = (uint32_t *)((uint8_t *)d_in.p + coef_bytes);
-            for (Chunk &c : chunks) {
-                if (rc || e != hipSuccess) break;
-                for (size_t i = c.f0; i < c.f1 && e == hipSuccess; i++) {
-                    const Parsed &p = parsed[i];
-                    if (fmt_of(p) != AFG_FORMAT_MP3 || !p.mp3.blocks()) continue;
-                    // the batch path parsed this file straight into page-locked staging: one asynchronous copy per file
-                    // into the packed device plane (a file parsed on its own comes from ordinary memory)
-                    e = hipMemcpyAsync((float *)d_in.p + mp3_blk_base[i] * 576, p.mp3_coef(), p.mp3.blocks() * 576 * sizeof(float),
-                                       hipMemcpyHostToDevice, up);
-                }
-                if (e == hipSuccess)
-                    e = hipMemcpyAsync(d_flags + c.blk0, hfl + c.blk0, c.blocks * sizeof(uint32_t), hipMemcpyHostToDevice, up);
-                if (e != hipSuccess) break;
-                // chunked stream: one state blob per run of the chunk, zero (a fresh decoder) except the first when the chunk
-                // goes on from the previous one; the last run's blob is what the next chunk goes on from
-                DeviceBuf d_states;
-                float *states = nullptr;
-                if (carry && chunks.size() == 1 && c.runs) {
-                    const size_t sb = AFG_MP3_STATE_FLOATS * sizeof(float);
-                    if ((rc = d_states.alloc(c.runs * sb)) != AFG_OK) break;
-                    states = (float *)d_states.p;
-                    e = hipMemsetAsync(states, 0, c.runs * sb, up);
-                    if (e == hipSuccess && carry->continues && carry->valid)
-                        e = hipMemcpyAsync(states, carry->state.p, sb, hipMemcpyDeviceToDevice, up);
-                    if (e != hipSuccess) break;
-                }
-                rc = afg_mp3_transform_hip(c.plan, (const float *)d_in.p + c.blk0 * 576, d_flags + c.blk0,
-                                           (float *)d_pcm.p + c.blk0 * 576, states, up);
-                if (rc) break;
-                if (states) {
-                    const size_t sb = AFG_MP3_STATE_FLOATS * sizeof(float);
-                    if (!carry->state.p && (rc = carry->state.alloc(sb)) != AFG_OK) break;
-                    e = hipMemcpyAsync(carry->state.p, states + (c.runs - 1) * AFG_MP3_STATE_FLOATS, sb, hipMemcpyDeviceToDevice, up);
-                    if (e == hipSuccess) e = hipStreamSynchronize(up);          // d_states goes out of scope below
-                    if (e != hipSuccess) break;
-                    carry->valid = true;
-                }
-                if (wide && (rc = convert(AFG_WAV_KIND_F32, d_pcm.p, c.blk0 * 576, c.blocks * 576, d_pcm64.p, runs_mp3, up)) != AFG_OK) break;
-                e = hipEventRecord(c.done, up);
-                if (e == hipSuccess) e = hipStreamWaitEvent(down, c.done, 0);
-                // delivery: the copy plan of each file, merged into maximal contiguous pieces (one per undamaged file),
-                // straight from the device PCM plane into the page-locked result plane
-                for (size_t i = c.f0; i < c.f1 && e == hipSuccess && fetch; i++) {
-                    const Parsed &p = parsed[i];
-                    if (fmt_of(p) != AFG_FORMAT_MP3) continue;
-                    const uint8_t *src = (const uint8_t *)(wide ? d_pcm64.p : d_pcm.p) + mp3_blk_base[i] * 576 * es;
-                    uint8_t *dst = (uint8_t *)out.plane.p + out.files[i].pcm_off * es;
-                    const std::vector<afg_mp3::Copy> &cp = p.mp3.copies;
-                    for (size_t k = 0; k < cp.size() && e == hipSuccess;) {
-                        uint64_t from = cp[k].src, cnt = cp[k].count;
-                        size_t j = k + 1;
-                        while (j < cp.size() && cp[j].src == from + cnt) cnt += cp[j++].count;
-                        e = hipMemcpyAsync(dst, src + from * es, (size_t)cnt * es, hipMemcpyDeviceToHost, down);
-                        dst += cnt * es;
-                        k = j;
-                    }
-                }
-            }
-            if (up) { hipError_t e2 = hipStreamSynchronize(up); if (e == hipSuccess) e = e2; }
-            if (down) { hipError_t e2 = hipStreamSynchronize(down); if (e == hipSuccess) e = e2; }
-            for (Chunk &c : chunks) {
-                if (c.plan) afg_mp3_plan_destroy(c.plan);
-                if (c.done) (void)hipEventDestroy(c.done);
-            }
-            g_streams.give(up, down);
-            tm.lap("mp3 h2d | kernel | d2h (chunks overlapped)");
-            if (rc) return rc;
-            if (e != hipSuccess) { afg::set_error("MP3 stage failed: %s", hipGetErrorString(e)); return AFG_ERR_HIP; }
-            tm.lap("mp3 delivery copies");
-        }
-        // ---- Vorbis: per chunk gather (host threads) -> upload + kernel on `up` -> download on `down` ----
-        if (!ogg.v.empty()) {
-            StagingPool::Lease h_spec;
-            DeviceBuf d_spec, d_pcm;
-            DeviceBuf &d_pcm64 = d_ogg_64;
-            if (wide && fetch) if (int rc = d_pcm64.alloc(std::max<size_t>(ogg_out * es, 16))) return rc;
-            if (!ogg_staged)
-                if (int rc = g_staging.take(ogg_spec * sizeof(float), h_spec)) return rc;
-            if (int rc = d_spec.alloc((ogg_staged ? ogg_stage->floats : ogg_spec) * sizeof(float))) return rc;
-            if (int rc = d_pcm.alloc(ogg_out * sizeof(float))) return rc;
-            uint8_t *ogg_plane = (uint8_t *)out.plane.p + (flac_out + qoa_out + mp3_out) * es;
-            hipStream_t up = nullptr, down = nullptr;
-            hipError_t e = g_streams.take(&up, &down);
-            int rc = AFG_OK;
-            // Files parsed with the floor left to the device: their packets' coupling / floor records go up
-            // with the chunk (one page-locked block: packets, curves, points, steps of chunk after chunk) and
-            // afg_vorbis_floor_hip turns the residue vectors into spectra in place, in front of the transform.
-            std::vector<size_t> f_pk(nf + 1, 0), f_cv(nf + 1, 0), f_pt(nf + 1, 0), f_st(nf + 1, 0);
-            for (size_t i = 0; i < nf; i++) {
-                const bool on = fmt_of(parsed[i]) == AFG_FORMAT_OGG && parsed[i].ogg.device_floor;
-                f_pk[i + 1] = f_pk[i] + (on ? parsed[i].ogg.fl_packets.size() : 0);
-                f_cv[i + 1] = f_cv[i] + (on ? parsed[i].ogg.fl_curves.size() : 0);
-                f_pt[i + 1] = f_pt[i] + (on ? parsed[i].ogg.fl_points.size() / 2 : 0);
-                f_st[i + 1] = f_st[i] + (on ? parsed[i].ogg.fl_steps.size() / 2 : 0);
-            }
-            const size_t fl_pk_bytes = f_pk[nf] * sizeof(afg_vorbis_floor_packet), fl_cv_bytes = f_cv[nf] * sizeof(afg_vorbis_floor_curve),
-                         fl_pt_bytes = f_pt[nf] * 8, fl_st_bytes = f_st[nf] * 2;
-            const size_t fl_bytes = fl_pk_bytes + fl_cv_bytes + fl_pt_bytes + fl_st_bytes;
-            StagingPool::Lease h_fl;
-            DeviceBuf d_fl;
-            if (f_pk[nf]) {
-                if (int rc2 = g_staging.take(fl_bytes, h_fl)) return rc2;
-                if (int rc2 = d_fl.alloc(fl_bytes)) return rc2;
-            }
-            auto fl_at = [&](void *base0, int which, size_t index) -> uint8_t * {   // 0 packets, 1 curves, 2 points, 3 steps
-                uint8_t *b = (uint8_t *)base0;
-                if (which == 0) return b + index * sizeof(afg_vorbis_floor_packet);
-                if (which == 1) return b + fl_pk_bytes + index * sizeof(afg_vorbis_floor_curve);
-                if (which == 2) return b + fl_pk_bytes + fl_cv_bytes + index * 8;
-                return b + fl_pk_bytes + fl_cv_bytes + fl_pt_bytes + index * 2;
-            };
-            for (size_t ci = 0; ci < ogg.v.size(); ci++) {
-                OggChunk &c = ogg.v[ci];
-                if (rc || e != hipSuccess) break;
-                const float *hs = ogg_staged ? ogg_stage->spec + c.spec0 : (const float *)h_spec.p + c.spec0;
-                const size_t npk_c = f_pk[c.f1] - f_pk[c.f0];
-                if (npk_c) {
-                    parallel_for(c.f1 - c.f0, threads, [&](size_t k) {
-                        const size_t i = c.f0 + k;
-                        const Parsed &p = parsed[i];
-                        if (f_pk[i + 1] == f_pk[i]) return;
-                        // chunk-local indices (the kernel gets the chunk's slices), absolute spectrum offsets
-                        const size_t spec_base = ogg_staged ? ogg_stage->base[i] : c.spec0 + c.spec_at[k];
-                        afg_vorbis_floor_packet *pk = (afg_vorbis_floor_packet *)fl_at(h_fl.p, 0, f_pk[i]);
-                        for (size_t q = 0; q < p.ogg.fl_packets.size(); q++) {
-                            afg_vorbis_floor_packet r = p.ogg.fl_packets[q];
-                            r.spec_off += spec_base;
-                            r.curve_index += (uint32_t)(f_cv[i] - f_cv[c.f0]);
-                            r.step_off += (uint32_t)(f_st[i] - f_st[c.f0]);
-                            pk[q] = r;
-                        }
-                        afg_vorbis_floor_curve *cv = (afg_vorbis_floor_curve *)fl_at(h_fl.p, 1, f_cv[i]);
-                        for (size_t q = 0; q < p.ogg.fl_curves.size(); q++) {
-                            afg_vorbis_floor_curve r = p.ogg.fl_curves[q];
-                            r.point_off += (uint32_t)(f_pt[i] - f_pt[c.f0]);
-                            cv[q] = r;
-                        }
-                        if (!p.ogg.fl_points.empty()) std::memcpy(fl_at(h_fl.p, 2, f_pt[i]), p.ogg.fl_points.data(), p.ogg.fl_points.size() * sizeof(int32_t));
-                        if (!p.ogg.fl_steps.empty()) std::memcpy(fl_at(h_fl.p, 3, f_st[i]), p.ogg.fl_steps.data(), p.ogg.fl_steps.size());
-                    });
-                }
-                if (!ogg_staged) {
-                    float *hw = (float *)h_spec.p + c.spec0;
-                    parallel_for(c.f1 - c.f0, threads, [&](size_t k) {
-                        Parsed &p = parsed[c.f0 + k];
-                        if (fmt_of(p) != AFG_FORMAT_OGG || !p.ogg.n_spec) return;
-                        std::memcpy(hw + c.spec_at[k], p.ogg.spectra(), p.ogg.n_spec * sizeof(float));
-                        std::vector<float>().swap(p.ogg.spec);         // the big one: released here, by many threads
-                    });
-                }
-                e = hipMemcpyAsync((float *)d_spec.p + c.spec0, hs, c.spec_n * sizeof(float), hipMemcpyHostToDevice, up);
-                if (e != hipSuccess) break;
-                if (npk_c) {
-                    const struct { int which; size_t i0, i1, unit; } part[4] = {
-                        { 0, f_pk[c.f0], f_pk[c.f1], sizeof(afg_vorbis_floor_packet) }, { 1, f_cv[c.f0], f_cv[c.f1], sizeof(afg_vorbis_floor_curve) },
-                        { 2, f_pt[c.f0], f_pt[c.f1], 8 }, { 3, f_st[c.f0], f_st[c.f1], 2 } };
-                    for (const auto &pt : part) {
-                        if (pt.i1 == pt.i0 || e != hipSuccess) continue;
-                        e = hipMemcpyAsync(fl_at(d_fl.p, pt.which, pt.i0), fl_at(h_fl.p, pt.which, pt.i0), (pt.i1 - pt.i0) * pt.unit, hipMemcpyHostToDevice, up);
-                    }
-                    if (e != hipSuccess) break;
-                    rc = afg_vorbis_floor_hip(npk_c, (const afg_vorbis_floor_packet *)fl_at(d_fl.p, 0, f_pk[c.f0]),
-                                              (const afg_vorbis_floor_curve *)fl_at(d_fl.p, 1, f_cv[c.f0]), (const int32_t *)fl_at(d_fl.p, 2, f_pt[c.f0]),
-                                              (const uint8_t *)fl_at(d_fl.p, 3, f_st[c.f0]), (float *)d_spec.p, up);
-                    if (rc) break;
-                }
-                // a staged plan addresses the staging layout from float 0; a gathered one is packed from its chunk's start
-                rc = afg_vorbis_transform_hip(c.plan, (const float *)d_spec.p + (ogg_staged ? 0 : c.spec0), (float *)d_pcm.p + c.out0, up);
-                if (rc) break;
-                if (wide && (rc = convert(AFG_WAV_KIND_F32, d_pcm.p, c.out0, c.out_n, d_pcm64.p, runs_ogg, up)) != AFG_OK) break;
-                e = hipEventCreateWithFlags(&c.done, hipEventDisableTiming);
-                if (e == hipSuccess) e = hipEventRecord(c.done, up);
-                if (e == hipSuccess) e = hipStreamWaitEvent(down, c.done, 0);
-                if (e == hipSuccess && fetch)
-                    e = hipMemcpyAsync(ogg_plane + c.out0 * es, (const uint8_t *)(wide ? d_pcm64.p : d_pcm.p) + c.out0 * es, c.out_n * es, hipMemcpyDeviceToHost, down);
-            }
-            if (up) { hipError_t e2 = hipStreamSynchronize(up); if (e == hipSuccess) e = e2; }
-            if (down) { hipError_t e2 = hipStreamSynchronize(down); if (e == hipSuccess) e = e2; }
-            g_streams.give(up, down);
-            if (rc) return rc;
-            if (e != hipSuccess) { afg::set_error("Vorbis stage failed: %s", hipGetErrorString(e)); return AFG_ERR_HIP; }
-            // files delivered as several runs (seek-style trims, damaged streams): close the runs up, in place
-            for (size_t bi = 0, at = 0; bi < ogg_broken.size() && fetch; bi++) {
-                const size_t i = ogg_broken[bi];
-                while (at < ogg_pieces.size() && ogg_pieces[at].file != i) at++;
-                uint8_t *dst = (uint8_t *)out.plane.p + out.files[i].pcm_off * es;
-                for (; at < ogg_pieces.size() && ogg_pieces[at].file == i; at++) {
-                    const uint8_t *src = ogg_plane + ogg_pieces[at].from * es;
-                    if (dst != src) std::memmove(dst, src, (size_t)ogg_pieces[at].count * es);
-                    dst += ogg_pieces[at].count * es;
-                }
-            }
-            tm.lap("vorbis gather | h2d | kernel | d2h (chunks overlapped)");
-        }
-        // ---- Opus (CELT): records + coefficients -> transform -> gain / int16 round trip -> result plane ----
-        if (opus_out) {
-            if (opus_seqs > 0xffffffffull) { afg::set_error("Opus stage: too many channel sequences"); return AFG_ERR_INVALID; }
-            const size_t base_bytes = ((opus_seqs + 1) * sizeof(uint64_t) + 15) & ~(size_t)15;
-            const size_t rec_bytes = (opus_recs * sizeof(afg_celt_frame) + 15) & ~(size_t)15;
-            StagingPool::Lease h_in;
-            DeviceBuf d_in, d_pcm;
-            DeviceBuf &d_pcm64 = d_opus_64;
-            if (wide && fetch) if (int rc = d_pcm64.alloc(std::max<size_t>(opus_out * es, 16))) return rc;
-            if (int rc = g_staging.take(base_bytes + rec_bytes + opus_coefs * sizeof(float), h_in)) return rc;
-            if (int rc = d_in.alloc(base_bytes + rec_bytes + opus_coefs * sizeof(float))) return rc;
-            if (int rc = d_pcm.alloc(opus_out * sizeof(float))) return rc;
-            uint64_t *hb = (uint64_t *)h_in.p;
-            afg_celt_frame *hr = (afg_celt_frame *)((uint8_t *)h_in.p + base_bytes);
-            float *hc = (float *)((uint8_t *)h_in.p + base_bytes + rec_bytes);
-            {
-                size_t seq = 0;
-                for (size_t i = 0; i < nf; i++) {
-                    const Parsed &p = parsed[i];
-                    if (fmt_of(p) != AFG_FORMAT_OPUS) continue;
-                    if (p.opus.channels == 2 && (seq & 1)) hb[seq++] = opus_rec_base[i];          // the empty sequence (above)
-                    for (int c = 0; c < p.opus.channels; c++) hb[seq++] = opus_rec_base[i] + (size_t)c * p.opus.frames.size();
-                }
-                hb[seq] = opus_recs;
-            }
-            parallel_for(nf, threads, [&](size_t i) {
-                Parsed &p = parsed[i];
-                if (fmt_of(p) != AFG_FORMAT_OPUS) return;
-                const size_t n = p.opus.frames.size();
-                for (int c = 0; c < p.opus.channels; c++)
-                    for (size_t k = 0; k < n; k++) {
-                        afg_celt_frame f = p.opus.frames[k];
-                        f.coef_off += opus_coef_base[i] + (uint64_t)c * f.frame_size;
-                        f.out_off += opus_pcm_base[i] + (uint64_t)c;
-                        hr[opus_rec_base[i] + (size_t)c * n + k] = f;
-                    }
-                if (!p.opus.coeffs.empty()) std::memcpy(hc + opus_coef_base[i], p.opus.coeffs.data(), p.opus.coeffs.size() * sizeof(float));
-                std::vector<float>().swap(p.opus.coeffs);
-            });
-            AFG_HIP_CHECK(hipMemcpyAsync(d_in.p, h_in.p, base_bytes + rec_bytes + opus_coefs * sizeof(float), hipMemcpyHostToDevice, stream));
-            // chunked stream (one file): the channel states live on the device between chunks, zero for a fresh decoder
-            float *states = nullptr;
-            if (opus_carry) {
-                const size_t sb = opus_seqs * AFG_CELT_STATE_FLOATS * sizeof(float);
-                if (!opus_carry->states.p) {
-                    if (int rc = opus_carry->states.alloc(sb)) return rc;
-                    opus_carry->valid = false;
-                }
-                if (!opus_carry->valid) AFG_HIP_CHECK(hipMemsetAsync(opus_carry->states.p, 0, sb, stream));
-                opus_carry->valid = true;
-                states = (float *)opus_carry->states.p;
-            }
-            if (int rc = afg_celt_transform_hip((uint32_t)opus_seqs, (const uint64_t *)d_in.p, (const afg_celt_frame *)((const uint8_t *)d_in.p + base_bytes),
-                                                (const float *)((const uint8_t *)d_in.p + base_bytes + rec_bytes), (float *)d_pcm.p, states, stream))
-                return rc;
-            // output gain (when the file asks for one) and the reference's int16 round trip, in place
-            bool any_gain = false;
-            for (size_t i = 0; i < nf; i++) any_gain = any_gain || (fmt_of(parsed[i]) == AFG_FORMAT_OPUS && parsed[i].opus.gain_i != 0);
-            if (!any_gain) {
-                if (int rc = afg_opus_output_hip(opus_out, (const float *)d_pcm.p, nullptr, (float *)d_pcm.p, stream)) return rc;
-            } else {
-                for (size_t i = 0; i < nf; i++) {
-                    const Parsed &p = parsed[i];
-                    if (fmt_of(p) != AFG_FORMAT_OPUS) continue;
-                    float *at = (float *)d_pcm.p + opus_pcm_base[i];
-                    const uint64_t n = p.opus.pcm_frames * (uint64_t)p.opus.channels;
-                    const int rc = p.opus.gain_i ? afg_opus_output_gain_hip(n, at, p.opus.gain, nullptr, at, stream)
-                                                 : afg_opus_output_hip(n, at, nullptr, at, stream);
-                    if (rc) return rc;
-                }
-            }
-            if (wide) if (int rc = convert(AFG_WAV_KIND_F32, d_pcm.p, 0, opus_out, d_pcm64.p, runs_opus, stream)) return rc;
-            if (fetch)
-                AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)out.plane.p + (flac_out + qoa_out + mp3_out + ogg_out) * es, wide ? d_pcm64.p : d_pcm.p, opus_out * es,
-                                             hipMemcpyDeviceToHost, stream));
-            AFG_HIP_CHECK(hipStreamSynchronize(stream));
-            tm.lap("opus gather | h2d | kernel | d2h");
-        }
-        drain.on = false;                                    // every stage has drained its own streams
-    }
-metadata:
-    for (size_t i = 0; i < nf; i++) {
-        Parsed &p = parsed[i];
-        Decoded &dcd = out.files[i];
-        dcd.format = fmt_of(p);
-        if (fmt_of(p) == AFG_FORMAT_FLAC) {
+    for (size_t i = 0; i < ctx.nf(); i++) {
+        Parsed &p = ctx.parsed[i];
+        Decoded &dcd = ctx.out.files[i];
+        const int fmt = dcd.format = ctx.fmt_of(i);
+        if (fmt == AFG_FORMAT_FLAC) {
             dcd.channels = (int)p.fi.channels;
             dcd.samplerate = (float)p.fi.sample_rate;
             dcd.frames = (int64_t)(p.flac.out_samples / p.fi.channels);
             dcd.declared_frames = (int64_t)p.fi.total_samples;      // totalSampleCount / channels, stream.d:1631
-        } else if (fmt_of(p) == AFG_FORMAT_MP3) {
+        } else if (fmt == AFG_FORMAT_MP3) {
             dcd.channels = p.mp3.channels;
             dcd.samplerate = (float)p.mp3.hz;
             dcd.frames = (int64_t)(p.mp3.pcm_samples / (uint64_t)p.mp3.channels);
             dcd.declared_frames = (int64_t)(p.mp3.declared_samples / (uint64_t)p.mp3.channels);   // stream.d:1737
-        } else if (fmt_of(p) == AFG_FORMAT_OGG) {
+        } else if (fmt == AFG_FORMAT_OGG) {
             dcd.channels = p.ogg.channels;
             dcd.samplerate = (float)p.ogg.sample_rate;
             dcd.frames = (int64_t)p.ogg.pcm_frames;
             dcd.declared_frames = (int64_t)p.ogg.total_samples;    // stb_vorbis_stream_length_in_samples, stream.d:1696
-        } else if (fmt_of(p) == AFG_FORMAT_OPUS) {
+        } else if (fmt == AFG_FORMAT_OPUS) {
             dcd.channels = p.opus.channels;
             dcd.samplerate = 48000.0f;                              // OpusFileCtx.rate (dopus.d:7973)
             dcd.declared_frames = p.opus.declared_frames;           // smpduration(), stream.d:1609
@@ -1432,7 +389,7 @@ metadata:
                 dcd.status = AFG_ERR_INVALID;
                 dcd.message = kErrorDecoderInitializationFailed;    // (the string stream.d:454 sets)
             }
-        } else if (fmt_of(p) == AFG_FORMAT_QOA) {
+        } else if (fmt == AFG_FORMAT_QOA) {
             dcd.channels = (int)p.qi.channels;
             dcd.samplerate = (float)p.qi.samplerate;
             dcd.frames = (int64_t)(p.qoa.back().out_off / p.qi.channels) + p.qoa.back().samples;
@@ -1442,6 +399,53 @@ metadata:
             dcd.message = p.opus_mode ? kErrorOpusMode : kErrorUnknownFormat;
         }
     }
+}
+
+// The device stages for a set of parsed files (afg_batch.h), each handed in with its optional inputs set: every FLAC record
+// of the batch in one stage, every QOA frame in another, and so on; the results come back as one plane, laid out FLAC,
+// QOA, MP3, Vorbis, Opus.
+// so.f64() (afg_read_samples_double, afg_batch_opts.sample_type): the result plane holds doubles.  Every stage's device plane
+// -- int32 for FLAC, float for the others -- is widened by afg_pcm_to_f64_hip behind the stage's kernels, on their
+// stream, and the doubles are what comes back.  The batch path's MP3 and Opus planes were widened by their own pipelines.
+// AFG_SAMPLE_PCM_* (afg_batch_opts.sample_type): the result plane holds samples of 1, 2 or 3 bytes, packed from every
+// stage's float plane by afg_pcm_pack_hip at the same place; FLAC restores to float as for a float read.
+// Collate mode (afg_batch_decode_to_device): there is no result plane.  afg_collate_hip scatters every stage's float plane
+// into the caller's tensor where the other types convert, and the downloads are left out; parsed[i] is batch file i.
+int decode_parsed(StageCtx &ctx, FlacDecode &flac, Mp3Decode &mp3, VorbisDecode &ogg, OpusDecode &opus)
+{
+    const SampleOut &so = ctx.so;
+    if (mp3.staged && mp3.staged->blocks && mp3.staged->so != so) { afg::set_error("decode_parsed: the MP3 stage's sample type differs"); return AFG_ERR_INVALID; }
+    BatchOut &out = ctx.out;
+    out.f64 = so.f64();
+    out.files.assign(ctx.nf(), Decoded());
+    QoaDecode qoa;
+    size_t at = flac.layout(ctx, 0);
+    at += qoa.layout(ctx, at);
+    const size_t main_floats = at;                           // FLAC and QOA: converted in place of the plane
+    at += mp3.layout(ctx, at);
+    size_t ogg_floats = 0;
+    if (int rc = ogg.layout(ctx, at, &ogg_floats)) return rc;
+    at += ogg_floats;
+    mp3.deliver_in_place(ctx);
+    at += opus.layout(ctx, at);
+    out.plane_floats = at;
+    if (out.plane_floats) {
+        if (so.fetch()) if (int rc = staging_take(out.plane_floats * so.es(), out.plane)) return rc;
+        ctx.tm.lap("layout + plane alloc");
+        // (the converted planes and the conversion records live out here and in the stages the caller holds: on an early way
+        //  out of a stage they are let go only after the device has drained, below them)
+        StageDev dev;
+        if (int rc = dev.d_out.alloc(out.plane_floats * sizeof(float))) return rc;
+        if (so.wide() && so.fetch()) if (int rc = dev.d_out64.alloc(std::max<size_t>(main_floats * so.es(), 16))) return rc;
+        struct Drain { bool on; ~Drain() { if (on) (void)hipDeviceSynchronize(); } } drain{ so.wide() };
+        if (int rc = flac.run(ctx, dev)) return rc;
+        if (int rc = qoa.run(ctx, dev)) return rc;
+        if (int rc = mp3.run(ctx, dev)) return rc;
+        if (int rc = ogg.run(ctx, dev)) return rc;
+        if (int rc = opus.run(ctx, dev)) return rc;
+        drain.on = false;                                    // every stage has drained its own streams
+    }
+    fill_metadata(ctx);
     return AFG_OK;
 }
 
@@ -1531,8 +535,8 @@ struct afg_stream {
         Parsed &p = parsed[0];
         const uint8_t *dp[1] = { bytes.data() };
         size_t lp[1] = { bytes.size() };
-        Mp3Carry *cr = nullptr;
-        OpusCarry *ocr = nullptr;
+        Mp3Decode mp3_stage;
+        OpusDecode opus_stage;
         if (format == AFG_FORMAT_OPUS) {
             if (opus_failed) { error = kErrorDecoderInitializationFailed; ended = true; return false; }      // stream.d:454
             if (opus_decoded >= declared_frames || !opus->more(p.opus, kOpusPackets)) { ended = true; return false; }
@@ -1544,7 +548,7 @@ struct afg_stream {
             p.opus.gain = opus_gain;
             p.opus.declared_frames = declared_frames - opus_decoded;
             opus_decoded += (int64_t)p.opus.pcm_frames;
-            ocr = &opus_carry;
+            opus_stage.carry = &opus_carry;
             p.format = AFG_FORMAT_OPUS;
         } else if (format == AFG_FORMAT_FLAC) {
             bool done = false;
@@ -1578,15 +582,17 @@ struct afg_stream {
             bool continues = false;
             if (!mp3->more(p.mp3, kMp3Frames, &continues)) { ended = true; return false; }
             carry.continues = continues;
-            cr = &carry;
+            mp3_stage.carry = &carry;
             p.format = AFG_FORMAT_MP3;
         } else {
             ended = true;
             return false;
         }
         BatchOut out;
-        if (decode_parsed(parsed, dp, lp, 1, out, nullptr, nullptr, nullptr, nullptr, cr, ocr, nullptr, fifo_es == sizeof(double)) != AFG_OK ||
-            out.files[0].status != AFG_OK) {
+        StageCtx ctx = stage_ctx(parsed, dp, lp, nullptr, 1, fifo_es == sizeof(double), out);
+        FlacDecode flac_stage;
+        VorbisDecode ogg_stage;
+        if (decode_parsed(ctx, flac_stage, mp3_stage, ogg_stage, opus_stage) != AFG_OK || out.files[0].status != AFG_OK) {
             error = kErrorDecodingError;
             ended = true;
             return false;
@@ -2241,8 +1247,8 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
     // samples, made on the device
     // Collate mode: nothing comes back.  Every stage scatters its chunks into so.d_out; what the files did not fill is written
     // as zero runs at the end, when every file's delivered length is known, and the items point at the slabs.
-    const bool f64 = so.f64(), wide = so.wide(), fetch = so.fetch();
-    const size_t es = so.es();
+        const bool fetch = so.fetch();
+        const size_t es = so.es();
     {
         if (int rc = afg::require_device()) return rc;
         int cur_dev = 0;
@@ -2288,10 +1294,10 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
             flac_base[i] = flac_total; flac_total += (flac_bound[i] + 3) & ~(size_t)3;        // 16-byte aligned planes
         }
         // pass 1b: FLAC files of known length straight into one page-locked residual buffer
-        StagingPool::Lease flac_lease;
+        StagingLease flac_lease;
         FlacStage flac_stage;
         if (flac_total) {
-            if (int rc = g_staging.take(flac_total * sizeof(int32_t), flac_lease)) return rc;
+            if (int rc = staging_take(flac_total * sizeof(int32_t), flac_lease)) return rc;
             int32_t *res0 = (int32_t *)flac_lease.p;
             std::atomic<bool> lost{ false };
             parallel_for((size_t)n_files, nt, [&](size_t i) {
@@ -2322,189 +1328,10 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
         BatchOut *owner = new (std::nothrow) BatchOut;
         if (!owner) return AFG_ERR_OOM;
         std::unique_ptr<BatchOut> guard(owner);
-        // ---- pass 1c: Ogg Opus.  The open scan gave exact sizes, so every file is decoded (range decoder + CELT frame decoder,
-        // by all helper threads) straight into one page-locked buffer, a chunk of files at a time; the chunk's upload, transform,
-        // output conversion and download are queued on two streams and run while the helpers decode the next chunk.
-        std::vector<size_t> opus_pcm_at((size_t)n_files, 0);
+        // ---- pass 1c: Ogg Opus, decoded by all helper threads and queued chunk by chunk (afg_opus_stage.cpp)
+        std::vector<size_t> opus_pcm_at;
         bool opus_staged = false;
-        {
-            size_t n_opus = 0, recs_total = 0, coefs_total = 0, seqs_total = 0;
-            std::vector<size_t> rec_at((size_t)n_files, 0), coef_at((size_t)n_files, 0), seq_at((size_t)n_files, 0);
-            for (size_t i = 0; i < (size_t)n_files; i++) {
-                if (!opus_open[i]) continue;
-                const afg_opus::File &m = parsed[i].opus;
-                rec_at[i] = recs_total; coef_at[i] = coefs_total;
-                opus_pcm_at[i] = coefs_total;                     // one PCM float per coefficient
-                recs_total += m.bound_frames * (size_t)m.channels;
-                coefs_total += m.bound_coeffs;
-                n_opus++;
-            }
-            // Channel sequences.  The transform stage walks sequences 2p and 2p + 1 of a launch together when they are the two
-            // channels of a stream (one wavefront, half each: afg.h), so a stereo file starts on an even index of its launch:
-            // an empty sequence goes in front of it after an odd number of mono files, and in front of a chunk (a launch, below)
-            // that would start on an odd one.  Without it such a file is walked one channel at a time -- slower, and in
-            // AFG_NUMERIC_TOLERANCE to samples that depend on what else is in the batch (tools/soak_damaged.py found one).
-            const size_t target = std::max<size_t>((coefs_total + 7) / 8, (size_t)stage_chunk_samples((size_t)4 << 20));      // coefficients per chunk
-            std::vector<uint8_t> seq_pad((size_t)n_files, 0);
-            for (size_t f0 = 0; f0 < (size_t)n_files;) {
-                size_t f1 = f0, acc = 0;
-                while (f1 < (size_t)n_files && acc < target) { if (opus_open[f1]) acc += parsed[f1].opus.bound_coeffs; f1++; }
-                bool first = true;
-                for (size_t i = f0; i < f1; i++) {
-                    if (!opus_open[i]) continue;
-                    const size_t C = (size_t)parsed[i].opus.channels;
-                    if ((seqs_total & 1) && (first || C == 2)) { seq_pad[i] = 1; seqs_total++; }
-                    seq_at[i] = seqs_total;
-                    seqs_total += C;
-                    first = false;
-                }
-                f0 = f1;
-            }
-            if (n_opus && seqs_total <= 0xffffffffull) {
-                const size_t base_bytes = ((seqs_total + 1) * sizeof(uint64_t) + 15) & ~(size_t)15;
-                const size_t rec_bytes = (recs_total * sizeof(afg_celt_frame) + 15) & ~(size_t)15;
-                StagingPool::Lease h_in;
-                DeviceBuf d_in, d_pcm, d_pcm64;
-                std::vector<std::unique_ptr<F64Plane>> widen;     // one per chunk; the streams are drained before the stage returns
-                std::vector<std::unique_ptr<PackPlane>> packs;
-                std::vector<std::unique_ptr<CollatePlane>> collated;
-                std::vector<PackRun> runs;                        // (ascending: the files lie in the plane in order)
-                for (size_t i = 0; i < (size_t)n_files && so.dither; i++)
-                    if (opus_open[i]) runs.push_back(PackRun{ opus_pcm_at[i], parsed[i].opus.bound_coeffs, 0 });
-                if (int rc = g_staging.take(base_bytes + rec_bytes + coefs_total * sizeof(float), h_in)) return rc;
-                if (fetch) if (int rc = g_staging.take(std::max<size_t>(coefs_total, 1) * es, owner->opus_plane)) return rc;
-                if (wide && fetch) if (int rc = d_pcm64.alloc(std::max<size_t>(coefs_total * es, 16))) return rc;
-                if (int rc = d_in.alloc(base_bytes + rec_bytes + coefs_total * sizeof(float))) return rc;
-                if (int rc = d_pcm.alloc(std::max<size_t>(coefs_total, 1) * sizeof(float))) return rc;
-                uint64_t *hb = (uint64_t *)h_in.p;
-                afg_celt_frame *hr = (afg_celt_frame *)((uint8_t *)h_in.p + base_bytes);
-                float *hc = (float *)((uint8_t *)h_in.p + base_bytes + rec_bytes);
-                const uint64_t *db = (const uint64_t *)d_in.p;
-                const afg_celt_frame *dr = (const afg_celt_frame *)((const uint8_t *)d_in.p + base_bytes);
-                const float *dc = (const float *)((const uint8_t *)d_in.p + base_bytes + rec_bytes);
-                for (size_t i = 0; i < (size_t)n_files; i++) {
-                    if (!opus_open[i]) continue;
-                    const afg_opus::File &m = parsed[i].opus;
-                    if (seq_pad[i]) hb[seq_at[i] - 1] = rec_at[i];                                  // the empty sequence
-                    for (int c = 0; c < m.channels; c++) hb[seq_at[i] + (size_t)c] = rec_at[i] + (size_t)c * m.bound_frames;
-                }
-                hb[seqs_total] = recs_total;
-                hipStream_t up = nullptr, down = nullptr;
-                std::vector<hipEvent_t> events;
-                hipError_t e = g_streams.take(&up, &down);
-                if (e == hipSuccess) e = hipMemcpyAsync(d_in.p, hb, base_bytes, hipMemcpyHostToDevice, up);
-                int rc = AFG_OK;
-                for (size_t f0 = 0; f0 < (size_t)n_files && !rc && e == hipSuccess;) {
-                    size_t f1 = f0, acc = 0;
-                    while (f1 < (size_t)n_files && acc < target) { if (opus_open[f1]) acc += parsed[f1].opus.bound_coeffs; f1++; }
-                    size_t first = (size_t)n_files, last = (size_t)n_files;
-                    for (size_t i = f0; i < f1; i++)
-                        if (opus_open[i]) { if (first == (size_t)n_files) first = i; last = i; }
-                    if (first == (size_t)n_files) { f0 = f1; continue; }
-                    parallel_for(f1 - f0, nt_long, [&](size_t k) {
-                        const size_t i = f0 + k;
-                        if (!opus_open[i]) return;
-                        Parsed &p = parsed[i];
-                        const size_t nfr = p.opus.bound_frames, nco = p.opus.bound_coeffs;
-                        const int C = p.opus.channels;
-                        afg_celt_frame *recs = hr + rec_at[i];
-                        bool ok = false;
-                        try {
-                            afg_opus::File f;
-                            ok = afg_opus::parse_file_into(data[i], length[i], f, recs, nfr, hc + coef_at[i], nco) == afg_opus::kOpened &&
-                                 !f.overflow && f.n_frames == nfr && f.n_coeffs == nco;
-                            f.ext_frames = nullptr;                // (the staging outlives this record)
-                            f.ext_coeffs = nullptr;
-                            if (ok) p.opus = f;
-                        } catch (...) { ok = false; }
-                        if (!ok) {                                 // cannot happen (the sizes are exact): an empty, failed file
-                            p.opus.error = true;
-                            p.opus.pcm_frames = 0;
-                            std::memset((void *)recs, 0, nfr * (size_t)C * sizeof(afg_celt_frame));
-                            std::memset(hc + coef_at[i], 0, nco * sizeof(float));
-                            for (size_t q = 0; q < nfr * (size_t)C; q++) { recs[q].frame_size = 120; recs[q].blocks = 1; recs[q].out_stride = 1; recs[q].imdct_scale = 1.0f; recs[q].out_off = opus_pcm_at[i]; recs[q].coef_off = coef_at[i]; }
-                            p.format = AFG_FORMAT_OPUS;
-                            return;
-                        }
-                        // channel 0's records are in place (file-relative offsets): make them plane-absolute, derive the others
-                        for (int c = C - 1; c >= 0; c--)
-                            for (size_t q = 0; q < nfr; q++) {
-                                afg_celt_frame r = recs[q];
-                                r.coef_off += coef_at[i] + (uint64_t)c * r.frame_size;
-                                r.out_off += opus_pcm_at[i] + (uint64_t)c;
-                                recs[(size_t)c * nfr + q] = r;
-                            }
-                        p.format = AFG_FORMAT_OPUS;
-                    });
-                    const size_t r0 = rec_at[first], r1 = rec_at[last] + parsed[last].opus.bound_frames * (size_t)parsed[last].opus.channels;
-                    const size_t c0 = coef_at[first], c1 = coef_at[last] + parsed[last].opus.bound_coeffs;
-                    const size_t s0 = seq_at[first], s1 = seq_at[last] + (size_t)parsed[last].opus.channels;
-                    e = hipMemcpyAsync((void *)(dr + r0), hr + r0, (r1 - r0) * sizeof(afg_celt_frame), hipMemcpyHostToDevice, up);
-                    if (e == hipSuccess && c1 > c0) e = hipMemcpyAsync((void *)(dc + c0), hc + c0, (c1 - c0) * sizeof(float), hipMemcpyHostToDevice, up);
-                    if (e != hipSuccess) break;
-                    if (c1 > c0) {
-                        rc = afg_celt_transform_hip((uint32_t)(s1 - s0), db + s0, dr, dc, (float *)d_pcm.p, nullptr, up);
-                        if (rc) break;
-                        bool any_gain = false;
-                        for (size_t i = first; i <= last; i++) any_gain = any_gain || (opus_open[i] && parsed[i].opus.gain_i != 0);
-                        if (!any_gain) {
-                            rc = afg_opus_output_hip(c1 - c0, (const float *)d_pcm.p + c0, nullptr, (float *)d_pcm.p + c0, up);
-                        } else {
-                            for (size_t i = first; i <= last && !rc; i++) {
-                                if (!opus_open[i] || !parsed[i].opus.bound_coeffs) continue;
-                                float *at = (float *)d_pcm.p + opus_pcm_at[i];
-                                const afg_opus::File &m = parsed[i].opus;
-                                rc = m.gain_i ? afg_opus_output_gain_hip(m.bound_coeffs, at, m.gain, nullptr, at, up)
-                                              : afg_opus_output_hip(m.bound_coeffs, at, nullptr, at, up);
-                            }
-                        }
-                        if (rc) break;
-                        if (f64) {
-                            widen.emplace_back(new F64Plane);
-                            rc = widen.back()->launch(AFG_WAV_KIND_F32, (const float *)d_pcm.p + c0, c1 - c0, (double *)d_pcm64.p + c0, up);
-                            if (rc) break;
-                        } else if (so.pcm()) {
-                            packs.emplace_back(new PackPlane);
-                            rc = packs.back()->launch(so, (const float *)d_pcm.p, (uint8_t *)d_pcm64.p, 0, c0, c1 - c0, runs, up);
-                            if (rc) break;
-                        } else if (so.collate()) {
-                            // the chunk's files have just been decoded: a file's run is what it delivers, not its bound
-                            // (the declared length cuts the delivery, stream.d:439-442); a failed file has none
-                            std::vector<PackRun> delivered;
-                            for (size_t i = first; i <= last; i++) {
-                                if (!opus_open[i] || parsed[i].opus.error) continue;
-                                const afg_opus::File &m = parsed[i].opus;
-                                const uint64_t frames = (uint64_t)std::min<int64_t>((int64_t)m.pcm_frames, std::max<int64_t>(m.declared_frames, 0));
-                                delivered.push_back(PackRun{ opus_pcm_at[i], std::min<uint64_t>(frames * (uint64_t)m.channels, m.bound_coeffs), 0, (uint32_t)i, (uint32_t)m.channels });
-                            }
-                            collated.emplace_back(new CollatePlane);
-                            rc = collated.back()->launch(so, (const float *)d_pcm.p, 0, c0, c1 - c0, delivered, up);
-                            if (rc) break;
-                        }
-                        hipEvent_t done = nullptr;
-                        e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
-                        if (e != hipSuccess) break;
-                        events.push_back(done);
-                        e = hipEventRecord(done, up);
-                        if (e == hipSuccess) e = hipStreamWaitEvent(down, done, 0);
-                        if (e == hipSuccess && fetch)
-                            e = hipMemcpyAsync((uint8_t *)owner->opus_plane.p + c0 * es, (const uint8_t *)(wide ? d_pcm64.p : d_pcm.p) + c0 * es, (c1 - c0) * es, hipMemcpyDeviceToHost, down);
-                    }
-                    f0 = f1;
-                }
-                if (up) { hipError_t e2 = hipStreamSynchronize(up); if (e == hipSuccess) e = e2; }
-                if (down) { hipError_t e2 = hipStreamSynchronize(down); if (e == hipSuccess) e = e2; }
-                for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
-                g_streams.give(up, down);
-                if (rc) return rc;
-                if (e != hipSuccess) { afg::set_error("Opus stage failed: %s", hipGetErrorString(e)); return AFG_ERR_HIP; }
-                opus_staged = true;
-                tm.lap("pass 1c: opus decode into staging | h2d | kernels | d2h (chunks overlapped)");
-            } else if (n_opus) {
-                afg::set_error("Opus stage: too many channel sequences");
-                return AFG_ERR_INVALID;
-            }
-        }
+        if (int rc = opus_pipeline(parsed, data, length, opus_open, nt_long, so, owner->opus_plane, opus_pcm_at, &opus_staged, tm)) return rc;
         // The FLAC and QOA files are complete now: their device stage (mostly PCIe time) runs on a second host thread
         // while this one parses the MP3 and Ogg files.  Each call of decode_parsed only touches the files it owns.
         std::vector<uint8_t> own_early((size_t)n_files, 0), own_late((size_t)n_files, 1);
@@ -2526,8 +1353,13 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
                 try {
                     // HIP's current device is per host thread and starts at 0: this thread works for the caller's device
                     if (hipSetDevice(cur_dev) != hipSuccess) { afg::set_error("hipSetDevice(%d) failed", cur_dev); early_job.rc = AFG_ERR_HIP; return; }
-                    early_job.rc = decode_parsed(parsed, data, length, 1 /* no helpers: they are parsing */, *eo, nullptr, nullptr, fs,
-                                                 own_early.data(), nullptr, nullptr, nullptr, so);
+                    StageCtx early = stage_ctx(parsed, data, length, own_early.data(), 1 /* no helpers: they are parsing */, so, *eo);
+                    FlacDecode early_flac;
+                    early_flac.staged = fs;
+                    Mp3Decode no_mp3;
+                    VorbisDecode no_ogg;
+                    OpusDecode no_opus;
+                    early_job.rc = decode_parsed(early, early_flac, no_mp3, no_ogg, no_opus);
                 } catch (...) {
                     afg::set_error("out of host memory");
                     early_job.rc = AFG_ERR_OOM;
@@ -2535,7 +1367,7 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
                 if (early_job.rc) early_job.error = afg_last_error();
             });
         }
-        StagingPool::Lease mp3_stage;
+        StagingLease mp3_stage;
         Mp3Stage stage;
         Mp3Pipe pipe;
         bool fallback = false;
@@ -2545,8 +1377,8 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
             const bool qmode = afg::dev_option(afg::kDevMp3FloatUpload) <= 0;
             const size_t per_block = qmode ? 576 * sizeof(int16_t) + sizeof(afg_mp3_qgranule) + sizeof(uint32_t)
                                            : 576 * sizeof(float) + sizeof(uint32_t);
-            if (int rc = g_staging.take(total_bound * per_block + 64, mp3_stage)) return rc;
-            if (fetch) if (int rc = g_staging.take(total_bound * 576 * es, owner->mp3_plane)) return rc;
+            if (int rc = staging_take(total_bound * per_block + 64, mp3_stage)) return rc;
+            if (fetch) if (int rc = staging_take(total_bound * 576 * es, owner->mp3_plane)) return rc;
             float *coef0 = nullptr;
             int16_t *q0 = nullptr;
             afg_mp3_qgranule *recs0 = nullptr;
@@ -2572,8 +1404,7 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
             if (afg::dev_option(afg::kDevMp3Chunks) > 0) want = (size_t)afg::dev_option(afg::kDevMp3Chunks);
             const size_t target = std::max<size_t>((total_bound + want - 1) / want, 8192);
             for (size_t f0 = 0; f0 < (size_t)n_files;) {
-                size_t f1 = f0, acc = 0;
-                while (f1 < (size_t)n_files && acc < target) acc += bound[f1++];
+                const size_t f1 = cut_chunk(f0, (size_t)n_files, target, [&](size_t i, size_t &w) { w = bound[i]; return true; }).f1;
                 std::atomic<bool> lost{ false };
                 parallel_for(f1 - f0, nt, [&](size_t k) {
                     const size_t i = f0 + k;
@@ -2635,10 +1466,10 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
         }
         // pass 1b: Ogg Vorbis files straight into one page-locked staging buffer (no per-file megabyte vectors to
         // fault in, gather and unmap) -- while the MP3 chunks queued above are still moving
-        StagingPool::Lease ogg_lease;
+        StagingLease ogg_lease;
         OggStage ogg_stage;
         if (ogg_total) {
-            if (int rc = g_staging.take(ogg_total * sizeof(float), ogg_lease)) return rc;
+            if (int rc = staging_take(ogg_total * sizeof(float), ogg_lease)) return rc;
             float *spec0 = (float *)ogg_lease.p;
             std::atomic<bool> lost{ false };
             parallel_for((size_t)n_files, nt, [&](size_t i) {
@@ -2665,9 +1496,16 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
             if (fallback) stage.blocks = 0;                   // decode_parsed does those files from their own buffers
         }
         if (parse_done) (*parse_done)();
-        int rc = decode_parsed(parsed, data, length, nt, *owner, stage.blocks ? &stage : nullptr, ogg_stage.floats ? &ogg_stage : nullptr,
-                               split ? nullptr : (flac_stage.words ? &flac_stage : nullptr), split ? own_late.data() : nullptr, nullptr, nullptr,
-                               opus_staged ? opus_pcm_at.data() : nullptr, so);
+        StageCtx late = stage_ctx(parsed, data, length, split ? own_late.data() : nullptr, nt, so, *owner);
+        FlacDecode late_flac;
+        if (!split && flac_stage.words) late_flac.staged = &flac_stage;
+        Mp3Decode late_mp3;
+        if (stage.blocks) late_mp3.staged = &stage;
+        VorbisDecode late_ogg;
+        if (ogg_stage.floats) late_ogg.staged = &ogg_stage;
+        OpusDecode late_opus;
+        if (opus_staged) late_opus.done_at = opus_pcm_at.data();
+        int rc = decode_parsed(late, late_flac, late_mp3, late_ogg, late_opus);
         tm.lap("decode_parsed total");
         if (split) {
             early_job.th.join();

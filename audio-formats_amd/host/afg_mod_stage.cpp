@@ -75,7 +75,6 @@ int StreamMix::read(void *out, int frames, bool f64)
 int batch_stage(const uint8_t *const *data, const size_t *length, const std::vector<int> &which,
                 int n_threads, afg_batch_item *items, std::shared_ptr<void> &keep, afg_front::SampleOut so)
 {
-    const bool f64 = so.f64();
     const size_t es = so.es();                                    // bytes per sample of the PCM plane the items point into
     if (which.empty()) return AFG_OK;
     // ---- the control layer, one file per helper-thread job ----
@@ -147,13 +146,10 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
     if (int rc = d_in.alloc(in_bytes)) return rc;
     if (int rc = d_songs.alloc(M * sizeof(afg_mod_song))) return rc;
     for (DevBuf &b : d_out) if (int rc = b.alloc(chunks.max_frames * 2 * sizeof(float))) return rc;
-    afg_front::F64Slots wide;                              // f64: the mixed floats stay on the device and are widened there
-    if (f64) if (int rc = wide.alloc(chunks.max_frames * 2)) return rc;
-    afg_front::PackSlots packed;                           // AFG_SAMPLE_PCM_*: ... or packed there; a song is one run of its own samples
-    std::vector<afg_front::PackRun> runs;
-    if (so.pcm()) if (int rc = packed.alloc(chunks.max_frames * 2, es)) return rc;
+    afg_front::WideSlots wide;                             // f64, AFG_SAMPLE_PCM_*, collate: the mixed floats stay on the device and are converted there
+    std::vector<afg_front::PackRun> runs;                  // a song is one run of its own samples
+    if (so.wide() && so.fetch()) if (int rc = wide.alloc(chunks.max_frames * 2, es)) return rc;
     for (size_t j = 0; j < M && so.runs(); j++) runs.push_back(afg_front::PackRun{ 2 * start[j], 2 * sims[mods[j]].frames, 0, (uint32_t)which[mods[j]], 2 });
-    std::vector<std::unique_ptr<afg_front::CollatePlane>> collated;   // collate: one per chunk, alive until run_chunks has drained
     const uint8_t *din = (const uint8_t *)d_in.p;
     const int rc = afg_front::run_chunks(
         chunks.count(),
@@ -168,16 +164,11 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
                                             (const afg_mod_segment *)(din + tick_bytes), (const afg_mod_tick *)din + songs[first[c]].tick_base,
                                             din + tick_bytes + seg_bytes, (float *)d_out[slot].p, up))
                 return rc;
-            if (so.pcm()) return packed.launch(slot, so, d_out[slot].p, 2 * start[first[c]], chunks.frames[c] * 2, runs, up);
-            if (so.collate()) {
-                collated.emplace_back(new afg_front::CollatePlane);
-                return collated.back()->launch(so, (const float *)d_out[slot].p, 2 * start[first[c]], 2 * start[first[c]], chunks.frames[c] * 2, runs, up);
-            }
-            return f64 ? wide.launch(slot, AFG_WAV_KIND_F32, d_out[slot].p, chunks.frames[c] * 2, up) : AFG_OK;
+            return wide.launch(slot, so, AFG_WAV_KIND_F32, d_out[slot].p, 2 * start[first[c]], chunks.frames[c] * 2, runs, up);
         },
         [&](size_t c, int slot, hipStream_t down) -> int {
             if (chunks.frames[c] && so.fetch())
-                AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)pcm + 2 * start[first[c]] * es, so.pcm() ? packed.bytes[slot].p : f64 ? wide.wide[slot].p : d_out[slot].p, chunks.frames[c] * 2 * es,
+                AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)pcm + 2 * start[first[c]] * es, so.wide() ? wide.buf[slot].p : d_out[slot].p, chunks.frames[c] * 2 * es,
                                              hipMemcpyDeviceToHost, down));
             return AFG_OK;
         });

@@ -15,7 +15,17 @@ int DevBuf::alloc(size_t bytes)
     release();
     if (int rc = devpool_take(bytes, &p, &cap)) { p = nullptr; cap = 0; return rc; }
     dev = cur;
+    if (bytes && poison_alloc()) {
+        (void)hipMemset(p, 0xff, bytes);
+        (void)hipStreamSynchronize(nullptr);
+    }
     return AFG_OK;
+}
+
+bool DevBuf::here() const
+{
+    int cur = 0;
+    return p && hipGetDevice(&cur) == hipSuccess && dev == cur;
 }
 
 void DevBuf::release()
@@ -65,18 +75,6 @@ int F64Plane::launch(uint32_t kind, const void *d_in, uint64_t count, double *d_
     if (int rc = span.alloc(sizeof(sp))) return rc;
     AFG_HIP_CHECK(hipMemcpyAsync(span.p, &sp, sizeof(sp), hipMemcpyHostToDevice, st));
     return afg_pcm_to_f64_hip(1, (const afg_wav_span *)span.p, tiles, (const uint8_t *)d_in, count * f64_kind_bytes(kind), d_out, count, st);
-}
-
-int F64Slots::alloc(size_t samples)
-{
-    for (DevBuf &b : wide) if (int rc = b.alloc(std::max<size_t>(samples, 2) * sizeof(double))) return rc;
-    return AFG_OK;
-}
-
-int F64Slots::launch(int slot, uint32_t kind, const void *d_in, uint64_t count, hipStream_t st)
-{
-    conv.emplace_back(new F64Plane);
-    return conv.back()->launch(kind, d_in, count, (double *)wide[slot].p, st);
 }
 
 uint64_t stage_chunk_samples(uint64_t dflt)
@@ -191,16 +189,75 @@ int CollatePlane::pad(const SampleOut &out, const std::vector<int64_t> &frames, 
     return submit(out, nullptr, 0, st);
 }
 
-int PackSlots::alloc(size_t samples, size_t es)
+int SampleConv::launch(const SampleOut &out, uint32_t kind, const void *d_in, uint64_t origin, uint64_t c0, uint64_t n, void *d_out,
+                       const std::vector<PackRun> &runs, hipStream_t st)
 {
-    for (DevBuf &b : bytes) if (int rc = b.alloc(std::max<size_t>(samples * es, 16))) return rc;
+    if (out.collate()) {
+        collated.emplace_back(new CollatePlane);
+        return collated.back()->launch(out, (const float *)d_in, origin, c0, n, runs, st);
+    }
+    if (out.pcm()) {
+        packs.emplace_back(new PackPlane);
+        return packs.back()->launch(out, (const float *)d_in, (uint8_t *)d_out, origin, c0, n, runs, st);
+    }
+    if (!out.f64()) return AFG_OK;
+    widen.emplace_back(new F64Plane);
+    return widen.back()->launch(kind, (const uint8_t *)d_in + (c0 - origin) * 4, n, (double *)d_out + (c0 - origin), st);
+}
+
+int WideSlots::alloc(size_t samples, size_t es)
+{
+    for (DevBuf &b : buf) if (int rc = b.alloc(std::max<size_t>(samples * es, 16))) return rc;
     return AFG_OK;
 }
 
-int PackSlots::launch(int slot, const SampleOut &out, const void *d_in, uint64_t origin, uint64_t n, const std::vector<PackRun> &runs, hipStream_t st)
+void StageStreams::take(bool three)
 {
-    conv.emplace_back(new PackPlane);
-    return conv.back()->launch(out, (const float *)d_in, (uint8_t *)bytes[slot].p, origin, origin, n, runs, st);
+    const hipError_t got = streams_take(&up, &down, three ? &mid : nullptr);
+    if (e == hipSuccess) e = got;
+}
+
+void StageStreams::chain(hipStream_t from, hipStream_t to)
+{
+    if (e != hipSuccess) return;
+    drained = false;
+    hipEvent_t ev = nullptr;
+    e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess) return;
+    events.push_back(ev);
+    e = hipEventRecord(ev, from);
+    if (e == hipSuccess) e = hipStreamWaitEvent(to, ev, 0);
+}
+
+void StageStreams::sync(hipStream_t st)
+{
+    if (!st) return;
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+}
+
+void StageStreams::drain(const std::function<void()> &uploads_done)
+{
+    sync(up);
+    sync(mid);
+    if (uploads_done) uploads_done();
+    sync(down);
+    drained = true;
+}
+
+void StageStreams::release()
+{
+    if (!up && !down && !mid) return;
+    if (!drained) {
+        const hipError_t first = e;
+        drain();
+        e = first;                                           // (what the stage saw, not what this last wait says)
+    }
+    for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
+    events.clear();
+    streams_give(up, down, mid);
+    up = down = mid = nullptr;
+    drained = false;
 }
 
 int PlaneFetch::run(const void *d_plane, uint32_t kind, uint64_t count, void *out, bool f64, hipStream_t st)
@@ -219,15 +276,6 @@ int PlaneFetch::run(const void *d_plane, uint32_t kind, uint64_t count, void *ou
 }
 
 namespace {
-// the kept upload / download pair, given back drained on every way out
-struct StreamPair {
-    hipStream_t up = nullptr, down = nullptr;
-    ~StreamPair()
-    {
-        for (hipStream_t st : { up, down }) if (st) (void)hipStreamSynchronize(st);
-        if (up && down) streams_give(up, down);
-    }
-};
 struct Events {
     hipEvent_t e[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
     ~Events() { for (hipEvent_t ev : e) if (ev) (void)hipEventDestroy(ev); }
@@ -237,8 +285,9 @@ struct Events {
 int run_chunks(size_t n_chunks, const std::function<int(hipStream_t up)> &before, const ChunkStep &upload, const ChunkStep &launch,
                const ChunkStep &download)
 {
-    StreamPair pair;
-    AFG_HIP_CHECK(streams_take(&pair.up, &pair.down));
+    StageStreams pair;                                       // given back drained on every way out
+    pair.take();
+    AFG_HIP_CHECK(pair.e);
     const hipStream_t up = pair.up, down = pair.down;
     // Rings of two events, one per slot.  A wait takes the event's state when it is queued, so at chunk c `uploaded[slot]`
     // and `fetched[slot]` still stand for chunk c - 2: the last chunk that used the slot.

@@ -1,5 +1,7 @@
-// afg_stage.h -- what the host stages beside afg_host.cpp share (MOD, XM and WAV decoding, the batch encoder, the write
-// stream): the library's pools, a pooled device buffer, a handle's own stream, and the chunk pipeline of the batch stages.
+// afg_stage.h -- the toolkit every host stage shares (the FLAC / QOA, MP3, Vorbis and Opus stages of afg_*_stage.cpp behind
+// afg_batch.h; MOD, XM and WAV decoding, the batch encoder, the write stream): the library's pools, the one pooled device
+// buffer, a handle's own stream, the conversion that follows a stage's kernels (SampleConv), the stream holder and chunk
+// cutter of the pipelined stages, and the two-slot chunk pipeline (run_chunks).
 #pragma once
 #include "../../include/afg.h"
 
@@ -16,17 +18,23 @@ namespace afg_front {
 // ---- the pools and helper threads of afg_host.cpp ----
 int devpool_take(size_t bytes, void **out, size_t *cap_out);   // device memory, kept between calls
 void devpool_give(void *p, size_t cap, int dev);               // dev: the device it was taken on
+bool poison_alloc();                                           // AFG_POISON_ALLOC was set when the library was loaded (tests)
 // a page-locked staging lease (pinning memory costs about as much as moving it); the buffer goes back to the pool when
 // the last owner lets go.  NULL: out of memory.
 std::shared_ptr<void> staging_lease(size_t bytes, void **p);
-hipError_t streams_take(hipStream_t *up, hipStream_t *down);   // the kept upload / download pair of the current device
-void streams_give(hipStream_t up, hipStream_t down);           // ... given back drained
+// the kept upload / download pair of the current device; mid (optional): a third stream for the kernels of a stage whose
+// uploads should never wait behind them
+hipError_t streams_take(hipStream_t *up, hipStream_t *down, hipStream_t *mid = nullptr);
+void streams_give(hipStream_t up, hipStream_t down, hipStream_t mid = nullptr);   // ... given back drained
 // fn(0) .. fn(n - 1) on the library's pooled host threads; n_threads 0 = the library's choice (afg_batch_decode)
 void parallel_run(size_t n, int n_threads, const std::function<void(size_t)> &fn);
 
 constexpr uint64_t align16(uint64_t n) { return (n + 15) & ~(uint64_t)15; }
 
-// Device memory from the pool, returned to the device it was taken on.
+// Device memory from the pool, returned to the device it was taken on: the library's one device-buffer type.
+// AFG_POISON_ALLOC (tests): a buffer freshly taken from the pool starts out holding NaN patterns, so that a stage that
+// reads what nobody wrote shows.  (hipMemset runs on the null stream and returns early; the stages copy on non-blocking
+// streams, which do not wait for it: alloc synchronises, or the fill could land on top of an upload.)
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
@@ -37,6 +45,7 @@ struct DevBuf {
     ~DevBuf() { release(); }
     int alloc(size_t bytes);                                    // keeps the buffer when it is large enough and on the current device
     void release();
+    bool here() const;                                          // holds a buffer, and of the current device: what it carries can be read
 };
 
 // The stream of one handle (a stream being read or written): non-blocking, on the device that was current at the last
@@ -75,16 +84,6 @@ struct PlaneFetch {
     DevBuf wide;
     std::vector<uint8_t> bounce;
     int run(const void *d_plane, uint32_t kind, uint64_t count, void *out, bool f64, hipStream_t st);
-};
-
-// The float64 side of a batch stage's two output slots (afg_batch_opts.sample_type): the chunk in `slot` is widened from the
-// stage's float plane into wide[slot] on the kernel stream, between the stage's kernels and the download.  One F64Plane per
-// launch, kept until the stage has drained (run_chunks drains on every way out).
-struct F64Slots {
-    DevBuf wide[2];
-    std::vector<std::unique_ptr<F64Plane>> conv;
-    int alloc(size_t samples);
-    int launch(int slot, uint32_t kind, const void *d_in, uint64_t count, hipStream_t st);
 };
 
 // ---- packed integer PCM output (afg_batch_opts.sample_type AFG_SAMPLE_PCM_*, afg_batch_transcode) ----
@@ -142,13 +141,74 @@ struct CollatePlane {
 private:
     int submit(const SampleOut &out, const float *d_in, uint64_t in_floats, hipStream_t st);
 };
-// The packed side of a batch stage's two output slots, beside F64Slots.
-struct PackSlots {
-    DevBuf bytes[2];
-    std::vector<std::unique_ptr<PackPlane>> conv;
-    int alloc(size_t samples, size_t es);
-    int launch(int slot, const SampleOut &out, const void *d_in, uint64_t origin, uint64_t n, const std::vector<PackRun> &runs, hipStream_t st);
+// The conversion that follows a stage's kernels, by what `out` asks for: floats [c0, c0 + n) of the stage's 4-byte plane
+// (elements of `kind`; d_in[0] is element `origin` of it) go to the same samples of its converted mirror (d_out[0] is the
+// mirror of element `origin`) as doubles (afg_pcm_to_f64_hip) or packed integers (afg_pcm_pack_hip), or -- collate mode,
+// d_out unused -- into the caller's tensor (afg_collate_hip); AFG_SAMPLE_F32: nothing.  One launch on `st`, behind whatever
+// wrote the plane there.
+// Lifetime: every launch uploads records asynchronously from host memory this object owns.  It therefore lives, and is not
+// cleared, until the streams it queued on have drained: declare it in front of whatever drains them on the way out
+// (StageStreams, run_chunks), and call clear() only behind a drain.
+struct SampleConv {
+    int launch(const SampleOut &out, uint32_t kind, const void *d_in, uint64_t origin, uint64_t c0, uint64_t n, void *d_out,
+               const std::vector<PackRun> &runs, hipStream_t st);
+    void clear() { widen.clear(); packs.clear(); collated.clear(); }
+private:
+    std::vector<std::unique_ptr<F64Plane>> widen;
+    std::vector<std::unique_ptr<PackPlane>> packs;
+    std::vector<std::unique_ptr<CollatePlane>> collated;
 };
+// The converted side of a batch stage's two output slots: the chunk in `slot` (its first float is float `origin` of the
+// stage's plane) is converted into buf[slot] on the kernel stream, between the stage's kernels and the download.
+struct WideSlots {
+    DevBuf buf[2];                                               // out.es() bytes per sample (not needed in collate mode)
+    SampleConv conv;
+    int alloc(size_t samples, size_t es);
+    int launch(int slot, const SampleOut &out, uint32_t kind, const void *d_in, uint64_t origin, uint64_t n, const std::vector<PackRun> &runs, hipStream_t st)
+    {
+        return conv.launch(out, kind, d_in, origin, origin, n, buf[slot].p, runs, st);
+    }
+};
+
+// ---- what the pipelined stages share ----
+// The streams of one stage -- the kept pair, or with `three` the pair and a kernel stream between them -- and the events
+// that chain them.  `e` keeps the first HIP error of take, chain and drain; a stage reports it once it has drained.  The
+// destructor drains the streams and gives them back, so the stage's buffers -- declared in front of it -- are idle when
+// they are let go, on every way out.
+struct StageStreams {
+    hipStream_t up = nullptr, down = nullptr, mid = nullptr;
+    hipError_t e = hipSuccess;
+    StageStreams() = default;
+    StageStreams(const StageStreams &) = delete;
+    StageStreams &operator=(const StageStreams &) = delete;
+    ~StageStreams() { release(); }
+    void take(bool three = false);                              // (e tells whether it worked)
+    void chain(hipStream_t from, hipStream_t to);               // what is queued on `to` from here on waits for what is on `from` now
+    // The end of the stage's device work: waits for up, mid and down in that order (the first error wins); nothing is queued
+    // behind it.  uploads_done (optional, a trace's clock) runs between the waits for the kernels and for the downloads.
+    void drain(const std::function<void()> &uploads_done = nullptr);
+    void release();                                             // drained, the events destroyed, the streams back in the pool
+private:
+    void sync(hipStream_t st);
+    std::vector<hipEvent_t> events;
+    bool drained = false;
+};
+
+// Files [f0, f1) of n: from f0 on until the members' weights reach `target`.  member(i, &w): file i belongs to the stage,
+// with weight w.  first / last: the first and last member of the chunk (both n: it has none).
+struct FileChunk { size_t f1, first, last, weight; };
+template <typename M> FileChunk cut_chunk(size_t f0, size_t n, size_t target, M member)
+{
+    FileChunk c{ f0, n, n, 0 };
+    for (; c.f1 < n && c.weight < target; c.f1++) {
+        size_t w = 0;
+        if (!member(c.f1, w)) continue;
+        c.weight += w;
+        if (c.first == n) c.first = c.f1;
+        c.last = c.f1;
+    }
+    return c;
+}
 
 // ---- the chunk pipeline of a batch stage ----
 // How much a stage puts into a chunk at least, or at most: `dflt`, unless afg_dev_option("stage_chunk_samples", n) says n.

@@ -194,8 +194,7 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
         if (int rc = d_in[b].alloc((size_t)max_in)) return rc;
         if (int rc = d_out[b].alloc((size_t)max_out * (so.pcm() ? sizeof(float) : es))) return rc;
     }
-    std::vector<std::unique_ptr<afg_front::CollatePlane>> collated;   // one per chunk, alive until run_chunks has drained
-    afg_front::PackSlots packed;                         // AFG_SAMPLE_PCM_*: the converted floats stay on the device and are packed there
+    afg_front::WideSlots packed;                         // AFG_SAMPLE_PCM_*, collate: the converted floats stay on the device and are packed or scattered there
     if (so.pcm()) if (int rc = packed.alloc((size_t)max_out, es)) return rc;
     // what chunk c takes up and brings back: both end with its last piece
     auto in_bytes = [&](size_t c) {
@@ -229,15 +228,12 @@ int batch_stage(const uint8_t *const *data, const size_t *length, const std::vec
                                              in_bytes(c), (float *)d_out[b].p, (out_floats(c) + 3) & ~(uint64_t)3, up))
                 return rc;
             // (without dither the alignment gaps between files are packed too: their floats are whatever the buffer held)
-            if (so.collate()) {
-                collated.emplace_back(new afg_front::CollatePlane);
-                return collated.back()->launch(so, (const float *)d_out[b].p, chunk_out0[c], chunk_out0[c], out_floats(c), runs, up);
-            }
-            return so.pcm() ? packed.launch(b, so, d_out[b].p, chunk_out0[c], out_floats(c), runs, up) : AFG_OK;
+            // (f64 was converted from the file's own sample type above: no launch follows)
+            return packed.launch(b, so, AFG_WAV_KIND_F32, d_out[b].p, chunk_out0[c], out_floats(c), runs, up);
         },
         [&](size_t c, int b, hipStream_t down) -> int {
             if (!so.fetch()) return AFG_OK;
-            AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)pcm + chunk_out0[c] * es, so.pcm() ? packed.bytes[b].p : d_out[b].p, (size_t)out_floats(c) * es, hipMemcpyDeviceToHost, down));
+            AFG_HIP_CHECK(hipMemcpyAsync((uint8_t *)pcm + chunk_out0[c] * es, so.pcm() ? packed.buf[b].p : d_out[b].p, (size_t)out_floats(c) * es, hipMemcpyDeviceToHost, down));
             return AFG_OK;
         });
     if (rc) return rc;
