@@ -60,6 +60,11 @@ COLLATE_SPAN_DTYPE = np.dtype([("in_off", np.uint64), ("count", np.uint64), ("sa
                                ("first_frame", np.int64), ("first_tile", np.uint64), ("frames", np.uint32), ("channels", np.uint16),
                                ("out_channels", np.uint16)])
 assert COLLATE_SPAN_DTYPE.itemsize == 56
+# afg_resample_row: one output row of afg_resample_hip (in_frames 0: a row of zeros)
+RESAMPLE_ROW_DTYPE = np.dtype([("in_off", np.uint64), ("in_stride", np.uint64), ("in_frame0", np.int64), ("out_off", np.uint64),
+                               ("first_tile", np.uint64), ("taps_off", np.uint64), ("in_rows", np.uint32), ("in_frames", np.uint32),
+                               ("out_frames", np.uint32), ("M", np.uint32), ("L", np.uint32), ("W", np.uint32)])
+assert RESAMPLE_ROW_DTYPE.itemsize == 72
 
 # every symbol include/afg.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -94,6 +99,7 @@ ABI_SYMBOLS = [
     "afg_batch_encode", "afg_encode_free",
     "afg_pcm_pack_layout", "afg_pcm_pack_hip", "afg_batch_transcode",
     "afg_collate_layout", "afg_collate_hip", "afg_batch_decode_to_device",
+    "afg_resample_taps", "afg_resample_layout", "afg_resample_hip", "afg_batch_decode_resampled",
 ]
 
 
@@ -225,6 +231,13 @@ class CollateOpts(C.Structure):
                 ("first_frame", C.POINTER(C.c_int64))]
 
 
+class ResampleOpts(C.Structure):
+    """afg_resample_opts (afg_batch_decode_resampled)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_threads", C.c_int), ("channels", C.c_uint32), ("frames", C.c_uint32),
+                ("first_frame", C.POINTER(C.c_int64)), ("samplerate", C.c_uint32), ("mono", C.c_uint32), ("in_channels", C.c_uint32),
+                ("max_in_rate", C.c_uint32), ("lowpass_width", C.c_uint32)]
+
+
 SAMPLE_F32, SAMPLE_F64, SAMPLE_PCM_S8, SAMPLE_PCM_S16, SAMPLE_PCM_S24 = range(5)     # afg_batch_opts.sample_type
 BATCH_OPTS_SIZE_V1 = BatchOpts.sample_type.offset        # the struct before sample_type was appended
 BATCH_OPTS_SIZE_V2 = BatchOpts.dither.offset             # ... up to sample_type, before dither and dither_seed were
@@ -271,7 +284,7 @@ _DEV_ENV = {"AFG_CELT_PATH": ("celt_path", {"stream": 1, "split": 2, "walk": 3})
             "AFG_MP3_CHUNKS": ("mp3_chunks", None), "AFG_MP3_FLOAT_UPLOAD": ("mp3_float_upload", None),
             "AFG_VORBIS_HOST_FLOOR": ("vorbis_host_floor", None), "AFG_FLAC_HOST_RES32": ("flac_host_res32", None),
             "AFG_VORBIS_SEG_PACKETS": ("vorbis_seg_packets", None), "AFG_BATCH_GROUPS": ("batch_groups", None),
-            "AFG_STAGE_CHUNK_SAMPLES": ("stage_chunk_samples", None)}
+            "AFG_STAGE_CHUNK_SAMPLES": ("stage_chunk_samples", None), "AFG_RESAMPLE_SCRATCH_BYTES": ("resample_scratch_bytes", None)}
 _dev_seen = {}
 
 
@@ -448,6 +461,12 @@ def lib():
     L.afg_collate_layout.restype = u64
     L.afg_collate_hip.argtypes = [u64, vp, u64, vp, u64, vp, u64, vp]
     L.afg_batch_decode_to_device.argtypes = [vp, vp, C.c_int, C.POINTER(CollateOpts), vp, C.POINTER(BatchResult)]
+    L.afg_resample_taps.argtypes = [u32, u32, u32, vp, u64, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    L.afg_resample_taps.restype = u64
+    L.afg_resample_layout.argtypes = [vp, u64]
+    L.afg_resample_layout.restype = u64
+    L.afg_resample_hip.argtypes = [u64, vp, u64, vp, u64, vp, u64, vp, u64, vp]
+    L.afg_batch_decode_resampled.argtypes = [vp, vp, C.c_int, C.POINTER(ResampleOpts), vp, C.POINTER(BatchResult)]
     _lib = L
     _sync_dev_options(L)
     return L
@@ -1304,6 +1323,87 @@ def batch_decode_tensor(files, frames, channels, first_frame=None, out=None, n_t
     opts = CollateOpts(C.sizeof(CollateOpts), int(n_threads), channels, frames, ff)
     res = BatchResult()
     check(lib().afg_batch_decode_to_device(ptrs, lens, n, C.byref(opts), out.data_ptr(), C.byref(res)))
+    try:
+        meta = []
+        for i in range(res.n_files):
+            it = res.items[i]
+            meta.append({"status": it.status, "message": None if it.message is None else it.message.decode(),
+                         "format": it.format, "channels": it.channels, "samplerate": it.samplerate, "frames": it.frames})
+        return out, meta
+    finally:
+        lib().afg_batch_free(C.byref(res))
+
+
+def resample_taps(in_rate, out_rate, lowpass_width=0):
+    """afg_resample_taps: (taps, M, L, W) -- the float32 table [L, 2 W] of the Hann-windowed sinc that takes in_rate to
+    out_rate (include/afg.h has the definition); equal rates have no filter: an empty table, M = L = 1, W = 0.  Host only.
+    AfgError for a rate of 0, a lowpass_width above 64, or a table of more than 2^22 floats."""
+    L_ = lib()
+    M, L, W = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    need = int(L_.afg_resample_taps(int(in_rate), int(out_rate), int(lowpass_width), None, 0, C.byref(M), C.byref(L), C.byref(W)))
+    if M.value == 0:
+        raise AfgError(f"afg: {L_.afg_last_error().decode()}")
+    taps = np.zeros(need, np.float32)
+    if need:
+        L_.afg_resample_taps(int(in_rate), int(out_rate), int(lowpass_width), taps.ctypes.data, need, None, None, None)
+    return taps.reshape(L.value, 2 * W.value), M.value, L.value, W.value
+
+
+def resample_layout(rows):
+    """afg_resample_layout: fills first_tile of a RESAMPLE_ROW_DTYPE array in place; returns the launch's tile count."""
+    assert rows.dtype == RESAMPLE_ROW_DTYPE and rows.flags.c_contiguous
+    return int(lib().afg_resample_layout(rows.ctypes.data, len(rows)))
+
+
+def resample(n_rows, d_rows, n_tiles, d_in, in_floats, d_taps, taps_floats, d_out, out_floats, stream=None):
+    """Enqueue the resampling kernel (afg_resample_hip) on device arrays: planar rows at one rate, mixed to mono or not, to
+    rows at another.  The rows are checked first (the call waits for `stream` to read them): AfgError, and nothing written,
+    when one leaves a plane."""
+    check(lib().afg_resample_hip(int(n_rows), _ptr(d_rows), int(n_tiles), _ptr(d_in), int(in_floats), _ptr(d_taps), int(taps_floats),
+                                 _ptr(d_out), int(out_floats), _stream(stream)))
+
+
+def batch_decode_tensor_resampled(files, frames, channels, samplerate, first_frame=None, mono=False, in_channels=0, max_in_rate=0,
+                                  lowpass_width=0, out=None, n_threads=0):
+    """afg_batch_decode_resampled: (tensor, meta) as batch_decode_tensor, with every file brought to `samplerate` (frames
+    count at that rate; first_frame stays in each file's own frames) and, with mono (channels must be 1), mixed down to the
+    mean of its channels first.  Files above max_in_rate (0: 48000 Hz), and with mono files of more than in_channels
+    (0: 2) channels, are refused: status -5, a message, a zero slab.  lowpass_width: the filter's zero crossings (0: 6).
+    The same device and stream rules as batch_decode_tensor."""
+    import torch
+    bufs = [bytes(f) for f in files]
+    n = len(bufs)
+    frames, channels, samplerate = int(frames), int(channels), int(samplerate)
+    if frames < 1 or channels < 1 or samplerate < 1:
+        raise ValueError("batch_decode_tensor_resampled: frames, channels and samplerate must be at least 1")
+    if mono and channels != 1:
+        raise ValueError("batch_decode_tensor_resampled: a mono tensor has one channel")
+    shape = (n, channels, frames)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+    else:
+        if tuple(out.shape) != shape or out.dtype != torch.float32:
+            raise ValueError(f"batch_decode_tensor_resampled: out must be a float32 tensor of shape {shape}")
+        if not out.is_cuda or out.device.index != torch.cuda.current_device():
+            raise ValueError("batch_decode_tensor_resampled: out must live on the current device")
+        if not out.is_contiguous():
+            raise ValueError("batch_decode_tensor_resampled: out must be contiguous")
+    if n == 0:
+        return out, []
+    if get_device() != torch.cuda.current_device():
+        raise ValueError(f"batch_decode_tensor_resampled: HIP's current device is {get_device()}, torch's {torch.cuda.current_device()}")
+    torch.cuda.current_stream().synchronize()                # (as batch_decode_tensor: the library's streams are ordered with nobody's)
+    ff = None
+    if first_frame is not None:
+        if len(first_frame) != n:
+            raise ValueError("batch_decode_tensor_resampled: one first_frame per file")
+        ff = (C.c_int64 * n)(*[int(v) for v in first_frame])
+    ptrs = (C.c_char_p * n)(*bufs)
+    lens = (C.c_size_t * n)(*[len(b) for b in bufs])
+    opts = ResampleOpts(C.sizeof(ResampleOpts), int(n_threads), channels, frames, ff, samplerate, 1 if mono else 0, int(in_channels),
+                        int(max_in_rate), int(lowpass_width))
+    res = BatchResult()
+    check(lib().afg_batch_decode_resampled(ptrs, lens, n, C.byref(opts), out.data_ptr(), C.byref(res)))
     try:
         meta = []
         for i in range(res.n_files):

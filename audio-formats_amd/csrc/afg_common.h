@@ -28,7 +28,7 @@ int numeric_mode();
 // Alternative code paths the test-suite runs side by side with the default ones (afg.h: afg_dev_option).  Set through
 // that call only -- the library reads no environment variable for them -- and -1 while unset.
 enum DevOption { kDevCeltPath, kDevCeltDeSeq, kDevCeltDeDuo, kDevCeltSegRecs, kDevCeltWholeFrames, kDevVorbisSingle,
-                 kDevMp3Chunks, kDevMp3FloatUpload, kDevVorbisHostFloor, kDevFlacHostRes32, kDevVorbisSegPackets, kDevBatchGroups, kDevStageChunkSamples, kDevCount };
+                 kDevMp3Chunks, kDevMp3FloatUpload, kDevVorbisHostFloor, kDevFlacHostRes32, kDevVorbisSegPackets, kDevBatchGroups, kDevStageChunkSamples, kDevResampleScratchBytes, kDevCount };
 long dev_option(DevOption which);
 
 #define AFG_HIP_CHECK(expr)                                                              \
@@ -67,6 +67,11 @@ int vorbis_plan_create_at(afg_vorbis_plan **plan, uint32_t n_streams, const uint
 // `stream`): the checks run on them and nothing waits for the device (collate.hip)
 int collate_launch(const afg_collate_span *h_spans, uint64_t n_spans, const afg_collate_span *d_spans, uint64_t n_tiles,
                    const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats, hipStream_t stream);
+
+// afg_resample_hip likewise, for a caller that still has the rows in host memory (resample.hip)
+int resample_launch(const afg_resample_row *h_rows, uint64_t n_rows, const afg_resample_row *d_rows, uint64_t n_tiles,
+                    const float *d_in, uint64_t in_floats, const float *d_taps, uint64_t taps_floats, float *d_out,
+                    uint64_t out_floats, hipStream_t stream);
 
 // Owns a device buffer filled from a host array at plan creation.
 struct DeviceArray {

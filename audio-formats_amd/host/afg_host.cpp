@@ -1235,6 +1235,7 @@ unsigned sustained_threads()
 // What a batch result owns: one BatchOut per device the batch ran on.
 struct BatchOwner {
     std::vector<std::unique_ptr<BatchOut>> parts;
+    std::deque<std::string> messages;                            // the item messages that are not static strings (afg_batch_decode_resampled)
 };
 
 // The whole batch path for the files handed in, on the calling thread's current device; fills items[0..n_files).
@@ -1246,7 +1247,8 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
     // so (afg_batch_opts.sample_type, dither, dither_seed): every plane the items point into holds doubles or packed integer
     // samples, made on the device
     // Collate mode: nothing comes back.  Every stage scatters its chunks into so.d_out; what the files did not fill is written
-    // as zero runs at the end, when every file's delivered length is known, and the items point at the slabs.
+    // as zero runs at the end, when every file's delivered length is known, and the items point at the slabs.  With
+    // so.no_pad (afg_batch_decode_resampled: the tensor is a scratch whose reader knows every file's length) they are left out.
         const bool fetch = so.fetch();
         const size_t es = so.es();
     {
@@ -1552,10 +1554,12 @@ int batch_decode_device(const uint8_t *const *data, const size_t *length, int n_
                 if (ok) { frames[(size_t)i] = items[i].frames; channels[(size_t)i] = items[i].channels; }
                 items[i].pcm = ok ? so.d_out + (size_t)i * so.C * so.T : nullptr;
             }
-            CollatePlane padding;
-            if (int rc2 = padding.pad(so, frames, channels, nullptr)) return rc2;
-            AFG_HIP_CHECK(hipStreamSynchronize(nullptr));
-            tm.lap("collate padding");
+            if (!so.no_pad) {
+                CollatePlane padding;
+                if (int rc2 = padding.pad(so, frames, channels, nullptr)) return rc2;
+                AFG_HIP_CHECK(hipStreamSynchronize(nullptr));
+                tm.lap("collate padding");
+            }
         }
         keep = std::move(guard);
         tm.lap("items filled");
@@ -1858,6 +1862,101 @@ int afg_batch_decode_to_device(const uint8_t *const *data, const size_t *length,
         // one pass over the whole list on the current device: a slab's place follows from the file's index in it
         owner->parts.emplace_back();
         if (int rc = batch_decode_device(data, length, n_files, opts->n_threads, items, owner->parts.back(), nullptr, so)) return rc;
+        items_guard.p = nullptr;
+        out->n_files = n_files;
+        out->items = items;
+        out->owner = owner.release();
+        return AFG_OK;
+    } catch (...) {
+        afg::set_error("out of host memory");
+        return AFG_ERR_OOM;
+    }
+}
+
+int afg_batch_decode_resampled(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
+                               float *d_out, afg_batch_result *out)
+{
+    try {
+        // (all of this before any device call: it holds on a machine without a GPU too)
+        if (!opts || !d_out || !out) { afg::set_error("afg_batch_decode_resampled: NULL %s", !opts ? "opts" : !d_out ? "d_out" : "out"); return AFG_ERR_INVALID; }
+        out->n_files = 0; out->items = nullptr; out->owner = nullptr;
+        if (opts->struct_size < offsetof(afg_resample_opts, lowpass_width) + sizeof(uint32_t)) {
+            afg::set_error("afg_resample_opts.struct_size too small");
+            return AFG_ERR_INVALID;
+        }
+        if (opts->channels == 0 || opts->frames == 0) {
+            afg::set_error("afg_resample_opts: channels and frames must be at least 1 (%u, %u)", opts->channels, opts->frames);
+            return AFG_ERR_INVALID;
+        }
+        constexpr uint32_t kMaxRate = 1u << 20;
+        if (opts->samplerate == 0 || opts->samplerate > kMaxRate) {
+            afg::set_error("afg_resample_opts.samplerate %u: 1 .. %u Hz", opts->samplerate, kMaxRate);
+            return AFG_ERR_INVALID;
+        }
+        if (opts->mono > 1 || (opts->mono && opts->channels != 1)) {
+            afg::set_error("afg_resample_opts.mono %u with %u channels: mono is 0 or 1, and a mono tensor has one channel", opts->mono, opts->channels);
+            return AFG_ERR_INVALID;
+        }
+        if (opts->in_channels > 0xffff) { afg::set_error("afg_resample_opts.in_channels %u: at most 65535 (0 means 2)", opts->in_channels); return AFG_ERR_INVALID; }
+        if (opts->max_in_rate > kMaxRate) { afg::set_error("afg_resample_opts.max_in_rate %u: at most %u Hz (0 means 48000)", opts->max_in_rate, kMaxRate); return AFG_ERR_INVALID; }
+        if (opts->lowpass_width > 64) { afg::set_error("afg_resample_opts.lowpass_width %u: at most 64 (0 means 6)", opts->lowpass_width); return AFG_ERR_INVALID; }
+        if (n_files < 0 || (n_files && (!data || !length))) { afg::set_error("afg_batch_decode_resampled: n_files %d, or no file list", n_files); return AFG_ERR_INVALID; }
+        for (int i = 0; i < n_files && opts->first_frame; i++)
+            if (opts->first_frame[i] < 0) { afg::set_error("afg_resample_opts.first_frame[%d] is negative", i); return AFG_ERR_INVALID; }
+        afg_front::ResampleJob job;
+        job.C = opts->channels;
+        job.T = opts->frames;
+        job.samplerate = opts->samplerate;
+        job.mono = opts->mono != 0;
+        job.Z = opts->lowpass_width ? opts->lowpass_width : 6;
+        job.in_channels = opts->in_channels ? opts->in_channels : 2;
+        job.max_in_rate = opts->max_in_rate ? opts->max_in_rate : 48000;
+        job.plan();
+        if (job.T_s > 0xffffffffull) {
+            afg::set_error("afg_batch_decode_resampled: %u frames at %u Hz from files of up to %u Hz: a scratch row of 2^32 floats or more", job.T,
+                           job.samplerate, job.max_in_rate);
+            return AFG_ERR_INVALID;
+        }
+        if (n_files == 0) return AFG_OK;
+        if ((uint64_t)opts->channels * opts->frames > (((uint64_t)1 << 62) / (uint64_t)n_files)) {
+            afg::set_error("afg_batch_decode_resampled: a tensor of %d x %u x %u floats", n_files, opts->channels, opts->frames);
+            return AFG_ERR_INVALID;
+        }
+        // the sublists: as many files as the scratch budget holds, one at the least
+        const long budget_opt = afg::dev_option(afg::kDevResampleScratchBytes);
+        const uint64_t budget = budget_opt > 0 ? (uint64_t)budget_opt : (uint64_t)2 << 30;
+        const uint64_t slab_bytes = (uint64_t)job.R_s * job.T_s * sizeof(float);
+        const size_t per_list = (size_t)std::min<uint64_t>((uint64_t)n_files, std::max<uint64_t>(budget / slab_bytes, 1));
+        // scratch frame 0 of a file: H frames ahead of its first frame, as far as the file reaches
+        std::vector<int64_t> frame0((size_t)n_files, 0);
+        for (int i = 0; i < n_files && opts->first_frame; i++) frame0[(size_t)i] = std::max<int64_t>(opts->first_frame[i] - (int64_t)job.H, 0);
+        auto owner = std::unique_ptr<BatchOwner>(new BatchOwner);
+        afg_batch_item *items = (afg_batch_item *)std::calloc((size_t)n_files, sizeof(afg_batch_item));
+        if (!items) return AFG_ERR_OOM;
+        struct ItemsGuard { afg_batch_item *p; ~ItemsGuard() { std::free(p); } } items_guard{ items };
+        if (int rc = afg::require_device()) return rc;
+        afg_front::ResamplePlane plane;                           // (declared in front of the drain: it holds what the uploads read)
+        afg_front::DevBuf scratch;
+        struct Drain { ~Drain() { (void)hipStreamSynchronize(nullptr); } } drain;
+        if (int rc = scratch.alloc((size_t)(per_list * slab_bytes))) return rc;
+        SampleOut so;
+        so.type = afg_front::kSampleCollate;
+        so.d_out = (float *)scratch.p;
+        so.C = job.R_s;
+        so.T = (uint32_t)job.T_s;
+        so.no_pad = true;
+        for (size_t f0 = 0; f0 < (size_t)n_files; f0 += per_list) {
+            const size_t n = std::min(per_list, (size_t)n_files - f0);
+            so.n_files = n;
+            so.first_frame = frame0.data() + f0;
+            // the collate pass at the files' own rates: a slab's place follows from the file's index in the sublist.  It returns
+            // with its streams drained; the items point at nothing it owns (messages are static), so its part is let go.
+            std::unique_ptr<BatchOut> part;
+            if (int rc = batch_decode_device(data + f0, length + f0, (int)n, opts->n_threads, items + f0, part, nullptr, so)) return rc;
+            if (int rc = plane.launch(job, (const float *)scratch.p, items + f0, n, opts->first_frame ? opts->first_frame + f0 : nullptr,
+                                      frame0.data() + f0, d_out + f0 * (size_t)job.C * job.T, owner->messages, nullptr)) return rc;
+            AFG_HIP_CHECK(hipStreamSynchronize(nullptr));         // the scratch and the records are free for the next sublist
+        }
         items_guard.p = nullptr;
         out->n_files = n_files;
         out->items = items;

@@ -9,8 +9,10 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <deque>
 #include <functional>
 #include <memory>
+#include <string>
 #include <vector>
 
 namespace afg_front {
@@ -100,6 +102,8 @@ struct SampleOut {
     uint32_t C = 0, T = 0;
     uint64_t n_files = 0;
     const int64_t *first_frame = nullptr;                        // ... and the file frame at t = 0, per batch file (NULL: 0)
+    bool no_pad = false;                                         // collate: the zero runs at the end are left out -- whoever reads
+                                                                 // the tensor reads only what the files delivered (ResamplePlane)
     SampleOut() = default;
     SampleOut(bool f64) : type(f64 ? AFG_SAMPLE_F64 : AFG_SAMPLE_F32) {}
     bool f64() const { return type == AFG_SAMPLE_F64; }
@@ -141,6 +145,35 @@ struct CollatePlane {
 private:
     int submit(const SampleOut &out, const float *d_in, uint64_t in_floats, hipStream_t st);
 };
+// ---- the tensor at one sample rate (afg_batch_decode_resampled, host/afg_resample.cpp) ----
+// What the call asks for, with the defaults filled in, and the scratch tensor [files, R_s, T_s] its collate pass fills at
+// the files' own rates: scratch frame 0 of a file is file frame max(0, first_frame - H).
+struct ResampleJob {
+    uint32_t C = 0, T = 0, samplerate = 0, Z = 6, in_channels = 2, max_in_rate = 48000;
+    bool mono = false;
+    uint32_t R_s = 0, H = 0;
+    uint64_t T_s = 0;
+    void plan();                                                 // R_s, H and T_s from the fields above
+};
+// The filter table of one rate pair (afg_resample_taps), made once per (in, out, Z) and kept for the process.
+struct ResampleTable {
+    uint32_t M = 0, L = 0, W = 0;
+    std::shared_ptr<const std::vector<float>> taps;              // L * 2 W floats (none for equal rates)
+};
+int resample_table(uint32_t in_rate, uint32_t out_rate, uint32_t Z, ResampleTable &t);   // AFG_ERR_INVALID: afg_last_error says why
+// One launch of afg_resample_hip (csrc/resample.hip) behind a collate pass: files [0, n) of a sublist, whose scratch slabs
+// lie at d_scratch in list order, to their slabs in d_out (the sublist's first).  One record per output row; a failed
+// or refused file's rows, and rows the file has no channel for, are records without input.  Refused files (rate, channel
+// count) get their status and message in `items`; the message strings live in `messages`.  The object holds the records
+// and tables its uploads read: it lives until `st` has drained.
+struct ResamplePlane {
+    std::vector<afg_resample_row> recs;
+    std::vector<float> taps;
+    DevBuf d_recs, d_taps;
+    int launch(const ResampleJob &job, const float *d_scratch, afg_batch_item *items, size_t n, const int64_t *first_frame,
+               const int64_t *scratch_frame0, float *d_out, std::deque<std::string> &messages, hipStream_t st);
+};
+
 // The conversion that follows a stage's kernels, by what `out` asks for: floats [c0, c0 + n) of the stage's 4-byte plane
 // (elements of `kind`; d_in[0] is element `origin` of it) go to the same samples of its converted mirror (d_out[0] is the
 // mirror of element `origin`) as doubles (afg_pcm_to_f64_hip) or packed integers (afg_pcm_pack_hip), or -- collate mode,

@@ -446,6 +446,16 @@ int afg_collate_hip(ulong n_spans, const(afg_collate_span)* d_spans, ulong n_til
 struct afg_collate_opts { uint struct_size; int n_threads; uint channels; uint frames; const(long)* first_frame; }
 int afg_batch_decode_to_device(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_collate_opts)* opts,
                                float* d_out, afg_batch_result* result);
+
+// the tensor at one sample rate (afg.h has the filter's definition; the reference has no resampler)
+ulong afg_resample_taps(uint in_rate, uint out_rate, uint lowpass_width, float* taps, ulong cap, uint* M, uint* L, uint* W);
+struct afg_resample_row { ulong in_off, in_stride; long in_frame0; ulong out_off, first_tile, taps_off; uint in_rows, in_frames, out_frames, M, L, W; }
+ulong afg_resample_layout(afg_resample_row* rows, ulong n_rows);
+int afg_resample_hip(ulong n_rows, const(afg_resample_row)* d_rows, ulong n_tiles, const(float)* d_in, ulong in_floats,
+                     const(float)* d_taps, ulong taps_floats, float* d_out, ulong out_floats, void* hip_stream);
+struct afg_resample_opts { uint struct_size; int n_threads; uint channels; uint frames; const(long)* first_frame; uint samplerate, mono, in_channels, max_in_rate, lowpass_width; }
+int afg_batch_decode_resampled(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_resample_opts)* opts,
+                               float* d_out, afg_batch_result* result);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

@@ -1083,6 +1083,85 @@ int afg_copy_probe_hip(void *d_dst, const void *d_src, size_t bytes, void *hip_s
  * passes; with 0x7fc00000 (NaN) behind it such a read shows.  The GPU tests run every case behind this. */
 int afg_lds_fill_probe_hip(uint32_t word, void *hip_stream);
 
+/* Sample-rate conversion and mono downmix behind the collate: afg_batch_decode_to_device's tensor at ONE sample rate.  The
+ * reference has no resampler (AudioStream delivers every file at its own rate), so nothing of it is restated here: the
+ * definition below is this library's own, and tests/resample_model.py states it again in numpy.
+ *
+ * The filter is a Hann-windowed sinc with Z zero crossings (lowpass_width; 0 means 6) and roll-off 0.99.  For a file rate
+ * `in` and a target rate `out`: g = gcd(in, out), M = in / g, L = out / g, fc = 0.99 * min(1, L / M), W = ceil(Z / fc),
+ * K = 2 W.  The tap of phase p in [0, L) and index k in [0, K): d = (k - (W - 1)) - p / L, x = clamp(d * fc, -Z, Z),
+ * h[p][k] = fc * sinc(x) * cos(pi x / (2 Z))^2 with sinc(x) = sin(pi x) / (pi x), computed in double and rounded once to
+ * float32.  Output frame t of a row: q = in_frame0 + floor(t * M / L), p = (t * M) mod L, and y[t] is the sum over
+ * k = 0 .. K - 1, in that order and starting from +0.0f, of h[p][k] * x[q - (W - 1) + k]: every product rounded to float32,
+ * then every add, no fused multiply-add.  Input indexes outside [0, in_frames) contribute nothing.  Equal rates have no
+ * filter (M = L = 1, W = 0): y[t] is the input word at q, NaN payloads included, +0.0f when q lies outside the row.
+ * The mono mix comes before the filter: for in_rows = R rows s = x[0], then s = s + x[r] in row order, m = s / (float)R
+ * (the IEEE division); for R == 1 the row itself.
+ *
+ * afg_resample_taps: host only, no device needed.  Returns L * K, the floats the table of (in_rate, out_rate,
+ * lowpass_width) needs, sets *M, *L, *W (each may be NULL) and fills taps[p * K + k] when cap >= L * K (taps may be NULL
+ * with cap 0).  Equal rates: returns 0 with *M = *L = 1, *W = 0, and no error.  Returns 0 with *M = *L = *W = 0 and
+ * afg_last_error set for a rate of 0, a lowpass_width above 64, or a table of more than 2^22 floats. */
+uint64_t afg_resample_taps(uint32_t in_rate, uint32_t out_rate, uint32_t lowpass_width, float *taps, uint64_t cap,
+                           uint32_t *M, uint32_t *L, uint32_t *W);
+typedef struct afg_resample_row {   /* one output row (72 bytes) */
+    uint64_t in_off;      /* float index in d_in of frame 0 of the file's first row */
+    uint64_t in_stride;   /* floats from one input row of the file to the next */
+    int64_t  in_frame0;   /* input frame of output frame 0: any value below 2^61 in size, before and past the row included */
+    uint64_t out_off;     /* float index in d_out of y[0] */
+    uint64_t first_tile;  /* filled in by afg_resample_layout */
+    uint64_t taps_off;    /* float index in d_taps of h[0][0] (unused when W == 0) */
+    uint32_t in_rows;     /* R: rows mixed into this one, 1 .. 65535 (1: no mix); unused when in_frames == 0 */
+    uint32_t in_frames;   /* frames of every input row; 0: the row is +0.0f throughout and d_in is not read */
+    uint32_t out_frames;  /* floats written */
+    uint32_t M, L, W;     /* as afg_resample_taps gives them: 1 <= M, L <= 2^20; W == 0 only with M == L == 1 */
+} afg_resample_row;
+/* Host: gives every row its tiles (first_tile) and returns the launch's tile count.  A tile is 1024 output frames of one
+ * row, fewer (512 ... 64) while the input frames a tile needs -- floor(tile * M / L) + 2 W + 1 -- exceed 4096. */
+uint64_t afg_resample_layout(afg_resample_row *rows, uint64_t n_rows);
+/* Runs every row in one launch, one workgroup per tile.  d_rows is the device copy of rows laid out by afg_resample_layout,
+ * n_tiles what it returned; d_in, d_taps (4-byte aligned; NULL allowed when no row reads them) and d_out do not overlap.
+ * Every record is checked before the launch (the entry fetches d_rows on hip_stream and waits for it): its input rows --
+ * in_frames floats from in_off + r * in_stride, r < in_rows -- must lie inside [0, in_floats), its table of L * 2 W floats
+ * inside [0, taps_floats), its out_frames floats inside [0, out_floats), and M, L, W and in_frame0 inside the ranges
+ * above.  Otherwise AFG_ERR_INVALID and nothing is written.  The kernel writes exactly out_frames floats per record and
+ * reads no input float outside [0, in_frames) of the record's rows. */
+int afg_resample_hip(uint64_t n_rows, const afg_resample_row *d_rows, uint64_t n_tiles, const float *d_in, uint64_t in_floats,
+                     const float *d_taps, uint64_t taps_floats, float *d_out, uint64_t out_floats, void *hip_stream);
+
+/* afg_batch_decode_to_device at one sample rate: d_out is n_files * channels * frames floats on the current device, and
+ * element [i, k, t] is the definition above applied to what afg_batch_decode_ex with AFG_SAMPLE_F32 delivers for file i in
+ * the same numeric mode -- row k of the file, or with `mono` (channels must be 1) the mix of all its rows -- from the
+ * file's rate to `samplerate`, with in_frame0 = first_frame[i] (in the file's own frames, as in afg_collate_opts).
+ * Without mono a row k >= channels_i is zero; the slab of a file that failed is zero.  Two kinds of file are refused with
+ * status AFG_ERR_UNSUPPORTED, a message of this library's own that names both numbers, and a zero slab, their neighbours
+ * undisturbed: a file whose rate is 0 or above max_in_rate, and -- with mono -- a file with more channels than
+ * in_channels.  (So is a file whose rate makes a table afg_resample_taps refuses.)
+ * The collate pass of afg_batch_decode_to_device runs at the files' own rates into a pooled scratch of
+ * [files, R, ceil(frames * max_in_rate / samplerate) + 2 H + 1] floats, R = channels or in_channels and H the W of
+ * max_in_rate; then one afg_resample_hip launch writes every element of d_out.  A list whose scratch would exceed
+ * afg_dev_option("resample_scratch_bytes") (default 2 GiB) is processed in sublists of at least one file.  Synchronous,
+ * the current device only, and d_out as for afg_batch_decode_to_device.  items[i] keeps the file's own frames, channels
+ * and samplerate; pcm is the device address of its slab (NULL when the file failed or was refused).
+ * Checked before any device call, AFG_ERR_INVALID with afg_last_error set: NULL opts, d_out or out; a struct_size that does
+ * not reach lowpass_width; channels == 0 or frames == 0; samplerate == 0 or above 2^20; mono with channels != 1; in_channels
+ * above 65535; max_in_rate above 2^20; lowpass_width above 64; a negative first_frame entry; n_files < 0; a scratch row of
+ * 2^32 floats or more.  n_files == 0 is AFG_OK and touches nothing. */
+typedef struct afg_resample_opts {
+    uint32_t       struct_size;   /* sizeof(afg_resample_opts) */
+    int            n_threads;     /* as afg_batch_opts */
+    uint32_t       channels;      /* C >= 1 */
+    uint32_t       frames;        /* T >= 1, at `samplerate` */
+    const int64_t *first_frame;   /* per file, >= 0, in the file's own frames; NULL: 0 for every file */
+    uint32_t       samplerate;    /* of the tensor, Hz */
+    uint32_t       mono;          /* 0, or 1: channels == 1 and the row is the mean of the file's rows */
+    uint32_t       in_channels;   /* mono: rows of a file kept for the mix, 0 means 2 */
+    uint32_t       max_in_rate;   /* 0 means 48000 */
+    uint32_t       lowpass_width; /* Z, 0 means 6 */
+} afg_resample_opts;
+int afg_batch_decode_resampled(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
+                               float *d_out, afg_batch_result *out);
+
 #ifdef __cplusplus
 }
 #endif
