@@ -65,6 +65,14 @@ RESAMPLE_ROW_DTYPE = np.dtype([("in_off", np.uint64), ("in_stride", np.uint64), 
                                ("first_tile", np.uint64), ("taps_off", np.uint64), ("in_rows", np.uint32), ("in_frames", np.uint32),
                                ("out_frames", np.uint32), ("M", np.uint32), ("L", np.uint32), ("W", np.uint32)])
 assert RESAMPLE_ROW_DTYPE.itemsize == 72
+# afg_mel_row: one input row of afg_melspec_hip and its [n_mels, out_frames] output
+MEL_ROW_DTYPE = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), ("first_tile", np.uint64), ("in_frames", np.uint32),
+                          ("out_frames", np.uint32)])
+assert MEL_ROW_DTYPE.itemsize == 32
+MEL_PAD_REFLECT, MEL_PAD_ZERO = 0, 1             # afg_mel_params.pad_mode
+MEL_POWER, MEL_LOG10 = 0, 1                      # afg_mel_params.out_kind
+MEL_SCALE_SLANEY, MEL_SCALE_HTK = 0, 1
+MEL_NORM_NONE, MEL_NORM_SLANEY = 0, 1
 
 # every symbol include/afg.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -100,6 +108,7 @@ ABI_SYMBOLS = [
     "afg_pcm_pack_layout", "afg_pcm_pack_hip", "afg_batch_transcode",
     "afg_collate_layout", "afg_collate_hip", "afg_batch_decode_to_device",
     "afg_resample_taps", "afg_resample_layout", "afg_resample_hip", "afg_batch_decode_resampled",
+    "afg_mel_basis", "afg_mel_filters", "afg_mel_frames", "afg_mel_layout", "afg_mel_check_rows", "afg_melspec_hip", "afg_batch_decode_mel",
 ]
 
 
@@ -238,6 +247,18 @@ class ResampleOpts(C.Structure):
                 ("max_in_rate", C.c_uint32), ("lowpass_width", C.c_uint32)]
 
 
+class MelParams(C.Structure):
+    """afg_mel_params (afg_melspec_hip)."""
+    _fields_ = [("n_fft", C.c_uint32), ("win_length", C.c_uint32), ("hop", C.c_uint32), ("n_mels", C.c_uint32), ("center", C.c_uint32),
+                ("pad_mode", C.c_uint32), ("out_kind", C.c_uint32), ("log_floor", C.c_float)]
+
+
+class MelOpts(C.Structure):
+    """afg_mel_opts (afg_batch_decode_mel): afg_resample_opts' fields, then the mel parameters and the bank's."""
+    _fields_ = ResampleOpts._fields_ + [("n_out", C.c_uint32), ("mel", MelParams), ("scale", C.c_uint32), ("norm", C.c_uint32),
+                                        ("f_min", C.c_double), ("f_max", C.c_double)]
+
+
 SAMPLE_F32, SAMPLE_F64, SAMPLE_PCM_S8, SAMPLE_PCM_S16, SAMPLE_PCM_S24 = range(5)     # afg_batch_opts.sample_type
 BATCH_OPTS_SIZE_V1 = BatchOpts.sample_type.offset        # the struct before sample_type was appended
 BATCH_OPTS_SIZE_V2 = BatchOpts.dither.offset             # ... up to sample_type, before dither and dither_seed were
@@ -284,7 +305,8 @@ _DEV_ENV = {"AFG_CELT_PATH": ("celt_path", {"stream": 1, "split": 2, "walk": 3})
             "AFG_MP3_CHUNKS": ("mp3_chunks", None), "AFG_MP3_FLOAT_UPLOAD": ("mp3_float_upload", None),
             "AFG_VORBIS_HOST_FLOOR": ("vorbis_host_floor", None), "AFG_FLAC_HOST_RES32": ("flac_host_res32", None),
             "AFG_VORBIS_SEG_PACKETS": ("vorbis_seg_packets", None), "AFG_BATCH_GROUPS": ("batch_groups", None),
-            "AFG_STAGE_CHUNK_SAMPLES": ("stage_chunk_samples", None), "AFG_RESAMPLE_SCRATCH_BYTES": ("resample_scratch_bytes", None)}
+            "AFG_STAGE_CHUNK_SAMPLES": ("stage_chunk_samples", None), "AFG_RESAMPLE_SCRATCH_BYTES": ("resample_scratch_bytes", None),
+            "AFG_MEL_SCRATCH_BYTES": ("mel_scratch_bytes", None)}
 _dev_seen = {}
 
 
@@ -467,6 +489,17 @@ def lib():
     L.afg_resample_layout.restype = u64
     L.afg_resample_hip.argtypes = [u64, vp, u64, vp, u64, vp, u64, vp, u64, vp]
     L.afg_batch_decode_resampled.argtypes = [vp, vp, C.c_int, C.POINTER(ResampleOpts), vp, C.POINTER(BatchResult)]
+    L.afg_mel_basis.argtypes = [u32, u32, vp, u64]
+    L.afg_mel_basis.restype = u64
+    L.afg_mel_filters.argtypes = [u32, u32, u32, C.c_double, C.c_double, u32, u32, vp, u64]
+    L.afg_mel_filters.restype = u64
+    L.afg_mel_frames.argtypes = [C.POINTER(MelParams), u32]
+    L.afg_mel_frames.restype = u32
+    L.afg_mel_layout.argtypes = [vp, u64, C.POINTER(MelParams)]
+    L.afg_mel_layout.restype = u64
+    L.afg_mel_check_rows.argtypes = [vp, u64, u64, C.POINTER(MelParams), u64, u64, u64, u64]
+    L.afg_melspec_hip.argtypes = [u64, vp, u64, C.POINTER(MelParams), vp, u64, vp, u64, vp, u64, vp, u64, vp]
+    L.afg_batch_decode_mel.argtypes = [vp, vp, C.c_int, C.POINTER(MelOpts), vp, C.POINTER(BatchResult)]
     _lib = L
     _sync_dev_options(L)
     return L
@@ -1404,6 +1437,125 @@ def batch_decode_tensor_resampled(files, frames, channels, samplerate, first_fra
                         int(max_in_rate), int(lowpass_width))
     res = BatchResult()
     check(lib().afg_batch_decode_resampled(ptrs, lens, n, C.byref(opts), out.data_ptr(), C.byref(res)))
+    try:
+        meta = []
+        for i in range(res.n_files):
+            it = res.items[i]
+            meta.append({"status": it.status, "message": None if it.message is None else it.message.decode(),
+                         "format": it.format, "channels": it.channels, "samplerate": it.samplerate, "frames": it.frames})
+        return out, meta
+    finally:
+        lib().afg_batch_free(C.byref(res))
+
+
+def mel_params(n_fft=400, hop=160, n_mels=80, win_length=None, center=True, pad_mode=MEL_PAD_REFLECT, out_kind=MEL_LOG10, log_floor=0.0):
+    """afg_mel_params with Whisper's shape as the default (win_length None: n_fft)."""
+    return MelParams(int(n_fft), int(n_fft if win_length is None else win_length), int(hop), int(n_mels), 1 if center else 0,
+                     int(pad_mode), int(out_kind), float(log_floor))
+
+
+def mel_basis(n_fft, win_length=None):
+    """afg_mel_basis: the float32 table [win_length, 2 * nb16] -- the windowed cosines in columns [0, n_bins), the negated
+    sines in [nb16, nb16 + n_bins), nb16 = n_bins rounded up to 16, zeros between (include/afg.h has the definition).
+    Host only.  AfgError for n_fft outside 16 .. 2048 or win_length outside 1 .. n_fft."""
+    L_ = lib()
+    win = int(n_fft if win_length is None else win_length)
+    need = int(L_.afg_mel_basis(int(n_fft), win, None, 0))
+    if need == 0:
+        raise AfgError(f"afg: {L_.afg_last_error().decode()}")
+    out = np.zeros(need, np.float32)
+    L_.afg_mel_basis(int(n_fft), win, out.ctypes.data, need)
+    return out.reshape(win, need // win)
+
+
+def mel_filters(samplerate, n_fft, n_mels, f_min=0.0, f_max=0.0, scale=MEL_SCALE_SLANEY, norm=MEL_NORM_SLANEY):
+    """afg_mel_filters: the float32 bank [n_mels, n_fft // 2 + 1] (f_max 0: samplerate / 2).  Host only.  AfgError for
+    arguments out of range."""
+    L_ = lib()
+    args = (int(samplerate), int(n_fft), int(n_mels), float(f_min), float(f_max), int(scale), int(norm))
+    need = int(L_.afg_mel_filters(*args, None, 0))
+    if need == 0:
+        raise AfgError(f"afg: {L_.afg_last_error().decode()}")
+    out = np.zeros(need, np.float32)
+    L_.afg_mel_filters(*args, out.ctypes.data, need)
+    return out.reshape(int(n_mels), need // int(n_mels))
+
+
+def mel_frames(params, in_frames):
+    """afg_mel_frames: the frames a row of in_frames samples has (max_frames of include/afg.h)."""
+    return int(lib().afg_mel_frames(C.byref(params), int(in_frames)))
+
+
+def mel_layout(rows, params):
+    """afg_mel_layout: fills first_tile of a MEL_ROW_DTYPE array in place; returns the launch's tile count."""
+    assert rows.dtype == MEL_ROW_DTYPE and rows.flags.c_contiguous
+    return int(lib().afg_mel_layout(rows.ctypes.data, len(rows), C.byref(params)))
+
+
+def mel_check_rows(rows, n_tiles, params, in_floats, basis_floats, filters_floats, out_floats):
+    """afg_mel_check_rows: what afg_melspec_hip checks before it launches, on host records.  AfgError when one fails."""
+    assert rows.dtype == MEL_ROW_DTYPE and rows.flags.c_contiguous
+    check(lib().afg_mel_check_rows(rows.ctypes.data, len(rows), int(n_tiles), C.byref(params), int(in_floats), int(basis_floats),
+                                   int(filters_floats), int(out_floats)))
+
+
+def melspec(n_rows, d_rows, n_tiles, params, d_in, in_floats, d_basis, basis_floats, d_filters, filters_floats, d_out, out_floats, stream=None):
+    """Enqueue the mel spectrogram kernel (afg_melspec_hip) on device arrays: planar float rows to [rows, n_mels, out_frames].
+    The parameters and the rows are checked first (the call waits for `stream` to read them): AfgError, and nothing written,
+    when one fails."""
+    check(lib().afg_melspec_hip(int(n_rows), _ptr(d_rows), int(n_tiles), C.byref(params), _ptr(d_in), int(in_floats), _ptr(d_basis),
+                                int(basis_floats), _ptr(d_filters), int(filters_floats), _ptr(d_out), int(out_floats), _stream(stream)))
+
+
+def batch_decode_mel(files, frames, samplerate=16000, n_fft=400, hop=160, n_mels=80, win_length=None, center=True,
+                     pad_mode=MEL_PAD_REFLECT, out_kind=MEL_LOG10, mono=True, out=None, channels=1, n_out=0, log_floor=0.0, f_min=0.0,
+                     f_max=0.0, scale=MEL_SCALE_SLANEY, norm=MEL_NORM_SLANEY, first_frame=None, in_channels=0, max_in_rate=0,
+                     lowpass_width=0, n_threads=0):
+    """afg_batch_decode_mel: (tensor, meta) as batch_decode_tensor_resampled, with the tensor [len(files), channels, n_mels,
+    n_out] the (log-)mel spectrogram of every row of that call's tensor of `frames` samples at `samplerate` (include/afg.h
+    has the definition).  n_out 0: every frame `frames` samples have.  The same device and stream rules as
+    batch_decode_tensor."""
+    import torch
+    bufs = [bytes(f) for f in files]
+    n = len(bufs)
+    frames, channels, samplerate = int(frames), int(channels), int(samplerate)
+    if frames < 1 or channels < 1 or samplerate < 1:
+        raise ValueError("batch_decode_mel: frames, channels and samplerate must be at least 1")
+    if mono and channels != 1:
+        raise ValueError("batch_decode_mel: a mono tensor has one channel")
+    prm = mel_params(n_fft, hop, n_mels, win_length, center, pad_mode, out_kind, log_floor)
+    most = mel_frames(prm, frames)
+    if most == 0:
+        raise ValueError(f"batch_decode_mel: {frames} samples hold no frame of these parameters ({lib().afg_last_error().decode()})")
+    n_out = int(n_out)
+    if n_out < 0 or n_out > most:
+        raise ValueError(f"batch_decode_mel: n_out {n_out}, but {frames} samples have {most} frames")
+    shape = (n, channels, int(n_mels), n_out if n_out else most)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+    else:
+        if tuple(out.shape) != shape or out.dtype != torch.float32:
+            raise ValueError(f"batch_decode_mel: out must be a float32 tensor of shape {shape}")
+        if not out.is_cuda or out.device.index != torch.cuda.current_device():
+            raise ValueError("batch_decode_mel: out must live on the current device")
+        if not out.is_contiguous():
+            raise ValueError("batch_decode_mel: out must be contiguous")
+    if n == 0:
+        return out, []
+    if get_device() != torch.cuda.current_device():
+        raise ValueError(f"batch_decode_mel: HIP's current device is {get_device()}, torch's {torch.cuda.current_device()}")
+    torch.cuda.current_stream().synchronize()                # (as batch_decode_tensor: the library's streams are ordered with nobody's)
+    ff = None
+    if first_frame is not None:
+        if len(first_frame) != n:
+            raise ValueError("batch_decode_mel: one first_frame per file")
+        ff = (C.c_int64 * n)(*[int(v) for v in first_frame])
+    ptrs = (C.c_char_p * n)(*bufs)
+    lens = (C.c_size_t * n)(*[len(b) for b in bufs])
+    opts = MelOpts(C.sizeof(MelOpts), int(n_threads), channels, frames, ff, samplerate, 1 if mono else 0, int(in_channels),
+                   int(max_in_rate), int(lowpass_width), n_out, prm, int(scale), int(norm), float(f_min), float(f_max))
+    res = BatchResult()
+    check(lib().afg_batch_decode_mel(ptrs, lens, n, C.byref(opts), out.data_ptr(), C.byref(res)))
     try:
         meta = []
         for i in range(res.n_files):

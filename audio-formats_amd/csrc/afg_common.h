@@ -28,7 +28,7 @@ int numeric_mode();
 // Alternative code paths the test-suite runs side by side with the default ones (afg.h: afg_dev_option).  Set through
 // that call only -- the library reads no environment variable for them -- and -1 while unset.
 enum DevOption { kDevCeltPath, kDevCeltDeSeq, kDevCeltDeDuo, kDevCeltSegRecs, kDevCeltWholeFrames, kDevVorbisSingle,
-                 kDevMp3Chunks, kDevMp3FloatUpload, kDevVorbisHostFloor, kDevFlacHostRes32, kDevVorbisSegPackets, kDevBatchGroups, kDevStageChunkSamples, kDevResampleScratchBytes, kDevCount };
+                 kDevMp3Chunks, kDevMp3FloatUpload, kDevVorbisHostFloor, kDevFlacHostRes32, kDevVorbisSegPackets, kDevBatchGroups, kDevStageChunkSamples, kDevResampleScratchBytes, kDevMelScratchBytes, kDevCount };
 long dev_option(DevOption which);
 
 #define AFG_HIP_CHECK(expr)                                                              \
@@ -72,6 +72,11 @@ int collate_launch(const afg_collate_span *h_spans, uint64_t n_spans, const afg_
 int resample_launch(const afg_resample_row *h_rows, uint64_t n_rows, const afg_resample_row *d_rows, uint64_t n_tiles,
                     const float *d_in, uint64_t in_floats, const float *d_taps, uint64_t taps_floats, float *d_out,
                     uint64_t out_floats, hipStream_t stream);
+
+// afg_melspec_hip likewise (melspec.hip)
+int melspec_launch(const afg_mel_row *h_rows, uint64_t n_rows, const afg_mel_row *d_rows, uint64_t n_tiles, const afg_mel_params *params,
+                   const float *d_in, uint64_t in_floats, const float *d_basis, uint64_t basis_floats, const float *d_filters,
+                   uint64_t filters_floats, float *d_out, uint64_t out_floats, hipStream_t stream);
 
 // Owns a device buffer filled from a host array at plan creation.
 struct DeviceArray {

@@ -1873,6 +1873,105 @@ int afg_batch_decode_to_device(const uint8_t *const *data, const size_t *length,
     }
 }
 
+}  // extern "C"
+
+namespace afg_front {
+
+// What afg_batch_decode_resampled checks of its options behind struct_size, before any device call; fills in the job.
+int resampled_check(const afg_resample_opts *opts, const uint8_t *const *data, const size_t *length, int n_files, ResampleJob &job)
+{
+    if (opts->channels == 0 || opts->frames == 0) {
+        afg::set_error("afg_resample_opts: channels and frames must be at least 1 (%u, %u)", opts->channels, opts->frames);
+        return AFG_ERR_INVALID;
+    }
+    constexpr uint32_t kMaxRate = 1u << 20;
+    if (opts->samplerate == 0 || opts->samplerate > kMaxRate) {
+        afg::set_error("afg_resample_opts.samplerate %u: 1 .. %u Hz", opts->samplerate, kMaxRate);
+        return AFG_ERR_INVALID;
+    }
+    if (opts->mono > 1 || (opts->mono && opts->channels != 1)) {
+        afg::set_error("afg_resample_opts.mono %u with %u channels: mono is 0 or 1, and a mono tensor has one channel", opts->mono, opts->channels);
+        return AFG_ERR_INVALID;
+    }
+    if (opts->in_channels > 0xffff) { afg::set_error("afg_resample_opts.in_channels %u: at most 65535 (0 means 2)", opts->in_channels); return AFG_ERR_INVALID; }
+    if (opts->max_in_rate > kMaxRate) { afg::set_error("afg_resample_opts.max_in_rate %u: at most %u Hz (0 means 48000)", opts->max_in_rate, kMaxRate); return AFG_ERR_INVALID; }
+    if (opts->lowpass_width > 64) { afg::set_error("afg_resample_opts.lowpass_width %u: at most 64 (0 means 6)", opts->lowpass_width); return AFG_ERR_INVALID; }
+    if (n_files < 0 || (n_files && (!data || !length))) { afg::set_error("afg_batch_decode_resampled: n_files %d, or no file list", n_files); return AFG_ERR_INVALID; }
+    for (int i = 0; i < n_files && opts->first_frame; i++)
+        if (opts->first_frame[i] < 0) { afg::set_error("afg_resample_opts.first_frame[%d] is negative", i); return AFG_ERR_INVALID; }
+    job.C = opts->channels;
+    job.T = opts->frames;
+    job.samplerate = opts->samplerate;
+    job.mono = opts->mono != 0;
+    job.Z = opts->lowpass_width ? opts->lowpass_width : 6;
+    job.in_channels = opts->in_channels ? opts->in_channels : 2;
+    job.max_in_rate = opts->max_in_rate ? opts->max_in_rate : 48000;
+    job.plan();
+    if (job.T_s > 0xffffffffull) {
+        afg::set_error("afg_batch_decode_resampled: %u frames at %u Hz from files of up to %u Hz: a scratch row of 2^32 floats or more", job.T,
+                       job.samplerate, job.max_in_rate);
+        return AFG_ERR_INVALID;
+    }
+    return AFG_OK;
+}
+
+// The resampled tensor of a checked call into d_out; items (n_files of them, zeroed) and messages as the entry returns them.
+int resampled_run(const ResampleJob &job, const afg_resample_opts *opts, const uint8_t *const *data, const size_t *length, int n_files,
+              float *d_out, afg_batch_item *items, std::deque<std::string> &messages)
+{
+    if ((uint64_t)opts->channels * opts->frames > (((uint64_t)1 << 62) / (uint64_t)n_files)) {
+        afg::set_error("afg_batch_decode_resampled: a tensor of %d x %u x %u floats", n_files, opts->channels, opts->frames);
+        return AFG_ERR_INVALID;
+    }
+    // the sublists: as many files as the scratch budget holds, one at the least
+    const long budget_opt = afg::dev_option(afg::kDevResampleScratchBytes);
+    const uint64_t budget = budget_opt > 0 ? (uint64_t)budget_opt : (uint64_t)2 << 30;
+    const uint64_t slab_bytes = (uint64_t)job.R_s * job.T_s * sizeof(float);
+    const size_t per_list = (size_t)std::min<uint64_t>((uint64_t)n_files, std::max<uint64_t>(budget / slab_bytes, 1));
+    // scratch frame 0 of a file: H frames ahead of its first frame, as far as the file reaches
+    std::vector<int64_t> frame0((size_t)n_files, 0);
+    for (int i = 0; i < n_files && opts->first_frame; i++) frame0[(size_t)i] = std::max<int64_t>(opts->first_frame[i] - (int64_t)job.H, 0);
+    if (int rc = afg::require_device()) return rc;
+    afg_front::ResamplePlane plane;                           // (declared in front of the drain: it holds what the uploads read)
+    afg_front::DevBuf scratch;
+    struct Drain { ~Drain() { (void)hipStreamSynchronize(nullptr); } } drain;
+    if (int rc = scratch.alloc((size_t)(per_list * slab_bytes))) return rc;
+    SampleOut so;
+    so.type = afg_front::kSampleCollate;
+    so.d_out = (float *)scratch.p;
+    so.C = job.R_s;
+    so.T = (uint32_t)job.T_s;
+    so.no_pad = true;
+    for (size_t f0 = 0; f0 < (size_t)n_files; f0 += per_list) {
+        const size_t n = std::min(per_list, (size_t)n_files - f0);
+        so.n_files = n;
+        so.first_frame = frame0.data() + f0;
+        // the collate pass at the files' own rates: a slab's place follows from the file's index in the sublist.  It returns
+        // with its streams drained; the items point at nothing it owns (messages are static), so its part is let go.
+        std::unique_ptr<BatchOut> part;
+        if (int rc = batch_decode_device(data + f0, length + f0, (int)n, opts->n_threads, items + f0, part, nullptr, so)) return rc;
+        if (int rc = plane.launch(job, (const float *)scratch.p, items + f0, n, opts->first_frame ? opts->first_frame + f0 : nullptr,
+                                  frame0.data() + f0, d_out + f0 * (size_t)job.C * job.T, messages, nullptr)) return rc;
+        AFG_HIP_CHECK(hipStreamSynchronize(nullptr));         // the scratch and the records are free for the next sublist
+    }
+    return AFG_OK;
+}
+
+// items (malloc'ed, n_files of them) and the strings their messages point into become what afg_batch_free lets go
+int batch_result_adopt(afg_batch_item *items, int n_files, std::deque<std::string> &messages, afg_batch_result *out)
+{
+    auto owner = std::unique_ptr<BatchOwner>(new BatchOwner);
+    owner->messages.swap(messages);                              // (a deque's elements stay where they are)
+    out->n_files = n_files;
+    out->items = items;
+    out->owner = owner.release();
+    return AFG_OK;
+}
+
+}  // namespace afg_front
+
+extern "C" {
+
 int afg_batch_decode_resampled(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
                                float *d_out, afg_batch_result *out)
 {
@@ -1884,84 +1983,16 @@ int afg_batch_decode_resampled(const uint8_t *const *data, const size_t *length,
             afg::set_error("afg_resample_opts.struct_size too small");
             return AFG_ERR_INVALID;
         }
-        if (opts->channels == 0 || opts->frames == 0) {
-            afg::set_error("afg_resample_opts: channels and frames must be at least 1 (%u, %u)", opts->channels, opts->frames);
-            return AFG_ERR_INVALID;
-        }
-        constexpr uint32_t kMaxRate = 1u << 20;
-        if (opts->samplerate == 0 || opts->samplerate > kMaxRate) {
-            afg::set_error("afg_resample_opts.samplerate %u: 1 .. %u Hz", opts->samplerate, kMaxRate);
-            return AFG_ERR_INVALID;
-        }
-        if (opts->mono > 1 || (opts->mono && opts->channels != 1)) {
-            afg::set_error("afg_resample_opts.mono %u with %u channels: mono is 0 or 1, and a mono tensor has one channel", opts->mono, opts->channels);
-            return AFG_ERR_INVALID;
-        }
-        if (opts->in_channels > 0xffff) { afg::set_error("afg_resample_opts.in_channels %u: at most 65535 (0 means 2)", opts->in_channels); return AFG_ERR_INVALID; }
-        if (opts->max_in_rate > kMaxRate) { afg::set_error("afg_resample_opts.max_in_rate %u: at most %u Hz (0 means 48000)", opts->max_in_rate, kMaxRate); return AFG_ERR_INVALID; }
-        if (opts->lowpass_width > 64) { afg::set_error("afg_resample_opts.lowpass_width %u: at most 64 (0 means 6)", opts->lowpass_width); return AFG_ERR_INVALID; }
-        if (n_files < 0 || (n_files && (!data || !length))) { afg::set_error("afg_batch_decode_resampled: n_files %d, or no file list", n_files); return AFG_ERR_INVALID; }
-        for (int i = 0; i < n_files && opts->first_frame; i++)
-            if (opts->first_frame[i] < 0) { afg::set_error("afg_resample_opts.first_frame[%d] is negative", i); return AFG_ERR_INVALID; }
         afg_front::ResampleJob job;
-        job.C = opts->channels;
-        job.T = opts->frames;
-        job.samplerate = opts->samplerate;
-        job.mono = opts->mono != 0;
-        job.Z = opts->lowpass_width ? opts->lowpass_width : 6;
-        job.in_channels = opts->in_channels ? opts->in_channels : 2;
-        job.max_in_rate = opts->max_in_rate ? opts->max_in_rate : 48000;
-        job.plan();
-        if (job.T_s > 0xffffffffull) {
-            afg::set_error("afg_batch_decode_resampled: %u frames at %u Hz from files of up to %u Hz: a scratch row of 2^32 floats or more", job.T,
-                           job.samplerate, job.max_in_rate);
-            return AFG_ERR_INVALID;
-        }
+        if (int rc = afg_front::resampled_check(opts, data, length, n_files, job)) return rc;
         if (n_files == 0) return AFG_OK;
-        if ((uint64_t)opts->channels * opts->frames > (((uint64_t)1 << 62) / (uint64_t)n_files)) {
-            afg::set_error("afg_batch_decode_resampled: a tensor of %d x %u x %u floats", n_files, opts->channels, opts->frames);
-            return AFG_ERR_INVALID;
-        }
-        // the sublists: as many files as the scratch budget holds, one at the least
-        const long budget_opt = afg::dev_option(afg::kDevResampleScratchBytes);
-        const uint64_t budget = budget_opt > 0 ? (uint64_t)budget_opt : (uint64_t)2 << 30;
-        const uint64_t slab_bytes = (uint64_t)job.R_s * job.T_s * sizeof(float);
-        const size_t per_list = (size_t)std::min<uint64_t>((uint64_t)n_files, std::max<uint64_t>(budget / slab_bytes, 1));
-        // scratch frame 0 of a file: H frames ahead of its first frame, as far as the file reaches
-        std::vector<int64_t> frame0((size_t)n_files, 0);
-        for (int i = 0; i < n_files && opts->first_frame; i++) frame0[(size_t)i] = std::max<int64_t>(opts->first_frame[i] - (int64_t)job.H, 0);
-        auto owner = std::unique_ptr<BatchOwner>(new BatchOwner);
         afg_batch_item *items = (afg_batch_item *)std::calloc((size_t)n_files, sizeof(afg_batch_item));
         if (!items) return AFG_ERR_OOM;
         struct ItemsGuard { afg_batch_item *p; ~ItemsGuard() { std::free(p); } } items_guard{ items };
-        if (int rc = afg::require_device()) return rc;
-        afg_front::ResamplePlane plane;                           // (declared in front of the drain: it holds what the uploads read)
-        afg_front::DevBuf scratch;
-        struct Drain { ~Drain() { (void)hipStreamSynchronize(nullptr); } } drain;
-        if (int rc = scratch.alloc((size_t)(per_list * slab_bytes))) return rc;
-        SampleOut so;
-        so.type = afg_front::kSampleCollate;
-        so.d_out = (float *)scratch.p;
-        so.C = job.R_s;
-        so.T = (uint32_t)job.T_s;
-        so.no_pad = true;
-        for (size_t f0 = 0; f0 < (size_t)n_files; f0 += per_list) {
-            const size_t n = std::min(per_list, (size_t)n_files - f0);
-            so.n_files = n;
-            so.first_frame = frame0.data() + f0;
-            // the collate pass at the files' own rates: a slab's place follows from the file's index in the sublist.  It returns
-            // with its streams drained; the items point at nothing it owns (messages are static), so its part is let go.
-            std::unique_ptr<BatchOut> part;
-            if (int rc = batch_decode_device(data + f0, length + f0, (int)n, opts->n_threads, items + f0, part, nullptr, so)) return rc;
-            if (int rc = plane.launch(job, (const float *)scratch.p, items + f0, n, opts->first_frame ? opts->first_frame + f0 : nullptr,
-                                      frame0.data() + f0, d_out + f0 * (size_t)job.C * job.T, owner->messages, nullptr)) return rc;
-            AFG_HIP_CHECK(hipStreamSynchronize(nullptr));         // the scratch and the records are free for the next sublist
-        }
+        std::deque<std::string> messages;
+        if (int rc = afg_front::resampled_run(job, opts, data, length, n_files, d_out, items, messages)) return rc;
         items_guard.p = nullptr;
-        out->n_files = n_files;
-        out->items = items;
-        out->owner = owner.release();
-        return AFG_OK;
+        return afg_front::batch_result_adopt(items, n_files, messages, out);
     } catch (...) {
         afg::set_error("out of host memory");
         return AFG_ERR_OOM;

@@ -173,6 +173,30 @@ struct ResamplePlane {
     int launch(const ResampleJob &job, const float *d_scratch, afg_batch_item *items, size_t n, const int64_t *first_frame,
                const int64_t *scratch_frame0, float *d_out, std::deque<std::string> &messages, hipStream_t st);
 };
+// afg_batch_decode_resampled in two steps (afg_host.cpp), for an entry that runs it into a tensor of its own
+// (afg_batch_decode_mel): the checks of the options behind struct_size, which fill in the job and touch no device; then the
+// tensor of a checked call into d_out, with `items` (n_files of them, zeroed) and the strings of `messages` as the entry
+// returns them.  batch_result_adopt hands malloc'ed items and those strings to a result afg_batch_free lets go.
+int resampled_check(const afg_resample_opts *opts, const uint8_t *const *data, const size_t *length, int n_files, ResampleJob &job);
+int resampled_run(const ResampleJob &job, const afg_resample_opts *opts, const uint8_t *const *data, const size_t *length, int n_files,
+                  float *d_out, afg_batch_item *items, std::deque<std::string> &messages);
+int batch_result_adopt(afg_batch_item *items, int n_files, std::deque<std::string> &messages, afg_batch_result *out);
+
+// ---- mel spectrogram features (afg_batch_decode_mel, host/afg_melspec.cpp) ----
+// The tables of one parameter set, made once and kept for the process: afg_mel_basis's and afg_mel_filters'.
+struct MelTables {
+    std::shared_ptr<const std::vector<float>> basis, filters;
+};
+int mel_tables(const afg_mel_opts &o, MelTables &t);            // AFG_ERR_INVALID: afg_last_error says why
+// One launch of afg_melspec_hip (csrc/melspec.hip) over rows [0, n_rows) of T samples each, contiguous in d_in, to slabs of
+// n_mels * n_out floats, contiguous in d_out.  The object holds the records its upload reads, and the tables on the device
+// (uploaded on the first launch): it lives until `st` has drained.
+struct MelPlane {
+    std::vector<afg_mel_row> recs;
+    DevBuf d_recs, d_basis, d_filters;
+    bool tables_up = false;
+    int launch(const afg_mel_opts &o, const MelTables &t, const float *d_in, uint64_t n_rows, float *d_out, hipStream_t st);
+};
 
 // The conversion that follows a stage's kernels, by what `out` asks for: floats [c0, c0 + n) of the stage's 4-byte plane
 // (elements of `kind`; d_in[0] is element `origin` of it) go to the same samples of its converted mirror (d_out[0] is the

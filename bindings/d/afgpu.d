@@ -456,6 +456,26 @@ int afg_resample_hip(ulong n_rows, const(afg_resample_row)* d_rows, ulong n_tile
 struct afg_resample_opts { uint struct_size; int n_threads; uint channels; uint frames; const(long)* first_frame; uint samplerate, mono, in_channels, max_in_rate, lowpass_width; }
 int afg_batch_decode_resampled(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_resample_opts)* opts,
                                float* d_out, afg_batch_result* result);
+
+// mel spectrogram features behind it (afg.h has the definition; the reference has no such stage)
+enum { AFG_MEL_PAD_REFLECT = 0, AFG_MEL_PAD_ZERO = 1 }
+enum { AFG_MEL_POWER = 0, AFG_MEL_LOG10 = 1 }
+enum { AFG_MEL_SCALE_SLANEY = 0, AFG_MEL_SCALE_HTK = 1 }
+enum { AFG_MEL_NORM_NONE = 0, AFG_MEL_NORM_SLANEY = 1 }
+struct afg_mel_params { uint n_fft, win_length, hop, n_mels, center, pad_mode, out_kind; float log_floor; }
+struct afg_mel_row { ulong in_off, out_off, first_tile; uint in_frames, out_frames; }
+ulong afg_mel_basis(uint n_fft, uint win_length, float* out_, ulong cap);
+ulong afg_mel_filters(uint samplerate, uint n_fft, uint n_mels, double f_min, double f_max, uint scale, uint norm, float* out_, ulong cap);
+uint afg_mel_frames(const(afg_mel_params)* params, uint in_frames);
+ulong afg_mel_layout(afg_mel_row* rows, ulong n_rows, const(afg_mel_params)* params);
+int afg_mel_check_rows(const(afg_mel_row)* rows, ulong n_rows, ulong n_tiles, const(afg_mel_params)* params, ulong in_floats,
+                       ulong basis_floats, ulong filters_floats, ulong out_floats);
+int afg_melspec_hip(ulong n_rows, const(afg_mel_row)* d_rows, ulong n_tiles, const(afg_mel_params)* params, const(float)* d_in,
+                    ulong in_floats, const(float)* d_basis, ulong basis_floats, const(float)* d_filters, ulong filters_floats,
+                    float* d_out, ulong out_floats, void* hip_stream);
+struct afg_mel_opts { uint struct_size; int n_threads; uint channels; uint frames; const(long)* first_frame; uint samplerate, mono, in_channels, max_in_rate, lowpass_width, n_out; afg_mel_params mel; uint scale, norm; double f_min, f_max; }
+int afg_batch_decode_mel(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_mel_opts)* opts, float* d_out,
+                         afg_batch_result* out_);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

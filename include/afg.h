@@ -1162,6 +1162,126 @@ typedef struct afg_resample_opts {
 int afg_batch_decode_resampled(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
                                float *d_out, afg_batch_result *out);
 
+/* Log-mel spectrogram features behind the tensor at one sample rate: a short-time Fourier transform by direct matrix
+ * product, the power spectrum, a dense mel filter bank and an optional log10, in one kernel on the float32 matrix
+ * instruction.  The reference has no such stage (and no resampler either), so nothing of it is restated here: the
+ * definition below is this library's own, and tests/melspec_model.py states it again in numpy.
+ *
+ * Parameters of a call (afg_mel_params), uniform over its rows: n_fft 16 .. 2048, win_length 1 .. n_fft, hop 1 .. n_fft,
+ * n_mels 1 .. 256, center 0 or 1, pad_mode AFG_MEL_PAD_REFLECT or AFG_MEL_PAD_ZERO, out_kind AFG_MEL_POWER or
+ * AFG_MEL_LOG10, log_floor a finite float >= 0 (0 means 1e-10f).  n_bins = n_fft / 2 + 1.
+ *
+ * Basis, computed on the host in double and rounded once to float32.  The window is a periodic Hann of win_length,
+ * w[j] = 0.5 - 0.5 cos(2 pi j / win_length), centred in the frame: n_lo = (n_fft - win_length) / 2 and sample n of a frame
+ * uses w[n - n_lo].  For n in [n_lo, n_lo + win_length) and k in [0, n_bins):
+ *   C[n][k] = float32( w * cos(2 pi ((n * k) mod n_fft) / n_fft)),  S[n][k] = float32(-w * sin(2 pi ((n * k) mod n_fft) / n_fft)),
+ * the product n * k reduced in integers before the trigonometry.
+ *
+ * Frame f of a row of in_frames samples: sample n is x[idx(f * hop + n - pad)] with pad = center ? n_fft / 2 : 0.  An index
+ * outside [0, in_frames) is reflected without repeating the edge (-i -> i, in_frames - 1 + i -> in_frames - 1 - i) or
+ * contributes +0.0f, according to pad_mode.  Reflect needs in_frames > pad: a record with output that breaks this is refused
+ * before the launch.  The row has max_frames = 1 + (in_frames + 2 pad - n_fft) / hop frames, 0 when the numerator is negative
+ * (afg_mel_frames); a record asks for out_frames <= max_frames.
+ *
+ * Arithmetic: every sum starts from +0.0f and runs in ascending index order, one fmaf per term and nothing wider:
+ *   re[k] = chain over n = n_lo .. n_lo + win_length - 1 of fmaf(x_n, C[n][k], acc), im[k] likewise with S,
+ *   p[k] = fmaf(im, im, re * re) with the product rounded to float32,
+ *   mel[m] = chain over k = 0 .. n_bins - 1 of fmaf(Wm[m][k], p[k], acc): all bins, a dense weight matrix.
+ * AFG_MEL_POWER delivers mel, AFG_MEL_LOG10 log10f(fmaxf(mel, log_floor)) (fmaxf: a NaN mel gives the floor).
+ * Output: [rows, n_mels, out_frames] float32, frames contiguous: record r's mel m, frame f at out_off + m * out_frames + f.
+ *
+ * afg_mel_basis: host only.  Returns win_length * ld floats, ld = 2 * nb16 and nb16 = n_bins rounded up to 16, and with
+ * cap >= that fills out[j * ld + k] = C[n_lo + j][k] and out[j * ld + nb16 + k] = S[n_lo + j][k], +0.0f in the columns
+ * k >= n_bins (out may be NULL with cap 0).  Returns 0 with afg_last_error set for n_fft or win_length out of range.
+ *
+ * afg_mel_filters: host only.  Returns n_mels * n_bins and with cap >= that fills out[m * n_bins + k] = Wm[m][k]: n_mels + 2
+ * points equally spaced on the mel scale from f_min to f_max (0 means samplerate / 2), converted back to Hz as
+ * f[0 .. n_mels + 1]; bin k lies at fk = k * samplerate / n_fft;
+ *   Wm[m][k] = max(0, min((fk - f[m]) / (f[m+1] - f[m]), (f[m+2] - fk) / (f[m+2] - f[m+1]))),
+ * with AFG_MEL_NORM_SLANEY times 2 / (f[m+2] - f[m]); computed in double, rounded once to float32.  Scales:
+ * AFG_MEL_SCALE_SLANEY mel = 3 f / 200 below 1000 Hz, 15 + 27 ln(f / 1000) / ln 6.4 above; AFG_MEL_SCALE_HTK
+ * 2595 log10(1 + f / 700).  Returns 0 with afg_last_error set for samplerate 0, n_fft or n_mels out of range, an unknown
+ * scale or norm, or not 0 <= f_min < f_max <= samplerate / 2.  The kernel entry takes any dense float32 [n_mels, n_bins]
+ * matrix of the caller's own instead. */
+#define AFG_MEL_PAD_REFLECT 0
+#define AFG_MEL_PAD_ZERO    1
+#define AFG_MEL_POWER       0
+#define AFG_MEL_LOG10       1
+#define AFG_MEL_SCALE_SLANEY 0
+#define AFG_MEL_SCALE_HTK    1
+#define AFG_MEL_NORM_NONE    0
+#define AFG_MEL_NORM_SLANEY  1
+typedef struct afg_mel_params {     /* 32 bytes */
+    uint32_t n_fft, win_length, hop, n_mels;
+    uint32_t center, pad_mode, out_kind;
+    float    log_floor;
+} afg_mel_params;
+typedef struct afg_mel_row {        /* one input row and its [n_mels, out_frames] output (32 bytes) */
+    uint64_t in_off;      /* float index in d_in of sample 0 */
+    uint64_t out_off;     /* float index in d_out of mel 0, frame 0 */
+    uint64_t first_tile;  /* filled in by afg_mel_layout */
+    uint32_t in_frames;   /* samples of the row; 0: d_in is not read */
+    uint32_t out_frames;  /* frames written per mel, <= afg_mel_frames(params, in_frames) */
+} afg_mel_row;
+uint64_t afg_mel_basis(uint32_t n_fft, uint32_t win_length, float *out, uint64_t cap);
+uint64_t afg_mel_filters(uint32_t samplerate, uint32_t n_fft, uint32_t n_mels, double f_min, double f_max, uint32_t scale, uint32_t norm,
+                         float *out, uint64_t cap);
+/* max_frames of a row of in_frames samples; 0 for params out of range (afg_last_error set). */
+uint32_t afg_mel_frames(const afg_mel_params *params, uint32_t in_frames);
+/* Host: gives every row its tiles (first_tile) and returns the launch's tile count.  A tile is 64 frames of one row, fewer
+ * (32, 16) while the tile's frames -- one LDS row of win_length samples each -- exceed the tile's LDS.  Returns 0 with
+ * afg_last_error set for params out of range. */
+uint64_t afg_mel_layout(afg_mel_row *rows, uint64_t n_rows, const afg_mel_params *params);
+/* Host: the checks afg_melspec_hip makes on every record before it launches, on a host copy of the records: params in
+ * range; basis_floats and filters_floats at least what afg_mel_basis and the bank need; first_tile and n_tiles as
+ * afg_mel_layout gives them; every row's in_frames floats inside [0, in_floats); out_frames <= max_frames; reflect with
+ * output only with in_frames > pad; its n_mels * out_frames floats inside [0, out_floats).  AFG_ERR_INVALID with
+ * afg_last_error set otherwise. */
+int afg_mel_check_rows(const afg_mel_row *rows, uint64_t n_rows, uint64_t n_tiles, const afg_mel_params *params, uint64_t in_floats,
+                       uint64_t basis_floats, uint64_t filters_floats, uint64_t out_floats);
+/* Runs every row in one launch, one workgroup per tile.  d_rows is the device copy of rows laid out by afg_mel_layout,
+ * n_tiles what it returned; d_basis is afg_mel_basis's table and d_filters a dense [n_mels, n_bins] bank, both on the
+ * device; the planes are 4-byte aligned and do not overlap (d_in may be NULL when no row reads it).  Params are checked
+ * first, then every record (the entry fetches d_rows on hip_stream and waits for it) as afg_mel_check_rows does; anything
+ * else than a pass is AFG_ERR_INVALID and nothing is written.  The kernel writes exactly n_mels * out_frames floats per
+ * record and reads no input float outside the record's row. */
+int afg_melspec_hip(uint64_t n_rows, const afg_mel_row *d_rows, uint64_t n_tiles, const afg_mel_params *params, const float *d_in,
+                    uint64_t in_floats, const float *d_basis, uint64_t basis_floats, const float *d_filters, uint64_t filters_floats,
+                    float *d_out, uint64_t out_floats, void *hip_stream);
+
+/* afg_batch_decode_resampled followed by afg_melspec_hip: d_out is n_files * channels * n_mels * n_out floats on the
+ * current device, and slab [i, k] is the definition above applied to row [i, k] of the tensor afg_batch_decode_resampled
+ * makes of the same list with the leading fields of the options (frames is T, in samples at `samplerate`).  n_out == 0
+ * means max_frames of T; otherwise n_out <= max_frames (Whisper takes 3000 of 3001), and reflect needs T > pad.  The tensor
+ * is a pooled scratch [files, channels, T]; a list whose scratch would exceed afg_dev_option("mel_scratch_bytes") (default
+ * 2 GiB) runs in sublists of at least one file.  The basis and the bank (afg_mel_filters of samplerate, n_fft, n_mels,
+ * f_min, f_max, scale, norm) are made once per parameter set and kept.  A file that failed or was refused upstream keeps
+ * its status and message, and its slab is what an all-zero row gives: +0.0f, or log10f(log_floor).  items[i] is as in
+ * afg_batch_decode_resampled; pcm points at the file's mel slab (NULL when the file failed or was refused).
+ * Checked before any device call, AFG_ERR_INVALID with afg_last_error set: everything afg_batch_decode_resampled checks, a
+ * struct_size below sizeof(afg_mel_opts), the mel parameters and the bank's arguments out of range, T without a frame,
+ * n_out above max_frames, reflect with T <= pad.  n_files == 0 is AFG_OK and touches nothing. */
+typedef struct afg_mel_opts {
+    uint32_t       struct_size;   /* sizeof(afg_mel_opts) */
+    int            n_threads;     /* from here to lowpass_width: as afg_resample_opts */
+    uint32_t       channels;
+    uint32_t       frames;        /* T, samples at `samplerate` */
+    const int64_t *first_frame;
+    uint32_t       samplerate;
+    uint32_t       mono;
+    uint32_t       in_channels;
+    uint32_t       max_in_rate;
+    uint32_t       lowpass_width;
+    uint32_t       n_out;         /* frames per mel row; 0 means max_frames of T */
+    afg_mel_params mel;
+    uint32_t       scale;         /* AFG_MEL_SCALE_* */
+    uint32_t       norm;          /* AFG_MEL_NORM_* */
+    double         f_min;         /* Hz */
+    double         f_max;         /* Hz; 0 means samplerate / 2 */
+} afg_mel_opts;
+int afg_batch_decode_mel(const uint8_t *const *data, const size_t *length, int n_files, const afg_mel_opts *opts, float *d_out,
+                         afg_batch_result *out);
+
 #ifdef __cplusplus
 }
 #endif
