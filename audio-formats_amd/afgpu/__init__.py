@@ -73,6 +73,9 @@ MEL_PAD_REFLECT, MEL_PAD_ZERO = 0, 1             # afg_mel_params.pad_mode
 MEL_POWER, MEL_LOG10 = 0, 1                      # afg_mel_params.out_kind
 MEL_SCALE_SLANEY, MEL_SCALE_HTK = 0, 1
 MEL_NORM_NONE, MEL_NORM_SLANEY = 0, 1
+NORM_NONE, NORM_PEAK, NORM_RMS, NORM_STANDARD, NORM_DYNAMIC_RANGE = range(5)     # afg_norm_params.mode
+NORM_MODE_NAMES = {"none": NORM_NONE, "peak": NORM_PEAK, "rms": NORM_RMS, "standard": NORM_STANDARD, "dynamic_range": NORM_DYNAMIC_RANGE}
+NORM_TILE = 4096                                 # floats of one row per tile of afg_normalize_hip
 
 # every symbol include/afg.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -109,6 +112,7 @@ ABI_SYMBOLS = [
     "afg_collate_layout", "afg_collate_hip", "afg_batch_decode_to_device",
     "afg_resample_taps", "afg_resample_layout", "afg_resample_hip", "afg_batch_decode_resampled",
     "afg_mel_basis", "afg_mel_filters", "afg_mel_frames", "afg_mel_layout", "afg_mel_check_rows", "afg_melspec_hip", "afg_batch_decode_mel",
+    "afg_norm_layout", "afg_norm_check_groups", "afg_normalize_hip", "afg_batch_decode_resampled_norm", "afg_batch_decode_mel_norm",
 ]
 
 
@@ -257,6 +261,29 @@ class MelOpts(C.Structure):
     """afg_mel_opts (afg_batch_decode_mel): afg_resample_opts' fields, then the mel parameters and the bank's."""
     _fields_ = ResampleOpts._fields_ + [("n_out", C.c_uint32), ("mel", MelParams), ("scale", C.c_uint32), ("norm", C.c_uint32),
                                         ("f_min", C.c_double), ("f_max", C.c_double)]
+
+
+class NormGroup(C.Structure):
+    """afg_norm_group: the rows one set of statistics covers (afg_normalize_hip)."""
+    _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("stride", C.c_uint64), ("first_tile", C.c_uint64),
+                ("rows", C.c_uint32), ("valid", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class NormStats(C.Structure):
+    """afg_norm_stats: one group's record."""
+    _fields_ = [("sum", C.c_double), ("sumsq", C.c_double), ("count", C.c_uint64), ("min", C.c_float), ("max", C.c_float),
+                ("offset", C.c_float), ("scale", C.c_float)]
+
+
+class NormParams(C.Structure):
+    """afg_norm_params."""
+    _fields_ = [("mode", C.c_uint32), ("target", C.c_float), ("eps", C.c_float), ("range", C.c_float), ("shift", C.c_float),
+                ("gain", C.c_float)]
+
+
+NORM_GROUP_DTYPE = np.dtype(NormGroup)           # arrays of the records, as the other stages' *_DTYPE
+NORM_STATS_DTYPE = np.dtype(NormStats)
+assert NORM_GROUP_DTYPE.itemsize == 48 and NORM_STATS_DTYPE.itemsize == 40 and C.sizeof(NormParams) == 24
 
 
 SAMPLE_F32, SAMPLE_F64, SAMPLE_PCM_S8, SAMPLE_PCM_S16, SAMPLE_PCM_S24 = range(5)     # afg_batch_opts.sample_type
@@ -500,6 +527,13 @@ def lib():
     L.afg_mel_check_rows.argtypes = [vp, u64, u64, C.POINTER(MelParams), u64, u64, u64, u64]
     L.afg_melspec_hip.argtypes = [u64, vp, u64, C.POINTER(MelParams), vp, u64, vp, u64, vp, u64, vp, u64, vp]
     L.afg_batch_decode_mel.argtypes = [vp, vp, C.c_int, C.POINTER(MelOpts), vp, C.POINTER(BatchResult)]
+    L.afg_norm_layout.argtypes = [vp, u64]
+    L.afg_norm_layout.restype = u64
+    L.afg_norm_check_groups.argtypes = [vp, u64, u64, C.POINTER(NormParams), u64, u64]
+    L.afg_normalize_hip.argtypes = [u64, vp, u64, C.POINTER(NormParams), vp, u64, vp, u64, vp, vp, vp]
+    L.afg_batch_decode_resampled_norm.argtypes = [vp, vp, C.c_int, C.POINTER(ResampleOpts), C.POINTER(NormParams), vp, vp, C.POINTER(BatchResult)]
+    L.afg_batch_decode_mel_norm.argtypes = [vp, vp, C.c_int, C.POINTER(MelOpts), C.POINTER(NormParams), C.POINTER(NormParams), vp,
+                                            C.POINTER(BatchResult)]
     _lib = L
     _sync_dev_options(L)
     return L
@@ -1565,6 +1599,141 @@ def batch_decode_mel(files, frames, samplerate=16000, n_fft=400, hop=160, n_mels
         return out, meta
     finally:
         lib().afg_batch_free(C.byref(res))
+
+
+def norm_params(mode, target=1.0, eps=0.0, range=8.0, shift=4.0, gain=0.25):
+    """afg_norm_params.  mode: NORM_* or its name ("none", "peak", "rms", "standard", "dynamic_range"); "whisper" is
+    dynamic_range with range 8, shift 4, gain 0.25.  A NormParams passes through.  ValueError for an unknown name."""
+    if isinstance(mode, NormParams):
+        return mode
+    if isinstance(mode, str):
+        if mode == "whisper":
+            return NormParams(NORM_DYNAMIC_RANGE, 1.0, 0.0, 8.0, 4.0, 0.25)
+        if mode not in NORM_MODE_NAMES:
+            raise ValueError(f"norm_params: unknown mode {mode!r}: one of {sorted(NORM_MODE_NAMES)} or 'whisper'")
+        mode = NORM_MODE_NAMES[mode]
+    return NormParams(int(mode), float(target), float(eps), float(range), float(shift), float(gain))
+
+
+def norm_layout(groups):
+    """afg_norm_layout: fills first_tile of a NORM_GROUP_DTYPE array in place; returns the launch's tile count."""
+    assert groups.dtype == NORM_GROUP_DTYPE and groups.flags.c_contiguous
+    return int(lib().afg_norm_layout(groups.ctypes.data, len(groups)))
+
+
+def norm_check_groups(groups, n_tiles, params, in_floats, out_floats):
+    """afg_norm_check_groups: what afg_normalize_hip checks before it launches, on host records.  AfgError when one fails."""
+    assert groups.dtype == NORM_GROUP_DTYPE and groups.flags.c_contiguous
+    check(lib().afg_norm_check_groups(groups.ctypes.data, len(groups), int(n_tiles), C.byref(params), int(in_floats), int(out_floats)))
+
+
+def normalize(n_groups, d_groups, n_tiles, params, d_in, in_floats, d_out, out_floats, d_partials, d_stats, stream=None):
+    """Enqueue the normalisation kernels (afg_normalize_hip) on device arrays: the statistics of every group into d_stats
+    (NORM_STATS_DTYPE records), and -- unless the mode is NORM_NONE, where d_out may be None -- every valid element scaled into
+    d_out (d_in itself for in place).  d_partials: n_tiles * 32 bytes.  The groups are checked first (the call waits for
+    `stream` to read them): AfgError, and nothing written, when one fails."""
+    check(lib().afg_normalize_hip(int(n_groups), _ptr(d_groups), int(n_tiles), C.byref(params), _ptr(d_in), int(in_floats), _ptr(d_out),
+                                  int(out_floats), _ptr(d_partials), _ptr(d_stats), _stream(stream)))
+
+
+def _batch_tensor_call(who, files, shape, out, first_frame, call):
+    """What the normalised batch calls share: the output tensor checked or made, the file list as C arrays, call(ptrs, lens,
+    n, first_frame array, out, result) run, and the items' metadata read.  Returns (out, meta)."""
+    import torch
+    bufs = [bytes(f) for f in files]
+    n = len(bufs)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+    else:
+        if tuple(out.shape) != shape or out.dtype != torch.float32:
+            raise ValueError(f"{who}: out must be a float32 tensor of shape {shape}")
+        if not out.is_cuda or out.device.index != torch.cuda.current_device():
+            raise ValueError(f"{who}: out must live on the current device")
+        if not out.is_contiguous():
+            raise ValueError(f"{who}: out must be contiguous")
+    if n == 0:
+        return out, []
+    if get_device() != torch.cuda.current_device():
+        raise ValueError(f"{who}: HIP's current device is {get_device()}, torch's {torch.cuda.current_device()}")
+    torch.cuda.current_stream().synchronize()                # (as batch_decode_tensor: the library's streams are ordered with nobody's)
+    ff = None
+    if first_frame is not None:
+        if len(first_frame) != n:
+            raise ValueError(f"{who}: one first_frame per file")
+        ff = (C.c_int64 * n)(*[int(v) for v in first_frame])
+    ptrs = (C.c_char_p * n)(*bufs)
+    lens = (C.c_size_t * n)(*[len(b) for b in bufs])
+    res = BatchResult()
+    check(call(ptrs, lens, n, ff, out, res))
+    try:
+        meta = []
+        for i in range(res.n_files):
+            it = res.items[i]
+            meta.append({"status": it.status, "message": None if it.message is None else it.message.decode(),
+                         "format": it.format, "channels": it.channels, "samplerate": it.samplerate, "frames": it.frames})
+        return out, meta
+    finally:
+        lib().afg_batch_free(C.byref(res))
+
+
+def batch_decode_tensor_normalized(files, frames, channels, samplerate, mode, target=1.0, eps=0.0, range=8.0, shift=4.0, gain=0.25,
+                                   first_frame=None, mono=False, in_channels=0, max_in_rate=0, lowpass_width=0, out=None, n_threads=0,
+                                   return_stats=False):
+    """afg_batch_decode_resampled_norm: batch_decode_tensor_resampled, then every file normalised in place over its own
+    samples -- its channel rows one group, the padding left out of the statistics and left as it is.  mode and its
+    parameters: norm_params.  return_stats: (tensor, meta, stats), stats a NORM_STATS_DTYPE array with one record per file
+    (all zero for a file that failed).  The same device and stream rules as batch_decode_tensor."""
+    import torch
+    prm = norm_params(mode, target, eps, range, shift, gain)
+    frames, channels, samplerate = int(frames), int(channels), int(samplerate)
+    if frames < 1 or channels < 1 or samplerate < 1:
+        raise ValueError("batch_decode_tensor_normalized: frames, channels and samplerate must be at least 1")
+    if mono and channels != 1:
+        raise ValueError("batch_decode_tensor_normalized: a mono tensor has one channel")
+    n = len(files)
+    d_stats = torch.zeros(max(n, 1) * NORM_STATS_DTYPE.itemsize, dtype=torch.uint8, device="cuda") if return_stats else None
+
+    def call(ptrs, lens, n, ff, out, res):
+        opts = ResampleOpts(C.sizeof(ResampleOpts), int(n_threads), channels, frames, ff, samplerate, 1 if mono else 0, int(in_channels),
+                            int(max_in_rate), int(lowpass_width))
+        return lib().afg_batch_decode_resampled_norm(ptrs, lens, n, C.byref(opts), C.byref(prm), out.data_ptr(), _ptr(d_stats), C.byref(res))
+
+    out, meta = _batch_tensor_call("batch_decode_tensor_normalized", files, (n, channels, frames), out, first_frame, call)
+    if not return_stats:
+        return out, meta
+    return out, meta, d_stats.cpu().numpy().view(NORM_STATS_DTYPE)[:n].copy()
+
+
+def batch_decode_mel_normalized(files, frames, samplerate=16000, n_fft=400, hop=160, n_mels=80, win_length=None, center=True,
+                                pad_mode=MEL_PAD_REFLECT, out_kind=MEL_LOG10, mono=True, out=None, channels=1, n_out=0, log_floor=0.0,
+                                f_min=0.0, f_max=0.0, scale=MEL_SCALE_SLANEY, norm=MEL_NORM_SLANEY, first_frame=None, in_channels=0,
+                                max_in_rate=0, lowpass_width=0, n_threads=0, wave_norm=None, feat_norm=None):
+    """afg_batch_decode_mel_norm: batch_decode_mel with wave_norm applied to every file's samples in front of the features
+    and feat_norm to every [n_mels, n_out] slab behind them.  Each is None, a NormParams (norm_params), or a mode name;
+    feat_norm="whisper" is Whisper's max(x, x.max() - 8), then (x + 4) / 4."""
+    wave = None if wave_norm is None else norm_params(wave_norm)
+    feat = None if feat_norm is None else norm_params(feat_norm)
+    frames, channels, samplerate = int(frames), int(channels), int(samplerate)
+    if frames < 1 or channels < 1 or samplerate < 1:
+        raise ValueError("batch_decode_mel_normalized: frames, channels and samplerate must be at least 1")
+    if mono and channels != 1:
+        raise ValueError("batch_decode_mel_normalized: a mono tensor has one channel")
+    prm = mel_params(n_fft, hop, n_mels, win_length, center, pad_mode, out_kind, log_floor)
+    most = mel_frames(prm, frames)
+    if most == 0:
+        raise ValueError(f"batch_decode_mel_normalized: {frames} samples hold no frame of these parameters ({lib().afg_last_error().decode()})")
+    n_out = int(n_out)
+    if n_out < 0 or n_out > most:
+        raise ValueError(f"batch_decode_mel_normalized: n_out {n_out}, but {frames} samples have {most} frames")
+
+    def call(ptrs, lens, n, ff, out, res):
+        opts = MelOpts(C.sizeof(MelOpts), int(n_threads), channels, frames, ff, samplerate, 1 if mono else 0, int(in_channels),
+                       int(max_in_rate), int(lowpass_width), n_out, prm, int(scale), int(norm), float(f_min), float(f_max))
+        return lib().afg_batch_decode_mel_norm(ptrs, lens, n, C.byref(opts), None if wave is None else C.byref(wave),
+                                               None if feat is None else C.byref(feat), out.data_ptr(), C.byref(res))
+
+    return _batch_tensor_call("batch_decode_mel_normalized", files, (len(files), channels, int(n_mels), n_out if n_out else most), out,
+                              first_frame, call)
 
 
 def batch_transcode(files, options=None, n_threads=0, devices=None):

@@ -78,6 +78,11 @@ int melspec_launch(const afg_mel_row *h_rows, uint64_t n_rows, const afg_mel_row
                    const float *d_in, uint64_t in_floats, const float *d_basis, uint64_t basis_floats, const float *d_filters,
                    uint64_t filters_floats, float *d_out, uint64_t out_floats, hipStream_t stream);
 
+// afg_normalize_hip likewise (normalize.hip)
+int normalize_launch(const afg_norm_group *h_groups, uint64_t n_groups, const afg_norm_group *d_groups, uint64_t n_tiles,
+                     const afg_norm_params *params, const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats,
+                     void *d_partials, afg_norm_stats *d_stats, hipStream_t stream);
+
 // Owns a device buffer filled from a host array at plan creation.
 struct DeviceArray {
     void *ptr = nullptr;

@@ -1,6 +1,7 @@
 // afg_melspec.cpp -- the host half of the mel spectrogram features (afg_stage.h: MelTables, MelPlane): the basis and the
 // filter bank of include/afg.h's definition, computed in double and kept per parameter set, and afg_batch_decode_mel -- the
-// resampled tensor into a pooled scratch, then one afg_melspec_hip launch per sublist.
+// resampled tensor into a pooled scratch, then one afg_melspec_hip launch per sublist, with the optional normalisations of
+// afg_batch_decode_mel_norm around it.
 #include "afg_stage.h"
 #include "../csrc/afg_common.h"
 
@@ -164,8 +165,10 @@ int MelPlane::launch(const afg_mel_opts &o, const MelTables &t, const float *d_i
 
 }  // namespace afg_front
 
-extern "C" int afg_batch_decode_mel(const uint8_t *const *data, const size_t *length, int n_files, const afg_mel_opts *opts, float *d_out,
-                                    afg_batch_result *out)
+// afg_batch_decode_mel, and with wave_norm / feat_norm afg_batch_decode_mel_norm: the tensor at one rate of a sublist,
+// normalised in place per file; its features; those normalised in place per slab
+int afg_front::mel_batch(const uint8_t *const *data, const size_t *length, int n_files, const afg_mel_opts *opts, const afg_norm_params *wave_norm,
+                         const afg_norm_params *feat_norm, float *d_out, afg_batch_result *out)
 {
     try {
         // (all of this before any device call: it holds on a machine without a GPU too)
@@ -200,6 +203,14 @@ extern "C" int afg_batch_decode_mel(const uint8_t *const *data, const size_t *le
             afg::set_error("afg_batch_decode_mel: reflect padding of %u samples needs more than %u samples (frames is %u)", pad, pad, o.frames);
             return AFG_ERR_INVALID;
         }
+        if (wave_norm)
+            if (int rc = afg_norm_check_groups(nullptr, 0, 0, wave_norm, 0, 0)) return rc;
+        if (feat_norm)
+            if (int rc = afg_norm_check_groups(nullptr, 0, 0, feat_norm, 0, 0)) return rc;
+        if (feat_norm && (uint64_t)o.mel.n_mels * (o.n_out ? o.n_out : most) > 0xffffffffull) {
+            afg::set_error("afg_batch_decode_mel_norm: a slab of %u x %u floats is more than a group's row holds", o.mel.n_mels, o.n_out ? o.n_out : most);
+            return AFG_ERR_INVALID;
+        }
         if (n_files == 0) return AFG_OK;
         const uint32_t n_out = o.n_out ? o.n_out : most;
         const uint64_t slab_out = (uint64_t)o.channels * o.mel.n_mels * n_out, slab_in = (uint64_t)o.channels * o.frames;
@@ -217,6 +228,8 @@ extern "C" int afg_batch_decode_mel(const uint8_t *const *data, const size_t *le
         std::deque<std::string> messages;
         if (int rc = afg::require_device()) return rc;
         afg_front::MelPlane plane;                               // (declared in front of the drain: it holds what the uploads read)
+        afg_front::NormPlane wave, feat;
+        std::vector<afg_norm_group> groups;
         afg_front::DevBuf scratch;
         struct Drain { ~Drain() { (void)hipStreamSynchronize(nullptr); } } drain;
         if (int rc = scratch.alloc((size_t)(per_list * slab_in * sizeof(float)))) return rc;
@@ -226,9 +239,27 @@ extern "C" int afg_batch_decode_mel(const uint8_t *const *data, const size_t *le
             if (sub.first_frame) sub.first_frame += f0;
             // the tensor at one rate of the sublist, every element written (a failed file's slab is zero) ...
             if (int rc = afg_front::resampled_run(job, &sub, data + f0, length + f0, (int)n, (float *)scratch.p, items + f0, messages)) return rc;
+            if (wave_norm) {                                     // ... every file's rows as one group, over its own samples ...
+                groups.clear();
+                afg_front::norm_file_groups(job, items + f0, n, o.first_frame ? o.first_frame + f0 : nullptr, groups);
+                if (int rc = wave.launch(*wave_norm, groups, (float *)scratch.p, n * slab_in, nullptr, nullptr)) return rc;
+            }
             // ... and its features: one row per file and channel
             float *y = d_out + f0 * slab_out;
             if (int rc = plane.launch(o, tables, (const float *)scratch.p, n * o.channels, y, nullptr)) return rc;
+            if (feat_norm) {                                     // every slab one group of a single row
+                groups.clear();
+                afg_norm_group g;
+                std::memset(&g, 0, sizeof(g));
+                g.rows = 1;
+                g.valid = (uint32_t)((uint64_t)o.mel.n_mels * n_out);
+                g.stride = g.valid;
+                for (uint64_t k = 0; k < n * o.channels; k++) {
+                    g.in_off = g.out_off = k * g.valid;
+                    groups.push_back(g);
+                }
+                if (int rc = feat.launch(*feat_norm, groups, y, n * slab_out, nullptr, nullptr)) return rc;
+            }
             for (size_t i = 0; i < n; i++)
                 if (items[f0 + i].pcm) items[f0 + i].pcm = y + i * slab_out;
             AFG_HIP_CHECK(hipStreamSynchronize(nullptr));         // the scratch and the records are free for the next sublist
@@ -239,4 +270,16 @@ extern "C" int afg_batch_decode_mel(const uint8_t *const *data, const size_t *le
         afg::set_error("out of host memory");
         return AFG_ERR_OOM;
     }
+}
+
+extern "C" int afg_batch_decode_mel(const uint8_t *const *data, const size_t *length, int n_files, const afg_mel_opts *opts, float *d_out,
+                                    afg_batch_result *out)
+{
+    return afg_front::mel_batch(data, length, n_files, opts, nullptr, nullptr, d_out, out);
+}
+
+extern "C" int afg_batch_decode_mel_norm(const uint8_t *const *data, const size_t *length, int n_files, const afg_mel_opts *opts,
+                                         const afg_norm_params *wave_norm, const afg_norm_params *feat_norm, float *d_out, afg_batch_result *out)
+{
+    return afg_front::mel_batch(data, length, n_files, opts, wave_norm, feat_norm, d_out, out);
 }

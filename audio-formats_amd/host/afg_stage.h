@@ -198,6 +198,25 @@ struct MelPlane {
     int launch(const afg_mel_opts &o, const MelTables &t, const float *d_in, uint64_t n_rows, float *d_out, hipStream_t st);
 };
 
+// ---- normalisation (afg_batch_decode_resampled_norm, afg_batch_decode_mel_norm; host/afg_normalize.cpp) ----
+// The valid length of a file's rows in the tensor at one rate: min(T, ceil((frames - first_frame) * L / M)) with
+// M / L = in_rate / out_rate in lowest terms; 0 when that is not positive or a rate is 0.
+uint32_t norm_valid(int64_t frames, int64_t first_frame, uint32_t in_rate, uint32_t out_rate, uint32_t T);
+// The groups of files [0, n) of a tensor [n, C, T] made by resampled_run (items: what it returned for them).
+void norm_file_groups(const ResampleJob &job, const afg_batch_item *items, size_t n, const int64_t *first_frame, std::vector<afg_norm_group> &groups);
+// One afg_normalize_hip over `groups`, in place on d_plane (plane_floats of it), with the groups, the partials and -- when
+// the caller has none, d_stats NULL -- the records in pooled buffers.  The object holds what its upload reads: it lives until
+// `st` has drained.
+struct NormPlane {
+    std::vector<afg_norm_group> recs;
+    DevBuf d_recs, d_partials, d_own_stats;
+    int launch(const afg_norm_params &prm, std::vector<afg_norm_group> &groups, float *d_plane, uint64_t plane_floats, afg_norm_stats *d_stats,
+               hipStream_t st);
+};
+// afg_batch_decode_mel with its two optional normalisations (afg_melspec.cpp): both entries run through it
+int mel_batch(const uint8_t *const *data, const size_t *length, int n_files, const afg_mel_opts *opts, const afg_norm_params *wave_norm,
+              const afg_norm_params *feat_norm, float *d_out, afg_batch_result *out);
+
 // The conversion that follows a stage's kernels, by what `out` asks for: floats [c0, c0 + n) of the stage's 4-byte plane
 // (elements of `kind`; d_in[0] is element `origin` of it) go to the same samples of its converted mirror (d_out[0] is the
 // mirror of element `origin`) as doubles (afg_pcm_to_f64_hip) or packed integers (afg_pcm_pack_hip), or -- collate mode,

@@ -476,6 +476,21 @@ int afg_melspec_hip(ulong n_rows, const(afg_mel_row)* d_rows, ulong n_tiles, con
 struct afg_mel_opts { uint struct_size; int n_threads; uint channels; uint frames; const(long)* first_frame; uint samplerate, mono, in_channels, max_in_rate, lowpass_width, n_out; afg_mel_params mel; uint scale, norm; double f_min, f_max; }
 int afg_batch_decode_mel(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_mel_opts)* opts, float* d_out,
                          afg_batch_result* out_);
+// normalisation: statistics per group of rows and the gain / offset they decide (include/afg.h has the definition)
+enum : uint { AFG_NORM_NONE = 0, AFG_NORM_PEAK = 1, AFG_NORM_RMS = 2, AFG_NORM_STANDARD = 3, AFG_NORM_DYNAMIC_RANGE = 4 }
+struct afg_norm_group { ulong in_off, out_off, stride, first_tile; uint rows, valid; uint[2] reserved; }
+struct afg_norm_stats { double sum, sumsq; ulong count; float min, max, offset, scale; }
+struct afg_norm_params { uint mode; float target, eps, range, shift, gain; }
+ulong afg_norm_layout(afg_norm_group* groups, ulong n_groups);
+int afg_norm_check_groups(const(afg_norm_group)* groups, ulong n_groups, ulong n_tiles, const(afg_norm_params)* params,
+                          ulong in_floats, ulong out_floats);
+int afg_normalize_hip(ulong n_groups, const(afg_norm_group)* d_groups, ulong n_tiles, const(afg_norm_params)* params,
+                      const(float)* d_in, ulong in_floats, float* d_out, ulong out_floats, void* d_partials,
+                      afg_norm_stats* d_stats, void* hip_stream);
+int afg_batch_decode_resampled_norm(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_resample_opts)* opts,
+                                    const(afg_norm_params)* norm, float* d_out, afg_norm_stats* d_stats, afg_batch_result* out_);
+int afg_batch_decode_mel_norm(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_mel_opts)* opts,
+                              const(afg_norm_params)* wave_norm, const(afg_norm_params)* feat_norm, float* d_out, afg_batch_result* out_);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

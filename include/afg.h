@@ -1282,6 +1282,88 @@ typedef struct afg_mel_opts {
 int afg_batch_decode_mel(const uint8_t *const *data, const size_t *length, int n_files, const afg_mel_opts *opts, float *d_out,
                          afg_batch_result *out);
 
+/* ---- normalisation: statistics per group of rows, and the gain / offset they decide ------------------------------------
+ * The last step in front of a model: peak or RMS gain of a waveform, zero mean and unit variance per utterance over its
+ * own samples (wav2vec2, HuBERT, WavLM), Whisper's dynamic range of a log-mel slab.  The reference has no such stage; the
+ * definition is this library's own, restated in numpy in tests/normalize_model.py, and the device follows it bit for bit.
+ *
+ * Groups.  A group (afg_norm_group) is what one set of statistics covers: rows 1 .. 65535; row r starts at float
+ * in_off + r * stride of d_in and out_off + r * stride of d_out; only the first `valid` floats of a row count and are
+ * touched.  One file's channel rows are one group; one mel slab is one group of a single row.  valid == 0: nothing is read,
+ * nothing written, and the statistics record is all zero.
+ *
+ * Tiles.  A tile is 4096 consecutive floats of one row, counted from the row's element 0; a row's last tile may be short.
+ * Tiles are numbered rows ascending, then tiles ascending inside a row; a group's tiles follow those of the group before.
+ *
+ * Statistics, in a fixed order, without atomics, sums in float64.  Element e of a tile belongs to lane (e / 4) % 256 of
+ * 256 lanes.  A lane starts from s = q = +0.0 and over its elements in ascending e does s = s + (double)x and
+ * q = q + (double)x * (double)x (the product is exact, only the adds round).  Lanes combine in a binary tree: step
+ * d = 1, 2, 4 .. 128, lane l with l % (2 d) == 0 takes v[l] = v[l] + v[l + d].  A group's tile results combine one after
+ * the other in tile order, starting from +0.0.  min and max are those of the samples that are no NaN, with -0 below +0
+ * (+inf and -inf when there is none); a NaN sample propagates through the sums.  count = rows * valid.
+ *
+ * Modes.  The mode gives offset and scale (float32), which go into the record; every valid element then becomes
+ * y = (x - offset) * scale: the float32 subtraction rounded, then the float32 product, no fused multiply-add.
+ *   AFG_NORM_NONE           statistics only (offset 0, scale 1); d_out is not used and may be NULL
+ *   AFG_NORM_PEAK           p = fmaxf(-min, max); offset 0, scale = target / p (float32 division), 1 when p is 0 or not finite
+ *   AFG_NORM_RMS            r = (float)sqrt(sumsq / count); offset 0, scale = target / r, 1 when r is 0 or not finite
+ *   AFG_NORM_STANDARD       in double: mean = sum / count, var = fmax(sumsq / count - mean * mean, 0) (a NaN gives 0);
+ *                           offset = (float)mean, scale = (float)(1.0 / sqrt(var + (double)eps)); eps 0 means 1e-7f
+ *   AFG_NORM_DYNAMIC_RANGE  y = ((x > offset ? x : offset) + shift) * gain with offset = max - range (a NaN sample takes
+ *                           the floor); scale = gain.  Whisper: range 8, shift 4, gain 0.25
+ * A NaN in sum, sumsq, offset, scale or the output is always the positive quiet NaN (0x7fc00000, 0x7ff8000000000000):
+ * which NaN an operation returns is the hardware's affair, and the definition leaves none of that in its results.
+ * The fields a mode uses must be finite; target, range and gain positive, eps at least 0.  The others are ignored.
+ * In place (d_out == d_in, out_off == in_off) is allowed; other overlaps of what a launch reads and writes are not.  No
+ * float outside the valid elements of a group is read or written. */
+#define AFG_NORM_NONE          0
+#define AFG_NORM_PEAK          1
+#define AFG_NORM_RMS           2
+#define AFG_NORM_STANDARD      3
+#define AFG_NORM_DYNAMIC_RANGE 4
+typedef struct afg_norm_group {   /* 48 bytes */
+    uint64_t in_off, out_off;     /* float index of row 0, element 0 in d_in / d_out */
+    uint64_t stride;              /* floats from one row to the next, in both planes; >= valid when rows > 1 */
+    uint64_t first_tile;          /* filled in by afg_norm_layout */
+    uint32_t rows, valid;
+    uint32_t reserved[2];
+} afg_norm_group;
+typedef struct afg_norm_stats {   /* 40 bytes, one per group */
+    double sum, sumsq; uint64_t count; float min, max, offset, scale;
+} afg_norm_stats;
+typedef struct afg_norm_params { uint32_t mode; float target, eps, range, shift, gain; } afg_norm_params;
+/* Host: fills first_tile of every group, returns the launch's tile count. */
+uint64_t afg_norm_layout(afg_norm_group *groups, uint64_t n_groups);
+/* Host only, no device: the checks afg_normalize_hip makes before it launches, on a host copy of the groups: the mode known
+ * and its parameters in range; rows 1 .. 65535; first_tile and n_tiles as afg_norm_layout gives them; and for a group with
+ * valid > 0: stride >= valid when rows > 1, its rows inside [0, in_floats) and -- unless the mode is AFG_NORM_NONE -- inside
+ * [0, out_floats).  AFG_ERR_INVALID with afg_last_error set otherwise.  n_groups == 0 checks the parameters alone. */
+int afg_norm_check_groups(const afg_norm_group *groups, uint64_t n_groups, uint64_t n_tiles, const afg_norm_params *params,
+                          uint64_t in_floats, uint64_t out_floats);
+/* Three launches on hip_stream: the tiles' partial sums into d_partials (n_tiles * 32 bytes, 8-byte aligned), the groups'
+ * records into d_stats (n_groups of them), and the apply pass.  d_groups is the device copy of groups laid out by
+ * afg_norm_layout; the entry fetches it on hip_stream, waits for it and checks every group as afg_norm_check_groups does:
+ * anything else than a pass is AFG_ERR_INVALID and nothing is written. */
+int afg_normalize_hip(uint64_t n_groups, const afg_norm_group *d_groups, uint64_t n_tiles, const afg_norm_params *params,
+                      const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats, void *d_partials,
+                      afg_norm_stats *d_stats, void *hip_stream);
+
+/* afg_batch_decode_resampled, then one group per file, in place: rows = min(channels, the file's channels), or 1 with
+ * mono; with g = gcd(file rate, samplerate), M = file rate / g and L = samplerate / g,
+ * valid = min(T, ceil((frames - first_frame) * L / M)), 0 when that is not positive: the samples whose place lies inside
+ * the file.  What lies behind them, and the rows a file has no channel for, stay as afg_batch_decode_resampled leaves them.  A
+ * failed or refused file is a group with valid == 0: a zero slab, a zero record.  d_stats (device, n_files records) may be
+ * NULL.  Checked before any device call: everything afg_batch_decode_resampled checks, and NULL or out-of-range norm.
+ * Statuses, messages and items[i] are afg_batch_decode_resampled's. */
+int afg_batch_decode_resampled_norm(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
+                                    const afg_norm_params *norm, float *d_out, afg_norm_stats *d_stats, afg_batch_result *out);
+/* afg_batch_decode_mel with wave_norm (NULL: none) applied to the pooled [files, channels, T] tensor in front of the mel
+ * launch, in the groups of afg_batch_decode_resampled_norm, and feat_norm (NULL: none) applied to every [i, k] slab as one
+ * group of n_mels * n_out floats, all of them valid.  A failed file's slab is what the definition gives for the all-floor
+ * slab.  Checked before any device call: everything afg_batch_decode_mel checks, and norm parameters out of range. */
+int afg_batch_decode_mel_norm(const uint8_t *const *data, const size_t *length, int n_files, const afg_mel_opts *opts,
+                              const afg_norm_params *wave_norm, const afg_norm_params *feat_norm, float *d_out, afg_batch_result *out);
+
 #ifdef __cplusplus
 }
 #endif
