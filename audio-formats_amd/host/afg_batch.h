@@ -1,6 +1,7 @@
-// afg_batch.h -- the batch path's inside: what afg_host.cpp (the passes over a batch, a stream's refill) and the device
-// stages of the five codecs it drives (afg_flac_stage.cpp, afg_mp3_stage.cpp, afg_vorbis_stage.cpp, afg_opus_stage.cpp)
-// share.  decode_parsed lays the five stages out in the order FLAC, QOA, MP3, Vorbis, Opus, runs them and fills the metadata.
+// afg_batch.h -- the batch path's inside: what afg_batch.cpp (the passes over a batch), afg_stream.cpp (a stream's refill),
+// afg_pools.cpp (staging buffers, helper threads) and the stages of the five codecs they drive (afg_flac_stage.cpp,
+// afg_mp3_stage.cpp, afg_vorbis_stage.cpp, afg_opus_stage.cpp) share: each codec's staging pass over a batch and its device
+// stage.  decode_parsed lays the five stages out in the order FLAC, QOA, MP3, Vorbis, Opus, runs them and fills the metadata.
 #pragma once
 #include "../csrc/afg_common.h"
 #include "afg_flac_front.h"
@@ -40,7 +41,7 @@ struct StageTimer {
     }
 };
 
-// A page-locked buffer on lease from the staging pool of afg_host.cpp; it goes back when the lease ends.
+// A page-locked buffer on lease from the staging pool of afg_pools.cpp; it goes back when the lease ends.
 struct StagingLease {
     void *p = nullptr;
     size_t cap = 0;
@@ -51,7 +52,7 @@ struct StagingLease {
 };
 int staging_take(size_t bytes, StagingLease &out);
 
-// work() on the caller and on up to `helpers` pooled threads of the calling thread's helper pool (afg_host.cpp)
+// work() on the caller and on up to `helpers` pooled threads of the calling thread's helper pool (afg_pools.cpp)
 void helpers_run(unsigned helpers, const std::function<void()> &work);
 template <typename F>
 void parallel_for(size_t n, unsigned threads, F fn)
@@ -68,6 +69,25 @@ void parallel_for(size_t n, unsigned threads, F fn)
     };
     helpers_run(threads - 1, work);
 }
+// host threads of a batch whose caller leaves the choice to the library, and of a stage that keeps every CPU busy by itself
+unsigned default_threads();
+unsigned sustained_threads();
+
+// The helper pool and the stage chunk count of the calling host thread, for as long as the scope lives; the destructor puts
+// back what it found.  kGroupLead / kGroup: the calling and the second host thread of a grouped batch, whose stages cut their
+// files into 2 chunks, the second with the group pool of device `index`; kDevice: the thread of part `index` of a
+// multi-device batch, with that part's pool.
+struct HelperScope {
+    enum Kind { kGroupLead, kGroup, kDevice };
+    HelperScope(Kind kind, int index);
+    HelperScope(const HelperScope &) = delete;
+    HelperScope &operator=(const HelperScope &) = delete;
+    ~HelperScope();
+private:
+    void *prev_pool;
+    unsigned prev_chunks;
+};
+unsigned stage_chunks();                         // chunks a device stage of the calling thread cuts its files into
 
 // ---------------------------------------------------------------------------------------------
 // decoded files: one result plane for a whole batch
@@ -139,43 +159,102 @@ struct StageDev {
     SampleConv conv;
 };
 
-// ---- the staged inputs of the batch path (afg_batch_decode) ----
-// Where the batch path parsed its FLAC files: file i's residual plane at word base[i] of one page-locked buffer
-struct FlacStage {
-    const int32_t *res = nullptr;
-    size_t words = 0;
-    const size_t *base = nullptr;
+// ---- the staging passes of the batch path (afg_batch_decode): FLAC, MP3 and Ogg Vorbis files are parsed straight into one
+// page-locked buffer per codec.  Pass 1 asks every file's bound (0: not this codec's file); prefix() gives file i its place
+// base[i]; the codec's parse pass fills the lease and says whether every file is in it (otherwise the codec's files are
+// gathered from their own buffers, wherever they sit). ----
+struct StagingPlan {
+    std::vector<size_t> bounds, base;
+    size_t total = 0;
+    StagingLease lease;
+    explicit StagingPlan(size_t n_files) : bounds(n_files, 0), base(n_files, 0) {}
+    void prefix(size_t align)                    // every file's share a multiple of `align` (a power of two)
+    {
+        for (size_t i = 0; i < bounds.size(); i++) { base[i] = total; total += (bounds[i] + align - 1) & ~(align - 1); }
+    }
 };
 
-// Where the batch path parsed its MP3 files: one page-locked buffer, file i at block base[i] (gaps between files).
+// FLAC files of declared length: file i's residual plane at word base[i] (16-byte aligned planes)
+struct FlacStaging : StagingPlan {              // afg_flac_stage.cpp
+    const int32_t *res = nullptr;               // set, with `words`, when every FLAC file of the batch is in the staging
+    size_t words = 0;
+    using StagingPlan::StagingPlan;
+    size_t bound(size_t i, const uint8_t *d, size_t n) { return bounds[i] = flac_res_bound(d, n); }
+    int parse(std::vector<Parsed> &parsed, const uint8_t *const *data, const size_t *len, unsigned nt, StageTimer &tm);
+};
+
+struct Mp3Staging;
+// H2D -> kernel on stream `up`, D2H on stream `down` behind an event: chunk k+1 uploads and transforms while chunk
+// k's PCM goes back (PCIe is full duplex) -- and while the host threads parse chunk k+2.
+struct Mp3Pipe {                        // afg_mp3_stage.cpp
+    const Mp3Staging *st = nullptr;
+    DevBuf d_in, d_pcm, d_pcm64;
+    SampleConv conv;
+    uint32_t *d_flags = nullptr;
+    std::vector<afg_mp3_plan *> plans;
+    DevBuf d_tables;                    // plan tables: at most one 16-byte segment and stream record per block
+    StagingLease h_tables;
+    afg::PlanArena arena;
+    int rc = AFG_OK;
+
+    DevBuf d_qin;                       // quantised upload: int16 plane, record slots, stereo descriptors
+    int16_t *d_q = nullptr;
+    afg_mp3_qgranule *d_recs = nullptr;
+    afg_mp3_sdesc *d_sdesc = nullptr;
+    StagingLease h_sdesc;
+    size_t sdesc_cap = 0, sdesc_used = 0;
+    uint64_t h2d_bytes = 0;
+    StageStreams s;                     // (behind the buffers and records: it drains first)
+
+    int open(const Mp3Staging &stage);
+    void submit(const std::vector<Parsed> &parsed, size_t f0, size_t f1);   // files [f0, f1) have been parsed into the stage: plan, upload, transform, download
+    int close();
+    ~Mp3Pipe() { (void)close(); }
+};
+
+// MP3 files: file i at block base[i] (gaps between files).
 // The device planes and the MP3 result plane mirror that layout, so a chunk of files moves in ONE copy each way and
 // a file's PCM is served where it lands (a per-file copy costs ~20 us of submission: 2 x 2048 of them were the whole
-// end-to-end time of a 2048-file batch).
-struct Mp3Stage {
-    const float *coef = nullptr;        // float upload: dequantised spectra, blocks * 576 ...
-    const int16_t *q = nullptr;         // ... or quantised upload: Huffman values, blocks * 576, and one record slot
-    const afg_mp3_qgranule *recs = nullptr;   // per block (the slot of a granule's first block is used, nch = 0 elsewhere)
-    const uint32_t *flags = nullptr;
-    size_t blocks = 0;
-    const size_t *base = nullptr;
-    float *plane = nullptr;             // host PCM plane, blocks * 576 floats (page-locked) ...
-    SampleOut so;                       // ... or as many doubles / packed integer samples (afg_batch_opts.sample_type): made of the transform's floats on the device
+// end-to-end time of a 2048-file batch).  The files are parsed chunk by chunk, and a parsed chunk's device work is queued
+// on `pipe` while the host threads go on with the next.
+struct Mp3Staging : StagingPlan {               // afg_mp3_stage.cpp
+    float *coef = nullptr;                      // float upload: dequantised spectra, blocks * 576 ...
+    int16_t *q = nullptr;                       // ... or quantised upload: Huffman values, blocks * 576, and one record slot
+    afg_mp3_qgranule *recs = nullptr;           // per block (the slot of a granule's first block is used, nch = 0 elsewhere)
+    uint32_t *flags = nullptr;
+    size_t blocks = 0;                          // `total` while the pipeline serves the files; 0: none, or the batch fell back
+    float *plane = nullptr;                     // host PCM plane, blocks * 576 floats (page-locked) ...
+    SampleOut so;                               // ... or as many doubles / packed integer samples (afg_batch_opts.sample_type): made of the transform's floats on the device
+    bool fallback = false;                      // a file did not fit the staging: decode_parsed gathers the MP3 files
+    Mp3Pipe pipe;                               // (behind the lease: it drains first)
+    using StagingPlan::StagingPlan;
     size_t es() const { return so.es(); }
+    size_t bound(size_t i, const uint8_t *d, size_t n) { return bounds[i] = afg_mp3::looks_like_mp3(d, n) ? afg_mp3::max_blocks(d, n) : 0; }
+    int open(StagingLease &owner_plane, const SampleOut &out, StageTimer &tm);
+    void parse_and_submit(std::vector<Parsed> &parsed, const uint8_t *const *data, const size_t *len, unsigned nt, StageTimer &tm);
+    int close(StageTimer &tm);
 };
 
-// Where the batch path parsed its Ogg Vorbis files: file i's spectra at float base[i] of one page-locked buffer
-struct OggStage {
-    const float *spec = nullptr;
+// Ogg Vorbis files: file i's spectra at float base[i]
+struct OggStaging : StagingPlan {               // afg_vorbis_stage.cpp
+    const float *spec = nullptr;                // set, with `floats`, when every Vorbis file of the batch is in the staging
     size_t floats = 0;
-    const size_t *base = nullptr;
+    using StagingPlan::StagingPlan;
+    size_t bound(size_t i, const uint8_t *d, size_t n) { return bounds[i] = afg_vorbis::max_spec_floats(d, n); }
+    int parse(std::vector<Parsed> &parsed, const uint8_t *const *data, const size_t *len, unsigned nt, StageTimer &tm);
 };
+
+// FLAC: residual rows that fit 16 bits are packed as int16 (default) or left as int32 (AFG_FLAC_HOST_RES32=1)
+bool flac_rows_int16();                         // afg_flac_stage.cpp
+// Vorbis: inverse coupling and floor curves on the device (default) or in the host parser (AFG_VORBIS_HOST_FLOOR=1)
+bool vorbis_floor_on_device();                  // afg_vorbis_stage.cpp
 
 // ---- the five stages.  layout(ctx, plane_off): the stage's files get their pcm_off (the stage's PCM starts at float
 // plane_off of the result plane), the stage its run list (with dither and in collate mode: afg_stage.h, PackRun) and its
 // totals; returns the floats it needs in the result plane.  run(ctx, dev): the device work, into the stage's range of
 // ctx.out.plane; it returns with its streams drained. ----
 struct FlacDecode {                     // afg_flac_stage.cpp
-    const FlacStage *staged = nullptr;
+    const FlacStaging *staged = nullptr;
     std::vector<size_t> res_base, fr_base, sf_base;
     size_t res_total = 0, fr_total = 0, sf_total = 0, out_floats = 0;
     std::vector<PackRun> runs;
@@ -205,7 +284,7 @@ struct Mp3Carry {
 void mp3_runs(std::vector<PackRun> &runs, const afg_mp3::File &f, uint64_t base, size_t file);
 
 struct Mp3Decode {                      // afg_mp3_stage.cpp
-    const Mp3Stage *staged = nullptr;   // the files are already decoded, in staging layout, in staged->plane (Mp3Pipe)
+    const Mp3Staging *staged = nullptr;   // the files are already decoded, in staging layout, in staged->plane (Mp3Pipe)
     Mp3Carry *carry = nullptr;          // a stream's chunk
     std::vector<size_t> blk_base;
     size_t blocks = 0, plane_off = 0;
@@ -217,36 +296,8 @@ struct Mp3Decode {                      // afg_mp3_stage.cpp
     int run(StageCtx &ctx, StageDev &dev);        // not staged: the gathered stage
 };
 
-// H2D -> kernel on stream `up`, D2H on stream `down` behind an event: chunk k+1 uploads and transforms while chunk
-// k's PCM goes back (PCIe is full duplex) -- and while the host threads parse chunk k+2.
-struct Mp3Pipe {                        // afg_mp3_stage.cpp
-    const Mp3Stage *st = nullptr;
-    DevBuf d_in, d_pcm, d_pcm64;
-    SampleConv conv;
-    uint32_t *d_flags = nullptr;
-    std::vector<afg_mp3_plan *> plans;
-    DevBuf d_tables;                    // plan tables: at most one 16-byte segment and stream record per block
-    StagingLease h_tables;
-    afg::PlanArena arena;
-    int rc = AFG_OK;
-
-    DevBuf d_qin;                       // quantised upload: int16 plane, record slots, stereo descriptors
-    int16_t *d_q = nullptr;
-    afg_mp3_qgranule *d_recs = nullptr;
-    afg_mp3_sdesc *d_sdesc = nullptr;
-    StagingLease h_sdesc;
-    size_t sdesc_cap = 0, sdesc_used = 0;
-    uint64_t h2d_bytes = 0;
-    StageStreams s;                     // (behind the buffers and records: it drains first)
-
-    int open(const Mp3Stage &stage);
-    void submit(const std::vector<Parsed> &parsed, size_t f0, size_t f1);   // files [f0, f1) have been parsed into the stage: plan, upload, transform, download
-    int close();
-    ~Mp3Pipe() { (void)close(); }
-};
-
 struct VorbisDecode {                   // afg_vorbis_stage.cpp
-    const OggStage *staged = nullptr;
+    const OggStaging *staged = nullptr;
     // chunks of files, one plan each; the Vorbis part of the result plane is the plans' output planes back to back, so a
     // chunk's PCM comes back in one copy and a file is served where it lands (first piece onwards)
     struct Chunk {
@@ -298,5 +349,14 @@ struct OpusDecode {                     // afg_opus_stage.cpp: the gathered stag
 // *staged: the stage ran (there were Opus files).
 int opus_pipeline(std::vector<Parsed> &parsed, const uint8_t *const *data, const size_t *length, const std::vector<uint8_t> &opened,
                   unsigned threads, const SampleOut &so, StagingLease &plane, std::vector<size_t> &pcm_at, bool *staged, StageTimer &tm);
+
+
+// ---- afg_batch.cpp ----
+// a decode_parsed call's context, with the calling thread's chunk count
+StageCtx stage_ctx(std::vector<Parsed> &parsed, const uint8_t *const *data, const size_t *len, const uint8_t *own, unsigned threads,
+                   SampleOut so, BatchOut &out);
+// The device stages for a set of parsed files, each handed in with its optional inputs set; the results come back as one
+// plane in ctx.out, laid out FLAC, QOA, MP3, Vorbis, Opus, and ctx.out.files tells where each file's PCM is.
+int decode_parsed(StageCtx &ctx, FlacDecode &flac, Mp3Decode &mp3, VorbisDecode &ogg, OpusDecode &opus);
 
 }  // namespace afg_front

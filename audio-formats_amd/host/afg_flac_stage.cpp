@@ -1,9 +1,45 @@
-// afg_flac_stage.cpp -- the FLAC and QOA device stages of decode_parsed (afg_batch.h): every FLAC record of the batch
-// restored chunk by chunk on three streams, every QOA frame in one launch; both write their range of the shared device
-// plane, in the result plane's layout.
+// afg_flac_stage.cpp -- the batch path's FLAC staging pass, and the FLAC and QOA device stages of decode_parsed
+// (afg_batch.h): every FLAC record of the batch restored chunk by chunk on three streams, every QOA frame in one launch;
+// both write their range of the shared device plane, in the result plane's layout.
 #include "afg_batch.h"
 
 namespace afg_front {
+
+bool flac_rows_int16() { return afg::dev_option(afg::kDevFlacHostRes32) <= 0; }
+
+// pass 1b: FLAC files of known length straight into one page-locked residual buffer
+int FlacStaging::parse(std::vector<Parsed> &parsed, const uint8_t *const *data, const size_t *len, unsigned nt, StageTimer &tm)
+{
+    if (!total) return AFG_OK;
+    if (int rc = staging_take(total * sizeof(int32_t), lease)) return rc;
+    int32_t *res0 = (int32_t *)lease.p;
+    std::atomic<bool> lost{ false };
+    parallel_for(parsed.size(), nt, [&](size_t i) {
+        if (!bounds[i]) return;
+        Parsed &p = parsed[i];
+        bool ok = false;
+        try {
+            p.flac.pack16 = flac_rows_int16();
+            ok = flac_parse_into(data[i], len[i], p.fi, p.flac, res0 + base[i], bounds[i]);
+            if (ok && p.flac.overflow) {                 // more audio than STREAMINFO declares: the file's own buffer
+                p.flac = FlacRecords();
+                p.flac.pack16 = flac_rows_int16();
+                ok = flac_parse(data[i], len[i], p.fi, p.flac);
+                lost = true;
+            }
+        } catch (...) { ok = false; }
+        if (ok) p.format = AFG_FORMAT_FLAC;
+        else p.flac = FlacRecords();
+    });
+    // the staged layout is used only when every FLAC file of the batch is in it (a file of undeclared length
+    // was parsed into its own buffer in pass 1): otherwise everything is gathered, wherever it sits
+    bool all_staged = !lost;
+    for (size_t i = 0; i < parsed.size() && all_staged; i++)
+        if (parsed[i].format == AFG_FORMAT_FLAC && !parsed[i].flac.ext_res && parsed[i].flac.res_size()) all_staged = false;
+    if (all_staged) { res = res0; words = total; }
+    tm.lap("pass 1b: flac parse into staging");
+    return AFG_OK;
+}
 
 size_t FlacDecode::layout(StageCtx &ctx, size_t plane_off)
 {

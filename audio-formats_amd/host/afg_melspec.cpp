@@ -222,10 +222,10 @@ int afg_front::mel_batch(const uint8_t *const *data, const size_t *length, int n
         const long budget_opt = afg::dev_option(afg::kDevMelScratchBytes);
         const uint64_t budget = budget_opt > 0 ? (uint64_t)budget_opt : (uint64_t)2 << 30;
         const size_t per_list = (size_t)std::min<uint64_t>((uint64_t)n_files, std::max<uint64_t>(budget / (slab_in * sizeof(float)), 1));
-        afg_batch_item *items = (afg_batch_item *)std::calloc((size_t)n_files, sizeof(afg_batch_item));
-        if (!items) return AFG_ERR_OOM;
-        struct ItemsGuard { afg_batch_item *p; ~ItemsGuard() { std::free(p); } } items_guard{ items };
-        std::deque<std::string> messages;
+        afg_front::BatchResult res;
+        if (int rc = res.alloc(n_files)) return rc;
+        afg_batch_item *const items = res.items;
+        std::deque<std::string> &messages = res.messages();
         if (int rc = afg::require_device()) return rc;
         afg_front::MelPlane plane;                               // (declared in front of the drain: it holds what the uploads read)
         afg_front::NormPlane wave, feat;
@@ -264,8 +264,7 @@ int afg_front::mel_batch(const uint8_t *const *data, const size_t *length, int n
                 if (items[f0 + i].pcm) items[f0 + i].pcm = y + i * slab_out;
             AFG_HIP_CHECK(hipStreamSynchronize(nullptr));         // the scratch and the records are free for the next sublist
         }
-        items_guard.p = nullptr;
-        return afg_front::batch_result_adopt(items, n_files, messages, out);
+        return res.finish(out);
     } catch (...) {
         afg::set_error("out of host memory");
         return AFG_ERR_OOM;

@@ -1,6 +1,7 @@
-// afg_mp3_stage.cpp -- the MP3 device stages (afg_batch.h): the pipeline the batch path feeds while it parses (Mp3Pipe),
-// the gathered stage of decode_parsed for files parsed into their own buffers (a stream's chunk with its carry, a batch
-// that fell back), and the in-place delivery of what the pipeline decoded.
+// afg_mp3_stage.cpp -- the MP3 stages (afg_batch.h): the batch path's staging pass (Mp3Staging), which parses chunks of
+// files into one page-locked buffer and feeds the pipeline (Mp3Pipe) while it parses; the gathered stage of decode_parsed
+// for files parsed into their own buffers (a stream's chunk with its carry, a batch that fell back), and the in-place
+// delivery of what the pipeline decoded.
 #include "afg_batch.h"
 
 namespace afg_front {
@@ -12,7 +13,7 @@ void mp3_runs(std::vector<PackRun> &runs, const afg_mp3::File &f, uint64_t base,
     for (const afg_mp3::Copy &c : f.copies) { runs.push_back(PackRun{ base * 576 + c.src, c.count, at, (uint32_t)file, (uint32_t)f.channels }); at += c.count; }
 }
 
-int Mp3Pipe::open(const Mp3Stage &stage)
+int Mp3Pipe::open(const Mp3Staging &stage)
 {
     st = &stage;
     const size_t coef_bytes = stage.blocks * 576 * sizeof(float), flag_bytes = (stage.blocks * 4 + 15) & ~(size_t)15;
@@ -70,7 +71,7 @@ void Mp3Pipe::submit(const std::vector<Parsed> &parsed, size_t f0, size_t f1)
     if (st->q) {
         // quantised upload: 2 bytes per line + a record per granule, requantised on the device into the plane the
         // transform reads (afg_mp3_requant_hip); the stereo descriptors of intensity frames are gathered per chunk
-        afg_mp3_qgranule *hrecs = const_cast<afg_mp3_qgranule *>(st->recs);
+        afg_mp3_qgranule *hrecs = st->recs;
         const size_t sd0 = sdesc_used;
         for (size_t i = f0; i < f1; i++) {
             const Parsed &p = parsed[i];
@@ -121,6 +122,115 @@ int Mp3Pipe::close()
     s.release();
     if (rc) return rc;
     if (s.e != hipSuccess) { afg::set_error("MP3 stage failed: %s", hipGetErrorString(s.e)); return AFG_ERR_HIP; }
+    return AFG_OK;
+}
+
+// The staging buffer carved for the quantised or the float upload, the batch's MP3 result plane, and the pipeline opened.
+int Mp3Staging::open(StagingLease &owner_plane, const SampleOut &out, StageTimer &tm)
+{
+    if (!total) return AFG_OK;
+    // Quantised upload by default: int16 Huffman values + a record per granule, requantised on the device.
+    // afg_dev_option("mp3_float_upload", 1) keeps the float spectra of round 1 (A/B of the bytes that cross the bus).
+    const bool qmode = afg::dev_option(afg::kDevMp3FloatUpload) <= 0;
+    const size_t per_block = qmode ? 576 * sizeof(int16_t) + sizeof(afg_mp3_qgranule) + sizeof(uint32_t)
+                                   : 576 * sizeof(float) + sizeof(uint32_t);
+    if (int rc = staging_take(total * per_block + 64, lease)) return rc;
+    if (out.fetch()) if (int rc = staging_take(total * 576 * out.es(), owner_plane)) return rc;
+    if (qmode) {
+        recs = (afg_mp3_qgranule *)lease.p;                                    // 8-byte aligned records first
+        flags = (uint32_t *)(recs + total);
+        q = (int16_t *)(flags + total);
+    } else {
+        coef = (float *)lease.p;
+        flags = (uint32_t *)(coef + total * 576);
+    }
+    blocks = total;
+    plane = (float *)owner_plane.p;
+    so = out;
+    if (int rc = pipe.open(*this)) return rc;
+    tm.lap("mp3 pipeline set-up (device planes, streams, table arena)");
+    return AFG_OK;
+}
+
+// pass 2, chunk by chunk: all host threads parse a chunk of files, its device work is queued, and they go on
+// with the next chunk while the copies and the kernel of this one run
+void Mp3Staging::parse_and_submit(std::vector<Parsed> &parsed, const uint8_t *const *data, const size_t *len, unsigned nt, StageTimer &tm)
+{
+    if (!total) return;
+    const size_t nf = parsed.size();
+    const bool qmode = q != nullptr;
+    size_t want = 8;
+    if (afg::dev_option(afg::kDevMp3Chunks) > 0) want = (size_t)afg::dev_option(afg::kDevMp3Chunks);
+    const size_t target = std::max<size_t>((total + want - 1) / want, 8192);
+    for (size_t f0 = 0; f0 < nf;) {
+        const size_t f1 = cut_chunk(f0, nf, target, [&](size_t i, size_t &w) { w = bounds[i]; return true; }).f1;
+        std::atomic<bool> lost{ false };
+        parallel_for(f1 - f0, nt, [&](size_t k) {
+            const size_t i = f0 + k;
+            if (!bounds[i]) return;
+            Parsed &p = parsed[i];
+            bool ok = false;
+            try {
+                if (qmode) {
+                    std::memset(recs + base[i], 0, bounds[i] * sizeof(afg_mp3_qgranule));     // nch = 0: slot unused
+                    p.mp3.quantised = true;
+                    p.mp3.ext_q = q + base[i] * 576;
+                    p.mp3.ext_qgr = recs + base[i];
+                    ok = afg_mp3::parse_file_into(data[i], len[i], p.mp3, nullptr, flags + base[i], bounds[i]);
+                    if (ok && !p.mp3.overflow && !p.mp3.q_unsupported) {
+                        const uint64_t shift = (uint64_t)base[i] * 576;                       // file-relative -> plane offsets
+                        for (size_t k = 0; k < p.mp3.blocks(); k++)
+                            if (recs[base[i] + k].nch) { recs[base[i] + k].q_off += shift; recs[base[i] + k].coef_off += shift; }
+                    }
+                } else {
+                    ok = afg_mp3::parse_file_into(data[i], len[i], p.mp3, coef + base[i] * 576, flags + base[i], bounds[i]);
+                }
+                if (ok && (p.mp3.overflow || p.mp3.q_unsupported)) {
+                    // overflow cannot happen; a stream the device requantiser does not cover (MPEG-2.5 8 kHz mixed
+                    // blocks) can: either way the file is parsed into its own float buffers and the batch takes the
+                    // gathered path
+                    p.mp3 = afg_mp3::File();
+                    ok = afg_mp3::parse_file(data[i], len[i], p.mp3);
+                    lost = true;
+                }
+            } catch (...) {
+                // the file may have left records with file-relative offsets in the staged plane: the chunk must not
+                // be submitted as it stands (afg_mp3_requant_hip walks every slot with nch != 0)
+                ok = false;
+                if (qmode) std::memset(recs + base[i], 0, bounds[i] * sizeof(afg_mp3_qgranule));
+                lost = true;
+            }
+            if (ok) p.format = AFG_FORMAT_MP3;
+            else p.mp3 = afg_mp3::File();
+        });
+        if (lost) fallback = true;
+        if (!fallback) pipe.submit(parsed, f0, f1);
+        f0 = f1;
+    }
+    if (fallback && qmode) {
+        // the gathered path works from float records: the files that were parsed into the quantised staging are
+        // parsed again into their own buffers (rare: one file of the batch is outside the requantiser's coverage)
+        parallel_for(nf, nt, [&](size_t i) {
+            if (!bounds[i] || parsed[i].format != AFG_FORMAT_MP3 || !parsed[i].mp3.quantised) return;
+            Parsed &p = parsed[i];
+            bool ok = false;
+            try {
+                p.mp3 = afg_mp3::File();
+                ok = afg_mp3::parse_file(data[i], len[i], p.mp3);
+            } catch (...) { ok = false; }
+            if (!ok) { p.mp3 = afg_mp3::File(); p.format = AFG_FORMAT_UNKNOWN; }
+        });
+    }
+    tm.lap("mp3 parse (all threads) | h2d | kernel | d2h");
+}
+
+int Mp3Staging::close(StageTimer &tm)
+{
+    if (!total) return AFG_OK;
+    const int rc = pipe.close();
+    tm.lap("mp3 pipeline drain");
+    if (rc) return rc;
+    if (fallback) blocks = 0;                         // decode_parsed does those files from their own buffers
     return AFG_OK;
 }
 

@@ -183,10 +183,10 @@ extern "C" int afg_batch_decode_resampled_norm(const uint8_t *const *data, const
         if (int rc = afg_norm_check_groups(nullptr, 0, 0, norm, 0, 0)) return rc;
         if (((uintptr_t)d_stats & 7u) != 0) { afg::set_error("afg_batch_decode_resampled_norm: d_stats must be 8-byte aligned"); return AFG_ERR_INVALID; }
         if (n_files == 0) return AFG_OK;
-        afg_batch_item *items = (afg_batch_item *)std::calloc((size_t)n_files, sizeof(afg_batch_item));
-        if (!items) return AFG_ERR_OOM;
-        struct ItemsGuard { afg_batch_item *p; ~ItemsGuard() { std::free(p); } } items_guard{ items };
-        std::deque<std::string> messages;
+        afg_front::BatchResult res;
+        if (int rc = res.alloc(n_files)) return rc;
+        afg_batch_item *const items = res.items;
+        std::deque<std::string> &messages = res.messages();
         if (int rc = afg_front::resampled_run(job, opts, data, length, n_files, d_out, items, messages)) return rc;
         // the tensor is whole (resampled_run returns drained): one group per file, in place
         afg_front::NormPlane plane;                              // (declared in front of the drain: it holds what the upload reads)
@@ -195,8 +195,7 @@ extern "C" int afg_batch_decode_resampled_norm(const uint8_t *const *data, const
         afg_front::norm_file_groups(job, items, (size_t)n_files, opts->first_frame, groups);
         if (int rc = plane.launch(*norm, groups, d_out, (uint64_t)n_files * job.C * job.T, d_stats, nullptr)) return rc;
         AFG_HIP_CHECK(hipStreamSynchronize(nullptr));
-        items_guard.p = nullptr;
-        return afg_front::batch_result_adopt(items, n_files, messages, out);
+        return res.finish(out);
     } catch (...) {
         afg::set_error("out of host memory");
         return AFG_ERR_OOM;

@@ -17,7 +17,7 @@
 
 namespace afg_front {
 
-// ---- the pools and helper threads of afg_host.cpp ----
+// ---- the pools and helper threads of afg_pools.cpp ----
 int devpool_take(size_t bytes, void **out, size_t *cap_out);   // device memory, kept between calls
 void devpool_give(void *p, size_t cap, int dev);               // dev: the device it was taken on
 bool poison_alloc();                                           // AFG_POISON_ALLOC was set when the library was loaded (tests)
@@ -173,14 +173,29 @@ struct ResamplePlane {
     int launch(const ResampleJob &job, const float *d_scratch, afg_batch_item *items, size_t n, const int64_t *first_frame,
                const int64_t *scratch_frame0, float *d_out, std::deque<std::string> &messages, hipStream_t st);
 };
-// afg_batch_decode_resampled in two steps (afg_host.cpp), for an entry that runs it into a tensor of its own
+// afg_batch_decode_resampled in two steps (afg_batch.cpp), for an entry that runs it into a tensor of its own
 // (afg_batch_decode_mel): the checks of the options behind struct_size, which fill in the job and touch no device; then the
 // tensor of a checked call into d_out, with `items` (n_files of them, zeroed) and the strings of `messages` as the entry
-// returns them.  batch_result_adopt hands malloc'ed items and those strings to a result afg_batch_free lets go.
+// returns them.
 int resampled_check(const afg_resample_opts *opts, const uint8_t *const *data, const size_t *length, int n_files, ResampleJob &job);
 int resampled_run(const ResampleJob &job, const afg_resample_opts *opts, const uint8_t *const *data, const size_t *length, int n_files,
                   float *d_out, afg_batch_item *items, std::deque<std::string> &messages);
-int batch_result_adopt(afg_batch_item *items, int n_files, std::deque<std::string> &messages, afg_batch_result *out);
+// A batch result in the making, for every batch entry: alloc makes the zeroed items and their owner -- what afg_batch_free
+// lets go: the planes the items' PCM points into (afg_batch.cpp) and the message strings that are not static -- and finish
+// hands both to `out`; until then they go with the object.
+struct BatchOwner;
+struct BatchResult {
+    afg_batch_item *items = nullptr;
+    int n_files = 0;
+    BatchOwner *owner = nullptr;
+    BatchResult() = default;
+    BatchResult(const BatchResult &) = delete;
+    BatchResult &operator=(const BatchResult &) = delete;
+    ~BatchResult();
+    int alloc(int n);                                            // AFG_ERR_OOM: no memory for the items
+    std::deque<std::string> &messages();
+    int finish(afg_batch_result *out);                           // AFG_OK
+};
 
 // ---- mel spectrogram features (afg_batch_decode_mel, host/afg_melspec.cpp) ----
 // The tables of one parameter set, made once and kept for the process: afg_mel_basis's and afg_mel_filters'.

@@ -1,8 +1,38 @@
-// afg_vorbis_stage.cpp -- the Ogg Vorbis device stage of decode_parsed (afg_batch.h): chunk planning, the floor records of
-// files parsed with the floor left to the device, the chunk pipeline, and the close-up of files delivered in pieces.
+// afg_vorbis_stage.cpp -- the batch path's Ogg Vorbis staging pass and the Ogg Vorbis device stage of decode_parsed
+// (afg_batch.h): chunk planning, the floor records of files parsed with the floor left to the device, the chunk pipeline,
+// and the close-up of files delivered in pieces.
 #include "afg_batch.h"
 
 namespace afg_front {
+
+bool vorbis_floor_on_device() { return afg::dev_option(afg::kDevVorbisHostFloor) <= 0; }
+
+// pass 1b: Ogg Vorbis files straight into one page-locked staging buffer (no per-file megabyte vectors to fault in,
+// gather and unmap)
+int OggStaging::parse(std::vector<Parsed> &parsed, const uint8_t *const *data, const size_t *len, unsigned nt, StageTimer &tm)
+{
+    if (!total) return AFG_OK;
+    if (int rc = staging_take(total * sizeof(float), lease)) return rc;
+    float *spec0 = (float *)lease.p;
+    std::atomic<bool> lost{ false };
+    parallel_for(parsed.size(), nt, [&](size_t i) {
+        if (!bounds[i]) return;
+        Parsed &p = parsed[i];
+        bool ok = false;
+        try {
+            ok = afg_vorbis::parse_file_into(data[i], len[i], p.ogg, spec0 + base[i], bounds[i], vorbis_floor_on_device());
+            if (ok && p.ogg.overflow) {                  // cannot happen; be safe: the file's own buffer
+                ok = afg_vorbis::parse_file(data[i], len[i], p.ogg, vorbis_floor_on_device());
+                lost = true;
+            }
+        } catch (...) { ok = false; }
+        if (ok) p.format = AFG_FORMAT_OGG;
+        else p.ogg = afg_vorbis::File();
+    });
+    if (!lost) { spec = spec0; floats = total; }
+    tm.lap("pass 1b: ogg parse into staging");
+    return AFG_OK;
+}
 
 VorbisDecode::~VorbisDecode()
 {

@@ -1,5 +1,5 @@
 // afg_write_stream.h -- what the write stream (afg_write_stream.cpp), the batch encoder (afg_encode_stage.cpp), the host
-// WAV writer (afg_wav.cpp) and the handle (afg_host.cpp) know of each other.
+// WAV writer (afg_wav.cpp) and the handle (afg_stream.cpp) know of each other.
 #pragma once
 #include "../../include/afg.h"
 
@@ -19,7 +19,7 @@ constexpr int sample_size(int format)
 }  // namespace afg_write
 
 namespace afg_front {
-// afg_host.cpp.  A handle opened for writing: format, channels and rate as the getters report them, `error` its state
+// afg_stream.cpp.  A handle opened for writing: format, channels and rate as the getters report them, `error` its state
 // (NULL: valid).  The handle owns the writer.  NULL: out of memory.
 afg_stream *stream_for_writing(afg_write::Writer *w, int format, int channels, float samplerate, const char *error);
 afg_write::Writer *stream_writer(const afg_stream *s);         // NULL: not opened for writing
