@@ -34,8 +34,12 @@ struct RowMeta {                       // what the load/store phases need to kno
     uint64_t in_off;
     uint64_t out_off;
     uint32_t bs;
-    uint32_t info;                     // channels | assignment << 8 | bps << 16 | res16 << 24
+    union {
+        uint32_t info;                 // channels | assignment << 8 | bps << 16 | res16 << 24
+        uint32_t sf_index;             // flac_restore_mc_kernel (one channel count and row width per wavefront): the frame's first subframe,
+    };                                 // all 32 bits -- the index is global over a batch call and passes 2^24 in a few hundred long files
 };
+static_assert(sizeof(RowMeta) == 24, "RowMeta: 24 bytes per tile row in LDS");
 
 __device__ __forceinline__ int wave_max(int v)
 {
@@ -634,7 +638,7 @@ __global__ __launch_bounds__(64, 2) void flac_restore_mc_kernel(
     if ((lane & 1) == 0) {
         RowMeta me;
         me.in_off = fr.in_off; me.out_off = fr.out_off; me.bs = valid ? fr.block_size : 0u;
-        me.info = (uint32_t)fr.channels | ((uint32_t)fr.sf_index << 8);          // (this kernel's own use of the word: the subframe index)
+        me.sf_index = fr.sf_index;                                               // (this kernel's own use of the word; the channel count is C)
         meta[lane >> 1] = me;
         for (int c = 0; c < 8; c++) {
             uint32_t sh = 0;
@@ -659,7 +663,7 @@ __global__ __launch_bounds__(64, 2) void flac_restore_mc_kernel(
 #pragma unroll
         for (int k = 0; k < MAXORD; k++) { c[k] = 0; h[k] = 0; }
         if (act) {
-            const afg_flac_subframe *sf = subframes + (mine.info >> 8) + ch;
+            const afg_flac_subframe *sf = subframes + mine.sf_index + ch;
             order = sf->order; shift = sf->shift; u64 = sf->use64 != 0;
 #pragma unroll
             for (int k = 0; k < MAXORD; k++) c[k] = (k < order) ? (int32_t)sf->coef[k] : 0;

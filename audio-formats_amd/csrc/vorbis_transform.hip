@@ -1096,7 +1096,9 @@ __device__ __forceinline__ void vorbis_wave2_body(
 #endif
 constexpr int kWavesPerGroup = AFG_VORBIS_GROUP_WAVES;
 constexpr int kWaveStride = 2 * kWaveLds;             // transform areas of two channels: previous_window is in registers
-constexpr uint32_t kMcGroupsMax = 24;          // runs of one (shape, channel count) among the streams with more than two channels
+// runs of one (shape, channel count) among the streams with more than two channels: as many as walk_shape admits -- 26 (a constant
+// 24 once: a plan that held every group failed as a whole)
+constexpr uint32_t kMcGroupsMax = walk_mc_groups();
 constexpr uint32_t kCounterSets = 32, kCountersPerLaunch = 1 + kWalkShapes + kMcGroupsMax;
 constexpr uint32_t kBothChannels = 0xffffffffu;       // VorbisSeg.pad of a wavefront that walks both channels of a stereo stream
 
@@ -1359,7 +1361,7 @@ int afg::vorbis_plan_create_at(afg_vorbis_plan **plan, uint32_t n_streams, const
         all_walk.insert(all_walk.end(), walk_segs[k].begin(), walk_segs[k].end());
     }
     p->walk_first[kWalkShapes] = (uint32_t)all_walk.size();
-    if (p->mc_groups.size() > kMcGroupsMax) {
+    if (p->mc_groups.size() > kMcGroupsMax) {           // (not reached while walk_shape and walk_mc_groups agree: kept as a guard of the counter block)
         afg::set_error("afg_vorbis_plan_create: more than %u different (block size, channel count) groups above two channels", kMcGroupsMax);
         delete p;
         return AFG_ERR_UNSUPPORTED;

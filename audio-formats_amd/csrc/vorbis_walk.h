@@ -11,6 +11,31 @@ constexpr int kWalkShapes = 12;
 // a segment); 6 + size for 3, 5 or 7 channels (a workgroup per segment, one wavefront per channel), 9 + size for an even
 // number up to 16 (a workgroup per segment, one wavefront per pair of channels); -1 for every other stream.
 int walk_shape(int channels, int blocksize0, int blocksize1);
+// (the rule itself, usable in constant expressions: the plan sizes its per-launch counter block by it)
+constexpr int walk_shape_of(int channels, int blocksize0, int blocksize1)
+{
+    // (equal block sizes: every packet is a long block between long blocks to the walk -- the plan rewrites its flags)
+    if (channels < 1 || (blocksize0 > 512 && blocksize0 != blocksize1) || blocksize0 > blocksize1) return -1;
+    const int size = blocksize1 == 1024 ? 0 : blocksize1 == 2048 ? 1 : blocksize1 == 4096 ? 2 : -1;
+    if (size < 0) return -1;
+    if (channels <= 2) return 2 * size + (channels - 1);
+    // More than two channels: one workgroup of at most 8 wavefronts per segment.  4096-sample blocks: one wavefront per channel
+    // whatever the count (a pair's transform areas, 18 KB, would leave room for three wavefronts per CU: 15.9 ms per C3-sized
+    // batch of 6 channels, against 13.9 for round 5's column stores), so at most 8 channels; the other sizes 3, 5, 7 or an
+    // even number up to 16.  Everything else stays on the bit-exact kernels.
+    if (size == 2) return channels <= 8 ? 8 : -1;
+    if (channels & 1) return channels <= 7 ? 6 + size : -1;
+    return channels <= 16 ? 9 + size : -1;
+}
+// The (shape, channel count) pairs above two channels that walk_shape admits: each is a launch group of a plan, with a work
+// counter of its own.  (blocksize_0 does not enter the key; 255: what a stream record's channel byte can hold.)
+constexpr uint32_t walk_mc_groups()
+{
+    uint32_t n = 0;
+    for (int bs1 = 1024; bs1 <= 4096; bs1 *= 2)
+        for (int ch = 3; ch <= 255; ch++) n += walk_shape_of(ch, 256, bs1) >= 6;
+    return n;
+}
 int walk_shape_channels(int shape);          // channels one wavefront of the shape walks
 int walk_shape_blocksize(int shape);
 size_t walk_table_floats(int shape);

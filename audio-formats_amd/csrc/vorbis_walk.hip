@@ -1313,21 +1313,7 @@ void build_tables_r(float *dst, const float *window)
 
 }  // namespace
 
-int walk_shape(int channels, int blocksize0, int blocksize1)
-{
-    // (equal block sizes: every packet is a long block between long blocks to the walk -- the plan rewrites its flags)
-    if (channels < 1 || (blocksize0 > 512 && blocksize0 != blocksize1) || blocksize0 > blocksize1) return -1;
-    const int size = blocksize1 == 1024 ? 0 : blocksize1 == 2048 ? 1 : blocksize1 == 4096 ? 2 : -1;
-    if (size < 0) return -1;
-    if (channels <= 2) return 2 * size + (channels - 1);
-    // More than two channels: one workgroup of at most 8 wavefronts per segment.  4096-sample blocks: one wavefront per channel
-    // whatever the count (a pair's transform areas, 18 KB, would leave room for three wavefronts per CU: 15.9 ms per C3-sized
-    // batch of 6 channels, against 13.9 for round 5's column stores), so at most 8 channels; the other sizes 3, 5, 7 or an
-    // even number up to 16.  Everything else stays on the bit-exact kernels.
-    if (size == 2) return channels <= 8 ? 8 : -1;
-    if (channels & 1) return channels <= 7 ? 6 + size : -1;
-    return channels <= 16 ? 9 + size : -1;
-}
+int walk_shape(int channels, int blocksize0, int blocksize1) { return walk_shape_of(channels, blocksize0, blocksize1); }
 
 int walk_shape_channels(int shape) { return shape < 6 ? (shape & 1) + 1 : shape < 9 ? 1 : 2; }
 

@@ -335,3 +335,29 @@ def test_walk_every_shape_in_one_plan(gpu):
         assert (got.view(np.uint32) == want.view(np.uint32)).all()
     finally:
         afgpu.set_numeric_mode(afgpu.NUMERIC_FROM_ENV)
+
+
+def test_walk_every_multichannel_group_in_one_plan(gpu):
+    """one stream of every (channel count, blocksize_1) the walk takes above two channels -- by the rule of walk_shape's
+    comment: 3, 5, 7 or an even count up to 16 at 1024 and 2048, 3 .. 8 at 4096; written out here, not read from the
+    library -- in one plan, each a launch group of its own, beside two stereo streams and a 9-channel one (the exact
+    kernels')"""
+    pairs = [(c, n) for n in (1024, 2048) for c in (3, 5, 7)] + [(c, n) for n in (1024, 2048) for c in range(4, 17, 2)] + \
+            [(c, 4096) for c in range(3, 9)]
+    assert len(pairs) == len(set(pairs)) == 26
+    ch = [c for c, _ in pairs] + [2, 2, 9]
+    bs1 = [n for _, n in pairs] + [2048, 4096, 2048]
+    bs0 = [512 if n == 4096 else 256 for n in bs1]
+    packets = [5 + i % 5 for i in range(len(ch))]
+    pflags, spec = synthetic.vorbis_batch(79, packets, ch, bs0, bs1, p_short_run=0.15)
+    for seg in (4, 16):
+        got, want = run_both(gpu, packets, ch, bs0, bs1, pflags, spec, seg)
+        rms, differ = check(got, want)
+        assert differ > got.size // 10, "tolerance mode produced the exact kernel's bits"
+    import afgpu
+    afgpu.set_numeric_mode(afgpu.NUMERIC_EXACT)
+    try:
+        got, want = run_both(gpu, packets, ch, bs0, bs1, pflags, spec, 16)
+        assert (got.view(np.uint32) == want.view(np.uint32)).all()
+    finally:
+        afgpu.set_numeric_mode(afgpu.NUMERIC_FROM_ENV)
