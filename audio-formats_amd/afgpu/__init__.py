@@ -71,6 +71,7 @@ MEL_ROW_DTYPE = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), ("first
 assert MEL_ROW_DTYPE.itemsize == 32
 MEL_PAD_REFLECT, MEL_PAD_ZERO = 0, 1             # afg_mel_params.pad_mode
 MEL_POWER, MEL_LOG10 = 0, 1                      # afg_mel_params.out_kind
+MEL_ALGO_DIRECT, MEL_ALGO_FFT = 0, 1             # afg_mel_opts.algorithm
 MEL_SCALE_SLANEY, MEL_SCALE_HTK = 0, 1
 MEL_NORM_NONE, MEL_NORM_SLANEY = 0, 1
 NORM_NONE, NORM_PEAK, NORM_RMS, NORM_STANDARD, NORM_DYNAMIC_RANGE = range(5)     # afg_norm_params.mode
@@ -112,6 +113,7 @@ ABI_SYMBOLS = [
     "afg_collate_layout", "afg_collate_hip", "afg_batch_decode_to_device",
     "afg_resample_taps", "afg_resample_layout", "afg_resample_hip", "afg_batch_decode_resampled",
     "afg_mel_basis", "afg_mel_filters", "afg_mel_frames", "afg_mel_layout", "afg_mel_check_rows", "afg_melspec_hip", "afg_batch_decode_mel",
+    "afg_mel_fft_tables", "afg_mel_fft_layout", "afg_mel_fft_check_rows", "afg_melspec_fft_hip",
     "afg_norm_layout", "afg_norm_check_groups", "afg_normalize_hip", "afg_batch_decode_resampled_norm", "afg_batch_decode_mel_norm",
 ]
 
@@ -258,9 +260,15 @@ class MelParams(C.Structure):
 
 
 class MelOpts(C.Structure):
-    """afg_mel_opts (afg_batch_decode_mel): afg_resample_opts' fields, then the mel parameters and the bank's."""
+    """afg_mel_opts (afg_batch_decode_mel): afg_resample_opts' fields, then the mel parameters and the bank's, then the
+    algorithm (MEL_ALGO_*; 0: the direct path) and a reserved 0.  The structure has all of them (sizeof, offsets, attributes),
+    but `_fields_` -- the list a positional construction walks -- stops at f_max as it did before the last two were appended:
+    they are set by keyword or attribute, and a construction that leaves them out gets the direct path."""
     _fields_ = ResampleOpts._fields_ + [("n_out", C.c_uint32), ("mel", MelParams), ("scale", C.c_uint32), ("norm", C.c_uint32),
-                                        ("f_min", C.c_double), ("f_max", C.c_double)]
+                                        ("f_min", C.c_double), ("f_max", C.c_double), ("algorithm", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+del MelOpts._fields_[-2:]                                    # (the layout is made; the list is what positional arguments map to)
 
 
 class NormGroup(C.Structure):
@@ -527,6 +535,12 @@ def lib():
     L.afg_mel_check_rows.argtypes = [vp, u64, u64, C.POINTER(MelParams), u64, u64, u64, u64]
     L.afg_melspec_hip.argtypes = [u64, vp, u64, C.POINTER(MelParams), vp, u64, vp, u64, vp, u64, vp, u64, vp]
     L.afg_batch_decode_mel.argtypes = [vp, vp, C.c_int, C.POINTER(MelOpts), vp, C.POINTER(BatchResult)]
+    L.afg_mel_fft_tables.argtypes = [u32, u32, vp, u64]
+    L.afg_mel_fft_tables.restype = u64
+    L.afg_mel_fft_layout.argtypes = [vp, u64, C.POINTER(MelParams)]
+    L.afg_mel_fft_layout.restype = u64
+    L.afg_mel_fft_check_rows.argtypes = [vp, u64, u64, C.POINTER(MelParams), u64, u64, u64, u64]
+    L.afg_melspec_fft_hip.argtypes = [u64, vp, u64, C.POINTER(MelParams), vp, u64, vp, u64, vp, u64, vp, u64, vp]
     L.afg_norm_layout.argtypes = [vp, u64]
     L.afg_norm_layout.restype = u64
     L.afg_norm_check_groups.argtypes = [vp, u64, u64, C.POINTER(NormParams), u64, u64]
@@ -1541,15 +1555,60 @@ def melspec(n_rows, d_rows, n_tiles, params, d_in, in_floats, d_basis, basis_flo
                                 int(basis_floats), _ptr(d_filters), int(filters_floats), _ptr(d_out), int(out_floats), _stream(stream)))
 
 
+def _mel_algorithm(who, algorithm):
+    if algorithm == "direct":
+        return MEL_ALGO_DIRECT
+    if algorithm == "fft":
+        return MEL_ALGO_FFT
+    raise ValueError(f"{who}: algorithm {algorithm!r}: 'direct' or 'fft'")
+
+
+def mel_fft_tables(n_fft, win_length=None):
+    """afg_mel_fft_tables: the float32 table of the FFT path, win_length window values then n_fft pairs (cos, -sin) of
+    2 pi j / n_fft, as one array of win_length + 2 * n_fft floats.  Host only.  AfgError for sizes out of range or an n_fft
+    with a prime factor other than 2, 3 and 5."""
+    L_ = lib()
+    win = int(n_fft if win_length is None else win_length)
+    need = int(L_.afg_mel_fft_tables(int(n_fft), win, None, 0))
+    if need == 0:
+        raise AfgError(f"afg: {L_.afg_last_error().decode()}")
+    out = np.zeros(need, np.float32)
+    L_.afg_mel_fft_tables(int(n_fft), win, out.ctypes.data, need)
+    return out
+
+
+def mel_fft_layout(rows, params):
+    """afg_mel_fft_layout: fills first_tile of a MEL_ROW_DTYPE array in place for the FFT path (tiles of 16 frames); returns
+    the launch's tile count, 0 for parameters that path does not take."""
+    assert rows.dtype == MEL_ROW_DTYPE and rows.flags.c_contiguous
+    return int(lib().afg_mel_fft_layout(rows.ctypes.data, len(rows), C.byref(params)))
+
+
+def mel_fft_check_rows(rows, n_tiles, params, in_floats, table_floats, filters_floats, out_floats):
+    """afg_mel_fft_check_rows: what afg_melspec_fft_hip checks before it launches, on host records.  AfgError when one fails."""
+    assert rows.dtype == MEL_ROW_DTYPE and rows.flags.c_contiguous
+    check(lib().afg_mel_fft_check_rows(rows.ctypes.data, len(rows), int(n_tiles), C.byref(params), int(in_floats), int(table_floats),
+                                       int(filters_floats), int(out_floats)))
+
+
+def melspec_fft(n_rows, d_rows, n_tiles, params, d_in, in_floats, d_table, table_floats, d_filters, filters_floats, d_out, out_floats, stream=None):
+    """Enqueue the FFT mel spectrogram kernel (afg_melspec_fft_hip): melspec with mel_fft_tables' table in place of the basis
+    and rows laid out by mel_fft_layout.  Checked like melspec: AfgError, and nothing written, when a check fails."""
+    check(lib().afg_melspec_fft_hip(int(n_rows), _ptr(d_rows), int(n_tiles), C.byref(params), _ptr(d_in), int(in_floats), _ptr(d_table),
+                                    int(table_floats), _ptr(d_filters), int(filters_floats), _ptr(d_out), int(out_floats), _stream(stream)))
+
+
 def batch_decode_mel(files, frames, samplerate=16000, n_fft=400, hop=160, n_mels=80, win_length=None, center=True,
                      pad_mode=MEL_PAD_REFLECT, out_kind=MEL_LOG10, mono=True, out=None, channels=1, n_out=0, log_floor=0.0, f_min=0.0,
                      f_max=0.0, scale=MEL_SCALE_SLANEY, norm=MEL_NORM_SLANEY, first_frame=None, in_channels=0, max_in_rate=0,
-                     lowpass_width=0, n_threads=0):
+                     lowpass_width=0, n_threads=0, algorithm="direct"):
     """afg_batch_decode_mel: (tensor, meta) as batch_decode_tensor_resampled, with the tensor [len(files), channels, n_mels,
     n_out] the (log-)mel spectrogram of every row of that call's tensor of `frames` samples at `samplerate` (include/afg.h
-    has the definition).  n_out 0: every frame `frames` samples have.  The same device and stream rules as
-    batch_decode_tensor."""
+    has the definition).  n_out 0: every frame `frames` samples have.  algorithm "fft" computes the same features through an
+    FFT per frame, held to include/afg.h's error bound instead of to bit patterns (n_fft with prime factors 2, 3 and 5 only).
+    The same device and stream rules as batch_decode_tensor."""
     import torch
+    algo = _mel_algorithm("batch_decode_mel", algorithm)
     bufs = [bytes(f) for f in files]
     n = len(bufs)
     frames, channels, samplerate = int(frames), int(channels), int(samplerate)
@@ -1587,7 +1646,7 @@ def batch_decode_mel(files, frames, samplerate=16000, n_fft=400, hop=160, n_mels
     ptrs = (C.c_char_p * n)(*bufs)
     lens = (C.c_size_t * n)(*[len(b) for b in bufs])
     opts = MelOpts(C.sizeof(MelOpts), int(n_threads), channels, frames, ff, samplerate, 1 if mono else 0, int(in_channels),
-                   int(max_in_rate), int(lowpass_width), n_out, prm, int(scale), int(norm), float(f_min), float(f_max))
+                   int(max_in_rate), int(lowpass_width), n_out, prm, int(scale), int(norm), float(f_min), float(f_max), algorithm=algo, reserved=0)
     res = BatchResult()
     check(lib().afg_batch_decode_mel(ptrs, lens, n, C.byref(opts), out.data_ptr(), C.byref(res)))
     try:
@@ -1707,10 +1766,11 @@ def batch_decode_tensor_normalized(files, frames, channels, samplerate, mode, ta
 def batch_decode_mel_normalized(files, frames, samplerate=16000, n_fft=400, hop=160, n_mels=80, win_length=None, center=True,
                                 pad_mode=MEL_PAD_REFLECT, out_kind=MEL_LOG10, mono=True, out=None, channels=1, n_out=0, log_floor=0.0,
                                 f_min=0.0, f_max=0.0, scale=MEL_SCALE_SLANEY, norm=MEL_NORM_SLANEY, first_frame=None, in_channels=0,
-                                max_in_rate=0, lowpass_width=0, n_threads=0, wave_norm=None, feat_norm=None):
+                                max_in_rate=0, lowpass_width=0, n_threads=0, wave_norm=None, feat_norm=None, algorithm="direct"):
     """afg_batch_decode_mel_norm: batch_decode_mel with wave_norm applied to every file's samples in front of the features
     and feat_norm to every [n_mels, n_out] slab behind them.  Each is None, a NormParams (norm_params), or a mode name;
-    feat_norm="whisper" is Whisper's max(x, x.max() - 8), then (x + 4) / 4."""
+    feat_norm="whisper" is Whisper's max(x, x.max() - 8), then (x + 4) / 4.  algorithm as in batch_decode_mel."""
+    algo = _mel_algorithm("batch_decode_mel_normalized", algorithm)
     wave = None if wave_norm is None else norm_params(wave_norm)
     feat = None if feat_norm is None else norm_params(feat_norm)
     frames, channels, samplerate = int(frames), int(channels), int(samplerate)
@@ -1728,7 +1788,7 @@ def batch_decode_mel_normalized(files, frames, samplerate=16000, n_fft=400, hop=
 
     def call(ptrs, lens, n, ff, out, res):
         opts = MelOpts(C.sizeof(MelOpts), int(n_threads), channels, frames, ff, samplerate, 1 if mono else 0, int(in_channels),
-                       int(max_in_rate), int(lowpass_width), n_out, prm, int(scale), int(norm), float(f_min), float(f_max))
+                       int(max_in_rate), int(lowpass_width), n_out, prm, int(scale), int(norm), float(f_min), float(f_max), algorithm=algo, reserved=0)
         return lib().afg_batch_decode_mel_norm(ptrs, lens, n, C.byref(opts), None if wave is None else C.byref(wave),
                                                None if feat is None else C.byref(feat), out.data_ptr(), C.byref(res))
 

@@ -78,6 +78,12 @@ int melspec_launch(const afg_mel_row *h_rows, uint64_t n_rows, const afg_mel_row
                    const float *d_in, uint64_t in_floats, const float *d_basis, uint64_t basis_floats, const float *d_filters,
                    uint64_t filters_floats, float *d_out, uint64_t out_floats, hipStream_t stream);
 
+// afg_melspec_fft_hip likewise (melspec_fft.hip), and the n_fft its path takes: 16 .. 2048 with prime factors 2, 3 and 5 only
+int melspec_fft_launch(const afg_mel_row *h_rows, uint64_t n_rows, const afg_mel_row *d_rows, uint64_t n_tiles, const afg_mel_params *params,
+                       const float *d_in, uint64_t in_floats, const float *d_table, uint64_t table_floats, const float *d_filters,
+                       uint64_t filters_floats, float *d_out, uint64_t out_floats, hipStream_t stream);
+bool mel_fft_n_ok(uint32_t n_fft);
+
 // afg_normalize_hip likewise (normalize.hip)
 int normalize_launch(const afg_norm_group *h_groups, uint64_t n_groups, const afg_norm_group *d_groups, uint64_t n_tiles,
                      const afg_norm_params *params, const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats,

@@ -1,6 +1,7 @@
 // afg_melspec.cpp -- the host half of the mel spectrogram features (afg_stage.h: MelTables, MelPlane): the basis and the
 // filter bank of include/afg.h's definition, computed in double and kept per parameter set, and afg_batch_decode_mel -- the
-// resampled tensor into a pooled scratch, then one afg_melspec_hip launch per sublist, with the optional normalisations of
+// resampled tensor into a pooled scratch, then one afg_melspec_hip (or, by afg_mel_opts.algorithm, afg_melspec_fft_hip,
+// whose window and twiddle table is made and kept here too) launch per sublist, with the optional normalisations of
 // afg_batch_decode_mel_norm around it.
 #include "afg_stage.h"
 #include "../csrc/afg_common.h"
@@ -38,6 +39,28 @@ void fill_basis(float *out, uint32_t n_fft, uint32_t win)
             row[k] = (float)(w * std::cos(a));
             row[nb16 + k] = (float)(-w * std::sin(a));
         }
+    }
+}
+
+bool fft_shape_ok(uint32_t n_fft, uint32_t win_length)
+{
+    if (n_fft < 16 || n_fft > 2048) { afg::set_error("afg_mel_fft_tables: n_fft %u: 16 .. 2048", n_fft); return false; }
+    if (win_length < 1 || win_length > n_fft) { afg::set_error("afg_mel_fft_tables: win_length %u: 1 .. n_fft (%u)", win_length, n_fft); return false; }
+    if (!afg::mel_fft_n_ok(n_fft)) {
+        afg::set_error("afg_mel_fft_tables: n_fft %u: the FFT path takes 16 .. 2048 with prime factors 2, 3 and 5 only", n_fft);
+        return false;
+    }
+    return true;
+}
+
+// the window, then n_fft pairs (cos, -sin) of 2 pi j / n_fft
+void fill_fft_tables(float *out, uint32_t n_fft, uint32_t win)
+{
+    for (uint32_t j = 0; j < win; j++) out[j] = (float)(0.5 - 0.5 * std::cos(2.0 * kPi * (double)j / (double)win));
+    for (uint32_t j = 0; j < n_fft; j++) {
+        const double a = 2.0 * kPi * (double)j / (double)n_fft;
+        out[win + 2 * j] = (float)std::cos(a);
+        out[win + 2 * j + 1] = (float)(-std::sin(a));
     }
 }
 
@@ -103,22 +126,34 @@ extern "C" uint64_t afg_mel_filters(uint32_t samplerate, uint32_t n_fft, uint32_
     return need;
 }
 
+extern "C" uint64_t afg_mel_fft_tables(uint32_t n_fft, uint32_t win_length, float *out, uint64_t cap)
+{
+    if (!fft_shape_ok(n_fft, win_length)) return 0;
+    const uint64_t need = (uint64_t)win_length + 2 * (uint64_t)n_fft;
+    if (out && cap >= need) fill_fft_tables(out, n_fft, win_length);
+    return need;
+}
+
 namespace afg_front {
 
 int mel_tables(const afg_mel_opts &o, MelTables &t)
 {
     static std::mutex mu;
-    static std::map<std::tuple<uint32_t, uint32_t>, std::shared_ptr<const std::vector<float>>> bases;
+    static std::map<std::tuple<uint32_t, uint32_t, uint32_t>, std::shared_ptr<const std::vector<float>>> bases;   // (algorithm, n_fft, win_length)
     static std::map<std::tuple<uint32_t, uint32_t, uint32_t, double, double, uint32_t, uint32_t>, std::shared_ptr<const std::vector<float>>> banks;
     double f_max = o.f_max;
+    const bool fft = o.algorithm == AFG_MEL_ALGO_FFT;
     if (!basis_shape_ok(o.mel.n_fft, o.mel.win_length)) return AFG_ERR_INVALID;
+    if (fft && !fft_shape_ok(o.mel.n_fft, o.mel.win_length)) return AFG_ERR_UNSUPPORTED;
     if (!filters_shape_ok(o.samplerate, o.mel.n_fft, o.mel.n_mels, o.f_min, &f_max, o.scale, o.norm)) return AFG_ERR_INVALID;
     std::lock_guard<std::mutex> lk(mu);
-    const auto bkey = std::make_tuple(o.mel.n_fft, o.mel.win_length);
+    const auto bkey = std::make_tuple(o.algorithm, o.mel.n_fft, o.mel.win_length);
     auto b = bases.find(bkey);
     if (b == bases.end()) {
-        auto v = std::make_shared<std::vector<float>>((size_t)o.mel.win_length * 2 * nb16_of(o.mel.n_fft));
-        fill_basis(v->data(), o.mel.n_fft, o.mel.win_length);
+        auto v = std::make_shared<std::vector<float>>(fft ? (size_t)o.mel.win_length + 2 * (size_t)o.mel.n_fft
+                                                          : (size_t)o.mel.win_length * 2 * nb16_of(o.mel.n_fft));
+        if (fft) fill_fft_tables(v->data(), o.mel.n_fft, o.mel.win_length);
+        else fill_basis(v->data(), o.mel.n_fft, o.mel.win_length);
         b = bases.emplace(bkey, std::move(v)).first;
     }
     const auto fkey = std::make_tuple(o.samplerate, o.mel.n_fft, o.mel.n_mels, o.f_min, f_max, o.scale, o.norm);
@@ -148,7 +183,8 @@ int MelPlane::launch(const afg_mel_opts &o, const MelTables &t, const float *d_i
         recs.push_back(r);
     }
     if (recs.empty()) return AFG_OK;
-    const uint64_t tiles = afg_mel_layout(recs.data(), recs.size(), &o.mel);
+    const bool fft = o.algorithm == AFG_MEL_ALGO_FFT;
+    const uint64_t tiles = fft ? afg_mel_fft_layout(recs.data(), recs.size(), &o.mel) : afg_mel_layout(recs.data(), recs.size(), &o.mel);
     if (!tables_up) {                                            // (the tables live as long as the process: mel_tables)
         if (int rc = d_basis.alloc(t.basis->size() * sizeof(float))) return rc;
         if (int rc = d_filters.alloc(t.filters->size() * sizeof(float))) return rc;
@@ -158,6 +194,10 @@ int MelPlane::launch(const afg_mel_opts &o, const MelTables &t, const float *d_i
     }
     if (int rc = d_recs.alloc(recs.size() * sizeof(afg_mel_row))) return rc;
     AFG_HIP_CHECK(hipMemcpyAsync(d_recs.p, recs.data(), recs.size() * sizeof(afg_mel_row), hipMemcpyHostToDevice, st));
+    if (fft)
+        return afg::melspec_fft_launch(recs.data(), recs.size(), (const afg_mel_row *)d_recs.p, tiles, &o.mel, d_in, n_rows * o.frames,
+                                       (const float *)d_basis.p, t.basis->size(), (const float *)d_filters.p, t.filters->size(), d_out,
+                                       n_rows * slab, st);
     return afg::melspec_launch(recs.data(), recs.size(), (const afg_mel_row *)d_recs.p, tiles, &o.mel, d_in, n_rows * o.frames,
                                (const float *)d_basis.p, t.basis->size(), (const float *)d_filters.p, t.filters->size(), d_out,
                                n_rows * slab, st);
@@ -179,6 +219,11 @@ int afg_front::mel_batch(const uint8_t *const *data, const size_t *length, int n
             return AFG_ERR_INVALID;
         }
         const afg_mel_opts &o = *opts;
+        if (o.algorithm != AFG_MEL_ALGO_DIRECT && o.algorithm != AFG_MEL_ALGO_FFT) {
+            afg::set_error("afg_mel_opts.algorithm %u: AFG_MEL_ALGO_DIRECT or AFG_MEL_ALGO_FFT", o.algorithm);
+            return AFG_ERR_INVALID;
+        }
+        if (o.reserved != 0) { afg::set_error("afg_mel_opts.reserved %u: must be 0", o.reserved); return AFG_ERR_INVALID; }
         afg_resample_opts ro;
         std::memset(&ro, 0, sizeof(ro));
         ro.struct_size = (uint32_t)sizeof(ro);
@@ -188,6 +233,8 @@ int afg_front::mel_batch(const uint8_t *const *data, const size_t *length, int n
         afg_front::ResampleJob job;
         if (int rc = afg_front::resampled_check(&ro, data, length, n_files, job)) return rc;
         if (int rc = afg_mel_check_rows(nullptr, 0, 0, &o.mel, 0, 0, 0, 0)) return rc;       // the mel parameters alone
+        if (o.algorithm == AFG_MEL_ALGO_FFT)
+            if (int rc = afg_mel_fft_check_rows(nullptr, 0, 0, &o.mel, 0, 0, 0, 0)) return rc;   // and the n_fft that path takes
         afg_front::MelTables tables;
         if (int rc = afg_front::mel_tables(o, tables)) return rc;
         const uint32_t most = afg_mel_frames(&o.mel, o.frames), pad = o.mel.center ? o.mel.n_fft / 2 : 0;

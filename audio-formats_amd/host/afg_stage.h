@@ -199,11 +199,12 @@ struct BatchResult {
 
 // ---- mel spectrogram features (afg_batch_decode_mel, host/afg_melspec.cpp) ----
 // The tables of one parameter set, made once and kept for the process: afg_mel_basis's and afg_mel_filters'.
+// With AFG_MEL_ALGO_FFT `basis` holds afg_mel_fft_tables' table instead.
 struct MelTables {
     std::shared_ptr<const std::vector<float>> basis, filters;
 };
 int mel_tables(const afg_mel_opts &o, MelTables &t);            // AFG_ERR_INVALID: afg_last_error says why
-// One launch of afg_melspec_hip (csrc/melspec.hip) over rows [0, n_rows) of T samples each, contiguous in d_in, to slabs of
+// One launch of afg_melspec_hip (csrc/melspec.hip), or by o.algorithm of afg_melspec_fft_hip (csrc/melspec_fft.hip), over rows [0, n_rows) of T samples each, contiguous in d_in, to slabs of
 // n_mels * n_out floats, contiguous in d_out.  The object holds the records its upload reads, and the tables on the device
 // (uploaded on the first launch): it lives until `st` has drained.
 struct MelPlane {

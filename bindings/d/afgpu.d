@@ -473,7 +473,16 @@ int afg_mel_check_rows(const(afg_mel_row)* rows, ulong n_rows, ulong n_tiles, co
 int afg_melspec_hip(ulong n_rows, const(afg_mel_row)* d_rows, ulong n_tiles, const(afg_mel_params)* params, const(float)* d_in,
                     ulong in_floats, const(float)* d_basis, ulong basis_floats, const(float)* d_filters, ulong filters_floats,
                     float* d_out, ulong out_floats, void* hip_stream);
-struct afg_mel_opts { uint struct_size; int n_threads; uint channels; uint frames; const(long)* first_frame; uint samplerate, mono, in_channels, max_in_rate, lowpass_width, n_out; afg_mel_params mel; uint scale, norm; double f_min, f_max; }
+// the same features through an FFT per frame (afg_mel_opts.algorithm, or the kernel-level entries below)
+enum { AFG_MEL_ALGO_DIRECT = 0, AFG_MEL_ALGO_FFT = 1 }
+ulong afg_mel_fft_tables(uint n_fft, uint win_length, float* out_, ulong cap);
+ulong afg_mel_fft_layout(afg_mel_row* rows, ulong n_rows, const(afg_mel_params)* params);
+int afg_mel_fft_check_rows(const(afg_mel_row)* rows, ulong n_rows, ulong n_tiles, const(afg_mel_params)* params, ulong in_floats,
+                           ulong table_floats, ulong filters_floats, ulong out_floats);
+int afg_melspec_fft_hip(ulong n_rows, const(afg_mel_row)* d_rows, ulong n_tiles, const(afg_mel_params)* params, const(float)* d_in,
+                        ulong in_floats, const(float)* d_table, ulong table_floats, const(float)* d_filters, ulong filters_floats,
+                        float* d_out, ulong out_floats, void* hip_stream);
+struct afg_mel_opts { uint struct_size; int n_threads; uint channels; uint frames; const(long)* first_frame; uint samplerate, mono, in_channels, max_in_rate, lowpass_width, n_out; afg_mel_params mel; uint scale, norm; double f_min, f_max; uint algorithm, reserved; }
 int afg_batch_decode_mel(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_mel_opts)* opts, float* d_out,
                          afg_batch_result* out_);
 // normalisation: statistics per group of rows and the gain / offset they decide (include/afg.h has the definition)

@@ -1249,6 +1249,44 @@ int afg_melspec_hip(uint64_t n_rows, const afg_mel_row *d_rows, uint64_t n_tiles
                     uint64_t in_floats, const float *d_basis, uint64_t basis_floats, const float *d_filters, uint64_t filters_floats,
                     float *d_out, uint64_t out_floats, void *hip_stream);
 
+/* The same features through an FFT per frame: an opt-in algorithm (AFG_MEL_ALGO_FFT) beside the direct product above.  It
+ * computes the value defined above -- the same window, centring, padding, frame count, bank, fmaxf floor and output layout,
+ * whose float64 statement is basis64, power64 and filters64 of tests/melspec_model.py -- but only the float32 summation
+ * order is free, so it is held to an error bound and not to bit patterns.  It does not listen to AFG_NUMERIC or
+ * afg_set_numeric_mode.  n_fft: 16 .. 2048 whose prime factors are 2, 3 and 5 only (400, 480, 512, 800, 960, 1024, 2048
+ * among them); any other n_fft is AFG_ERR_UNSUPPORTED and the direct path remains for it.
+ *
+ * Bound.  u = 2^-24; A_f = sum over n of |x_n| w[n] of frame f in float64; B = 8 ceil(log2(n_fft)) + 8.  Then
+ * |re - re64| and |im - im64| are at most E_f = B u A_f: a binary level of a Cooley-Tukey factorisation costs a value at
+ * most a rounded twiddle, a complex multiply (3 roundings), a butterfly add and the rotation constants of radix 3 and 5 --
+ * 8 per level -- and 8 more cover the window multiply, the real / complex split pass and second-order terms.  p and mel are
+ * summed in any order, fused or not, over the bank's weights as given (dense, every bin).  For a bank without negative
+ * weights, with p_hi = (|re64| + E)^2 + (|im64| + E)^2 and p_lo = max(|re64| - E, 0)^2 + max(|im64| - E, 0)^2, the
+ * AFG_MEL_POWER output lies in [(1 - (n_bins + 4) u) sum_k W p_lo, (1 + (n_bins + 4) u) sum_k W p_hi], W the float32 bank
+ * taken to float64, and AFG_MEL_LOG10 within 3 ulp of log10 of that interval after the floor.
+ * Locality.  A frame's outputs depend on that row's samples under that frame and on the parameters, and on nothing else:
+ * the same row gives the same bits wherever it stands, and a NaN sample makes NaN (AFG_MEL_POWER; log10f(floor) with
+ * AFG_MEL_LOG10) of every mel of exactly the frames whose window span covers it.  A row without samples under zero padding
+ * and padding outside the row give +0.0f power, or log10f(log_floor), as above.
+ *
+ * afg_mel_fft_tables: host only.  Returns win_length + 2 * n_fft floats and with cap >= that fills the window w[j],
+ * j < win_length, then n_fft pairs (cos, -sin) of 2 pi j / n_fft; each computed in double and rounded once to float32.
+ * Returns 0 with afg_last_error set for sizes out of range or an n_fft this path does not take.
+ * afg_mel_fft_layout, afg_mel_fft_check_rows, afg_melspec_fft_hip: as afg_mel_layout, afg_mel_check_rows and
+ * afg_melspec_hip, with the same afg_mel_params and afg_mel_row records and afg_mel_fft_tables' table in place of the
+ * basis.  A tile is 16 frames of one row, so a layout made by afg_mel_layout does not serve here.  The same checks are
+ * made before the launch; afg_mel_fft_check_rows needs no device.  The kernel writes exactly n_mels * out_frames floats
+ * per record and reads no input float outside the record's row. */
+#define AFG_MEL_ALGO_DIRECT 0
+#define AFG_MEL_ALGO_FFT    1
+uint64_t afg_mel_fft_tables(uint32_t n_fft, uint32_t win_length, float *out, uint64_t cap);
+uint64_t afg_mel_fft_layout(afg_mel_row *rows, uint64_t n_rows, const afg_mel_params *params);
+int afg_mel_fft_check_rows(const afg_mel_row *rows, uint64_t n_rows, uint64_t n_tiles, const afg_mel_params *params, uint64_t in_floats,
+                           uint64_t table_floats, uint64_t filters_floats, uint64_t out_floats);
+int afg_melspec_fft_hip(uint64_t n_rows, const afg_mel_row *d_rows, uint64_t n_tiles, const afg_mel_params *params, const float *d_in,
+                        uint64_t in_floats, const float *d_table, uint64_t table_floats, const float *d_filters, uint64_t filters_floats,
+                        float *d_out, uint64_t out_floats, void *hip_stream);
+
 /* afg_batch_decode_resampled followed by afg_melspec_hip: d_out is n_files * channels * n_mels * n_out floats on the
  * current device, and slab [i, k] is the definition above applied to row [i, k] of the tensor afg_batch_decode_resampled
  * makes of the same list with the leading fields of the options (frames is T, in samples at `samplerate`).  n_out == 0
@@ -1260,7 +1298,10 @@ int afg_melspec_hip(uint64_t n_rows, const afg_mel_row *d_rows, uint64_t n_tiles
  * afg_batch_decode_resampled; pcm points at the file's mel slab (NULL when the file failed or was refused).
  * Checked before any device call, AFG_ERR_INVALID with afg_last_error set: everything afg_batch_decode_resampled checks, a
  * struct_size below sizeof(afg_mel_opts), the mel parameters and the bank's arguments out of range, T without a frame,
- * n_out above max_frames, reflect with T <= pad.  n_files == 0 is AFG_OK and touches nothing. */
+ * n_out above max_frames, reflect with T <= pad, an unknown algorithm, a non-zero `reserved`; AFG_ERR_UNSUPPORTED for
+ * AFG_MEL_ALGO_FFT with an n_fft that path does not take.  n_files == 0 is AFG_OK and touches nothing.
+ * algorithm: AFG_MEL_ALGO_DIRECT (0) is afg_melspec_hip; AFG_MEL_ALGO_FFT runs afg_melspec_fft_hip in its place, its table
+ * kept per parameter set like the basis; everything around the kernel is the same. */
 typedef struct afg_mel_opts {
     uint32_t       struct_size;   /* sizeof(afg_mel_opts) */
     int            n_threads;     /* from here to lowpass_width: as afg_resample_opts */
@@ -1278,6 +1319,8 @@ typedef struct afg_mel_opts {
     uint32_t       norm;          /* AFG_MEL_NORM_* */
     double         f_min;         /* Hz */
     double         f_max;         /* Hz; 0 means samplerate / 2 */
+    uint32_t       algorithm;     /* AFG_MEL_ALGO_* */
+    uint32_t       reserved;      /* 0 */
 } afg_mel_opts;
 int afg_batch_decode_mel(const uint8_t *const *data, const size_t *length, int n_files, const afg_mel_opts *opts, float *d_out,
                          afg_batch_result *out);

@@ -2,11 +2,13 @@
 """tools/bench_melspec.py -- what the mel spectrogram features cost, written to profiles/melspec_bench.json.
 
 (a) kernel leg: rows of 480 000 device-resident samples (30 s at 16 kHz) at the Whisper shape (n_fft 400, hop 160, 80 mels,
-    3000 of 3001 frames) and at n_fft 1024, hop 256, 128 mels: afg_melspec_hip beside torch.stft + power + matmul with the
-    same bank + log10 on the same device over the same tensor, alternating in one process, medians of 5.  The float32 MFMA
+    3000 of 3001 frames) and at n_fft 1024, hop 256, 128 mels: afg_melspec_hip (the direct product), afg_melspec_fft_hip (the
+    FFT path) and torch.stft + power + matmul with the same bank + log10 on the same device over the same tensor, the three
+    alternating in one process, medians of 5.  The float32 MFMA
     rate the kernel is compared with is 155 TFLOP/s; the record carries the fraction reached.
-(b) call leg: generated MP3 files (44.1 kHz stereo) to [files, 1, 80, 3000] through afgpu.batch_decode_mel, against
-    afgpu.batch_decode_tensor_resampled followed by the same torch expression.  The two alternate; medians of 5.
+(b) call leg: generated MP3 files (44.1 kHz stereo) to [files, 1, 80, 3000] through afgpu.batch_decode_mel with either
+    algorithm, against afgpu.batch_decode_tensor_resampled followed by the same torch expression.  The three alternate; medians
+    of 5.
 No ratio is promised and nothing gates on one.
 
     python tools/bench_melspec.py [--rows 1024] [--call-files 256] [--distinct 32] [--out profiles/melspec_bench.json]
@@ -73,25 +75,38 @@ def kernel_leg(n_rows):
         rec["in_frames"], rec["out_frames"] = SAMPLES, n_out
         tiles = afgpu.mel_layout(rec, prm)
         d_rec = torch.from_numpy(rec.view(np.uint8).copy()).cuda()
+        fft_rec = rec.copy()
+        fft_tiles = afgpu.mel_fft_layout(fft_rec, prm)
+        d_fft_rec = torch.from_numpy(fft_rec.view(np.uint8).copy()).cuda()
+        table = afgpu.mel_fft_tables(n_fft)
+        d_table = torch.from_numpy(table.copy()).cuda()
         d_out = torch.empty((n_rows, n_mels, n_out), dtype=torch.float32, device="cuda")
 
         def run_kernel():
             afgpu.melspec(n_rows, d_rec, tiles, prm, x, x.numel(), d_basis, basis.size, d_bank, bank.size, d_out, d_out.numel())
 
+        def run_fft():
+            afgpu.melspec_fft(n_rows, d_fft_rec, fft_tiles, prm, x, x.numel(), d_table, table.size, d_bank, bank.size, d_out, d_out.numel())
+
         def run_torch():
             return torch_features(x, n_fft, hop, d_bank, window, n_out)
 
+        run_fft()
+        worst_fft = float((run_torch() - d_out).abs().max().item())
         run_kernel()
         worst = float((run_torch() - d_out).abs().max().item())
-        tk, tt = [], []
-        for _ in range(PASSES):                                   # alternating, so that clocks and neighbours hit both alike
+        tk, tf, tt = [], [], []
+        for _ in range(PASSES):                                   # alternating, so that clocks and neighbours hit all alike
             tk.append(timed(run_kernel))
+            tf.append(timed(run_fft))
             tt.append(timed(run_torch))
-        sk, st_ = median(tk), median(tt)
+        sk, sf, st_ = median(tk), median(tf), median(tt)
         n_bins = n_fft // 2 + 1
         flops = n_rows * n_out * (2.0 * n_fft * 2 * n_bins + 2.0 * n_bins * n_mels)      # the two products as the definition has them
         out.append({"n_fft": n_fft, "hop": hop, "n_mels": n_mels, "rows": n_rows, "samples": SAMPLES, "frames": n_out, "tiles": tiles,
                     "max_abs_difference_log10": worst, "melspec_seconds": sk, "torch_seconds": st_, "torch_over_melspec": st_ / sk,
+                    "fft_tiles": fft_tiles, "fft_max_abs_difference_log10": worst_fft, "fft_seconds": sf, "melspec_over_fft": sk / sf,
+                    "torch_over_fft": st_ / sf,
                     "flops": flops, "melspec_TFLOPs": flops / sk / 1e12, "fraction_of_f32_mfma_rate": flops / sk / MFMA_F32_FLOPS,
                     "bytes_read_and_written": n_rows * (SAMPLES + n_mels * n_out) * 4})
         print(json.dumps(out[-1]), flush=True)
@@ -119,18 +134,27 @@ def call_leg(blobs, threads):
         torch.cuda.synchronize()
         return t[:, 0]
 
-    a, b = old(), new()                                           # warm-up; the two agree to float32 rounding, not bit for bit
-    worst = float((a - b).abs().max().item())
-    wall = {"old": [], "new": []}
+    def fft():
+        t, _ = afgpu.batch_decode_mel(blobs, SAMPLES, RATE, n_out=s["n_out"], out=out, n_threads=threads, algorithm="fft")
+        torch.cuda.synchronize()
+        return t[:, 0]
+
+    a = old()                                                     # warm-up; the three agree to float32 rounding, not bit for bit
+    worst_fft = float((a - fft()).abs().max().item())
+    worst = float((a - new()).abs().max().item())
+    wall = {"old": [], "new": [], "fft": []}
     for _ in range(PASSES):
-        for name, fn in (("old", old), ("new", new)):
+        for name, fn in (("old", old), ("new", new), ("fft", fft)):
             t0 = time.perf_counter()
             fn()
             wall[name].append(time.perf_counter() - t0)
     rec = {"files": len(blobs), "samples": SAMPLES, "frames": s["n_out"], "max_abs_difference_log10": worst}
-    for name in ("old", "new"):
+    rec["fft_max_abs_difference_log10"] = worst_fft
+    for name in ("old", "new", "fft"):
         rec[name + "_seconds"] = median(wall[name])
     rec["speedup"] = rec["old_seconds"] / rec["new_seconds"]
+    rec["fft_speedup"] = rec["old_seconds"] / rec["fft_seconds"]
+    rec["new_over_fft"] = rec["new_seconds"] / rec["fft_seconds"]
     print(json.dumps(rec), flush=True)
     return rec
 
@@ -147,7 +171,8 @@ def main():
     args = ap.parse_args()
     res = {"what": "tools/bench_melspec.py", "passes": PASSES,
            "note": "kernel leg: timed through the public afg_melspec_hip, which fetches the rows and waits for its stream before every "
-                   "launch (the batch path checks its host copy and does not)"}
+                   "launch (the batch path checks its host copy and does not); afg_melspec_fft_hip likewise.  old: resampled tensor + torch; "
+                   "new: batch_decode_mel, direct; fft: batch_decode_mel, algorithm fft"}
     distinct = {}
     if not args.skip_call:                                         # (worker processes: before anything touches the GPU)
         from e2e_files import generate_files
