@@ -8,13 +8,15 @@ from afgpu import Mp3Plan, MP3_STATE_FLOATS, synthetic
 pytestmark = pytest.mark.gpu
 
 
-def run_gpu(gpu, granules, channels, coef, flags, seg=0, state=None):
+def run_gpu(gpu, granules, channels, coef, flags, seg=0, state=None, pcm=None):
+    """`pcm`: a caller's device plane of coef.size floats to decode into (default: a fresh one full of NaN)."""
     import torch
     plan = Mp3Plan(granules, channels, seg)
     assert plan.blocks * 576 == coef.size
     d_coef = torch.from_numpy(coef).to(gpu)
     d_flags = torch.from_numpy(flags.view(np.int32)).to(gpu)
-    d_pcm = torch.full((coef.size,), float("nan"), dtype=torch.float32, device=gpu)
+    d_pcm = torch.full((coef.size,), float("nan"), dtype=torch.float32, device=gpu) if pcm is None else pcm
+    assert d_pcm.numel() == coef.size
     d_state = None if state is None else torch.from_numpy(state).to(gpu)
     plan.transform(d_coef, d_flags, d_pcm, d_state)
     torch.cuda.synchronize()
