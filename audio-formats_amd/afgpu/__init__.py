@@ -77,6 +77,9 @@ MEL_NORM_NONE, MEL_NORM_SLANEY = 0, 1
 NORM_NONE, NORM_PEAK, NORM_RMS, NORM_STANDARD, NORM_DYNAMIC_RANGE = range(5)     # afg_norm_params.mode
 NORM_MODE_NAMES = {"none": NORM_NONE, "peak": NORM_PEAK, "rms": NORM_RMS, "standard": NORM_STANDARD, "dynamic_range": NORM_DYNAMIC_RANGE}
 NORM_TILE = 4096                                 # floats of one row per tile of afg_normalize_hip
+CEP_DCT_NONE, CEP_DCT_ORTHO = 0, 1               # afg_cep_dct's norm, afg_mfcc_opts.dct_norm
+CEP_DCT_NAMES = {"none": CEP_DCT_NONE, "ortho": CEP_DCT_ORTHO}
+CEP_TILE = 64                                    # frames of one record per tile of afg_cepstra_hip
 
 # every symbol include/afg.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -115,6 +118,7 @@ ABI_SYMBOLS = [
     "afg_mel_basis", "afg_mel_filters", "afg_mel_frames", "afg_mel_layout", "afg_mel_check_rows", "afg_melspec_hip", "afg_batch_decode_mel",
     "afg_mel_fft_tables", "afg_mel_fft_layout", "afg_mel_fft_check_rows", "afg_melspec_fft_hip",
     "afg_norm_layout", "afg_norm_check_groups", "afg_normalize_hip", "afg_batch_decode_resampled_norm", "afg_batch_decode_mel_norm",
+    "afg_cep_dct", "afg_cep_layout", "afg_cep_check_rows", "afg_cepstra_hip", "afg_batch_decode_mfcc",
 ]
 
 
@@ -292,6 +296,28 @@ class NormParams(C.Structure):
 NORM_GROUP_DTYPE = np.dtype(NormGroup)           # arrays of the records, as the other stages' *_DTYPE
 NORM_STATS_DTYPE = np.dtype(NormStats)
 assert NORM_GROUP_DTYPE.itemsize == 48 and NORM_STATS_DTYPE.itemsize == 40 and C.sizeof(NormParams) == 24
+
+
+class CepParams(C.Structure):
+    """afg_cep_params (afg_cepstra_hip)."""
+    _fields_ = [("n_mels", C.c_uint32), ("n_ceps", C.c_uint32), ("delta_order", C.c_uint32), ("delta_win", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class CepRow(C.Structure):
+    """afg_cep_row: one [n_mels, frames] slab and its [(1 + delta_order) * n_ceps, frames] output (afg_cepstra_hip)."""
+    _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("first_tile", C.c_uint64), ("frames", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class MfccOpts(C.Structure):
+    """afg_mfcc_opts (afg_batch_decode_mfcc)."""
+    _fields_ = [("struct_size", C.c_uint32), ("dct_norm", C.c_uint32), ("mel", MelOpts), ("cep", CepParams), ("lifter", C.c_double),
+                ("log_scale", C.c_double)]
+
+
+CEP_ROW_DTYPE = np.dtype(CepRow)                 # arrays of the records, as the other stages' *_DTYPE
+assert CEP_ROW_DTYPE.itemsize == 32 and C.sizeof(CepParams) == 32
 
 
 SAMPLE_F32, SAMPLE_F64, SAMPLE_PCM_S8, SAMPLE_PCM_S16, SAMPLE_PCM_S24 = range(5)     # afg_batch_opts.sample_type
@@ -546,6 +572,14 @@ def lib():
     L.afg_norm_check_groups.argtypes = [vp, u64, u64, C.POINTER(NormParams), u64, u64]
     L.afg_normalize_hip.argtypes = [u64, vp, u64, C.POINTER(NormParams), vp, u64, vp, u64, vp, vp, vp]
     L.afg_batch_decode_resampled_norm.argtypes = [vp, vp, C.c_int, C.POINTER(ResampleOpts), C.POINTER(NormParams), vp, vp, C.POINTER(BatchResult)]
+    L.afg_cep_dct.argtypes = [u32, u32, u32, C.c_double, C.c_double, vp, u64]
+    L.afg_cep_dct.restype = u64
+    L.afg_cep_layout.argtypes = [vp, u64, C.POINTER(CepParams)]
+    L.afg_cep_layout.restype = u64
+    L.afg_cep_check_rows.argtypes = [vp, u64, u64, C.POINTER(CepParams), u64, u64, u64]
+    L.afg_cepstra_hip.argtypes = [u64, vp, u64, C.POINTER(CepParams), vp, u64, vp, u64, vp, u64, vp]
+    L.afg_batch_decode_mfcc.argtypes = [vp, vp, C.c_int, C.POINTER(MfccOpts), C.POINTER(NormParams), C.POINTER(NormParams), vp,
+                                        C.POINTER(BatchResult)]
     L.afg_batch_decode_mel_norm.argtypes = [vp, vp, C.c_int, C.POINTER(MelOpts), C.POINTER(NormParams), C.POINTER(NormParams), vp,
                                             C.POINTER(BatchResult)]
     _lib = L
@@ -1793,6 +1827,96 @@ def batch_decode_mel_normalized(files, frames, samplerate=16000, n_fft=400, hop=
                                                None if feat is None else C.byref(feat), out.data_ptr(), C.byref(res))
 
     return _batch_tensor_call("batch_decode_mel_normalized", files, (len(files), channels, int(n_mels), n_out if n_out else most), out,
+                              first_frame, call)
+
+
+def cep_params(n_mels=80, n_ceps=13, delta_order=0, delta_win=2):
+    """afg_cep_params: n_ceps coefficients of slabs of n_mels rows, delta_order planes of regression deltas over
+    2 * delta_win + 1 frames behind them (torchaudio's win_length 5 is delta_win 2)."""
+    return CepParams(int(n_mels), int(n_ceps), int(delta_order), int(delta_win))
+
+
+def _cep_dct_norm(who, norm):
+    if isinstance(norm, str):
+        if norm not in CEP_DCT_NAMES:
+            raise ValueError(f"{who}: dct norm {norm!r}: one of {sorted(CEP_DCT_NAMES)}")
+        return CEP_DCT_NAMES[norm]
+    return int(norm)
+
+
+def cep_dct(n_ceps, n_mels, norm="ortho", lifter=0.0, log_scale=1.0):
+    """afg_cep_dct: the float32 table [n_ceps, n_mels] of a DCT-II over the mel axis with its lifter (HTK / Kaldi: 1 +
+    lifter / 2 * sin(pi q / lifter), q from 0; 0: none) and log_scale folded in (include/afg.h has the definition).  norm:
+    "ortho", "none" or CEP_DCT_*.  Host only.  AfgError for arguments out of range."""
+    L_ = lib()
+    args = (int(n_ceps), int(n_mels), _cep_dct_norm("cep_dct", norm), float(lifter), float(log_scale))
+    need = int(L_.afg_cep_dct(*args, None, 0))
+    if need == 0:
+        raise AfgError(f"afg: {L_.afg_last_error().decode()}")
+    out = np.zeros(need, np.float32)
+    L_.afg_cep_dct(*args, out.ctypes.data, need)
+    return out.reshape(int(n_ceps), int(n_mels))
+
+
+def cep_layout(rows, params):
+    """afg_cep_layout: fills first_tile of a CEP_ROW_DTYPE array in place; returns the launch's tile count."""
+    assert rows.dtype == CEP_ROW_DTYPE and rows.flags.c_contiguous
+    return int(lib().afg_cep_layout(rows.ctypes.data, len(rows), C.byref(params)))
+
+
+def cep_check_rows(rows, n_tiles, params, in_floats, dct_floats, out_floats):
+    """afg_cep_check_rows: what afg_cepstra_hip checks before it launches, on host records.  AfgError when one fails."""
+    assert rows.dtype == CEP_ROW_DTYPE and rows.flags.c_contiguous
+    check(lib().afg_cep_check_rows(rows.ctypes.data, len(rows), int(n_tiles), C.byref(params), int(in_floats), int(dct_floats),
+                                   int(out_floats)))
+
+
+def cepstra(n_rows, d_rows, n_tiles, params, d_in, in_floats, d_dct, dct_floats, d_out, out_floats, stream=None):
+    """Enqueue the cepstral kernel (afg_cepstra_hip) on device arrays: [n_mels, frames] slabs to [(1 + delta_order) * n_ceps,
+    frames] statics and deltas.  The parameters and the records are checked first (the call waits for `stream` to read
+    them): AfgError, and nothing written, when one fails."""
+    check(lib().afg_cepstra_hip(int(n_rows), _ptr(d_rows), int(n_tiles), C.byref(params), _ptr(d_in), int(in_floats), _ptr(d_dct),
+                                int(dct_floats), _ptr(d_out), int(out_floats), _stream(stream)))
+
+
+def batch_decode_mfcc(files, frames, n_mfcc=13, delta_order=0, delta_win=2, dct_norm="ortho", lifter=0, log_scale=1.0, cmvn=None,
+                      wave_norm=None, algorithm="direct", samplerate=16000, n_fft=400, hop=160, n_mels=80, win_length=None, center=True,
+                      pad_mode=MEL_PAD_REFLECT, mono=True, out=None, channels=1, n_out=0, log_floor=0.0, f_min=0.0, f_max=0.0,
+                      scale=MEL_SCALE_SLANEY, norm=MEL_NORM_SLANEY, first_frame=None, in_channels=0, max_in_rate=0, lowpass_width=0,
+                      n_threads=0):
+    """afg_batch_decode_mfcc: (tensor, meta) as batch_decode_mel, with the tensor [len(files), channels, (1 + delta_order) *
+    n_mfcc, n_out]: the cepstra (cep_dct of n_mfcc, n_mels, dct_norm, lifter, log_scale) of every log-mel slab
+    batch_decode_mel_normalized(..., wave_norm=wave_norm) makes of the same list, their deltas and delta-deltas stacked
+    behind them.  cmvn: None, a NormParams (norm_params) or a mode name, applied to every output row over its n_out frames;
+    "standard" is per-coefficient mean and variance normalisation.  algorithm and the mel keywords as in batch_decode_mel."""
+    algo = _mel_algorithm("batch_decode_mfcc", algorithm)
+    dct = _cep_dct_norm("batch_decode_mfcc", dct_norm)
+    wave = None if wave_norm is None else norm_params(wave_norm)
+    rows = None if cmvn is None else norm_params(cmvn)
+    frames, channels, samplerate = int(frames), int(channels), int(samplerate)
+    if frames < 1 or channels < 1 or samplerate < 1:
+        raise ValueError("batch_decode_mfcc: frames, channels and samplerate must be at least 1")
+    if mono and channels != 1:
+        raise ValueError("batch_decode_mfcc: a mono tensor has one channel")
+    n_mfcc, delta_order = int(n_mfcc), int(delta_order)
+    if n_mfcc < 1 or delta_order < 0:
+        raise ValueError("batch_decode_mfcc: n_mfcc must be at least 1 and delta_order at least 0")
+    prm = mel_params(n_fft, hop, n_mels, win_length, center, pad_mode, MEL_LOG10, log_floor)
+    most = mel_frames(prm, frames)
+    if most == 0:
+        raise ValueError(f"batch_decode_mfcc: {frames} samples hold no frame of these parameters ({lib().afg_last_error().decode()})")
+    n_out = int(n_out)
+    if n_out < 0 or n_out > most:
+        raise ValueError(f"batch_decode_mfcc: n_out {n_out}, but {frames} samples have {most} frames")
+
+    def call(ptrs, lens, n, ff, out, res):
+        mel = MelOpts(C.sizeof(MelOpts), int(n_threads), channels, frames, ff, samplerate, 1 if mono else 0, int(in_channels),
+                      int(max_in_rate), int(lowpass_width), n_out, prm, int(scale), int(norm), float(f_min), float(f_max), algorithm=algo, reserved=0)
+        opts = MfccOpts(C.sizeof(MfccOpts), dct, mel, cep_params(n_mels, n_mfcc, delta_order, delta_win), float(lifter), float(log_scale))
+        return lib().afg_batch_decode_mfcc(ptrs, lens, n, C.byref(opts), None if wave is None else C.byref(wave),
+                                           None if rows is None else C.byref(rows), out.data_ptr(), C.byref(res))
+
+    return _batch_tensor_call("batch_decode_mfcc", files, (len(files), channels, (1 + delta_order) * n_mfcc, n_out if n_out else most), out,
                               first_frame, call)
 
 

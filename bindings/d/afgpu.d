@@ -500,6 +500,21 @@ int afg_batch_decode_resampled_norm(const(ubyte*)* data, const(size_t)* length, 
                                     const(afg_norm_params)* norm, float* d_out, afg_norm_stats* d_stats, afg_batch_result* out_);
 int afg_batch_decode_mel_norm(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_mel_opts)* opts,
                               const(afg_norm_params)* wave_norm, const(afg_norm_params)* feat_norm, float* d_out, afg_batch_result* out_);
+// cepstral features behind the log-mel stage: a DCT-II over the mel axis with its lifter, and regression deltas (include/afg.h
+// has the definition)
+enum : uint { AFG_CEP_DCT_NONE = 0, AFG_CEP_DCT_ORTHO = 1 }
+enum : uint { AFG_CEP_TILE = 64 }
+struct afg_cep_params { uint n_mels, n_ceps, delta_order, delta_win; uint[4] reserved; }
+struct afg_cep_row { ulong in_off, out_off, first_tile; uint frames, reserved; }
+struct afg_mfcc_opts { uint struct_size, dct_norm; afg_mel_opts mel; afg_cep_params cep; double lifter, log_scale; }
+ulong afg_cep_dct(uint n_ceps, uint n_mels, uint norm, double lifter, double log_scale, float* out_, ulong cap);
+ulong afg_cep_layout(afg_cep_row* rows, ulong n_rows, const(afg_cep_params)* params);
+int afg_cep_check_rows(const(afg_cep_row)* rows, ulong n_rows, ulong n_tiles, const(afg_cep_params)* params, ulong in_floats,
+                       ulong dct_floats, ulong out_floats);
+int afg_cepstra_hip(ulong n_rows, const(afg_cep_row)* d_rows, ulong n_tiles, const(afg_cep_params)* params, const(float)* d_in,
+                    ulong in_floats, const(float)* d_dct, ulong dct_floats, float* d_out, ulong out_floats, void* hip_stream);
+int afg_batch_decode_mfcc(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_mfcc_opts)* opts,
+                          const(afg_norm_params)* wave_norm, const(afg_norm_params)* cmvn, float* d_out, afg_batch_result* out_);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

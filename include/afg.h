@@ -1407,6 +1407,101 @@ int afg_batch_decode_resampled_norm(const uint8_t *const *data, const size_t *le
 int afg_batch_decode_mel_norm(const uint8_t *const *data, const size_t *length, int n_files, const afg_mel_opts *opts,
                               const afg_norm_params *wave_norm, const afg_norm_params *feat_norm, float *d_out, afg_batch_result *out);
 
+/* ---- cepstral features behind the log-mel stage: a DCT-II over the mel axis, a lifter, and regression deltas -------------
+ * What speaker and keyword models and Kaldi-style recipes take: MFCC statics with their first and second time derivatives
+ * stacked behind them (torchaudio.transforms.MFCC and ComputeDeltas), in one kernel.  The reference has no such stage; the
+ * definition is this library's own, restated in numpy in tests/cepstra_model.py, and the device follows it bit for bit.
+ *
+ * Parameters of a call (afg_cep_params), uniform over its records: n_mels 1 .. 256 (rows of an input slab), n_ceps
+ * 1 .. n_mels, delta_order 0, 1 or 2 (planes behind the statics), delta_win N 1 .. 8 (ignored when delta_order is 0;
+ * torchaudio's win_length 5 is N = 2), reserved words 0.  Anything else is AFG_ERR_INVALID.
+ *
+ * A record (afg_cep_row) is one slab [n_mels, F] of d_in, frames contiguous, mel 0 frame 0 at float in_off, and its output
+ * [(1 + delta_order) * n_ceps, F] float32: plane p, coefficient q, frame t lies at out_off + (p * n_ceps + q) * F + t.  The
+ * planes are p = 0 statics, 1 delta, 2 delta-delta.  frames == 0: nothing is read, nothing written.
+ *
+ * Arithmetic.  Every operation is float32 and nothing wider; every sum starts from +0.0f and runs in ascending index
+ * order, one fmaf per term.  D is the caller's dense [n_ceps, n_mels] matrix (afg_cep_dct makes the usual ones).
+ *   c[q][t]  = chain over m = 0 .. n_mels - 1 of fmaf(D[q][m], x[m][t], acc)
+ *   d1[q][t] = (chain over n = 1 .. N of fmaf((float)n, c[q][min(t + n, F - 1)] - c[q][max(t - n, 0)], acc)) * g
+ * with the difference rounded to float32, the final product rounded to float32, and g = float32(1 / (2 * sum n^2)) computed
+ * in double.  d2 is the same expression over d1 taken at the clamped frame indices: the delta of the edge-replicated delta
+ * sequence, which is what ComputeDeltas(mode="replicate") applied twice computes.  (librosa.feature.delta fits a
+ * Savitzky-Golay polynomial and treats the edges differently: a different definition, not provided here.)
+ *
+ * Locality.  A record's outputs depend on that record's slab and the parameters only; the same slab gives the same bits
+ * wherever it stands.  A NaN at input frame t makes NaN of every static of frame t; of the deltas of exactly the frames t'
+ * whose clamped span reads it -- some min(t' + n, F - 1) or max(t' - n, 0), n = 1 .. N, is t: the frames within N of t, and t
+ * itself only where the clamp lands on it (t = 0, t = F - 1); of the delta-deltas of exactly the frames whose span reads one
+ * of those; and of nothing else.  No float outside a record's n_mels * F inputs is read, and exactly
+ * (1 + delta_order) * n_ceps * F floats are written.
+ *
+ * afg_cep_dct: host only.  Returns n_ceps * n_mels and with cap >= that fills out[q * n_mels + m] = D[q][m] (out may be NULL
+ * with cap 0):  D[q][m] = float32(log_scale * L[q] * s[q] * cos(pi * r / (2 * n_mels))),  r = (q * (2 m + 1)) mod (4 * n_mels)
+ * reduced in integers before the cosine, all of it in double and rounded once.  AFG_CEP_DCT_ORTHO: s[0] = sqrt(1 / n_mels),
+ * s[q] = sqrt(2 / n_mels) otherwise; AFG_CEP_DCT_NONE: s = 2 (scipy's and torchaudio's unnormalised type II).  lifter 0:
+ * L = 1; lifter > 0: L[q] = 1 + (lifter / 2) * sin(pi * q / lifter) with q counted from 0, the HTK / Kaldi convention
+ * (librosa counts q from 1).  log_scale is finite and not 0: 1 keeps the log10 units of the mel stage, 10 gives dB of power,
+ * ln 10 natural-log cepstra.  Returns 0 with afg_last_error set for n_mels, n_ceps or norm out of range, a lifter that is
+ * negative or not finite, or such a log_scale.
+ *
+ * afg_cep_layout, afg_cep_check_rows, afg_cepstra_hip: as afg_mel_layout, afg_mel_check_rows and afg_melspec_hip.  A tile is
+ * 64 consecutive frames of one record (AFG_CEP_TILE); a record's last tile may be short.  The layout fills first_tile and
+ * returns the launch's tile count (0 with afg_last_error set for params out of range).  The check function needs no device:
+ * params in range; dct_floats at least n_ceps * n_mels; first_tile and n_tiles as the layout gives them; reserved words 0;
+ * and for a record with frames > 0 its n_mels * F floats inside [0, in_floats) and its (1 + delta_order) * n_ceps * F floats
+ * inside [0, out_floats); n_rows == 0 checks the parameters alone.  The entry runs every record in one launch, one
+ * workgroup per tile: d_rows is the device copy of the laid-out records, which the entry fetches on hip_stream, waits for
+ * and checks in the same way; anything else than a pass is AFG_ERR_INVALID and nothing is written.  The planes are 4-byte
+ * aligned, offsets may be odd, and d_in and d_out do not overlap. */
+#define AFG_CEP_DCT_NONE  0
+#define AFG_CEP_DCT_ORTHO 1
+#define AFG_CEP_TILE      64
+typedef struct afg_cep_params {   /* 32 bytes */
+    uint32_t n_mels;       /* 1 .. 256: rows of an input slab */
+    uint32_t n_ceps;       /* 1 .. n_mels */
+    uint32_t delta_order;  /* 0, 1 or 2: planes behind the statics */
+    uint32_t delta_win;    /* N, 1 .. 8 (ignored when delta_order is 0); torchaudio's win_length 5 is N = 2 */
+    uint32_t reserved[4];  /* 0 */
+} afg_cep_params;
+typedef struct afg_cep_row {      /* 32 bytes */
+    uint64_t in_off;       /* float index in d_in of mel 0, frame 0; the slab is [n_mels, frames], frames contiguous */
+    uint64_t out_off;      /* float index in d_out of plane 0, coefficient 0, frame 0 */
+    uint64_t first_tile;   /* filled in by afg_cep_layout */
+    uint32_t frames;       /* F; 0: nothing read, nothing written */
+    uint32_t reserved;     /* 0 */
+} afg_cep_row;
+uint64_t afg_cep_dct(uint32_t n_ceps, uint32_t n_mels, uint32_t norm, double lifter, double log_scale, float *out, uint64_t cap);
+uint64_t afg_cep_layout(afg_cep_row *rows, uint64_t n_rows, const afg_cep_params *params);
+int afg_cep_check_rows(const afg_cep_row *rows, uint64_t n_rows, uint64_t n_tiles, const afg_cep_params *params, uint64_t in_floats,
+                       uint64_t dct_floats, uint64_t out_floats);
+int afg_cepstra_hip(uint64_t n_rows, const afg_cep_row *d_rows, uint64_t n_tiles, const afg_cep_params *params, const float *d_in,
+                    uint64_t in_floats, const float *d_dct, uint64_t dct_floats, float *d_out, uint64_t out_floats, void *hip_stream);
+
+/* afg_batch_decode_mel_norm(..., wave_norm, NULL, ...) followed by afg_cepstra_hip: d_out is n_files * channels *
+ * (1 + delta_order) * n_ceps * n_out floats on the current device, and slab [i, k] is the definition above applied to slab
+ * [i, k] of the log-mel tensor that call makes of the same list (either algorithm), with D = afg_cep_dct(cep.n_ceps,
+ * cep.n_mels, dct_norm, lifter, log_scale); log_scale 0 means 1.  The log-mel tensor is a pooled scratch; a list whose scratch
+ * would exceed afg_dev_option("mel_scratch_bytes") runs in sublists of at least one file, one afg_cepstra_hip launch each.
+ * The table is made once per parameter set and kept, like the bank.  cmvn (NULL: none): every one of the
+ * (1 + delta_order) * n_ceps rows of every slab is one afg_norm_group of a single row with valid = n_out, normalised in
+ * place -- with AFG_NORM_STANDARD, per-coefficient mean and variance normalisation over time; the other modes work too.
+ * A failed or refused file keeps its status and message, and its slab is what the definition gives for the all-floor mel
+ * slab.  items[i] is as in afg_batch_decode_mel, with pcm at the file's slab.
+ * Checked before any device call, AFG_ERR_INVALID with afg_last_error set: everything afg_batch_decode_mel_norm checks, a
+ * struct_size below sizeof(afg_mfcc_opts), mel.mel.out_kind other than AFG_MEL_LOG10, cep.n_mels other than mel.mel.n_mels,
+ * the cepstral parameters, dct_norm, lifter and log_scale out of range, cmvn parameters out of range.  n_files == 0 is AFG_OK
+ * and touches nothing. */
+typedef struct afg_mfcc_opts {
+    uint32_t       struct_size;   /* sizeof(afg_mfcc_opts) */
+    uint32_t       dct_norm;      /* AFG_CEP_DCT_* */
+    afg_mel_opts   mel;           /* as for afg_batch_decode_mel; mel.mel.out_kind must be AFG_MEL_LOG10 */
+    afg_cep_params cep;           /* cep.n_mels must equal mel.mel.n_mels */
+    double         lifter, log_scale;   /* log_scale 0 means 1 */
+} afg_mfcc_opts;
+int afg_batch_decode_mfcc(const uint8_t *const *data, const size_t *length, int n_files, const afg_mfcc_opts *opts,
+                          const afg_norm_params *wave_norm, const afg_norm_params *cmvn, float *d_out, afg_batch_result *out);
+
 #ifdef __cplusplus
 }
 #endif
