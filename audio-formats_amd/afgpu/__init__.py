@@ -80,6 +80,9 @@ NORM_TILE = 4096                                 # floats of one row per tile of
 CEP_DCT_NONE, CEP_DCT_ORTHO = 0, 1               # afg_cep_dct's norm, afg_mfcc_opts.dct_norm
 CEP_DCT_NAMES = {"none": CEP_DCT_NONE, "ortho": CEP_DCT_ORTHO}
 CEP_TILE = 64                                    # frames of one record per tile of afg_cepstra_hip
+TRIM_REF_MAX, TRIM_REF_ABS = 0, 1                # afg_trim_params.reference
+TRIM_REF_NAMES = {"max": TRIM_REF_MAX, "abs": TRIM_REF_ABS}
+TRIM_TILE = 4096                                 # floats of one output row per tile of afg_trim_hip
 
 # every symbol include/afg.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -119,6 +122,7 @@ ABI_SYMBOLS = [
     "afg_mel_fft_tables", "afg_mel_fft_layout", "afg_mel_fft_check_rows", "afg_melspec_fft_hip",
     "afg_norm_layout", "afg_norm_check_groups", "afg_normalize_hip", "afg_batch_decode_resampled_norm", "afg_batch_decode_mel_norm",
     "afg_cep_dct", "afg_cep_layout", "afg_cep_check_rows", "afg_cepstra_hip", "afg_batch_decode_mfcc",
+    "afg_trim_layout", "afg_trim_check_groups", "afg_trim_hip", "afg_batch_decode_trimmed",
 ]
 
 
@@ -320,6 +324,29 @@ CEP_ROW_DTYPE = np.dtype(CepRow)                 # arrays of the records, as the
 assert CEP_ROW_DTYPE.itemsize == 32 and C.sizeof(CepParams) == 32
 
 
+class TrimParams(C.Structure):
+    """afg_trim_params (afg_trim_hip)."""
+    _fields_ = [("frame_length", C.c_uint32), ("hop", C.c_uint32), ("reference", C.c_uint32), ("lead", C.c_uint32), ("trail", C.c_uint32),
+                ("reserved", C.c_uint32 * 3), ("ratio", C.c_double), ("abs_power", C.c_double)]
+
+
+class TrimGroup(C.Structure):
+    """afg_trim_group: the input rows one region is found over, and the output slab they are shifted into (afg_trim_hip)."""
+    _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("in_stride", C.c_uint64), ("out_stride", C.c_uint64),
+                ("first_block", C.c_uint64), ("first_tile", C.c_uint64), ("rows", C.c_uint32), ("valid", C.c_uint32),
+                ("out_rows", C.c_uint32), ("out_frames", C.c_uint32)]
+
+
+class TrimRegion(C.Structure):
+    """afg_trim_region: one group's record."""
+    _fields_ = [("begin", C.c_uint32), ("end", C.c_uint32), ("ref_power", C.c_double)]
+
+
+TRIM_GROUP_DTYPE = np.dtype(TrimGroup)           # arrays of the records, as the other stages' *_DTYPE
+TRIM_REGION_DTYPE = np.dtype(TrimRegion)
+assert TRIM_GROUP_DTYPE.itemsize == 64 and TRIM_REGION_DTYPE.itemsize == 16 and C.sizeof(TrimParams) == 48
+
+
 SAMPLE_F32, SAMPLE_F64, SAMPLE_PCM_S8, SAMPLE_PCM_S16, SAMPLE_PCM_S24 = range(5)     # afg_batch_opts.sample_type
 BATCH_OPTS_SIZE_V1 = BatchOpts.sample_type.offset        # the struct before sample_type was appended
 BATCH_OPTS_SIZE_V2 = BatchOpts.dither.offset             # ... up to sample_type, before dither and dither_seed were
@@ -367,7 +394,7 @@ _DEV_ENV = {"AFG_CELT_PATH": ("celt_path", {"stream": 1, "split": 2, "walk": 3})
             "AFG_VORBIS_HOST_FLOOR": ("vorbis_host_floor", None), "AFG_FLAC_HOST_RES32": ("flac_host_res32", None),
             "AFG_VORBIS_SEG_PACKETS": ("vorbis_seg_packets", None), "AFG_BATCH_GROUPS": ("batch_groups", None),
             "AFG_STAGE_CHUNK_SAMPLES": ("stage_chunk_samples", None), "AFG_RESAMPLE_SCRATCH_BYTES": ("resample_scratch_bytes", None),
-            "AFG_MEL_SCRATCH_BYTES": ("mel_scratch_bytes", None)}
+            "AFG_MEL_SCRATCH_BYTES": ("mel_scratch_bytes", None), "AFG_TRIM_SCRATCH_BYTES": ("trim_scratch_bytes", None)}
 _dev_seen = {}
 
 
@@ -582,6 +609,10 @@ def lib():
                                         C.POINTER(BatchResult)]
     L.afg_batch_decode_mel_norm.argtypes = [vp, vp, C.c_int, C.POINTER(MelOpts), C.POINTER(NormParams), C.POINTER(NormParams), vp,
                                             C.POINTER(BatchResult)]
+    L.afg_trim_layout.argtypes = [vp, u64, C.POINTER(TrimParams), C.POINTER(u64), C.POINTER(u64)]
+    L.afg_trim_check_groups.argtypes = [vp, u64, u64, u64, C.POINTER(TrimParams), u64, u64]
+    L.afg_trim_hip.argtypes = [u64, vp, u64, u64, C.POINTER(TrimParams), vp, u64, vp, u64, vp, vp, vp]
+    L.afg_batch_decode_trimmed.argtypes = [vp, vp, C.c_int, C.POINTER(ResampleOpts), C.POINTER(TrimParams), u32, vp, vp, C.POINTER(BatchResult)]
     _lib = L
     _sync_dev_options(L)
     return L
@@ -1918,6 +1949,81 @@ def batch_decode_mfcc(files, frames, n_mfcc=13, delta_order=0, delta_win=2, dct_
 
     return _batch_tensor_call("batch_decode_mfcc", files, (len(files), channels, (1 + delta_order) * n_mfcc, n_out if n_out else most), out,
                               first_frame, call)
+
+
+def trim_params(top_db=60.0, frame_length=2048, hop=512, reference="max", abs_power=1.0, lead=0, trail=0):
+    """afg_trim_params with librosa.effects.trim's defaults: a frame is silent when its power lies top_db decibels or more
+    below the reference -- ratio = 10 ** (-top_db / 10), computed here in double: the library never sees decibels.
+    reference: TRIM_REF_* or its name, "max" (the loudest frame) or "abs" (abs_power, a mean square per sample).  lead, trail:
+    samples kept in front of and behind the region.  ValueError for an unknown reference; the ranges are the library's to
+    check."""
+    if isinstance(reference, str):
+        if reference not in TRIM_REF_NAMES:
+            raise ValueError(f"trim_params: unknown reference {reference!r}: one of {sorted(TRIM_REF_NAMES)}")
+        reference = TRIM_REF_NAMES[reference]
+    return TrimParams(int(frame_length), int(hop), int(reference), int(lead), int(trail), (C.c_uint32 * 3)(0, 0, 0),
+                      10.0 ** (-float(top_db) / 10.0), float(abs_power))
+
+
+def trim_layout(groups, params):
+    """afg_trim_layout: fills first_block and first_tile of a TRIM_GROUP_DTYPE array in place; returns (n_blocks, n_tiles).
+    AfgError for parameters out of range."""
+    assert groups.dtype == TRIM_GROUP_DTYPE and groups.flags.c_contiguous
+    L = lib()
+    n_blocks, n_tiles = C.c_uint64(), C.c_uint64()
+    if not L.afg_trim_layout(groups.ctypes.data, len(groups), C.byref(params), C.byref(n_blocks), C.byref(n_tiles)):
+        raise AfgError(f"afg: {L.afg_last_error().decode()}")
+    return n_blocks.value, n_tiles.value
+
+
+def trim_check_groups(groups, n_blocks, n_tiles, params, in_floats, out_floats):
+    """afg_trim_check_groups: what afg_trim_hip checks before it launches, on host records.  AfgError when one fails."""
+    assert groups.dtype == TRIM_GROUP_DTYPE and groups.flags.c_contiguous
+    check(lib().afg_trim_check_groups(groups.ctypes.data, len(groups), int(n_blocks), int(n_tiles), C.byref(params), int(in_floats),
+                                      int(out_floats)))
+
+
+def trim(n_groups, d_groups, n_blocks, n_tiles, params, d_in, in_floats, d_out, out_floats, d_blocks, d_regions, stream=None):
+    """Enqueue the trim kernels (afg_trim_hip) on device arrays: every group's block powers into d_blocks (n_blocks doubles),
+    its region into d_regions (TRIM_REGION_DTYPE records), and its rows from `begin` on into its output slab, zeros behind
+    them.  The groups are checked first (the call waits for `stream` to read them): AfgError, and nothing written, when one
+    fails or the planes overlap."""
+    check(lib().afg_trim_hip(int(n_groups), _ptr(d_groups), int(n_blocks), int(n_tiles), C.byref(params), _ptr(d_in), int(in_floats),
+                             _ptr(d_out), int(out_floats), _ptr(d_blocks), _ptr(d_regions), _stream(stream)))
+
+
+def batch_decode_tensor_trimmed(files, frames, channels, samplerate, scan_frames=None, top_db=60.0, frame_length=2048, hop=512,
+                                reference="max", abs_power=1.0, lead=0, trail=0, trim=None, first_frame=None, mono=False, in_channels=0,
+                                max_in_rate=0, lowpass_width=0, out=None, n_threads=0):
+    """afg_batch_decode_trimmed: (tensor, meta) as batch_decode_tensor_resampled, with every file's slab starting at the
+    begin of its non-silent region: scan_frames (None: frames) frames at `samplerate` from first_frame on are decoded and
+    examined, and the first `frames` of [begin, end) are delivered, zeros behind them.  The trim parameters: trim_params'
+    keywords, or a TrimParams as `trim`.  meta[i] has "begin" and "end" added, in frames at `samplerate` from first_frame.
+    The same device and stream rules as batch_decode_tensor; ValueError for arguments out of range, before any call."""
+    prm = trim if isinstance(trim, TrimParams) else trim_params(top_db, frame_length, hop, reference, abs_power, lead, trail)
+    frames, channels, samplerate = int(frames), int(channels), int(samplerate)
+    if frames < 1 or channels < 1 or samplerate < 1:
+        raise ValueError("batch_decode_tensor_trimmed: frames, channels and samplerate must be at least 1")
+    if mono and channels != 1:
+        raise ValueError("batch_decode_tensor_trimmed: a mono tensor has one channel")
+    scan = frames if scan_frames is None else int(scan_frames)
+    if scan < frames or scan > 0xffffffff:
+        raise ValueError(f"batch_decode_tensor_trimmed: scan_frames {scan} must be at least frames ({frames}) and below 2^32")
+    L = lib()
+    if L.afg_trim_check_groups(None, 0, 0, 0, C.byref(prm), 0, 0) != 0:
+        raise ValueError(f"batch_decode_tensor_trimmed: {L.afg_last_error().decode()}")
+    n = len(files)
+    regions = np.zeros(max(n, 1), TRIM_REGION_DTYPE)
+
+    def call(ptrs, lens, n, ff, out, res):
+        opts = ResampleOpts(C.sizeof(ResampleOpts), int(n_threads), channels, frames, ff, samplerate, 1 if mono else 0, int(in_channels),
+                            int(max_in_rate), int(lowpass_width))
+        return L.afg_batch_decode_trimmed(ptrs, lens, n, C.byref(opts), C.byref(prm), scan, out.data_ptr(), regions.ctypes.data, C.byref(res))
+
+    out, meta = _batch_tensor_call("batch_decode_tensor_trimmed", files, (n, channels, frames), out, first_frame, call)
+    for i, m in enumerate(meta):
+        m["begin"], m["end"] = int(regions[i]["begin"]), int(regions[i]["end"])
+    return out, meta
 
 
 def batch_transcode(files, options=None, n_threads=0, devices=None):

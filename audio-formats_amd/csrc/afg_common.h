@@ -28,7 +28,7 @@ int numeric_mode();
 // Alternative code paths the test-suite runs side by side with the default ones (afg.h: afg_dev_option).  Set through
 // that call only -- the library reads no environment variable for them -- and -1 while unset.
 enum DevOption { kDevCeltPath, kDevCeltDeSeq, kDevCeltDeDuo, kDevCeltSegRecs, kDevCeltWholeFrames, kDevVorbisSingle,
-                 kDevMp3Chunks, kDevMp3FloatUpload, kDevVorbisHostFloor, kDevFlacHostRes32, kDevVorbisSegPackets, kDevBatchGroups, kDevStageChunkSamples, kDevResampleScratchBytes, kDevMelScratchBytes, kDevCount };
+                 kDevMp3Chunks, kDevMp3FloatUpload, kDevVorbisHostFloor, kDevFlacHostRes32, kDevVorbisSegPackets, kDevBatchGroups, kDevStageChunkSamples, kDevResampleScratchBytes, kDevMelScratchBytes, kDevTrimScratchBytes, kDevCount };
 long dev_option(DevOption which);
 
 #define AFG_HIP_CHECK(expr)                                                              \
@@ -93,6 +93,11 @@ int normalize_launch(const afg_norm_group *h_groups, uint64_t n_groups, const af
 int cepstra_launch(const afg_cep_row *h_rows, uint64_t n_rows, const afg_cep_row *d_rows, uint64_t n_tiles, const afg_cep_params *params,
                    const float *d_in, uint64_t in_floats, const float *d_dct, uint64_t dct_floats, float *d_out, uint64_t out_floats,
                    hipStream_t stream);
+
+// afg_trim_hip likewise (trim.hip)
+int trim_launch(const afg_trim_group *h_groups, uint64_t n_groups, const afg_trim_group *d_groups, uint64_t n_blocks, uint64_t n_tiles,
+                const afg_trim_params *params, const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats, double *d_blocks,
+                afg_trim_region *d_regions, hipStream_t stream);
 
 // Owns a device buffer filled from a host array at plan creation.
 struct DeviceArray {

@@ -515,6 +515,21 @@ int afg_cepstra_hip(ulong n_rows, const(afg_cep_row)* d_rows, ulong n_tiles, con
                     ulong in_floats, const(float)* d_dct, ulong dct_floats, float* d_out, ulong out_floats, void* hip_stream);
 int afg_batch_decode_mfcc(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_mfcc_opts)* opts,
                           const(afg_norm_params)* wave_norm, const(afg_norm_params)* cmvn, float* d_out, afg_batch_result* out_);
+// trimming silence: the non-silent region of a group of rows, and the rows shifted to start there (include/afg.h has the
+// definition)
+enum : uint { AFG_TRIM_REF_MAX = 0, AFG_TRIM_REF_ABS = 1 }
+struct afg_trim_params { uint frame_length, hop, reference, lead, trail; uint[3] reserved; double ratio, abs_power; }
+struct afg_trim_group { ulong in_off, out_off, in_stride, out_stride, first_block, first_tile; uint rows, valid, out_rows, out_frames; }
+struct afg_trim_region { uint begin, end; double ref_power; }
+int afg_trim_layout(afg_trim_group* groups, ulong n_groups, const(afg_trim_params)* params, ulong* n_blocks, ulong* n_tiles);
+int afg_trim_check_groups(const(afg_trim_group)* groups, ulong n_groups, ulong n_blocks, ulong n_tiles,
+                          const(afg_trim_params)* params, ulong in_floats, ulong out_floats);
+int afg_trim_hip(ulong n_groups, const(afg_trim_group)* d_groups, ulong n_blocks, ulong n_tiles, const(afg_trim_params)* params,
+                 const(float)* d_in, ulong in_floats, float* d_out, ulong out_floats, double* d_blocks, afg_trim_region* d_regions,
+                 void* hip_stream);
+int afg_batch_decode_trimmed(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_resample_opts)* opts,
+                             const(afg_trim_params)* trim, uint scan_frames, float* d_out, afg_trim_region* regions,
+                             afg_batch_result* out_);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

@@ -1502,6 +1502,93 @@ typedef struct afg_mfcc_opts {
 int afg_batch_decode_mfcc(const uint8_t *const *data, const size_t *length, int n_files, const afg_mfcc_opts *opts,
                           const afg_norm_params *wave_norm, const afg_norm_params *cmvn, float *d_out, afg_batch_result *out);
 
+/* ---- trimming silence: the non-silent region of a group of rows, and the rows shifted to start there ----------------------
+ * What librosa.effects.trim and the non-silent region operators of loaders do, behind the collate on planar rows, so that a
+ * clip of a fixed length starts where the sound starts.  The reference has no such stage; the definition is this library's
+ * own, restated in numpy in tests/trim_model.py, and the device follows it bit for bit.
+ *
+ * Parameters (afg_trim_params), uniform over a call: hop >= 1, frame_length a multiple of hop and at most 65536,
+ * k = frame_length / hop 1 or an even number up to 64; reference AFG_TRIM_REF_MAX or AFG_TRIM_REF_ABS; ratio finite and above
+ * 0, at most 1 with AFG_TRIM_REF_MAX (a power ratio: 10 ^ (-top_db / 10) -- the library never sees decibels); abs_power finite
+ * and above 0 with AFG_TRIM_REF_ABS, ignored otherwise; lead and trail: samples kept in front of and behind the region;
+ * reserved words 0.  Anything else is AFG_ERR_INVALID.
+ *
+ * Groups.  A group (afg_trim_group) is `rows` input rows (1 .. 65535) of `valid` floats, row r at float in_off + r * in_stride
+ * of d_in -- one file's channel rows -- and out_rows >= rows output rows of out_frames floats, row r at out_off + r * out_stride
+ * of d_out.
+ *
+ * Blocks.  Block j of a group is samples [j * hop, min((j + 1) * hop, valid)) of every row; n_blocks = ceil(valid / hop).  Its
+ * power S_j is a float64 in a fixed order: in row r, sample i of the block (counted from the block's start) belongs to lane
+ * i % 64 of 64 lanes; a lane starts from +0.0 and over its samples in ascending i does q = q + (double)x * (double)x (the
+ * product is exact); the lanes combine in the tree of the normalisation stage -- step d = 1, 2 .. 32, lane l with
+ * l % (2 d) == 0 takes v[l] + v[l + d]; the rows' results are added in ascending r, starting from +0.0.
+ *
+ * Frames.  There are n_blocks analysis frames; frame f covers blocks [f - k / 2, f + k / 2) cut to [0, n_blocks) -- the frame of
+ * frame_length samples centred on sample f * hop -- and for k == 1 block f alone.  P_f is the sum of the frame's S_j in
+ * ascending j from +0.0.  P_ref = max over f of P_f, taken as P > m ? P : m from +0.0: a NaN never wins.  The threshold is
+ * ratio * P_ref with AFG_TRIM_REF_MAX and ratio * abs_power * (double)(rows * frame_length) -- two products in that order --
+ * with AFG_TRIM_REF_ABS (abs_power is a mean square per sample).  A frame is non-silent when P_f > threshold; a NaN is silent.
+ *
+ * Region (afg_trim_region).  No non-silent frame: begin = end = 0.  Otherwise, with f_first and f_last the first and last
+ * non-silent frame, b = f_first * hop, e = min(valid, (f_last + 1) * hop) -- librosa.effects.trim's index arithmetic -- and
+ * begin = b > lead ? b - lead : 0, end = min(valid, e + trail).  ref_power is P_ref in both modes.
+ *
+ * Output.  For r < rows and t < min(out_frames, end - begin), out[r][t] has the bits of in[r][begin + t]; every other element
+ * of the out_rows x out_frames slab is +0.0f.  Every element of the slab is written; no float outside [0, valid) of the input
+ * rows is read; the output may not overlap the input.  valid == 0: a zero slab and a zero record.
+ *
+ * afg_trim_layout fills first_block (blocks are numbered through the groups in order) and first_tile (a tile is 4096
+ * consecutive floats of one output row, rows ascending, then tiles ascending inside a row) and stores the two counts; it
+ * returns 1, or 0 with afg_last_error set for parameters out of range or a NULL pointer.  afg_trim_check_groups needs no
+ * device: the parameters in range; rows 1 .. 65535 and out_rows >= rows; with more than one row a stride at least the row
+ * (in_stride >= valid, out_stride >= out_frames); the rows inside [0, in_floats) and [0, out_floats), offsets that would wrap
+ * included; first_block, first_tile and the counts as the layout gives them.  n_groups == 0 checks the parameters alone.
+ * afg_trim_hip runs three launches on hip_stream -- the blocks' powers into d_blocks (n_blocks doubles), the regions into
+ * d_regions (n_groups records), the shifted copy -- without atomics and without a host round trip between them.  d_groups is
+ * the device copy of the laid-out groups; the entry fetches it on hip_stream, waits for it and checks it in the same way,
+ * and refuses planes that overlap (from the pointers and the float counts): anything else than a pass is AFG_ERR_INVALID
+ * and nothing is written.  The planes are 4-byte aligned, d_blocks, d_regions and d_groups 8-byte aligned. */
+#define AFG_TRIM_REF_MAX 0
+#define AFG_TRIM_REF_ABS 1
+typedef struct afg_trim_params {  /* 48 bytes */
+    uint32_t frame_length, hop;   /* samples; frame_length = k * hop */
+    uint32_t reference;           /* AFG_TRIM_REF_* */
+    uint32_t lead, trail;         /* samples kept in front of / behind the non-silent region */
+    uint32_t reserved[3];         /* 0 */
+    double   ratio;               /* threshold over the reference, as a power ratio */
+    double   abs_power;           /* AFG_TRIM_REF_ABS: the reference, a mean square per sample */
+} afg_trim_params;
+typedef struct afg_trim_group {   /* 64 bytes */
+    uint64_t in_off, out_off;     /* float index of row 0, element 0 in d_in / d_out */
+    uint64_t in_stride, out_stride;   /* floats from one row to the next */
+    uint64_t first_block, first_tile; /* filled in by afg_trim_layout */
+    uint32_t rows, valid;         /* input rows and their length */
+    uint32_t out_rows, out_frames;    /* the output slab; out_rows >= rows */
+} afg_trim_group;
+typedef struct afg_trim_region {  /* 16 bytes, one per group */
+    uint32_t begin, end;          /* out[r][t] = in[r][begin + t] for t < min(out_frames, end - begin) */
+    double   ref_power;           /* P_ref */
+} afg_trim_region;
+int afg_trim_layout(afg_trim_group *groups, uint64_t n_groups, const afg_trim_params *params, uint64_t *n_blocks, uint64_t *n_tiles);
+int afg_trim_check_groups(const afg_trim_group *groups, uint64_t n_groups, uint64_t n_blocks, uint64_t n_tiles,
+                          const afg_trim_params *params, uint64_t in_floats, uint64_t out_floats);
+int afg_trim_hip(uint64_t n_groups, const afg_trim_group *d_groups, uint64_t n_blocks, uint64_t n_tiles, const afg_trim_params *params,
+                 const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats, double *d_blocks, afg_trim_region *d_regions,
+                 void *hip_stream);
+
+/* afg_batch_decode_resampled with frames = scan_frames into a pooled scratch [files, channels, scan_frames], then one group
+ * per file as afg_batch_decode_resampled_norm makes them -- rows = min(channels, the file's channels), or 1 with mono; valid
+ * as defined there with T = scan_frames, 0 for a failed or refused file; out_rows = channels -- trimmed into d_out, which is
+ * n_files * channels * opts->frames floats on the current device.  scan_frames >= opts->frames says how many frames at the
+ * target rate are decoded and examined, counted from first_frame; 0 means opts->frames.  A list whose scratch would exceed
+ * afg_dev_option("trim_scratch_bytes") (default 2 GiB) runs in sublists of at least one file, one afg_trim_hip launch each.
+ * regions (host, n_files records) may be NULL; it is filled when the call's last launch has drained.  Checked before any
+ * device call, AFG_ERR_INVALID with afg_last_error set: everything afg_batch_decode_resampled checks, NULL opts, trim, d_out or
+ * out, scan_frames below opts->frames, the trim parameters.  Statuses, messages and items[i] are afg_batch_decode_resampled's. */
+int afg_batch_decode_trimmed(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
+                             const afg_trim_params *trim, uint32_t scan_frames, float *d_out, afg_trim_region *regions,
+                             afg_batch_result *out);
+
 #ifdef __cplusplus
 }
 #endif
