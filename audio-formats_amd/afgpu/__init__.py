@@ -83,6 +83,7 @@ CEP_TILE = 64                                    # frames of one record per tile
 TRIM_REF_MAX, TRIM_REF_ABS = 0, 1                # afg_trim_params.reference
 TRIM_REF_NAMES = {"max": TRIM_REF_MAX, "abs": TRIM_REF_ABS}
 TRIM_TILE = 4096                                 # floats of one output row per tile of afg_trim_hip
+STFT_COMPLEX, STFT_MAGNITUDE, STFT_POWER, STFT_LOG10 = 0, 1, 2, 3       # afg_stft_params.out_kind
 
 # every symbol include/afg.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -123,6 +124,7 @@ ABI_SYMBOLS = [
     "afg_norm_layout", "afg_norm_check_groups", "afg_normalize_hip", "afg_batch_decode_resampled_norm", "afg_batch_decode_mel_norm",
     "afg_cep_dct", "afg_cep_layout", "afg_cep_check_rows", "afg_cepstra_hip", "afg_batch_decode_mfcc",
     "afg_trim_layout", "afg_trim_check_groups", "afg_trim_hip", "afg_batch_decode_trimmed",
+    "afg_stft_tile_frames", "afg_stft_layout", "afg_stft_check_rows", "afg_stft_hip", "afg_batch_decode_stft",
 ]
 
 
@@ -277,6 +279,17 @@ class MelOpts(C.Structure):
 
 
 del MelOpts._fields_[-2:]                                    # (the layout is made; the list is what positional arguments map to)
+
+
+class StftParams(C.Structure):
+    """afg_stft_params (afg_stft_hip)."""
+    _fields_ = [("n_fft", C.c_uint32), ("win_length", C.c_uint32), ("hop", C.c_uint32), ("center", C.c_uint32), ("pad_mode", C.c_uint32),
+                ("out_kind", C.c_uint32), ("log_floor", C.c_float), ("reserved", C.c_uint32)]
+
+
+class StftOpts(C.Structure):
+    """afg_stft_opts (afg_batch_decode_stft): afg_resample_opts' fields, n_out, the parameters and a reserved 0."""
+    _fields_ = ResampleOpts._fields_ + [("n_out", C.c_uint32), ("stft", StftParams), ("reserved", C.c_uint32)]
 
 
 class NormGroup(C.Structure):
@@ -613,6 +626,13 @@ def lib():
     L.afg_trim_check_groups.argtypes = [vp, u64, u64, u64, C.POINTER(TrimParams), u64, u64]
     L.afg_trim_hip.argtypes = [u64, vp, u64, u64, C.POINTER(TrimParams), vp, u64, vp, u64, vp, vp, vp]
     L.afg_batch_decode_trimmed.argtypes = [vp, vp, C.c_int, C.POINTER(ResampleOpts), C.POINTER(TrimParams), u32, vp, vp, C.POINTER(BatchResult)]
+    L.afg_stft_tile_frames.argtypes = [C.POINTER(StftParams)]
+    L.afg_stft_tile_frames.restype = u32
+    L.afg_stft_layout.argtypes = [vp, u64, C.POINTER(StftParams)]
+    L.afg_stft_layout.restype = u64
+    L.afg_stft_check_rows.argtypes = [vp, u64, u64, C.POINTER(StftParams), u64, u64, u64]
+    L.afg_stft_hip.argtypes = [u64, vp, u64, C.POINTER(StftParams), vp, u64, vp, u64, vp, u64, vp]
+    L.afg_batch_decode_stft.argtypes = [vp, vp, C.c_int, C.POINTER(StftOpts), vp, C.POINTER(BatchResult)]
     _lib = L
     _sync_dev_options(L)
     return L
@@ -2056,6 +2076,79 @@ def batch_transcode(files, options=None, n_threads=0, devices=None):
 def copy_probe(d_dst, d_src, nbytes, stream=None):
     """Enqueue the streaming copy used to measure the practical HBM copy ceiling (afg_copy_probe_hip)."""
     check(lib().afg_copy_probe_hip(_ptr(d_dst), _ptr(d_src), int(nbytes), _stream(stream)))
+
+
+def stft_params(n_fft=400, hop=160, win_length=None, center=True, pad_mode=MEL_PAD_REFLECT, out_kind=STFT_POWER, log_floor=0.0):
+    """afg_stft_params with Whisper's framing as the default (win_length None: n_fft)."""
+    return StftParams(int(n_fft), int(n_fft if win_length is None else win_length), int(hop), 1 if center else 0, int(pad_mode),
+                      int(out_kind), float(log_floor), 0)
+
+
+def stft_tile_frames(params):
+    """afg_stft_tile_frames: the frames of one row a workgroup of afg_stft_hip takes for these parameters (it depends on n_fft
+    and out_kind).  AfgError for parameters out of range."""
+    tile = int(lib().afg_stft_tile_frames(C.byref(params)))
+    if tile == 0:
+        raise AfgError(lib().afg_last_error().decode())
+    return tile
+
+
+def stft_layout(rows, params):
+    """afg_stft_layout: fills first_tile of a MEL_ROW_DTYPE array in place for afg_stft_hip (tiles of stft_tile_frames);
+    returns the launch's tile count."""
+    assert rows.dtype == MEL_ROW_DTYPE and rows.flags.c_contiguous
+    return int(lib().afg_stft_layout(rows.ctypes.data, len(rows), C.byref(params)))
+
+
+def stft_check_rows(rows, n_tiles, params, in_floats, table_floats, out_floats):
+    """afg_stft_check_rows: what afg_stft_hip checks before it launches, on host records.  AfgError when one fails."""
+    assert rows.dtype == MEL_ROW_DTYPE and rows.flags.c_contiguous
+    check(lib().afg_stft_check_rows(rows.ctypes.data, len(rows), int(n_tiles), C.byref(params), int(in_floats), int(table_floats),
+                                    int(out_floats)))
+
+
+def stft(n_rows, d_rows, n_tiles, params, d_in, in_floats, d_table, table_floats, d_out, out_floats, stream=None):
+    """Enqueue the linear spectrogram kernel (afg_stft_hip) on device arrays: planar float rows to [rows, n_bins, out_frames]
+    (pairs of re, im with STFT_COMPLEX), with mel_fft_tables' table and rows laid out by stft_layout.  The records are checked
+    first (the call waits for `stream` to read them): AfgError, and nothing written, when a check fails."""
+    check(lib().afg_stft_hip(int(n_rows), _ptr(d_rows), int(n_tiles), C.byref(params), _ptr(d_in), int(in_floats), _ptr(d_table),
+                             int(table_floats), _ptr(d_out), int(out_floats), _stream(stream)))
+
+
+def batch_decode_stft(files, frames, samplerate=16000, n_fft=400, hop=160, win_length=None, center=True, pad_mode=MEL_PAD_REFLECT,
+                      out_kind=STFT_POWER, log_floor=0.0, n_out=0, mono=True, out=None, channels=1, first_frame=None, in_channels=0,
+                      max_in_rate=0, lowpass_width=0, n_threads=0):
+    """afg_batch_decode_stft: (tensor, meta) as batch_decode_mel, with the tensor [len(files), channels, n_fft // 2 + 1, n_out]
+    the linear-frequency spectrogram of every row of batch_decode_tensor_resampled's tensor of `frames` samples at
+    `samplerate` (include/afg.h has the definition): float32 for STFT_MAGNITUDE, STFT_POWER and STFT_LOG10, complex64 for
+    STFT_COMPLEX -- torch.stft's layout (`out`, when given, is the float32 tensor with a last dimension of 2 that
+    torch.view_as_real makes of it).  n_out 0: every frame `frames` samples have.  n_fft: prime factors 2, 3 and 5 only.
+    The same device and stream rules as batch_decode_tensor."""
+    import torch
+    frames, channels, samplerate = int(frames), int(channels), int(samplerate)
+    if frames < 1 or channels < 1 or samplerate < 1:
+        raise ValueError("batch_decode_stft: frames, channels and samplerate must be at least 1")
+    if mono and channels != 1:
+        raise ValueError("batch_decode_stft: a mono tensor has one channel")
+    prm = stft_params(n_fft, hop, win_length, center, pad_mode, out_kind, log_floor)
+    stft_tile_frames(prm)                                    # (the parameters: AfgError says which)
+    most = mel_frames(MelParams(prm.n_fft, prm.win_length, prm.hop, 1, prm.center, prm.pad_mode, MEL_POWER, 0.0), frames)
+    if most == 0:
+        raise ValueError(f"batch_decode_stft: {frames} samples hold no frame of n_fft {prm.n_fft}")
+    n_out = int(n_out)
+    if n_out < 0 or n_out > most:
+        raise ValueError(f"batch_decode_stft: n_out {n_out}, but {frames} samples have {most} frames")
+    shape = (len(files), channels, prm.n_fft // 2 + 1, n_out if n_out else most)
+    if prm.out_kind == STFT_COMPLEX:
+        shape += (2,)
+
+    def call(ptrs, lens, n, ff, out, res):
+        opts = StftOpts(C.sizeof(StftOpts), int(n_threads), channels, frames, ff, samplerate, 1 if mono else 0, int(in_channels),
+                        int(max_in_rate), int(lowpass_width), n_out, prm, 0)
+        return lib().afg_batch_decode_stft(ptrs, lens, n, C.byref(opts), out.data_ptr(), C.byref(res))
+
+    out, meta = _batch_tensor_call("batch_decode_stft", files, shape, out, first_frame, call)
+    return (torch.view_as_complex(out) if prm.out_kind == STFT_COMPLEX else out), meta
 
 
 def lds_fill(word=0x7fc00000, stream=None):

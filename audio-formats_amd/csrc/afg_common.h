@@ -84,6 +84,12 @@ int melspec_fft_launch(const afg_mel_row *h_rows, uint64_t n_rows, const afg_mel
                        uint64_t filters_floats, float *d_out, uint64_t out_floats, hipStream_t stream);
 bool mel_fft_n_ok(uint32_t n_fft);
 
+// afg_stft_hip likewise (stft.hip), and max_frames of a row for its parameters (afg_mel_frames' formula)
+uint32_t stft_frames(const afg_stft_params &p, uint32_t in_frames);
+int stft_launch(const afg_mel_row *h_rows, uint64_t n_rows, const afg_mel_row *d_rows, uint64_t n_tiles, const afg_stft_params *params,
+                const float *d_in, uint64_t in_floats, const float *d_table, uint64_t table_floats, float *d_out, uint64_t out_floats,
+                hipStream_t stream);
+
 // afg_normalize_hip likewise (normalize.hip)
 int normalize_launch(const afg_norm_group *h_groups, uint64_t n_groups, const afg_norm_group *d_groups, uint64_t n_tiles,
                      const afg_norm_params *params, const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats,

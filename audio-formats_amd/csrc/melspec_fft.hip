@@ -26,6 +26,7 @@
 // in[in_off + g] for 0 <= g < in_frames only, table[0 .. win_length + 2 * n_fft) and filters[0 .. n_mels * n_bins) only, and
 // writes out[out_off .. out_off + n_mels * out_frames) only.
 #include "afg_common.h"
+#include "fft_frame.h"
 
 #include <vector>
 
@@ -36,113 +37,19 @@ constexpr uint32_t kTile = 16;                                  // frames per ti
 constexpr uint32_t kPPitch = 17;
 constexpr uint32_t kMelTiles = 4;                               // mel tiles of 16 per wavefront: 256 mels
 constexpr uint32_t kLdsBudget = 152 * 1024;
-constexpr uint32_t kMaxPasses = 12;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct FftGeo {
-    uint32_t nc;                                                // length of the complex transform: n_fft / 2 (even) or n_fft
-    uint32_t half;                                              // 1: n_fft even, the split pass follows
-    uint32_t n_pass;
-    uint32_t waves;                                             // wavefronts that transform (4, or fewer while LDS is short)
-    uint32_t wbuf;                                              // floats of one wavefront's two buffers: 4 * nc
-    uint32_t lds_floats;
-    uint8_t radix[kMaxPasses];
-};
-
-bool n_fft_ok(uint32_t n)
-{
-    if (n < 16 || n > 2048) return false;
-    for (uint32_t q : { 2u, 3u, 5u })
-        while (n % q == 0) n /= q;
-    return n == 1;
-}
 
 // (params already checked: check_params)
 FftGeo geo_of(const afg_mel_params &p)
 {
-    FftGeo g;
-    std::memset(&g, 0, sizeof(g));
-    g.half = (p.n_fft & 1) ? 0 : 1;
-    g.nc = g.half ? p.n_fft / 2 : p.n_fft;
-    uint32_t m = g.nc;
-    for (uint32_t q : { 4u, 2u, 3u, 5u })
-        while (m % q == 0 && g.n_pass < kMaxPasses) { g.radix[g.n_pass++] = (uint8_t)q; m /= q; }
-    g.wbuf = 4 * g.nc;
+    FftGeo g = fft_geo_of(p.n_fft);
     const uint32_t p_floats = (p.n_fft / 2 + 1) * kPPitch;
     for (g.waves = 4;; g.waves >>= 1) {
         g.lds_floats = g.waves * g.wbuf + p_floats;
         if (g.waves == 1 || g.lds_floats * 4 <= kLdsBudget) break;
     }
     return g;
-}
-
-struct cf { float re, im; };
-__device__ inline cf operator+(cf a, cf b) { return { a.re + b.re, a.im + b.im }; }
-__device__ inline cf operator-(cf a, cf b) { return { a.re - b.re, a.im - b.im }; }
-__device__ inline cf cmul(cf a, cf b) { return { a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re }; }
-__device__ inline cf scale(cf a, float s) { return { a.re * s, a.im * s }; }
-__device__ inline cf mul_mi(cf a) { return { a.im, -a.re }; }   // a * -i
-
-// the DFT of R values, forward (e^{-2 pi i / R})
-template <int R> __device__ inline void butterfly(cf *v);
-template <> __device__ inline void butterfly<2>(cf *v)
-{
-    const cf a = v[0] + v[1], b = v[0] - v[1];
-    v[0] = a; v[1] = b;
-}
-template <> __device__ inline void butterfly<4>(cf *v)
-{
-    const cf t0 = v[0] + v[2], t1 = v[0] - v[2], t2 = v[1] + v[3], t3 = mul_mi(v[1] - v[3]);
-    v[0] = t0 + t2; v[1] = t1 + t3; v[2] = t0 - t2; v[3] = t1 - t3;
-}
-template <> __device__ inline void butterfly<3>(cf *v)
-{
-    const cf t = v[1] + v[2], m = v[0] - scale(t, 0.5f), s = mul_mi(scale(v[1] - v[2], 0.86602540378443864676f));
-    v[0] = v[0] + t; v[1] = m + s; v[2] = m - s;
-}
-template <> __device__ inline void butterfly<5>(cf *v)
-{
-    constexpr float c1 = 0.30901699437494742410f, c2 = -0.80901699437494742410f, s1 = 0.95105651629515357212f, s2 = 0.58778525229247312917f;
-    const cf t1 = v[1] + v[4], t2 = v[2] + v[3], t3 = v[1] - v[4], t4 = v[2] - v[3];
-    const cf a1 = v[0] + (scale(t1, c1) + scale(t2, c2)), a2 = v[0] + (scale(t1, c2) + scale(t2, c1));
-    const cf b1 = mul_mi(scale(t3, s1) + scale(t4, s2)), b2 = mul_mi(scale(t3, s2) - scale(t4, s1));
-    v[0] = v[0] + (t1 + t2); v[1] = a1 + b1; v[2] = a2 + b2; v[3] = a2 - b2; v[4] = a1 - b1;
-}
-
-// One Stockham pass of radix R over nc values: butterfly j takes src[j + r * nc / R], turned by e^{-2 pi i r k / (ns R)} with
-// k = j mod ns, and leaves dst[(j - k) R + k + r ns].  tw is the table of n_fft pairs; ns R divides nc, which divides n_fft.
-template <int R>
-__device__ inline void fft_pass(const float *__restrict__ sr, const float *__restrict__ si, float *__restrict__ dr, float *__restrict__ di,
-                                uint32_t nc, uint32_t ns, uint32_t n_fft, const float *__restrict__ tw, uint32_t lane)
-{
-    const uint32_t m = nc / R, tstep = n_fft / (ns * R);
-    const bool pow2 = (ns & (ns - 1)) == 0;
-    for (uint32_t j = lane; j < m; j += 64) {
-        const uint32_t k = pow2 ? (j & (ns - 1)) : j % ns;
-        cf v[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) v[r] = { sr[j + r * m], si[j + r * m] };
-        if (ns > 1) {
-#pragma unroll
-            for (int r = 1; r < R; r++) {
-                const uint32_t t = 2 * (r * k * tstep);         // r k < R ns: inside the table
-                v[r] = cmul(v[r], cf{ tw[t], tw[t + 1] });
-            }
-        }
-        butterfly<R>(v);
-        const uint32_t j0 = (j - k) * R + k;
-#pragma unroll
-        for (int r = 0; r < R; r++) { dr[j0 + r * ns] = v[r].re; di[j0 + r * ns] = v[r].im; }
-    }
-}
-
-// a wavefront's LDS traffic in program order: what one pass wrote, the next reads in other lanes
-__device__ inline void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 __global__ __launch_bounds__(kThreads) void melspec_fft_kernel(uint32_t n_rows, const afg_mel_row *__restrict__ rows, afg_mel_params prm, FftGeo geo,
@@ -177,7 +84,6 @@ __global__ __launch_bounds__(kThreads) void melspec_fft_kernel(uint32_t n_rows, 
                 for (uint32_t k = lane; k < n_bins; k += 64) P[k * kPPitch + f] = 0.0f;
                 continue;
             }
-            float *sr = buf, *si = buf + nc, *dr = buf + 2 * nc, *di = buf + 3 * nc;
             const int64_t s0 = (int64_t)(t0 + f) * prm.hop - (int64_t)(prm.center ? n_fft / 2 : 0);
             // sample i of the frame times its window value; +0.0f outside the window
             auto fetch = [&](uint32_t i) -> float {
@@ -190,41 +96,12 @@ __global__ __launch_bounds__(kThreads) void melspec_fft_kernel(uint32_t n_rows, 
                 const float v = (s >= 0 && s < nin) ? x[s] : 0.0f;
                 return v * table[i - n_lo];
             };
-            wave_sync();                                         // the frame before has read its result
-            if (geo.half)
-                for (uint32_t j = lane; j < nc; j += 64) { sr[j] = fetch(2 * j); si[j] = fetch(2 * j + 1); }
-            else
-                for (uint32_t j = lane; j < nc; j += 64) { sr[j] = fetch(j); si[j] = 0.0f; }
-            wave_sync();
-            uint32_t ns = 1;
-            for (uint32_t p = 0; p < geo.n_pass; p++) {
-                const uint32_t R = geo.radix[p];
-                switch (R) {
-                case 4: fft_pass<4>(sr, si, dr, di, nc, ns, n_fft, tw, lane); break;
-                case 2: fft_pass<2>(sr, si, dr, di, nc, ns, n_fft, tw, lane); break;
-                case 3: fft_pass<3>(sr, si, dr, di, nc, ns, n_fft, tw, lane); break;
-                default: fft_pass<5>(sr, si, dr, di, nc, ns, n_fft, tw, lane); break;
-                }
-                ns *= R;
-                float *t = sr; sr = dr; dr = t;
-                t = si; si = di; di = t;
-                wave_sync();
-            }
+            const float *sr, *si;
+            fft_frame(geo, n_fft, buf, tw, lane, fetch, &sr, &si);
             // ---- p of bins 0 .. n_fft / 2
-            if (geo.half) {
-                // X[k] = E + W^k O with E = (Z[k] + conj Z[nc - k]) / 2, O = -i (Z[k] - conj Z[nc - k]) / 2, W = e^{-2 pi i / n_fft}
-                for (uint32_t k = lane; k <= nc; k += 64) {
-                    const uint32_t k1 = k == nc ? 0 : k, k2 = k == 0 ? 0 : nc - k;
-                    const float a = sr[k1], b = si[k1], c = sr[k2], d = si[k2];
-                    const cf E = { 0.5f * (a + c), 0.5f * (b - d) }, O = { 0.5f * (b + d), -0.5f * (a - c) };
-                    const cf X = E + cmul(cf{ tw[2 * k], tw[2 * k + 1] }, O);
-                    P[k * kPPitch + f] = X.re * X.re + X.im * X.im;
-                }
-            } else {
-                for (uint32_t k = lane; k < n_bins; k += 64) {
-                    const float a = sr[k], b = si[k];
-                    P[k * kPPitch + f] = a * a + b * b;
-                }
+            for (uint32_t k = lane; k < n_bins; k += 64) {
+                const cf X = geo.half ? fft_split_bin(sr, si, nc, k, tw) : cf{ sr[k], si[k] };
+                P[k * kPPitch + f] = X.re * X.re + X.im * X.im;
             }
         }
     }

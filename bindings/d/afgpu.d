@@ -530,6 +530,19 @@ int afg_trim_hip(ulong n_groups, const(afg_trim_group)* d_groups, ulong n_blocks
 int afg_batch_decode_trimmed(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_resample_opts)* opts,
                              const(afg_trim_params)* trim, uint scan_frames, float* d_out, afg_trim_region* regions,
                              afg_batch_result* out_);
+// the linear-frequency spectrogram: the FFT mel path's transform delivered as complex, magnitude, power or log10 power
+// (include/afg.h has the definition); rows are afg_mel_row, the table is afg_mel_fft_tables'
+enum : uint { AFG_STFT_COMPLEX = 0, AFG_STFT_MAGNITUDE = 1, AFG_STFT_POWER = 2, AFG_STFT_LOG10 = 3 }
+struct afg_stft_params { uint n_fft, win_length, hop, center, pad_mode, out_kind; float log_floor; uint reserved; }
+struct afg_stft_opts { uint struct_size; int n_threads; uint channels; uint frames; const(long)* first_frame; uint samplerate, mono, in_channels, max_in_rate, lowpass_width, n_out; afg_stft_params stft; uint reserved; }
+uint afg_stft_tile_frames(const(afg_stft_params)* params);
+ulong afg_stft_layout(afg_mel_row* rows, ulong n_rows, const(afg_stft_params)* params);
+int afg_stft_check_rows(const(afg_mel_row)* rows, ulong n_rows, ulong n_tiles, const(afg_stft_params)* params, ulong in_floats,
+                        ulong table_floats, ulong out_floats);
+int afg_stft_hip(ulong n_rows, const(afg_mel_row)* d_rows, ulong n_tiles, const(afg_stft_params)* params, const(float)* d_in,
+                 ulong in_floats, const(float)* d_table, ulong table_floats, float* d_out, ulong out_floats, void* hip_stream);
+int afg_batch_decode_stft(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_stft_opts)* opts, float* d_out,
+                          afg_batch_result* out_);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

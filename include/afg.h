@@ -1287,6 +1287,92 @@ int afg_melspec_fft_hip(uint64_t n_rows, const afg_mel_row *d_rows, uint64_t n_t
                         uint64_t in_floats, const float *d_table, uint64_t table_floats, const float *d_filters, uint64_t filters_floats,
                         float *d_out, uint64_t out_floats, void *hip_stream);
 
+/* The linear-frequency spectrum itself: the short-time Fourier transform afg_melspec_fft_hip computes per frame, delivered
+ * instead of multiplied into a bank -- complex for separation and enhancement, magnitude for vocoders, power for a bank of
+ * the caller's own.  A stage of its own beside the mel stage, with its own parameters (afg_stft_params); the rows are
+ * afg_mel_row records.  The value is the one defined above up to re / im: the periodic Hann window of win_length centred in
+ * the frame, center / pad_mode (reflect without edge repeat, or +0.0f), max_frames (afg_mel_frames' formula), and the FFT
+ * path's n_fft: 16 .. 2048 with prime factors 2, 3 and 5 only, anything else AFG_ERR_UNSUPPORTED.  Its float64 statement is
+ * basis64 / power64 of tests/melspec_model.py; tests/stft_model.py holds the intervals below.  n_bins = n_fft / 2 + 1.
+ *
+ * Parameters: n_fft as above, win_length 1 .. n_fft, hop 1 .. n_fft, center 0 or 1, pad_mode AFG_MEL_PAD_REFLECT or
+ * AFG_MEL_PAD_ZERO, out_kind AFG_STFT_*, log_floor a finite float >= 0 (0 means 1e-10f; read by AFG_STFT_LOG10 only, checked
+ * always), reserved 0.  With p = re * re + im * im: AFG_STFT_COMPLEX delivers (re, im), AFG_STFT_MAGNITUDE sqrtf(p),
+ * AFG_STFT_POWER p, AFG_STFT_LOG10 log10f(fmaxf(p, log_floor)).
+ *
+ * Output: record r writes comps * n_bins * out_frames floats at out_off, comps = 2 for AFG_STFT_COMPLEX and 1 otherwise, as
+ * [n_bins, out_frames] with frames contiguous (torch.stft's layout): bin k, frame f at out_off + k * out_frames + f, and for
+ * AFG_STFT_COMPLEX the pair at out_off + 2 * (k * out_frames + f), re first -- torch.view_as_real of a [n_bins, out_frames]
+ * complex64.
+ *
+ * Bound.  With u, A_f, B and E_f = B u A_f exactly as in the FFT mel path above, and p_hi = (|re64| + E)^2 + (|im64| + E)^2,
+ * p_lo = max(|re64| - E, 0)^2 + max(|im64| - E, 0)^2:
+ *   AFG_STFT_COMPLEX    |re - re64| <= E_f and |im - im64| <= E_f;
+ *   AFG_STFT_POWER      inside [(1 - 4u) p_lo, (1 + 4u) p_hi] (two products and a sum, fused or not);
+ *   AFG_STFT_MAGNITUDE  within 2 float32 ulp of the square root of that interval (the hardware square root is specified to
+ *                       1 ulp; the second is margin);
+ *   AFG_STFT_LOG10      within 3 float32 ulp of log10 of that interval after the floor, the mel path's figure.
+ * Locality as above: the same row gives the same bits wherever it stands; a NaN sample makes NaN of every bin of exactly the
+ * frames whose window span covers it (AFG_STFT_LOG10: log10f(floor), since fmaxf drops the NaN); padding outside the row and
+ * rows without samples give +0.0f under zero padding (AFG_STFT_LOG10: log10f(floor)).  The kernel does not listen to
+ * AFG_NUMERIC or afg_set_numeric_mode.
+ *
+ * The table is afg_mel_fft_tables' (the same window and twiddles).  afg_stft_tile_frames: host only; the frames of one row a
+ * workgroup takes for these parameters -- it depends on n_fft and out_kind, because the tile's LDS does -- or 0 with
+ * afg_last_error set for parameters out of range.  afg_stft_layout: host only; gives every row its tiles (first_tile) and
+ * returns their count, the sum of ceil(out_frames / tile); 0 with afg_last_error set for parameters out of range.  A layout
+ * made by afg_mel_layout or afg_mel_fft_layout does not serve.  afg_stft_check_rows: host only, needs no device; the checks
+ * afg_stft_hip makes before it launches, on a host copy of the records: parameters in range; table_floats at least
+ * win_length + 2 * n_fft; first_tile and n_tiles as afg_stft_layout gives them; every row's in_frames floats inside
+ * [0, in_floats); out_frames <= max_frames; reflect with output only with in_frames > pad; the record's comps * n_bins *
+ * out_frames floats inside [0, out_floats).  AFG_ERR_UNSUPPORTED for the n_fft, AFG_ERR_INVALID otherwise, afg_last_error set.
+ * afg_stft_hip runs every row in one launch, one workgroup per tile; arguments as afg_melspec_fft_hip's without the bank.
+ * The same checks come first (the entry fetches d_rows on hip_stream and waits for it); on anything but a pass nothing is
+ * written.  The kernel writes exactly the record's floats and reads no input float outside the record's row. */
+#define AFG_STFT_COMPLEX   0   /* (re, im) pairs */
+#define AFG_STFT_MAGNITUDE 1   /* sqrtf(p) */
+#define AFG_STFT_POWER     2   /* p = re*re + im*im */
+#define AFG_STFT_LOG10     3   /* log10f(fmaxf(p, log_floor)), log_floor 0 means 1e-10f */
+typedef struct afg_stft_params {   /* 32 bytes */
+    uint32_t n_fft, win_length, hop, center, pad_mode, out_kind;
+    float    log_floor;
+    uint32_t reserved;             /* 0 */
+} afg_stft_params;
+uint32_t afg_stft_tile_frames(const afg_stft_params *params);
+uint64_t afg_stft_layout(afg_mel_row *rows, uint64_t n_rows, const afg_stft_params *params);
+int afg_stft_check_rows(const afg_mel_row *rows, uint64_t n_rows, uint64_t n_tiles, const afg_stft_params *params, uint64_t in_floats,
+                        uint64_t table_floats, uint64_t out_floats);
+int afg_stft_hip(uint64_t n_rows, const afg_mel_row *d_rows, uint64_t n_tiles, const afg_stft_params *params, const float *d_in,
+                 uint64_t in_floats, const float *d_table, uint64_t table_floats, float *d_out, uint64_t out_floats, void *hip_stream);
+
+/* afg_batch_decode_resampled followed by afg_stft_hip: d_out is n_files * channels * n_bins * n_out floats on the current
+ * device (twice that for AFG_STFT_COMPLEX), and slab [i, k] is the definition above applied to row [i, k] of the tensor
+ * afg_batch_decode_resampled makes of the same list with the leading fields of the options.  In every other respect it is
+ * afg_batch_decode_mel (below): n_out == 0 means max_frames of T, the scratch is pooled under
+ * afg_dev_option("mel_scratch_bytes") with sublists of at least one file, the table is made once per (n_fft, win_length) and
+ * kept, a file that failed or was refused keeps its status and message and gets the all-zero row's slab, items[i].pcm points
+ * at the file's slab (NULL when it failed or was refused), n_files == 0 is AFG_OK and touches nothing.  Checked before any
+ * device call, afg_last_error set: everything afg_batch_decode_resampled checks, a struct_size below sizeof(afg_stft_opts),
+ * a non-zero `reserved`, the parameters (AFG_ERR_UNSUPPORTED for the n_fft), T without a frame, n_out above max_frames,
+ * reflect with T <= pad. */
+typedef struct afg_stft_opts {
+    uint32_t        struct_size;   /* sizeof(afg_stft_opts) */
+    int             n_threads;     /* from here to lowpass_width: as afg_resample_opts */
+    uint32_t        channels;
+    uint32_t        frames;        /* T, samples at `samplerate` */
+    const int64_t  *first_frame;
+    uint32_t        samplerate;
+    uint32_t        mono;
+    uint32_t        in_channels;
+    uint32_t        max_in_rate;
+    uint32_t        lowpass_width;
+    uint32_t        n_out;         /* frames per bin row; 0 means max_frames of T */
+    afg_stft_params stft;
+    uint32_t        reserved;      /* 0 */
+} afg_stft_opts;
+int afg_batch_decode_stft(const uint8_t *const *data, const size_t *length, int n_files, const afg_stft_opts *opts, float *d_out,
+                          afg_batch_result *out);
+
 /* afg_batch_decode_resampled followed by afg_melspec_hip: d_out is n_files * channels * n_mels * n_out floats on the
  * current device, and slab [i, k] is the definition above applied to row [i, k] of the tensor afg_batch_decode_resampled
  * makes of the same list with the leading fields of the options (frames is T, in samples at `samplerate`).  n_out == 0
