@@ -83,6 +83,12 @@ CEP_TILE = 64                                    # frames of one record per tile
 TRIM_REF_MAX, TRIM_REF_ABS = 0, 1                # afg_trim_params.reference
 TRIM_REF_NAMES = {"max": TRIM_REF_MAX, "abs": TRIM_REF_ABS}
 TRIM_TILE = 4096                                 # floats of one output row per tile of afg_trim_hip
+FILTER_TILE, FILTER_CHUNK, FILTER_K, FILTER_MAX_SECTIONS = 4096, 16, 64, 8     # afg_filter_hip: AFG_FILTER_*
+BIQUAD_KINDS = {"lowpass": 0, "highpass": 1, "bandpass": 2, "notch": 3, "allpass": 4, "peaking": 5, "lowshelf": 6, "highshelf": 7,
+                "preemphasis": 8, "dc_block": 9}                                  # AFG_BIQUAD_*
+# afg_filter_row: one row of afg_filter_hip
+FILTER_ROW_DTYPE = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), ("frames", np.uint32), ("reserved", np.uint32)])
+assert FILTER_ROW_DTYPE.itemsize == 24
 STFT_COMPLEX, STFT_MAGNITUDE, STFT_POWER, STFT_LOG10 = 0, 1, 2, 3       # afg_stft_params.out_kind
 
 # every symbol include/afg.h declares (checked by tests/test_abi.py)
@@ -125,6 +131,7 @@ ABI_SYMBOLS = [
     "afg_cep_dct", "afg_cep_layout", "afg_cep_check_rows", "afg_cepstra_hip", "afg_batch_decode_mfcc",
     "afg_trim_layout", "afg_trim_check_groups", "afg_trim_hip", "afg_batch_decode_trimmed",
     "afg_stft_tile_frames", "afg_stft_layout", "afg_stft_check_rows", "afg_stft_hip", "afg_batch_decode_stft",
+    "afg_biquad_design", "afg_filter_bound", "afg_filter_tile_frames", "afg_filter_check_rows", "afg_filter_hip", "afg_batch_decode_filtered",
 ]
 
 
@@ -366,6 +373,16 @@ BATCH_OPTS_SIZE_V2 = BatchOpts.dither.offset             # ... up to sample_type
 # what an item's pcm is viewed as, per sample type: (numpy dtype, trailing shape)
 _SAMPLE_VIEW = {SAMPLE_F32: (np.float32, ()), SAMPLE_F64: (np.float64, ()), SAMPLE_PCM_S8: (np.uint8, ()),
                 SAMPLE_PCM_S16: (np.int16, ()), SAMPLE_PCM_S24: (np.uint8, (3,))}
+
+
+class Biquad(C.Structure):
+    """afg_biquad: one second-order section, a0 == 1."""
+    _fields_ = [("b0", C.c_double), ("b1", C.c_double), ("b2", C.c_double), ("a1", C.c_double), ("a2", C.c_double)]
+
+
+class FilterParams(C.Structure):
+    """afg_filter_params (afg_filter_hip)."""
+    _fields_ = [("n_sections", C.c_uint32), ("sec", Biquad * 8)]
 
 
 class EncodingOptions(C.Structure):
@@ -625,6 +642,14 @@ def lib():
     L.afg_trim_layout.argtypes = [vp, u64, C.POINTER(TrimParams), C.POINTER(u64), C.POINTER(u64)]
     L.afg_trim_check_groups.argtypes = [vp, u64, u64, u64, C.POINTER(TrimParams), u64, u64]
     L.afg_trim_hip.argtypes = [u64, vp, u64, u64, C.POINTER(TrimParams), vp, u64, vp, u64, vp, vp, vp]
+    L.afg_biquad_design.argtypes = [u32, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(Biquad)]
+    L.afg_filter_bound.argtypes = [C.POINTER(FilterParams)]
+    L.afg_filter_bound.restype = C.c_double
+    L.afg_filter_tile_frames.argtypes = []
+    L.afg_filter_tile_frames.restype = u32
+    L.afg_filter_check_rows.argtypes = [vp, u64, C.POINTER(FilterParams), u64, u64, C.c_int]
+    L.afg_filter_hip.argtypes = [u64, vp, C.POINTER(FilterParams), vp, u64, vp, u64, vp, vp]
+    L.afg_batch_decode_filtered.argtypes = [vp, vp, C.c_int, C.POINTER(ResampleOpts), C.POINTER(FilterParams), vp, C.POINTER(BatchResult)]
     L.afg_batch_decode_trimmed.argtypes = [vp, vp, C.c_int, C.POINTER(ResampleOpts), C.POINTER(TrimParams), u32, vp, vp, C.POINTER(BatchResult)]
     L.afg_stft_tile_frames.argtypes = [C.POINTER(StftParams)]
     L.afg_stft_tile_frames.restype = u32
@@ -2044,6 +2069,124 @@ def batch_decode_tensor_trimmed(files, frames, channels, samplerate, scan_frames
     for i, m in enumerate(meta):
         m["begin"], m["end"] = int(regions[i]["begin"]), int(regions[i]["end"])
     return out, meta
+
+
+def biquad(kind, samplerate=1.0, f0=0.0, q=0.7071067811865476, gain_db=0.0):
+    """afg_biquad_design: the section (b0, b1, b2, a1, a2), a0 == 1, of one of BIQUAD_KINDS -- the Audio EQ Cookbook's
+    kinds at f0 Hz with quality q (and gain_db for "peaking" and the shelves), "preemphasis" with its coefficient in f0, and
+    "dc_block" with its corner in f0.  ValueError for what the helper refuses."""
+    if kind not in BIQUAD_KINDS:
+        raise ValueError(f"biquad: unknown kind {kind!r}: one of {sorted(BIQUAD_KINDS)}")
+    out = Biquad()
+    L = lib()
+    if L.afg_biquad_design(BIQUAD_KINDS[kind], float(samplerate), float(f0), float(q), float(gain_db), C.byref(out)) != 0:
+        raise ValueError(f"biquad: {L.afg_last_error().decode()}")
+    return (out.b0, out.b1, out.b2, out.a1, out.a2)
+
+
+def filter_params(sos):
+    """afg_filter_params of a cascade: a sequence of 1 .. 8 sections (b0, b1, b2, a1, a2), or scipy's rows of six with
+    a0 == 1.  Not checked here beyond its shape: the library refuses what it does not take."""
+    if isinstance(sos, FilterParams):
+        return sos
+    rows = [tuple(float(v) for v in r) for r in np.atleast_2d(np.asarray(sos, dtype=np.float64))]
+    if len(rows) > 8 or any(len(r) not in (5, 6) for r in rows):
+        raise ValueError("filter_params: 1 .. 8 sections of (b0, b1, b2, a1, a2) or (b0, b1, b2, 1, a1, a2)")
+    p = FilterParams()
+    p.n_sections = len(rows)
+    for k, r in enumerate(rows):
+        if len(r) == 6:
+            if r[3] != 1.0:
+                raise ValueError("filter_params: a section of six numbers must have a0 == 1")
+            r = r[:3] + r[4:]
+        p.sec[k] = Biquad(*r)
+    return p
+
+
+def filter_bound(sos):
+    """afg_filter_bound: E / max|x| of the cascade's interval (include/afg.h).  ValueError for a refused cascade."""
+    L = lib()
+    e = L.afg_filter_bound(C.byref(filter_params(sos)))
+    if not e > 0.0:
+        raise ValueError(f"filter_bound: {L.afg_last_error().decode()}")
+    return e
+
+
+def filter_check_rows(rows, sos, in_floats, out_floats, same_plane):
+    """afg_filter_check_rows: what afg_filter_hip checks before it launches, on host records.  AfgError when one fails."""
+    rows = np.ascontiguousarray(rows, dtype=FILTER_ROW_DTYPE)
+    check(lib().afg_filter_check_rows(rows.ctypes.data, len(rows), C.byref(filter_params(sos)), int(in_floats), int(out_floats), 1 if same_plane else 0))
+
+
+def filter_rows(n_rows, d_rows, sos, d_in, in_floats, d_out, out_floats, d_state=None, stream=None):
+    """Enqueue the filter kernel (afg_filter_hip) on device arrays: row k of d_rows (FILTER_ROW_DTYPE records) from d_in to
+    d_out -- the same tensor for in place -- through the cascade `sos`; d_state is None or n_rows * n_sections * 4 doubles,
+    read as the rows' history and overwritten with the history behind their last frames."""
+    check(lib().afg_filter_hip(int(n_rows), _ptr(d_rows), C.byref(filter_params(sos)), _ptr(d_in), int(in_floats), _ptr(d_out), int(out_floats),
+                               _ptr(d_state), _stream(stream)))
+
+
+def filter_tensor(t, sos, valid=None, state=None, out=None):
+    """Filter every row of a contiguous float32 device tensor along its last axis through the cascade `sos` (afg_filter_hip,
+    one launch on the current stream).  valid: None, or one length per row (the tensor's leading axes flattened): only
+    that many frames of the row are read and written.  state: None (zero history), or a float64 device tensor of shape
+    t.shape[:-1] + (n_sections, 4) that is read and updated -- a stream filtered in pieces.  out: None (a new tensor), `t`
+    itself (in place) or another contiguous tensor of t's shape that does not overlap it; what lies behind `valid` in it is
+    left as it is (zero in a new tensor).  Returns out."""
+    import torch
+    prm = filter_params(sos)
+    if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 1:
+        raise ValueError("filter_tensor: a contiguous float32 device tensor with at least one axis")
+    frames = int(t.shape[-1])
+    n = t.numel() // frames if frames else 0
+    if out is None:
+        out = torch.zeros_like(t) if valid is not None else torch.empty_like(t)
+    elif out.shape != t.shape or out.dtype != t.dtype or out.device != t.device or not out.is_contiguous():
+        raise ValueError("filter_tensor: out must be a contiguous tensor of t's shape, dtype and device")
+    if state is not None and (state.dtype != torch.float64 or state.device != t.device or not state.is_contiguous()
+                              or tuple(state.shape) != tuple(t.shape[:-1]) + (prm.n_sections, 4)):
+        raise ValueError(f"filter_tensor: state must be a contiguous float64 tensor of shape {tuple(t.shape[:-1]) + (prm.n_sections, 4)} on t's device")
+    if frames >= 1 << 32:
+        raise ValueError("filter_tensor: rows of 2^32 frames or more")
+    rows = np.zeros(n, FILTER_ROW_DTYPE)
+    rows["in_off"] = rows["out_off"] = np.arange(n, dtype=np.uint64) * np.uint64(frames)
+    rows["frames"] = frames
+    if valid is not None:
+        v = np.asarray(valid.cpu() if hasattr(valid, "cpu") else valid).reshape(-1)
+        if v.size != n or (v < 0).any() or (v > frames).any():
+            raise ValueError("filter_tensor: valid holds one length per row, 0 .. the last axis")
+        rows["frames"] = v
+    if n == 0:
+        if lib().afg_filter_check_rows(None, 0, C.byref(prm), 0, 0, 0) != 0:
+            raise ValueError(f"filter_tensor: {lib().afg_last_error().decode()}")
+        return out
+    with torch.cuda.device(t.device):
+        d_rows = torch.from_numpy(rows.view(np.uint8)).to(t.device)
+        filter_rows(n, d_rows, prm, t, t.numel(), out, out.numel(), state, torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+def batch_decode_tensor_filtered(files, frames, channels, samplerate, sos, first_frame=None, mono=False, in_channels=0, max_in_rate=0,
+                                 lowpass_width=0, out=None, n_threads=0):
+    """afg_batch_decode_filtered: batch_decode_tensor_resampled, then every file's rows filtered in place through the cascade
+    `sos` over their own samples -- the rows and lengths of batch_decode_tensor_normalized --, the padding left +0.0.
+    Returns (tensor, meta).  The same device and stream rules as batch_decode_tensor."""
+    prm = filter_params(sos)
+    frames, channels, samplerate = int(frames), int(channels), int(samplerate)
+    if frames < 1 or channels < 1 or samplerate < 1:
+        raise ValueError("batch_decode_tensor_filtered: frames, channels and samplerate must be at least 1")
+    if mono and channels != 1:
+        raise ValueError("batch_decode_tensor_filtered: a mono tensor has one channel")
+    L = lib()
+    if L.afg_filter_check_rows(None, 0, C.byref(prm), 0, 0, 0) != 0:
+        raise ValueError(f"batch_decode_tensor_filtered: {L.afg_last_error().decode()}")
+
+    def call(ptrs, lens, n, ff, out, res):
+        opts = ResampleOpts(C.sizeof(ResampleOpts), int(n_threads), channels, frames, ff, samplerate, 1 if mono else 0, int(in_channels),
+                            int(max_in_rate), int(lowpass_width))
+        return L.afg_batch_decode_filtered(ptrs, lens, n, C.byref(opts), C.byref(prm), out.data_ptr(), C.byref(res))
+
+    return _batch_tensor_call("batch_decode_tensor_filtered", files, (len(files), channels, frames), out, first_frame, call)
 
 
 def batch_transcode(files, options=None, n_threads=0, devices=None):

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "../../include/afg.h"
 
@@ -104,6 +105,15 @@ int cepstra_launch(const afg_cep_row *h_rows, uint64_t n_rows, const afg_cep_row
 int trim_launch(const afg_trim_group *h_groups, uint64_t n_groups, const afg_trim_group *d_groups, uint64_t n_blocks, uint64_t n_tiles,
                 const afg_trim_params *params, const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats, double *d_blocks,
                 afg_trim_region *d_regions, hipStream_t stream);
+
+// afg_filter_hip likewise (filter.hip).  filter_check_params and filter_tables are host only (host/afg_filter.cpp): the
+// cascade's checks, the bound's cap included, and the kernel's tables -- per section kFilterSecDoubles doubles: the five
+// coefficients at 0, the chunk's two homogeneous responses at kFilterH1 and kFilterH2, A^(16 i) for i = 0 .. 64 at kFilterPow
+constexpr uint32_t kFilterH1 = 8, kFilterH2 = 24, kFilterPow = 40, kFilterSecDoubles = 300;
+int filter_check_params(const afg_filter_params *params);
+void filter_tables(const afg_filter_params *params, std::vector<double> &tab);
+int filter_launch(const afg_filter_row *h_rows, uint64_t n_rows, const afg_filter_row *d_rows, const afg_filter_params *params,
+                  const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats, double *d_state, hipStream_t stream);
 
 // Owns a device buffer filled from a host array at plan creation.
 struct DeviceArray {

@@ -543,6 +543,23 @@ int afg_stft_hip(ulong n_rows, const(afg_mel_row)* d_rows, ulong n_tiles, const(
                  ulong in_floats, const(float)* d_table, ulong table_floats, float* d_out, ulong out_floats, void* hip_stream);
 int afg_batch_decode_stft(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_stft_opts)* opts, float* d_out,
                           afg_batch_result* out_);
+// filtering: cascades of second-order recursive sections over float rows, computed in float64 (include/afg.h has the
+// definition, the interval the result is held to and its constant AFG_FILTER_K)
+enum : uint { AFG_FILTER_MAX_SECTIONS = 8, AFG_FILTER_TILE = 4096, AFG_FILTER_CHUNK = 16, AFG_FILTER_K = 64 }
+enum : uint { AFG_BIQUAD_LOWPASS = 0, AFG_BIQUAD_HIGHPASS = 1, AFG_BIQUAD_BANDPASS = 2, AFG_BIQUAD_NOTCH = 3, AFG_BIQUAD_ALLPASS = 4,
+              AFG_BIQUAD_PEAKING = 5, AFG_BIQUAD_LOWSHELF = 6, AFG_BIQUAD_HIGHSHELF = 7, AFG_BIQUAD_PREEMPHASIS = 8, AFG_BIQUAD_DC_BLOCK = 9 }
+struct afg_biquad { double b0, b1, b2, a1, a2; }
+struct afg_filter_params { uint n_sections; afg_biquad[8] sec; }
+struct afg_filter_row { ulong in_off, out_off; uint frames, reserved; }
+int afg_biquad_design(uint kind, double samplerate, double f0, double q, double gain_db, afg_biquad* out_);
+double afg_filter_bound(const(afg_filter_params)* params);
+uint afg_filter_tile_frames();
+int afg_filter_check_rows(const(afg_filter_row)* rows, ulong n_rows, const(afg_filter_params)* params, ulong in_floats,
+                          ulong out_floats, int same_plane);
+int afg_filter_hip(ulong n_rows, const(afg_filter_row)* d_rows, const(afg_filter_params)* params, const(float)* d_in,
+                   ulong in_floats, float* d_out, ulong out_floats, double* d_state, void* hip_stream);
+int afg_batch_decode_filtered(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_resample_opts)* opts,
+                              const(afg_filter_params)* filter, float* d_out, afg_batch_result* out_);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

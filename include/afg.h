@@ -1675,6 +1675,124 @@ int afg_batch_decode_trimmed(const uint8_t *const *data, const size_t *length, i
                              const afg_trim_params *trim, uint32_t scan_frames, float *d_out, afg_trim_region *regions,
                              afg_batch_result *out);
 
+/* ---- filtering: cascades of second-order recursive sections over float rows ------------------------------------------------
+ * A rumble or DC high-pass in front of trim and normalisation, pre-emphasis in front of the spectral features, band limiting
+ * and equalisers, behind the collate on planar rows.  The reference has no such stage; the definition is this library's
+ * own, restated in numpy in tests/filter_model.py.
+ *
+ * Parameters (afg_filter_params), uniform over a call's rows: n_sections 1 .. 8 sections (afg_biquad) b0, b1, b2, a1, a2
+ * with a0 normalised to 1.  Section s maps its input u to
+ *     v[n] = b0 u[n] + b1 u[n-1] + b2 u[n-2] - a1 v[n-1] - a2 v[n-2]
+ * over the real numbers -- scipy.signal.sosfilt's definition.  Everything in front of a row's first sample is zero unless
+ * a state is passed in (below).  The sections run in order: the first reads the row's float32 samples, the last is rounded
+ * once to float32.  A section is refused (AFG_ERR_INVALID) unless its five numbers are finite and its poles lie strictly
+ * inside the unit circle: |a2| < 1 and |a1| < 1 + a2.  a1 == a2 == 0 is a plain FIR section.
+ *
+ * The device computes in float64, in chunks (below); the chunking is not part of the definition.  The contract is an
+ * interval round the exact result y^ of the definition:
+ *     |y - y^| <= ulp32(|y^| + K E) / 2 + K E,        ulp32 never below 2^-149,
+ *     E = 2^-53 * max|x| * sum over s of |g_s|_1 * (beta_s * P_(s-1) + alpha_s * P_s) * product over t > s of |h_t|_1
+ * with g_s the impulse response of 1 / A_s, h_s that of the whole section, |.|_1 the sum of magnitudes,
+ * beta = |b0| + |b1| + |b2|, alpha = |a1| + |a2|, P_s = product over t <= s of |h_t|_1 and P_0 = 1: one rounding unit on
+ * every term of every section's recurrence, carried by the rest of the cascade.  afg_filter_bound returns E / max|x|: host
+ * only, it sums the impulse responses in double until what is left of them -- bounded through the pole radius r by
+ * (n + 1) r^n -- is below 2^-60 of the sum.  It returns 0 with afg_last_error set for a refused cascade, for one whose
+ * responses have not decayed after 2^28 samples, and for one whose bound exceeds 2^30; such a cascade is refused by every
+ * entry below as well.
+ *
+ * K = AFG_FILTER_K = 64, from the operations an output passes through in the evaluation of csrc/filter.hip, every fused
+ * multiply-add counted as one rounding on each of its terms: the zero-state run of a chunk, 5 (three for the b terms, two
+ * for the a terms, as a sequential evaluation has them); the carry correction, 3 (two products, the sum onto the run); the
+ * state a lane's carry is made of, 3 for each of the 6 steps of the scan inside a wavefront, of the 3 steps across the four
+ * wavefronts and of the product with the lane's power of the chunk matrix, 30 in all, and 1 for the tables (rounded once
+ * from long double); the previous section's state standing in for its output at a wavefront's first lane, 1; and the
+ * model's own long-double recurrence, below 1.  That is 41, taken to the next power of two.  (A count to first order, as
+ * E is: inside a chunk of 16 the zero-state run may exceed the true signal, by at most the 16-sample partial sum of |g_s|.)
+ *
+ * From a row's first non-finite input sample onward that row's outputs and outgoing state are unspecified; everything in
+ * front of it, every other row and every float outside the rows keep the contract.
+ *
+ * afg_biquad_design: host only, in double.  With w = 2 pi f0 / samplerate, c = cos w, alpha = sin w / (2 q) and
+ * A = 10^(gain_db / 40), the Audio EQ Cookbook's (R. Bristow-Johnson) sections, every coefficient divided by a0:
+ *   LOWPASS    b = ((1-c)/2, 1-c, (1-c)/2)              a = (1+alpha, -2c, 1-alpha)
+ *   HIGHPASS   b = ((1+c)/2, -(1+c), (1+c)/2)           a likewise
+ *   BANDPASS   b = (alpha, 0, -alpha)                   a likewise        (constant 0 dB peak gain)
+ *   NOTCH      b = (1, -2c, 1)                          a likewise
+ *   ALLPASS    b = (1-alpha, -2c, 1+alpha)              a likewise
+ *   PEAKING    b = (1+alpha A, -2c, 1-alpha A)          a = (1+alpha/A, -2c, 1-alpha/A)
+ *   LOWSHELF   with S = 2 sqrt(A) alpha:
+ *              b = (A((A+1)-(A-1)c+S), 2A((A-1)-(A+1)c), A((A+1)-(A-1)c-S))    a = ((A+1)+(A-1)c+S, -2((A-1)+(A+1)c), (A+1)+(A-1)c-S)
+ *   HIGHSHELF  b = (A((A+1)+(A-1)c+S), -2A((A-1)+(A+1)c), A((A+1)+(A-1)c-S))   a = ((A+1)-(A-1)c+S, 2((A-1)-(A+1)c), (A+1)-(A-1)c-S)
+ *   PREEMPHASIS  b = (1, -f0, 0), a1 = a2 = 0: the coefficient (0.97, say) stands in the f0 argument; |f0| <= 1
+ *   DC_BLOCK     b = (1, -1, 0), a1 = -r, a2 = 0 with r = exp(-2 pi f0 / samplerate): a zero at z = 1 and a pole at r
+ * samplerate, q and gain_db are not looked at by PREEMPHASIS; q and gain_db not by DC_BLOCK; gain_db by the shelves and
+ * PEAKING only.  AFG_ERR_INVALID with a message and *out untouched: an unknown kind, NULL out, an argument that is looked at
+ * and not finite, samplerate <= 0, f0 outside (0, samplerate / 2), q <= 0, a pre-emphasis coefficient above 1 in size.
+ *
+ * Rows.  A row (afg_filter_row) is `frames` floats at in_off of d_in, filtered into `frames` floats at out_off of d_out;
+ * frames == 0 reads and writes nothing.  d_in == d_out with in_off == out_off is in place; any other overlap -- of one
+ * row's output with another's, of a row's output with any row's input, or of the two planes when they are not the same
+ * pointer -- is refused.  afg_filter_check_rows needs no device (same_plane says whether d_in == d_out): the parameters as
+ * above, the bound included; every row inside [0, in_floats) and [0, out_floats), offsets that would wrap included;
+ * reserved 0; the overlaps.  n_rows == 0 checks the parameters alone.
+ *
+ * State.  d_state is NULL or n_rows * n_sections * 4 doubles, 8-byte aligned: for row i and section s the four at
+ * (i * n_sections + s) * 4 are u[n-1], u[n-2], v[n-1], v[n-2] of the section, unrounded -- read as the row's history in
+ * front of frame 0, overwritten with the history behind the last frame, untouched for frames == 0.  A row filtered in
+ * pieces through its state meets the interval of the whole row.
+ *
+ * afg_filter_hip is one launch on hip_stream, one workgroup of 256 lanes per row, without atomics or waiting between
+ * workgroups: the row is walked in tiles of AFG_FILTER_TILE = 4096 frames (afg_filter_tile_frames returns it), every lane
+ * takes a chunk of AFG_FILTER_CHUNK = 16 consecutive frames, runs each section over it from zero state in float64, and
+ * the chunks' end states meet in a scan of the map s -> A^16 s + e over the workgroup, the tile's outgoing state carried
+ * to the next.  d_rows is the device copy of the rows; the entry fetches it on hip_stream, waits for it and checks it as
+ * afg_filter_check_rows does: anything but a pass is AFG_ERR_INVALID and nothing is written.  Exactly `frames` floats are
+ * written per row.  The planes are 4-byte aligned, d_rows and d_state 8-byte aligned; at most 2^31 - 1 rows a launch.  The
+ * tables of a cascade (16 KiB at the most) are kept on the device per distinct parameters. */
+#define AFG_FILTER_MAX_SECTIONS 8
+#define AFG_FILTER_TILE   4096
+#define AFG_FILTER_CHUNK  16
+#define AFG_FILTER_K      64
+#define AFG_BIQUAD_LOWPASS     0
+#define AFG_BIQUAD_HIGHPASS    1
+#define AFG_BIQUAD_BANDPASS    2
+#define AFG_BIQUAD_NOTCH       3
+#define AFG_BIQUAD_ALLPASS     4
+#define AFG_BIQUAD_PEAKING     5
+#define AFG_BIQUAD_LOWSHELF    6
+#define AFG_BIQUAD_HIGHSHELF   7
+#define AFG_BIQUAD_PREEMPHASIS 8
+#define AFG_BIQUAD_DC_BLOCK    9
+typedef struct afg_biquad {       /* 40 bytes */
+    double b0, b1, b2, a1, a2;    /* a0 == 1 */
+} afg_biquad;
+typedef struct afg_filter_params {    /* 328 bytes */
+    uint32_t   n_sections;        /* 1 .. 8 */
+    afg_biquad sec[8];            /* sec[n_sections ..] are not looked at */
+} afg_filter_params;
+typedef struct afg_filter_row {   /* 24 bytes */
+    uint64_t in_off, out_off;     /* float index of frame 0 in d_in / d_out */
+    uint32_t frames, reserved;    /* reserved 0 */
+} afg_filter_row;
+int afg_biquad_design(uint32_t kind, double samplerate, double f0, double q, double gain_db, afg_biquad *out);
+double afg_filter_bound(const afg_filter_params *params);
+uint32_t afg_filter_tile_frames(void);
+int afg_filter_check_rows(const afg_filter_row *rows, uint64_t n_rows, const afg_filter_params *params, uint64_t in_floats,
+                          uint64_t out_floats, int same_plane);
+int afg_filter_hip(uint64_t n_rows, const afg_filter_row *d_rows, const afg_filter_params *params, const float *d_in,
+                   uint64_t in_floats, float *d_out, uint64_t out_floats, double *d_state, void *hip_stream);
+
+/* afg_batch_decode_resampled, then one afg_filter_hip launch in place over the rows and lengths that
+ * afg_batch_decode_resampled_norm defines: rows = min(channels, the file's channels), or 1 with mono, each over its valid
+ * frames, from zero state.  What lies behind `valid` is +0.0f -- the filter's ringing into the padding is not produced, and
+ * the few frames of the resampler's own tail that afg_batch_decode_resampled leaves there are cleared --, and so are the rows
+ * a file has no channel for and the slab of a file that failed or was refused.  Sublists as in
+ * afg_batch_decode_resampled.  Checked before any device call, AFG_ERR_INVALID with afg_last_error set: everything
+ * afg_batch_decode_resampled checks, NULL filter, a cascade afg_filter_bound refuses.  Statuses, messages and items[i] are
+ * afg_batch_decode_resampled's. */
+int afg_batch_decode_filtered(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
+                              const afg_filter_params *filter, float *d_out, afg_batch_result *out);
+
 #ifdef __cplusplus
 }
 #endif
