@@ -90,6 +90,8 @@ BIQUAD_KINDS = {"lowpass": 0, "highpass": 1, "bandpass": 2, "notch": 3, "allpass
 FILTER_ROW_DTYPE = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), ("frames", np.uint32), ("reserved", np.uint32)])
 assert FILTER_ROW_DTYPE.itemsize == 24
 STFT_COMPLEX, STFT_MAGNITUDE, STFT_POWER, STFT_LOG10 = 0, 1, 2, 3       # afg_stft_params.out_kind
+LOUDNESS_K = 64                                  # AFG_LOUDNESS_K
+LOUDNESS_UNGATED, LOUDNESS_GAIN_CLAMPED, LOUDNESS_PEAK_CLAMPED = 1, 2, 4     # afg_loudness_stats.flags
 
 # every symbol include/afg.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -132,6 +134,7 @@ ABI_SYMBOLS = [
     "afg_trim_layout", "afg_trim_check_groups", "afg_trim_hip", "afg_batch_decode_trimmed",
     "afg_stft_tile_frames", "afg_stft_layout", "afg_stft_check_rows", "afg_stft_hip", "afg_batch_decode_stft",
     "afg_biquad_design", "afg_filter_bound", "afg_filter_tile_frames", "afg_filter_check_rows", "afg_filter_hip", "afg_batch_decode_filtered",
+    "afg_kweight_design", "afg_loudness_lufs", "afg_loudness_layout", "afg_loudness_check_groups", "afg_loudness_hip", "afg_batch_decode_loudnorm",
 ]
 
 
@@ -383,6 +386,34 @@ class Biquad(C.Structure):
 class FilterParams(C.Structure):
     """afg_filter_params (afg_filter_hip)."""
     _fields_ = [("n_sections", C.c_uint32), ("sec", Biquad * 8)]
+
+
+class LoudnessParams(C.Structure):
+    """afg_loudness_params (afg_loudness_hip)."""
+    _fields_ = [("samplerate", C.c_uint32), ("apply", C.c_uint32), ("target_lufs", C.c_double), ("max_peak", C.c_float), ("max_gain", C.c_float),
+                ("weights", C.c_double * 8), ("reserved", C.c_uint32 * 2)]
+
+
+class LoudnessGroup(C.Structure):
+    """afg_loudness_group: the rows one measurement covers (afg_loudness_hip)."""
+    _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("stride", C.c_uint64), ("first_sub", C.c_uint64), ("first_block", C.c_uint64),
+                ("rows", C.c_uint32), ("valid", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+class LoudnessCounts(C.Structure):
+    """afg_loudness_counts: the doubles of d_sub and d_blocks a launch takes (afg_loudness_layout)."""
+    _fields_ = [("n_sub", C.c_uint64), ("n_blocks", C.c_uint64)]
+
+
+class LoudnessStats(C.Structure):
+    """afg_loudness_stats: one group's record."""
+    _fields_ = [("energy", C.c_double), ("rel_threshold", C.c_double), ("n_blocks", C.c_uint32), ("n_abs", C.c_uint32), ("n_gated", C.c_uint32),
+                ("flags", C.c_uint32), ("peak", C.c_float), ("gain", C.c_float)]
+
+
+LOUDNESS_GROUP_DTYPE = np.dtype(LoudnessGroup)   # arrays of the records, as the other stages' *_DTYPE
+LOUDNESS_STATS_DTYPE = np.dtype(LoudnessStats)
+assert LOUDNESS_GROUP_DTYPE.itemsize == 64 and LOUDNESS_STATS_DTYPE.itemsize == 40 and C.sizeof(LoudnessParams) == 96 and C.sizeof(LoudnessCounts) == 16
 
 
 class EncodingOptions(C.Structure):
@@ -651,6 +682,13 @@ def lib():
     L.afg_filter_hip.argtypes = [u64, vp, C.POINTER(FilterParams), vp, u64, vp, u64, vp, vp]
     L.afg_batch_decode_filtered.argtypes = [vp, vp, C.c_int, C.POINTER(ResampleOpts), C.POINTER(FilterParams), vp, C.POINTER(BatchResult)]
     L.afg_batch_decode_trimmed.argtypes = [vp, vp, C.c_int, C.POINTER(ResampleOpts), C.POINTER(TrimParams), u32, vp, vp, C.POINTER(BatchResult)]
+    L.afg_kweight_design.argtypes = [u32, C.POINTER(FilterParams)]
+    L.afg_loudness_lufs.argtypes = [C.c_double]
+    L.afg_loudness_lufs.restype = C.c_double
+    L.afg_loudness_layout.argtypes = [vp, u64, C.POINTER(LoudnessParams), C.POINTER(LoudnessCounts)]
+    L.afg_loudness_check_groups.argtypes = [vp, u64, C.POINTER(LoudnessCounts), C.POINTER(LoudnessParams), u64, u64, C.c_int]
+    L.afg_loudness_hip.argtypes = [u64, vp, C.POINTER(LoudnessCounts), C.POINTER(LoudnessParams), vp, u64, vp, u64, vp, vp, vp, vp]
+    L.afg_batch_decode_loudnorm.argtypes = [vp, vp, C.c_int, C.POINTER(ResampleOpts), C.POINTER(LoudnessParams), vp, vp, C.POINTER(BatchResult)]
     L.afg_stft_tile_frames.argtypes = [C.POINTER(StftParams)]
     L.afg_stft_tile_frames.restype = u32
     L.afg_stft_layout.argtypes = [vp, u64, C.POINTER(StftParams)]
@@ -2187,6 +2225,143 @@ def batch_decode_tensor_filtered(files, frames, channels, samplerate, sos, first
         return L.afg_batch_decode_filtered(ptrs, lens, n, C.byref(opts), C.byref(prm), out.data_ptr(), C.byref(res))
 
     return _batch_tensor_call("batch_decode_tensor_filtered", files, (len(files), channels, frames), out, first_frame, call)
+
+
+def kweight_design(samplerate):
+    """afg_kweight_design: the two sections (b0, b1, b2, a1, a2) of BS.1770's K-weighting at `samplerate` (8000 .. 192000 Hz), the
+    shelf and the high-pass -- a cascade filter_tensor takes as it is.  Host only.  ValueError for a rate out of range."""
+    out = FilterParams()
+    L = lib()
+    if L.afg_kweight_design(int(samplerate), C.byref(out)) != 0:
+        raise ValueError(f"kweight_design: {L.afg_last_error().decode()}")
+    return [(q.b0, q.b1, q.b2, q.a1, q.a2) for q in out.sec[:2]]
+
+
+def loudness_lufs(energy):
+    """afg_loudness_lufs: -0.691 + 10 log10(energy), -inf for 0: the integrated loudness of a record's energy."""
+    return float(lib().afg_loudness_lufs(float(energy)))
+
+
+def loudness_params(samplerate, target_lufs=-23.0, max_peak=0.0, max_gain=0.0, apply=True, weights=None):
+    """afg_loudness_params.  weights: None (every row 1) or up to 8 channel weights G_i -- BS.1770's 5.1 order is
+    (1, 1, 1, 0, 1.41, 1.41).  A LoudnessParams passes through.  The ranges are the library's to check."""
+    if isinstance(samplerate, LoudnessParams):
+        return samplerate
+    w = [0.0] * 8
+    if weights is not None:
+        weights = [float(v) for v in weights]
+        if len(weights) > 8:
+            raise ValueError("loudness_params: at most 8 channel weights")
+        w[:len(weights)] = weights
+    return LoudnessParams(int(samplerate), 1 if apply else 0, float(target_lufs), float(max_peak), float(max_gain), (C.c_double * 8)(*w),
+                          (C.c_uint32 * 2)(0, 0))
+
+
+def loudness_layout(groups, params):
+    """afg_loudness_layout: fills first_sub and first_block of a LOUDNESS_GROUP_DTYPE array in place; returns the
+    LoudnessCounts of the launch.  AfgError for parameters out of range."""
+    assert groups.dtype == LOUDNESS_GROUP_DTYPE and groups.flags.c_contiguous
+    L = lib()
+    counts = LoudnessCounts()
+    if not L.afg_loudness_layout(groups.ctypes.data, len(groups), C.byref(params), C.byref(counts)):
+        raise AfgError(f"afg: {L.afg_last_error().decode()}")
+    return counts
+
+
+def loudness_check_groups(groups, counts, params, in_floats, out_floats, same_plane):
+    """afg_loudness_check_groups: what afg_loudness_hip checks before it launches, on host records.  AfgError when one fails."""
+    assert groups.dtype == LOUDNESS_GROUP_DTYPE and groups.flags.c_contiguous
+    check(lib().afg_loudness_check_groups(groups.ctypes.data, len(groups), C.byref(counts), C.byref(params), int(in_floats), int(out_floats),
+                                          1 if same_plane else 0))
+
+
+def loudness(n_groups, d_groups, counts, params, d_in, in_floats, d_out, out_floats, d_sub, d_blocks, d_stats, stream=None):
+    """Enqueue the loudness kernels (afg_loudness_hip) on device arrays: every group's block energies z_j into d_blocks
+    (counts.n_blocks doubles), its record into d_stats (LOUDNESS_STATS_DTYPE records) and -- with params.apply -- its valid
+    elements times the gain into d_out (d_in itself for in place; None when measuring only).  d_sub: counts.n_sub doubles of
+    scratch.  The groups are checked first (the call waits for `stream` to read them): AfgError, and nothing written, when
+    one fails."""
+    check(lib().afg_loudness_hip(int(n_groups), _ptr(d_groups), C.byref(counts), C.byref(params), _ptr(d_in), int(in_floats), _ptr(d_out),
+                                 int(out_floats), _ptr(d_sub), _ptr(d_blocks), _ptr(d_stats), _stream(stream)))
+
+
+def loudness_tensor(t, valid=None, samplerate=16000, target_lufs=-23.0, max_peak=0.0, max_gain=0.0, apply=True, weights=None, out=None,
+                    params=None):
+    """Measure the integrated loudness (BS.1770-4) of every group of a contiguous float32 device tensor [..., channels, frames]
+    -- the channel axis, 8 rows at the most, is one group; the leading axes are flattened -- and, with apply, bring it to
+    target_lufs (afg_loudness_hip, on the current stream).  valid: None, or one length per group: only that many frames of
+    its rows count and are touched.  out: None (a new tensor, a copy of t behind `valid`), `t` itself (in place) or another
+    contiguous tensor of t's shape that does not overlap it.  params: a LoudnessParams instead of the keywords.  Returns
+    (out, stats): stats a LOUDNESS_STATS_DTYPE array with one record per group (loudness_lufs(energy) is its loudness); out
+    is None when apply is off."""
+    import torch
+    prm = params if isinstance(params, LoudnessParams) else loudness_params(samplerate, target_lufs, max_peak, max_gain, apply, weights)
+    if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 2:
+        raise ValueError("loudness_tensor: a contiguous float32 device tensor [..., channels, frames]")
+    rows, frames = int(t.shape[-2]), int(t.shape[-1])
+    if rows < 1 or rows > 8 or frames >= 1 << 32:
+        raise ValueError("loudness_tensor: 1 .. 8 channels of fewer than 2^32 frames")
+    n = t.numel() // (rows * frames) if frames else 0
+    L = lib()
+    if L.afg_loudness_check_groups(None, 0, None, C.byref(prm), 0, 0, 0) != 0:
+        raise ValueError(f"loudness_tensor: {L.afg_last_error().decode()}")
+    if not prm.apply:
+        if out is not None:
+            raise ValueError("loudness_tensor: out without apply")
+    elif out is None:
+        out = t.clone() if valid is not None else torch.empty_like(t)
+    elif out.shape != t.shape or out.dtype != t.dtype or out.device != t.device or not out.is_contiguous():
+        raise ValueError("loudness_tensor: out must be a contiguous tensor of t's shape, dtype and device")
+    groups = np.zeros(n, LOUDNESS_GROUP_DTYPE)
+    groups["in_off"] = groups["out_off"] = np.arange(n, dtype=np.uint64) * np.uint64(rows * frames)
+    groups["stride"], groups["rows"], groups["valid"] = frames, rows, frames
+    if valid is not None:
+        v = np.asarray(valid.cpu() if hasattr(valid, "cpu") else valid).reshape(-1)
+        if v.size != n or (v < 0).any() or (v > frames).any():
+            raise ValueError("loudness_tensor: valid holds one length per group, 0 .. the last axis")
+        groups["valid"] = v
+    if n == 0:
+        return out, np.zeros(0, LOUDNESS_STATS_DTYPE)
+    counts = loudness_layout(groups, prm)
+    with torch.cuda.device(t.device):
+        d_groups = torch.from_numpy(groups.view(np.uint8)).to(t.device)
+        d_sub = torch.empty(max(counts.n_sub, 1), dtype=torch.float64, device=t.device)
+        d_blocks = torch.empty(max(counts.n_blocks, 1), dtype=torch.float64, device=t.device)
+        d_stats = torch.zeros(n * LOUDNESS_STATS_DTYPE.itemsize, dtype=torch.uint8, device=t.device)
+        loudness(n, d_groups, counts, prm, t, t.numel(), out, out.numel() if out is not None else 0, d_sub, d_blocks, d_stats,
+                 torch.cuda.current_stream().cuda_stream)
+        stats = d_stats.cpu().numpy().view(LOUDNESS_STATS_DTYPE).copy()
+    return out, stats
+
+
+def batch_decode_tensor_loudnorm(files, frames, channels, samplerate, target_lufs=-23.0, max_peak=0.0, max_gain=0.0, apply=True, weights=None,
+                                 first_frame=None, mono=False, in_channels=0, max_in_rate=0, lowpass_width=0, out=None, n_threads=0):
+    """afg_batch_decode_loudnorm: batch_decode_tensor_resampled, then every file measured after BS.1770-4 over its own samples
+    -- its channel rows one group, the rows and lengths of batch_decode_tensor_normalized -- and, with apply, brought to
+    target_lufs in place; the padding is left as it is.  Returns (tensor, meta, stats): stats a LOUDNESS_STATS_DTYPE array
+    with one record per file (zero with gain 1 for a file that failed).  The same device and stream rules as
+    batch_decode_tensor; ValueError for arguments out of range, before any call."""
+    prm = loudness_params(samplerate, target_lufs, max_peak, max_gain, apply, weights)
+    frames, channels, samplerate = int(frames), int(channels), int(samplerate)
+    if frames < 1 or channels < 1 or samplerate < 1:
+        raise ValueError("batch_decode_tensor_loudnorm: frames, channels and samplerate must be at least 1")
+    if channels > 8:
+        raise ValueError("batch_decode_tensor_loudnorm: at most 8 channels")
+    if mono and channels != 1:
+        raise ValueError("batch_decode_tensor_loudnorm: a mono tensor has one channel")
+    L = lib()
+    if L.afg_loudness_check_groups(None, 0, None, C.byref(prm), 0, 0, 0) != 0:
+        raise ValueError(f"batch_decode_tensor_loudnorm: {L.afg_last_error().decode()}")
+    n = len(files)
+    stats = np.zeros(max(n, 1), LOUDNESS_STATS_DTYPE)
+
+    def call(ptrs, lens, n, ff, out, res):
+        opts = ResampleOpts(C.sizeof(ResampleOpts), int(n_threads), channels, frames, ff, samplerate, 1 if mono else 0, int(in_channels),
+                            int(max_in_rate), int(lowpass_width))
+        return L.afg_batch_decode_loudnorm(ptrs, lens, n, C.byref(opts), C.byref(prm), out.data_ptr(), stats.ctypes.data, C.byref(res))
+
+    out, meta = _batch_tensor_call("batch_decode_tensor_loudnorm", files, (n, channels, frames), out, first_frame, call)
+    return out, meta, stats[:n].copy()
 
 
 def batch_transcode(files, options=None, n_threads=0, devices=None):

@@ -115,6 +115,17 @@ void filter_tables(const afg_filter_params *params, std::vector<double> &tab);
 int filter_launch(const afg_filter_row *h_rows, uint64_t n_rows, const afg_filter_row *d_rows, const afg_filter_params *params,
                   const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats, double *d_state, hipStream_t stream);
 
+// afg_loudness_hip likewise (loudness.hip).  loudness_check_params, loudness_kweight (the K-weighting of a rate, checked),
+// loudness_step (100 ms in samples) and loudness_blocks (whole gating blocks of `valid` samples) are host only
+// (host/afg_loudness.cpp)
+int loudness_check_params(const afg_loudness_params *params);
+int loudness_kweight(uint32_t samplerate, afg_filter_params *out);
+constexpr uint32_t loudness_step(uint32_t samplerate) { return (samplerate + 5u) / 10u; }
+constexpr uint32_t loudness_blocks(uint32_t valid, uint32_t step) { return valid >= 4u * step ? (valid - 4u * step) / step + 1u : 0u; }
+int loudness_launch(const afg_loudness_group *h_groups, uint64_t n_groups, const afg_loudness_group *d_groups, const afg_loudness_counts *counts,
+                    const afg_loudness_params *params, const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats,
+                    double *d_sub, double *d_blocks, afg_loudness_stats *d_stats, hipStream_t stream);
+
 // Owns a device buffer filled from a host array at plan creation.
 struct DeviceArray {
     void *ptr = nullptr;

@@ -560,6 +560,23 @@ int afg_filter_hip(ulong n_rows, const(afg_filter_row)* d_rows, const(afg_filter
                    ulong in_floats, float* d_out, ulong out_floats, double* d_state, void* hip_stream);
 int afg_batch_decode_filtered(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_resample_opts)* opts,
                               const(afg_filter_params)* filter, float* d_out, afg_batch_result* out_);
+// loudness: integrated loudness after ITU-R BS.1770-4 per group of rows and the gain to a target (include/afg.h has the
+// definition, the interval the block energies are held to and its constant AFG_LOUDNESS_K)
+enum : uint { AFG_LOUDNESS_K = 64, AFG_LOUDNESS_UNGATED = 1, AFG_LOUDNESS_GAIN_CLAMPED = 2, AFG_LOUDNESS_PEAK_CLAMPED = 4 }
+struct afg_loudness_params { uint samplerate, apply; double target_lufs; float max_peak, max_gain; double[8] weights; uint[2] reserved; }
+struct afg_loudness_group { ulong in_off, out_off, stride, first_sub, first_block; uint rows, valid; uint[4] reserved; }
+struct afg_loudness_counts { ulong n_sub, n_blocks; }
+struct afg_loudness_stats { double energy, rel_threshold; uint n_blocks, n_abs, n_gated, flags; float peak, gain; }
+int afg_kweight_design(uint samplerate, afg_filter_params* out_);
+double afg_loudness_lufs(double energy);
+int afg_loudness_layout(afg_loudness_group* groups, ulong n_groups, const(afg_loudness_params)* params, afg_loudness_counts* counts);
+int afg_loudness_check_groups(const(afg_loudness_group)* groups, ulong n_groups, const(afg_loudness_counts)* counts,
+                              const(afg_loudness_params)* params, ulong in_floats, ulong out_floats, int same_plane);
+int afg_loudness_hip(ulong n_groups, const(afg_loudness_group)* d_groups, const(afg_loudness_counts)* counts,
+                     const(afg_loudness_params)* params, const(float)* d_in, ulong in_floats, float* d_out, ulong out_floats,
+                     double* d_sub, double* d_blocks, afg_loudness_stats* d_stats, void* hip_stream);
+int afg_batch_decode_loudnorm(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_resample_opts)* opts,
+                              const(afg_loudness_params)* loudness, float* d_out, afg_loudness_stats* stats, afg_batch_result* out_);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

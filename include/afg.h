@@ -1793,6 +1793,128 @@ int afg_filter_hip(uint64_t n_rows, const afg_filter_row *d_rows, const afg_filt
 int afg_batch_decode_filtered(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
                               const afg_filter_params *filter, float *d_out, afg_batch_result *out);
 
+/* ---- loudness: integrated loudness after ITU-R BS.1770-4 / EBU R 128 per group of rows, and the gain to a target ---------
+ * What speech and music corpora are levelled with ("every file at -23 LUFS"), as pyloudnorm and ffmpeg's loudnorm measure
+ * it: K-weighting, blocks of 400 ms with 75 % overlap, an absolute gate at -70 LKFS and a relative gate 10 LU below the
+ * mean of what passes it.  The reference has no such stage; the definition is restated in numpy in tests/loudness_model.py.
+ *
+ * Parameters (afg_loudness_params), uniform over a call: samplerate 8000 .. 192000 Hz; target_lufs finite, -200 .. 200;
+ * max_peak finite and >= 0 (0: no ceiling); max_gain finite and >= 0, linear (0: none); apply 0 (measure only; d_out is not
+ * used and may be NULL) or 1; weights[8] the channel weights G_i of rows 0 .. 7, finite and >= 0 -- all zero means every row
+ * has weight 1; BS.1770's surround weight is 1.41, its LFE weight 0 --; reserved words 0.  Anything else is AFG_ERR_INVALID.
+ *
+ * K-weighting.  afg_kweight_design(samplerate, out): host only, in double; out becomes a cascade of two sections, the
+ * shelf and then the high-pass, from the analogue prototypes of the standard's 48 kHz table (which these formulas reproduce
+ * to 1e-15):
+ *   shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; K = tan(pi f0 / fs),
+ *              Vh = 10^(G / 20), Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2;
+ *              b = (Vh + Vb K / Q + K^2, 2 (K^2 - Vh), Vh - Vb K / Q + K^2) / a0, a1 = 2 (K^2 - 1) / a0, a2 = (1 - K / Q + K^2) / a0
+ *   high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773; K, a0, a1, a2 of the same form; b = (1, -2, 1), not divided
+ *              by a0 -- the standard's table
+ * AFG_ERR_INVALID with *out untouched for a samplerate out of range or NULL out.
+ *
+ * Groups.  A group (afg_loudness_group) is what one measurement covers -- one file's channel rows: rows 1 .. 8; row i
+ * starts at float in_off + i * stride of d_in and out_off + i * stride of d_out; only the first `valid` floats of a row count
+ * and are touched.
+ *
+ * Blocks, with libebur128's rounding: step = (samplerate + 5) / 10 in integers, a gating block is N = 4 step samples, block j
+ * covers samples [j step, j step + N) of every row, and only whole blocks count:
+ * n_blocks = valid >= N ? (valid - N) / step + 1 : 0.  With v_i the K-weighted row i from zero state, over the real numbers,
+ *     z_j = (1 / N) * sum over i of G_i * sum over the block's n of v_i[n]^2.
+ * Gating is linear throughout -- the device takes no logarithm.  Gamma_abs = 10^((-70 + 0.691) / 10), rounded once in
+ * double on the host.  Block j passes the absolute gate when z_j > Gamma_abs; n_abs counts those; Gamma_rel
+ * (rel_threshold) = 0.1 * their mean; block j is gated in when z_j > Gamma_abs and z_j > Gamma_rel; n_gated counts those and
+ * energy is their mean.  The integrated loudness is -0.691 + 10 log10(energy): afg_loudness_lufs(energy), host only, -inf
+ * for 0.
+ *
+ * Gain.  T = 10^((target_lufs + 0.691) / 10), in double on the host; g = (float)sqrt(T / energy), double division and square
+ * root, both correctly rounded; peak is the largest |x| of the group's valid samples, a float32 and exact; with
+ * max_gain > 0, g = min(g, max_gain) (AFG_LOUDNESS_GAIN_CLAMPED when that lowers it); with max_peak > 0 and peak > 0,
+ * g = min(g, max_peak / peak), a float32 division (AFG_LOUDNESS_PEAK_CLAMPED likewise).  No block gated in -- a group
+ * shorter than 400 ms among them --: energy = 0, rel_threshold as computed (0 without a block above the absolute gate),
+ * g = 1 and AFG_LOUDNESS_UNGATED.  With apply, every valid element becomes y = x * g, one float32 product; in place
+ * (d_out == d_in, out_off == in_off) is allowed, other overlaps of what a launch reads and writes are not.  Nothing outside
+ * the valid elements is read or written.  valid == 0: nothing read, nothing written but the record: zero, gain 1,
+ * AFG_LOUDNESS_UNGATED.
+ *
+ * Contract.  An interval, like the filter's, not bits: the device evaluates the K-weighting in float64 exactly as
+ * afg_filter_hip evaluates a cascade (chunks of 16 from zero state, the scan), squares and adds in float64 in an order of
+ * its own -- the same for the same group wherever it stands.  With
+ *     e    = K_L * afg_filter_bound(the K-weighting) * max|x| of the group, K_L = AFG_LOUDNESS_K = 64 = AFG_FILTER_K: the
+ *            evaluation is the filter kernel's, operation for operation, and nothing is rounded to float32;
+ *     S_ij = the exact sum of squares of the K-weighted row i over block j;
+ *     c    = N + rows + 8, which bounds the additions on any path of any summation order,
+ * the delivered z^_j (d_blocks) lies within
+ *     |z_j - z^_j| <= B_j = (1 / N) * sum over i of G_i * (2 e sqrt(N S_ij) + N e^2) + c * 2^-53 * z^_j
+ * of the exact z_j.  A block's gate decision may differ from the exact one only where z^_j lies within its bound of the
+ * threshold -- B_j for Gamma_abs, B_j + 0.1 * mean B for Gamma_rel --; given equal gate sets,
+ * |energy - e^| <= mean of the gated-in B_j * (1 + 2^-50) (the means are summed with compensation), and the gain follows
+ * from the delivered energy by the definition's own operations.  A group holding a sample that is not finite has unspecified
+ * results of its own; every other group keeps the contract, and nothing outside the group's valid outputs is written.
+ *
+ * afg_loudness_layout fills first_sub and first_block of every group and the counts: a group with n_blocks > 0 has
+ * n_blocks + 3 sub-blocks of `step` samples per row, and every row of a group with valid > 0 takes its sub-block sums and
+ * one more double, its peak, in d_sub; blocks are numbered through the groups in order.  It returns 1, or 0 with
+ * afg_last_error set for parameters out of range or a NULL pointer.  afg_loudness_check_groups needs no device
+ * (same_plane: whether d_in == d_out): the parameters in range; rows 1 .. 8; reserved words 0; first_sub, first_block and
+ * the counts as the layout gives them; for a group with valid > 0, stride >= valid when rows > 1 and its rows inside
+ * [0, in_floats) and -- with apply -- [0, out_floats), offsets that would wrap included; and with apply no output row
+ * meeting another output row or any input row but its own at the same offset.  n_groups == 0 checks the parameters alone.
+ *
+ * afg_loudness_hip runs three launches on hip_stream, without atomics, without a workgroup waiting for another and
+ * without a host round trip: measure (one workgroup per row: the K-weighted signal is never written, only its sub-block sums
+ * and the row's peak, into d_sub, counts->n_sub doubles), gate (one wavefront per group: z^_j into d_blocks,
+ * counts->n_blocks doubles, and the record into d_stats, n_groups of them) and, with apply, the product.  d_groups is the
+ * device copy of the laid-out groups; the entry fetches it on hip_stream, waits for it and checks it as
+ * afg_loudness_check_groups does: anything but a pass is AFG_ERR_INVALID and nothing is written.  The planes are 4-byte
+ * aligned, d_groups, d_sub, d_blocks and d_stats 8-byte aligned; at most 2^31 - 1 groups a launch. */
+#define AFG_LOUDNESS_K            64
+#define AFG_LOUDNESS_UNGATED      1u   /* flags: no block gated in; energy 0, gain 1 */
+#define AFG_LOUDNESS_GAIN_CLAMPED 2u   /* flags: max_gain lowered the gain */
+#define AFG_LOUDNESS_PEAK_CLAMPED 4u   /* flags: max_peak lowered the gain */
+typedef struct afg_loudness_params {  /* 96 bytes */
+    uint32_t samplerate;          /* Hz, 8000 .. 192000 */
+    uint32_t apply;               /* 0: measure only; 1: also y = x * gain */
+    double   target_lufs;
+    float    max_peak;            /* 0: no ceiling */
+    float    max_gain;            /* linear; 0: none */
+    double   weights[8];          /* G_i; all zero: every row 1 */
+    uint32_t reserved[2];         /* 0 */
+} afg_loudness_params;
+typedef struct afg_loudness_group {   /* 64 bytes */
+    uint64_t in_off, out_off;     /* float index of row 0, element 0 in d_in / d_out */
+    uint64_t stride;              /* floats from one row to the next, in both planes; >= valid when rows > 1 */
+    uint64_t first_sub, first_block;  /* filled in by afg_loudness_layout */
+    uint32_t rows, valid;
+    uint32_t reserved[4];         /* 0 */
+} afg_loudness_group;
+typedef struct afg_loudness_counts { uint64_t n_sub, n_blocks; } afg_loudness_counts;
+typedef struct afg_loudness_stats {   /* 40 bytes, one per group */
+    double   energy, rel_threshold;
+    uint32_t n_blocks, n_abs, n_gated, flags;
+    float    peak, gain;
+} afg_loudness_stats;
+int afg_kweight_design(uint32_t samplerate, afg_filter_params *out);
+double afg_loudness_lufs(double energy);
+int afg_loudness_layout(afg_loudness_group *groups, uint64_t n_groups, const afg_loudness_params *params, afg_loudness_counts *counts);
+int afg_loudness_check_groups(const afg_loudness_group *groups, uint64_t n_groups, const afg_loudness_counts *counts,
+                              const afg_loudness_params *params, uint64_t in_floats, uint64_t out_floats, int same_plane);
+int afg_loudness_hip(uint64_t n_groups, const afg_loudness_group *d_groups, const afg_loudness_counts *counts,
+                     const afg_loudness_params *params, const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats,
+                     double *d_sub, double *d_blocks, afg_loudness_stats *d_stats, void *hip_stream);
+
+/* afg_batch_decode_resampled, then one afg_loudness_hip launch in place, one group per file exactly as
+ * afg_batch_decode_resampled_norm makes them: rows = min(channels, the file's channels), or 1 with mono, and `valid` as
+ * defined there; what lies behind `valid` stays as afg_batch_decode_resampled leaves it.  loudness->samplerate must equal
+ * opts->samplerate, and at most 8 channels.  A failed or refused file is a group with valid == 0: a zero slab, a zero record
+ * with gain 1.  stats (host, n_files records) may be NULL; it is filled when the launch has drained.  Sublists as in
+ * afg_batch_decode_resampled; the scratch for sub-block sums, block energies and records is pooled.  Checked before any
+ * device call, AFG_ERR_INVALID with afg_last_error set: everything afg_batch_decode_resampled checks, NULL loudness, its
+ * parameters, the two rates differing, more than 8 channels.  Statuses, messages and items[i] are
+ * afg_batch_decode_resampled's. */
+int afg_batch_decode_loudnorm(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
+                              const afg_loudness_params *loudness, float *d_out, afg_loudness_stats *stats, afg_batch_result *out);
+
 #ifdef __cplusplus
 }
 #endif
