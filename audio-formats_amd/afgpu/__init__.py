@@ -90,6 +90,10 @@ BIQUAD_KINDS = {"lowpass": 0, "highpass": 1, "bandpass": 2, "notch": 3, "allpass
 FILTER_ROW_DTYPE = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), ("frames", np.uint32), ("reserved", np.uint32)])
 assert FILTER_ROW_DTYPE.itemsize == 24
 STFT_COMPLEX, STFT_MAGNITUDE, STFT_POWER, STFT_LOG10 = 0, 1, 2, 3       # afg_stft_params.out_kind
+# afg_istft_row: one [n_bins, n_frames] slab of (re, im) pairs of afg_istft_hip and its out_frames samples
+ISTFT_ROW_DTYPE = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), ("first_tile", np.uint64), ("n_frames", np.uint32),
+                            ("in_pitch", np.uint32), ("out_first", np.uint32), ("out_frames", np.uint32)])
+assert ISTFT_ROW_DTYPE.itemsize == 40
 LOUDNESS_K = 64                                  # AFG_LOUDNESS_K
 LOUDNESS_UNGATED, LOUDNESS_GAIN_CLAMPED, LOUDNESS_PEAK_CLAMPED = 1, 2, 4     # afg_loudness_stats.flags
 
@@ -135,6 +139,7 @@ ABI_SYMBOLS = [
     "afg_stft_tile_frames", "afg_stft_layout", "afg_stft_check_rows", "afg_stft_hip", "afg_batch_decode_stft",
     "afg_biquad_design", "afg_filter_bound", "afg_filter_tile_frames", "afg_filter_check_rows", "afg_filter_hip", "afg_batch_decode_filtered",
     "afg_kweight_design", "afg_loudness_lufs", "afg_loudness_layout", "afg_loudness_check_groups", "afg_loudness_hip", "afg_batch_decode_loudnorm",
+    "afg_istft_tile_samples", "afg_istft_layout", "afg_istft_envelope_min", "afg_istft_check_rows", "afg_istft_hip",
 ]
 
 
@@ -295,6 +300,11 @@ class StftParams(C.Structure):
     """afg_stft_params (afg_stft_hip)."""
     _fields_ = [("n_fft", C.c_uint32), ("win_length", C.c_uint32), ("hop", C.c_uint32), ("center", C.c_uint32), ("pad_mode", C.c_uint32),
                 ("out_kind", C.c_uint32), ("log_floor", C.c_float), ("reserved", C.c_uint32)]
+
+
+class IstftParams(C.Structure):
+    """afg_istft_params (afg_istft_hip)."""
+    _fields_ = [("n_fft", C.c_uint32), ("win_length", C.c_uint32), ("hop", C.c_uint32), ("center", C.c_uint32), ("reserved", C.c_uint32 * 4)]
 
 
 class StftOpts(C.Structure):
@@ -696,6 +706,14 @@ def lib():
     L.afg_stft_check_rows.argtypes = [vp, u64, u64, C.POINTER(StftParams), u64, u64, u64]
     L.afg_stft_hip.argtypes = [u64, vp, u64, C.POINTER(StftParams), vp, u64, vp, u64, vp, u64, vp]
     L.afg_batch_decode_stft.argtypes = [vp, vp, C.c_int, C.POINTER(StftOpts), vp, C.POINTER(BatchResult)]
+    L.afg_istft_tile_samples.argtypes = [C.POINTER(IstftParams)]
+    L.afg_istft_tile_samples.restype = u32
+    L.afg_istft_layout.argtypes = [vp, u64, C.POINTER(IstftParams)]
+    L.afg_istft_layout.restype = u64
+    L.afg_istft_envelope_min.argtypes = [C.POINTER(IstftParams), u32, u32, u32]
+    L.afg_istft_envelope_min.restype = C.c_double
+    L.afg_istft_check_rows.argtypes = [vp, u64, u64, C.POINTER(IstftParams), u64, u64, u64]
+    L.afg_istft_hip.argtypes = [u64, vp, u64, C.POINTER(IstftParams), vp, u64, vp, u64, vp, u64, vp]
     _lib = L
     _sync_dev_options(L)
     return L
@@ -2467,6 +2485,113 @@ def batch_decode_stft(files, frames, samplerate=16000, n_fft=400, hop=160, win_l
 
     out, meta = _batch_tensor_call("batch_decode_stft", files, shape, out, first_frame, call)
     return (torch.view_as_complex(out) if prm.out_kind == STFT_COMPLEX else out), meta
+
+
+def istft_params(n_fft=400, hop=160, win_length=None, center=True):
+    """afg_istft_params with Whisper's framing as the default (win_length None: n_fft)."""
+    return IstftParams(int(n_fft), int(n_fft if win_length is None else win_length), int(hop), 1 if center else 0)
+
+
+def istft_tile_samples(params):
+    """afg_istft_tile_samples: the consecutive delivered samples of one row a workgroup of afg_istft_hip owns for these
+    parameters (it depends on n_fft and hop).  AfgError for parameters out of range."""
+    tile = int(lib().afg_istft_tile_samples(C.byref(params)))
+    if tile == 0:
+        raise AfgError(lib().afg_last_error().decode())
+    return tile
+
+
+def istft_layout(rows, params):
+    """afg_istft_layout: fills first_tile of an ISTFT_ROW_DTYPE array in place (tiles of istft_tile_samples); returns the
+    launch's tile count."""
+    assert rows.dtype == ISTFT_ROW_DTYPE and rows.flags.c_contiguous
+    return int(lib().afg_istft_layout(rows.ctypes.data, len(rows), C.byref(params)))
+
+
+def istft_envelope_min(params, n_frames, out_first, out_frames):
+    """afg_istft_envelope_min: the smallest window envelope D[t] over the delivered range of a record, summed in double from
+    the table's float32 window.  Host only.  AfgError for parameters or a range out of bounds."""
+    d = float(lib().afg_istft_envelope_min(C.byref(params), int(n_frames), int(out_first), int(out_frames)))
+    if d < 0.0:
+        raise AfgError(lib().afg_last_error().decode())
+    return d
+
+
+def istft_check_rows(rows, n_tiles, params, in_floats, table_floats, out_floats):
+    """afg_istft_check_rows: what afg_istft_hip checks before it launches, on host records.  AfgError when one fails."""
+    assert rows.dtype == ISTFT_ROW_DTYPE and rows.flags.c_contiguous
+    check(lib().afg_istft_check_rows(rows.ctypes.data, len(rows), int(n_tiles), C.byref(params), int(in_floats), int(table_floats),
+                                     int(out_floats)))
+
+
+def istft(n_rows, d_rows, n_tiles, params, d_in, in_floats, d_table, table_floats, d_out, out_floats, stream=None):
+    """Enqueue the inverse STFT kernel (afg_istft_hip) on device arrays: slabs of (re, im) pairs in STFT_COMPLEX's layout to
+    rows of samples, with mel_fft_tables' table and rows laid out by istft_layout.  The records are checked first (the call
+    waits for `stream` to read them): AfgError, and nothing written, when a check fails."""
+    check(lib().afg_istft_hip(int(n_rows), _ptr(d_rows), int(n_tiles), C.byref(params), _ptr(d_in), int(in_floats), _ptr(d_table),
+                              int(table_floats), _ptr(d_out), int(out_floats), _stream(stream)))
+
+
+_istft_tables = {}                                           # (device index, n_fft, win_length): the device table, made once and kept
+
+
+def istft_tensor(spec, n_fft=400, hop=160, win_length=None, center=True, length=None, first=0, valid_frames=None, out=None):
+    """The inverse STFT of every slab of a contiguous device tensor (afg_istft_hip, one launch on the current stream;
+    include/afg.h has the definition): spec is complex64 [..., n_bins, F] -- torch.stft's and batch_decode_stft(out_kind=
+    STFT_COMPLEX)'s layout -- or float32 [..., n_bins, F, 2]; the result is float32 [..., length], samples first .. first +
+    length of every line behind the centring pad.  length None: hop * (F - 1) when centred (torch.istft's default), the rest
+    of the line otherwise.  valid_frames: None, or one frame count per slab (the leading axes flattened): only that many
+    frames are read, and only the samples they make are written -- what lies behind them is left as it is (zero in a new
+    tensor).  out: None, or a contiguous float32 tensor [..., length].  Returns out.  AfgError when a record is refused,
+    for instance center=False with first=0, where the window envelope is zero."""
+    import torch
+    prm = istft_params(n_fft, hop, win_length, center)
+    istft_tile_samples(prm)                                  # (the parameters: AfgError says which)
+    if not spec.is_cuda or not spec.is_contiguous():
+        raise ValueError("istft_tensor: a contiguous device tensor")
+    if spec.dtype == torch.complex64 and spec.dim() >= 2:
+        flat, lead = torch.view_as_real(spec), tuple(spec.shape[:-2])
+    elif spec.dtype == torch.float32 and spec.dim() >= 3 and spec.shape[-1] == 2:
+        flat, lead = spec, tuple(spec.shape[:-3])
+    else:
+        raise ValueError("istft_tensor: complex64 [..., n_bins, F] or float32 [..., n_bins, F, 2]")
+    n_bins, F = int(flat.shape[-3]), int(flat.shape[-2])
+    if n_bins != prm.n_fft // 2 + 1 or F < 1:
+        raise ValueError(f"istft_tensor: n_fft {prm.n_fft} has {prm.n_fft // 2 + 1} bins, and at least one frame is needed")
+    pad, first = (prm.n_fft // 2 if center else 0), int(first)
+    line = lambda frames: prm.n_fft + prm.hop * (frames - 1)
+    if length is None:
+        length = prm.hop * (F - 1) if center else line(F) - first
+    length = int(length)
+    if first < 0 or length < 0 or pad + first + length > line(F):
+        raise ValueError(f"istft_tensor: samples {first} .. {first + length}, but {F} frames make {line(F) - pad} behind the pad")
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    if out is None:
+        out = (torch.zeros if valid_frames is not None else torch.empty)(lead + (length,), dtype=torch.float32, device=spec.device)
+    elif tuple(out.shape) != lead + (length,) or out.dtype != torch.float32 or out.device != spec.device or not out.is_contiguous():
+        raise ValueError(f"istft_tensor: out must be a contiguous float32 tensor of shape {lead + (length,)} on spec's device")
+    rows = np.zeros(n, ISTFT_ROW_DTYPE)
+    rows["in_off"] = np.arange(n, dtype=np.uint64) * np.uint64(2 * n_bins * F)
+    rows["out_off"] = np.arange(n, dtype=np.uint64) * np.uint64(length)
+    rows["n_frames"], rows["in_pitch"], rows["out_first"], rows["out_frames"] = F, F, first, length
+    if valid_frames is not None:
+        v = np.asarray(valid_frames.cpu() if hasattr(valid_frames, "cpu") else valid_frames).reshape(-1).astype(np.int64)
+        if v.size != n or (v < 0).any() or (v > F).any():
+            raise ValueError("istft_tensor: valid_frames holds one frame count per slab, 0 .. F")
+        rows["n_frames"] = v
+        reach = np.where(v > 0, (prm.hop * (v - 1) if center else prm.n_fft + prm.hop * (v - 1)) - first, 0)   # as `length`'s default
+        rows["out_frames"] = np.clip(reach, 0, length)
+    if n == 0 or length == 0:
+        return out
+    tiles = istft_layout(rows, prm)
+    with torch.cuda.device(spec.device):
+        key = (torch.cuda.current_device(), prm.n_fft, prm.win_length)
+        if key not in _istft_tables:
+            _istft_tables[key] = torch.from_numpy(mel_fft_tables(prm.n_fft, prm.win_length)).to(spec.device)
+        table = _istft_tables[key]
+        d_rows = torch.from_numpy(rows.view(np.uint8)).to(spec.device)
+        istft(n, d_rows, tiles, prm, flat, flat.numel(), table, table.numel(), out, out.numel(), torch.cuda.current_stream().cuda_stream)
+    return out
 
 
 def lds_fill(word=0x7fc00000, stream=None):

@@ -1,8 +1,9 @@
-// fft_frame.h -- the device-side pieces of the per-frame mixed-radix FFT that melspec_fft.hip (afg_melspec_fft_hip) and
-// stft.hip (afg_stft_hip) share: the n_fft the transform takes, its pass list, the butterflies of radix 2, 3, 4 and 5, one
-// Stockham autosort pass over a wavefront's LDS buffers, the wavefront-level ordering of that LDS traffic, one frame's run
-// through the passes (fft_frame) and a bin of the split pass (fft_split_bin).  The kernels keep their own tiling, fetch and
-// epilogue; what is here decides the bits of (re, im), and both kernels get the same.
+// fft_frame.h -- the device-side pieces of the per-frame mixed-radix FFT that melspec_fft.hip (afg_melspec_fft_hip),
+// stft.hip (afg_stft_hip) and istft.hip (afg_istft_hip) share: the n_fft the transform takes, its pass list, the butterflies
+// of radix 2, 3, 4 and 5, one Stockham autosort pass over a wavefront's LDS buffers, the wavefront-level ordering of that
+// LDS traffic, one frame's run through the passes (fft_frame; fft_frame_complex for complex input) and a bin of the split
+// pass, forwards and backwards (fft_split_bin, fft_unsplit_bin).  The kernels keep their own tiling, fetch and epilogue;
+// what is here decides the bits of (re, im), and the two forward kernels get the same.
 #pragma once
 #include "afg_common.h"
 
@@ -111,21 +112,13 @@ __device__ inline void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// One frame through the transform, by one wavefront in its own buffers `buf` (4 nc floats): fetch(i) is sample i of the frame
-// times its window value; an even n_fft packs z[j] = x[2j] + i x[2j+1] into half the length (the caller's split pass follows),
-// an odd n_fft runs the full length with a zero imaginary part.  Leaves the planes of the result in *zr, *zi (inside buf).
-template <typename Fetch>
-__device__ inline void fft_frame(const FftGeo &geo, uint32_t n_fft, float *buf, const float *__restrict__ tw, uint32_t lane, Fetch fetch,
-                                 const float **zr, const float **zi)
+// The passes over a wavefront's filled buffers `buf` (4 nc floats; planes 0 and 1 hold the input, the wavefront has synchronised
+// behind the fill): leaves the planes of the result in *zr, *zi (inside buf: the first pair after an even number of passes).
+__device__ inline void fft_passes(const FftGeo &geo, uint32_t n_fft, float *buf, const float *__restrict__ tw, uint32_t lane, const float **zr,
+                                  const float **zi)
 {
     const uint32_t nc = geo.nc;
     float *sr = buf, *si = buf + nc, *dr = buf + 2 * nc, *di = buf + 3 * nc;
-    wave_sync();                                                 // the frame before has read its result
-    if (geo.half)
-        for (uint32_t j = lane; j < nc; j += 64) { sr[j] = fetch(2 * j); si[j] = fetch(2 * j + 1); }
-    else
-        for (uint32_t j = lane; j < nc; j += 64) { sr[j] = fetch(j); si[j] = 0.0f; }
-    wave_sync();
     uint32_t ns = 1;
     for (uint32_t p = 0; p < geo.n_pass; p++) {
         const uint32_t R = geo.radix[p];
@@ -143,6 +136,37 @@ __device__ inline void fft_frame(const FftGeo &geo, uint32_t n_fft, float *buf, 
     *zr = sr; *zi = si;
 }
 
+// One frame through the transform, by one wavefront in its own buffers `buf` (4 nc floats): fetch(i) is sample i of the frame
+// times its window value; an even n_fft packs z[j] = x[2j] + i x[2j+1] into half the length (the caller's split pass follows),
+// an odd n_fft runs the full length with a zero imaginary part.  Leaves the planes of the result in *zr, *zi (inside buf).
+template <typename Fetch>
+__device__ inline void fft_frame(const FftGeo &geo, uint32_t n_fft, float *buf, const float *__restrict__ tw, uint32_t lane, Fetch fetch,
+                                 const float **zr, const float **zi)
+{
+    const uint32_t nc = geo.nc;
+    float *sr = buf, *si = buf + nc;
+    wave_sync();                                                 // the frame before has read its result
+    if (geo.half)
+        for (uint32_t j = lane; j < nc; j += 64) { sr[j] = fetch(2 * j); si[j] = fetch(2 * j + 1); }
+    else
+        for (uint32_t j = lane; j < nc; j += 64) { sr[j] = fetch(j); si[j] = 0.0f; }
+    wave_sync();
+    fft_passes(geo, n_fft, buf, tw, lane, zr, zi);
+}
+
+// The complex transform of length nc alone, for a caller with complex input (istft.hip): fetch(j) is value j, j < nc.
+template <typename Fetch>
+__device__ inline void fft_frame_complex(const FftGeo &geo, uint32_t n_fft, float *buf, const float *__restrict__ tw, uint32_t lane, Fetch fetch,
+                                         const float **zr, const float **zi)
+{
+    const uint32_t nc = geo.nc;
+    float *sr = buf, *si = buf + nc;
+    wave_sync();
+    for (uint32_t j = lane; j < nc; j += 64) { const cf v = fetch(j); sr[j] = v.re; si[j] = v.im; }
+    wave_sync();
+    fft_passes(geo, n_fft, buf, tw, lane, zr, zi);
+}
+
 // bin k of an even n_fft from the half-length result Z (the split pass): X[k] = E + W^k O with E = (Z[k] + conj Z[nc - k]) / 2,
 // O = -i (Z[k] - conj Z[nc - k]) / 2, W = e^{-2 pi i / n_fft}; k = 0 .. nc
 __device__ inline cf fft_split_bin(const float *zr, const float *zi, uint32_t nc, uint32_t k, const float *__restrict__ tw)
@@ -151,6 +175,16 @@ __device__ inline cf fft_split_bin(const float *zr, const float *zi, uint32_t nc
     const float a = zr[k1], b = zi[k1], c = zr[k2], d = zi[k2];
     const cf E = { 0.5f * (a + c), 0.5f * (b - d) }, O = { 0.5f * (b + d), -0.5f * (a - c) };
     return E + cmul(cf{ tw[2 * k], tw[2 * k + 1] }, O);
+}
+
+// the split pass backwards: Z[k], k = 1 .. nc - 1, of the half-length transform from X[k] = (a, b) and X[nc - k] = (c, d) of an
+// even n_fft, times s: E = s (X[k] + conj X[nc - k]), O = conj(W^k) s (X[k] - conj X[nc - k]), Z = E + i O.  (Z[0] comes from
+// the two real-only bins and is the caller's: s (re_0 + re_nc) + i s (re_0 - re_nc).)
+__device__ inline cf fft_unsplit_bin(cf Xk, cf Xm, float s, uint32_t k, const float *__restrict__ tw)
+{
+    const cf E = { s * (Xk.re + Xm.re), s * (Xk.im - Xm.im) };
+    const cf O = cmul(cf{ tw[2 * k], -tw[2 * k + 1] }, cf{ s * (Xk.re - Xm.re), s * (Xk.im + Xm.im) });
+    return { E.re - O.im, E.im + O.re };
 }
 
 }  // namespace

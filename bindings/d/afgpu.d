@@ -577,6 +577,17 @@ int afg_loudness_hip(ulong n_groups, const(afg_loudness_group)* d_groups, const(
                      double* d_sub, double* d_blocks, afg_loudness_stats* d_stats, void* hip_stream);
 int afg_batch_decode_loudnorm(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_resample_opts)* opts,
                               const(afg_loudness_params)* loudness, float* d_out, afg_loudness_stats* stats, afg_batch_result* out_);
+// the inverse of the linear spectrogram: AFG_STFT_COMPLEX's layout back to samples, overlap-add over the window envelope
+// (include/afg.h has the definition and the bound); the table is afg_mel_fft_tables'
+struct afg_istft_params { uint n_fft, win_length, hop, center; uint[4] reserved; }
+struct afg_istft_row { ulong in_off, out_off, first_tile; uint n_frames, in_pitch, out_first, out_frames; }
+uint afg_istft_tile_samples(const(afg_istft_params)* params);
+ulong afg_istft_layout(afg_istft_row* rows, ulong n_rows, const(afg_istft_params)* params);
+double afg_istft_envelope_min(const(afg_istft_params)* params, uint n_frames, uint out_first, uint out_frames);
+int afg_istft_check_rows(const(afg_istft_row)* rows, ulong n_rows, ulong n_tiles, const(afg_istft_params)* params, ulong in_floats,
+                         ulong table_floats, ulong out_floats);
+int afg_istft_hip(ulong n_rows, const(afg_istft_row)* d_rows, ulong n_tiles, const(afg_istft_params)* params, const(float)* d_in,
+                  ulong in_floats, const(float)* d_table, ulong table_floats, float* d_out, ulong out_floats, void* hip_stream);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

@@ -1915,6 +1915,84 @@ int afg_loudness_hip(uint64_t n_groups, const afg_loudness_group *d_groups, cons
 int afg_batch_decode_loudnorm(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
                               const afg_loudness_params *loudness, float *d_out, afg_loudness_stats *stats, afg_batch_result *out);
 
+/* The inverse of the linear spectrogram: from a complex spectrum in AFG_STFT_COMPLEX's layout -- masked or edited on the
+ * device, or any other -- back to a waveform, by the inverse real transform of every frame and the windowed overlap-add
+ * divided by the window envelope: torch.istft's value.  The reference has no such stage.  tests/istft_model.py holds the
+ * float64 definition and the interval below.
+ *
+ * Parameters (afg_istft_params, 32 bytes): n_fft 16 .. 2048 with prime factors 2, 3 and 5 only (anything else is
+ * AFG_ERR_UNSUPPORTED), win_length 1 .. n_fft, hop 1 .. n_fft, center 0 or 1, reserved zeros.  The window is the forward
+ * stage's: periodic Hann of win_length, w[j] = 0.5 - 0.5 cos(2 pi j / win_length), at n_lo = (n_fft - win_length) / 2 inside
+ * the frame.  The table is afg_mel_fft_tables' table unchanged: one device table serves afg_stft_hip and its inverse.
+ *
+ * Records (afg_istft_row, 40 bytes).  The input is AFG_STFT_COMPLEX's layout: the pair (re, im) of bin k, frame f lies at
+ * float in_off + 2 * (k * in_pitch + f), k < n_bins = n_fft / 2 + 1, f < n_frames <= in_pitch (in_pitch lets a padded batch
+ * tensor carry a frame count per row).  out_frames samples are written at out_off.
+ *
+ * Frame f, in float64:
+ *   x_f[j] = (1 / n_fft) (re_0 + [n_fft even] (-1)^j re_{n_fft/2}
+ *                         + 2 sum over 0 < k < n_fft / 2 of (re_k cos(2 pi k j / n_fft) - im_k sin(2 pi k j / n_fft)))
+ * (for odd n_fft the sum runs over 0 < k <= (n_fft - 1) / 2).  im of bin 0, and of bin n_fft / 2 for even n_fft, takes no
+ * part, as in torch.istft and every complex-to-real transform: a NaN or an infinity there changes nothing.
+ * Line.  n_frames frames make a line of L = n_fft + hop * (n_frames - 1) samples,
+ *   N[t] = sum over f of w[t - f hop - n_lo] x_f[t - f hop],    D[t] = sum over f of w[t - f hop - n_lo]^2,
+ * both over the frames whose window span (win_length samples from f hop + n_lo) holds t.  Delivered sample i of the record
+ * is N[t] / D[t] at t = pad + out_first + i, pad = center ? n_fft / 2 : 0, and pad + out_first + out_frames <= L must hold.
+ * torch.istft(..., center=True, length=n) is out_first = 0, out_frames = n.  Without centring the caller sets out_first past
+ * the window's zero: the Hann window starts at 0, so center = 0, out_first = 0 is refused, as torch refuses it.
+ * Envelope.  afg_istft_envelope_min: host only; the smallest D[t] over the delivered range of a record with these
+ * n_frames, out_first and out_frames (each at least 1, the range inside the line), summed in double from the float32 window
+ * of the table -- what the device divides by -- or a negative value with afg_last_error set for parameters out of range.
+ * A record whose minimum is below 1e-11 (torch.istft's figure) is refused with AFG_ERR_INVALID before the launch; the
+ * kernel divides unconditionally.  hop > win_length leaves samples under no window and is refused this way.
+ *
+ * Bound.  u = 2^-24, B = 8 ceil(log2 n_fft) + 8 (the forward path's), m = ceil(win_length / hop),
+ * A'_f = (1 / n_fft) sum over k of c_k (|re_k| + |im_k|) with c_k = 1 and im not counted for the real-only bins and c_k = 2
+ * otherwise, S[t] = sum over f of w A'_f over the frames that cover t.  Every delivered sample lies within
+ *   E[t] = (B + 2 m + 8) u S[t] / D[t]
+ * of the float64 value: to first order a frame sample carries B u A'_f from the transform as in the forward direction; the
+ * window product and the sum of at most m terms, in any fixed order, add m u S; D's squares and its sum add m u relative;
+ * the division one more u; the remaining 8 cover the float32 window in N and D, the 1 / n_fft scale and second-order terms.
+ * Locality and order.  The sum over frames for one sample runs in ascending frame order from +0.0f whatever the tile,
+ * wavefront or position of the row, without floating-point atomics: the same row gives the same bits wherever it stands in
+ * the batch and whichever tile a sample falls in.  A NaN in a part that is read, in frame f, makes NaN of exactly the
+ * delivered samples inside frame f's window span -- the one where w is 0 included, since 0 * NaN is NaN -- and of nothing
+ * else.  An all-zero spectrum gives +0.0f.  A record with out_frames = 0 writes nothing and reads nothing.  The kernel
+ * writes exactly out_frames floats per record and reads no input float outside the record's n_bins x n_frames pairs.  It
+ * does not listen to AFG_NUMERIC or afg_set_numeric_mode.
+ *
+ * afg_istft_tile_samples: host only; the consecutive delivered samples of one row a workgroup owns for these parameters (it
+ * depends on n_fft and hop), or 0 with afg_last_error set for parameters out of range.  afg_istft_layout: host only; gives
+ * every row its tiles (first_tile) and returns their count, the sum of ceil(out_frames / tile); 0 with afg_last_error set for
+ * parameters out of range.  afg_istft_check_rows: host only, needs no device; the checks afg_istft_hip makes before it
+ * launches, on a host copy of the records: parameters in range (AFG_ERR_UNSUPPORTED for the n_fft, AFG_ERR_INVALID
+ * otherwise); table_floats at least win_length + 2 * n_fft; first_tile and n_tiles as afg_istft_layout gives them; and for
+ * every record with output: n_frames >= 1; n_frames <= in_pitch; the slab's 2 * ((n_bins - 1) * in_pitch + n_frames) floats
+ * inside [0, in_floats); its out_frames floats inside [0, out_floats); pad + out_first + out_frames <= L; the envelope's
+ * minimum at least 1e-11.  afg_last_error says which.  afg_istft_hip runs every row in one launch, one workgroup per tile;
+ * the same checks come first (the entry fetches d_rows on hip_stream and waits for it), and on anything but a pass nothing
+ * is written. */
+typedef struct afg_istft_params {  /* 32 bytes */
+    uint32_t n_fft, win_length, hop, center;
+    uint32_t reserved[4];          /* 0 */
+} afg_istft_params;
+typedef struct afg_istft_row {     /* one [n_bins, n_frames] slab of pairs and its out_frames samples (40 bytes) */
+    uint64_t in_off;               /* float index of (re, im) of bin 0, frame 0 */
+    uint64_t out_off;              /* float index of the first output sample */
+    uint64_t first_tile;           /* filled in by afg_istft_layout */
+    uint32_t n_frames;             /* spectrum frames used */
+    uint32_t in_pitch;             /* frames per bin row of the slab, >= n_frames */
+    uint32_t out_first;            /* first delivered sample of the line, behind pad */
+    uint32_t out_frames;           /* samples written */
+} afg_istft_row;
+uint32_t afg_istft_tile_samples(const afg_istft_params *params);
+uint64_t afg_istft_layout(afg_istft_row *rows, uint64_t n_rows, const afg_istft_params *params);
+double afg_istft_envelope_min(const afg_istft_params *params, uint32_t n_frames, uint32_t out_first, uint32_t out_frames);
+int afg_istft_check_rows(const afg_istft_row *rows, uint64_t n_rows, uint64_t n_tiles, const afg_istft_params *params, uint64_t in_floats,
+                         uint64_t table_floats, uint64_t out_floats);
+int afg_istft_hip(uint64_t n_rows, const afg_istft_row *d_rows, uint64_t n_tiles, const afg_istft_params *params, const float *d_in,
+                  uint64_t in_floats, const float *d_table, uint64_t table_floats, float *d_out, uint64_t out_floats, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
