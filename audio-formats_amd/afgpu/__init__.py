@@ -94,6 +94,11 @@ STFT_COMPLEX, STFT_MAGNITUDE, STFT_POWER, STFT_LOG10 = 0, 1, 2, 3       # afg_st
 ISTFT_ROW_DTYPE = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), ("first_tile", np.uint64), ("n_frames", np.uint32),
                             ("in_pitch", np.uint32), ("out_first", np.uint32), ("out_frames", np.uint32)])
 assert ISTFT_ROW_DTYPE.itemsize == 40
+# afg_pvoc_row: one [n_bins, n_frames] slab of (re, im) pairs of afg_pvoc_hip and the [n_bins, out_frames] slab it makes
+PVOC_ROW_DTYPE = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), ("rate", np.float64), ("n_frames", np.uint32),
+                           ("in_pitch", np.uint32), ("out_frames", np.uint32), ("out_pitch", np.uint32), ("reserved", np.uint32, (2,))])
+assert PVOC_ROW_DTYPE.itemsize == 48
+PVOC_KA, PVOC_KP, PVOC_CHUNK, PVOC_TILE = 2, 52, 4, 256      # AFG_PVOC_*
 LOUDNESS_K = 64                                  # AFG_LOUDNESS_K
 LOUDNESS_UNGATED, LOUDNESS_GAIN_CLAMPED, LOUDNESS_PEAK_CLAMPED = 1, 2, 4     # afg_loudness_stats.flags
 
@@ -140,6 +145,7 @@ ABI_SYMBOLS = [
     "afg_biquad_design", "afg_filter_bound", "afg_filter_tile_frames", "afg_filter_check_rows", "afg_filter_hip", "afg_batch_decode_filtered",
     "afg_kweight_design", "afg_loudness_lufs", "afg_loudness_layout", "afg_loudness_check_groups", "afg_loudness_hip", "afg_batch_decode_loudnorm",
     "afg_istft_tile_samples", "afg_istft_layout", "afg_istft_envelope_min", "afg_istft_check_rows", "afg_istft_hip",
+    "afg_pvoc_out_frames", "afg_pvoc_bound", "afg_pvoc_check_rows", "afg_pvoc_hip",
 ]
 
 
@@ -305,6 +311,11 @@ class StftParams(C.Structure):
 class IstftParams(C.Structure):
     """afg_istft_params (afg_istft_hip)."""
     _fields_ = [("n_fft", C.c_uint32), ("win_length", C.c_uint32), ("hop", C.c_uint32), ("center", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+class PvocParams(C.Structure):
+    """afg_pvoc_params (afg_pvoc_hip)."""
+    _fields_ = [("n_fft", C.c_uint32), ("hop", C.c_uint32), ("reserved", C.c_uint32 * 6)]
 
 
 class StftOpts(C.Structure):
@@ -714,6 +725,12 @@ def lib():
     L.afg_istft_envelope_min.restype = C.c_double
     L.afg_istft_check_rows.argtypes = [vp, u64, u64, C.POINTER(IstftParams), u64, u64, u64]
     L.afg_istft_hip.argtypes = [u64, vp, u64, C.POINTER(IstftParams), vp, u64, vp, u64, vp, u64, vp]
+    L.afg_pvoc_out_frames.argtypes = [u32, C.c_double]
+    L.afg_pvoc_out_frames.restype = u32
+    L.afg_pvoc_bound.argtypes = [C.POINTER(PvocParams), u64]
+    L.afg_pvoc_bound.restype = C.c_double
+    L.afg_pvoc_check_rows.argtypes = [vp, u64, C.POINTER(PvocParams), u64, u64]
+    L.afg_pvoc_hip.argtypes = [u64, vp, C.POINTER(PvocParams), vp, u64, vp, u64, vp]
     _lib = L
     _sync_dev_options(L)
     return L
@@ -2535,7 +2552,7 @@ def istft(n_rows, d_rows, n_tiles, params, d_in, in_floats, d_table, table_float
 _istft_tables = {}                                           # (device index, n_fft, win_length): the device table, made once and kept
 
 
-def istft_tensor(spec, n_fft=400, hop=160, win_length=None, center=True, length=None, first=0, valid_frames=None, out=None):
+def istft_tensor(spec, n_fft=400, hop=160, win_length=None, center=True, length=None, first=0, valid_frames=None, out=None, _counts=None):
     """The inverse STFT of every slab of a contiguous device tensor (afg_istft_hip, one launch on the current stream;
     include/afg.h has the definition): spec is complex64 [..., n_bins, F] -- torch.stft's and batch_decode_stft(out_kind=
     STFT_COMPLEX)'s layout -- or float32 [..., n_bins, F, 2]; the result is float32 [..., length], samples first .. first +
@@ -2581,6 +2598,8 @@ def istft_tensor(spec, n_fft=400, hop=160, win_length=None, center=True, length=
         rows["n_frames"] = v
         reach = np.where(v > 0, (prm.hop * (v - 1) if center else prm.n_fft + prm.hop * (v - 1)) - first, 0)   # as `length`'s default
         rows["out_frames"] = np.clip(reach, 0, length)
+        if _counts is not None:                              # (time_stretch_tensor: fewer samples than the frames make)
+            rows["out_frames"] = np.minimum(rows["out_frames"], _counts)
     if n == 0 or length == 0:
         return out
     tiles = istft_layout(rows, prm)
@@ -2592,6 +2611,184 @@ def istft_tensor(spec, n_fft=400, hop=160, win_length=None, center=True, length=
         d_rows = torch.from_numpy(rows.view(np.uint8)).to(spec.device)
         istft(n, d_rows, tiles, prm, flat, flat.numel(), table, table.numel(), out, out.numel(), torch.cuda.current_stream().cuda_stream)
     return out
+
+
+def stft_tensor(wave, n_fft=400, hop=160, win_length=None, center=True, pad_mode=MEL_PAD_REFLECT, out_kind=STFT_COMPLEX, valid=None):
+    """The linear spectrogram of every row of a contiguous float32 device tensor [..., n] (afg_stft_hip, one launch on the
+    current stream; include/afg.h has the definition): the tensor-in counterpart of istft_tensor.  The result is
+    [..., n_bins, F] with F the frames n samples have: complex64 for STFT_COMPLEX (torch.stft's layout), float32 otherwise.
+    valid: None, or one sample count per row (the leading axes flattened), 0 .. n: row i is then framed as a row of valid[i]
+    samples (reflection at its own end), its F_i frames are packed at the front of its slab with a pitch of F_i frames, the
+    rest of the slab stays zero, and the call returns (tensor, frame counts).  The table is istft_tensor's, made once per
+    device and (n_fft, win_length) and kept.  AfgError when a record is refused."""
+    import torch
+    prm = stft_params(n_fft, hop, win_length, center, pad_mode, out_kind)
+    stft_tile_frames(prm)                                    # (the parameters: AfgError says which)
+    if not wave.is_cuda or not wave.is_contiguous() or wave.dtype != torch.float32 or wave.dim() < 1:
+        raise ValueError("stft_tensor: a contiguous float32 device tensor [..., n]")
+    lead, length = tuple(wave.shape[:-1]), int(wave.shape[-1])
+    mel = MelParams(prm.n_fft, prm.win_length, prm.hop, 1, prm.center, prm.pad_mode, MEL_POWER, 0.0)
+    F = mel_frames(mel, length)
+    if F == 0:
+        raise ValueError(f"stft_tensor: {length} samples hold no frame of n_fft {prm.n_fft}")
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    n_bins, comps = prm.n_fft // 2 + 1, 2 if prm.out_kind == STFT_COMPLEX else 1
+    shape = lead + (n_bins, F) + ((2,) if comps == 2 else ())
+    out = (torch.zeros if valid is not None else torch.empty)(shape, dtype=torch.float32, device=wave.device)
+    rows = np.zeros(n, MEL_ROW_DTYPE)
+    rows["in_off"] = np.arange(n, dtype=np.uint64) * np.uint64(length)
+    rows["out_off"] = np.arange(n, dtype=np.uint64) * np.uint64(comps * n_bins * F)
+    rows["in_frames"], rows["out_frames"] = length, F
+    if valid is not None:
+        v = np.asarray(valid.cpu() if hasattr(valid, "cpu") else valid).reshape(-1).astype(np.int64)
+        if v.size != n or (v < 0).any() or (v > length).any():
+            raise ValueError("stft_tensor: valid holds one sample count per row, 0 .. n")
+        rows["in_frames"] = v
+        rows["out_frames"] = [mel_frames(mel, int(c)) if c > 0 else 0 for c in v]
+    if n:
+        tiles = stft_layout(rows, prm)
+        with torch.cuda.device(wave.device):
+            key = (torch.cuda.current_device(), prm.n_fft, prm.win_length)
+            if key not in _istft_tables:
+                _istft_tables[key] = torch.from_numpy(mel_fft_tables(prm.n_fft, prm.win_length)).to(wave.device)
+            table = _istft_tables[key]
+            d_rows = torch.from_numpy(rows.view(np.uint8)).to(wave.device)
+            stft(n, d_rows, tiles, prm, wave, wave.numel(), table, table.numel(), out, out.numel(), torch.cuda.current_stream().cuda_stream)
+    res = torch.view_as_complex(out) if comps == 2 else out
+    return res if valid is None else (res, rows["out_frames"].astype(np.int64))
+
+
+def pvoc_params(n_fft=400, hop=160):
+    """afg_pvoc_params with Whisper's framing as the default."""
+    return PvocParams(int(n_fft), int(hop))
+
+
+def pvoc_out_frames(n_frames, rate):
+    """afg_pvoc_out_frames: the steps t >= 0 with fl(t * rate) < n_frames -- the frames a slab of n_frames frames stretches
+    to at `rate`.  Host only.  AfgError for arguments out of range."""
+    n = int(lib().afg_pvoc_out_frames(int(n_frames), float(rate)))
+    if n == 0:
+        raise AfgError(lib().afg_last_error().decode())
+    return n
+
+
+def pvoc_bound(params, t):
+    """afg_pvoc_bound: K_A * 2^-24 + K_P * 2^-53 * pi * (t + 1), the bracket of the interval E_t = m_t * bracket."""
+    b = float(lib().afg_pvoc_bound(C.byref(params), int(t)))
+    if b < 0.0:
+        raise AfgError(lib().afg_last_error().decode())
+    return b
+
+
+def pvoc_layout(rows, params):
+    """Fills out_frames of a PVOC_ROW_DTYPE array in place from n_frames and rate (pvoc_out_frames; 0 for a record without
+    frames) and returns their sum.  afg_pvoc_hip needs no tiles, so there is nothing else to lay out."""
+    assert rows.dtype == PVOC_ROW_DTYPE and rows.flags.c_contiguous
+    for r in rows:
+        r["out_frames"] = pvoc_out_frames(r["n_frames"], r["rate"]) if r["n_frames"] else 0
+    return int(rows["out_frames"].sum(dtype=np.uint64))
+
+
+def pvoc_check_rows(rows, params, in_floats, out_floats):
+    """afg_pvoc_check_rows: what afg_pvoc_hip checks before it launches, on host records.  AfgError when one fails."""
+    assert rows.dtype == PVOC_ROW_DTYPE and rows.flags.c_contiguous
+    check(lib().afg_pvoc_check_rows(rows.ctypes.data, len(rows), C.byref(params), int(in_floats), int(out_floats)))
+
+
+def pvoc(n_rows, d_rows, params, d_in, in_floats, d_out, out_floats, stream=None):
+    """Enqueue the phase-vocoder kernel (afg_pvoc_hip) on device arrays: slabs of (re, im) pairs in STFT_COMPLEX's layout to
+    slabs of the same layout, stretched by each record's rate.  The records are checked first (the call waits for `stream`
+    to read them): AfgError, and nothing written, when a check fails."""
+    check(lib().afg_pvoc_hip(int(n_rows), _ptr(d_rows), C.byref(params), _ptr(d_in), int(in_floats), _ptr(d_out), int(out_floats),
+                             _stream(stream)))
+
+
+def _pvoc_slabs(who, flat, lead, n_bins, F, rate, frames, pitch, prm, out):
+    """One afg_pvoc_hip launch over the slabs of `flat` (float32 [..., n_bins, F, 2]): slab i holds frames[i] frames at a pitch
+    of pitch[i].  Returns (out as float32 [..., n_bins, F_out, 2], the frame counts)."""
+    import torch
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    rates = np.broadcast_to(np.asarray(rate.cpu() if hasattr(rate, "cpu") else rate, dtype=np.float64).reshape(-1), (n,)) if n else np.zeros(0)
+    rows = np.zeros(n, PVOC_ROW_DTYPE)
+    rows["in_off"] = np.arange(n, dtype=np.uint64) * np.uint64(2 * n_bins * F)
+    rows["rate"], rows["n_frames"], rows["in_pitch"] = rates, frames, pitch
+    pvoc_layout(rows, prm)                                   # (AfgError for a rate out of range)
+    counts = rows["out_frames"].astype(np.int64)
+    most = int(counts.max()) if n else 0
+    if out is None:
+        out = torch.zeros(lead + (n_bins, most, 2), dtype=torch.float32, device=flat.device)
+    else:
+        if out.dtype == torch.complex64:
+            out = torch.view_as_real(out)
+        if out.dtype != torch.float32 or out.device != flat.device or not out.is_contiguous() or tuple(out.shape[:-2]) != lead + (n_bins,) \
+                or out.shape[-1] != 2 or out.shape[-2] < most:
+            raise ValueError(f"{who}: out must be a contiguous tensor [..., {n_bins}, at least {most}] of complex64 (or float32 pairs) on spec's device")
+        if (counts != out.shape[-2]).any():
+            out.zero_()                                      # zero behind each slab's own frames
+    P = int(out.shape[-2])
+    rows["out_off"], rows["out_pitch"] = np.arange(n, dtype=np.uint64) * np.uint64(2 * n_bins * P), P
+    if n and most:
+        with torch.cuda.device(flat.device):
+            d_rows = torch.from_numpy(rows.view(np.uint8)).to(flat.device)
+            pvoc(n, d_rows, prm, flat, flat.numel(), out, out.numel(), torch.cuda.current_stream().cuda_stream)
+    return out, counts
+
+
+def phase_vocoder_tensor(spec, rate, n_fft=400, hop=160, valid_frames=None, out=None):
+    """The phase-vocoder time stretch of every slab of a contiguous device tensor (afg_pvoc_hip, one launch on the current
+    stream; include/afg.h has the definition -- torchaudio's phase_vocoder with the phase summed in float64): spec is
+    complex64 [..., n_bins, F] or float32 [..., n_bins, F, 2]; rate is a number or one per slab (the leading axes flattened),
+    1/64 .. 64: above 1 is faster and shorter.  valid_frames: None, or one frame count per slab, 0 .. F.  Slab i comes out with
+    pvoc_out_frames(its frames, its rate) frames; out (None: a new tensor) is [..., n_bins, the largest of them] or longer,
+    of spec's kind, and is zero behind each slab's own frames.  Returns (out, the frame counts)."""
+    import torch
+    prm = pvoc_params(n_fft, hop)
+    pvoc_check_rows(np.zeros(0, PVOC_ROW_DTYPE), prm, 0, 0)  # (the parameters: AfgError says which)
+    if not spec.is_cuda or not spec.is_contiguous():
+        raise ValueError("phase_vocoder_tensor: a contiguous device tensor")
+    if spec.dtype == torch.complex64 and spec.dim() >= 2:
+        flat, lead, cplx = torch.view_as_real(spec), tuple(spec.shape[:-2]), True
+    elif spec.dtype == torch.float32 and spec.dim() >= 3 and spec.shape[-1] == 2:
+        flat, lead, cplx = spec, tuple(spec.shape[:-3]), False
+    else:
+        raise ValueError("phase_vocoder_tensor: complex64 [..., n_bins, F] or float32 [..., n_bins, F, 2]")
+    n_bins, F = int(flat.shape[-3]), int(flat.shape[-2])
+    if n_bins != prm.n_fft // 2 + 1 or F < 1:
+        raise ValueError(f"phase_vocoder_tensor: n_fft {prm.n_fft} has {prm.n_fft // 2 + 1} bins, and at least one frame is needed")
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    frames = np.full(n, F, np.int64)
+    if valid_frames is not None:
+        frames = np.asarray(valid_frames.cpu() if hasattr(valid_frames, "cpu") else valid_frames).reshape(-1).astype(np.int64)
+        if frames.size != n or (frames < 0).any() or (frames > F).any():
+            raise ValueError("phase_vocoder_tensor: valid_frames holds one frame count per slab, 0 .. F")
+    res, counts = _pvoc_slabs("phase_vocoder_tensor", flat, lead, n_bins, F, rate, frames, F, prm, out)
+    return (torch.view_as_complex(res) if cplx else res), counts
+
+
+def time_stretch_tensor(wave, rate, n_fft=400, hop=160, win_length=None, valid=None):
+    """Stretch every row of a contiguous float32 device tensor [..., n] in time without changing its pitch: stft_tensor
+    (complex, centred, reflect) -> the phase vocoder -> istft_tensor with valid_frames -- three launches on the current stream
+    and no host round trip beyond the record uploads.  rate is a number or one per row, 1/64 .. 64 (above 1: faster, shorter);
+    valid: None, or one sample count per row (each above n_fft / 2, for the reflection).  Row i delivers
+    min(floor(n_i / rate_i + 0.5), hop * (F_out_i - 1)) samples, zeros behind them.  Returns (the tensor [..., the longest
+    of them], the lengths)."""
+    import torch
+    lead, length = tuple(wave.shape[:-1]), int(wave.shape[-1])
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    if valid is None:
+        spec = stft_tensor(wave, n_fft, hop, win_length, True, MEL_PAD_REFLECT, STFT_COMPLEX)
+        samples, frames = np.full(n, length, np.int64), np.full(n, spec.shape[-1], np.int64)
+    else:
+        spec, frames = stft_tensor(wave, n_fft, hop, win_length, True, MEL_PAD_REFLECT, STFT_COMPLEX, valid)
+        samples = np.asarray(valid.cpu() if hasattr(valid, "cpu") else valid).reshape(-1).astype(np.int64)
+    flat = torch.view_as_real(spec)
+    n_bins, F = int(flat.shape[-3]), int(flat.shape[-2])
+    stretched, counts = _pvoc_slabs("time_stretch_tensor", flat, lead, n_bins, F, rate, frames, np.maximum(frames, 1), pvoc_params(n_fft, hop), None)
+    rates = np.broadcast_to(np.asarray(rate.cpu() if hasattr(rate, "cpu") else rate, dtype=np.float64).reshape(-1), (n,))
+    lengths = np.minimum(np.floor(samples / rates + 0.5).astype(np.int64), int(hop) * np.maximum(counts - 1, 0))
+    most = int(lengths.max()) if n else 0
+    y = istft_tensor(torch.view_as_complex(stretched), n_fft, hop, win_length, True, length=most, valid_frames=counts, _counts=lengths)
+    return y, lengths.reshape(lead)
 
 
 def lds_fill(word=0x7fc00000, stream=None):

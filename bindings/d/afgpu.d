@@ -588,6 +588,16 @@ int afg_istft_check_rows(const(afg_istft_row)* rows, ulong n_rows, ulong n_tiles
                          ulong table_floats, ulong out_floats);
 int afg_istft_hip(ulong n_rows, const(afg_istft_row)* d_rows, ulong n_tiles, const(afg_istft_params)* params, const(float)* d_in,
                   ulong in_floats, const(float)* d_table, ulong table_floats, float* d_out, ulong out_floats, void* hip_stream);
+// the phase-vocoder time stretch between afg_stft_hip and afg_istft_hip: AFG_STFT_COMPLEX's layout in and out, a rate per
+// slab, the phase summed in double (include/afg.h has the definition, the interval and the constants)
+enum AFG_PVOC_KA = 2, AFG_PVOC_KP = 52, AFG_PVOC_CHUNK = 4, AFG_PVOC_TILE = 256;
+struct afg_pvoc_params { uint n_fft, hop; uint[6] reserved; }
+struct afg_pvoc_row { ulong in_off, out_off; double rate; uint n_frames, in_pitch, out_frames, out_pitch; uint[2] reserved; }
+uint afg_pvoc_out_frames(uint n_frames, double rate);
+double afg_pvoc_bound(const(afg_pvoc_params)* params, ulong t);
+int afg_pvoc_check_rows(const(afg_pvoc_row)* rows, ulong n_rows, const(afg_pvoc_params)* params, ulong in_floats, ulong out_floats);
+int afg_pvoc_hip(ulong n_rows, const(afg_pvoc_row)* d_rows, const(afg_pvoc_params)* params, const(float)* d_in, ulong in_floats,
+                 float* d_out, ulong out_floats, void* hip_stream);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

@@ -1993,6 +1993,99 @@ int afg_istft_check_rows(const afg_istft_row *rows, uint64_t n_rows, uint64_t n_
 int afg_istft_hip(uint64_t n_rows, const afg_istft_row *d_rows, uint64_t n_tiles, const afg_istft_params *params, const float *d_in,
                   uint64_t in_floats, const float *d_table, uint64_t table_floats, float *d_out, uint64_t out_floats, void *hip_stream);
 
+/* The phase-vocoder time stretch: between afg_stft_hip and afg_istft_hip, a complex spectrum is stretched along time by a
+ * rate per slab -- torchaudio's phase_vocoder (TimeStretch; librosa.effects.time_stretch's core), as one pass with the phase
+ * summed in float64.  The reference has no such stage.  tests/pvoc_model.py holds the definition in long double and the
+ * interval below.
+ *
+ * Input: a slab in AFG_STFT_COMPLEX's layout, the pair (re, im) of bin k, frame f at float in_off + 2 * (k * in_pitch + f),
+ * k < n_bins = n_fft / 2 + 1, f < n_frames <= in_pitch.  Output: the same layout with out_pitch and out_frames.
+ * Parameters (afg_pvoc_params, 32 bytes): n_fft 2 .. 65536 (no factor rule: nothing is transformed), hop 1 .. n_fft,
+ * reserved zeros.  Records (afg_pvoc_row, 48 bytes): in_off, out_off, rate (a double, finite, 1/64 <= rate <= 64), n_frames
+ * 1 .. 2^24, in_pitch, out_frames, out_pitch, reserved zeros.
+ *
+ * Steps.  s_t = fl(t * rate), the one IEEE double product of the integer t and the record's rate (the library is built with
+ * -ffp-contract=off, and the kernel writes the product as __dmul_rn, which is never fused); i_t = floor(s_t);
+ * a_t = s_t - i_t, which is exact.  afg_pvoc_out_frames(n_frames, rate): host only; the number of t >= 0 with s_t < n_frames
+ * -- ceil(n_frames / rate), corrected by at most one where the rounded product disagrees -- or 0 with afg_last_error set for
+ * arguments out of range.  A record's out_frames is 0 or exactly that number; with 0 it reads nothing and writes nothing
+ * (and only its rate and reserved words are looked at).  The steps go through the rounded product on purpose: floor is
+ * discontinuous, and over the real product two evaluations could pick different frame pairs for some rates.
+ *
+ * Per bin k, over the real numbers from the float32 inputs:
+ *   th_f = atan2(im_f, re_f), f < n_frames (IEEE atan2, signed zeros included, as torch.angle has it);
+ *   |X_f| = sqrt(re_f^2 + im_f^2); frame n_frames is one frame of (+0, +0), only ever read as i_t + 1;
+ *   w_k  = 2 pi hop k / n_fft -- for even n_fft torchaudio's linspace(0, pi hop, n_bins)[k]; for odd n_fft it is the bin's
+ *          true advance per hop, which torchaudio's figure (pi hop k / (n_bins - 1)) is not;
+ *   d_t  = th_{i_t + 1} - th_{i_t} - w_k,   p_t = d_t - 2 pi round(d_t / 2 pi) + w_k,   ph_t = th_0 + sum over s < t of p_s,
+ *   m_t  = a_t |X_{i_t + 1}| + (1 - a_t) |X_{i_t}|,   Y_t = (m_t cos ph_t, m_t sin ph_t), delivered as float32.
+ * Only ph_t modulo 2 pi reaches the result: round's tie rule is free, and so is where multiples of 2 pi are dropped.
+ *
+ * Contract: an interval, not bits.  With u = 2^-24 and v = 2^-53 every delivered component lies within
+ *     E_t = m_t * (K_A * u + K_P * v * pi * (t + 1)),   K_A = AFG_PVOC_KA = 2,  K_P = AFG_PVOC_KP = 52
+ * of the model's value; afg_pvoc_bound(params, t) returns the bracket (host only; negative with afg_last_error set for
+ * parameters out of range).  The accounting, counted from csrc/pvoc.hip's operations before its first run:
+ *   K_A  the delivered product is rounded once to float32 (u, relative to |Y| <= m_t); the second u covers the float64
+ *        roundings of the magnitude (below) many times over.  (Below float32's normal range a rounding is 2^-150 absolute;
+ *        the interval is stated for m_t >= 2^-100.)
+ *   K_P  in units of v * pi of phase.  The device keeps every phase in turns (radians / 2 pi), where a value of at most half a
+ *        turn rounds by at most v / 2 turn = v * pi radians: one unit; x - rint(x) is then the wrap, and it is exact, as are
+ *        the reduction of the carry at every tile and the one in front of sincospi.  Accuracy of the device library: no page
+ *        of it is installed with the toolkit, so the assumption is the OpenCL full-profile limits its functions are written
+ *        to: double atan2 6 ulp, sinpi / cospi 4 ulp, sqrt correctly rounded; an ulp of x is at most 2 v |x|.
+ *        Per summed step s < t (34):  the two atan2, 6 ulp of at most half a turn each: 2 * 12;  their products with
+ *        1 / (2 pi), the constant's rounding and the product's: 2 * 2;  th_{i+1} - th_i, at most one turn: 2;  minus the
+ *        advance, at most 1.5 turns: 3;  the advance itself, w = centred((hop k) mod n_fft) / n_fft, one division: 1.
+ *        Additions, each v times its result, a result of n terms being at most n half-turns (18 (t + 1)):  the chunk sums
+ *        (3 deep) and the wavefront scan (6 deep), every level over disjoint terms, all tiles: 9;  the carry's addition per
+ *        tile, (T + 1) half-turns each: 2;  carry + lanes below: 1;  the steps below in the chunk: 3;  adding them: 1;
+ *        adding the advance's share, up to t + 2 half-turns: 2.
+ *        Once (22, under the 34 the step t itself does not spend):  th_0 as above: 14;  the advance's share
+ *        centred((hop k t) mod n_fft) * (1 / n_fft), exact integers and two roundings: 2;  sincospi, 4 ulp of at most 1,
+ *        8 v <= 3 v pi: 3;  the magnitude -- the sum of two exact squares, the square root, 1 - a, two products, their sum,
+ *        the product with cos or sin: at most 8 v relative <= 3 v pi: 3.
+ *        34 t + 18 (t + 1) + 22 <= 52 (t + 1).
+ * The phase does not grow: its floating sum holds wrapped differences only and is reduced at every tile, so (t + 1) pi, not
+ * (t + 1) pi (hop + 1), is the size behind the bound.  m_t = 0 delivers a zero of either sign, with no error allowed.  A NaN or
+ * an infinity in bin k, frame f may change the outputs of bin k at the steps with i_t + 1 >= f, and nothing else; every other
+ * bin and record keeps the contract.  The same slab gives the same bits wherever it stands in a batch: a row's order of
+ * summation is fixed by t alone (chunks of AFG_PVOC_CHUNK steps per lane, tiles of AFG_PVOC_TILE steps, one wavefront per
+ * row).  The kernel writes exactly 2 * n_bins * out_frames floats per record, at the pitch, and reads nothing outside the
+ * record's n_bins x n_frames pairs.  In place is not allowed: the planes must not overlap.  It does not listen to
+ * AFG_NUMERIC or afg_set_numeric_mode.  The launch needs no tiles, so there is no layout helper: a workgroup is four rows.
+ *
+ * afg_pvoc_check_rows: host only, needs no device; the checks afg_pvoc_hip makes before it launches, on a host copy of the
+ * records: n_fft and hop in range and the parameters' reserved words 0; per record the reserved words 0; rate finite and
+ * in 1/64 .. 64 (a NaN is refused); and for a record with out_frames > 0: n_frames 1 .. 2^24; n_frames <= in_pitch;
+ * out_frames as afg_pvoc_out_frames gives it; out_frames <= out_pitch; the slab's 2 * ((n_bins - 1) * in_pitch + n_frames)
+ * floats inside [0, in_floats) and its 2 * ((n_bins - 1) * out_pitch + out_frames) floats inside [0, out_floats), offsets
+ * that would wrap included.  Everything is AFG_ERR_INVALID, and afg_last_error says which.  n_rows == 0 checks the
+ * parameters alone.  afg_pvoc_hip runs every record in one launch; it fetches d_rows (8-byte aligned; the planes 4-byte)
+ * on hip_stream, waits, makes the same checks, and on anything but a pass writes nothing. */
+#define AFG_PVOC_KA    2
+#define AFG_PVOC_KP    52
+#define AFG_PVOC_CHUNK 4      /* consecutive steps a lane sums */
+#define AFG_PVOC_TILE  256    /* steps between two reductions of the carry */
+typedef struct afg_pvoc_params {   /* 32 bytes */
+    uint32_t n_fft, hop;
+    uint32_t reserved[6];          /* 0 */
+} afg_pvoc_params;
+typedef struct afg_pvoc_row {      /* one [n_bins, n_frames] slab of pairs and the [n_bins, out_frames] slab it makes (48 bytes) */
+    uint64_t in_off;               /* float index of (re, im) of bin 0, frame 0 in d_in */
+    uint64_t out_off;              /* likewise in d_out */
+    double   rate;                 /* input frames per output step, 1/64 .. 64 */
+    uint32_t n_frames;             /* spectrum frames used, 1 .. 2^24 */
+    uint32_t in_pitch;             /* frames per bin row of the input slab, >= n_frames */
+    uint32_t out_frames;           /* 0, or afg_pvoc_out_frames(n_frames, rate) */
+    uint32_t out_pitch;            /* frames per bin row of the output slab, >= out_frames */
+    uint32_t reserved[2];          /* 0 */
+} afg_pvoc_row;
+uint32_t afg_pvoc_out_frames(uint32_t n_frames, double rate);
+double afg_pvoc_bound(const afg_pvoc_params *params, uint64_t t);
+int afg_pvoc_check_rows(const afg_pvoc_row *rows, uint64_t n_rows, const afg_pvoc_params *params, uint64_t in_floats, uint64_t out_floats);
+int afg_pvoc_hip(uint64_t n_rows, const afg_pvoc_row *d_rows, const afg_pvoc_params *params, const float *d_in, uint64_t in_floats,
+                 float *d_out, uint64_t out_floats, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
