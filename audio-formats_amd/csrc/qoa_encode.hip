@@ -10,9 +10,11 @@
 // smallest squared error (ties: the smallest scalefactor, as the reference's strict `<` keeps the first), and the
 // winner's LMS state and slice bits are broadcast.  The early `break` of the reference (:361) only skips work on
 // trials that can no longer win; results are identical.  Optional float input is converted as
-// QOAEncoder.writeSamples does (:632-636).  Integer arithmetic wraps exactly as in D: output bytes are the
-// reference's.
+// QOAEncoder.writeSamples does (:632-636, narrowed to 16 bits as its release build does: qoa_sample.h).  Integer
+// arithmetic wraps exactly as in D -- sums that can pass 2^31 are formed in unsigned, as in qoa_lms.hip -- so the
+// output bytes are the reference's.
 #include "afg_common.h"
+#include "qoa_sample.h"
 
 namespace {
 
@@ -41,8 +43,7 @@ __device__ __forceinline__ int clamp_s16(int v) { return v < -32768 ? -32768 : (
 __device__ __forceinline__ int load_sample(const int16_t *__restrict__ pi, const float *__restrict__ pf, uint64_t at)
 {
     if (pi) return pi[at];
-    const double x = pf[at];                               // QOAEncoder.writeSamples, qoa.d:632-636
-    return (int)(32768.5 + x * 32767.0) - 32768;
+    return afg_qoa_sample((double)pf[at]);                 // QOAEncoder.writeSamples, qoa.d:632-636
 }
 
 // One pass of the wavefront: lane group g (16 lanes) encodes channel `c` of stream `st` when `act`; the groups of a
@@ -109,7 +110,9 @@ __device__ __forceinline__ void encode_pass(const afg_qoa_enc_stream &st, int c,
             for (int j = 0; j < kSliceLen; j++) {
                 if (j < slice_len) {
                     const int sample = x[j];
-                    const int predicted = (tw[0] * th[0] + tw[1] * th[1] + tw[2] * th[2] + tw[3] * th[3]) >> 13;
+                    // a losing trial's weights are not bounded: the sum wraps, as in D (and in qoa_lms.hip)
+                    const int predicted = (int)((unsigned)tw[0] * (unsigned)th[0] + (unsigned)tw[1] * (unsigned)th[1] +
+                                                (unsigned)tw[2] * (unsigned)th[2] + (unsigned)tw[3] * (unsigned)th[3]) >> 13;
                     const int residual = sample - predicted;
                     int n = (int)((unsigned)residual * (unsigned)recip + (1u << 15)) >> 16;        // qoa_div, :263-269
                     n = n + ((residual > 0) - (residual < 0)) - ((n > 0) - (n < 0));
@@ -122,7 +125,7 @@ __device__ __forceinline__ void encode_pass(const afg_qoa_enc_stream &st, int c,
                     err += (uint64_t)(e * e);
                     const int delta = dequantized >> 4;                                          // qoa_lms_update, :241-254
 #pragma unroll
-                    for (int i = 0; i < 4; i++) tw[i] += th[i] < 0 ? -delta : delta;
+                    for (int i = 0; i < 4; i++) tw[i] = (int)((unsigned)tw[i] + (unsigned)(th[i] < 0 ? -delta : delta));
                     th[0] = th[1]; th[1] = th[2]; th[2] = th[3]; th[3] = reconstructed;
                     slice = (slice << 3) | (uint64_t)quantized;
                 }

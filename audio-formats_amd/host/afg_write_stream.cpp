@@ -11,6 +11,7 @@
 #include "afg_stage.h"
 #include "afg_write_stream.h"
 #include "../csrc/afg_common.h"
+#include "../csrc/qoa_sample.h"
 
 #include <algorithm>
 #include <cstring>
@@ -227,16 +228,17 @@ template <typename T> int write_any(afg_stream *s, const T *in, int frames)
         const size_t n = (size_t)frames * (size_t)w->channels;
         if (w->format == AFG_FORMAT_QOA) {
             if (sizeof(T) == sizeof(double) && !w->qoa_int) {
-                // doubles are converted in double (qoa.d:632-634): what was queued as floats follows, by the same expression
+                // doubles are converted in double (qoa.d:632-634): what was queued as floats follows, by the same function
+                // the kernel converts floats with (csrc/qoa_sample.h)
                 w->qoa_i16.resize(w->qoa_f32.size());
-                for (size_t i = 0; i < w->qoa_f32.size(); i++) w->qoa_i16[i] = (int16_t)((int)(32768.5 + (double)w->qoa_f32[i] * 32767.0) - 32768);
+                for (size_t i = 0; i < w->qoa_f32.size(); i++) w->qoa_i16[i] = afg_qoa_sample((double)w->qoa_f32[i]);
                 std::vector<float>().swap(w->qoa_f32);
                 w->qoa_int = true;
             }
             if (w->qoa_int) {
                 const size_t at = w->qoa_i16.size();
                 w->qoa_i16.resize(at + n);
-                for (size_t i = 0; i < n; i++) w->qoa_i16[at + i] = (int16_t)((int)(32768.5 + (double)in[i] * 32767.0) - 32768);
+                for (size_t i = 0; i < n; i++) w->qoa_i16[at + i] = afg_qoa_sample((double)in[i]);
             } else {
                 w->qoa_f32.insert(w->qoa_f32.end(), (const float *)(const void *)in, (const float *)(const void *)in + n);
             }

@@ -641,8 +641,15 @@ typedef struct afg_qoa_enc_stream {
 /* Size in bytes of the QOA file for `samples` frames of `channels` channels (file header + frames). */
 uint64_t afg_qoa_encoded_size(uint32_t samples, uint32_t channels);
 
-/* Exactly one of d_pcm_i16 / d_pcm_f32 is given; floats are converted as QOAEncoder.writeSamples does
- * (qoa.d:632-636: (int)(32768.5 + x * 32767.0) - 32768, |x| <= 1).  Descriptors must respect the ranges above. */
+/* Exactly one of d_pcm_i16 / d_pcm_f32 is given.  Descriptors must respect the ranges above.
+ *
+ * A float (or, through the write stream, double) sample x of any value, beyond full scale, infinite or NaN included,
+ * becomes the int16 sample s that a release build of QOAEncoder.writeSamples (qoa.d:632-636) makes of it on x86-64:
+ *     v = 32768.5 + (double)x * 32767.0
+ *     t = trunc(v) if -2147483649 < v < 2147483648, else INT32_MIN (NaN falls here)
+ *     s = (int16)(uint16)((uint32)t - 32768u), the low 16 bits in two's complement
+ * so 1.0 is 32767, -1.0 is -32767, and 1.0001f wraps to -32766; nothing clamps.  The kernel, afg_write_samples_float,
+ * afg_write_samples_double and afg_batch_encode all convert by this one definition (csrc/qoa_sample.h). */
 int afg_qoa_encode_hip(uint32_t n_streams, const afg_qoa_enc_stream *d_streams, const int16_t *d_pcm_i16,
                        const float *d_pcm_f32, uint8_t *d_out, void *hip_stream);
 
@@ -798,7 +805,8 @@ int afg_batch_decode_to_device(const uint8_t *const *data, const size_t *length,
  *        reports every WAV finalize as failed (wav.d:604); this library does not.
  *   QOA  writes queue frames; finalize encodes the whole stream with one afg_qoa_encode_hip call -- the bytes of the
  *        reference's frame-by-frame writes, since the LMS state runs through the stream either way.  Doubles are
- *        converted in double (qoa.d:632-634).
+ *        converted in double (qoa.d:632-634); floats and doubles alike by the definition at afg_qoa_encode_hip, so a
+ *        value beyond full scale wraps the same way whichever call wrote it.
  * afg_open_to_memory: the first write whose bytes would pass max_length writes nothing, returns 0 and sets the error
  * state; for QOA the bound is checked at finalize.  A write after finalize returns 0 and sets the error state (the
  * reference asserts). */

@@ -88,6 +88,22 @@ def test_qoa_batch_items_are_the_stream_writers(gpu):
     assert [s["bytes"] for s in shuffled] == [got[i]["bytes"] for i in order]
 
 
+def test_qoa_batch_items_at_the_encoder_edges(gpu):
+    """Floats beyond full scale, a 3-channel item beside a narrow one and an item of no frames (the inputs of
+    test_qoa_encode_edges_gpu.py): the stream writer's bytes, which are the oracle's on the int16 that afg.h defines."""
+    import oraclelib
+    from test_qoa_encode_edges_gpu import c1_streams, float_to_s16, make_pcm
+    over, short = c1_streams()
+    wide = (make_pcm(np.random.default_rng(404), 50, 3) / 32767.0).astype(np.float32)
+    inputs = [(over, 48000), (wide, 44100), (np.zeros((0, 2), np.float32), 8000), (short, 48000)]
+    got = afgpu.batch_encode(inputs, afgpu.FORMAT_QOA)
+    for k, ((x, rate), it) in enumerate(zip(inputs, got)):
+        assert it["status"] == 0, (k, it["message"])
+        assert it["bytes"] == qoa_single(x, rate), (k, x.shape)
+        assert it["bytes"] == oraclelib.qoa_encode(float_to_s16(x), rate)[0].tobytes(), (k, x.shape)
+    assert got[2]["bytes"] == b"qoaf" + bytes(4)
+
+
 def test_bad_items_keep_to_themselves(gpu):
     rng = np.random.default_rng(30)
     good = (noise(rng, 500, 2), 44100)
