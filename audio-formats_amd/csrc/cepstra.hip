@@ -27,9 +27,7 @@
 // Bounds: every record is checked on the host before the launch (afg_cep_check_rows); the kernel relies on it.  It reads
 // in[in_off + m * F + t] for m < n_mels and t < F only, dct[0 .. n_ceps * n_mels) only, and writes
 // out[out_off + (p * n_ceps + q) * F + t] for p <= delta_order, q < n_ceps and t < F only.
-#include "afg_common.h"
-
-#include <vector>
+#include "afg_records.h"
 
 namespace {
 
@@ -52,11 +50,7 @@ __global__ __launch_bounds__(kThreads) void cepstra_kernel(uint32_t n_rows, cons
     extern __shared__ __attribute__((aligned(16))) float sh_t[];    // [waves][n_mels][QB]: every wave's chunk of the table
     const uint64_t tile = blockIdx.x;
     // the record of this tile: the last one whose first tile is <= tile (records without frames have no tiles)
-    uint32_t lo = 0, hi = n_rows - 1;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (rows[mid].first_tile <= tile) lo = mid; else hi = mid - 1;
-    }
+    const uint32_t lo = afg::last_at_or_before(rows, n_rows, tile, &afg_cep_row::first_tile);
     const afg_cep_row r = rows[lo];
     if (r.first_tile > tile) return;
     const uint64_t first = (tile - r.first_tile) * kTile;        // first frame of the tile
@@ -161,11 +155,7 @@ int check_args(uint64_t n_rows, const afg_cep_row *d_rows, uint64_t n_tiles, con
         afg::set_error("afg_cepstra_hip: the planes must be 4-byte aligned, the records 8-byte aligned");
         return AFG_ERR_INVALID;
     }
-    if (n_rows > 0xffffffffull || n_tiles > 0x7fffffffull) {
-        afg::set_error("afg_cepstra_hip: at most 2^32 - 1 records and 2^31 - 1 tiles per launch");
-        return AFG_ERR_INVALID;
-    }
-    return AFG_OK;
+    return afg::launch_caps("afg_cepstra_hip", "records", n_rows, n_tiles);
 }
 
 }  // namespace
@@ -201,15 +191,8 @@ extern "C" int afg_cepstra_hip(uint64_t n_rows, const afg_cep_row *d_rows, uint6
     if (n_rows == 0) return AFG_OK;
     if (int rc = check_args(n_rows, d_rows, n_tiles, d_in, d_dct, d_out)) return rc;
     if (int rc = afg::require_device()) return rc;
-    // the records as the kernel will see them (whatever wrote them was queued on this stream)
-    try {
-        std::vector<afg_cep_row> h((size_t)n_rows);
-        AFG_HIP_CHECK(hipMemcpyAsync(h.data(), d_rows, (size_t)n_rows * sizeof(afg_cep_row), hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-        AFG_HIP_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));
-        return afg::cepstra_launch(h.data(), n_rows, d_rows, n_tiles, params, d_in, in_floats, d_dct, dct_floats, d_out, out_floats,
+    return afg::with_host_records(d_rows, n_rows, (hipStream_t)hip_stream, [&](const afg_cep_row *h) {
+        return afg::cepstra_launch(h, n_rows, d_rows, n_tiles, params, d_in, in_floats, d_dct, dct_floats, d_out, out_floats,
                                    (hipStream_t)hip_stream);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    });
 }

@@ -21,9 +21,7 @@
 //
 // Bounds: every span is checked on the host before the launch (check_spans below); the kernel relies on it -- a copy
 // span reads floats [in_off, in_off + count) only and writes rows k < out_channels at t in [0, frames) only.
-#include "afg_common.h"
-
-#include <vector>
+#include "afg_records.h"
 
 namespace {
 
@@ -116,11 +114,7 @@ __global__ __launch_bounds__(kThreads) void collate_kernel(uint32_t n_spans, con
 {
     const uint64_t t = blockIdx.x;
     // the span of tile t: the last one whose first tile is <= t (spans without samples have no tiles)
-    uint32_t lo = 0, hi = n_spans - 1;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (spans[mid].first_tile <= t) lo = mid; else hi = mid - 1;
-    }
+    const uint32_t lo = afg::last_at_or_before(spans, n_spans, t, &afg_collate_span::first_tile);
     const afg_collate_span sp = spans[lo];
     if (sp.first_tile > t) return;
     const uint64_t s0 = (t - sp.first_tile) * kTile;             // first sample of the tile within the span
@@ -203,12 +197,12 @@ int check_spans(const afg_collate_span *sp, uint64_t n_spans, uint64_t n_tiles, 
             afg::set_error("afg_collate_hip: span %llu: |first_frame| must be below 2^61", (unsigned long long)k);
             return AFG_ERR_INVALID;
         }
-        if (s.count && (!have_in || s.count > in_floats || s.in_off > in_floats - s.count)) {
+        if (s.count && (!have_in || !afg::rows_inside(s.in_off, 1, 0, s.count, in_floats))) {
             afg::set_error("afg_collate_hip: span %llu: the run leaves the input (%llu floats)", (unsigned long long)k, (unsigned long long)in_floats);
             return AFG_ERR_INVALID;
         }
         const uint64_t slab = (uint64_t)s.out_channels * s.frames;        // < 2^48
-        if (slab > out_floats || s.out_off > out_floats - slab) {
+        if (!afg::rows_inside(s.out_off, 1, 0, slab, out_floats)) {
             afg::set_error("afg_collate_hip: span %llu: the slab leaves the output (%llu floats)", (unsigned long long)k, (unsigned long long)out_floats);
             return AFG_ERR_INVALID;
         }
@@ -231,11 +225,7 @@ int check_args(uint64_t n_spans, const afg_collate_span *d_spans, uint64_t n_til
         afg::set_error("afg_collate_hip: the planes must be 4-byte aligned");
         return AFG_ERR_INVALID;
     }
-    if (n_spans > 0xffffffffull || n_tiles > 0x7fffffffull) {
-        afg::set_error("afg_collate_hip: at most 2^32 - 1 spans and 2^31 - 1 tiles per launch");
-        return AFG_ERR_INVALID;
-    }
-    return AFG_OK;
+    return afg::launch_caps("afg_collate_hip", "spans", n_spans, n_tiles);
 }
 
 }  // namespace
@@ -270,14 +260,7 @@ extern "C" int afg_collate_hip(uint64_t n_spans, const afg_collate_span *d_spans
     if (n_spans == 0) return AFG_OK;
     if (int rc = check_args(n_spans, d_spans, n_tiles, d_in, in_floats, d_out)) return rc;
     if (int rc = afg::require_device()) return rc;
-    // the spans as the kernel will see them (whatever wrote them was queued on this stream)
-    try {
-        std::vector<afg_collate_span> h((size_t)n_spans);
-        AFG_HIP_CHECK(hipMemcpyAsync(h.data(), d_spans, (size_t)n_spans * sizeof(afg_collate_span), hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-        AFG_HIP_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));
-        return afg::collate_launch(h.data(), n_spans, d_spans, n_tiles, d_in, in_floats, d_out, out_floats, (hipStream_t)hip_stream);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    return afg::with_host_records(d_spans, n_spans, (hipStream_t)hip_stream, [&](const afg_collate_span *h) {
+        return afg::collate_launch(h, n_spans, d_spans, n_tiles, d_in, in_floats, d_out, out_floats, (hipStream_t)hip_stream);
+    });
 }

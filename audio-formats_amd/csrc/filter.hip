@@ -26,7 +26,7 @@
 // Bounds: every row is checked on the host before the launch (afg_filter_check_rows); the kernel relies on it.  It reads
 // in[in_off + e] and writes out[out_off + e] for e < frames only, d_state[(row * n_sections + s) * 4 ..+ 4) for rows with
 // frames, the cascade's table inside n_sections * 300 doubles.
-#include "afg_common.h"
+#include "afg_records.h"
 
 #include <map>
 #include <mutex>
@@ -276,14 +276,7 @@ extern "C" int afg_filter_hip(uint64_t n_rows, const afg_filter_row *d_rows, con
     if (n_rows == 0) return AFG_OK;
     if (int rc = check_args(n_rows, d_rows, d_in, in_floats, d_out, out_floats, d_state)) return rc;
     if (int rc = afg::require_device()) return rc;
-    // the rows as the kernel will see them (whatever wrote them was queued on this stream)
-    try {
-        std::vector<afg_filter_row> h((size_t)n_rows);
-        AFG_HIP_CHECK(hipMemcpyAsync(h.data(), d_rows, (size_t)n_rows * sizeof(afg_filter_row), hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-        AFG_HIP_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));
-        return afg::filter_launch(h.data(), n_rows, d_rows, params, d_in, in_floats, d_out, out_floats, d_state, (hipStream_t)hip_stream);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    return afg::with_host_records(d_rows, n_rows, (hipStream_t)hip_stream, [&](const afg_filter_row *h) {
+        return afg::filter_launch(h, n_rows, d_rows, params, d_in, in_floats, d_out, out_floats, d_state, (hipStream_t)hip_stream);
+    });
 }

@@ -38,7 +38,7 @@
 // Bounds: every row is checked on the host before the launch (check_rows below); the kernel relies on it.  It reads
 // in[in_off + 2 (k in_pitch + f)] and the float behind it for k < n_bins, f < n_frames only, table[0 .. win_length + 2 n_fft)
 // only, and writes out[out_off .. out_off + out_frames) only.  No atomics, no inline assembly.
-#include "afg_common.h"
+#include "afg_records.h"
 #include "fft_frame.h"
 
 #include <cmath>
@@ -97,11 +97,7 @@ __global__ __launch_bounds__(kThreads) void istft_kernel(uint32_t n_rows, const 
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const uint64_t tile = blockIdx.x;
     // the row of this tile: the last one whose first tile is <= tile (rows without output have no tiles)
-    uint32_t lo = 0, hi = n_rows - 1;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (rows[mid].first_tile <= tile) lo = mid; else hi = mid - 1;
-    }
+    const uint32_t lo = afg::last_at_or_before(rows, n_rows, tile, &afg_istft_row::first_tile);
     const afg_istft_row r = rows[lo];
     if (r.first_tile > tile) return;
     const uint64_t i0 = (tile - r.first_tile) * tile_samples;   // first delivered sample of the tile
@@ -292,11 +288,11 @@ int check_rows(const afg_istft_row *rows, uint64_t n_rows, uint64_t n_tiles, con
         if (r.n_frames < 1) { afg::set_error("afg_istft_hip: row %llu: %u samples of no frame", kk, r.out_frames); return AFG_ERR_INVALID; }
         if (r.n_frames > r.in_pitch) { afg::set_error("afg_istft_hip: row %llu: n_frames %u above in_pitch %u", kk, r.n_frames, r.in_pitch); return AFG_ERR_INVALID; }
         const uint64_t need = 2 * ((n_bins - 1) * r.in_pitch + r.n_frames);                                // < 2^44
-        if (r.in_off > in_floats || need > in_floats - r.in_off) {
+        if (!afg::rows_inside(r.in_off, 1, 0, need, in_floats)) {
             afg::set_error("afg_istft_hip: row %llu: the slab's %llu floats leave the input (%llu floats)", kk, (unsigned long long)need, (unsigned long long)in_floats);
             return AFG_ERR_INVALID;
         }
-        if (r.out_off > out_floats || r.out_frames > out_floats - r.out_off) {
+        if (!afg::rows_inside(r.out_off, 1, 0, r.out_frames, out_floats)) {
             afg::set_error("afg_istft_hip: row %llu: the row's %u samples leave the output (%llu floats)", kk, r.out_frames, (unsigned long long)out_floats);
             return AFG_ERR_INVALID;
         }
@@ -331,11 +327,7 @@ int check_args(uint64_t n_rows, const afg_istft_row *d_rows, uint64_t n_tiles, c
         afg::set_error("afg_istft_hip: the planes must be 4-byte aligned");
         return AFG_ERR_INVALID;
     }
-    if (n_rows > 0xffffffffull || n_tiles > 0x7fffffffull) {
-        afg::set_error("afg_istft_hip: at most 2^32 - 1 rows and 2^31 - 1 tiles per launch");
-        return AFG_ERR_INVALID;
-    }
-    return AFG_OK;
+    return afg::launch_caps("afg_istft_hip", "rows", n_rows, n_tiles);
 }
 
 }  // namespace
@@ -398,16 +390,10 @@ extern "C" int afg_istft_hip(uint64_t n_rows, const afg_istft_row *d_rows, uint6
     if (int rc = check_args(n_rows, d_rows, n_tiles, d_in, d_table, d_out)) return rc;
     if (int rc = afg::require_device()) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
-    // the rows as the kernel will see them (whatever wrote them was queued on this stream)
-    try {
-        std::vector<afg_istft_row> h((size_t)n_rows);
-        AFG_HIP_CHECK(hipMemcpyAsync(h.data(), d_rows, (size_t)n_rows * sizeof(afg_istft_row), hipMemcpyDeviceToHost, stream));
-        AFG_HIP_CHECK(hipStreamSynchronize(stream));
-        if (int rc = check_rows(h.data(), n_rows, n_tiles, *params, in_floats, table_floats, out_floats)) return rc;
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    if (int rc = afg::with_host_records(d_rows, n_rows, stream, [&](const afg_istft_row *h) {
+            return check_rows(h, n_rows, n_tiles, *params, in_floats, table_floats, out_floats);
+        }))
+        return rc;
     if (n_tiles == 0) return AFG_OK;
     const IstftGeo g = istft_geo(*params);
     static_assert((size_t)kLdsBudget <= 160 * 1024, "LDS budget");

@@ -25,7 +25,7 @@
 // read in[in_off + r * stride + e] and write out[out_off + r * stride + e] for r < rows and e < valid only, the group's
 // doubles of d_sub ([first_sub, first_sub + rows * (n_sub + 1)) with n_sub its sub-blocks per row) and of d_blocks
 // ([first_block, first_block + n_blocks)), its record, and the K-weighting's table of 2 * 300 doubles.
-#include "afg_common.h"
+#include "afg_records.h"
 
 #include <algorithm>
 #include <cmath>
@@ -455,15 +455,8 @@ extern "C" int afg_loudness_hip(uint64_t n_groups, const afg_loudness_group *d_g
     if (n_groups == 0) return AFG_OK;
     if (int rc = check_args(n_groups, d_groups, counts, params, d_in, in_floats, d_out, out_floats, d_sub, d_blocks, d_stats)) return rc;
     if (int rc = afg::require_device()) return rc;
-    // the groups as the kernels will see them (whatever wrote them was queued on this stream)
-    try {
-        std::vector<afg_loudness_group> h((size_t)n_groups);
-        AFG_HIP_CHECK(hipMemcpyAsync(h.data(), d_groups, (size_t)n_groups * sizeof(afg_loudness_group), hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-        AFG_HIP_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));
-        return afg::loudness_launch(h.data(), n_groups, d_groups, counts, params, d_in, in_floats, d_out, out_floats, d_sub, d_blocks, d_stats,
+    return afg::with_host_records(d_groups, n_groups, (hipStream_t)hip_stream, [&](const afg_loudness_group *h) {
+        return afg::loudness_launch(h, n_groups, d_groups, counts, params, d_in, in_floats, d_out, out_floats, d_sub, d_blocks, d_stats,
                                     (hipStream_t)hip_stream);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    });
 }

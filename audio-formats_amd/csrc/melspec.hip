@@ -32,9 +32,7 @@
 // Bounds: every row is checked on the host before the launch (check_rows below); the kernel relies on it.  It reads
 // in[in_off + g] for 0 <= g < in_frames only, basis[0 .. win_length * ld) and filters[0 .. n_mels * n_bins) only, and writes
 // out[out_off .. out_off + n_mels * out_frames) only.
-#include "afg_common.h"
-
-#include <vector>
+#include "mel_rows.h"
 
 namespace {
 
@@ -85,11 +83,7 @@ __global__ __launch_bounds__(kThreads) void melspec_kernel(uint32_t n_rows, cons
     float *const X = lds, *const P = lds + geo.x_floats;
     const uint64_t tile = blockIdx.x;
     // the row of this tile: the last one whose first tile is <= tile (rows without output have no tiles)
-    uint32_t lo = 0, hi = n_rows - 1;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (rows[mid].first_tile <= tile) lo = mid; else hi = mid - 1;
-    }
+    const uint32_t lo = afg::last_at_or_before(rows, n_rows, tile, &afg_mel_row::first_tile);
     const afg_mel_row r = rows[lo];
     if (r.first_tile > tile) return;
     const uint64_t t0 = (tile - r.first_tile) * F;              // first frame of the tile
@@ -233,40 +227,8 @@ int check_rows(const afg_mel_row *rows, uint64_t n_rows, uint64_t n_tiles, const
                        (unsigned long long)p.n_mels * (p.n_fft / 2 + 1));
         return AFG_ERR_INVALID;
     }
-    uint64_t tiles = 0;
-    for (uint64_t k = 0; k < n_rows; k++) {
-        const afg_mel_row &r = rows[k];
-        const unsigned long long kk = (unsigned long long)k;
-        if (r.first_tile != tiles) {
-            afg::set_error("afg_melspec_hip: row %llu: first_tile %llu, afg_mel_layout gives %llu", kk, (unsigned long long)r.first_tile, (unsigned long long)tiles);
-            return AFG_ERR_INVALID;
-        }
-        tiles += tiles_of(r, g.F);
-        if (r.in_frames && (r.in_off > in_floats || r.in_frames > in_floats - r.in_off)) {
-            afg::set_error("afg_melspec_hip: row %llu: the row leaves the input (%llu floats)", kk, (unsigned long long)in_floats);
-            return AFG_ERR_INVALID;
-        }
-        if (r.out_frames == 0) continue;
-        const uint32_t most = max_frames_of(p, r.in_frames);
-        if (r.out_frames > most) {
-            afg::set_error("afg_melspec_hip: row %llu: out_frames %u, but %u samples have %u frames", kk, r.out_frames, r.in_frames, most);
-            return AFG_ERR_INVALID;
-        }
-        if (p.pad_mode == AFG_MEL_PAD_REFLECT && pad && r.in_frames <= pad) {
-            afg::set_error("afg_melspec_hip: row %llu: reflect padding of %u samples needs more than %u samples in the row (%u)", kk, pad, pad, r.in_frames);
-            return AFG_ERR_INVALID;
-        }
-        const uint64_t need = (uint64_t)p.n_mels * r.out_frames;
-        if (r.out_off > out_floats || need > out_floats - r.out_off) {
-            afg::set_error("afg_melspec_hip: row %llu: the row's %llu floats leave the output (%llu floats)", kk, (unsigned long long)need, (unsigned long long)out_floats);
-            return AFG_ERR_INVALID;
-        }
-    }
-    if (tiles != n_tiles) {
-        afg::set_error("afg_melspec_hip: n_tiles %llu, afg_mel_layout gives %llu", (unsigned long long)n_tiles, (unsigned long long)tiles);
-        return AFG_ERR_INVALID;
-    }
-    return AFG_OK;
+    return afg::check_mel_rows("afg_melspec_hip", "afg_mel_layout", rows, n_rows, n_tiles, g.F, p.pad_mode == AFG_MEL_PAD_REFLECT ? pad : 0, p.n_mels,
+                               in_floats, out_floats, [&](uint32_t in_frames) { return max_frames_of(p, in_frames); });
 }
 
 // what can be said without the rows
@@ -281,11 +243,7 @@ int check_args(uint64_t n_rows, const afg_mel_row *d_rows, uint64_t n_tiles, con
         afg::set_error("afg_melspec_hip: the planes must be 4-byte aligned");
         return AFG_ERR_INVALID;
     }
-    if (n_rows > 0xffffffffull || n_tiles > 0x7fffffffull) {
-        afg::set_error("afg_melspec_hip: at most 2^32 - 1 rows and 2^31 - 1 tiles per launch");
-        return AFG_ERR_INVALID;
-    }
-    return AFG_OK;
+    return afg::launch_caps("afg_melspec_hip", "rows", n_rows, n_tiles);
 }
 
 template <int G>
@@ -360,15 +318,8 @@ extern "C" int afg_melspec_hip(uint64_t n_rows, const afg_mel_row *d_rows, uint6
     if (n_rows == 0) return AFG_OK;
     if (int rc = check_args(n_rows, d_rows, n_tiles, d_in, d_basis, d_filters, d_out)) return rc;
     if (int rc = afg::require_device()) return rc;
-    // the rows as the kernel will see them (whatever wrote them was queued on this stream)
-    try {
-        std::vector<afg_mel_row> h((size_t)n_rows);
-        AFG_HIP_CHECK(hipMemcpyAsync(h.data(), d_rows, (size_t)n_rows * sizeof(afg_mel_row), hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-        AFG_HIP_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));
-        return afg::melspec_launch(h.data(), n_rows, d_rows, n_tiles, params, d_in, in_floats, d_basis, basis_floats, d_filters, filters_floats,
+    return afg::with_host_records(d_rows, n_rows, (hipStream_t)hip_stream, [&](const afg_mel_row *h) {
+        return afg::melspec_launch(h, n_rows, d_rows, n_tiles, params, d_in, in_floats, d_basis, basis_floats, d_filters, filters_floats,
                                    d_out, out_floats, (hipStream_t)hip_stream);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    });
 }

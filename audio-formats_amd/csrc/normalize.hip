@@ -20,14 +20,12 @@
 // Bounds: every group is checked on the host before the launch (afg_norm_check_groups); the kernels rely on it.  They
 // read in[in_off + r * stride + e] and write out[out_off + r * stride + e] for r < rows and e < valid only, partials
 // [0, n_tiles) and stats [0, n_groups).
-#include "afg_common.h"
-
-#include <vector>
+#include "afg_records.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr uint32_t kTile = 4096;                                // floats; 16 per lane
+constexpr uint32_t kTile = afg::kPlaneTile;                      // floats; 16 per lane
 constexpr uint32_t kKeyPosInf = 0xff800000u, kKeyNegInf = 0x007fffffu;
 
 struct Partial { double sum, sumsq; float mn, mx; uint32_t pad[2]; };
@@ -99,12 +97,7 @@ template <int D> __device__ __forceinline__ void tree_step(Acc &a)
 __device__ __forceinline__ bool find_tile(uint32_t n_groups, const afg_norm_group *__restrict__ groups, uint64_t tile, afg_norm_group *g,
                                           uint32_t *gi, uint64_t *at, uint32_t *n)
 {
-    // the last group whose first tile is <= tile (groups without floats have no tiles)
-    uint32_t lo = 0, hi = n_groups - 1;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (groups[mid].first_tile <= tile) lo = mid; else hi = mid - 1;
-    }
+    const uint32_t lo = afg::last_at_or_before(groups, n_groups, tile, &afg_norm_group::first_tile);   // (groups without floats have no tiles)
     *g = groups[lo];
     *gi = lo;
     if (g->first_tile > tile || g->valid == 0) return false;
@@ -278,11 +271,7 @@ int check_args(uint64_t n_groups, const afg_norm_group *d_groups, uint64_t n_til
         afg::set_error("afg_normalize_hip: the planes must be 4-byte aligned, the records, partials and statistics 8-byte aligned");
         return AFG_ERR_INVALID;
     }
-    if (n_groups > 0xffffffffull || n_tiles > 0x7fffffffull) {
-        afg::set_error("afg_normalize_hip: at most 2^32 - 1 groups and 2^31 - 1 tiles per launch");
-        return AFG_ERR_INVALID;
-    }
-    return AFG_OK;
+    return afg::launch_caps("afg_normalize_hip", "groups", n_groups, n_tiles);
 }
 
 }  // namespace
@@ -314,15 +303,8 @@ extern "C" int afg_normalize_hip(uint64_t n_groups, const afg_norm_group *d_grou
     if (n_groups == 0) return AFG_OK;
     if (int rc = check_args(n_groups, d_groups, n_tiles, params, d_in, d_out, d_partials, d_stats)) return rc;
     if (int rc = afg::require_device()) return rc;
-    // the groups as the kernels will see them (whatever wrote them was queued on this stream)
-    try {
-        std::vector<afg_norm_group> h((size_t)n_groups);
-        AFG_HIP_CHECK(hipMemcpyAsync(h.data(), d_groups, (size_t)n_groups * sizeof(afg_norm_group), hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-        AFG_HIP_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));
-        return afg::normalize_launch(h.data(), n_groups, d_groups, n_tiles, params, d_in, in_floats, d_out, out_floats, d_partials, d_stats,
+    return afg::with_host_records(d_groups, n_groups, (hipStream_t)hip_stream, [&](const afg_norm_group *h) {
+        return afg::normalize_launch(h, n_groups, d_groups, n_tiles, params, d_in, in_floats, d_out, out_floats, d_partials, d_stats,
                                      (hipStream_t)hip_stream);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    });
 }

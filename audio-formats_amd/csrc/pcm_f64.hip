@@ -17,7 +17,7 @@
 //   f32             v_cvt_f64_f32: exact, denormals kept, a quiet NaN keeps sign and payload (top mantissa bits), a
 //                   signalling NaN comes out quiet with its sign.
 //   f64             the 64 bits moved through integer registers.
-#include "afg_common.h"
+#include "afg_records.h"
 
 namespace {
 
@@ -123,11 +123,7 @@ __global__ __launch_bounds__(kThreads) void pcm_to_f64_kernel(uint32_t n_spans, 
 {
     const uint64_t t = blockIdx.x;
     // the span of tile t: the last one whose first tile is <= t (spans without samples have no tiles)
-    uint32_t lo = 0, hi = n_spans - 1;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (spans[mid].tile_first <= t) lo = mid; else hi = mid - 1;
-    }
+    const uint32_t lo = afg::last_at_or_before(spans, n_spans, t, &afg_wav_span::tile_first);
     const afg_wav_span sp = spans[lo];
     if (sp.tile_first > t || sp.kind > AFG_F64_KIND_FLAC_S32) return;
     const uint64_t s0 = (t - sp.tile_first) * kTile;             // first sample of the tile within the span
@@ -161,10 +157,7 @@ extern "C" int afg_pcm_to_f64_hip(uint64_t n_spans, const afg_wav_span *d_spans,
         afg::set_error("afg_pcm_to_f64_hip: NULL device pointer");
         return AFG_ERR_INVALID;
     }
-    if (n_spans > 0xffffffffull || n_tiles > 0x7fffffffull) {
-        afg::set_error("afg_pcm_to_f64_hip: at most 2^32 - 1 spans and 2^31 - 1 tiles per launch");
-        return AFG_ERR_INVALID;
-    }
+    if (int rc = afg::launch_caps("afg_pcm_to_f64_hip", "spans", n_spans, n_tiles)) return rc;
     if (int rc = afg::require_device()) return rc;
     hipLaunchKernelGGL(pcm_to_f64_kernel, dim3((uint32_t)n_tiles), dim3(kThreads), 0, (hipStream_t)hip_stream, (uint32_t)n_spans,
                        d_spans, d_in, in_bytes, (uint64_t *)d_out, out_doubles);

@@ -23,7 +23,7 @@
 // Dither: sample n of a file uses draws draw0 + 2n and draw0 + 2n + 1 of the 31-bit LCG.  n steps of it are one affine
 // map; a workgroup computes the map to its first unit's first draw from uniform values, a lane composes it with entry
 // `lane` of a constant table (32 draws per unit) and steps from there.  A byte lane jumps straight to its sample.
-#include "afg_common.h"
+#include "afg_records.h"
 
 namespace {
 
@@ -196,11 +196,7 @@ __global__ __launch_bounds__(kThreads) void pcm_pack_kernel(uint32_t n_spans, co
 {
     const uint64_t t = blockIdx.x;
     // the span of tile t: the last one whose first tile is <= t (spans without samples have no tiles)
-    uint32_t lo = 0, hi = n_spans - 1;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (spans[mid].first_tile <= t) lo = mid; else hi = mid - 1;
-    }
+    const uint32_t lo = afg::last_at_or_before(spans, n_spans, t, &afg_pcm_pack_span::first_tile);
     const afg_pcm_pack_span sp = spans[lo];
     if (sp.first_tile > t || sp.format > AFG_WAV_S24LE) return;
     const uint64_t s0 = (t - sp.first_tile) * kTile;             // first sample of the tile within the span
@@ -253,10 +249,7 @@ extern "C" int afg_pcm_pack_hip(uint64_t n_spans, const afg_pcm_pack_span *d_spa
         afg::set_error("afg_pcm_pack_hip: the input plane must be 4-byte aligned");
         return AFG_ERR_INVALID;
     }
-    if (n_spans > 0xffffffffull || n_tiles > 0x7fffffffull) {
-        afg::set_error("afg_pcm_pack_hip: at most 2^32 - 1 spans and 2^31 - 1 tiles per launch");
-        return AFG_ERR_INVALID;
-    }
+    if (int rc = afg::launch_caps("afg_pcm_pack_hip", "spans", n_spans, n_tiles)) return rc;
     if (int rc = afg::require_device()) return rc;
     hipLaunchKernelGGL(pcm_pack_kernel, dim3((uint32_t)n_tiles), dim3(kThreads), 0, (hipStream_t)hip_stream, (uint32_t)n_spans,
                        d_spans, (const uint32_t *)d_in, in_floats, d_out, out_bytes);

@@ -25,7 +25,7 @@
 // Bounds: every record is checked on the host before the launch (check_rows below); the kernel relies on it.  It reads
 // in[in_off + 2 (k in_pitch + f)] and the float behind it for k < n_bins, f < n_frames only and writes
 // out[out_off + 2 (k out_pitch + t)] and the float behind it for t < out_frames only.  LDS slots are clamped to the array.
-#include "afg_common.h"
+#include "afg_records.h"
 
 #include <cmath>
 #include <vector>
@@ -196,11 +196,11 @@ int check_rows(const afg_pvoc_row *rows, uint64_t n_rows, const afg_pvoc_params 
         }
         if (r.out_frames > r.out_pitch) { afg::set_error("afg_pvoc_hip: row %llu: out_frames %u above out_pitch %u", kk, r.out_frames, r.out_pitch); return AFG_ERR_INVALID; }
         const uint64_t need = 2 * ((n_bins - 1) * r.in_pitch + r.n_frames), make = 2 * ((n_bins - 1) * r.out_pitch + r.out_frames);      // < 2^49
-        if (r.in_off > in_floats || need > in_floats - r.in_off) {
+        if (!afg::rows_inside(r.in_off, 1, 0, need, in_floats)) {
             afg::set_error("afg_pvoc_hip: row %llu: the slab's %llu floats leave the input (%llu floats)", kk, (unsigned long long)need, (unsigned long long)in_floats);
             return AFG_ERR_INVALID;
         }
-        if (r.out_off > out_floats || make > out_floats - r.out_off) {
+        if (!afg::rows_inside(r.out_off, 1, 0, make, out_floats)) {
             afg::set_error("afg_pvoc_hip: row %llu: the slab's %llu floats leave the output (%llu floats)", kk, (unsigned long long)make, (unsigned long long)out_floats);
             return AFG_ERR_INVALID;
         }
@@ -239,7 +239,7 @@ extern "C" uint32_t afg_pvoc_out_frames(uint32_t n_frames, double rate)
 extern "C" double afg_pvoc_bound(const afg_pvoc_params *params, uint64_t t)
 {
     if (check_params(params, "afg_pvoc_bound")) return -1.0;
-    return AFG_PVOC_KA * 0x1p-24 + AFG_PVOC_KP * 0x1p-53 * 3.14159265358979323846 * ((double)t + 1.0);
+    return AFG_PVOC_KA * 0x1p-24 + AFG_PVOC_KP * 0x1p-53 * afg::kPi * ((double)t + 1.0);
 }
 
 extern "C" int afg_pvoc_check_rows(const afg_pvoc_row *rows, uint64_t n_rows, const afg_pvoc_params *params, uint64_t in_floats, uint64_t out_floats)
@@ -258,16 +258,10 @@ extern "C" int afg_pvoc_hip(uint64_t n_rows, const afg_pvoc_row *d_rows, const a
     if (int rc = check_args(n_rows, d_rows, *params, d_in, in_floats, d_out, out_floats)) return rc;
     if (int rc = afg::require_device()) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
-    // the rows as the kernel will see them (whatever wrote them was queued on this stream)
-    try {
-        std::vector<afg_pvoc_row> h((size_t)n_rows);
-        AFG_HIP_CHECK(hipMemcpyAsync(h.data(), d_rows, (size_t)n_rows * sizeof(afg_pvoc_row), hipMemcpyDeviceToHost, stream));
-        AFG_HIP_CHECK(hipStreamSynchronize(stream));
-        if (int rc = check_rows(h.data(), n_rows, *params, in_floats, out_floats)) return rc;
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    if (int rc = afg::with_host_records(d_rows, n_rows, stream, [&](const afg_pvoc_row *h) {
+            return check_rows(h, n_rows, *params, in_floats, out_floats);
+        }))
+        return rc;
     const uint32_t groups = (params->n_fft / 2 + 1 + kWaves - 1) / kWaves;
     hipLaunchKernelGGL(pvoc_kernel, dim3((uint32_t)(n_rows * groups)), dim3(kThreads), 0, stream, d_rows, params->n_fft, params->hop, groups, d_in, d_out);
     AFG_HIP_CHECK(hipGetLastError());

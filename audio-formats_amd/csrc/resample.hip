@@ -20,9 +20,7 @@
 // Bounds: every row is checked on the host before the launch (check_rows below); the kernel relies on it.  It reads
 // in[in_off + r * in_stride + g] for r < in_rows and 0 <= g < in_frames only, taps[taps_off .. taps_off + L * K) only, and
 // writes out[out_off .. out_off + out_frames) only.
-#include "afg_common.h"
-
-#include <vector>
+#include "afg_records.h"
 
 namespace {
 
@@ -98,11 +96,7 @@ __global__ __launch_bounds__(kThreads) void resample_kernel(uint32_t n_rows, con
     __shared__ float tab[kTapsLds];
     const uint64_t tile = blockIdx.x;
     // the row of this tile: the last one whose first tile is <= tile (rows without output have no tiles)
-    uint32_t lo = 0, hi = n_rows - 1;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (rows[mid].first_tile <= tile) lo = mid; else hi = mid - 1;
-    }
+    const uint32_t lo = afg::last_at_or_before(rows, n_rows, tile, &afg_resample_row::first_tile);
     const afg_resample_row r = rows[lo];
     if (r.first_tile > tile) return;
     const uint32_t lane = threadIdx.x;
@@ -178,7 +172,7 @@ int check_rows(const afg_resample_row *rows, uint64_t n_rows, uint64_t n_tiles, 
             return AFG_ERR_INVALID;
         }
         tiles += tiles_of(r);
-        if (r.out_frames && (r.out_off > out_floats || r.out_frames > out_floats - r.out_off)) {
+        if (r.out_frames && !afg::rows_inside(r.out_off, 1, 0, r.out_frames, out_floats)) {
             afg::set_error("afg_resample_hip: row %llu: the row leaves the output (%llu floats)", kk, (unsigned long long)out_floats);
             return AFG_ERR_INVALID;
         }
@@ -187,16 +181,13 @@ int check_rows(const afg_resample_row *rows, uint64_t n_rows, uint64_t n_tiles, 
             afg::set_error("afg_resample_hip: row %llu: in_rows %u: 1 .. 65535", kk, r.in_rows);
             return AFG_ERR_INVALID;
         }
-        // in_off + (in_rows - 1) * in_stride + in_frames <= in_floats, without a sum that wraps
-        bool inside = have_in && r.in_frames <= in_floats && r.in_off <= in_floats - r.in_frames;
-        if (inside && r.in_rows > 1) inside = r.in_stride <= (in_floats - r.in_frames - r.in_off) / (r.in_rows - 1);
-        if (!inside) {
+        if (!have_in || !afg::rows_inside(r.in_off, r.in_rows, r.in_stride, r.in_frames, in_floats)) {
             afg::set_error("afg_resample_hip: row %llu: the input rows leave the input (%llu floats)", kk, (unsigned long long)in_floats);
             return AFG_ERR_INVALID;
         }
         if (r.W == 0) continue;
         const uint64_t table = (uint64_t)r.L * 2 * r.W;
-        if (!have_taps || table > kMaxTable || r.taps_off > taps_floats || table > taps_floats - r.taps_off) {
+        if (!have_taps || table > kMaxTable || !afg::rows_inside(r.taps_off, 1, 0, table, taps_floats)) {
             afg::set_error("afg_resample_hip: row %llu: the table of %llu floats leaves d_taps (%llu floats; a table holds 2^22 at the most)", kk,
                            (unsigned long long)table, (unsigned long long)taps_floats);
             return AFG_ERR_INVALID;
@@ -220,11 +211,7 @@ int check_args(uint64_t n_rows, const afg_resample_row *d_rows, uint64_t n_tiles
         afg::set_error("afg_resample_hip: the planes must be 4-byte aligned");
         return AFG_ERR_INVALID;
     }
-    if (n_rows > 0xffffffffull || n_tiles > 0x7fffffffull) {
-        afg::set_error("afg_resample_hip: at most 2^32 - 1 rows and 2^31 - 1 tiles per launch");
-        return AFG_ERR_INVALID;
-    }
-    return AFG_OK;
+    return afg::launch_caps("afg_resample_hip", "rows", n_rows, n_tiles);
 }
 
 }  // namespace
@@ -259,14 +246,7 @@ extern "C" int afg_resample_hip(uint64_t n_rows, const afg_resample_row *d_rows,
     if (n_rows == 0) return AFG_OK;
     if (int rc = check_args(n_rows, d_rows, n_tiles, d_in, d_taps, d_out)) return rc;
     if (int rc = afg::require_device()) return rc;
-    // the rows as the kernel will see them (whatever wrote them was queued on this stream)
-    try {
-        std::vector<afg_resample_row> h((size_t)n_rows);
-        AFG_HIP_CHECK(hipMemcpyAsync(h.data(), d_rows, (size_t)n_rows * sizeof(afg_resample_row), hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-        AFG_HIP_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));
-        return afg::resample_launch(h.data(), n_rows, d_rows, n_tiles, d_in, in_floats, d_taps, taps_floats, d_out, out_floats, (hipStream_t)hip_stream);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    return afg::with_host_records(d_rows, n_rows, (hipStream_t)hip_stream, [&](const afg_resample_row *h) {
+        return afg::resample_launch(h, n_rows, d_rows, n_tiles, d_in, in_floats, d_taps, taps_floats, d_out, out_floats, (hipStream_t)hip_stream);
+    });
 }

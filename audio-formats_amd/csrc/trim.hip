@@ -24,14 +24,12 @@
 // in[in_off + r * in_stride + e] for r < rows and e < valid only -- the apply pass reads e in [begin, end), and the region
 // kernel makes end <= valid -- write out[out_off + r * out_stride + t] for r < out_rows and t < out_frames, blocks
 // [0, n_blocks) and regions [0, n_groups).
-#include "afg_common.h"
-
-#include <vector>
+#include "afg_records.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr uint32_t kTile = 4096;                                // floats of one output row per tile
+constexpr uint32_t kTile = afg::kPlaneTile;                      // floats of one output row per tile
 constexpr uint32_t kRun = 16;                                   // blocks per workgroup of the powers kernel
 
 static_assert(sizeof(afg_trim_group) == 64 && sizeof(afg_trim_region) == 16 && sizeof(afg_trim_params) == 48, "include/afg.h");
@@ -70,12 +68,7 @@ __global__ __launch_bounds__(kThreads) void trim_powers_kernel(uint32_t n_groups
         if (b >= n_blocks) break;
         if (!found) {
             // the last group whose first block is <= b (groups without samples have no blocks)
-            uint32_t lo = 0, hi = n_groups - 1;
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi + 1) >> 1;
-                if (groups[mid].first_block <= b) lo = mid; else hi = mid - 1;
-            }
-            gi = lo;
+            gi = afg::last_at_or_before(groups, n_groups, b, &afg_trim_group::first_block);
             found = true;
         } else {
             while (gi + 1 < n_groups && groups[gi + 1].first_block <= b) gi++;
@@ -180,11 +173,7 @@ __global__ __launch_bounds__(kThreads) void trim_apply_kernel(uint32_t n_groups,
 {
     const uint64_t tile = blockIdx.x;
     // the last group whose first tile is <= tile (groups without output have no tiles)
-    uint32_t lo = 0, hi = n_groups - 1;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (groups[mid].first_tile <= tile) lo = mid; else hi = mid - 1;
-    }
+    const uint32_t lo = afg::last_at_or_before(groups, n_groups, tile, &afg_trim_group::first_tile);
     const afg_trim_group g = groups[lo];
     if (g.first_tile > tile || g.out_frames == 0) return;       // (never, behind the checks)
     const uint64_t per_row = ((uint64_t)g.out_frames + kTile - 1) / kTile, local = tile - g.first_tile;
@@ -289,15 +278,8 @@ extern "C" int afg_trim_hip(uint64_t n_groups, const afg_trim_group *d_groups, u
     if (n_groups == 0) return AFG_OK;
     if (int rc = check_args(n_groups, d_groups, n_blocks, n_tiles, params, d_in, in_floats, d_out, out_floats, d_blocks, d_regions)) return rc;
     if (int rc = afg::require_device()) return rc;
-    // the groups as the kernels will see them (whatever wrote them was queued on this stream)
-    try {
-        std::vector<afg_trim_group> h((size_t)n_groups);
-        AFG_HIP_CHECK(hipMemcpyAsync(h.data(), d_groups, (size_t)n_groups * sizeof(afg_trim_group), hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-        AFG_HIP_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));
-        return afg::trim_launch(h.data(), n_groups, d_groups, n_blocks, n_tiles, params, d_in, in_floats, d_out, out_floats, d_blocks, d_regions,
+    return afg::with_host_records(d_groups, n_groups, (hipStream_t)hip_stream, [&](const afg_trim_group *h) {
+        return afg::trim_launch(h, n_groups, d_groups, n_blocks, n_tiles, params, d_in, in_floats, d_out, out_floats, d_blocks, d_regions,
                                 (hipStream_t)hip_stream);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    });
 }

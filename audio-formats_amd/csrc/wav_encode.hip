@@ -17,7 +17,7 @@
 // draw once, from uniform values (31 square-and-multiply steps on the scalar unit); a lane composes that state with
 // entry `lane` of a constant table (the maps of 8 * lane draws: its four samples of step 0) and reaches the steps after
 // it through three compile-time maps (2048 draws each).  Inside its four samples a lane steps the LCG eight times.
-#include "afg_common.h"
+#include "afg_records.h"
 
 namespace {
 
@@ -185,11 +185,7 @@ __global__ __launch_bounds__(kThreads) void wav_pack_kernel(uint32_t n_spans, co
 {
     const uint64_t t = blockIdx.x;
     // the span of tile t: the last one whose first tile is <= t (spans without samples have no tiles)
-    uint32_t lo = 0, hi = n_spans - 1;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (spans[mid].first_tile <= t) lo = mid; else hi = mid - 1;
-    }
+    const uint32_t lo = afg::last_at_or_before(spans, n_spans, t, &afg_wav_pack_span::first_tile);
     const afg_wav_pack_span sp = spans[lo];
     if (sp.first_tile > t || sp.format > AFG_WAV_FP64LE) return;
     const uint64_t s0 = (t - sp.first_tile) * kTile;             // first sample of the tile within the span
@@ -248,10 +244,7 @@ extern "C" int afg_wav_pack_hip(uint64_t n_spans, const afg_wav_pack_span *d_spa
         afg::set_error("afg_wav_pack_hip: the planes must be 16-byte aligned");
         return AFG_ERR_INVALID;
     }
-    if (n_spans > 0xffffffffull || n_tiles > 0x7fffffffull) {
-        afg::set_error("afg_wav_pack_hip: at most 2^32 - 1 spans and 2^31 - 1 tiles per launch");
-        return AFG_ERR_INVALID;
-    }
+    if (int rc = afg::launch_caps("afg_wav_pack_hip", "spans", n_spans, n_tiles)) return rc;
     if (int rc = afg::require_device()) return rc;
     hipLaunchKernelGGL(wav_pack_kernel, dim3((uint32_t)n_tiles), dim3(kThreads), 0, (hipStream_t)hip_stream, (uint32_t)n_spans,
                        d_spans, d_in, in_floats, d_out, out_bytes);

@@ -14,7 +14,7 @@
 // (v_div_scale / v_div_fmas / v_div_fixup).  s32: int-to-float conversion rounds once and the scale by 2^-31 is exact.
 // f32: the 32 bits are moved as an integer, so NaN payloads survive.  f64: v_cvt_f32_f64 (round to nearest even,
 // denormal results kept).
-#include "afg_common.h"
+#include "afg_records.h"
 
 namespace {
 
@@ -122,11 +122,7 @@ __global__ __launch_bounds__(kThreads) void wav_convert_kernel(uint32_t n_spans,
 {
     const uint64_t t = blockIdx.x;
     // the span of tile t: the last one whose first tile is <= t (spans without samples have no tiles)
-    uint32_t lo = 0, hi = n_spans - 1;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (spans[mid].tile_first <= t) lo = mid; else hi = mid - 1;
-    }
+    const uint32_t lo = afg::last_at_or_before(spans, n_spans, t, &afg_wav_span::tile_first);
     const afg_wav_span sp = spans[lo];
     if (sp.tile_first > t || sp.kind > AFG_WAV_KIND_F64) return;
     const uint64_t s0 = (t - sp.tile_first) * kTile;             // first sample of the tile within the span
@@ -169,10 +165,7 @@ extern "C" int afg_wav_convert_hip(uint64_t n_spans, const afg_wav_span *d_spans
         afg::set_error("afg_wav_convert_hip: NULL device pointer");
         return AFG_ERR_INVALID;
     }
-    if (n_spans > 0xffffffffull || n_tiles > 0x7fffffffull) {
-        afg::set_error("afg_wav_convert_hip: at most 2^32 - 1 spans and 2^31 - 1 tiles per launch");
-        return AFG_ERR_INVALID;
-    }
+    if (int rc = afg::launch_caps("afg_wav_convert_hip", "spans", n_spans, n_tiles)) return rc;
     if (int rc = afg::require_device()) return rc;
     hipLaunchKernelGGL(wav_convert_kernel, dim3((uint32_t)n_tiles), dim3(kThreads), 0, (hipStream_t)hip_stream, (uint32_t)n_spans,
                        d_spans, d_in, in_bytes, d_out, out_floats);

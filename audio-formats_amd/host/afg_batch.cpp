@@ -682,18 +682,15 @@ int resampled_run(const ResampleJob &job, const afg_resample_opts *opts, const u
         afg::set_error("afg_batch_decode_resampled: a tensor of %d x %u x %u floats", n_files, opts->channels, opts->frames);
         return AFG_ERR_INVALID;
     }
-    // the sublists: as many files as the scratch budget holds, one at the least
-    const long budget_opt = afg::dev_option(afg::kDevResampleScratchBytes);
-    const uint64_t budget = budget_opt > 0 ? (uint64_t)budget_opt : (uint64_t)2 << 30;
     const uint64_t slab_bytes = (uint64_t)job.R_s * job.T_s * sizeof(float);
-    const size_t per_list = (size_t)std::min<uint64_t>((uint64_t)n_files, std::max<uint64_t>(budget / slab_bytes, 1));
+    const size_t per_list = sublist_size(n_files, slab_bytes, afg::kDevResampleScratchBytes);
     // scratch frame 0 of a file: H frames ahead of its first frame, as far as the file reaches
     std::vector<int64_t> frame0((size_t)n_files, 0);
     for (int i = 0; i < n_files && opts->first_frame; i++) frame0[(size_t)i] = std::max<int64_t>(opts->first_frame[i] - (int64_t)job.H, 0);
     if (int rc = afg::require_device()) return rc;
     afg_front::ResamplePlane plane;                           // (declared in front of the drain: it holds what the uploads read)
     afg_front::DevBuf scratch;
-    struct Drain { ~Drain() { (void)hipStreamSynchronize(nullptr); } } drain;
+    NullStreamDrain drain;
     if (int rc = scratch.alloc((size_t)(per_list * slab_bytes))) return rc;
     SampleOut so;
     so.type = afg_front::kSampleCollate;
@@ -723,25 +720,17 @@ extern "C" {
 int afg_batch_decode_resampled(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
                                float *d_out, afg_batch_result *out)
 {
-    try {
+    return afg_front::tensor_entry([&]() -> int {
         // (all of this before any device call: it holds on a machine without a GPU too)
-        if (!opts || !d_out || !out) { afg::set_error("afg_batch_decode_resampled: NULL %s", !opts ? "opts" : !d_out ? "d_out" : "out"); return AFG_ERR_INVALID; }
-        out->n_files = 0; out->items = nullptr; out->owner = nullptr;
-        if (opts->struct_size < offsetof(afg_resample_opts, lowpass_width) + sizeof(uint32_t)) {
-            afg::set_error("afg_resample_opts.struct_size too small");
-            return AFG_ERR_INVALID;
-        }
         afg_front::ResampleJob job;
-        if (int rc = afg_front::resampled_check(opts, data, length, n_files, job)) return rc;
+        if (int rc = afg_front::entry_args("afg_batch_decode_resampled", { { "opts", opts }, { "d_out", d_out }, { "out", out } }, out)) return rc;
+        if (int rc = afg_front::resampled_opts_check(opts, data, length, n_files, job)) return rc;
         if (n_files == 0) return AFG_OK;
         afg_front::BatchResult res;
         if (int rc = res.alloc(n_files)) return rc;
         if (int rc = afg_front::resampled_run(job, opts, data, length, n_files, d_out, res.items, res.messages())) return rc;
         return res.finish(out);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    });
 }
 
 void afg_batch_free(afg_batch_result *r)

@@ -15,7 +15,6 @@
 
 namespace {
 
-constexpr double kPi = 3.14159265358979323846;
 constexpr uint32_t kTile = AFG_CEP_TILE;
 
 uint64_t tiles_of(const afg_cep_row &r) { return ((uint64_t)r.frames + kTile - 1) / kTile; }
@@ -45,11 +44,11 @@ bool dct_args_ok(uint32_t n_ceps, uint32_t n_mels, uint32_t norm, double lifter,
 void fill_dct(float *out, uint32_t n_ceps, uint32_t n_mels, uint32_t norm, double lifter, double log_scale)
 {
     for (uint32_t q = 0; q < n_ceps; q++) {
-        const double L = lifter > 0.0 ? 1.0 + (lifter / 2.0) * std::sin(kPi * (double)q / lifter) : 1.0;
+        const double L = lifter > 0.0 ? 1.0 + (lifter / 2.0) * std::sin(afg::kPi * (double)q / lifter) : 1.0;
         const double s = norm == AFG_CEP_DCT_ORTHO ? std::sqrt((q == 0 ? 1.0 : 2.0) / (double)n_mels) : 2.0;
         for (uint32_t m = 0; m < n_mels; m++) {
             const uint64_t r = ((uint64_t)q * (2 * (uint64_t)m + 1)) % (4 * (uint64_t)n_mels);
-            out[(size_t)q * n_mels + m] = (float)(log_scale * L * s * std::cos(kPi * (double)r / (2.0 * (double)n_mels)));
+            out[(size_t)q * n_mels + m] = (float)(log_scale * L * s * std::cos(afg::kPi * (double)r / (2.0 * (double)n_mels)));
         }
     }
 }
@@ -69,9 +68,6 @@ std::shared_ptr<const std::vector<float>> dct_table(uint32_t n_ceps, uint32_t n_
     }
     return t->second;
 }
-
-// off + need <= floats, without a sum that wraps
-bool inside(uint64_t off, uint64_t need, uint64_t floats) { return need <= floats && off <= floats - need; }
 
 }  // namespace
 
@@ -120,12 +116,12 @@ extern "C" int afg_cep_check_rows(const afg_cep_row *rows, uint64_t n_rows, uint
         tiles += tiles_of(r);                                    // below 2^26 a record: no wrap before the launch's cap refuses
         if (tiles > ((uint64_t)1 << 62)) { afg::set_error("afg_cepstra_hip: record %llu: too many tiles", kk); return AFG_ERR_INVALID; }
         if (r.frames == 0) continue;
-        if (!inside(r.in_off, (uint64_t)p.n_mels * r.frames, in_floats)) {
+        if (!afg::rows_inside(r.in_off, 1, 0, (uint64_t)p.n_mels * r.frames, in_floats)) {
             afg::set_error("afg_cepstra_hip: record %llu: its slab of %u x %u floats leaves the input (%llu floats)", kk, p.n_mels, r.frames,
                            (unsigned long long)in_floats);
             return AFG_ERR_INVALID;
         }
-        if (!inside(r.out_off, out_rows * r.frames, out_floats)) {
+        if (!afg::rows_inside(r.out_off, 1, 0, out_rows * r.frames, out_floats)) {
             afg::set_error("afg_cepstra_hip: record %llu: its %llu x %u floats leave the output (%llu floats)", kk, (unsigned long long)out_rows,
                            r.frames, (unsigned long long)out_floats);
             return AFG_ERR_INVALID;
@@ -141,10 +137,9 @@ extern "C" int afg_cep_check_rows(const afg_cep_row *rows, uint64_t n_rows, uint
 extern "C" int afg_batch_decode_mfcc(const uint8_t *const *data, const size_t *length, int n_files, const afg_mfcc_opts *opts,
                                      const afg_norm_params *wave_norm, const afg_norm_params *cmvn, float *d_out, afg_batch_result *out)
 {
-    try {
+    return afg_front::tensor_entry([&]() -> int {
         // (all of this before any device call: it holds on a machine without a GPU too)
-        if (!opts || !d_out || !out) { afg::set_error("afg_batch_decode_mfcc: NULL %s", !opts ? "opts" : !d_out ? "d_out" : "out"); return AFG_ERR_INVALID; }
-        out->n_files = 0; out->items = nullptr; out->owner = nullptr;
+        if (int rc = afg_front::entry_args("afg_batch_decode_mfcc", { { "opts", opts }, { "d_out", d_out }, { "out", out } }, out)) return rc;
         if (opts->struct_size < sizeof(afg_mfcc_opts)) {
             afg::set_error("afg_mfcc_opts.struct_size too small");
             return AFG_ERR_INVALID;
@@ -154,12 +149,7 @@ extern "C" int afg_batch_decode_mfcc(const uint8_t *const *data, const size_t *l
             // what afg_batch_decode_mel_norm checks of its options (an empty list: it touches nothing), then of the list
             afg_batch_result none;
             if (int rc = afg_front::mel_batch(data, length, 0, &o.mel, wave_norm, nullptr, d_out, &none)) return rc;
-            afg_resample_opts ro;
-            std::memset(&ro, 0, sizeof(ro));
-            ro.struct_size = (uint32_t)sizeof(ro);
-            ro.n_threads = o.mel.n_threads; ro.channels = o.mel.channels; ro.frames = o.mel.frames; ro.first_frame = o.mel.first_frame;
-            ro.samplerate = o.mel.samplerate; ro.mono = o.mel.mono; ro.in_channels = o.mel.in_channels; ro.max_in_rate = o.mel.max_in_rate;
-            ro.lowpass_width = o.mel.lowpass_width;
+            const afg_resample_opts ro = afg_front::resample_opts_of(o.mel);
             afg_front::ResampleJob job;
             if (int rc = afg_front::resampled_check(&ro, data, length, n_files, job)) return rc;
         }
@@ -185,10 +175,7 @@ extern "C" int afg_batch_decode_mfcc(const uint8_t *const *data, const size_t *l
             return AFG_ERR_INVALID;
         }
         const auto table = dct_table(o.cep.n_ceps, o.cep.n_mels, o.dct_norm, o.lifter, log_scale);
-        // the sublists: as many files as the scratch budget holds, one at the least
-        const long budget_opt = afg::dev_option(afg::kDevMelScratchBytes);
-        const uint64_t budget = budget_opt > 0 ? (uint64_t)budget_opt : (uint64_t)2 << 30;
-        const size_t per_list = (size_t)std::min<uint64_t>((uint64_t)n_files, std::max<uint64_t>(budget / (slab_in * sizeof(float)), 1));
+        const size_t per_list = afg_front::sublist_size(n_files, slab_in * sizeof(float), afg::kDevMelScratchBytes);
         afg_front::BatchResult res;
         if (int rc = res.alloc(n_files)) return rc;
         std::deque<std::string> &messages = res.messages();
@@ -197,7 +184,7 @@ extern "C" int afg_batch_decode_mfcc(const uint8_t *const *data, const size_t *l
         std::vector<afg_norm_group> groups;
         afg_front::NormPlane norm;
         afg_front::DevBuf scratch, d_recs, d_dct;
-        struct Drain { ~Drain() { (void)hipStreamSynchronize(nullptr); } } drain;
+        afg_front::NullStreamDrain drain;
         if (int rc = scratch.alloc((size_t)(per_list * slab_in * sizeof(float)))) return rc;
         if (int rc = d_dct.alloc(table->size() * sizeof(float))) return rc;
         AFG_HIP_CHECK(hipMemcpyAsync(d_dct.p, table->data(), table->size() * sizeof(float), hipMemcpyHostToDevice, nullptr));
@@ -230,8 +217,7 @@ extern "C" int afg_batch_decode_mfcc(const uint8_t *const *data, const size_t *l
                 recs.push_back(r);
             }
             const uint64_t tiles = afg_cep_layout(recs.data(), recs.size(), &o.cep);
-            if (int rc = d_recs.alloc(recs.size() * sizeof(afg_cep_row))) return rc;
-            AFG_HIP_CHECK(hipMemcpyAsync(d_recs.p, recs.data(), recs.size() * sizeof(afg_cep_row), hipMemcpyHostToDevice, nullptr));
+            if (int rc = afg_front::upload_records(d_recs, recs, nullptr)) return rc;
             if (int rc = afg::cepstra_launch(recs.data(), recs.size(), (const afg_cep_row *)d_recs.p, tiles, &o.cep, (const float *)scratch.p,
                                              n * slab_in, (const float *)d_dct.p, table->size(), y, n * slab_out, nullptr))
                 return rc;
@@ -251,8 +237,5 @@ extern "C" int afg_batch_decode_mfcc(const uint8_t *const *data, const size_t *l
             AFG_HIP_CHECK(hipStreamSynchronize(nullptr));         // the scratch and the records are free for the next sublist
         }
         return res.finish(out);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    });
 }

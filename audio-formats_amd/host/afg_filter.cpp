@@ -13,7 +13,6 @@
 
 namespace {
 
-constexpr double kPi = 3.14159265358979323846;
 constexpr double kBoundCap = 1073741824.0;                      // 2^30
 constexpr uint64_t kMaxResponse = (uint64_t)1 << 28;            // samples of an impulse response that are summed at the most
 
@@ -98,8 +97,6 @@ double bound_of(const afg_filter_params *p)
     return E;
 }
 
-struct Range { uint64_t lo, hi; uint64_t row; bool out; };
-
 }  // namespace
 
 // (the cascades that passed are remembered: a launch does not sum impulse responses again)
@@ -167,7 +164,7 @@ extern "C" int afg_biquad_design(uint32_t kind, double samplerate, double f0, do
         afg::set_error("afg_biquad_design: f0 %g: inside (0, samplerate / 2) = (0, %g)", f0, samplerate / 2.0);
         return AFG_ERR_INVALID;
     }
-    const double w = 2.0 * kPi * f0 / samplerate;
+    const double w = 2.0 * afg::kPi * f0 / samplerate;
     if (kind == AFG_BIQUAD_DC_BLOCK) {
         r.b0 = 1.0; r.b1 = -1.0; r.b2 = 0.0; r.a1 = -std::exp(-w); r.a2 = 0.0;
         *out = r;
@@ -221,35 +218,27 @@ extern "C" int afg_filter_check_rows(const afg_filter_row *rows, uint64_t n_rows
         if (int rc = afg::filter_check_params(params)) return rc;
         if (n_rows == 0) return AFG_OK;
         if (!rows) { afg::set_error("afg_filter_row: NULL rows"); return AFG_ERR_INVALID; }
-        std::vector<Range> r;
+        std::vector<afg::Range> r;
         for (uint64_t k = 0; k < n_rows; k++) {
             const afg_filter_row &w = rows[k];
             const unsigned long long kk = (unsigned long long)k;
             if (w.reserved != 0) { afg::set_error("afg_filter_row %llu: reserved %u: must be 0", kk, w.reserved); return AFG_ERR_INVALID; }
             if (w.frames == 0) continue;
-            if (w.frames > in_floats || w.in_off > in_floats - w.frames) {
+            if (!afg::rows_inside(w.in_off, 1, 0, w.frames, in_floats)) {
                 afg::set_error("afg_filter_row %llu: it leaves the input (%llu floats)", kk, (unsigned long long)in_floats);
                 return AFG_ERR_INVALID;
             }
-            if (w.frames > out_floats || w.out_off > out_floats - w.frames) {
+            if (!afg::rows_inside(w.out_off, 1, 0, w.frames, out_floats)) {
                 afg::set_error("afg_filter_row %llu: it leaves the output (%llu floats)", kk, (unsigned long long)out_floats);
                 return AFG_ERR_INVALID;
             }
-            r.push_back(Range{ w.out_off, w.out_off + w.frames, k, true });
-            if (same_plane && w.in_off != w.out_off) r.push_back(Range{ w.in_off, w.in_off + w.frames, k, false });
+            r.push_back(afg::Range{ w.out_off, w.out_off + w.frames, k, true });
+            if (same_plane && w.in_off != w.out_off) r.push_back(afg::Range{ w.in_off, w.in_off + w.frames, k, false });
         }
-        // an output row may meet nothing but its own input at the same offset (which has no range of its own above)
-        std::sort(r.begin(), r.end(), [](const Range &a, const Range &b) { return a.lo != b.lo ? a.lo < b.lo : a.out > b.out; });
-        uint64_t out_hi = 0, any_hi = 0;                         // the furthest end so far of the outputs, of all ranges
-        unsigned long long out_row = 0, any_row = 0;
-        for (const Range &x : r) {
-            const uint64_t reach = x.out ? any_hi : out_hi;      // an input may overlap inputs
-            if (x.lo < reach) {
-                afg::set_error("afg_filter_row %llu: it overlaps row %llu without being in place", (unsigned long long)x.row, x.out ? any_row : out_row);
-                return AFG_ERR_INVALID;
-            }
-            if (x.out && x.hi > out_hi) { out_hi = x.hi; out_row = x.row; }
-            if (x.hi > any_hi) { any_hi = x.hi; any_row = x.row; }
+        uint64_t row = 0, other = 0;
+        if (afg::first_overlap(r, &row, &other)) {
+            afg::set_error("afg_filter_row %llu: it overlaps row %llu without being in place", (unsigned long long)row, (unsigned long long)other);
+            return AFG_ERR_INVALID;
         }
         return AFG_OK;
     } catch (...) {
@@ -261,19 +250,11 @@ extern "C" int afg_filter_check_rows(const afg_filter_row *rows, uint64_t n_rows
 extern "C" int afg_batch_decode_filtered(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
                                          const afg_filter_params *filter, float *d_out, afg_batch_result *out)
 {
-    try {
+    return afg_front::tensor_entry([&]() -> int {
         // (all of this before any device call: it holds on a machine without a GPU too)
-        if (!opts || !filter || !d_out || !out) {
-            afg::set_error("afg_batch_decode_filtered: NULL %s", !opts ? "opts" : !filter ? "filter" : !d_out ? "d_out" : "out");
-            return AFG_ERR_INVALID;
-        }
-        out->n_files = 0; out->items = nullptr; out->owner = nullptr;
-        if (opts->struct_size < offsetof(afg_resample_opts, lowpass_width) + sizeof(uint32_t)) {
-            afg::set_error("afg_resample_opts.struct_size too small");
-            return AFG_ERR_INVALID;
-        }
         afg_front::ResampleJob job;
-        if (int rc = afg_front::resampled_check(opts, data, length, n_files, job)) return rc;
+        if (int rc = afg_front::entry_args("afg_batch_decode_filtered", { { "opts", opts }, { "filter", filter }, { "d_out", d_out }, { "out", out } }, out)) return rc;
+        if (int rc = afg_front::resampled_opts_check(opts, data, length, n_files, job)) return rc;
         if (int rc = afg::filter_check_params(filter)) return rc;
         if (n_files == 0) return AFG_OK;
         afg_front::BatchResult res;
@@ -284,7 +265,7 @@ extern "C" int afg_batch_decode_filtered(const uint8_t *const *data, const size_
         // the tensor is whole (resampled_run returns drained): every file's rows over their valid frames, in place
         std::vector<afg_filter_row> rows;                        // (declared in front of the drain: the upload reads them)
         afg_front::DevBuf d_rows;
-        struct Drain { ~Drain() { (void)hipStreamSynchronize(nullptr); } } drain;
+        afg_front::NullStreamDrain drain;
         std::vector<afg_norm_group> groups;
         afg_front::norm_file_groups(job, items, (size_t)n_files, opts->first_frame, groups);
         for (const afg_norm_group &g : groups)
@@ -299,15 +280,11 @@ extern "C" int afg_batch_decode_filtered(const uint8_t *const *data, const size_
             }
         if (!rows.empty()) {
             const uint64_t plane = (uint64_t)n_files * job.C * job.T;
-            if (int rc = d_rows.alloc(rows.size() * sizeof(afg_filter_row))) return rc;
-            AFG_HIP_CHECK(hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * sizeof(afg_filter_row), hipMemcpyHostToDevice, nullptr));
+            if (int rc = afg_front::upload_records(d_rows, rows, nullptr)) return rc;
             if (int rc = afg::filter_launch(rows.data(), rows.size(), (const afg_filter_row *)d_rows.p, filter, d_out, plane, d_out, plane, nullptr, nullptr))
                 return rc;
             AFG_HIP_CHECK(hipStreamSynchronize(nullptr));
         }
         return res.finish(out);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    });
 }

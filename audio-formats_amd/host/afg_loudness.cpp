@@ -13,10 +13,7 @@
 
 namespace {
 
-constexpr double kPi = 3.14159265358979323846;
 constexpr uint32_t kMinRate = 8000, kMaxRate = 192000, kMaxRows = 8;
-
-struct Range { uint64_t lo, hi; uint64_t group; bool out; };
 
 // the sub-blocks a row of the group has sums for, and the doubles the group takes in d_sub (a peak behind every row's sums)
 uint32_t subs_of(const afg_loudness_group &g, uint32_t step)
@@ -25,13 +22,6 @@ uint32_t subs_of(const afg_loudness_group &g, uint32_t step)
     return nb ? nb + 3u : 0u;
 }
 uint64_t sub_doubles(const afg_loudness_group &g, uint32_t step) { return g.valid ? (uint64_t)g.rows * ((uint64_t)subs_of(g, step) + 1u) : 0; }
-
-// off + (rows - 1) * stride + valid <= floats, without a sum that wraps
-bool inside(uint64_t off, const afg_loudness_group &g, uint64_t floats)
-{
-    if (g.valid > floats || off > floats - g.valid) return false;
-    return g.rows == 1 || g.stride <= (floats - g.valid - off) / (g.rows - 1);
-}
 
 }  // namespace
 
@@ -77,7 +67,7 @@ int afg::loudness_kweight(uint32_t samplerate, afg_filter_params *out)
     kw.n_sections = 2;
     {   // the shelf
         const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
-        const double K = std::tan(kPi * f0 / (double)samplerate), Vh = std::pow(10.0, G / 20.0), Vb = std::pow(Vh, 0.4996667741545416);
+        const double K = std::tan(afg::kPi * f0 / (double)samplerate), Vh = std::pow(10.0, G / 20.0), Vb = std::pow(Vh, 0.4996667741545416);
         const double a0 = 1.0 + K / Q + K * K;
         afg_biquad &s = kw.sec[0];
         s.b0 = (Vh + Vb * K / Q + K * K) / a0;
@@ -88,7 +78,7 @@ int afg::loudness_kweight(uint32_t samplerate, afg_filter_params *out)
     }
     {   // the high-pass; its numerator is the standard's table's (1, -2, 1)
         const double f0 = 38.13547087602444, Q = 0.5003270373238773;
-        const double K = std::tan(kPi * f0 / (double)samplerate);
+        const double K = std::tan(afg::kPi * f0 / (double)samplerate);
         const double a0 = 1.0 + K / Q + K * K;
         afg_biquad &s = kw.sec[1];
         s.b0 = 1.0; s.b1 = -2.0; s.b2 = 1.0;
@@ -138,7 +128,7 @@ extern "C" int afg_loudness_check_groups(const afg_loudness_group *groups, uint6
         if (!groups || !counts) { afg::set_error("afg_loudness_check_groups: NULL %s", !groups ? "groups" : "counts"); return AFG_ERR_INVALID; }
         const uint32_t step = afg::loudness_step(params->samplerate);
         uint64_t subs = 0, blocks = 0;
-        std::vector<Range> r;
+        std::vector<afg::Range> r;
         for (uint64_t k = 0; k < n_groups; k++) {
             const afg_loudness_group &g = groups[k];
             const unsigned long long kk = (unsigned long long)k;
@@ -163,19 +153,19 @@ extern "C" int afg_loudness_check_groups(const afg_loudness_group *groups, uint6
                 afg::set_error("afg_loudness_group %llu: stride %llu below valid %u with %u rows", kk, (unsigned long long)g.stride, g.valid, g.rows);
                 return AFG_ERR_INVALID;
             }
-            if (!inside(g.in_off, g, in_floats)) {
+            if (!afg::rows_inside(g.in_off, g.rows, g.stride, g.valid, in_floats)) {
                 afg::set_error("afg_loudness_group %llu: its rows leave the input (%llu floats)", kk, (unsigned long long)in_floats);
                 return AFG_ERR_INVALID;
             }
             if (!params->apply) continue;
-            if (!inside(g.out_off, g, out_floats)) {
+            if (!afg::rows_inside(g.out_off, g.rows, g.stride, g.valid, out_floats)) {
                 afg::set_error("afg_loudness_group %llu: its rows leave the output (%llu floats)", kk, (unsigned long long)out_floats);
                 return AFG_ERR_INVALID;
             }
             for (uint32_t q = 0; q < g.rows; q++) {
                 const uint64_t o = g.out_off + q * g.stride, i = g.in_off + q * g.stride;
-                r.push_back(Range{ o, o + g.valid, k, true });
-                if (same_plane && g.in_off != g.out_off) r.push_back(Range{ i, i + g.valid, k, false });
+                r.push_back(afg::Range{ o, o + g.valid, k, true });
+                if (same_plane && g.in_off != g.out_off) r.push_back(afg::Range{ i, i + g.valid, k, false });
             }
         }
         if (subs != counts->n_sub) {
@@ -187,19 +177,11 @@ extern "C" int afg_loudness_check_groups(const afg_loudness_group *groups, uint6
                            (unsigned long long)blocks);
             return AFG_ERR_INVALID;
         }
-        // an output row may meet nothing but its own input at the same offset (which has no range of its own above)
-        std::sort(r.begin(), r.end(), [](const Range &a, const Range &b) { return a.lo != b.lo ? a.lo < b.lo : a.out > b.out; });
-        uint64_t out_hi = 0, any_hi = 0;                         // the furthest end so far of the outputs, of all ranges
-        unsigned long long out_group = 0, any_group = 0;
-        for (const Range &x : r) {
-            const uint64_t reach = x.out ? any_hi : out_hi;      // an input may overlap inputs
-            if (x.lo < reach) {
-                afg::set_error("afg_loudness_group %llu: a row of it overlaps one of group %llu without being in place", (unsigned long long)x.group,
-                               x.out ? any_group : out_group);
-                return AFG_ERR_INVALID;
-            }
-            if (x.out && x.hi > out_hi) { out_hi = x.hi; out_group = x.group; }
-            if (x.hi > any_hi) { any_hi = x.hi; any_group = x.group; }
+        uint64_t group = 0, other = 0;
+        if (afg::first_overlap(r, &group, &other)) {
+            afg::set_error("afg_loudness_group %llu: a row of it overlaps one of group %llu without being in place", (unsigned long long)group,
+                           (unsigned long long)other);
+            return AFG_ERR_INVALID;
         }
         return AFG_OK;
     } catch (...) {
@@ -211,19 +193,11 @@ extern "C" int afg_loudness_check_groups(const afg_loudness_group *groups, uint6
 extern "C" int afg_batch_decode_loudnorm(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
                                          const afg_loudness_params *loudness, float *d_out, afg_loudness_stats *stats, afg_batch_result *out)
 {
-    try {
+    return afg_front::tensor_entry([&]() -> int {
         // (all of this before any device call: it holds on a machine without a GPU too)
-        if (!opts || !loudness || !d_out || !out) {
-            afg::set_error("afg_batch_decode_loudnorm: NULL %s", !opts ? "opts" : !loudness ? "loudness" : !d_out ? "d_out" : "out");
-            return AFG_ERR_INVALID;
-        }
-        out->n_files = 0; out->items = nullptr; out->owner = nullptr;
-        if (opts->struct_size < offsetof(afg_resample_opts, lowpass_width) + sizeof(uint32_t)) {
-            afg::set_error("afg_resample_opts.struct_size too small");
-            return AFG_ERR_INVALID;
-        }
         afg_front::ResampleJob job;
-        if (int rc = afg_front::resampled_check(opts, data, length, n_files, job)) return rc;
+        if (int rc = afg_front::entry_args("afg_batch_decode_loudnorm", { { "opts", opts }, { "loudness", loudness }, { "d_out", d_out }, { "out", out } }, out)) return rc;
+        if (int rc = afg_front::resampled_opts_check(opts, data, length, n_files, job)) return rc;
         if (int rc = afg::loudness_check_params(loudness)) return rc;
         if (loudness->samplerate != job.samplerate) {
             afg::set_error("afg_batch_decode_loudnorm: afg_loudness_params.samplerate %u is not the tensor's %u", loudness->samplerate, job.samplerate);
@@ -239,7 +213,7 @@ extern "C" int afg_batch_decode_loudnorm(const uint8_t *const *data, const size_
         // the tensor is whole (resampled_run returns drained): one group per file, in place
         std::vector<afg_loudness_group> groups;                  // (declared in front of the drain: the upload reads them)
         afg_front::DevBuf d_groups, d_sub, d_blocks, d_stats;
-        struct Drain { ~Drain() { (void)hipStreamSynchronize(nullptr); } } drain;
+        afg_front::NullStreamDrain drain;
         std::vector<afg_norm_group> file_groups;
         afg_front::norm_file_groups(job, items, (size_t)n_files, opts->first_frame, file_groups);
         for (const afg_norm_group &f : file_groups) {
@@ -251,19 +225,15 @@ extern "C" int afg_batch_decode_loudnorm(const uint8_t *const *data, const size_
         afg_loudness_counts counts;
         if (!afg_loudness_layout(groups.data(), groups.size(), loudness, &counts)) return AFG_ERR_INVALID;
         const uint64_t plane = (uint64_t)n_files * job.C * job.T;
-        if (int rc = d_groups.alloc(groups.size() * sizeof(afg_loudness_group))) return rc;
         if (int rc = d_sub.alloc((size_t)std::max<uint64_t>(counts.n_sub, 1) * sizeof(double))) return rc;
         if (int rc = d_blocks.alloc((size_t)std::max<uint64_t>(counts.n_blocks, 1) * sizeof(double))) return rc;
         if (int rc = d_stats.alloc(groups.size() * sizeof(afg_loudness_stats))) return rc;
-        AFG_HIP_CHECK(hipMemcpyAsync(d_groups.p, groups.data(), groups.size() * sizeof(afg_loudness_group), hipMemcpyHostToDevice, nullptr));
+        if (int rc = afg_front::upload_records(d_groups, groups, nullptr)) return rc;
         if (int rc = afg::loudness_launch(groups.data(), groups.size(), (const afg_loudness_group *)d_groups.p, &counts, loudness, d_out, plane, d_out,
                                           plane, (double *)d_sub.p, (double *)d_blocks.p, (afg_loudness_stats *)d_stats.p, nullptr))
             return rc;
         AFG_HIP_CHECK(hipStreamSynchronize(nullptr));
         if (stats) AFG_HIP_CHECK(hipMemcpy(stats, d_stats.p, groups.size() * sizeof(afg_loudness_stats), hipMemcpyDeviceToHost));
         return res.finish(out);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    });
 }

@@ -16,8 +16,6 @@
 
 namespace {
 
-constexpr double kPi = 3.14159265358979323846;
-
 bool basis_shape_ok(uint32_t n_fft, uint32_t win_length)
 {
     if (n_fft < 16 || n_fft > 2048) { afg::set_error("afg_mel_basis: n_fft %u: 16 .. 2048", n_fft); return false; }
@@ -32,10 +30,10 @@ void fill_basis(float *out, uint32_t n_fft, uint32_t win)
     const uint32_t n_bins = n_fft / 2 + 1, nb16 = nb16_of(n_fft), ld = 2 * nb16, n_lo = (n_fft - win) / 2;
     std::memset(out, 0, (size_t)win * ld * sizeof(float));      // the padding columns: +0.0f
     for (uint32_t j = 0; j < win; j++) {
-        const double w = 0.5 - 0.5 * std::cos(2.0 * kPi * (double)j / (double)win);
+        const double w = 0.5 - 0.5 * std::cos(2.0 * afg::kPi * (double)j / (double)win);
         float *row = out + (size_t)j * ld;
         for (uint32_t k = 0; k < n_bins; k++) {
-            const double a = 2.0 * kPi * (double)(((uint64_t)(n_lo + j) * k) % n_fft) / (double)n_fft;
+            const double a = 2.0 * afg::kPi * (double)(((uint64_t)(n_lo + j) * k) % n_fft) / (double)n_fft;
             row[k] = (float)(w * std::cos(a));
             row[nb16 + k] = (float)(-w * std::sin(a));
         }
@@ -56,9 +54,9 @@ bool fft_shape_ok(uint32_t n_fft, uint32_t win_length)
 // the window, then n_fft pairs (cos, -sin) of 2 pi j / n_fft
 void fill_fft_tables(float *out, uint32_t n_fft, uint32_t win)
 {
-    for (uint32_t j = 0; j < win; j++) out[j] = (float)(0.5 - 0.5 * std::cos(2.0 * kPi * (double)j / (double)win));
+    for (uint32_t j = 0; j < win; j++) out[j] = (float)(0.5 - 0.5 * std::cos(2.0 * afg::kPi * (double)j / (double)win));
     for (uint32_t j = 0; j < n_fft; j++) {
-        const double a = 2.0 * kPi * (double)j / (double)n_fft;
+        const double a = 2.0 * afg::kPi * (double)j / (double)n_fft;
         out[win + 2 * j] = (float)std::cos(a);
         out[win + 2 * j + 1] = (float)(-std::sin(a));
     }
@@ -192,8 +190,7 @@ int MelPlane::launch(const afg_mel_opts &o, const MelTables &t, const float *d_i
         AFG_HIP_CHECK(hipMemcpyAsync(d_filters.p, t.filters->data(), t.filters->size() * sizeof(float), hipMemcpyHostToDevice, st));
         tables_up = true;
     }
-    if (int rc = d_recs.alloc(recs.size() * sizeof(afg_mel_row))) return rc;
-    AFG_HIP_CHECK(hipMemcpyAsync(d_recs.p, recs.data(), recs.size() * sizeof(afg_mel_row), hipMemcpyHostToDevice, st));
+    if (int rc = upload_records(d_recs, recs, st)) return rc;
     if (fft)
         return afg::melspec_fft_launch(recs.data(), recs.size(), (const afg_mel_row *)d_recs.p, tiles, &o.mel, d_in, n_rows * o.frames,
                                        (const float *)d_basis.p, t.basis->size(), (const float *)d_filters.p, t.filters->size(), d_out,
@@ -210,10 +207,9 @@ int MelPlane::launch(const afg_mel_opts &o, const MelTables &t, const float *d_i
 int afg_front::mel_batch(const uint8_t *const *data, const size_t *length, int n_files, const afg_mel_opts *opts, const afg_norm_params *wave_norm,
                          const afg_norm_params *feat_norm, float *d_out, afg_batch_result *out)
 {
-    try {
+    return afg_front::tensor_entry([&]() -> int {
         // (all of this before any device call: it holds on a machine without a GPU too)
-        if (!opts || !d_out || !out) { afg::set_error("afg_batch_decode_mel: NULL %s", !opts ? "opts" : !d_out ? "d_out" : "out"); return AFG_ERR_INVALID; }
-        out->n_files = 0; out->items = nullptr; out->owner = nullptr;
+        if (int rc = entry_args("afg_batch_decode_mel", { { "opts", opts }, { "d_out", d_out }, { "out", out } }, out)) return rc;
         if (opts->struct_size < sizeof(afg_mel_opts)) {
             afg::set_error("afg_mel_opts.struct_size too small");
             return AFG_ERR_INVALID;
@@ -224,12 +220,7 @@ int afg_front::mel_batch(const uint8_t *const *data, const size_t *length, int n
             return AFG_ERR_INVALID;
         }
         if (o.reserved != 0) { afg::set_error("afg_mel_opts.reserved %u: must be 0", o.reserved); return AFG_ERR_INVALID; }
-        afg_resample_opts ro;
-        std::memset(&ro, 0, sizeof(ro));
-        ro.struct_size = (uint32_t)sizeof(ro);
-        ro.n_threads = o.n_threads; ro.channels = o.channels; ro.frames = o.frames; ro.first_frame = o.first_frame;
-        ro.samplerate = o.samplerate; ro.mono = o.mono; ro.in_channels = o.in_channels; ro.max_in_rate = o.max_in_rate;
-        ro.lowpass_width = o.lowpass_width;
+        const afg_resample_opts ro = resample_opts_of(o);
         afg_front::ResampleJob job;
         if (int rc = afg_front::resampled_check(&ro, data, length, n_files, job)) return rc;
         if (int rc = afg_mel_check_rows(nullptr, 0, 0, &o.mel, 0, 0, 0, 0)) return rc;       // the mel parameters alone
@@ -265,10 +256,7 @@ int afg_front::mel_batch(const uint8_t *const *data, const size_t *length, int n
             afg::set_error("afg_batch_decode_mel: a tensor of %d x %u x %u x %u floats", n_files, o.channels, o.mel.n_mels, n_out);
             return AFG_ERR_INVALID;
         }
-        // the sublists: as many files as the scratch budget holds, one at the least
-        const long budget_opt = afg::dev_option(afg::kDevMelScratchBytes);
-        const uint64_t budget = budget_opt > 0 ? (uint64_t)budget_opt : (uint64_t)2 << 30;
-        const size_t per_list = (size_t)std::min<uint64_t>((uint64_t)n_files, std::max<uint64_t>(budget / (slab_in * sizeof(float)), 1));
+        const size_t per_list = afg_front::sublist_size(n_files, slab_in * sizeof(float), afg::kDevMelScratchBytes);
         afg_front::BatchResult res;
         if (int rc = res.alloc(n_files)) return rc;
         afg_batch_item *const items = res.items;
@@ -278,7 +266,7 @@ int afg_front::mel_batch(const uint8_t *const *data, const size_t *length, int n
         afg_front::NormPlane wave, feat;
         std::vector<afg_norm_group> groups;
         afg_front::DevBuf scratch;
-        struct Drain { ~Drain() { (void)hipStreamSynchronize(nullptr); } } drain;
+        afg_front::NullStreamDrain drain;
         if (int rc = scratch.alloc((size_t)(per_list * slab_in * sizeof(float)))) return rc;
         for (size_t f0 = 0; f0 < (size_t)n_files; f0 += per_list) {
             const size_t n = std::min(per_list, (size_t)n_files - f0);
@@ -312,10 +300,7 @@ int afg_front::mel_batch(const uint8_t *const *data, const size_t *length, int n
             AFG_HIP_CHECK(hipStreamSynchronize(nullptr));         // the scratch and the records are free for the next sublist
         }
         return res.finish(out);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    });
 }
 
 extern "C" int afg_batch_decode_mel(const uint8_t *const *data, const size_t *length, int n_files, const afg_mel_opts *opts, float *d_out,

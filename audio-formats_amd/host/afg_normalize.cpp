@@ -11,7 +11,7 @@
 
 namespace {
 
-constexpr uint32_t kTile = 4096;
+constexpr uint32_t kTile = afg::kPlaneTile;
 
 uint64_t tiles_of(const afg_norm_group &g)
 {
@@ -44,19 +44,6 @@ int check_params(const afg_norm_params *p)
         afg::set_error("afg_norm_params.mode %u: AFG_NORM_NONE .. AFG_NORM_DYNAMIC_RANGE", p->mode);
         return AFG_ERR_INVALID;
     }
-}
-
-// off + (rows - 1) * stride + valid <= floats, without a sum that wraps
-bool inside(uint64_t off, const afg_norm_group &g, uint64_t floats)
-{
-    if (g.valid > floats || off > floats - g.valid) return false;
-    return g.rows == 1 || g.stride <= (floats - g.valid - off) / (g.rows - 1);
-}
-
-uint32_t gcd32(uint32_t a, uint32_t b)
-{
-    while (b) { const uint32_t t = a % b; a = b; b = t; }
-    return a;
 }
 
 }  // namespace
@@ -97,11 +84,11 @@ extern "C" int afg_norm_check_groups(const afg_norm_group *groups, uint64_t n_gr
             afg::set_error("afg_normalize_hip: group %llu: stride %llu below valid %u with %u rows", kk, (unsigned long long)g.stride, g.valid, g.rows);
             return AFG_ERR_INVALID;
         }
-        if (!inside(g.in_off, g, in_floats)) {
+        if (!afg::rows_inside(g.in_off, g.rows, g.stride, g.valid, in_floats)) {
             afg::set_error("afg_normalize_hip: group %llu: its rows leave the input (%llu floats)", kk, (unsigned long long)in_floats);
             return AFG_ERR_INVALID;
         }
-        if (params->mode != AFG_NORM_NONE && !inside(g.out_off, g, out_floats)) {
+        if (params->mode != AFG_NORM_NONE && !afg::rows_inside(g.out_off, g.rows, g.stride, g.valid, out_floats)) {
             afg::set_error("afg_normalize_hip: group %llu: its rows leave the output (%llu floats)", kk, (unsigned long long)out_floats);
             return AFG_ERR_INVALID;
         }
@@ -118,7 +105,7 @@ namespace afg_front {
 uint32_t norm_valid(int64_t frames, int64_t first_frame, uint32_t in_rate, uint32_t out_rate, uint32_t T)
 {
     if (in_rate == 0 || out_rate == 0 || first_frame < 0 || frames <= first_frame) return 0;
-    const uint32_t g = gcd32(in_rate, out_rate);
+    const uint32_t g = afg::gcd32(in_rate, out_rate);
     const uint64_t M = in_rate / g, L = out_rate / g;
     const unsigned __int128 d = (unsigned __int128)(uint64_t)(frames - first_frame) * L;      // below 2^95
     const unsigned __int128 v = (d + (M - 1)) / M;
@@ -151,13 +138,12 @@ int NormPlane::launch(const afg_norm_params &prm, std::vector<afg_norm_group> &g
     recs.swap(groups);                                           // the upload's source lives as long as the object
     if (recs.empty()) return AFG_OK;
     const uint64_t tiles = afg_norm_layout(recs.data(), recs.size());
-    if (int rc = d_recs.alloc(recs.size() * sizeof(afg_norm_group))) return rc;
     if (int rc = d_partials.alloc((size_t)std::max<uint64_t>(tiles, 1) * 32)) return rc;
     if (!d_stats) {
         if (int rc = d_own_stats.alloc(recs.size() * sizeof(afg_norm_stats))) return rc;
         d_stats = (afg_norm_stats *)d_own_stats.p;
     }
-    AFG_HIP_CHECK(hipMemcpyAsync(d_recs.p, recs.data(), recs.size() * sizeof(afg_norm_group), hipMemcpyHostToDevice, st));
+    if (int rc = upload_records(d_recs, recs, st)) return rc;
     return afg::normalize_launch(recs.data(), recs.size(), (const afg_norm_group *)d_recs.p, tiles, &prm, d_plane, plane_floats, d_plane,
                                  plane_floats, d_partials.p, d_stats, st);
 }
@@ -167,19 +153,11 @@ int NormPlane::launch(const afg_norm_params &prm, std::vector<afg_norm_group> &g
 extern "C" int afg_batch_decode_resampled_norm(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
                                                const afg_norm_params *norm, float *d_out, afg_norm_stats *d_stats, afg_batch_result *out)
 {
-    try {
+    return afg_front::tensor_entry([&]() -> int {
         // (all of this before any device call: it holds on a machine without a GPU too)
-        if (!opts || !norm || !d_out || !out) {
-            afg::set_error("afg_batch_decode_resampled_norm: NULL %s", !opts ? "opts" : !norm ? "norm" : !d_out ? "d_out" : "out");
-            return AFG_ERR_INVALID;
-        }
-        out->n_files = 0; out->items = nullptr; out->owner = nullptr;
-        if (opts->struct_size < offsetof(afg_resample_opts, lowpass_width) + sizeof(uint32_t)) {
-            afg::set_error("afg_resample_opts.struct_size too small");
-            return AFG_ERR_INVALID;
-        }
         afg_front::ResampleJob job;
-        if (int rc = afg_front::resampled_check(opts, data, length, n_files, job)) return rc;
+        if (int rc = afg_front::entry_args("afg_batch_decode_resampled_norm", { { "opts", opts }, { "norm", norm }, { "d_out", d_out }, { "out", out } }, out)) return rc;
+        if (int rc = afg_front::resampled_opts_check(opts, data, length, n_files, job)) return rc;
         if (int rc = afg_norm_check_groups(nullptr, 0, 0, norm, 0, 0)) return rc;
         if (((uintptr_t)d_stats & 7u) != 0) { afg::set_error("afg_batch_decode_resampled_norm: d_stats must be 8-byte aligned"); return AFG_ERR_INVALID; }
         if (n_files == 0) return AFG_OK;
@@ -190,14 +168,11 @@ extern "C" int afg_batch_decode_resampled_norm(const uint8_t *const *data, const
         if (int rc = afg_front::resampled_run(job, opts, data, length, n_files, d_out, items, messages)) return rc;
         // the tensor is whole (resampled_run returns drained): one group per file, in place
         afg_front::NormPlane plane;                              // (declared in front of the drain: it holds what the upload reads)
-        struct Drain { ~Drain() { (void)hipStreamSynchronize(nullptr); } } drain;
+        afg_front::NullStreamDrain drain;
         std::vector<afg_norm_group> groups;
         afg_front::norm_file_groups(job, items, (size_t)n_files, opts->first_frame, groups);
         if (int rc = plane.launch(*norm, groups, d_out, (uint64_t)n_files * job.C * job.T, d_stats, nullptr)) return rc;
         AFG_HIP_CHECK(hipStreamSynchronize(nullptr));
         return res.finish(out);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    });
 }

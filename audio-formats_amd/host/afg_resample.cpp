@@ -12,15 +12,8 @@
 
 namespace {
 
-constexpr double kPi = 3.14159265358979323846;
 constexpr double kRolloff = 0.99;
 constexpr uint64_t kMaxTable = (uint64_t)1 << 22;
-
-uint32_t gcd32(uint32_t a, uint32_t b)
-{
-    while (b) { const uint32_t t = a % b; a = b; b = t; }
-    return a;
-}
 
 // W of a rate pair that does filter: ceil(Z / fc) with fc = 0.99 * min(1, L / M)
 uint32_t width_of(double fc, uint32_t Z, bool *fits)
@@ -36,7 +29,7 @@ bool shape_of(uint32_t in_rate, uint32_t out_rate, uint32_t lowpass_width, uint3
     if (in_rate == 0 || out_rate == 0) { afg::set_error("afg_resample_taps: a sample rate of 0 (%u -> %u)", in_rate, out_rate); return false; }
     if (lowpass_width > 64) { afg::set_error("afg_resample_taps: lowpass_width %u: at most 64 (0 means 6)", lowpass_width); return false; }
     *Z = lowpass_width ? lowpass_width : 6;
-    const uint32_t g = gcd32(in_rate, out_rate);
+    const uint32_t g = afg::gcd32(in_rate, out_rate);
     *M = in_rate / g;
     *L = out_rate / g;
     *fc = kRolloff * std::min(1.0, (double)*L / (double)*M);
@@ -58,8 +51,8 @@ void fill_taps(float *taps, uint32_t Z, uint32_t L, uint32_t W, double fc)
         for (uint32_t k = 0; k < K; k++) {
             const double d = ((double)k - (double)(W - 1)) - (double)p / (double)L;
             const double x = std::max(-(double)Z, std::min((double)Z, d * fc));
-            const double s = x == 0.0 ? 1.0 : std::sin(kPi * x) / (kPi * x);
-            const double c = std::cos(kPi * x / (2.0 * (double)Z));
+            const double s = x == 0.0 ? 1.0 : std::sin(afg::kPi * x) / (afg::kPi * x);
+            const double c = std::cos(afg::kPi * x / (2.0 * (double)Z));
             taps[(size_t)p * K + k] = (float)(fc * s * (c * c));
         }
 }
@@ -181,8 +174,7 @@ int ResamplePlane::launch(const ResampleJob &job, const float *d_scratch, afg_ba
     }
     if (recs.empty()) return AFG_OK;
     const uint64_t tiles = afg_resample_layout(recs.data(), recs.size());
-    if (int rc = d_recs.alloc(recs.size() * sizeof(afg_resample_row))) return rc;
-    AFG_HIP_CHECK(hipMemcpyAsync(d_recs.p, recs.data(), recs.size() * sizeof(afg_resample_row), hipMemcpyHostToDevice, st));
+    if (int rc = upload_records(d_recs, recs, st)) return rc;
     if (!taps.empty()) {
         if (int rc = d_taps.alloc(taps.size() * sizeof(float))) return rc;
         AFG_HIP_CHECK(hipMemcpyAsync(d_taps.p, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, st));

@@ -118,8 +118,7 @@ int PackPlane::launch(const SampleOut &out, const float *d_in, uint8_t *d_out, u
         if (recs.empty()) return AFG_OK;
     }
     const uint64_t tiles = afg_pcm_pack_layout(recs.data(), recs.size());
-    if (int rc = spans.alloc(recs.size() * sizeof(afg_pcm_pack_span))) return rc;
-    AFG_HIP_CHECK(hipMemcpyAsync(spans.p, recs.data(), recs.size() * sizeof(afg_pcm_pack_span), hipMemcpyHostToDevice, st));
+    if (int rc = upload_records(spans, recs, st)) return rc;
     return afg_pcm_pack_hip(recs.size(), (const afg_pcm_pack_span *)spans.p, tiles, d_in, c1 - origin, d_out, (c1 - origin) * B, st);
 }
 
@@ -127,8 +126,7 @@ int CollatePlane::submit(const SampleOut &out, const float *d_in, uint64_t in_fl
 {
     if (recs.empty()) return AFG_OK;
     const uint64_t tiles = afg_collate_layout(recs.data(), recs.size());
-    if (int rc = spans.alloc(recs.size() * sizeof(afg_collate_span))) return rc;
-    AFG_HIP_CHECK(hipMemcpyAsync(spans.p, recs.data(), recs.size() * sizeof(afg_collate_span), hipMemcpyHostToDevice, st));
+    if (int rc = upload_records(spans, recs, st)) return rc;
     return afg::collate_launch(recs.data(), recs.size(), (const afg_collate_span *)spans.p, tiles, d_in, in_floats, out.d_out,
                                out.n_files * out.C * out.T, st);
 }

@@ -1,16 +1,16 @@
 // afg_stage.h -- the toolkit every host stage shares (the FLAC / QOA, MP3, Vorbis and Opus stages of afg_*_stage.cpp behind
 // afg_batch.h; MOD, XM and WAV decoding, the batch encoder, the write stream): the library's pools, the one pooled device
 // buffer, a handle's own stream, the conversion that follows a stage's kernels (SampleConv), the stream holder and chunk
-// cutter of the pipelined stages, and the two-slot chunk pipeline (run_chunks).
+// cutter of the pipelined stages, the two-slot chunk pipeline (run_chunks), and what the tensor entries behind
+// afg_batch_decode_resampled open and close with (tensor_entry .. resample_opts_of).
 #pragma once
-#include "../../include/afg.h"
-
-#include <hip/hip_runtime.h>
+#include "../csrc/afg_records.h"
 
 #include <cstddef>
 #include <cstdint>
 #include <deque>
 #include <functional>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <vector>
@@ -180,6 +180,68 @@ struct ResamplePlane {
 int resampled_check(const afg_resample_opts *opts, const uint8_t *const *data, const size_t *length, int n_files, ResampleJob &job);
 int resampled_run(const ResampleJob &job, const afg_resample_opts *opts, const uint8_t *const *data, const size_t *length, int n_files,
                   float *d_out, afg_batch_item *items, std::deque<std::string> &messages);
+// ---- what the tensor entries share (afg_batch_decode_resampled and the stages that run behind it) ----
+// body() under the entries' one catch: what throws there is out of host memory.
+template <typename Body> int tensor_entry(Body body)
+{
+    try {
+        return body();
+    } catch (...) {
+        afg::set_error("out of host memory");
+        return AFG_ERR_OOM;
+    }
+}
+// An entry's required pointers in the order it names them: the first NULL one is refused by name; with all of them there,
+// `out` -- one of them -- is zeroed.
+struct EntryArg { const char *name; const void *p; };
+inline int entry_args(const char *who, std::initializer_list<EntryArg> args, afg_batch_result *out)
+{
+    for (const EntryArg &a : args)
+        if (!a.p) { afg::set_error("%s: NULL %s", who, a.name); return AFG_ERR_INVALID; }
+    out->n_files = 0; out->items = nullptr; out->owner = nullptr;
+    return AFG_OK;
+}
+// How an entry that takes afg_resample_opts goes on behind entry_args: the struct_size test, then resampled_check, which
+// fills in the job.
+inline int resampled_opts_check(const afg_resample_opts *opts, const uint8_t *const *data, const size_t *length, int n_files, ResampleJob &job)
+{
+    if (opts->struct_size < offsetof(afg_resample_opts, lowpass_width) + sizeof(uint32_t)) {
+        afg::set_error("afg_resample_opts.struct_size too small");
+        return AFG_ERR_INVALID;
+    }
+    return resampled_check(opts, data, length, n_files, job);
+}
+// The afg_resample_opts of an entry whose own options (afg_mel_opts, afg_stft_opts, afg_resample_opts itself) carry its fields.
+template <typename Opts> afg_resample_opts resample_opts_of(const Opts &o)
+{
+    afg_resample_opts ro;
+    std::memset(&ro, 0, sizeof(ro));
+    ro.struct_size = (uint32_t)sizeof(ro);
+    ro.n_threads = o.n_threads; ro.channels = o.channels; ro.frames = o.frames; ro.first_frame = o.first_frame;
+    ro.samplerate = o.samplerate; ro.mono = o.mono; ro.in_channels = o.in_channels; ro.max_in_rate = o.max_in_rate;
+    ro.lowpass_width = o.lowpass_width;
+    return ro;
+}
+// The files of one sublist: as many as the scratch budget (2 GiB, or what afg_dev_option says for `budget_option`) holds
+// slabs of slab_bytes, one at the least.
+inline size_t sublist_size(int n_files, uint64_t slab_bytes, afg::DevOption budget_option)
+{
+    const long opt = afg::dev_option(budget_option);
+    const uint64_t budget = opt > 0 ? (uint64_t)opt : (uint64_t)2 << 30;
+    return (size_t)std::min<uint64_t>((uint64_t)n_files, std::max<uint64_t>(budget / slab_bytes, 1));
+}
+// Waits for the null stream on the way out of an entry that queues on it.  Whatever the queued uploads read -- record
+// vectors, planes, pooled buffers -- is declared in front of it, so that it is still there when the wait ends.
+struct NullStreamDrain {
+    ~NullStreamDrain() { (void)hipStreamSynchronize(nullptr); }
+};
+// The records of a launch into a pooled buffer, queued on st.  recs is read until st has passed the copy.
+template <typename Rec> int upload_records(DevBuf &d, const std::vector<Rec> &recs, hipStream_t st)
+{
+    if (int rc = d.alloc(recs.size() * sizeof(Rec))) return rc;
+    AFG_HIP_CHECK(hipMemcpyAsync(d.p, recs.data(), recs.size() * sizeof(Rec), hipMemcpyHostToDevice, st));
+    return AFG_OK;
+}
 // A batch result in the making, for every batch entry: alloc makes the zeroed items and their owner -- what afg_batch_free
 // lets go: the planes the items' PCM points into (afg_batch.cpp) and the message strings that are not static -- and finish
 // hands both to `out`; until then they go with the object.

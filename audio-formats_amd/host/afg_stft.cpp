@@ -57,8 +57,7 @@ struct StftPlane {
             AFG_HIP_CHECK(hipMemcpyAsync(d_table.p, t->data(), t->size() * sizeof(float), hipMemcpyHostToDevice, st));
             table_up = true;
         }
-        if (int rc = d_recs.alloc(recs.size() * sizeof(afg_mel_row))) return rc;
-        AFG_HIP_CHECK(hipMemcpyAsync(d_recs.p, recs.data(), recs.size() * sizeof(afg_mel_row), hipMemcpyHostToDevice, st));
+        if (int rc = afg_front::upload_records(d_recs, recs, st)) return rc;
         return afg::stft_launch(recs.data(), recs.size(), (const afg_mel_row *)d_recs.p, tiles, &o.stft, d_in, n_rows * o.frames,
                                 (const float *)d_table.p, t->size(), d_out, n_rows * slab, st);
     }
@@ -69,22 +68,16 @@ struct StftPlane {
 extern "C" int afg_batch_decode_stft(const uint8_t *const *data, const size_t *length, int n_files, const afg_stft_opts *opts, float *d_out,
                                      afg_batch_result *out)
 {
-    try {
+    return afg_front::tensor_entry([&]() -> int {
         // (all of this before any device call: it holds on a machine without a GPU too)
-        if (!opts || !d_out || !out) { afg::set_error("afg_batch_decode_stft: NULL %s", !opts ? "opts" : !d_out ? "d_out" : "out"); return AFG_ERR_INVALID; }
-        out->n_files = 0; out->items = nullptr; out->owner = nullptr;
+        if (int rc = afg_front::entry_args("afg_batch_decode_stft", { { "opts", opts }, { "d_out", d_out }, { "out", out } }, out)) return rc;
         if (opts->struct_size < sizeof(afg_stft_opts)) {
             afg::set_error("afg_stft_opts.struct_size too small");
             return AFG_ERR_INVALID;
         }
         const afg_stft_opts &o = *opts;
         if (o.reserved != 0) { afg::set_error("afg_stft_opts.reserved %u: must be 0", o.reserved); return AFG_ERR_INVALID; }
-        afg_resample_opts ro;
-        std::memset(&ro, 0, sizeof(ro));
-        ro.struct_size = (uint32_t)sizeof(ro);
-        ro.n_threads = o.n_threads; ro.channels = o.channels; ro.frames = o.frames; ro.first_frame = o.first_frame;
-        ro.samplerate = o.samplerate; ro.mono = o.mono; ro.in_channels = o.in_channels; ro.max_in_rate = o.max_in_rate;
-        ro.lowpass_width = o.lowpass_width;
+        const afg_resample_opts ro = afg_front::resample_opts_of(o);
         afg_front::ResampleJob job;
         if (int rc = afg_front::resampled_check(&ro, data, length, n_files, job)) return rc;
         if (int rc = afg_stft_check_rows(nullptr, 0, 0, &o.stft, 0, 0, 0)) return rc;        // the parameters alone
@@ -111,10 +104,7 @@ extern "C" int afg_batch_decode_stft(const uint8_t *const *data, const size_t *l
             afg::set_error("afg_batch_decode_stft: a tensor of %d x %u x %u x %u floats", n_files, o.channels, comps * (o.stft.n_fft / 2 + 1), n_out);
             return AFG_ERR_INVALID;
         }
-        // the sublists: as many files as the scratch budget holds, one at the least
-        const long budget_opt = afg::dev_option(afg::kDevMelScratchBytes);
-        const uint64_t budget = budget_opt > 0 ? (uint64_t)budget_opt : (uint64_t)2 << 30;
-        const size_t per_list = (size_t)std::min<uint64_t>((uint64_t)n_files, std::max<uint64_t>(budget / (slab_in * sizeof(float)), 1));
+        const size_t per_list = afg_front::sublist_size(n_files, slab_in * sizeof(float), afg::kDevMelScratchBytes);
         afg_front::BatchResult res;
         if (int rc = res.alloc(n_files)) return rc;
         afg_batch_item *const items = res.items;
@@ -122,7 +112,7 @@ extern "C" int afg_batch_decode_stft(const uint8_t *const *data, const size_t *l
         if (int rc = afg::require_device()) return rc;
         StftPlane plane;                                         // (declared in front of the drain: it holds what the uploads read)
         afg_front::DevBuf scratch;
-        struct Drain { ~Drain() { (void)hipStreamSynchronize(nullptr); } } drain;
+        afg_front::NullStreamDrain drain;
         if (int rc = scratch.alloc((size_t)(per_list * slab_in * sizeof(float)))) return rc;
         for (size_t f0 = 0; f0 < (size_t)n_files; f0 += per_list) {
             const size_t n = std::min(per_list, (size_t)n_files - f0);
@@ -138,8 +128,5 @@ extern "C" int afg_batch_decode_stft(const uint8_t *const *data, const size_t *l
             AFG_HIP_CHECK(hipStreamSynchronize(nullptr));         // the scratch and the records are free for the next sublist
         }
         return res.finish(out);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    });
 }

@@ -11,7 +11,7 @@
 
 namespace {
 
-constexpr uint32_t kTile = 4096;
+constexpr uint32_t kTile = afg::kPlaneTile;
 
 uint64_t blocks_of(const afg_trim_group &g, uint32_t hop) { return ((uint64_t)g.valid + hop - 1) / hop; }
 uint64_t tiles_of(const afg_trim_group &g) { return (((uint64_t)g.out_frames + kTile - 1) / kTile) * g.out_rows; }
@@ -49,13 +49,6 @@ int check_params(const afg_trim_params *p)
     for (int k3 = 0; k3 < 3; k3++)
         if (p->reserved[k3] != 0) { afg::set_error("afg_trim_params.reserved[%d] %u: must be 0", k3, p->reserved[k3]); return AFG_ERR_INVALID; }
     return AFG_OK;
-}
-
-// off + (rows - 1) * stride + len <= floats, without a sum that wraps
-bool inside(uint64_t off, uint64_t rows, uint64_t stride, uint64_t len, uint64_t floats)
-{
-    if (len > floats || off > floats - len) return false;
-    return rows == 1 || stride <= (floats - len - off) / (rows - 1);
 }
 
 }  // namespace
@@ -114,7 +107,7 @@ extern "C" int afg_trim_check_groups(const afg_trim_group *groups, uint64_t n_gr
                 afg::set_error("afg_trim_group %llu: in_stride %llu below valid %u with %u rows", kk, (unsigned long long)g.in_stride, g.valid, g.rows);
                 return AFG_ERR_INVALID;
             }
-            if (!inside(g.in_off, g.rows, g.in_stride, g.valid, in_floats)) {
+            if (!afg::rows_inside(g.in_off, g.rows, g.in_stride, g.valid, in_floats)) {
                 afg::set_error("afg_trim_group %llu: its rows leave the input (%llu floats)", kk, (unsigned long long)in_floats);
                 return AFG_ERR_INVALID;
             }
@@ -125,7 +118,7 @@ extern "C" int afg_trim_check_groups(const afg_trim_group *groups, uint64_t n_gr
                                g.out_frames, g.out_rows);
                 return AFG_ERR_INVALID;
             }
-            if (!inside(g.out_off, g.out_rows, g.out_stride, g.out_frames, out_floats)) {
+            if (!afg::rows_inside(g.out_off, g.out_rows, g.out_stride, g.out_frames, out_floats)) {
                 afg::set_error("afg_trim_group %llu: its rows leave the output (%llu floats)", kk, (unsigned long long)out_floats);
                 return AFG_ERR_INVALID;
             }
@@ -146,31 +139,19 @@ extern "C" int afg_batch_decode_trimmed(const uint8_t *const *data, const size_t
                                         const afg_trim_params *trim, uint32_t scan_frames, float *d_out, afg_trim_region *regions,
                                         afg_batch_result *out)
 {
-    try {
+    return afg_front::tensor_entry([&]() -> int {
         // (all of this before any device call: it holds on a machine without a GPU too)
-        if (!opts || !trim || !d_out || !out) {
-            afg::set_error("afg_batch_decode_trimmed: NULL %s", !opts ? "opts" : !trim ? "trim" : !d_out ? "d_out" : "out");
-            return AFG_ERR_INVALID;
-        }
-        out->n_files = 0; out->items = nullptr; out->owner = nullptr;
-        if (opts->struct_size < offsetof(afg_resample_opts, lowpass_width) + sizeof(uint32_t)) {
-            afg::set_error("afg_resample_opts.struct_size too small");
-            return AFG_ERR_INVALID;
-        }
         afg_front::ResampleJob clip, job;                        // the caller's tensor; the scratch that is examined
-        if (int rc = afg_front::resampled_check(opts, data, length, n_files, clip)) return rc;
+        if (int rc = afg_front::entry_args("afg_batch_decode_trimmed", { { "opts", opts }, { "trim", trim }, { "d_out", d_out }, { "out", out } }, out)) return rc;
+        if (int rc = afg_front::resampled_opts_check(opts, data, length, n_files, clip)) return rc;
         if (int rc = afg_trim_check_groups(nullptr, 0, 0, 0, trim, 0, 0)) return rc;
         const uint32_t scan = scan_frames ? scan_frames : opts->frames;
         if (scan < opts->frames) {
             afg::set_error("afg_batch_decode_trimmed: scan_frames %u below frames %u", scan_frames, opts->frames);
             return AFG_ERR_INVALID;
         }
-        afg_resample_opts ro;
-        std::memset(&ro, 0, sizeof(ro));
-        ro.struct_size = (uint32_t)sizeof(ro);
-        ro.n_threads = opts->n_threads; ro.channels = opts->channels; ro.frames = scan; ro.first_frame = opts->first_frame;
-        ro.samplerate = opts->samplerate; ro.mono = opts->mono; ro.in_channels = opts->in_channels; ro.max_in_rate = opts->max_in_rate;
-        ro.lowpass_width = opts->lowpass_width;
+        afg_resample_opts ro = afg_front::resample_opts_of(*opts);
+        ro.frames = scan;
         if (int rc = afg_front::resampled_check(&ro, data, length, n_files, job)) return rc;
         if (n_files == 0) return AFG_OK;
         const uint64_t slab_in = (uint64_t)job.C * scan, slab_out = (uint64_t)job.C * opts->frames;
@@ -178,10 +159,7 @@ extern "C" int afg_batch_decode_trimmed(const uint8_t *const *data, const size_t
             afg::set_error("afg_batch_decode_trimmed: a scratch of %d x %u x %u floats", n_files, job.C, scan);
             return AFG_ERR_INVALID;
         }
-        // the sublists: as many files as the scratch budget holds, one at the least
-        const long budget_opt = afg::dev_option(afg::kDevTrimScratchBytes);
-        const uint64_t budget = budget_opt > 0 ? (uint64_t)budget_opt : (uint64_t)2 << 30;
-        const size_t per_list = (size_t)std::min<uint64_t>((uint64_t)n_files, std::max<uint64_t>(budget / (slab_in * sizeof(float)), 1));
+        const size_t per_list = afg_front::sublist_size(n_files, slab_in * sizeof(float), afg::kDevTrimScratchBytes);
         afg_front::BatchResult res;
         if (int rc = res.alloc(n_files)) return rc;
         afg_batch_item *const items = res.items;
@@ -190,7 +168,7 @@ extern "C" int afg_batch_decode_trimmed(const uint8_t *const *data, const size_t
         std::vector<afg_trim_group> groups;                      // (declared in front of the drain: the uploads read them)
         std::vector<afg_norm_group> file_groups;
         afg_front::DevBuf scratch, d_groups, d_blocks, d_regions;
-        struct Drain { ~Drain() { (void)hipStreamSynchronize(nullptr); } } drain;
+        afg_front::NullStreamDrain drain;
         if (int rc = scratch.alloc((size_t)(per_list * slab_in * sizeof(float)))) return rc;
         if (int rc = d_regions.alloc((size_t)n_files * sizeof(afg_trim_region))) return rc;
         for (size_t f0 = 0; f0 < (size_t)n_files; f0 += per_list) {
@@ -218,9 +196,8 @@ extern "C" int afg_batch_decode_trimmed(const uint8_t *const *data, const size_t
             }
             uint64_t n_blocks = 0, n_tiles = 0;
             if (!afg_trim_layout(groups.data(), groups.size(), trim, &n_blocks, &n_tiles)) return AFG_ERR_INVALID;
-            if (int rc = d_groups.alloc(groups.size() * sizeof(afg_trim_group))) return rc;
             if (int rc = d_blocks.alloc((size_t)std::max<uint64_t>(n_blocks, 1) * sizeof(double))) return rc;
-            AFG_HIP_CHECK(hipMemcpyAsync(d_groups.p, groups.data(), groups.size() * sizeof(afg_trim_group), hipMemcpyHostToDevice, nullptr));
+            if (int rc = afg_front::upload_records(d_groups, groups, nullptr)) return rc;
             float *y = d_out + f0 * slab_out;
             if (int rc = afg::trim_launch(groups.data(), groups.size(), (const afg_trim_group *)d_groups.p, n_blocks, n_tiles, trim,
                                           (const float *)scratch.p, n * slab_in, y, n * slab_out, (double *)d_blocks.p,
@@ -232,8 +209,5 @@ extern "C" int afg_batch_decode_trimmed(const uint8_t *const *data, const size_t
         }
         if (regions) AFG_HIP_CHECK(hipMemcpy(regions, d_regions.p, (size_t)n_files * sizeof(afg_trim_region), hipMemcpyDeviceToHost));
         return res.finish(out);
-    } catch (...) {
-        afg::set_error("out of host memory");
-        return AFG_ERR_OOM;
-    }
+    });
 }

@@ -10,6 +10,7 @@ import torch
 
 import afgpu
 import cepstra_model as cm
+from record_cases import RECORD_CASES, record_lengths
 import melspec_model as mm
 
 pytestmark = pytest.mark.gpu
@@ -212,3 +213,13 @@ def test_every_device_side_refusal_writes_nothing(gpu):
     refused(prm=afgpu.cep_params(80, 13, 2, 9))
     got = la.device(rec, d_in, before)                           # the records as they were: the launch runs
     assert (got != SENTINEL).sum() == 39 * 75
+
+
+@pytest.mark.parametrize("case", RECORD_CASES)
+def test_record_counts_and_records_without_tiles(gpu, case):
+    """1, 2 and 5 records, with records of no frames first, in the middle and last (record_cases.py): the tile search's edges"""
+    rng = np.random.default_rng(31)
+    la = Launch(40, 13, 1, 2)
+    for F in record_lengths(TILE)[case]:
+        la.add(slab(rng, 40, F))
+    la.run()

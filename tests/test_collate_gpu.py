@@ -6,6 +6,7 @@ import torch
 
 import afgpu
 import collate_model as cm
+from record_cases import RECORD_CASES, record_lengths
 
 pytestmark = pytest.mark.gpu
 
@@ -198,3 +199,14 @@ def test_a_span_that_leaves_a_plane_is_refused_and_nothing_is_written(gpu):
             launch([dict(far, first_frame=-(1 << 61))], d_in, 8192)
         got, want = launch([dict(far, first_frame=(1 << 61) - 1)], d_in, 8192)
         assert (got == want).all() and (got == cm.PREFILL).all()
+
+
+@pytest.mark.parametrize("case", RECORD_CASES)
+def test_record_counts_and_spans_without_tiles(gpu, case):
+    """1, 2 and 5 spans, with spans of no samples first, in the middle and last (record_cases.py): the tile search's edges"""
+    pl = Planes(np.random.default_rng(17))
+    for k, count in enumerate(record_lengths(TILE)[case]):
+        T = max(count, 1)
+        pl.spans.append(cm.span(in_off=pl.run(count, k & 1), count=count, sample0=0, out_off=pl.slab(T, k & 3), first_frame=0, frames=T,
+                                channels=1, out_channels=1))
+    pl.check()

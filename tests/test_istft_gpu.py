@@ -12,6 +12,7 @@ import torch
 
 import afgpu
 import istft_model as im
+from record_cases import RECORD_CASES, record_lengths
 import melspec_fft_model as fm
 
 pytestmark = pytest.mark.gpu
@@ -301,3 +302,13 @@ def test_a_record_that_breaks_a_rule_is_refused_and_nothing_is_written(gpu):
     refused(prm=afgpu.IstftParams(400, 400, 160, 1, (1, 0, 0, 0)))
     refused(word="unsupported", prm=afgpu.IstftParams(14 * 3 * 5, 16, 16, 1))
     assert len(seen) == 10
+
+
+@pytest.mark.parametrize("case", RECORD_CASES)
+def test_record_counts_and_rows_without_tiles(gpu, case):
+    """1, 2 and 5 rows, with rows of no samples first, in the middle and last (record_cases.py): the tile search's edges"""
+    rng = np.random.default_rng(29)
+    la = Launch((16, 16, 4, True))
+    for count in record_lengths(la.tile)[case]:
+        la.add(noise_spec(rng, la.n_bins, la.frames_for(la.first0, count)), count)
+    la.run()

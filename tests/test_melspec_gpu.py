@@ -11,6 +11,7 @@ import torch
 
 import afgpu
 import melspec_model as mm
+from record_cases import RECORD_CASES, record_lengths
 
 pytestmark = pytest.mark.gpu
 
@@ -245,3 +246,15 @@ def test_a_record_that_breaks_a_rule_is_refused_and_nothing_is_written(gpu):
     refused(lambda b: b["in_frames"].__setitem__(1, 200))                          # reflect with in_frames <= pad (and too many frames)
     refused(prm=afgpu.mel_params(400, 160, 257))
     assert len(seen) >= 9
+
+
+@pytest.mark.parametrize("case", RECORD_CASES)
+def test_record_counts_and_rows_without_tiles(gpu, case):
+    """1, 2 and 5 rows, with rows of no frames first, in the middle and last (record_cases.py): the tile search's edges"""
+    shape = (16, 16, 1, 1, True)
+    n_fft, hop = shape[0], shape[2]
+    rng = np.random.default_rng(23)
+    la = Launch(shape, afgpu.MEL_PAD_ZERO)
+    for f in record_lengths(tile_frames(16, 16, 1))[case]:
+        la.add(rng.standard_normal(max(f, 1) * hop + n_fft) * 0.5, f)          # (room for more frames than are asked for)
+    la.run()

@@ -7,6 +7,7 @@ import torch
 
 import afgpu
 import normalize_model as nm
+from record_cases import RECORD_CASES, record_lengths
 
 pytestmark = pytest.mark.gpu
 
@@ -166,3 +167,29 @@ def test_a_bad_record_is_refused_and_nothing_is_written(case):
         assert (d_out.cpu().numpy().view(np.uint32) == SENTINEL).all()
         assert (stats.cpu().numpy() == 0xAB).all() and (partials.cpu().numpy() == 0xAB).all()
         assert (case["d_x"].cpu().numpy().view(np.uint32) == case["x"].view(np.uint32)).all()
+
+
+@pytest.mark.parametrize("lengths", RECORD_CASES)
+def test_record_counts_and_groups_without_tiles(gpu, lengths):
+    """1, 2 and 5 groups, with groups of no floats first, in the middle and last (record_cases.py): the tile search's edges"""
+    rng = np.random.default_rng(37)
+    valids = record_lengths(4096)[lengths]
+    groups = np.zeros(len(valids), afgpu.NORM_GROUP_DTYPE)
+    at = 3
+    for k, valid in enumerate(valids):
+        g, rows = groups[k], 1 + k % 2
+        g["in_off"], g["out_off"], g["stride"], g["rows"], g["valid"] = at, at, valid + 5, rows, valid
+        at += rows * (valid + 5) + 2
+    n = at + 3
+    tiles = afgpu.norm_layout(groups)
+    x = rng.standard_normal(n).astype(np.float32)
+    d_out = sentinel_plane(n)
+    partials = torch.full((max(tiles, 1) * 32,), 0xAB, dtype=torch.uint8, device="cuda")
+    stats = torch.full((len(valids) * 40,), 0xAB, dtype=torch.uint8, device="cuda")
+    afgpu.normalize(len(valids), torch.from_numpy(groups.view(np.uint8).copy()).cuda(), tiles, params_of("peak", afgpu), torch.from_numpy(x).cuda(), n,
+                    d_out, n, partials, stats)
+    torch.cuda.synchronize()
+    want_plane, want_stats = nm.normalize(x, np.full(n, SENTINEL, np.uint32).view(np.float32), groups.view(nm.GROUP_DTYPE), params_of("peak", nm))
+    assert nm.same_stats(stats.cpu().numpy().view(afgpu.NORM_STATS_DTYPE), want_stats) == []
+    bad = nm.same_bits(d_out.cpu().numpy(), want_plane)          # the sentinel's bits outside the valid elements included
+    assert bad.size == 0, (bad.size, bad[:5].tolist())

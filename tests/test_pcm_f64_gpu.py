@@ -8,6 +8,7 @@ import pytest
 
 import afgpu
 import f64_model as fm
+from record_cases import RECORD_CASES, record_lengths
 
 pytestmark = pytest.mark.gpu
 
@@ -197,3 +198,11 @@ def test_adjacent_spans_and_spans_that_leave_the_planes(gpu):
         assert (got[o:o + n] == fm.convert(raw, kind).view(np.uint64)).all(), fm.KIND_NAMES[kind]
         o += n
     assert (got[:2] == SENTINEL).all() and (got[gap:] == SENTINEL).all()
+
+
+@pytest.mark.parametrize("case", RECORD_CASES)
+def test_record_counts_and_spans_without_tiles(gpu, case):
+    """1, 2 and 5 spans, with spans of no samples first, in the middle and last (record_cases.py): the tile search's edges"""
+    rng = np.random.default_rng(7)
+    convert(gpu, [(fm.KIND_S16, rng.integers(0, 65536, n, dtype=np.uint64).astype("<u2").tobytes(), 2 * (k % 2), k % 2)
+                  for k, n in enumerate(record_lengths(afgpu.WAV_TILE_SAMPLES)[case])])

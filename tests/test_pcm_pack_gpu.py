@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import afgpu
+from record_cases import RECORD_CASES, record_lengths
 
 pytestmark = pytest.mark.gpu
 
@@ -195,3 +196,18 @@ def test_spans_that_leave_the_planes_are_not_touched(gpu, fmt):
     spans = np.concatenate([span(1 << 63, 0, n, fmt), span(0, 5, n, fmt), span(0, (1 << 64) - 8, n, fmt), span(n, 5 + n * B, 16, afgpu.WAV_FP32LE)])
     got = launch(gpu, spans, x, 5 + n * B + 100)
     check(got, [(5, expected(x[:n], fmt, 0))])
+
+
+@pytest.mark.parametrize("case", RECORD_CASES)
+def test_record_counts_and_spans_without_tiles(gpu, case):
+    """1, 2 and 5 spans, with spans of no samples first, in the middle and last (record_cases.py): the tile search's edges"""
+    fmt, B = afgpu.WAV_S16LE, 2
+    spans, pieces, plane, out_at = [], [], [], 16
+    for k, count in enumerate(record_lengths(4096)[case]):
+        x = signal(count, 900 + k)
+        spans.append(span(sum(p.size for p in plane), out_at, count, fmt, 1, 77 + k))
+        pieces.append((out_at, expected(x, fmt, 1, 77 + k)))
+        plane.append(x)
+        out_at += count * B + 16
+    got = launch(gpu, np.concatenate(spans), np.concatenate(plane + [np.full(4, np.nan, np.float32)]), out_at + 16)
+    check(got, pieces)

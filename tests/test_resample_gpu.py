@@ -9,6 +9,7 @@ import torch
 
 import afgpu
 import resample_model as rm
+from record_cases import RECORD_CASES, record_lengths
 
 pytestmark = pytest.mark.gpu
 
@@ -178,3 +179,14 @@ def test_a_record_that_leaves_a_plane_is_refused_and_nothing_is_written(gpu):
     refused(lambda b: b["in_rows"].__setitem__(0, 0))
     refused(lambda b: b["in_frame0"].__setitem__(0, 1 << 61))
     assert len(seen) >= 8
+
+
+@pytest.mark.parametrize("case", RECORD_CASES)
+def test_record_counts_and_rows_without_tiles(gpu, case):
+    """1, 2 and 5 rows, with rows of no frames first, in the middle and last (record_cases.py): the tile search's edges"""
+    pair = (44100, 16000)
+    M, L, W, _ = rm.shape(*pair)
+    la = Launch(np.random.default_rng(19))
+    for k, out_frames in enumerate(record_lengths(tile_frames(M, L, W))[case]):
+        la.add(pair, 1 + k % 2, out_frames * M // L + 40, out_frames, (0, 17)[k % 2])
+    la.run()

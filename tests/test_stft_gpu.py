@@ -13,6 +13,7 @@ import afgpu
 import melspec_fft_model as fm
 import melspec_model as mm
 import stft_model as sm
+from record_cases import RECORD_CASES, record_lengths
 
 pytestmark = pytest.mark.gpu
 
@@ -261,3 +262,15 @@ def test_a_record_that_breaks_a_rule_is_refused_and_nothing_is_written(gpu, kind
     both(prm=afgpu.StftParams(400, 400, 160, 1, 0, kind[0], 0.0, 1))
     both(word="unsupported", prm=afgpu.StftParams(14 * 3 * 5, 16, 16, 1, 0, kind[0], 0.0, 0))
     assert len(seen) >= 10
+
+
+@pytest.mark.parametrize("case", RECORD_CASES)
+def test_record_counts_and_rows_without_tiles(gpu, case):
+    """1, 2 and 5 rows, with rows of no frames first, in the middle and last (record_cases.py): the tile search's edges"""
+    shape = (60, 45, 7, True)
+    n_fft, hop = shape[0], shape[2]
+    rng = np.random.default_rng(23)
+    la = Launch(shape, afgpu.MEL_PAD_ZERO)
+    for f in record_lengths(la.tile)[case]:
+        la.add(rng.standard_normal(max(f, 1) * hop + n_fft) * 0.5, f)          # (room for more frames than are asked for)
+    la.run()

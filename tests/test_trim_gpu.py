@@ -7,6 +7,7 @@ import torch
 
 import afgpu
 import trim_model as tm
+from record_cases import RECORD_CASES, record_lengths
 
 pytestmark = pytest.mark.gpu
 
@@ -156,3 +157,38 @@ def test_a_bad_record_or_overlapping_planes_are_refused_and_nothing_is_written(g
     # side by side in one allocation is no overlap
     _, d_out, _, _ = run(case, d_in=both[:n_in], d_out=both[n_in:])
     assert tm.same_bits(d_out.cpu().numpy(), case["out"]).size == 0
+
+
+@pytest.mark.parametrize("lengths", RECORD_CASES)
+def test_record_counts_and_groups_without_blocks_or_tiles(gpu, lengths):
+    """1, 2 and 5 groups, with groups of no samples and no output first, in the middle and last (record_cases.py): the edges of
+    the search by block and of the search by tile"""
+    fl, hop = 2048, 512
+    rng = np.random.default_rng(41)
+    prm, lib_prm = tm.params(60.0, fl, hop, tm.REF_MAX, 1.0, 0, 0), afgpu.trim_params(60.0, fl, hop, "max", 1.0, 0, 0)
+    valids = record_lengths(4096)[lengths]
+    groups = np.zeros(len(valids), afgpu.TRIM_GROUP_DTYPE)
+    xs, a, b = [], 3, 5
+    for i, valid in enumerate(valids):
+        g, rows = groups[i], 1 + i % 2
+        xs.append(signal(rng, "loud", rows, valid, hop, 0))
+        g["in_off"], g["out_off"], g["rows"], g["valid"] = a, b, rows, valid
+        g["in_stride"], g["out_stride"], g["out_rows"], g["out_frames"] = valid + 2, valid + 1, rows, valid
+        a += rows * (valid + 2) + 2
+        b += rows * (valid + 1) + 3
+    plane = np.full(a + 3, GUARD, np.uint32).view(np.float32)
+    for g, x in zip(groups, xs):
+        for r in range(x.shape[0]):
+            at = int(g["in_off"]) + r * int(g["in_stride"])
+            plane[at:at + x.shape[1]] = x[r]
+    blocks, tiles = afgpu.trim_layout(groups, lib_prm)
+    assert blocks == sum(-(-v // hop) for v in valids) and tiles == sum((1 + i % 2) * -(-v // 4096) for i, v in enumerate(valids))
+    want_out, want_regions, want_powers = tm.trim(plane, np.full(b + 3, SENTINEL, np.uint32).view(np.float32), groups.view(tm.GROUP_DTYPE).copy(), prm)
+    case = {"groups": groups, "blocks": blocks, "tiles": tiles, "plane": plane, "n_out": b + 3, "params": lib_prm}
+    d_in, d_out, powers, regions = run(case)
+    assert tm.same_bits(powers.cpu().numpy().view(np.float64)[:blocks], want_powers).size == 0
+    got_regions = regions.cpu().numpy().view(afgpu.TRIM_REGION_DTYPE)
+    for field in ("begin", "end", "ref_power"):
+        assert tm.same_bits(np.ascontiguousarray(got_regions[field]), np.ascontiguousarray(want_regions[field])).size == 0, field
+    bad = tm.same_bits(d_out.cpu().numpy(), want_out)            # the sentinel's bits outside the slabs included
+    assert bad.size == 0, (bad.size, bad[:5].tolist())

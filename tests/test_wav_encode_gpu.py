@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import afgpu
+from record_cases import RECORD_CASES, record_lengths
 
 pytestmark = pytest.mark.gpu
 
@@ -265,3 +266,17 @@ def test_spans_outside_the_planes_are_not_touched(gpu):
         assert (out == 0xA5).all(), (piece.get("count"), piece.get("in_off"), piece.get("out_off"), kw)
     out, _ = pack(gpu, [ok])                                                      # and the same span inside the planes is packed
     same(out[:8192 * 2], model(x, afgpu.WAV_S16LE, False), "control")
+
+
+@pytest.mark.parametrize("case", RECORD_CASES)
+def test_record_counts_and_spans_without_tiles(gpu, case):
+    """1, 2 and 5 spans, with spans of no samples first, in the middle and last (record_cases.py): the tile search's edges"""
+    rng = np.random.default_rng(11)
+    pieces = [dict(x=rng.uniform(-1, 1, n).astype(np.float32), fmt=afgpu.WAV_S16LE, dither=True, seed=SEED + k)
+              for k, n in enumerate(record_lengths(afgpu.WAV_TILE_SAMPLES)[case])]
+    out, spans = pack(gpu, pieces)
+    want = np.full(out.size, 0xA5, np.uint8)
+    for p, sp in zip(pieces, spans):
+        body = model(p["x"], p["fmt"], True, seed=p["seed"])
+        want[int(sp["out_off"]):int(sp["out_off"]) + body.size] = body
+    same(out, want, case)

@@ -14,6 +14,7 @@ import mod_bitstream as mb
 import pocketmod_model as pm
 import wav_bitstream as wb
 import wav_model as M
+from record_cases import RECORD_CASES, record_lengths
 from test_flac_frontend import make_pcm
 from test_stream_gpu import MP3_FIXTURE, flac_expected, qoa_file
 
@@ -391,3 +392,11 @@ def test_damaged_file_sweep_streams(gpu):
             assert M.same_floats(buf[:got * model.channels], want, model.kind), (n, label)
     print(f"sweep: {len(files)} files, {opened} open, {failed_reads} ended in a failing read, {own} in the two own rules")
     assert own <= 0.05 * len(files) and opened >= 0.5 * len(files) and failed_reads >= 0.05 * len(files)
+
+
+@pytest.mark.parametrize("case", RECORD_CASES)
+def test_convert_record_counts_and_spans_without_tiles(gpu, case):
+    """1, 2 and 5 spans, with spans of no samples first, in the middle and last (record_cases.py): the tile search's edges"""
+    rng = np.random.default_rng(13)
+    convert(gpu, [(M.KIND_S16, rng.integers(0, 65536, n, dtype=np.uint64).astype("<u2").tobytes(), 2 * (k % 2), k % 4)
+                  for k, n in enumerate(record_lengths(afgpu.WAV_TILE_SAMPLES)[case])])
