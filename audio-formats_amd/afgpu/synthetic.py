@@ -365,9 +365,11 @@ def flac_batch_device(seed, n_files, frames_per_file, device, block_size=4096, b
 
 # ----------------------------------------------------------------- CELT ------
 
-def celt_batch(seed, frames_per_stream, channels, p_transient=0.15, p_postfilter=0.3, frame_sizes=(960,)):
+def celt_batch(seed, frames_per_stream, channels, p_transient=0.15, p_postfilter=0.3, frame_sizes=(960,), imdct_scale=1.0):
     """numpy batch of CELT transform-stage records.  One channel sequence per (stream, channel);
-    output interleaved per stream ([frame][sample][channel]).  Returns (rec_base, recs, coeffs, out_total)."""
+    output interleaved per stream ([frame][sample][channel]).  imdct_scale: one value for every stream or one per stream
+    (0.5 is the stereo -> mono downmix).  Returns (rec_base, recs, coeffs, out_total)."""
+    scales = np.broadcast_to(np.asarray(imdct_scale, np.float32), (len(frames_per_stream),))
     taps = np.array([[0.3066406250, 0.2170410156, 0.1296386719], [0.4638671875, 0.2680664062, 0.0],
                      [0.7998046875, 0.1000976562, 0.0]], np.float32)            # dopus.d:3382-3386
     recs, rec_base, coefs = [], [0], []
@@ -398,7 +400,7 @@ def celt_batch(seed, frames_per_stream, channels, p_transient=0.15, p_postfilter
                 k = np.arange(fs, dtype=np.float64)
                 x = rng.standard_normal(fs) * 2000.0 * 10.0 ** (-(k / fs) * 2.0)
                 coefs.append(x.astype(np.float32))
-                recs.append((coef_off, out_base + int(starts[f]) * C + c, C, fs, blocks, 0, per, tuple(g), 1.0, 0))
+                recs.append((coef_off, out_base + int(starts[f]) * C + c, C, fs, blocks, 0, per, tuple(g), float(scales[s]), 0))
                 coef_off += fs
             rec_base.append(len(recs))
         out_base += int(starts[-1]) * C

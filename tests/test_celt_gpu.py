@@ -41,6 +41,7 @@ def check(got, want):
     dict(frames_per_stream=[12], channels=[2], p_transient=1.0, p_postfilter=1.0),
     dict(frames_per_stream=[10, 7], channels=[1, 2], frame_sizes=(120, 240, 480, 960), p_transient=0.5, p_postfilter=0.6),
     dict(frames_per_stream=[8], channels=[1], p_postfilter=0.0),
+    dict(frames_per_stream=[5, 4, 6], channels=[1, 2, 1], frame_sizes=(120, 480, 960), p_transient=0.4, imdct_scale=[0.5, 1.0, 0.5]),
 ])
 def test_celt_matches_oracle(gpu, kw):
     rec_base, recs, coeffs, total = synthetic.celt_batch(5, **kw)

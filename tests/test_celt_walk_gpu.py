@@ -53,6 +53,7 @@ CASES = [
     dict(frames_per_stream=[10, 7], channels=[1, 2], frame_sizes=(120, 240, 480, 960), p_transient=0.5, p_postfilter=0.6),
     dict(frames_per_stream=[8], channels=[1], p_postfilter=0.0),
     dict(frames_per_stream=[3] * 42, channels=[2] * 37 + [1] * 5, p_postfilter=0.5),
+    dict(frames_per_stream=[5, 4, 6], channels=[1, 2, 1], frame_sizes=(120, 480, 960), p_transient=0.4, imdct_scale=[0.5, 1.0, 0.5]),
 ]
 
 
