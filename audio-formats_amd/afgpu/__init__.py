@@ -99,6 +99,12 @@ PVOC_ROW_DTYPE = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), ("rate
                            ("in_pitch", np.uint32), ("out_frames", np.uint32), ("out_pitch", np.uint32), ("reserved", np.uint32, (2,))])
 assert PVOC_ROW_DTYPE.itemsize == 48
 PVOC_KA, PVOC_KP, PVOC_CHUNK, PVOC_TILE = 2, 52, 4, 256      # AFG_PVOC_*
+# afg_convolve_kernel: one kernel of a bank; afg_convolve_row: one row, one kernel and the range of their line (afg_convolve_hip)
+CONV_KERNEL_DTYPE = np.dtype([("bank_off", np.uint64), ("spec_off", np.uint64), ("taps", np.uint32), ("reserved", np.uint32)])
+CONV_ROW_DTYPE = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), ("first_tile", np.uint64), ("work_off", np.uint64),
+                           ("frames", np.uint32), ("kernel", np.uint32), ("out_first", np.uint32), ("out_frames", np.uint32)])
+assert CONV_KERNEL_DTYPE.itemsize == 24 and CONV_ROW_DTYPE.itemsize == 48
+CONV_BLOCK, CONV_MAX_TAPS, CONV_DIRECT_MAX, CONV_DIRECT_TILE, CONV_TABLE_FLOATS, CONV_SPEC_FLOATS = 1024, 65536, 128, 4096, 4096, 2050   # AFG_CONV_*
 LOUDNESS_K = 64                                  # AFG_LOUDNESS_K
 LOUDNESS_UNGATED, LOUDNESS_GAIN_CLAMPED, LOUDNESS_PEAK_CLAMPED = 1, 2, 4     # afg_loudness_stats.flags
 
@@ -146,6 +152,8 @@ ABI_SYMBOLS = [
     "afg_kweight_design", "afg_loudness_lufs", "afg_loudness_layout", "afg_loudness_check_groups", "afg_loudness_hip", "afg_batch_decode_loudnorm",
     "afg_istft_tile_samples", "afg_istft_layout", "afg_istft_envelope_min", "afg_istft_check_rows", "afg_istft_hip",
     "afg_pvoc_out_frames", "afg_pvoc_bound", "afg_pvoc_check_rows", "afg_pvoc_hip",
+    "afg_convolve_bank_layout", "afg_convolve_bank_check", "afg_convolve_bank_hip", "afg_convolve_layout", "afg_convolve_bound",
+    "afg_convolve_check_rows", "afg_convolve_hip",
 ]
 
 
@@ -316,6 +324,11 @@ class IstftParams(C.Structure):
 class PvocParams(C.Structure):
     """afg_pvoc_params (afg_pvoc_hip)."""
     _fields_ = [("n_fft", C.c_uint32), ("hop", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+
+class ConvolveParams(C.Structure):
+    """afg_convolve_params (afg_convolve_hip)."""
+    _fields_ = [("direct_max", C.c_uint32), ("reserved", C.c_uint32 * 7)]
 
 
 class StftOpts(C.Structure):
@@ -731,6 +744,16 @@ def lib():
     L.afg_pvoc_bound.restype = C.c_double
     L.afg_pvoc_check_rows.argtypes = [vp, u64, C.POINTER(PvocParams), u64, u64]
     L.afg_pvoc_hip.argtypes = [u64, vp, C.POINTER(PvocParams), vp, u64, vp, u64, vp]
+    L.afg_convolve_bank_layout.argtypes = [vp, u64]
+    L.afg_convolve_bank_layout.restype = u64
+    L.afg_convolve_bank_check.argtypes = [vp, u64, u64, u64]
+    L.afg_convolve_bank_hip.argtypes = [u64, vp, vp, u64, vp, u64, vp]
+    L.afg_convolve_layout.argtypes = [vp, u64, vp, u64, C.POINTER(ConvolveParams), C.POINTER(u64)]
+    L.afg_convolve_layout.restype = u64
+    L.afg_convolve_bound.argtypes = [C.POINTER(ConvolveParams), u32]
+    L.afg_convolve_bound.restype = C.c_double
+    L.afg_convolve_check_rows.argtypes = [vp, u64, u64, vp, u64, C.POINTER(ConvolveParams), u64, u64, u64, u64, u64, C.POINTER(u64)]
+    L.afg_convolve_hip.argtypes = [u64, vp, u64, vp, u64, C.POINTER(ConvolveParams), vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, vp]
     _lib = L
     _sync_dev_options(L)
     return L
@@ -2789,6 +2812,172 @@ def time_stretch_tensor(wave, rate, n_fft=400, hop=160, win_length=None, valid=N
     most = int(lengths.max()) if n else 0
     y = istft_tensor(torch.view_as_complex(stretched), n_fft, hop, win_length, True, length=most, valid_frames=counts, _counts=lengths)
     return y, lengths.reshape(lead)
+
+
+def convolve_params(direct_max=CONV_DIRECT_MAX):
+    """afg_convolve_params: kernels of at most direct_max taps (0 .. 128) take the direct path, every other the FFT path."""
+    return ConvolveParams(int(direct_max))
+
+
+def convolve_bank_layout(kernels):
+    """afg_convolve_bank_layout: fills spec_off of a CONV_KERNEL_DTYPE array in place; returns the spectrum plane's floats
+    (the table and one spectrum per partition of 1024 taps).  AfgError for taps out of range."""
+    assert kernels.dtype == CONV_KERNEL_DTYPE and kernels.flags.c_contiguous
+    need = int(lib().afg_convolve_bank_layout(kernels.ctypes.data, len(kernels)))
+    if need == 0:
+        raise AfgError(lib().afg_last_error().decode())
+    return need
+
+
+def convolve_bank_check(kernels, bank_floats, spec_floats):
+    """afg_convolve_bank_check: what afg_convolve_bank_hip checks before it launches, on host records.  AfgError when one fails."""
+    assert kernels.dtype == CONV_KERNEL_DTYPE and kernels.flags.c_contiguous
+    check(lib().afg_convolve_bank_check(kernels.ctypes.data, len(kernels), int(bank_floats), int(spec_floats)))
+
+
+def convolve_bank(n_kernels, d_kernels, d_bank, bank_floats, d_spec, spec_floats, stream=None):
+    """Enqueue the bank transform (afg_convolve_bank_hip): the table and every partition's spectrum into d_spec, one launch.
+    The records are checked first (the call waits for `stream` to read them): AfgError, and nothing written, when one fails."""
+    check(lib().afg_convolve_bank_hip(int(n_kernels), _ptr(d_kernels), _ptr(d_bank), int(bank_floats), _ptr(d_spec), int(spec_floats),
+                                      _stream(stream)))
+
+
+def convolve_layout(rows, kernels, params):
+    """afg_convolve_layout: fills first_tile and work_off of a CONV_ROW_DTYPE array in place; returns (tiles, work floats)."""
+    assert rows.dtype == CONV_ROW_DTYPE and rows.flags.c_contiguous and kernels.dtype == CONV_KERNEL_DTYPE and kernels.flags.c_contiguous
+    work = C.c_uint64(0)
+    L = lib()
+    tiles = int(L.afg_convolve_layout(rows.ctypes.data, len(rows), kernels.ctypes.data, len(kernels), C.byref(params), C.byref(work)))
+    if tiles == 0 and (rows["out_frames"] > 0).any():        # (rows with output have tiles: the parameters or a kernel index were refused)
+        raise AfgError(L.afg_last_error().decode())
+    return tiles, int(work.value)
+
+
+def convolve_bound(params, taps):
+    """afg_convolve_bound: C of the FFT path's interval E[b] = C * 2^-24 * S[b] for a kernel of `taps`."""
+    c = float(lib().afg_convolve_bound(C.byref(params), int(taps)))
+    if c < 0.0:
+        raise AfgError(lib().afg_last_error().decode())
+    return c
+
+
+def convolve_check_rows(rows, n_tiles, kernels, params, in_floats, bank_floats, spec_floats, work_floats, out_floats, plane_at=None):
+    """afg_convolve_check_rows: what afg_convolve_hip checks before it launches, on host records.  plane_at: None, or the float
+    index of the first float of the input, bank, spectrum, work and output plane in one address space.  AfgError when a check fails."""
+    assert rows.dtype == CONV_ROW_DTYPE and rows.flags.c_contiguous and kernels.dtype == CONV_KERNEL_DTYPE and kernels.flags.c_contiguous
+    at = None if plane_at is None else (C.c_uint64 * 5)(*[int(v) for v in plane_at])
+    check(lib().afg_convolve_check_rows(rows.ctypes.data, len(rows), int(n_tiles), kernels.ctypes.data, len(kernels), C.byref(params),
+                                        int(in_floats), int(bank_floats), int(spec_floats), int(work_floats), int(out_floats), at))
+
+
+def convolve(n_rows, d_rows, n_tiles, d_kernels, n_kernels, params, d_in, in_floats, d_bank, bank_floats, d_spec, spec_floats, d_work,
+             work_floats, d_out, out_floats, stream=None):
+    """Enqueue the convolution (afg_convolve_hip) on device arrays: rows laid out by convolve_layout, a bank transformed by
+    convolve_bank, a work plane of convolve_layout's size; at most three launches.  The records are checked first (the call
+    waits for `stream` to read them): AfgError, and nothing written, when a check fails."""
+    check(lib().afg_convolve_hip(int(n_rows), _ptr(d_rows), int(n_tiles), _ptr(d_kernels), int(n_kernels), C.byref(params), _ptr(d_in),
+                                 int(in_floats), _ptr(d_bank), int(bank_floats), _ptr(d_spec), int(spec_floats), _ptr(d_work), int(work_floats),
+                                 _ptr(d_out), int(out_floats), _stream(stream)))
+
+
+class ConvolveBank:
+    """A bank of convolution kernels on one device, built once: `kernels` is a list of 1-D float32 arrays or tensors (FIR
+    taps, impulse responses; 1 .. 65536 values each).  Holds the device bank, the kernel records (host and device) and the
+    partition spectra (afg_convolve_bank_hip, run here on the current stream)."""
+
+    def __init__(self, kernels, device=None):
+        import torch
+        hs = [np.ascontiguousarray(k.detach().cpu().numpy() if hasattr(k, "detach") else k, dtype=np.float32) for k in kernels]
+        if not hs or any(h.ndim != 1 for h in hs):
+            raise ValueError("ConvolveBank: a list of at least one 1-D array")
+        if any(h.size < 1 or h.size > CONV_MAX_TAPS for h in hs):
+            raise ValueError(f"ConvolveBank: kernels of 1 .. {CONV_MAX_TAPS} taps")
+        self.taps = np.array([h.size for h in hs], np.int64)
+        self.records = np.zeros(len(hs), CONV_KERNEL_DTYPE)
+        self.records["taps"] = self.taps
+        self.records["bank_off"] = np.concatenate([[0], np.cumsum(self.taps)[:-1]])
+        self.spec_floats = convolve_bank_layout(self.records)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        with torch.cuda.device(self.device):
+            self.bank = torch.from_numpy(np.concatenate(hs)).to(self.device)
+            self.d_records = torch.from_numpy(self.records.view(np.uint8)).to(self.device)
+            self.spec = torch.empty(self.spec_floats, dtype=torch.float32, device=self.device)
+            convolve_bank(len(hs), self.d_records, self.bank, self.bank.numel(), self.spec, self.spec_floats, torch.cuda.current_stream().cuda_stream)
+
+    def __len__(self):
+        return len(self.records)
+
+
+def convolve_tensor(t, bank, kernel=0, mode="full", first=None, valid=None, out=None, direct_max=CONV_DIRECT_MAX):
+    """Convolve every row of a contiguous float32 device tensor along its last axis with a kernel of a ConvolveBank
+    (afg_convolve_hip on the current stream; include/afg.h has the definition).  kernel: one index, or one per row (the
+    leading axes flattened).  valid: None, or one length per row, as in filter_tensor.  With n the row's length and T its
+    kernel's taps, mode "full" delivers the n + T - 1 samples of the line, "same" n samples from (T - 1) // 2, and "head" n
+    samples from `first` (default 0; one value or one per row, at most T - 1) -- a reverb that keeps the length, with
+    first = the response's peak.  The work plane is allocated here and freed behind the launch on the current stream.
+    Returns a tensor whose last axis is the longest delivered length, with +0.0 behind each row's own; out: None, or a
+    contiguous float32 tensor of that shape on t's device that does not overlap t."""
+    import torch
+    prm = convolve_params(direct_max)
+    if prm.direct_max > CONV_DIRECT_MAX:
+        raise ValueError(f"convolve_tensor: direct_max 0 .. {CONV_DIRECT_MAX}")
+    if not isinstance(bank, ConvolveBank):
+        raise ValueError("convolve_tensor: bank is a ConvolveBank")
+    if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 1 or t.device != bank.device:
+        raise ValueError("convolve_tensor: a contiguous float32 tensor with at least one axis on the bank's device")
+    if mode not in ("full", "same", "head"):
+        raise ValueError('convolve_tensor: mode is "full", "same" or "head"')
+    if first is not None and mode != "head":
+        raise ValueError('convolve_tensor: first goes with mode "head"')
+    lead, frames = tuple(t.shape[:-1]), int(t.shape[-1])
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    if frames >= (1 << 31) - CONV_MAX_TAPS:
+        raise ValueError("convolve_tensor: rows of 2^31 - 65536 frames or more")
+
+    def per_row(v, what, hi):
+        a = np.asarray(v.cpu() if hasattr(v, "cpu") else v).reshape(-1).astype(np.int64)
+        a = np.broadcast_to(a, (n,)) if a.size == 1 else a
+        if a.size != n or (a < 0).any() or (a > hi).any():
+            raise ValueError(f"convolve_tensor: {what}")
+        return a
+
+    named = np.asarray(kernel.cpu() if hasattr(kernel, "cpu") else kernel).reshape(-1)
+    if named.size not in (1, n):
+        raise ValueError(f"convolve_tensor: kernel is one index or one per row, 0 .. {len(bank) - 1}")
+    k = per_row(kernel, f"kernel is one index or one per row, 0 .. {len(bank) - 1}", len(bank) - 1)
+    taps = bank.taps[k]
+    length = per_row(frames if valid is None else valid, "valid holds one length per row, 0 .. the last axis", frames)
+    if mode == "full":
+        start, count = np.zeros(n, np.int64), np.where(length > 0, length + taps - 1, 0)
+    elif mode == "same":
+        start, count = (taps - 1) // 2, length
+    else:
+        start = per_row(0 if first is None else first, "first is one value or one per row, 0 .. taps - 1", CONV_MAX_TAPS)
+        if (start > taps - 1).any():
+            raise ValueError("convolve_tensor: first is one value or one per row, 0 .. taps - 1")
+        count = length
+    # (a row's widest delivery: its whole axis, whatever `valid` says, so that the shape does not depend on the lengths)
+    widest = int(frames + bank.taps[named.astype(np.int64)].max() - 1) if mode == "full" and frames and named.size else frames
+    shape = lead + (widest,)
+    if out is None:
+        out = torch.zeros(shape, dtype=torch.float32, device=t.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != t.device or not out.is_contiguous():
+        raise ValueError(f"convolve_tensor: out must be a contiguous float32 tensor of shape {shape} on t's device")
+    elif n and (count < widest).any():
+        out.zero_()
+    if n == 0 or frames == 0:
+        return out
+    rows = np.zeros(n, CONV_ROW_DTYPE)
+    rows["in_off"] = np.arange(n, dtype=np.uint64) * np.uint64(frames)
+    rows["out_off"] = np.arange(n, dtype=np.uint64) * np.uint64(widest)
+    rows["frames"], rows["kernel"], rows["out_first"], rows["out_frames"] = length, k, start, count
+    tiles, work_floats = convolve_layout(rows, bank.records, prm)
+    with torch.cuda.device(t.device):
+        d_rows = torch.from_numpy(rows.view(np.uint8)).to(t.device)
+        work = torch.empty(max(work_floats, 2), dtype=torch.float32, device=t.device)      # (freed behind the launch: the caching allocator's stream order)
+        convolve(n, d_rows, tiles, bank.d_records, len(bank), prm, t, t.numel(), bank.bank, bank.bank.numel(), bank.spec, bank.spec_floats,
+                 work, work_floats, out, out.numel(), torch.cuda.current_stream().cuda_stream)
+    return out
 
 
 def lds_fill(word=0x7fc00000, stream=None):

@@ -598,6 +598,27 @@ double afg_pvoc_bound(const(afg_pvoc_params)* params, ulong t);
 int afg_pvoc_check_rows(const(afg_pvoc_row)* rows, ulong n_rows, const(afg_pvoc_params)* params, ulong in_floats, ulong out_floats);
 int afg_pvoc_hip(ulong n_rows, const(afg_pvoc_row)* d_rows, const(afg_pvoc_params)* params, const(float)* d_in, ulong in_floats,
                  float* d_out, ulong out_floats, void* hip_stream);
+// convolution of waveform rows with the kernels of a bank: a direct path for kernels of at most direct_max taps (bits), a
+// partitioned overlap-save FFT path for the rest (an interval); include/afg.h has the definition, the bound and the checks
+enum AFG_CONV_BLOCK = 1024, AFG_CONV_MAX_TAPS = 65536, AFG_CONV_DIRECT_MAX = 128, AFG_CONV_DIRECT_TILE = 4096,
+     AFG_CONV_TABLE_FLOATS = 4096, AFG_CONV_SPEC_FLOATS = 2050;
+struct afg_convolve_params { uint direct_max; uint[7] reserved; }
+struct afg_convolve_kernel { ulong bank_off, spec_off; uint taps, reserved; }
+struct afg_convolve_row { ulong in_off, out_off, first_tile, work_off; uint frames, kernel, out_first, out_frames; }
+ulong afg_convolve_bank_layout(afg_convolve_kernel* kernels, ulong n_kernels);
+int afg_convolve_bank_check(const(afg_convolve_kernel)* kernels, ulong n_kernels, ulong bank_floats, ulong spec_floats);
+int afg_convolve_bank_hip(ulong n_kernels, const(afg_convolve_kernel)* d_kernels, const(float)* d_bank, ulong bank_floats, float* d_spec,
+                          ulong spec_floats, void* hip_stream);
+ulong afg_convolve_layout(afg_convolve_row* rows, ulong n_rows, const(afg_convolve_kernel)* kernels, ulong n_kernels,
+                          const(afg_convolve_params)* params, ulong* work_floats);
+double afg_convolve_bound(const(afg_convolve_params)* params, uint taps);
+int afg_convolve_check_rows(const(afg_convolve_row)* rows, ulong n_rows, ulong n_tiles, const(afg_convolve_kernel)* kernels, ulong n_kernels,
+                            const(afg_convolve_params)* params, ulong in_floats, ulong bank_floats, ulong spec_floats, ulong work_floats,
+                            ulong out_floats, const(ulong)* plane_at);
+int afg_convolve_hip(ulong n_rows, const(afg_convolve_row)* d_rows, ulong n_tiles, const(afg_convolve_kernel)* d_kernels, ulong n_kernels,
+                     const(afg_convolve_params)* params, const(float)* d_in, ulong in_floats, const(float)* d_bank, ulong bank_floats,
+                     const(float)* d_spec, ulong spec_floats, float* d_work, ulong work_floats, float* d_out, ulong out_floats,
+                     void* hip_stream);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

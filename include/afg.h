@@ -2094,6 +2094,137 @@ int afg_pvoc_check_rows(const afg_pvoc_row *rows, uint64_t n_rows, const afg_pvo
 int afg_pvoc_hip(uint64_t n_rows, const afg_pvoc_row *d_rows, const afg_pvoc_params *params, const float *d_in, uint64_t in_floats,
                  float *d_out, uint64_t out_floats, void *hip_stream);
 
+/* Convolution of waveform rows with finite kernels: y = h * x for FIR filters, room impulse responses and short smoothing
+ * kernels.  The reference has no such stage.  tests/convolve_model.py holds the float64 definition, the float32 restatement
+ * of the direct path, S[b] and the interval below.
+ *
+ * Definition.  A row is `frames` float32 samples x at in_off of the input plane, x[m] = 0 for m outside [0, frames).  A
+ * kernel is `taps` >= 1 float32 values h at bank_off of the bank plane (afg_convolve_kernel, 24 bytes).  A record
+ * (afg_convolve_row, 48 bytes) names one row and one kernel of the bank by index: rows may share a kernel or each have
+ * their own.  Line sample n = 0 .. frames + taps - 2 is, over the real numbers,
+ *   y[n] = sum over k = 0 .. taps - 1 with 0 <= n - k < frames of h[k] x[n - k],
+ * and the record delivers out_frames samples from out_first at out_off; out_first + out_frames <= frames + taps - 1 must
+ * hold.  "full" is out_first = 0, out_frames = frames + taps - 1; "same" is out_first = (taps - 1) / 2, out_frames =
+ * frames; a reverb that keeps the file's length and its direct-path alignment is out_first = the index of the response's
+ * peak, out_frames = frames.  There is no in-place form: an output shares no float with any input row, the bank, the
+ * spectra, the work plane or another output.
+ *
+ * Two paths, chosen per kernel by its length: a kernel of at most afg_convolve_params.direct_max taps (0 ..
+ * AFG_CONV_DIRECT_MAX = 128) takes the direct path, every other kernel the FFT path; direct_max = 0 sends everything
+ * through the FFT path.
+ *
+ * Direct path: bits.  One launch for all direct rows, a workgroup per tile of AFG_CONV_DIRECT_TILE delivered samples.
+ * Every sample is
+ *   acc = +0.0f;  for k ascending over the terms inside the row:  acc = fmaf(h[k], x[n - k], acc)
+ * -- terms outside the row are skipped, not multiplied by zero -- and the result is that float32 bit pattern whatever the
+ * tile, the lane, out_first or the place of the row.  A NaN at input sample m reaches exactly the line samples [m, m + taps).
+ *
+ * FFT path: an interval.  Uniformly partitioned overlap-save on the transform of the STFT stages (csrc/fft_frame.h) with one
+ * block length B = AFG_CONV_BLOCK = 1024 and n_fft = 2 B.  A kernel of `taps` has P = ceil(taps / B) partitions; taps goes
+ * up to AFG_CONV_MAX_TAPS = 65536 (P <= 64), more is AFG_ERR_UNSUPPORTED.  The block grid is anchored to the line: block b
+ * holds line samples [b B, (b + 1) B), whatever out_first is.
+ *   The spectrum plane d_spec (afg_convolve_bank_layout gives its size and every kernel's spec_off; 8-byte aligned) starts
+ * with the transform's table -- AFG_CONV_TABLE_FLOATS floats, the 2048 pairs (cos, -sin) of afg_mel_fft_tables -- and holds
+ * per kernel P spectra of AFG_CONV_SPEC_FLOATS floats: the 1025 pairs (re, im) of the forward real transform of partition p,
+ * h[p B .. p B + B) in the first B places of 2 B and zeros behind.  afg_convolve_bank_hip makes the plane: the table is
+ * copied in and one launch transforms every partition.  A fixed bank of responses is transformed once and reused over every
+ * batch; afg_convolve_hip never writes d_spec.
+ *   afg_convolve_hip queues two launches for its FFT rows.  (a) The forward spectrum of every input block pair
+ * x[(j - 1) B .. (j + 1) B), zero outside the row, that an output block of the record needs, into the caller's work plane
+ * d_work (8-byte aligned; afg_convolve_layout gives its size and every row's work_off): pairs j_lo .. j_hi with
+ * j_lo = max(0, b_lo - P + 1), j_hi = min(b_hi, (frames - 1) / B + 1), b_lo and b_hi the first and last block of the
+ * delivered range -- about twice the input plus one block per row.  (b) One wavefront per output block forms
+ *   Y[k] = sum over p = 0 .. P - 1 of H_p[k] X_{b-p}[k]      in ascending p from +0.0f,
+ * each term the four products and two sums of the complex product, unfused; pairs wholly outside the row (b - p < 0 or
+ * b - p > (frames - 1) / B + 1) are skipped.  Then the split pass backwards (fft_unsplit_bin) with the scale 1 / n_fft, the
+ * inverse complex transform, and the last B samples of the 2 B are delivered as v + (+0.0f), cropped to the record's range.
+ * No floating-point atomics: the same (row, kernel) gives the same bits wherever it stands in the batch, in whichever
+ * launch, and for any out_first / out_frames that deliver the same line sample.
+ *
+ * Bound of the FFT path.  u = 2^-24, B_f = 8 ceil(log2 2048) + 8 = 96 per transform (the forward path's: each component of
+ * a bin within B_f u A of its float64 value, A the sum of |input|).  A_x(j) = the sum of |x| over block pair j, A_h(p) = the
+ * sum of |h| over partition p, S[b] = sum over p of A_h(p) A_x(b - p).  Every delivered sample of block b lies within
+ *   E[b] = C u S[b],   C = 6 B_f + 2 P + 11   (afg_convolve_bound; 589 at P = 1, 715 at P = 64)
+ * of the float64 value.  Counted per component, to first order, before the first run:
+ *   the two forward transforms entering a product: with |X| <= A_x, |H| <= A_h and component errors B_f u A_x, B_f u A_h
+ *       a component of H X moves by at most 2 sqrt(2) B_f u A_h A_x:                                       3 B_f
+ *   the complex product: two rounded products and their rounded sum, 2 u (|ac| + |bd|) <= 2 u A_h A_x:    2
+ *   the sum of at most P terms in fixed order from +0.0f, P - 1 roundings of partial sums within S:        P
+ *   so a component of Y is within (3 B_f + 2 + P) u S; the exact inverse, a sum of re cos - im sin over the bins with
+ *       weights c_k / n_fft that add up to 1, takes that to at most sqrt(2) (3 B_f + 2 + P) u S:            4.5 B_f + 3 + 1.5 P
+ *   the inverse's own arithmetic, B_f u A' with A' = (1 / n_fft) sum of c_k (|re_k| + |im_k|) <= sqrt(2) S: 1.5 B_f
+ *   the scale 1 / n_fft is a power of two and v + 0.0f is exact; second-order terms and the roundings up:   8 + 0.5 P
+ * The largest share of E[b] used over the GPU suite is measured, not fixed: DESIGN.md has it.
+ *
+ * NaN.  An FFT row's spectrum of a pair that holds a NaN is NaN in every bin, and a block whose Y holds a NaN is delivered
+ * as NaN whole (wavefront votes: containment is stated per block).  So a NaN at input sample m of an FFT row may reach
+ * only delivered samples of blocks floor(m / B) .. floor(m / B) + P + 1 of that row, and reaches all of [m, m + taps) inside
+ * the delivered range; on the direct path it reaches exactly [m, m + taps).  Other rows are untouched bit for bit.  An
+ * all-zero row gives +0.0f on both paths.  A record with out_frames = 0 reads and writes nothing.  Exactly out_frames
+ * floats are written per record; no input float outside [in_off, in_off + frames) is read, and no bank float outside a
+ * kernel's taps.  The stage does not listen to AFG_NUMERIC or afg_set_numeric_mode.
+ *
+ * Host entries.  afg_convolve_bank_layout: host only; fills spec_off of every kernel (AFG_CONV_TABLE_FLOATS +
+ * AFG_CONV_SPEC_FLOATS * the partitions before it) and returns the spectrum plane's floats; 0 with afg_last_error set for
+ * taps 0 (AFG_ERR_INVALID's case) or above 65536.  afg_convolve_bank_check: host only; taps 1 .. 65536 (0: AFG_ERR_INVALID,
+ * more: AFG_ERR_UNSUPPORTED), reserved 0, the taps inside [0, bank_floats), spec_off as the layout gives it, spec_floats at
+ * least the layout's.  afg_convolve_bank_hip: fetches d_kernels on hip_stream, waits, makes those checks and refuses a
+ * spectrum plane that overlaps the bank; then the copy and the launch.  afg_convolve_layout: host only; fills first_tile
+ * and work_off of every row and returns the tile count -- a direct row has ceil(out_frames / AFG_CONV_DIRECT_TILE) tiles,
+ * an FFT row one per block its range meets -- and *work_floats (AFG_CONV_SPEC_FLOATS per pair; 0 with nothing on the FFT
+ * path); 0 with afg_last_error set for parameters out of range or a kernel index outside the bank.  afg_convolve_bound:
+ * host only; C for a kernel of `taps` (negative with afg_last_error set when taps or the parameters are out of range).
+ * afg_convolve_check_rows: host only, needs no device; the checks afg_convolve_hip makes before it launches, on host
+ * copies of the records: direct_max <= 128 and reserved words 0; the bank's checks; first_tile, work_off, n_tiles as the
+ * layout gives them and work_floats at least its figure; per record a kernel index inside the bank, and with output asked
+ * for: frames 1 .. 2^31 - 65536; the row inside [0, in_floats); the output inside [0, out_floats); out_first + out_frames
+ * <= frames + taps - 1.  plane_at: NULL, or the float index of the first float of the input, bank, spectrum, work and
+ * output plane (in that order) in one address space, for planes that share an allocation: then an output that meets an
+ * input row, the bank, the spectra, the work plane or another output is refused, and so is a work plane that meets the
+ * input plane, the bank or the spectra.  Everything is AFG_ERR_INVALID unless said otherwise, and afg_last_error says
+ * which.  afg_convolve_hip fetches d_rows and d_kernels on hip_stream, waits, makes the same checks with plane_at taken
+ * from the pointers, and queues at most three launches; on anything but a pass nothing is written. */
+#define AFG_CONV_BLOCK        1024
+#define AFG_CONV_MAX_TAPS     65536
+#define AFG_CONV_DIRECT_MAX   128
+#define AFG_CONV_DIRECT_TILE  4096
+#define AFG_CONV_TABLE_FLOATS 4096
+#define AFG_CONV_SPEC_FLOATS  2050
+typedef struct afg_convolve_params {  /* 32 bytes */
+    uint32_t direct_max;           /* kernels of at most this many taps take the direct path: 0 .. 128 */
+    uint32_t reserved[7];          /* 0 */
+} afg_convolve_params;
+typedef struct afg_convolve_kernel {  /* one kernel of the bank (24 bytes) */
+    uint64_t bank_off;             /* float index of h[0] in the bank plane */
+    uint64_t spec_off;             /* float index of its first spectrum in d_spec: filled in by afg_convolve_bank_layout */
+    uint32_t taps;                 /* 1 .. 65536 */
+    uint32_t reserved;             /* 0 */
+} afg_convolve_kernel;
+typedef struct afg_convolve_row {     /* one row, one kernel, out_frames samples of their line (48 bytes) */
+    uint64_t in_off;               /* float index of x[0] */
+    uint64_t out_off;              /* float index of the first delivered sample */
+    uint64_t first_tile;           /* filled in by afg_convolve_layout */
+    uint64_t work_off;             /* likewise: float index of the row's first input spectrum in d_work */
+    uint32_t frames;               /* samples of the row */
+    uint32_t kernel;               /* index into the bank's records */
+    uint32_t out_first;            /* first delivered sample of the line */
+    uint32_t out_frames;           /* samples written */
+} afg_convolve_row;
+uint64_t afg_convolve_bank_layout(afg_convolve_kernel *kernels, uint64_t n_kernels);
+int afg_convolve_bank_check(const afg_convolve_kernel *kernels, uint64_t n_kernels, uint64_t bank_floats, uint64_t spec_floats);
+int afg_convolve_bank_hip(uint64_t n_kernels, const afg_convolve_kernel *d_kernels, const float *d_bank, uint64_t bank_floats, float *d_spec,
+                          uint64_t spec_floats, void *hip_stream);
+uint64_t afg_convolve_layout(afg_convolve_row *rows, uint64_t n_rows, const afg_convolve_kernel *kernels, uint64_t n_kernels,
+                             const afg_convolve_params *params, uint64_t *work_floats);
+double afg_convolve_bound(const afg_convolve_params *params, uint32_t taps);
+int afg_convolve_check_rows(const afg_convolve_row *rows, uint64_t n_rows, uint64_t n_tiles, const afg_convolve_kernel *kernels, uint64_t n_kernels,
+                            const afg_convolve_params *params, uint64_t in_floats, uint64_t bank_floats, uint64_t spec_floats, uint64_t work_floats,
+                            uint64_t out_floats, const uint64_t *plane_at);
+int afg_convolve_hip(uint64_t n_rows, const afg_convolve_row *d_rows, uint64_t n_tiles, const afg_convolve_kernel *d_kernels, uint64_t n_kernels,
+                     const afg_convolve_params *params, const float *d_in, uint64_t in_floats, const float *d_bank, uint64_t bank_floats,
+                     const float *d_spec, uint64_t spec_floats, float *d_work, uint64_t work_floats, float *d_out, uint64_t out_floats,
+                     void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
