@@ -1,37 +1,23 @@
-// vorbis_transform.hip -- Vorbis inverse MDCT + window/overlap-add on gfx950.
+// vorbis_transform.hip -- Vorbis inverse MDCT + window/overlap-add on gfx950, bit for bit the reference's.
 //
-// Replaces, for whole batches of streams, reference stb_vorbis2.d:2526-2527
-// (inverse_mdct per channel, :1941-2242), vorbis_finish_frame (:2606-2657) and
-// the interleave of stb_vorbis_get_samples_float_interleaved (:3927-3952).
-// Every output sample is produced by the same float32 expression tree as the
-// reference (library built with -ffp-contract=off); only the schedule differs:
-//
-//   * a thread group (one wavefront, or a 256-thread workgroup for long blocks on the general path) walks `seg_packets`
-//     consecutive packets of ONE CHANNEL of one stream (the fast path: both channels of a stereo stream) with its working
-//     set resident in LDS; a segment that does not start at packet 0 first redoes the IMDCT of the preceding packet to
-//     get its right half (the only carried state, stb_vorbis2.d:2641-2643);
-//   * every pass of the reference's in-place algorithm is a set of independent
-//     butterflies; passes are spread over the group's threads, ordered by the hardware's in-order LDS queue within a
-//     wavefront and by a barrier across wavefronts.  Step 3's iter0 / inner_r / inner_s loops (:1720-1864)
-//     are one formula: stage l, group i < 2^(l+1), butterfly b < n >> (l+4):
+// Replaces, for whole batches of streams, reference stb_vorbis2.d:2526-2527 (inverse_mdct per channel, :1941-2242),
+// vorbis_finish_frame (:2606-2657) and the interleave of stb_vorbis_get_samples_float_interleaved (:3927-3952).
+// Every output sample is produced by the same float32 expression tree as the reference (library built with
+// -ffp-contract=off); only the schedule differs:
+//   * a thread group walks `seg_packets` consecutive packets of one stream with its working set resident in LDS; a
+//     segment that does not start at packet 0 first redoes the IMDCT of the preceding packet to get its right half (the
+//     only carried state, :2641-2643);
+//   * every pass of the reference's in-place algorithm is a set of independent butterflies spread over the group's
+//     threads, ordered by the hardware's in-order LDS queue within a wavefront and by a barrier across wavefronts.  Step
+//     3's iter0 / inner_r / inner_s loops (:1720-1864) are one formula: stage l, group i < 2^(l+1), butterfly b < n >> (l+4):
 //         p = n/2-1 - (n >> (l+2))*i - 2b,  q = p - (n >> (l+3)),  twiddle A[b << (l+3)]
-//   * spectra are read with coalesced row loads, PCM leaves as interleaved
-//     rows (a channel's column of them on the general path); twiddle/window tables (host-computed exactly as
-//     :851-881) are shared by all workgroups and served from L2 or staged in LDS.
-// Kernels: vorbis_wave_kernel (blocksize_1 = 2048, one or two channels: register passes), vorbis_channel_kernel (every
-// other stream).  The default numeric mode sends most streams to vorbis_walk.hip instead (afg_vorbis_transform_hip below).
+//   * spectra are read with coalesced row loads, PCM leaves as interleaved rows or a channel's column of them; the
+//     twiddle/window tables (host-computed exactly as :851-881) are shared by all workgroups: from L2, or staged in LDS.
+// Kernels: vorbis_wave_kernel (blocksize_1 = 2048, at most two channels: one transform written over the CH = 1 or 2
+// channels a wavefront carries, and a packet walk for each channel count) and vorbis_channel_kernel (every other stream: a wavefront or a
+// 256-thread workgroup per channel).  The default numeric mode sends most streams to vorbis_walk.hip instead
+// (afg_vorbis_transform_hip below).
 #include "afg_common.h"
-#ifndef AFG_VORBIS_NT_LOAD
-#define AFG_VORBIS_NT_LOAD 1   // nontemporal spectrum loads (0: plain -- A/B builds)
-#endif
-#ifndef AFG_VORBIS_NT_STORE
-#define AFG_VORBIS_NT_STORE 1  // nontemporal PCM stores in the wave kernel (0: plain stores -- A/B builds)
-#endif
-#if AFG_VORBIS_NT_STORE
-#define AFG_VORBIS_ST(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#else
-#define AFG_VORBIS_ST(ptr, val) (*(ptr) = (val))
-#endif
 #include "afg_pk.h"
 #include "vorbis_core.h"
 #include "vorbis_walk.h"
@@ -43,11 +29,9 @@
 
 namespace {
 
-#ifndef AFG_VORBIS_CHAN_WIDE
-#define AFG_VORBIS_CHAN_WIDE 2048    // long blocks from this size up: a 256-thread workgroup per channel
-#endif
-
 using namespace afg_vorbis;
+
+constexpr uint32_t kChanWide = 2048;    // long blocks from this size up: a 256-thread workgroup per channel
 
 // General path (round 5; round 1's version gave a 256-thread workgroup to a segment and walked its channels one after
 // the other with block-wide barriers between the reference's steps: 54-109 ms per C3-sized batch): ONE WAVEFRONT walks one
@@ -127,7 +111,7 @@ __global__ __launch_bounds__(T * CPG) void vorbis_channel_kernel(
 
 // the general path's launch shape for a stream set whose longest block has n samples
 struct ChannelShape { int threads, per_group; };
-inline ChannelShape channel_shape(uint32_t nmax) { return nmax >= AFG_VORBIS_CHAN_WIDE ? ChannelShape{ 256, 1 } : nmax > 1024 ? ChannelShape{ 64, 5 } : ChannelShape{ 64, 8 }; }
+inline ChannelShape channel_shape(uint32_t nmax) { return nmax >= kChanWide ? ChannelShape{ 256, 1 } : nmax > 1024 ? ChannelShape{ 64, 5 } : ChannelShape{ 64, 8 }; }
 
 template <int T, int CPG>
 int channel_launch(bool set_attr, uint32_t n_segs, uint32_t nmax, hipStream_t stream, const VorbisSeg *segs, const VorbisStream *streams,
@@ -162,6 +146,10 @@ int channel_dispatch(bool set_attr, uint32_t n_segs, uint32_t nmax, hipStream_t 
 // =========================================================================================
 // Fast path: one wavefront per (stream, packet segment), blocksize_1 == 2048, <= 2 channels.
 //
+// A wavefront carries CH channels of its segment: both channels of a stereo stream, or one channel (mono streams, and
+// stereo streams under the test option "vorbis_single").  The transform is written once over CH.  The packet walk is
+// kept per channel count (vorbis_wave_body, vorbis_wave2_body): a walk written over CH computes the same PCM, but the
+// compiler then arranges the window-and-store code of the last frame row differently, and the one-channel walk lost 0.7 %.
 // The whole transform of a channel lives in 8.7 KB of LDS: the n/4 = 512 complex points
 // E[m] = (u[n/2-1-2m], u[n/2-2-2m]) of the reference's step 3 are kept as float2 at index
 // m + (m >> 3) (one pad per 8 points: every access pattern below is conflict-free or 2-way),
@@ -169,22 +157,21 @@ int channel_dispatch(bool set_attr, uint32_t n_segs, uint32_t nmax, hipStream_t 
 // The 8 radix-2 stages of :2053-2090 run as three register passes (distances 128/64,
 // 32/16/8 and the reference's own fused 4/2/1 pass), steps 7 and 8 are fused (each step-7
 // butterfly feeds exactly two step-8 items), the spectrum is consumed straight from HBM
-// with 16-byte loads issued one transform ahead, the previous window half lives in
-// registers, and stereo PCM leaves as interleaved 8-byte stores.
+// with 16-byte loads issued one transform ahead, and the previous window half lives in registers.
+// Every pass issues the LDS reads of all CH channels, computes all, writes all: with two channels the second one's reads
+// are in flight while the first is computed (a one-channel walk spends half its life in s_waitcnt:
+// profiles/r02_pmc_vorbis_wave_kernel.json), and the tables are read once for both.
 // Arithmetic per output is the reference's, operation for operation.
 // =========================================================================================
 constexpr int kNL = 2048;
 constexpr int kUFloats = kNL / 2 + kNL / 16;       // 1152: padded complex buffer
 constexpr int kWaveLds = kUFloats + kNL / 2;        // + buf2 = 2176 floats >= n
+constexpr int kDualStride = kWaveLds;               // channel 1's transform area follows channel 0's
 
 // f2 and the packed-arithmetic helpers: afg_pk.h
 
 __device__ __forceinline__ int pad_e(int m) { return m + (m >> 3); }
 
-// Opaque copy of a (wave-uniform) table pointer.  Without it the compiler hoists the 64-bit
-// address of every table access out of the packet loop (two VGPRs each, ~120 in total);
-// laundering the base per pass keeps addresses as SGPR base + 32-bit lane offset, live
-// only inside the pass.
 // Opaque copy of the lane id: address arithmetic derived from it cannot be hoisted out of the
 // packet loop (where it would sit in VGPRs for the whole kernel), it is recomputed per pass.
 __device__ __forceinline__ int fresh_lane()
@@ -194,13 +181,6 @@ __device__ __forceinline__ int fresh_lane()
     return l;
 }
 
-template <typename T>
-__device__ __forceinline__ const T *fresh(const T *p)
-{
-    asm volatile("" : "+v"(p));
-    return p;
-}
-
 __device__ __forceinline__ void bfly2(f2 &p, f2 &q, f2 c)
 {
     const f2 d = p - q;
@@ -208,54 +188,27 @@ __device__ __forceinline__ void bfly2(f2 &p, f2 &q, f2 c)
     q = pk_mul_ll_hl(d, c) + pk_mul_xneg(d, c);       // (d.x*c.x - d.y*c.y, d.y*c.x + d.x*c.y)
 }
 
-// issue the loads of one channel spectrum (n = 2048): 4 x 16 bytes per lane
+// issue the loads of one channel spectrum (n = 2048): 4 x 16 bytes per lane, nontemporal -- a spectrum is read once, and
+// L1 is kept for the tables
 __device__ __forceinline__ void load_spectrum(float4 (&x)[4], const float *__restrict__ X)
 {
     const int lane = threadIdx.x & 63;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         typedef float v4f __attribute__((ext_vector_type(4)));
-#if AFG_VORBIS_NT_LOAD
-        const v4f t = __builtin_nontemporal_load((const v4f *)X + lane + 64 * r);   // read once: keep L1 for the tables
-#else
-        const v4f t = *((const v4f *)X + lane + 64 * r);
-#endif
+        const v4f t = __builtin_nontemporal_load((const v4f *)X + lane + 64 * r);
         x[r] = make_float4(t.x, t.y, t.z, t.w);
     }
 }
 
-// inverse_mdct for n = 2048 (stb_vorbis2.d:1941-2242); result in smem[0..2048)
-// Twiddles of the passes whose lane -> table index mapping is strided (they would hit a few LDS
-// banks only): they do not depend on the packet, so each lane keeps its own in registers.
-#ifndef AFG_VORBIS_TW_REGS
-#define AFG_VORBIS_TW_REGS 1
-#endif
-// Step 2 and the first two butterfly stages without the LDS round trip between them: half-iteration `it` of step 2 makes the
-// points n8-1-it and n4-1-it; with it = 63 - lane + 64 r these are j + 64 (3 - r) and n4/2 + j + 64 (3 - r) for j = lane, i.e.
-// exactly the eight points lane j combines in stages 0 and 1 -- they stay in registers.
-#ifndef AFG_VORBIS_FUSE12
-#define AFG_VORBIS_FUSE12 1
-#endif
-// Stages 0-1 and stages 2-4 without the LDS round trip between them (stereo walk): after stages 0, 1 slot s of lane j holds
-// point 64 s + j; stages 2..4 want slot k of lane 8 g + jp to hold point 64 g + jp + 8 k -- an 8 x 8 transpose between the slot
-// index and lane bits [5:3], done in place with v_permlane32_swap (bit 5), v_permlane16_swap (bit 4) and a row_ror:8 DPP
-// move with two selects (bit 3): tools/ubench_lanetr.hip checks the exchange on its own.
-#ifndef AFG_VORBIS_FUSE23
-#define AFG_VORBIS_FUSE23 AFG_VORBIS_FUSE12
-#endif
 constexpr int kLaneTw = 14;                          // lane-constant twiddles per lane
-constexpr int kTabBase = kNL / 2 + kNL / 2 + kNL / 4 + kNL / 2;      // A B C window of n = 2048 (floats)
-constexpr int kTabFloats = kTabBase + (AFG_VORBIS_TW_REGS ? 0 : kLaneTw * 64 * 2);   // + the lane-major twiddle copy
+constexpr int kTabFloats = kNL / 2 + kNL / 2 + kNL / 4 + kNL / 2;    // A B C window of n = 2048 (floats)
 // which A entry lane `lane` needs as its i-th lane-constant twiddle (complex index into A)
 __device__ __forceinline__ int lane_twiddle_index(int i, int lane)
 {
     constexpr int n4 = kNL / 4;
     const int jp = lane & 7;
-#if AFG_VORBIS_FUSE12
     if (i < 4) return n4 - 2 - 2 * ((63 - lane) + 64 * i);      // step 2:      A[n2-4-2o], o = 2 it, it = 63 - lane + 64 r (below)
-#else
-    if (i < 4) return n4 - 2 - 2 * (lane + 64 * i);             // step 2:      A[n2-4-2o], o = 2 (lane + 64 r)
-#endif
     if (i == 4) return 4 * lane;                                // stages 0, 1: A[j << 3]
     if (i == 5) return 4 * (lane + 64);                         //              A[(j+64) << 3]
     if (i == 6) return 8 * lane;                                //              A[j << 4]
@@ -264,31 +217,20 @@ __device__ __forceinline__ int lane_twiddle_index(int i, int lane)
     return 64 * jp;                                             //              A[jp << 7]
 }
 
-#if AFG_VORBIS_TW_REGS
-struct LaneTwiddles {                                // kept in registers
+// Twiddles of the passes whose lane -> table index mapping is strided (read from the LDS table they would hit a few banks
+// only): they do not depend on the packet, so each lane keeps its own in registers for the whole walk.
+struct LaneTwiddles {
     f2 v[kLaneTw];
     __device__ __forceinline__ f2 p1(int r) const { return v[r]; }
     __device__ __forceinline__ f2 pa(int i) const { return v[4 + i]; }
     __device__ __forceinline__ f2 pb(int k) const { return v[7 + k]; }
 };
-__device__ __forceinline__ void load_lane_twiddles(LaneTwiddles &t, const float *A, const float *)
+__device__ __forceinline__ void load_lane_twiddles(LaneTwiddles &t, const float *A)
 {
     const int lane = threadIdx.x & 63;
 #pragma unroll
     for (int i = 0; i < kLaneTw; i++) t.v[i] = ((const f2 *)A)[lane_twiddle_index(i, lane)];
 }
-#else
-struct LaneTwiddles {                                // lane-major copy in LDS: [i][lane], conflict-free 8-byte reads
-    const f2 *t;
-    __device__ __forceinline__ f2 p1(int r) const { return t[r * 64]; }
-    __device__ __forceinline__ f2 pa(int i) const { return t[(4 + i) * 64]; }
-    __device__ __forceinline__ f2 pb(int k) const { return t[(7 + k) * 64]; }
-};
-__device__ __forceinline__ void load_lane_twiddles(LaneTwiddles &t, const float *, const float *lane_major)
-{
-    t.t = (const f2 *)lane_major + (threadIdx.x & 63);
-}
-#endif
 
 __device__ __forceinline__ void lane_swap32(float &x, float &y)      // x of lanes 32..63 <-> y of lanes 0..31
 {
@@ -326,11 +268,14 @@ __device__ __forceinline__ void transpose_slots_hi(f2 (&e)[8], bool hi8)
     for (int k = 0; k < 8; k++) e[k] = f2{ x[k], y[k] };
 }
 
-template <typename AfterStep0>
-__device__ __forceinline__ void imdct_2048_wave(const float4 (&xin)[4], float *smem, const LaneTwiddles &tw,
+// inverse_mdct for n = 2048 (stb_vorbis2.d:1941-2242) of CH channels: channel ch takes its spectrum from xin[ch], works
+// in smem + ch * kDualStride and leaves its result in the first 2048 floats there.  A, B, C: the table set (LDS).
+template <int CH, typename AfterStep0>
+__device__ __forceinline__ void imdct_2048_wave(const float4 (&xin)[CH][4], float *smem, const LaneTwiddles &tw,
                                                 const float *A, const float *B, const float *C, AfterStep0 after_step0)
 {
     constexpr int n = kNL, n2 = n / 2, n4 = n / 4, n8 = n / 8;
+    constexpr int CS = kDualStride / 2;             // channel stride in f2
     int lane = fresh_lane();
     f2 *const U = (f2 *)smem;
     f2 *const V = (f2 *)(smem + kUFloats);
@@ -340,149 +285,159 @@ __device__ __forceinline__ void imdct_2048_wave(const float4 (&xin)[4], float *s
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int q = lane + 64 * r, qm = n8 - 1 - q;
-        const f2 xa = f2{ xin[r].x, xin[r].y }, xb = f2{ xin[r].z, xin[r].w };
         const f2 a0 = A2p[q];                       // A[2q], A[2q+1]
         const f2 a1 = A2p[n8 + qm];                 // A[n4+2q'], A[n4+2q'+1]
-        // d.x = x.x*a0.y + x.z*a0.x, d.y = x.x*a0.x - x.z*a0.y
-        const f2 d = pk_mul_lh_ll(xa, a0) + pk_mul_ll_lnh(xb, a0);
-        V[n4 - 1 - q] = d;                          // buf2[n2-2-2q], [n2-1-2q]
-        // g.x = -x.w*a1.y + -x.y*a1.x, g.y = -x.w*a1.x - -x.y*a1.y
-        const f2 g = pk_mul_nhh_nhl(xb, a1) + pk_mul_nhl_hh(xa, a1);
-        V[q] = g;                                   // buf2[n4-2-2q'] = buf2[2q]
+#pragma unroll
+        for (int ch = 0; ch < CH; ch++) {
+            const f2 xa = f2{ xin[ch][r].x, xin[ch][r].y }, xb = f2{ xin[ch][r].z, xin[ch][r].w };
+            // d.x = x.x*a0.y + x.z*a0.x, d.y = x.x*a0.x - x.z*a0.y
+            const f2 d = pk_mul_lh_ll(xa, a0) + pk_mul_ll_lnh(xb, a0);
+            V[ch * CS + n4 - 1 - q] = d;            // buf2[n2-2-2q], [n2-1-2q]
+            // g.x = -x.w*a1.y + -x.y*a1.x, g.y = -x.w*a1.x - -x.y*a1.y
+            const f2 g = pk_mul_nhh_nhl(xb, a1) + pk_mul_nhl_hh(xa, a1);
+            V[ch * CS + q] = g;                     // buf2[n4-2-2q'] = buf2[2q]
+        }
     }
     __builtin_amdgcn_wave_barrier();
     after_step0();                                  // the spectrum registers are free from here on
     lane = fresh_lane();
 
-    // step 2 (:2006-2040): half-iteration `it` makes points n4-1-it and n8-1-it
-#if AFG_VORBIS_FUSE12
-    f2 s2[2][4];                                    // [half][r']: the points base + 64 r' of stages 0, 1
-#endif
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-#if AFG_VORBIS_FUSE12
-        const int it = 63 - lane + 64 * r;
-#else
-        const int it = lane + 64 * r;
-#endif
-        const f2 e0 = V[n8 + it];                   // v[n4+o], v[n4+o+1], o = 2 it
-        const f2 e1 = V[it];
-        const f2 aa = tw.p1(r);                     // A[n2-4-2o], A[n2-3-2o]
-        const f2 df = e0 - e1;                      // (v40_20, v41_21)
-        const f2 hi = pk_add_swap(e0, e1);          // (d0[1], d0[0])
-        // lo.x = v41_21*aa.x - v40_20*aa.y (d1[1]), lo.y = v40_20*aa.x + v41_21*aa.y (d1[0])
-        const f2 lo = pk_mul_hl_ll(df, aa) + pk_mul_nlh_hh(df, aa);
-#if AFG_VORBIS_FUSE12
-        s2[0][3 - r] = hi;
-        s2[1][3 - r] = lo;
-#else
-        U[pad_e(n8 - 1 - it)] = hi;
-        U[pad_e(n4 - 1 - it)] = lo;
-#endif
-    }
-#if !AFG_VORBIS_FUSE12
-    __builtin_amdgcn_wave_barrier();
-    lane = fresh_lane();
-#endif
-
-    // stages l = 0, 1 (:2053-2060): point sets {base + j + 64 r}, lane j, both halves
     {
-            const int j = lane;
-        const f2 w00 = tw.pa(0);                    // A[(j) << 3]
-        const f2 w01 = tw.pa(1);                    // A[(j+64) << 3]
-        const f2 w1 = tw.pa(2);                     // A[j << 4]
+        // step 2 (:2006-2040): half-iteration `it` makes points n4-1-it and n8-1-it.  With it = 63 - lane + 64 r these are
+        // j + 64 (3 - r) and n4/2 + j + 64 (3 - r) for j = lane: exactly the eight points lane j combines in stages 0 and 1,
+        // so they stay in registers instead of going through LDS.
+        f2 e0[CH][4], e1[CH][4];
 #pragma unroll
-        for (int hb = 0; hb < 2; hb++) {
-            const int base = hb * (n4 / 2) + j;
-            f2 e[4];
+        for (int ch = 0; ch < CH; ch++)
 #pragma unroll
-#if AFG_VORBIS_FUSE12
-            for (int r = 0; r < 4; r++) e[r] = s2[hb][r];
-#else
-            for (int r = 0; r < 4; r++) e[r] = U[pad_e(base + 64 * r)];
-#endif
-            bfly2(e[0], e[2], w00);
-            bfly2(e[1], e[3], w01);
-            bfly2(e[0], e[1], w1);
-            bfly2(e[2], e[3], w1);
+            for (int r = 0; r < 4; r++) {
+                const int it = 63 - lane + 64 * r;
+                e0[ch][r] = V[ch * CS + n8 + it];               // v[n4+o], v[n4+o+1], o = 2 it
+                e1[ch][r] = V[ch * CS + it];
+            }
 #pragma unroll
-            for (int r = 0; r < 4; r++) U[pad_e(base + 64 * r)] = e[r];
+        for (int ch = 0; ch < CH; ch++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const f2 aa = tw.p1(r);                         // A[n2-4-2o], A[n2-3-2o]
+                const f2 df = e0[ch][r] - e1[ch][r];            // (v40_20, v41_21)
+                const f2 hi = pk_add_swap(e0[ch][r], e1[ch][r]);   // (d0[1], d0[0])
+                // lo.x = v41_21*aa.x - v40_20*aa.y (d1[1]), lo.y = v40_20*aa.x + v41_21*aa.y (d1[0])
+                const f2 lo = pk_mul_hl_ll(df, aa) + pk_mul_nlh_hh(df, aa);
+                e0[ch][r] = hi;                                 // point j + 64 (3 - r) of the lower half
+                e1[ch][r] = lo;                                 // the same point of the upper half
+            }
+
+        // stages l = 0, 1 (:2053-2060) on the registers step 2 left: slot s of lane j holds point j + 64 s
+        const f2 w00 = tw.pa(0), w01 = tw.pa(1), w1 = tw.pa(2);   // A[j << 3], A[(j+64) << 3], A[j << 4]
+        f2 e[CH][8];
+#pragma unroll
+        for (int ch = 0; ch < CH; ch++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) { e[ch][r] = e0[ch][3 - r]; e[ch][4 + r] = e1[ch][3 - r]; }
+        auto stages_0_1 = [&](f2 *q) __attribute__((always_inline)) {      // the four slots of one half
+            bfly2(q[0], q[2], w00);
+            bfly2(q[1], q[3], w01);
+            bfly2(q[0], q[1], w1);
+            bfly2(q[2], q[3], w1);
+        };
+        // Stages l = 2, 3, 4 (:2062-2083) want slot k of lane 8 g + jp to hold point 64 g + jp + 8 k: an 8 x 8 transpose
+        // between the slot index and lane bits [5:3].  This is the one place in the transform where the channel count changes the schedule.
+        if constexpr (CH == 2) {
+            // in registers: v_permlane32_swap (bit 5), v_permlane16_swap (bit 4), a row_ror:8 DPP move with two selects
+            // (bit 3).  It costs about what the LDS round trip costs, in fewer LDS instructions.
+#pragma unroll
+            for (int ch = 0; ch < CH; ch++)
+#pragma unroll
+                for (int hb = 0; hb < 8; hb += 4) stages_0_1(&e[ch][hb]);
+#pragma unroll
+            for (int ch = 0; ch < CH; ch++) transpose_slots_hi(e[ch], (lane & 8) != 0);
+        } else {
+            // through U: a half's stores leave while the other half is computed
+#pragma unroll
+            for (int hb = 0; hb < 8; hb += 4) {
+                stages_0_1(&e[0][hb]);
+#pragma unroll
+                for (int r = 0; r < 4; r++) U[pad_e(lane + 64 * (hb + r))] = e[0][hb + r];
+            }
+            __builtin_amdgcn_wave_barrier();
+            lane = fresh_lane();
+#pragma unroll
+            for (int k = 0; k < 8; k++) e[0][k] = U[pad_e(64 * (lane >> 3) + (lane & 7) + 8 * k)];
+        }
+        const int base = 64 * (lane >> 3) + (lane & 7);             // point sets {64 g + jp + 8 k}
+#pragma unroll
+        for (int ch = 0; ch < CH; ch++) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) bfly2(e[ch][k], e[ch][k + 4], tw.pb(k));          // A[b << 5]
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const f2 w = tw.pb(4 + k);                                                // A[b << 6]
+                bfly2(e[ch][k], e[ch][k + 2], w);
+                bfly2(e[ch][k + 4], e[ch][k + 6], w);
+            }
+            {
+                const f2 w = tw.pb(6);                                                    // A[b << 7]
+#pragma unroll
+                for (int k = 0; k < 8; k += 2) bfly2(e[ch][k], e[ch][k + 1], w);
+            }
+#pragma unroll
+            for (int k = 0; k < 8; k++) U[ch * CS + pad_e(base + 8 * k)] = e[ch][k];
         }
     }
     __builtin_amdgcn_wave_barrier();
     lane = fresh_lane();
 
-    // stages l = 2, 3, 4 (:2062-2083): point sets {64 g + j' + 8 e}
-    {
-            const int g = lane >> 3, jp = lane & 7;
-        const int base = 64 * g + jp;
-        f2 e[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) e[k] = U[pad_e(base + 8 * k)];
-#pragma unroll
-        for (int k = 0; k < 4; k++) bfly2(e[k], e[k + 4], tw.pb(k));                    // A[b << 5]
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const f2 w = tw.pb(4 + k);                                                    // A[b << 6]
-            bfly2(e[k], e[k + 2], w);
-            bfly2(e[k + 4], e[k + 6], w);
-        }
-        {
-            const f2 w = tw.pb(6);                                                        // A[b << 7]
-#pragma unroll
-            for (int k = 0; k < 8; k += 2) bfly2(e[k], e[k + 1], w);
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) U[pad_e(base + 8 * k)] = e[k];
-    }
-    __builtin_amdgcn_wave_barrier();
-    lane = fresh_lane();
-
-    // last three stages, the reference's fused loop (:1898-1939) on points 8 it .. 8 it + 7;
-    // zz[i] = z[-i]
+    // last three stages, the reference's fused loop (:1898-1939) on points 8 it .. 8 it + 7
     {
         const float A2 = A[n >> 3];
         const f2 A2p2 = f2{ A2, A2 };
         const int b9 = 9 * lane;                    // pad_e(8 lane)
-        f2 t[8];                                    // t[k] = (zz[2k], zz[2k+1]), zz[i] = z[-i]
+        f2 t[CH][8];                                // t[ch][k] = (zz[2k], zz[2k+1]), zz[i] = z[-i]
 #pragma unroll
-        for (int k = 0; k < 8; k++) t[k] = U[b9 + k];
-        {
-            const f2 K = t[0] - t[4];               // (k00, k11)
-            const f2 L = t[1] - t[5];               // (l00, l11)
-            t[0] = t[0] + t[4];
-            t[1] = t[1] + t[5];
-            t[4] = K;                                                   // zz[8] = k00, zz[9] = k11
-            t[5] = pk_add_lh_hnl(L, L) * A2p2;                          // ((l00+l11)*A2, (l11-l00)*A2)
-        }
-        {
-            const f2 L = t[3] - t[7];               // (l00, l11)
-            const f2 k6 = pk_add_hnh_nll(t[2], t[6]);                   // (k11, -k00) = (zz5-zz13, zz12-zz4)
-            t[2] = t[2] + t[6];
-            t[3] = t[3] + t[7];
-            t[6] = k6;
-            t[7] = pk_add_hnl_lh(L, L) * f2{ A2, -A2 };                 // ((l11-l00)*A2, (l00+l11)*-A2)
-        }
+        for (int ch = 0; ch < CH; ch++)
 #pragma unroll
-        for (int h = 0; h < 8; h += 4) {            // iter_54 (:1866-1896) on z and z-8
-            const f2 y02 = t[h] + t[h + 2];         // (y0, y1)
-            const f2 i01 = t[h] - t[h + 2];         // (i00, i11)
-            const f2 y23 = t[h + 1] + t[h + 3];     // (y2, y3)
-            const f2 i23 = t[h + 1] - t[h + 3];     // (i22, i33)
-            t[h] = y02 + y23;
-            t[h + 1] = y02 - y23;
-            t[h + 2] = pk_add_lh_hnl(i01, i23);     // (i00 + i33, i11 - i22)
-            t[h + 3] = pk_add_lnh_hl(i01, i23);     // (i00 - i33, i11 + i22)
-        }
+            for (int k = 0; k < 8; k++) t[ch][k] = U[ch * CS + b9 + k];
         // steps 4-6 (:2096-2124) folded into the store: entry e of the bit-reverse table takes points
         // 511-2*brev8(e) -> v2[511-e] and 510-2*brev8(e) -> v2[255-e].  Point 8*lane+k is 511-(8J+kk) with
         // J = 63-lane, kk = 7-k, i.e. e = brev2(kk>>1)*64 + brev6(J): a per-k constant minus a per-lane one.
         f2 *const Vr = V - (int)(__brev((unsigned)(63 - lane)) >> 26);
 #pragma unroll
-        for (int k = 0; k < 8; k++) {
-            constexpr int rev2[4] = { 0, 2, 1, 3 };
-            const int kk = 7 - k;
-            Vr[((kk & 1) ? n8 - 1 : n4 - 1) - 64 * rev2[kk >> 1]] = t[k];
+        for (int ch = 0; ch < CH; ch++) {
+            f2 (&tt)[8] = t[ch];
+            {
+                const f2 K = tt[0] - tt[4];             // (k00, k11)
+                const f2 L = tt[1] - tt[5];             // (l00, l11)
+                tt[0] = tt[0] + tt[4];
+                tt[1] = tt[1] + tt[5];
+                tt[4] = K;                                                  // zz[8] = k00, zz[9] = k11
+                tt[5] = pk_add_lh_hnl(L, L) * A2p2;                         // ((l00+l11)*A2, (l11-l00)*A2)
+            }
+            {
+                const f2 L = tt[3] - tt[7];             // (l00, l11)
+                const f2 k6 = pk_add_hnh_nll(tt[2], tt[6]);                 // (k11, -k00) = (zz5-zz13, zz12-zz4)
+                tt[2] = tt[2] + tt[6];
+                tt[3] = tt[3] + tt[7];
+                tt[6] = k6;
+                tt[7] = pk_add_hnl_lh(L, L) * f2{ A2, -A2 };                // ((l11-l00)*A2, (l00+l11)*-A2)
+            }
+#pragma unroll
+            for (int h = 0; h < 8; h += 4) {            // iter_54 (:1866-1896) on z and z-8
+                const f2 y02 = tt[h] + tt[h + 2];       // (y0, y1)
+                const f2 i01 = tt[h] - tt[h + 2];       // (i00, i11)
+                const f2 y23 = tt[h + 1] + tt[h + 3];   // (y2, y3)
+                const f2 i23 = tt[h + 1] - tt[h + 3];   // (i22, i33)
+                tt[h] = y02 + y23;
+                tt[h + 1] = y02 - y23;
+                tt[h + 2] = pk_add_lh_hnl(i01, i23);    // (i00 + i33, i11 - i22)
+                tt[h + 3] = pk_add_lnh_hl(i01, i23);    // (i00 - i33, i11 + i22)
+            }
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                constexpr int rev2[4] = { 0, 2, 1, 3 };
+                const int kk = 7 - k;
+                Vr[ch * CS + ((kk & 1) ? n8 - 1 : n4 - 1) - 64 * rev2[kk >> 1]] = tt[k];
+            }
         }
     }
     __builtin_amdgcn_wave_barrier();
@@ -494,44 +449,49 @@ __device__ __forceinline__ void imdct_2048_wave(const float4 (&xin)[4], float *s
     {
         const f2 *const C2 = (const f2 *)C;
         const f2 *const B2 = (const f2 *)B;
-        f2 dn[4], en[4];
+        f2 dn[CH][4], en[CH][4];
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int sidx = lane + 64 * r;
-            dn[r] = V[sidx];
-            en[r] = V[n4 - 1 - sidx];
-        }
+        for (int ch = 0; ch < CH; ch++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int sidx = lane + 64 * r;
+                dn[ch][r] = V[ch * CS + sidx];
+                en[ch][r] = V[ch * CS + n4 - 1 - sidx];
+            }
         __builtin_amdgcn_wave_barrier();
-    lane = fresh_lane();
+        lane = fresh_lane();
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int sidx = lane + 64 * r;
             const f2 cc = C2[sidx];
-            const f2 aa = pk_add_lnl_hh(dn[r], en[r]);                  // (a02, a11)
-            const f2 bs = pk_add_ll_hnh(dn[r], en[r]);                  // (b2, b3)
-            // b0 = cc.y*a02 + cc.x*a11, b1 = cc.y*a11 - cc.x*a02
-            const f2 bq = pk_mul_lh_hh(aa, cc) + pk_mul_hl_nll(aa, cc);
-            const f2 dnew = bs + bq;                                    // (b2 + b0, b3 + b1)
-            const f2 enew = pk_add_lnl_nhh(bs, bq);                     // (b2 - b0, b1 - b3)
-            // step 8 for x = sidx (pair v2[n4-1-x] = enew) and x = n4-1-sidx (pair v2[sidx] = dnew):
-            //   pa = e.x*bb.y - e.y*bb.x, pb = -e.x*bb.x - e.y*bb.y
-            {
-                const int x = sidx;
-                const f2 bb = B2[n4 - 1 - x];
-                const f2 pp = pk_mul_lh_nll(enew, bb) + pk_mul_nhl_nhh(enew, bb);
-                smem[x] = pp.x;
-                smem[n2 - 1 - x] = -pp.x;
-                smem[n2 + x] = pp.y;
-                smem[n - 1 - x] = pp.y;
-            }
-            {
-                const int x = n4 - 1 - sidx;
-                const f2 bb = B2[sidx];
-                const f2 pp = pk_mul_lh_nll(dnew, bb) + pk_mul_nhl_nhh(dnew, bb);
-                smem[x] = pp.x;
-                smem[n2 - 1 - x] = -pp.x;
-                smem[n2 + x] = pp.y;
-                smem[n - 1 - x] = pp.y;
+            const f2 bb0 = B2[n4 - 1 - sidx], bb1 = B2[sidx];
+#pragma unroll
+            for (int ch = 0; ch < CH; ch++) {
+                float *const sm = smem + ch * kDualStride;
+                const f2 aa = pk_add_lnl_hh(dn[ch][r], en[ch][r]);          // (a02, a11)
+                const f2 bs = pk_add_ll_hnh(dn[ch][r], en[ch][r]);          // (b2, b3)
+                // b0 = cc.y*a02 + cc.x*a11, b1 = cc.y*a11 - cc.x*a02
+                const f2 bq = pk_mul_lh_hh(aa, cc) + pk_mul_hl_nll(aa, cc);
+                const f2 dnew = bs + bq;                                    // (b2 + b0, b3 + b1)
+                const f2 enew = pk_add_lnl_nhh(bs, bq);                     // (b2 - b0, b1 - b3)
+                // step 8 for x = sidx (pair v2[n4-1-x] = enew) and x = n4-1-sidx (pair v2[sidx] = dnew):
+                //   pa = e.x*bb.y - e.y*bb.x, pb = -e.x*bb.x - e.y*bb.y
+                {
+                    const int x = sidx;
+                    const f2 pp = pk_mul_lh_nll(enew, bb0) + pk_mul_nhl_nhh(enew, bb0);
+                    sm[x] = pp.x;
+                    sm[n2 - 1 - x] = -pp.x;
+                    sm[n2 + x] = pp.y;
+                    sm[n - 1 - x] = pp.y;
+                }
+                {
+                    const int x = n4 - 1 - sidx;
+                    const f2 pp = pk_mul_lh_nll(dnew, bb1) + pk_mul_nhl_nhh(dnew, bb1);
+                    sm[x] = pp.x;
+                    sm[n2 - 1 - x] = -pp.x;
+                    sm[n2 + x] = pp.y;
+                    sm[n - 1 - x] = pp.y;
+                }
             }
         }
     }
@@ -539,9 +499,6 @@ __device__ __forceinline__ void imdct_2048_wave(const float4 (&xin)[4], float *s
     lane = fresh_lane();
 }
 
-#ifndef AFG_VORBIS_MIN_WAVES
-#define AFG_VORBIS_MIN_WAVES 2
-#endif
 // Make the prefetched spectrum resident *here*: the wait this forces only covers loads that were
 // issued a whole transform ago.  (Loads and stores share one in-order counter on gfx9-class hardware;
 // waiting for a load that was issued after a batch of PCM stores would wait for those stores too.)
@@ -566,7 +523,7 @@ __device__ __forceinline__ void vorbis_wave_body(
     const int C = (int)st.nch, c = (int)seg.pad;      // channels of the stream, channel of this wavefront
 
     LaneTwiddles tw;
-    load_lane_twiddles(tw, ltab, ltab + kTabBase);
+    load_lane_twiddles(tw, ltab);
     int previous_length = 0;
     const int p_first = seg.p0 > 0 ? (int)seg.p0 - 1 : 0;
     const int p_end = (int)(seg.p0 + seg.count);
@@ -607,13 +564,13 @@ __device__ __forceinline__ void vorbis_wave_body(
 
     // One spectrum is in flight: step 0 of transform k empties xin, the loads of transform k+1 follow at once
     // and are waited for (settle) just before the PCM stores of transform k enter the queue.
-    float4 xin[4];
+    float4 xin[1][4];
     auto issue = [&](int p) {
         if (p < p_end && (flags_of(p) & AFG_VORBIS_LONG))
-            load_spectrum(xin, spec + lane64(so_reg, p) + c * (kNL / 2));
+            load_spectrum(xin[0], spec + lane64(so_reg, p) + c * (kNL / 2));
     };
     issue(p_first);
-    settle(xin);                                     // waited for here: a wait at the loop top would be executed by every
+    settle(xin[0]);                                  // waited for here: a wait at the loop top would be executed by every
                                                      // iteration and drain the previous packet's PCM stores each time
 
     for (int p = p_first; p < p_end; p++) {
@@ -634,14 +591,14 @@ __device__ __forceinline__ void vorbis_wave_body(
         {
             auto next = [&]() { issue(p + 1); };
             if (which) {
-                imdct_2048_wave(xin, smem, tw, ltab, ltab + kNL / 2, ltab + kNL, next);   // :2526-2527, tables in LDS
+                imdct_2048_wave<1>(xin, smem, tw, ltab, ltab + kNL / 2, ltab + kNL, next);   // :2526-2527, tables in LDS
             } else {
                 for (int k = lane; k < n2; k += 64) smem[k] = src[c * n2 + k];
                 __builtin_amdgcn_wave_barrier();
                 inverse_mdct_lds<64>(smem, smem + n, n, 31 - __clz(n), A, B, Ct);
                 next();
             }
-            settle(xin);
+            settle(xin[0]);
             // vorbis_finish_frame (:2606-2657) + interleave (:3927-3952) for this channel: each
             // channel stores its own 4-byte column of the interleaved frames (merged in L2)
             if (emit) {
@@ -682,279 +639,6 @@ __device__ __forceinline__ void vorbis_wave_body(
     }
 }
 
-// =========================================================================================
-// Two channels per wavefront (stereo streams): the transforms of the left and the right channel of a packet are
-// independent, so every pass issues the LDS reads of both, computes both, writes both.  The second channel's reads
-// are in flight while the first is being computed -- the single-channel walk spent half its life in s_waitcnt
-// (profiles/r02_pmc_vorbis_wave_kernel.json) -- the tables are read once for both, and the PCM leaves as
-// interleaved (L, R) 8-byte stores, half as many instructions for the same bytes.
-// =========================================================================================
-constexpr int kDualStride = kWaveLds;               // channel 1's transform area follows channel 0's
-
-template <typename AfterStep0>
-__device__ __forceinline__ void imdct_2048_wave2(const float4 (&xin)[2][4], float *smem, const LaneTwiddles &tw,
-                                                 const float *A, const float *B, const float *C, AfterStep0 after_step0)
-{
-    constexpr int n = kNL, n2 = n / 2, n4 = n / 4, n8 = n / 8;
-    int lane = fresh_lane();
-    f2 *const U0 = (f2 *)smem;
-    f2 *const V0 = (f2 *)(smem + kUFloats);
-    constexpr int CS = kDualStride / 2;             // channel stride in f2
-    const f2 *A2p = (const f2 *)A;
-
-    // step 0 (:1972-1994)
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int q = lane + 64 * r, qm = n8 - 1 - q;
-        const f2 a0 = A2p[q];
-        const f2 a1 = A2p[n8 + qm];
-#pragma unroll
-        for (int ch = 0; ch < 2; ch++) {
-            const f2 xa = f2{ xin[ch][r].x, xin[ch][r].y }, xb = f2{ xin[ch][r].z, xin[ch][r].w };
-            const f2 d = pk_mul_lh_ll(xa, a0) + pk_mul_ll_lnh(xb, a0);
-            V0[ch * CS + n4 - 1 - q] = d;
-            const f2 g = pk_mul_nhh_nhl(xb, a1) + pk_mul_nhl_hh(xa, a1);
-            V0[ch * CS + q] = g;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    after_step0();                                  // the spectrum registers are free from here on
-    lane = fresh_lane();
-
-    // step 2 (:2006-2040)
-    {
-        f2 e0[2][4], e1[2][4];
-#pragma unroll
-        for (int ch = 0; ch < 2; ch++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-#if AFG_VORBIS_FUSE12
-                const int it = 63 - lane + 64 * r;
-#else
-                const int it = lane + 64 * r;
-#endif
-                e0[ch][r] = V0[ch * CS + n8 + it];
-                e1[ch][r] = V0[ch * CS + it];
-            }
-#pragma unroll
-        for (int ch = 0; ch < 2; ch++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const f2 aa = tw.p1(r);
-                const f2 df = e0[ch][r] - e1[ch][r];
-                const f2 hi = pk_add_swap(e0[ch][r], e1[ch][r]);
-                const f2 lo = pk_mul_hl_ll(df, aa) + pk_mul_nlh_hh(df, aa);
-#if AFG_VORBIS_FUSE12
-                e0[ch][r] = hi;                                 // point j + 64 (3 - r) of the lower half (j = lane)
-                e1[ch][r] = lo;                                 // the same point of the upper half
-#else
-                const int it = lane + 64 * r;
-                U0[ch * CS + pad_e(n8 - 1 - it)] = hi;
-                U0[ch * CS + pad_e(n4 - 1 - it)] = lo;
-#endif
-            }
-#if !AFG_VORBIS_FUSE12
-    }
-    __builtin_amdgcn_wave_barrier();
-    lane = fresh_lane();
-
-    // stages l = 0, 1 (:2053-2060)
-    {
-#else
-        // stages l = 0, 1 (:2053-2060) on the registers step 2 left
-#endif
-        const int j = lane;
-        const f2 w00 = tw.pa(0), w01 = tw.pa(1), w1 = tw.pa(2);
-#if AFG_VORBIS_FUSE23
-        f2 e[2][8];                                             // slot 4 hb + r: point hb n4/2 + j + 64 r
-#pragma unroll
-        for (int ch = 0; ch < 2; ch++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) { e[ch][r] = e0[ch][3 - r]; e[ch][4 + r] = e1[ch][3 - r]; }
-#pragma unroll
-        for (int ch = 0; ch < 2; ch++)
-#pragma unroll
-            for (int hb = 0; hb < 8; hb += 4) {
-                bfly2(e[ch][hb + 0], e[ch][hb + 2], w00);
-                bfly2(e[ch][hb + 1], e[ch][hb + 3], w01);
-                bfly2(e[ch][hb + 0], e[ch][hb + 1], w1);
-                bfly2(e[ch][hb + 2], e[ch][hb + 3], w1);
-            }
-        // stages l = 2, 3, 4 (:2062-2083) want slot k of lane 8 g + jp to hold point 64 g + jp + 8 k
-        transpose_slots_hi(e[0], (j & 8) != 0);
-        transpose_slots_hi(e[1], (j & 8) != 0);
-        const int g = lane >> 3, jp = lane & 7;
-        const int base = 64 * g + jp;
-#pragma unroll
-        for (int ch = 0; ch < 2; ch++) {
-#else
-#pragma unroll
-        for (int hb = 0; hb < 2; hb++) {
-            const int base = hb * (n4 / 2) + j;
-            f2 e[2][4];
-#pragma unroll
-            for (int ch = 0; ch < 2; ch++)
-#pragma unroll
-#if AFG_VORBIS_FUSE12
-                for (int r = 0; r < 4; r++) e[ch][r] = hb ? e1[ch][3 - r] : e0[ch][3 - r];
-#else
-                for (int r = 0; r < 4; r++) e[ch][r] = U0[ch * CS + pad_e(base + 64 * r)];
-#endif
-#pragma unroll
-            for (int ch = 0; ch < 2; ch++) {
-                bfly2(e[ch][0], e[ch][2], w00);
-                bfly2(e[ch][1], e[ch][3], w01);
-                bfly2(e[ch][0], e[ch][1], w1);
-                bfly2(e[ch][2], e[ch][3], w1);
-#pragma unroll
-                for (int r = 0; r < 4; r++) U0[ch * CS + pad_e(base + 64 * r)] = e[ch][r];
-            }
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    lane = fresh_lane();
-
-    // stages l = 2, 3, 4 (:2062-2083)
-    {
-        const int g = lane >> 3, jp = lane & 7;
-        const int base = 64 * g + jp;
-        f2 e[2][8];
-#pragma unroll
-        for (int ch = 0; ch < 2; ch++)
-#pragma unroll
-            for (int k = 0; k < 8; k++) e[ch][k] = U0[ch * CS + pad_e(base + 8 * k)];
-#pragma unroll
-        for (int ch = 0; ch < 2; ch++) {
-#endif
-#pragma unroll
-            for (int k = 0; k < 4; k++) bfly2(e[ch][k], e[ch][k + 4], tw.pb(k));
-#pragma unroll
-            for (int k = 0; k < 2; k++) {
-                const f2 w = tw.pb(4 + k);
-                bfly2(e[ch][k], e[ch][k + 2], w);
-                bfly2(e[ch][k + 4], e[ch][k + 6], w);
-            }
-            {
-                const f2 w = tw.pb(6);
-#pragma unroll
-                for (int k = 0; k < 8; k += 2) bfly2(e[ch][k], e[ch][k + 1], w);
-            }
-#pragma unroll
-            for (int k = 0; k < 8; k++) U0[ch * CS + pad_e(base + 8 * k)] = e[ch][k];
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    lane = fresh_lane();
-
-    // last three stages (:1898-1939) + steps 4-6 folded into the store (:2096-2124)
-    {
-        const float A2 = A[n >> 3];
-        const f2 A2p2 = f2{ A2, A2 };
-        const int b9 = 9 * lane;
-        f2 t[2][8];
-#pragma unroll
-        for (int ch = 0; ch < 2; ch++)
-#pragma unroll
-            for (int k = 0; k < 8; k++) t[ch][k] = U0[ch * CS + b9 + k];
-        f2 *const Vr = V0 - (int)(__brev((unsigned)(63 - lane)) >> 26);
-#pragma unroll
-        for (int ch = 0; ch < 2; ch++) {
-            f2 (&tt)[8] = t[ch];
-            {
-                const f2 K = tt[0] - tt[4];
-                const f2 L = tt[1] - tt[5];
-                tt[0] = tt[0] + tt[4];
-                tt[1] = tt[1] + tt[5];
-                tt[4] = K;
-                tt[5] = pk_add_lh_hnl(L, L) * A2p2;
-            }
-            {
-                const f2 L = tt[3] - tt[7];
-                const f2 k6 = pk_add_hnh_nll(tt[2], tt[6]);
-                tt[2] = tt[2] + tt[6];
-                tt[3] = tt[3] + tt[7];
-                tt[6] = k6;
-                tt[7] = pk_add_hnl_lh(L, L) * f2{ A2, -A2 };
-            }
-#pragma unroll
-            for (int h = 0; h < 8; h += 4) {
-                const f2 y02 = tt[h] + tt[h + 2];
-                const f2 i01 = tt[h] - tt[h + 2];
-                const f2 y23 = tt[h + 1] + tt[h + 3];
-                const f2 i23 = tt[h + 1] - tt[h + 3];
-                tt[h] = y02 + y23;
-                tt[h + 1] = y02 - y23;
-                tt[h + 2] = pk_add_lh_hnl(i01, i23);
-                tt[h + 3] = pk_add_lnh_hl(i01, i23);
-            }
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                constexpr int rev2[4] = { 0, 2, 1, 3 };
-                const int kk = 7 - k;
-                Vr[ch * CS + ((kk & 1) ? n8 - 1 : n4 - 1) - 64 * rev2[kk >> 1]] = tt[k];
-            }
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    lane = fresh_lane();
-
-    // step 7 (:2133-2175) fused with step 8 (:2187-2238); all of buf2 is read before the first output is written
-    {
-        const f2 *const C2 = (const f2 *)C;
-        const f2 *const B2 = (const f2 *)B;
-        f2 dn[2][4], en[2][4];
-#pragma unroll
-        for (int ch = 0; ch < 2; ch++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int sidx = lane + 64 * r;
-                dn[ch][r] = V0[ch * CS + sidx];
-                en[ch][r] = V0[ch * CS + n4 - 1 - sidx];
-            }
-        __builtin_amdgcn_wave_barrier();
-        lane = fresh_lane();
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int sidx = lane + 64 * r;
-            const f2 cc = C2[sidx];
-            const f2 bb0 = B2[n4 - 1 - sidx], bb1 = B2[sidx];
-#pragma unroll
-            for (int ch = 0; ch < 2; ch++) {
-                float *const sm = smem + ch * kDualStride;
-                const f2 aa = pk_add_lnl_hh(dn[ch][r], en[ch][r]);
-                const f2 bs = pk_add_ll_hnh(dn[ch][r], en[ch][r]);
-                const f2 bq = pk_mul_lh_hh(aa, cc) + pk_mul_hl_nll(aa, cc);
-                const f2 dnew = bs + bq;
-                const f2 enew = pk_add_lnl_nhh(bs, bq);
-                {
-                    const int x = sidx;
-                    const f2 pp = pk_mul_lh_nll(enew, bb0) + pk_mul_nhl_nhh(enew, bb0);
-                    sm[x] = pp.x;
-                    sm[n2 - 1 - x] = -pp.x;
-                    sm[n2 + x] = pp.y;
-                    sm[n - 1 - x] = pp.y;
-                }
-                {
-                    const int x = n4 - 1 - sidx;
-                    const f2 pp = pk_mul_lh_nll(dnew, bb1) + pk_mul_nhl_nhh(dnew, bb1);
-                    sm[x] = pp.x;
-                    sm[n2 - 1 - x] = -pp.x;
-                    sm[n2 + x] = pp.y;
-                    sm[n - 1 - x] = pp.y;
-                }
-            }
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    lane = fresh_lane();
-}
-
-__device__ __forceinline__ void settle2(float4 (&x)[2][4])
-{
-    settle(x[0]);
-    settle(x[1]);
-}
-
 // One wavefront walks BOTH channels of a stereo segment.
 __device__ __forceinline__ void vorbis_wave2_body(
     float *smem, const float *ltab, const VorbisSeg &seg, const VorbisStream &st,
@@ -967,7 +651,7 @@ __device__ __forceinline__ void vorbis_wave2_body(
     const uint32_t tab0 = st.tab[0], tab1 = st.tab[1];
 
     LaneTwiddles tw;
-    load_lane_twiddles(tw, ltab, ltab + kTabBase);
+    load_lane_twiddles(tw, ltab);
     int previous_length = 0;
     const int p_first = seg.p0 > 0 ? (int)seg.p0 - 1 : 0;
     const int p_end = (int)(seg.p0 + seg.count);
@@ -1009,7 +693,8 @@ __device__ __forceinline__ void vorbis_wave2_body(
         }
     };
     issue(p_first);
-    settle2(xin);
+    settle(xin[0]);
+    settle(xin[1]);
 
     for (int p = p_first; p < p_end; p++) {
         if (p + 1 - fbase >= 64) refill(p);
@@ -1029,7 +714,7 @@ __device__ __forceinline__ void vorbis_wave2_body(
 
         auto next = [&]() { issue(p + 1); };
         if (which) {
-            imdct_2048_wave2(xin, smem, tw, ltab, ltab + kNL / 2, ltab + kNL, next);   // :2526-2527, tables in LDS
+            imdct_2048_wave<2>(xin, smem, tw, ltab, ltab + kNL / 2, ltab + kNL, next);   // :2526-2527, tables in LDS
         } else {
             for (int ch = 0; ch < 2; ch++) {
                 float *sm = smem + ch * kDualStride;
@@ -1039,7 +724,8 @@ __device__ __forceinline__ void vorbis_wave2_body(
             }
             next();
         }
-        settle2(xin);
+        settle(xin[0]);
+        settle(xin[1]);
         // vorbis_finish_frame (:2606-2657) + interleave (:3927-3952)
         if (emit) {
             const int nwin = pn < nout ? pn : nout;
@@ -1048,7 +734,7 @@ __device__ __forceinline__ void vorbis_wave2_body(
                 for (int i = 0; i < 16; i++) {
                     const int jj = lane + 64 * i;
                     const float w0 = lwin[jj], w1 = lwin[1023 - jj];
-                    AFG_VORBIS_ST(o + jj, (f2{ sm0[left + jj] * w0 + pv[0][i] * w1, sm1[left + jj] * w0 + pv[1][i] * w1 }));   // :2624-2626
+                    __builtin_nontemporal_store(f2{ sm0[left + jj] * w0 + pv[0][i] * w1, sm1[left + jj] * w0 + pv[1][i] * w1 }, o + jj);   // :2624-2626
                 }
             } else if (pn * 2 == kNL) {
 #pragma unroll
@@ -1056,7 +742,7 @@ __device__ __forceinline__ void vorbis_wave2_body(
                     const int jj = lane + 64 * i;
                     if (jj < nwin) {
                         const float w0 = lwin[jj], w1 = lwin[1023 - jj];
-                        AFG_VORBIS_ST(o + jj, (f2{ sm0[left + jj] * w0 + pv[0][i] * w1, sm1[left + jj] * w0 + pv[1][i] * w1 }));
+                        __builtin_nontemporal_store(f2{ sm0[left + jj] * w0 + pv[0][i] * w1, sm1[left + jj] * w0 + pv[1][i] * w1 }, o + jj);
                     }
                 }
             } else {
@@ -1066,11 +752,11 @@ __device__ __forceinline__ void vorbis_wave2_body(
                     const int jj = lane + 64 * i;
                     if (jj < nwin) {
                         const float w0 = wt[jj], w1 = wt[pn - 1 - jj];
-                        AFG_VORBIS_ST(o + jj, (f2{ sm0[left + jj] * w0 + pv[0][i] * w1, sm1[left + jj] * w0 + pv[1][i] * w1 }));
+                        __builtin_nontemporal_store(f2{ sm0[left + jj] * w0 + pv[0][i] * w1, sm1[left + jj] * w0 + pv[1][i] * w1 }, o + jj);
                     }
                 }
             }
-            for (int jj = nwin + lane; jj < nout; jj += 64) AFG_VORBIS_ST(o + jj, (f2{ sm0[left + jj], sm1[left + jj] }));
+            for (int jj = nwin + lane; jj < nout; jj += 64) __builtin_nontemporal_store(f2{ sm0[left + jj], sm1[left + jj] }, o + jj);
         }
         if (plen == kNL / 2) {                                 // :2641-2643
 #pragma unroll
@@ -1091,10 +777,8 @@ __device__ __forceinline__ void vorbis_wave2_body(
     }
 }
 
-#ifndef AFG_VORBIS_GROUP_WAVES
-#define AFG_VORBIS_GROUP_WAVES 8
-#endif
-constexpr int kWavesPerGroup = AFG_VORBIS_GROUP_WAVES;
+constexpr int kWavesPerGroup = 8;
+constexpr int kWavesPerEu = 2;                        // two wavefronts per SIMD: the register budget of the two-channel walk
 constexpr int kWaveStride = 2 * kWaveLds;             // transform areas of two channels: previous_window is in registers
 // runs of one (shape, channel count) among the streams with more than two channels: as many as walk_shape admits -- 26 (a constant
 // 24 once: a plan that held every group failed as a whole)
@@ -1102,10 +786,7 @@ constexpr uint32_t kMcGroupsMax = walk_mc_groups();
 constexpr uint32_t kCounterSets = 32, kCountersPerLaunch = 1 + kWalkShapes + kMcGroupsMax;
 constexpr uint32_t kBothChannels = 0xffffffffu;       // VorbisSeg.pad of a wavefront that walks both channels of a stereo stream
 
-#ifndef AFG_VORBIS_WAVES_PER_EU
-#define AFG_VORBIS_WAVES_PER_EU 2
-#endif
-__global__ __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_waves_per_eu(AFG_VORBIS_WAVES_PER_EU, AFG_VORBIS_WAVES_PER_EU)))
+__global__ __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_waves_per_eu(kWavesPerEu, kWavesPerEu)))
 void vorbis_wave_kernel(
     const VorbisSeg *__restrict__ segs, uint32_t n_segs, const VorbisStream *__restrict__ streams,
     const uint8_t *__restrict__ pflags, const uint64_t *__restrict__ spec_off,
@@ -1117,8 +798,8 @@ void vorbis_wave_kernel(
     {   // 14 KB of tables: every 16-byte piece in flight at once (a dependent load -> LDS-store loop of 28 rounds cost
         // 15 % of a 16-packet wavefront's life)
         typedef float v4f __attribute__((ext_vector_type(4)));
-        constexpr int kQuads = kTabBase / 4, kPer = (kQuads + 64 * kWavesPerGroup - 1) / (64 * kWavesPerGroup);
-        static_assert(kTabBase % 4 == 0, "table quads");
+        constexpr int kQuads = kTabFloats / 4, kPer = (kQuads + 64 * kWavesPerGroup - 1) / (64 * kWavesPerGroup);
+        static_assert(kTabFloats % 4 == 0, "table quads");
         const v4f *src = (const v4f *)(tables + tab2048);                // tab2048 is a multiple of 4 floats (16-byte aligned)
         v4f t[kPer];
 #pragma unroll
@@ -1132,8 +813,6 @@ void vorbis_wave_kernel(
             if (i < kQuads) ((v4f *)ltab)[i] = t[k];
         }
     }
-    for (int i = threadIdx.x; i < (AFG_VORBIS_TW_REGS ? 0 : kLaneTw * 64); i += 64 * kWavesPerGroup)
-        ((f2 *)(ltab + kTabBase))[i] = ((const f2 *)(tables + tab2048))[lane_twiddle_index(i >> 6, i & 63)];
     __syncthreads();                                                     // the only block-level barrier
     // Persistent wavefronts: the grid is one workgroup per CU (the LDS holds exactly one) and every wavefront draws
     // segments from a counter until none are left.  Launching a workgroup per 8 segments instead left each CU idle

@@ -44,6 +44,38 @@ def test_vorbis_long_short_mix(gpu, seg):
     assert compare(got, want) == 0
 
 
+@pytest.mark.parametrize("seg", [1, 5, 1000])
+def test_vorbis_stereo_through_single_channel_body(gpu, monkeypatch, seg):
+    """AFG_VORBIS_SINGLE: every stereo stream of the batch above takes the wave kernel's one-channel body, a wavefront per
+    channel storing its own column of the frames.  Same bits as the oracle, and as the two-channel body."""
+    packets = [40, 1, 2, 25]
+    channels = [2, 2, 1, 2]
+    bs0 = [256] * 4
+    bs1 = [2048] * 4
+    pflags, spec = synthetic.vorbis_batch(7, packets, channels, bs0, bs1, p_short_run=0.2)
+    both, want = run_both(gpu, packets, channels, bs0, bs1, pflags, spec, seg)
+    monkeypatch.setenv("AFG_VORBIS_SINGLE", "1")
+    single, _ = run_both(gpu, packets, channels, bs0, bs1, pflags, spec, seg)
+    assert compare(single, want) == 0
+    assert (single.view(np.uint32) == both.view(np.uint32)).all()
+
+
+@pytest.mark.parametrize("single", [False, True])
+@pytest.mark.parametrize("seg", [64, 1000])
+def test_vorbis_refill_crossings(gpu, monkeypatch, seg, single):
+    """A wavefront keeps the flags and offsets of 64 packets in a register, one per lane, and refills it on the way.  130
+    packets in one segment refill twice; 64-packet segments start exactly on a refill boundary and redo the packet before it."""
+    packets = [130, 130]
+    channels = [2, 1]
+    bs0 = [256] * 2
+    bs1 = [2048] * 2
+    pflags, spec = synthetic.vorbis_batch(17, packets, channels, bs0, bs1, p_short_run=0.2)
+    if single:
+        monkeypatch.setenv("AFG_VORBIS_SINGLE", "1")
+    got, want = run_both(gpu, packets, channels, bs0, bs1, pflags, spec, seg)
+    assert compare(got, want) == 0
+
+
 @pytest.mark.parametrize("bs", [(256, 256), (256, 512), (512, 1024), (1024, 4096), (2048, 8192), (512, 2048), (1024, 2048), (2048, 2048)])
 def test_vorbis_blocksizes(gpu, bs):
     packets = [9, 6]
