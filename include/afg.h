@@ -306,6 +306,9 @@ typedef struct afg_qoa_frame {
     uint8_t  channels;    /* 1..8 (header field) */
     uint8_t  pad[5];
 } afg_qoa_frame;           /* 24 bytes */
+/* A record with samples == 0 is skipped -- it writes nothing -- but the kernel still loads through it: its channels
+ * must be 1..8 and its byte_off must point at a whole frame header with its LMS state (8 + 16 * channels bytes) inside
+ * the byte plane. */
 
 /* d_out_i16 (qoa_decode_frame's sample_data) and/or d_out_f32 (value * (1.0f/32767)) may be NULL. */
 int afg_qoa_transform_hip(uint64_t n_frames, const afg_qoa_frame *d_frames, const uint8_t *d_bytes,

@@ -131,6 +131,7 @@ void afgo_qoa_transform(uint64_t n_frames, const afgo_qoa_frame *frames, const u
     int16_t buf[QOA_FRAME_LEN * 8];
     for (uint64_t f = 0; f < n_frames; f++) {
         const afgo_qoa_frame *fr = &frames[f];
+        if (fr->samples == 0) continue;                        /* a skipped record (afg.h), whatever the header it points at says */
         memset(buf, 0, sizeof(buf));
         uint32_t n = afgo_qoa_decode_frame(bytes + fr->byte_off, (size_t)1 << 20, fr->channels, buf);
         size_t cnt = (size_t)n * fr->channels;
