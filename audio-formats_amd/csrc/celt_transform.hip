@@ -30,6 +30,14 @@ __device__ __constant__ float d_celt_window[120];
 __device__ __constant__ float d_celt_window2[120];
 
 
+// fn(geometry) with geo_960() as a compile-time constant for the dominant record (celt_core.h), else the record's own
+template <class Fn>
+__device__ __forceinline__ void with_geo(const Geo &g, Fn &&fn)
+{
+    if (is_960(g)) fn(geo_960());
+    else fn(g);
+}
+
 constexpr int kAWaves = 4;               // wavefronts per workgroup of kernel A (they share the LDS copy of the tables)
 
 __global__ __launch_bounds__(64 * kAWaves) void celt_imdct_kernel(
@@ -66,15 +74,11 @@ __global__ __launch_bounds__(64 * kAWaves) void celt_imdct_kernel(
         const Geo g = geo_of(fr);
         const int F = g.F;
         float xa[15], xb[15];
-        if (is_960(g)) {
-            load_inputs(xa, xb, coeffs, fr, geo_960(), l);
-            frame_fft(z, xa, xb, fr, geo_960(), ltab, lwin, tb, l, act);
-            frame_rest(z, fr, geo_960(), ltab, lwin, tb, l, act);
-        } else {
-            load_inputs(xa, xb, coeffs, fr, g, l);
-            frame_fft(z, xa, xb, fr, g, ltab, lwin, tb, l, act);
-            frame_rest(z, fr, g, ltab, lwin, tb, l, act);
-        }
+        with_geo(g, [&](const Geo &gg) {
+            load_inputs(xa, xb, coeffs, fr, gg, l);
+            frame_fft(z, xa, xb, fr, gg, ltab, lwin, tb, l, act);
+            frame_rest(z, fr, gg, ltab, lwin, tb, l, act);
+        });
         // frame positions [60, F) -> this frame's slots
         if (paired) {
             f32x2 *o = (f32x2 *)(out + out_even);
@@ -124,6 +128,36 @@ __global__ __launch_bounds__(64 * kAWaves) void celt_imdct_kernel(
 struct PfState {
     int period, period_old;
     float g[3], g_old[3];
+
+    // words [2048, 2056) of a channel's state blob; without a blob, a fresh decoder
+    __device__ __forceinline__ void load(const float *st)
+    {
+        period = period_old = 0;
+        g[0] = g[1] = g[2] = g_old[0] = g_old[1] = g_old[2] = 0.0f;
+        if (st) {
+            period = __float_as_int(st[2048]);
+            g[0] = st[2049]; g[1] = st[2050]; g[2] = st[2051];
+            period_old = __float_as_int(st[2052]);
+            g_old[0] = st[2053]; g_old[1] = st[2054]; g_old[2] = st[2055];
+        }
+    }
+    __device__ __forceinline__ void store(float *st) const
+    {
+        st[2048] = __int_as_float(period);
+        st[2049] = g[0]; st[2050] = g[1]; st[2051] = g[2];
+        st[2052] = __int_as_float(period_old);
+        st[2053] = g_old[0]; st[2054] = g_old[1]; st[2055] = g_old[2];
+    }
+    __device__ __forceinline__ void shift()
+    {
+        period_old = period;
+        g_old[0] = g[0]; g_old[1] = g[1]; g_old[2] = g[2];
+    }
+    __device__ __forceinline__ void install(const afg_celt_frame &fr)
+    {
+        period = fr.pf_period_new;
+        g[0] = fr.pf_gains_new[0]; g[1] = fr.pf_gains_new[1]; g[2] = fr.pf_gains_new[2];
+    }
 };
 
 constexpr int kRing = 2048;
@@ -218,6 +252,53 @@ __device__ __forceinline__ void pf_apply(float *ring, int n0, int len, const PfS
     }
 }
 
+// block-0 window taps of this lane (samples l and l + 32 of the 60)
+__device__ __forceinline__ void block0_taps(const float *win, float (&wi)[2], float (&wj)[2], int l)
+{
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+        const int k = min(l + 32 * u, 59);
+        wi[u] = win[k];
+        wj[u] = win[119 - k];
+    }
+}
+
+// vector_fmul_window of block 0 (dopus.d:3688, :230-243) on the frame's first 120 samples, at(k) being sample k: the
+// ring of kernel B wraps, the stream kernel's buffer does not
+template <class At>
+__device__ __forceinline__ void window_block0(At &&at, const float (&wi)[2], const float (&wj)[2], int l)
+{
+    float a[2], b[2];
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+        const int k = l + 32 * u;
+        if (k < 60) {
+            const float s0 = at(k), s1 = at(119 - k);
+            a[u] = s0 * wj[u] - s1 * wi[u];
+            b[u] = s0 * wi[u] + s1 * wj[u];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+        const int k = l + 32 * u;
+        if (k < 60) { at(k) = a[u]; at(119 - k) = b[u]; }
+    }
+}
+
+// celt_postfilter, dopus.d:3357-3378, on the F samples at ring position n0
+__device__ __forceinline__ void postfilter_frame(float *ring, const float *win2, int n0, int F, PfState &pf,
+                                                 const afg_celt_frame &fr, int l, bool lane_on)
+{
+    pf_transition(ring, win2, n0, pf, l, lane_on);
+    pf.shift();
+    pf.install(fr);
+    if (F > 120) {
+        pf_transition(ring, win2, n0 + 120, pf, l, lane_on);
+        pf_apply(ring, n0 + 240, F - 240, pf, l, lane_on);
+        pf.shift();
+    }
+}
+
 __global__ __launch_bounds__(64) void celt_postfilter_kernel(
     const uint64_t *__restrict__ rec_base, const afg_celt_frame *__restrict__ recs, float *__restrict__ out,
     float *__restrict__ states, uint32_t n_chan)
@@ -253,27 +334,14 @@ __global__ __launch_bounds__(64) void celt_postfilter_kernel(
     float *st = states ? states + (size_t)my_chan * AFG_CELT_STATE_FLOATS : nullptr;
     float *ring = rings[h];
 
-    PfState pf;
-    pf.period = pf.period_old = 0;
-    pf.g[0] = pf.g[1] = pf.g[2] = pf.g_old[0] = pf.g_old[1] = pf.g_old[2] = 0.0f;
-    if (lane_on) {
+    if (lane_on)
         for (int i = l; i < 1024; i += 32) ring[i] = st ? st[i] : 0.0f;
-        if (st) {
-            pf.period = __float_as_int(st[2048]);
-            pf.g[0] = st[2049]; pf.g[1] = st[2050]; pf.g[2] = st[2051];
-            pf.period_old = __float_as_int(st[2052]);
-            pf.g_old[0] = st[2053]; pf.g_old[1] = st[2054]; pf.g_old[2] = st[2055];
-        }
-    }
+    PfState pf;
+    pf.load(lane_on ? st : nullptr);
     int n0 = 1024;
     for (int i = lane; i < 120; i += 64) win2[i] = d_celt_window2[i];
-    float wi[2], wj[2];                                      // block-0 window taps of this lane
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-        const int k = min(l + 32 * u, 59);
-        wi[u] = d_celt_window[k];
-        wj[u] = d_celt_window[119 - k];
-    }
+    float wi[2], wj[2];
+    block0_taps(d_celt_window, wi, wj, l);
     __builtin_amdgcn_wave_barrier();
 
     // frames are fetched one ahead into registers (15 x 64 positions cover the largest frame), records two ahead
@@ -313,38 +381,9 @@ __global__ __launch_bounds__(64) void celt_postfilter_kernel(
         if (q == 0 && lane_on)                               // the overlap a fresh call starts from: state or silence
             for (int k = l; k < 60; k += 32) RD(k) = st ? st[1024 + k] : 0.0f;
         __builtin_amdgcn_wave_barrier();
-        // vector_fmul_window of block 0 (dopus.d:3688, :230-243)
-        if (lane_on) {
-            float a[2], b[2];
-#pragma unroll
-            for (int u = 0; u < 2; u++) {
-                const int k = l + 32 * u;
-                if (k < 60) {
-                    const float s0 = RD(k), s1 = RD(119 - k);
-                    a[u] = s0 * wj[u] - s1 * wi[u];
-                    b[u] = s0 * wi[u] + s1 * wj[u];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 2; u++) {
-                const int k = l + 32 * u;
-                if (k < 60) { RD(k) = a[u]; RD(119 - k) = b[u]; }
-            }
-        }
+        if (lane_on) window_block0([&](int k) -> float & { return RD(k); }, wi, wj, l);
         __builtin_amdgcn_wave_barrier();
-
-        // celt_postfilter, dopus.d:3357-3378
-        pf_transition(ring, win2, n0, pf, l, lane_on);
-        pf.period_old = pf.period;
-        pf.g_old[0] = pf.g[0]; pf.g_old[1] = pf.g[1]; pf.g_old[2] = pf.g[2];
-        pf.period = fr.pf_period_new;
-        pf.g[0] = fr.pf_gains_new[0]; pf.g[1] = fr.pf_gains_new[1]; pf.g[2] = fr.pf_gains_new[2];
-        if (F > 120) {
-            pf_transition(ring, win2, n0 + 120, pf, l, lane_on);
-            pf_apply(ring, n0 + 240, F - 240, pf, l, lane_on);
-            pf.period_old = pf.period;
-            pf.g_old[0] = pf.g[0]; pf.g_old[1] = pf.g[1]; pf.g_old[2] = pf.g[2];
-        }
+        postfilter_frame(ring, win2, n0, F, pf, fr, l, lane_on);
 
         // Make the prefetched frame resident *here*: loads and stores share one in-order counter on this hardware,
         // so a wait placed after the stores below would also wait for them to drain.
@@ -373,12 +412,7 @@ __global__ __launch_bounds__(64) void celt_postfilter_kernel(
     if (st && lane_on) {
         for (int i = l; i < 1024; i += 32) st[i] = ring[(n0 - 1024 + i) & (kRing - 1)];
         for (int k = l; k < 60; k += 32) st[1024 + k] = st[kTailSlot + k];
-        if (l == 0) {
-            st[2048] = __int_as_float(pf.period);
-            st[2049] = pf.g[0]; st[2050] = pf.g[1]; st[2051] = pf.g[2];
-            st[2052] = __int_as_float(pf.period_old);
-            st[2053] = pf.g_old[0]; st[2054] = pf.g_old[1]; st[2055] = pf.g_old[2];
-        }
+        if (l == 0) pf.store(st);
     }
 }
 #undef RD
@@ -430,82 +464,31 @@ __global__ __launch_bounds__(64 * kSWaves) void celt_stream_kernel(
         cpx *z = (cpx *)(buf + 1024 + 60);
         const float *b0 = bufs, *b1 = bufs + 2048;
 
-        PfState pf;
-        pf.period = pf.period_old = 0;
-        pf.g[0] = pf.g[1] = pf.g[2] = pf.g_old[0] = pf.g_old[1] = pf.g_old[2] = 0.0f;
-        if (act) {
+        if (act)
             for (int i = l; i < 2048; i += 32) buf[i] = st ? st[i] : 0.0f;
-            if (st) {
-                pf.period = __float_as_int(st[2048]);
-                pf.g[0] = st[2049]; pf.g[1] = st[2050]; pf.g[2] = st[2051];
-                pf.period_old = __float_as_int(st[2052]);
-                pf.g_old[0] = st[2053]; pf.g_old[1] = st[2054]; pf.g_old[2] = st[2055];
-            }
-        }
-        float wi[2], wj[2];                                  // block-0 window taps of this lane
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-            const int k = min(l + 32 * u, 59);
-            wi[u] = lwin[k];
-            wj[u] = lwin[119 - k];
-        }
+        PfState pf;
+        pf.load(act ? st : nullptr);
+        float wi[2], wj[2];
+        block0_taps(lwin, wi, wj, l);
         __builtin_amdgcn_wave_barrier();
 
         afg_celt_frame fr = recs[my_base], fr_next = fr;
         if (cnt > 1) fr_next = recs[my_base + 1];
         float xa[15], xb[15];
-        {
-            const Geo g0 = geo_of(fr);
-            if (is_960(g0)) load_inputs(xa, xb, coeffs, fr, geo_960(), l);
-            else load_inputs(xa, xb, coeffs, fr, g0, l);
-        }
+        with_geo(geo_of(fr), [&](const Geo &gg) { load_inputs(xa, xb, coeffs, fr, gg, l); });
 
         for (uint64_t q = 0; q < cnt; q++) {
             const Geo g = geo_of(fr);
             const int F = g.F;
             afg_celt_frame fr_next2 = recs[my_base + (q + 2 < cnt ? q + 2 : cnt - 1)];
             // iMDCT and overlap-add, dopus.d:3684-3690
-            if (is_960(g)) frame_fft(z, xa, xb, fr, geo_960(), ltab, lwin, tb, l, act);
-            else frame_fft(z, xa, xb, fr, g, ltab, lwin, tb, l, act);
-            {                                                // (the last frame's again at the end)
-                const Geo gn = geo_of(fr_next);
-                if (is_960(gn)) load_inputs(xa, xb, coeffs, fr_next, geo_960(), l);
-                else load_inputs(xa, xb, coeffs, fr_next, gn, l);
-            }
-            if (is_960(g)) frame_rest(z, fr, geo_960(), ltab, lwin, tb, l, act);
-            else frame_rest(z, fr, g, ltab, lwin, tb, l, act);
-            if (act) {                                       // vector_fmul_window of block 0
-                float *d = buf + 1024;
-                float a[2], b[2];
-#pragma unroll
-                for (int u = 0; u < 2; u++) {
-                    const int k = l + 32 * u;
-                    if (k < 60) {
-                        const float s0 = d[k], s1 = d[119 - k];
-                        a[u] = s0 * wj[u] - s1 * wi[u];
-                        b[u] = s0 * wi[u] + s1 * wj[u];
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < 2; u++) {
-                    const int k = l + 32 * u;
-                    if (k < 60) { d[k] = a[u]; d[119 - k] = b[u]; }
-                }
-            }
+            with_geo(g, [&](const Geo &gg) { frame_fft(z, xa, xb, fr, gg, ltab, lwin, tb, l, act); });
+            // (the last frame's again at the end)
+            with_geo(geo_of(fr_next), [&](const Geo &gg) { load_inputs(xa, xb, coeffs, fr_next, gg, l); });
+            with_geo(g, [&](const Geo &gg) { frame_rest(z, fr, gg, ltab, lwin, tb, l, act); });
+            if (act) window_block0([d = buf + 1024](int k) -> float & { return d[k]; }, wi, wj, l);
             __builtin_amdgcn_wave_barrier();
-
-            // celt_postfilter, dopus.d:3357-3378
-            pf_transition(buf, win2, 1024, pf, l, act);
-            pf.period_old = pf.period;
-            pf.g_old[0] = pf.g[0]; pf.g_old[1] = pf.g[1]; pf.g_old[2] = pf.g[2];
-            pf.period = fr.pf_period_new;
-            pf.g[0] = fr.pf_gains_new[0]; pf.g[1] = fr.pf_gains_new[1]; pf.g[2] = fr.pf_gains_new[2];
-            if (F > 120) {
-                pf_transition(buf, win2, 1024 + 120, pf, l, act);
-                pf_apply(buf, 1024 + 240, F - 240, pf, l, act);
-                pf.period_old = pf.period;
-                pf.g_old[0] = pf.g[0]; pf.g_old[1] = pf.g[1]; pf.g_old[2] = pf.g[2];
-            }
+            postfilter_frame(buf, win2, 1024, F, pf, fr, l, act);
 
             // make the prefetched inputs resident before the stores enter the queue
 #pragma unroll
@@ -546,12 +529,7 @@ __global__ __launch_bounds__(64 * kSWaves) void celt_stream_kernel(
 
         if (st && act) {
             for (int i = l; i < 2048; i += 32) st[i] = buf[i];
-            if (l == 0) {
-                st[2048] = __int_as_float(pf.period);
-                st[2049] = pf.g[0]; st[2050] = pf.g[1]; st[2051] = pf.g[2];
-                st[2052] = __int_as_float(pf.period_old);
-                st[2053] = pf.g_old[0]; st[2054] = pf.g_old[1]; st[2055] = pf.g_old[2];
-            }
+            if (l == 0) pf.store(st);
         }
         __builtin_amdgcn_wave_barrier();
     };
@@ -583,40 +561,52 @@ __global__ __launch_bounds__(64 * kSWaves) void celt_stream_kernel(
 // already being loaded (same slots) when that frame has the same geometry -- so neither the record fetch nor the
 // first row fetch of a frame is ever waited for at full memory latency.  All prefetch loads are unconditional
 // (address-selected), which lets the compiler count them instead of draining the queue at every step.
-template <int STRIDE, int SEQ, int GROUP, int D>
-__device__ __forceinline__ void deemph_rows(float *xs, float *__restrict__ out, bool have, uint64_t off, uint64_t off_next,
-                                            int n, float &m, f32x4 (&ring)[D][(SEQ * GROUP / 4 + 63) / 64], bool primed,
-                                            bool chain_next)
-{
-    constexpr int PITCH = GROUP + 4;                          // floats; rows stay 16-byte aligned
-    constexpr int QUADS = SEQ * GROUP / 4;                    // float4 per step
-    constexpr int LOADS = (QUADS + 63) / 64;                  // float4 per lane per step
-    constexpr int F = GROUP / 4 * STRIDE;                     // float4 per row per step
-    constexpr int GS = GROUP * STRIDE;                        // floats a row advances per step
-    constexpr int CH = (GROUP / 4) % 10 == 0 ? 10 : GROUP / 4;   // float4 per chain chunk held in registers
-    static_assert((GROUP / 4) % CH == 0, "chunking");
-    const int lane = threadIdx.x;
+//
+// A lane's share of one step of the row walk, used by both schedules below: where its float4s live in memory and in an
+// LDS step buffer, and the transposes between the two.
+template <int STRIDE, int SEQ, int GROUP>
+struct RowPlan {
+    static constexpr int PITCH = GROUP + 4;                   // floats; rows stay 16-byte aligned
+    static constexpr int QUADS = SEQ * GROUP / 4;             // float4 per step
+    static constexpr int LOADS = (QUADS + 63) / 64;           // float4 per lane per step
+    static constexpr int F = GROUP / 4 * STRIDE;              // float4 per row per step
+    static constexpr int GS = GROUP * STRIDE;                 // floats a row advances per step
+    int lane;
     float *ptr[LOADS];                                        // where this lane's float4 of a step lives (stores)
     const float *lptr[LOADS], *lptr_n[LOADS];                 // load addresses: this frame / the next one (always valid memory)
     int lds_at[LOADS];
     bool valid[LOADS];
-    const int lead0 = __ffsll((unsigned long long)__ballot(have)) - 1;
-    const uint64_t safe = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(off >> 32), lead0) << 32) | (uint32_t)__shfl((int)(uint32_t)off, lead0);
+
+    __device__ __forceinline__ void fill(float *out, bool have, uint64_t off, uint64_t off_next, bool chain_next, int lane_)
+    {
+        lane = lane_;
+        const int lead0 = __ffsll((unsigned long long)__ballot(have)) - 1;
+        const uint64_t safe = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(off >> 32), lead0) << 32) | (uint32_t)__shfl((int)(uint32_t)off, lead0);
 #pragma unroll
-    for (int i = 0; i < LOADS; i++) {
-        const int idx = lane + 64 * i;
-        const int row = idx / F, q = idx - row * F;
-        const int lead = (row * STRIDE) & 63;                // first chain lane of the row
-        const uint32_t lo = __shfl((uint32_t)off, lead), hi = __shfl((uint32_t)(off >> 32), lead);
-        const uint32_t nlo = __shfl((uint32_t)off_next, lead), nhi = __shfl((uint32_t)(off_next >> 32), lead);
-        valid[i] = idx < QUADS && __shfl((int)have, lead) != 0;
-        ptr[i] = out + (((uint64_t)hi << 32) | lo) + 4 * q;
-        lptr[i] = valid[i] ? ptr[i] : out + safe;
-        lptr_n[i] = (valid[i] && chain_next) ? out + (((uint64_t)nhi << 32) | nlo) + 4 * q : lptr[i];
-        lds_at[i] = STRIDE == 1 ? row * PITCH + 4 * q : (2 * row) * PITCH + 2 * q;
+        for (int i = 0; i < LOADS; i++) {
+            const int idx = lane + 64 * i;
+            const int row = idx / F, q = idx - row * F;
+            const int lead = (row * STRIDE) & 63;            // first chain lane of the row
+            const uint32_t lo = __shfl((uint32_t)off, lead), hi = __shfl((uint32_t)(off >> 32), lead);
+            const uint32_t nlo = __shfl((uint32_t)off_next, lead), nhi = __shfl((uint32_t)(off_next >> 32), lead);
+            valid[i] = idx < QUADS && __shfl((int)have, lead) != 0;
+            ptr[i] = out + (((uint64_t)hi << 32) | lo) + 4 * q;
+            lptr[i] = valid[i] ? ptr[i] : out + safe;
+            lptr_n[i] = (valid[i] && chain_next) ? out + (((uint64_t)nhi << 32) | nlo) + 4 * q : lptr[i];
+            lds_at[i] = STRIDE == 1 ? row * PITCH + 4 * q : (2 * row) * PITCH + 2 * q;
+        }
     }
-    const int groups = n / GROUP;
-    if (!primed) {
+    // a wavefront that moves nothing (the chainer of a pair)
+    __device__ __forceinline__ void none(float *out, int lane_)
+    {
+        lane = lane_;
+#pragma unroll
+        for (int i = 0; i < LOADS; i++) { ptr[i] = out; lptr[i] = lptr_n[i] = out; lds_at[i] = 0; valid[i] = false; }
+    }
+    // the first D steps of a frame into the register ring (a frame shorter than D steps repeats its last one)
+    template <int D>
+    __device__ __forceinline__ void prime(f32x4 (&ring)[D][LOADS], int groups) const
+    {
 #pragma unroll
         for (int d = 0; d < D; d++) {
             const int g = d < groups ? d : groups - 1;
@@ -624,7 +614,9 @@ __device__ __forceinline__ void deemph_rows(float *xs, float *__restrict__ out, 
             for (int i = 0; i < LOADS; i++) ring[d][i] = __builtin_nontemporal_load((const f32x4 *)(lptr[i] + (size_t)g * GS));
         }
     }
-    auto step = [&](f32x4 (&b)[LOADS], int g) {
+    // a step's rows into the LDS step buffer xs, one LDS row per chain
+    __device__ __forceinline__ void put(float *xs, const f32x4 (&b)[LOADS]) const
+    {
 #pragma unroll
         for (int i = 0; i < LOADS; i++) {
             if (QUADS % 64 != 0 && lane + 64 * i >= QUADS) continue;
@@ -635,53 +627,10 @@ __device__ __forceinline__ void deemph_rows(float *xs, float *__restrict__ out, 
                 *(f32x2 *)(xs + lds_at[i] + PITCH) = f32x2{ b[i].y, b[i].w };
             }
         }
-        {   // refill the slot: D steps ahead in this frame, else the next frame's step (same slot: groups % D == 0 there),
-            // else a harmless re-read of this step (end of the sequence)
-            const int gn = g + D;
-            const bool here = gn < groups;
-            const size_t at = (size_t)(here ? gn : (chain_next ? gn - groups : g)) * GS;
-#pragma unroll
-            for (int i = 0; i < LOADS; i++)
-                b[i] = __builtin_nontemporal_load((const f32x4 *)(((here || !chain_next) ? lptr[i] : lptr_n[i]) + at));
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (lane < SEQ && have) {
-            f32x4 *row = (f32x4 *)(xs + lane * PITCH);
-            // two register chunks, ping-pong: while one is chained (14 cycles per sample, measured: tools/ubench_chain.hip)
-            // the LDS reads of the other are in flight; no register copies on the chain's path
-            auto chain = [&](f32x4 (&c)[CH], int k0) {
-#pragma unroll
-                for (int k = 0; k < CH; k++) {
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const float t = c[k][e] + m;                               // the chain: two dependent operations per
-                        m = t * 0.85000610f;                                       // sample on SEQ lanes, nothing else
-                        c[k][e] = t;
-                    }
-                    row[k0 + k] = c[k];
-                }
-            };
-            auto fill = [&](f32x4 (&c)[CH], int k0) {
-#pragma unroll
-                for (int k = 0; k < CH; k++) c[k] = row[k0 + k];
-            };
-            constexpr int NCH = GROUP / 4 / CH;               // chunks per step: 1 (GROUP 40, 60), 3, 6 or 12
-            f32x4 ca[CH], cb[CH];
-            fill(ca, 0);
-            if (NCH == 1) {
-                chain(ca, 0);
-            } else {
-#pragma unroll 1
-                for (int k0 = 0; k0 < GROUP / 4; k0 += 2 * CH) {
-                    const bool two = k0 + CH < GROUP / 4;     // (an odd chunk count ends on `ca`)
-                    if (two) fill(cb, k0 + CH);
-                    chain(ca, k0);
-                    if (k0 + 2 * CH < GROUP / 4) fill(ca, k0 + 2 * CH);
-                    if (two) chain(cb, k0 + CH);
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
+    }
+    // the chained rows out of xs, scaled, to memory `at` floats into the frame (ok false: nothing is stored)
+    __device__ __forceinline__ void get_store(const float *xs, bool ok, size_t at) const
+    {
 #pragma unroll
         for (int i = 0; i < LOADS; i++) {
             f32x4 o;
@@ -693,8 +642,79 @@ __device__ __forceinline__ void deemph_rows(float *xs, float *__restrict__ out, 
                 o = f32x4{ l.x, r.x, l.y, r.y };
             }
             o *= (1.0f / 32768.0f);                                                // tmp / 32768. (exact), on all 64 lanes
-            if (valid[i]) *(f32x4 *)(ptr[i] + (size_t)g * GS) = o;
+            if (valid[i] && ok) *(f32x4 *)(ptr[i] + at) = o;
         }
+    }
+};
+
+// The chain over one LDS row of GROUP samples, in place: the only arithmetic of the pass.
+template <int GROUP>
+__device__ __forceinline__ void chain_rows(f32x4 *row, float &m)
+{
+    constexpr int CH = (GROUP / 4) % 10 == 0 ? 10 : GROUP / 4;   // float4 per chain chunk held in registers
+    static_assert((GROUP / 4) % CH == 0, "chunking");
+    // two register chunks, ping-pong: while one is chained (14 cycles per sample, measured: tools/ubench_chain.hip)
+    // the LDS reads of the other are in flight; no register copies on the chain's path
+    auto chain = [&](f32x4 (&c)[CH], int k0) {
+#pragma unroll
+        for (int k = 0; k < CH; k++) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const float t = c[k][e] + m;                               // the chain: two dependent operations per
+                m = t * 0.85000610f;                                       // sample on SEQ lanes, nothing else
+                c[k][e] = t;
+            }
+            row[k0 + k] = c[k];
+        }
+    };
+    auto fill = [&](f32x4 (&c)[CH], int k0) {
+#pragma unroll
+        for (int k = 0; k < CH; k++) c[k] = row[k0 + k];
+    };
+    constexpr int NCH = GROUP / 4 / CH;                       // chunks per step: 1 (GROUP 40, 60), 3, 6 or 12
+    f32x4 ca[CH], cb[CH];
+    fill(ca, 0);
+    if (NCH == 1) {
+        chain(ca, 0);
+    } else {
+#pragma unroll 1
+        for (int k0 = 0; k0 < GROUP / 4; k0 += 2 * CH) {
+            const bool two = k0 + CH < GROUP / 4;             // (an odd chunk count ends on `ca`)
+            if (two) fill(cb, k0 + CH);
+            chain(ca, k0);
+            if (k0 + 2 * CH < GROUP / 4) fill(ca, k0 + 2 * CH);
+            if (two) chain(cb, k0 + CH);
+        }
+    }
+}
+
+// The single-wavefront schedule: a step is put, refill, chain, get and store, one after the other.
+template <int STRIDE, int SEQ, int GROUP, int D>
+__device__ __forceinline__ void deemph_rows(float *xs, float *__restrict__ out, bool have, uint64_t off, uint64_t off_next,
+                                            int n, float &m, f32x4 (&ring)[D][RowPlan<STRIDE, SEQ, GROUP>::LOADS], bool primed,
+                                            bool chain_next, int lane)
+{
+    using Plan = RowPlan<STRIDE, SEQ, GROUP>;
+    constexpr int LOADS = Plan::LOADS, GS = Plan::GS;
+    Plan p;
+    p.fill(out, have, off, off_next, chain_next, lane);
+    const int groups = n / GROUP;
+    if (!primed) p.prime(ring, groups);
+    auto step = [&](f32x4 (&b)[LOADS], int g) {
+        p.put(xs, b);
+        {   // refill the slot: D steps ahead in this frame, else the next frame's step (same slot: groups % D == 0 there),
+            // else a harmless re-read of this step (end of the sequence)
+            const int gn = g + D;
+            const bool here = gn < groups;
+            const size_t at = (size_t)(here ? gn : (chain_next ? gn - groups : g)) * GS;
+#pragma unroll
+            for (int i = 0; i < LOADS; i++)
+                b[i] = __builtin_nontemporal_load((const f32x4 *)(((here || !chain_next) ? p.lptr[i] : p.lptr_n[i]) + at));
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (lane < SEQ && have) chain_rows<GROUP>((f32x4 *)(xs + lane * Plan::PITCH), m);
+        __builtin_amdgcn_wave_barrier();
+        p.get_store(xs, true, (size_t)g * GS);
         __builtin_amdgcn_wave_barrier();
     };
     for (int g = 0; g < groups; g += D) {
@@ -711,51 +731,17 @@ __device__ __forceinline__ void deemph_rows(float *xs, float *__restrict__ out, 
 // (step g), on three LDS step buffers, one workgroup barrier per step: the chain never waits for a transpose.
 template <int STRIDE, int SEQ, int GROUP, int D>
 __device__ __forceinline__ void deemph_rows_duo(float *xs2, float *__restrict__ out, bool have, uint64_t off, uint64_t off_next,
-                                                int n, float &m, f32x4 (&ring)[D][(SEQ * GROUP / 4 + 63) / 64], bool primed,
-                                                bool chain_next, int role)
+                                                int n, float &m, f32x4 (&ring)[D][RowPlan<STRIDE, SEQ, GROUP>::LOADS], bool primed,
+                                                bool chain_next, int lane, int role)
 {
-    constexpr int PITCH = GROUP + 4;                          // floats; rows stay 16-byte aligned
-    constexpr int BUF = SEQ * PITCH;                          // floats per step buffer
-    constexpr int QUADS = SEQ * GROUP / 4;                    // float4 per step
-    constexpr int LOADS = (QUADS + 63) / 64;                  // float4 per lane per step
-    constexpr int F = GROUP / 4 * STRIDE;                     // float4 per row per step
-    constexpr int GS = GROUP * STRIDE;                        // floats a row advances per step
-    constexpr int CH = (GROUP / 4) % 10 == 0 ? 10 : GROUP / 4;   // float4 per chain chunk held in registers
-    static_assert((GROUP / 4) % CH == 0, "chunking");
-    const int lane = threadIdx.x & 63;
-    float *ptr[LOADS];
-    const float *lptr[LOADS], *lptr_n[LOADS];
-    int lds_at[LOADS];
-    bool valid[LOADS];
-    if (role == 0) {                                          // (the chainer needs none of the addresses)
-    const int lead0 = __ffsll((unsigned long long)__ballot(have)) - 1;
-    const uint64_t safe = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(off >> 32), lead0) << 32) | (uint32_t)__shfl((int)(uint32_t)off, lead0);
-#pragma unroll
-    for (int i = 0; i < LOADS; i++) {
-        const int idx = lane + 64 * i;
-        const int row = idx / F, q = idx - row * F;
-        const int lead = (row * STRIDE) & 63;                // first chain lane of the row
-        const uint32_t lo = __shfl((uint32_t)off, lead), hi = __shfl((uint32_t)(off >> 32), lead);
-        const uint32_t nlo = __shfl((uint32_t)off_next, lead), nhi = __shfl((uint32_t)(off_next >> 32), lead);
-        valid[i] = idx < QUADS && __shfl((int)have, lead) != 0;
-        ptr[i] = out + (((uint64_t)hi << 32) | lo) + 4 * q;
-        lptr[i] = valid[i] ? ptr[i] : out + safe;
-        lptr_n[i] = (valid[i] && chain_next) ? out + (((uint64_t)nhi << 32) | nlo) + 4 * q : lptr[i];
-        lds_at[i] = STRIDE == 1 ? row * PITCH + 4 * q : (2 * row) * PITCH + 2 * q;
-    }
-    } else {
-#pragma unroll
-        for (int i = 0; i < LOADS; i++) { ptr[i] = out; lptr[i] = lptr_n[i] = out; lds_at[i] = 0; valid[i] = false; }
-    }
+    using Plan = RowPlan<STRIDE, SEQ, GROUP>;
+    constexpr int LOADS = Plan::LOADS, GS = Plan::GS;
+    constexpr int BUF = SEQ * Plan::PITCH;                    // floats per step buffer
+    Plan p;
+    if (role == 0) p.fill(out, have, off, off_next, chain_next, lane);
+    else p.none(out, lane);                                   // (the chainer needs none of the addresses)
     const int groups = n / GROUP;
-    if (role == 0 && !primed) {
-#pragma unroll
-        for (int d = 0; d < D; d++) {
-            const int g = d < groups ? d : groups - 1;
-#pragma unroll
-            for (int i = 0; i < LOADS; i++) ring[d][i] = __builtin_nontemporal_load((const f32x4 *)(lptr[i] + (size_t)g * GS));
-        }
-    }
+    if (role == 0 && !primed) p.prime(ring, groups);
     // Three LDS step buffers (step g in buffer g % 3): while the chainer works on step g the mover first fills step g+1's
     // (rows that were loaded D steps ago) and then empties step g-1's.  In that order, and with every load issued
     // unconditionally (the slot keeps its value by a select when there is nothing to fetch), the wait in front of the
@@ -763,81 +749,22 @@ __device__ __forceinline__ void deemph_rows_duo(float *xs2, float *__restrict__ 
     // the loads, the compiler has to drain the stores of the same phase every time (one in-order memory counter).
     auto feed = [&](f32x4 (&b)[LOADS], int g, bool more) {
         float *xs = xs2 + (g % 3) * BUF;
-        if (more) {
-#pragma unroll
-            for (int i = 0; i < LOADS; i++) {
-                if (QUADS % 64 != 0 && lane + 64 * i >= QUADS) continue;
-                if (STRIDE == 1) {
-                    *(f32x4 *)(xs + lds_at[i]) = b[i];
-                } else {
-                    *(f32x2 *)(xs + lds_at[i]) = f32x2{ b[i].x, b[i].z };
-                    *(f32x2 *)(xs + lds_at[i] + PITCH) = f32x2{ b[i].y, b[i].w };
-                }
-            }
-        }
+        if (more) p.put(xs, b);
         const int gn = g + D;
         const bool here = more && gn < groups;
         const bool ahead = more && !here && chain_next;      // the next frame's first steps (same slots)
         const size_t at = (size_t)(here ? gn : (ahead ? gn - groups : (g < groups ? g : groups - 1))) * GS;   // else: a harmless re-read
 #pragma unroll
         for (int i = 0; i < LOADS; i++) {
-            const f32x4 t = __builtin_nontemporal_load((const f32x4 *)((ahead ? lptr_n[i] : lptr[i]) + at));
+            const f32x4 t = __builtin_nontemporal_load((const f32x4 *)((ahead ? p.lptr_n[i] : p.lptr[i]) + at));
             b[i] = more ? t : b[i];
         }
     };
     // mover: step g's chained rows out of buffer g % 3, scaled, to memory (g = -1: nothing is stored)
-    auto drain = [&](int g) {
-        const float *xs = xs2 + ((g + 3) % 3) * BUF;
-#pragma unroll
-        for (int i = 0; i < LOADS; i++) {
-            f32x4 o;
-            if (QUADS % 64 != 0 && lane + 64 * i >= QUADS) continue;
-            if (STRIDE == 1) {
-                o = *(const f32x4 *)(xs + lds_at[i]);
-            } else {
-                const f32x2 l = *(const f32x2 *)(xs + lds_at[i]), r = *(const f32x2 *)(xs + lds_at[i] + PITCH);
-                o = f32x4{ l.x, r.x, l.y, r.y };
-            }
-            o *= (1.0f / 32768.0f);                                                // tmp / 32768. (exact)
-            if (valid[i] && g >= 0) *(f32x4 *)(ptr[i] + (size_t)(g >= 0 ? g : 0) * GS) = o;
-        }
-    };
+    auto drain = [&](int g) { p.get_store(xs2 + ((g + 3) % 3) * BUF, g >= 0, (size_t)(g >= 0 ? g : 0) * GS); };
     // chainer: step g in buffer g % 3
     auto chain_step = [&](int g) {
-        if (lane < SEQ && have) {
-            f32x4 *row = (f32x4 *)(xs2 + (g % 3) * BUF + lane * PITCH);
-            auto chain = [&](f32x4 (&c)[CH], int k0) {
-#pragma unroll
-                for (int k = 0; k < CH; k++) {
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const float t = c[k][e] + m;
-                        m = t * 0.85000610f;
-                        c[k][e] = t;
-                    }
-                    row[k0 + k] = c[k];
-                }
-            };
-            auto fill = [&](f32x4 (&c)[CH], int k0) {
-#pragma unroll
-                for (int k = 0; k < CH; k++) c[k] = row[k0 + k];
-            };
-            constexpr int NCH = GROUP / 4 / CH;
-            f32x4 ca[CH], cb[CH];
-            fill(ca, 0);
-            if (NCH == 1) {
-                chain(ca, 0);
-            } else {
-#pragma unroll 1
-                for (int k0 = 0; k0 < GROUP / 4; k0 += 2 * CH) {
-                    const bool two = k0 + CH < GROUP / 4;
-                    if (two) fill(cb, k0 + CH);
-                    chain(ca, k0);
-                    if (k0 + 2 * CH < GROUP / 4) fill(ca, k0 + 2 * CH);
-                    if (two) chain(cb, k0 + CH);
-                }
-            }
-        }
+        if (lane < SEQ && have) chain_rows<GROUP>((f32x4 *)(xs2 + (g % 3) * BUF + lane * Plan::PITCH), m);
     };
     // The ring slot of step s is s % D (a frame that is chained to the next one has groups % D == 0, so the next frame's
     // step 0 finds its rows in slot 0 again).
@@ -861,110 +788,35 @@ __device__ __forceinline__ void deemph_rows_duo(float *xs2, float *__restrict__ 
     if (role == 0) drain(groups - 1);
 }
 
-template <int SEQ, int GROUP>
-__global__ __launch_bounds__(64) void celt_deemph_kernel(
-    const uint64_t *__restrict__ rec_base, const afg_celt_frame *__restrict__ recs, float *__restrict__ out,
-    float *__restrict__ states, uint32_t n_chan)
+// this lane's frame sample by sample, eight loads ahead of the chain: layouts the row walk does not cover
+__device__ __forceinline__ void deemph_strided(float *o, int n, int stride, float &m)
 {
-    constexpr int D = (960 / GROUP) >= 4 ? 4 : 2;            // steps in flight (divides the steps of a 20 ms frame)
-    constexpr int LOADS = (SEQ * GROUP / 4 + 63) / 64;
-    __shared__ __attribute__((aligned(16))) float xs[SEQ * (GROUP + 4)];
-    __builtin_amdgcn_s_setprio(3);                            // a serial chain: its instructions go first whenever ready
-    const int lane = threadIdx.x;
-    const uint32_t chan = blockIdx.x * (uint32_t)SEQ + (uint32_t)lane;
-    const bool mine = lane < SEQ && chan < n_chan;
-    const uint32_t chan_c = chan < n_chan ? chan : n_chan - 1;
-    float *st = (states && mine) ? states + (size_t)chan * AFG_CELT_STATE_FLOATS : nullptr;
-    float m = st ? st[2056] : 0.0f;
-    const uint64_t total = rec_base[n_chan];                  // records in the batch
-    if (total == 0) return;
-    uint64_t r = rec_base[chan_c];
-    const uint64_t r_end = mine ? rec_base[chan_c + 1] : r;
-    struct Rec { uint32_t n, stride; uint64_t off; };
-    static_assert(offsetof(afg_celt_frame, out_off) == 8 && offsetof(afg_celt_frame, out_stride) == 16 &&
-                  offsetof(afg_celt_frame, frame_size) == 20, "record layout");
-    auto fetch = [&](uint64_t idx) -> Rec {                   // always a valid record: the fields of one past the end are unused
-        const uint64_t *p = (const uint64_t *)(recs + (idx < total ? idx : total - 1));
-        const uint64_t a = p[1], b = p[2];
-        return Rec{ (uint32_t)(b >> 32) & 0xffffu, (uint32_t)b, a };
-    };
-    // can a step of the SEQ sequences be walked as rows?  Geometry of the first lane that still has a record
-    // (sequences of a wavefront may end at different frames: the finished ones sit the step out)
-    auto rows_ok = [&](const Rec &rc, bool hv, int &n0, int &s0) -> bool {
-        const unsigned long long bal = __ballot(hv);
-        n0 = s0 = 0;
-        if (!bal) return false;
-        const int first = __ffsll(bal) - 1;
-        n0 = __shfl((int)rc.n, first);
-        s0 = __shfl((int)rc.stride, first);
-        bool bad = false;
-        const bool p_have = __shfl_xor((int)hv, 1) != 0;
-        const uint32_t plo = __shfl_xor((uint32_t)rc.off, 1), phi = __shfl_xor((uint32_t)(rc.off >> 32), 1);
-        const uint64_t p_off = ((uint64_t)phi << 32) | plo;
-        if (lane < SEQ) {
-            if (hv) bad = (int)rc.n != n0 || (int)rc.stride != s0;
-            if (s0 == 2) {
-                if (hv != p_have) bad = true;
-                else if (hv) bad = bad || ((lane & 1) ? rc.off != p_off + 1 : (rc.off & 3) != 0);
-            } else if (hv) {
-                bad = bad || (rc.off & 3) != 0;
+    for (int j0 = 0; j0 < n; j0 += 8) {
+        float x[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) x[k] = j0 + k < n ? o[(size_t)(j0 + k) * stride] : 0.0f;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            if (j0 + k < n) {
+                const float t = x[k] + m;
+                m = t * 0.85000610f;
+                o[(size_t)(j0 + k) * stride] = t * (1.0f / 32768.0f);
             }
         }
-        return (s0 == 1 || s0 == 2) && n0 > 0 && n0 % GROUP == 0 && !__any(bad);
-    };
-    Rec cur = fetch(r), nxt = fetch(r + 1);
-    bool have = r < r_end;
-    bool primed = false;
-    f32x4 ring[D][LOADS];
-    while (__any(have)) {
-        const Rec nn = fetch(r + 2);                          // lands while this frame is chained
-        const bool have_n = r + 1 < r_end;
-        int n0, s0, n1, s1;
-        const bool rows = rows_ok(cur, have, n0, s0);
-        const bool rows_n = rows_ok(nxt, have_n, n1, s1);
-        const bool chain_next = rows && rows_n && n1 == n0 && s1 == s0 && __ballot(have_n) == __ballot(have) && (n0 / GROUP) % D == 0;
-        if (rows) {
-            if (s0 == 2) deemph_rows<2, SEQ, GROUP, D>(xs, out, have, cur.off, nxt.off, n0, m, ring, primed, chain_next);
-            else deemph_rows<1, SEQ, GROUP, D>(xs, out, have, cur.off, nxt.off, n0, m, ring, primed, chain_next);
-            primed = chain_next;
-        } else {
-            primed = false;
-            if (have) {
-                const int n = (int)cur.n, stride = (int)cur.stride;
-                float *o = out + cur.off;
-                for (int j0 = 0; j0 < n; j0 += 8) {
-                    float x[8];
-#pragma unroll
-                    for (int k = 0; k < 8; k++) x[k] = j0 + k < n ? o[(size_t)(j0 + k) * stride] : 0.0f;
-#pragma unroll
-                    for (int k = 0; k < 8; k++) {
-                        if (j0 + k < n) {
-                            const float t = x[k] + m;
-                            m = t * 0.85000610f;
-                            o[(size_t)(j0 + k) * stride] = t * (1.0f / 32768.0f);
-                        }
-                    }
-                }
-            }
-        }
-        cur = nxt;
-        nxt = nn;
-        r++;
-        have = r < r_end;
     }
-    if (st) st[2056] = m;
 }
 
-// two wavefronts per SEQ sequences: see deemph_rows_duo
-template <int SEQ, int GROUP>
-__global__ __launch_bounds__(128) void celt_deemph_duo_kernel(
+// The record walk of the pass, SEQ sequences per workgroup: one wavefront (WAVES 1: deemph_rows) or two (WAVES 2: deemph_rows_duo)
+template <int SEQ, int GROUP, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void celt_deemph_kernel(
     const uint64_t *__restrict__ rec_base, const afg_celt_frame *__restrict__ recs, float *__restrict__ out,
     float *__restrict__ states, uint32_t n_chan)
 {
+    static_assert(WAVES == 1 || WAVES == 2, "one wavefront, or a mover and a chainer");
     constexpr int D = (960 / GROUP) >= 4 ? 4 : 2;            // steps in flight (divides the steps of a 20 ms frame)
     constexpr int LOADS = (SEQ * GROUP / 4 + 63) / 64;
-    __shared__ __attribute__((aligned(16))) float xs[3 * SEQ * (GROUP + 4)];
-    const int role = threadIdx.x >> 6;                        // 0 moves, 1 chains
+    __shared__ __attribute__((aligned(16))) float xs[(WAVES == 2 ? 3 : 1) * SEQ * (GROUP + 4)];
+    const int role = WAVES == 2 ? threadIdx.x >> 6 : 1;       // of a pair: 0 moves, 1 chains; a single wavefront does both
     __builtin_amdgcn_s_setprio(3);                            // a serial chain: its instructions go first whenever ready
     const int lane = threadIdx.x & 63;
     const uint32_t chan = blockIdx.x * (uint32_t)SEQ + (uint32_t)lane;
@@ -1020,28 +872,17 @@ __global__ __launch_bounds__(128) void celt_deemph_duo_kernel(
         const bool rows_n = rows_ok(nxt, have_n, n1, s1);
         const bool chain_next = rows && rows_n && n1 == n0 && s1 == s0 && __ballot(have_n) == __ballot(have) && (n0 / GROUP) % D == 0;
         if (rows) {
-            if (s0 == 2) deemph_rows_duo<2, SEQ, GROUP, D>(xs, out, have, cur.off, nxt.off, n0, m, ring, primed, chain_next, role);
-            else deemph_rows_duo<1, SEQ, GROUP, D>(xs, out, have, cur.off, nxt.off, n0, m, ring, primed, chain_next, role);
+            if constexpr (WAVES == 2) {
+                if (s0 == 2) deemph_rows_duo<2, SEQ, GROUP, D>(xs, out, have, cur.off, nxt.off, n0, m, ring, primed, chain_next, lane, role);
+                else deemph_rows_duo<1, SEQ, GROUP, D>(xs, out, have, cur.off, nxt.off, n0, m, ring, primed, chain_next, lane, role);
+            } else {
+                if (s0 == 2) deemph_rows<2, SEQ, GROUP, D>(xs, out, have, cur.off, nxt.off, n0, m, ring, primed, chain_next, lane);
+                else deemph_rows<1, SEQ, GROUP, D>(xs, out, have, cur.off, nxt.off, n0, m, ring, primed, chain_next, lane);
+            }
             primed = chain_next;
         } else {
             primed = false;
-            if (have && role == 1) {
-                const int n = (int)cur.n, stride = (int)cur.stride;
-                float *o = out + cur.off;
-                for (int j0 = 0; j0 < n; j0 += 8) {
-                    float x[8];
-#pragma unroll
-                    for (int k = 0; k < 8; k++) x[k] = j0 + k < n ? o[(size_t)(j0 + k) * stride] : 0.0f;
-#pragma unroll
-                    for (int k = 0; k < 8; k++) {
-                        if (j0 + k < n) {
-                            const float t = x[k] + m;
-                            m = t * 0.85000610f;
-                            o[(size_t)(j0 + k) * stride] = t * (1.0f / 32768.0f);
-                        }
-                    }
-                }
-            }
+            if (have && role == 1) deemph_strided(out + cur.off, (int)cur.n, (int)cur.stride, m);
         }
         cur = nxt;
         nxt = nn;
@@ -1070,7 +911,7 @@ void launch_deemph(const uint64_t *d_rec_base, const afg_celt_frame *d_recs, flo
 {
     int seq = deemph_seq_for(n_chan);
     // Few, long sequences (fewer than 16384: not enough for 512 wavefronts of 32 chains, the form that runs at memory rate): the
-    // pass is as long as its longest chain, so the chain gets a wavefront of its own (celt_deemph_duo_kernel).
+    // pass is as long as its longest chain, so the chain gets a wavefront of its own (WAVES 2: deemph_rows_duo).
     // afg_dev_option("celt_de_duo", 0 / 1) overrides (tests run both forms of every instantiation).
     bool duo = seq < 32;
     if (afg::dev_option(afg::kDevCeltDeDuo) >= 0) duo = afg::dev_option(afg::kDevCeltDeDuo) != 0;
@@ -1079,19 +920,19 @@ void launch_deemph(const uint64_t *d_rec_base, const afg_celt_frame *d_recs, flo
         if (seq > 8) seq = 8;
         const dim3 grid((n_chan + (uint32_t)seq - 1) / (uint32_t)seq), block(128);
         switch (seq) {
-        case 8:  hipLaunchKernelGGL((celt_deemph_duo_kernel<8, 120>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
-        case 4:  hipLaunchKernelGGL((celt_deemph_duo_kernel<4, 240>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
-        default: hipLaunchKernelGGL((celt_deemph_duo_kernel<2, 480>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
+        case 8:  hipLaunchKernelGGL((celt_deemph_kernel<8, 120, 2>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
+        case 4:  hipLaunchKernelGGL((celt_deemph_kernel<4, 240, 2>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
+        default: hipLaunchKernelGGL((celt_deemph_kernel<2, 480, 2>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
         }
         return;
     }
     const dim3 grid((n_chan + (uint32_t)seq - 1) / (uint32_t)seq), block(64);
     switch (seq) {
-    case 32: hipLaunchKernelGGL((celt_deemph_kernel<32, 40>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
-    case 16: hipLaunchKernelGGL((celt_deemph_kernel<16, 60>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
-    case 8:  hipLaunchKernelGGL((celt_deemph_kernel<8, 120>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
-    case 4:  hipLaunchKernelGGL((celt_deemph_kernel<4, 240>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
-    default: hipLaunchKernelGGL((celt_deemph_kernel<2, 480>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
+    case 32: hipLaunchKernelGGL((celt_deemph_kernel<32, 40, 1>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
+    case 16: hipLaunchKernelGGL((celt_deemph_kernel<16, 60, 1>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
+    case 8:  hipLaunchKernelGGL((celt_deemph_kernel<8, 120, 1>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
+    case 4:  hipLaunchKernelGGL((celt_deemph_kernel<4, 240, 1>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
+    default: hipLaunchKernelGGL((celt_deemph_kernel<2, 480, 1>), grid, block, 0, stream, d_rec_base, d_recs, d_out, d_states, n_chan); break;
     }
 }
 
@@ -1280,6 +1121,18 @@ extern "C" int afg_celt_transform_streams_hip(uint32_t n_chan, const uint64_t *d
     return celt_transform_impl(n_chan, d_rec_base, d_recs, d_coeffs, d_out, d_states, (hipStream_t)hip_stream, (hipStream_t)hip_tail_stream);
 }
 
+// What is queued on `on` from here runs behind what `after` holds now (an event between the two streams).
+static int run_behind(hipStream_t after, hipStream_t on, const char *who)
+{
+    hipEvent_t done = nullptr;
+    AFG_HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(done, after);
+    if (e == hipSuccess) e = hipStreamWaitEvent(on, done, 0);
+    (void)hipEventDestroy(done);                                            // released once the record has completed
+    if (e != hipSuccess) { afg::set_error("%s: %s", who, hipGetErrorString(e)); return AFG_ERR_HIP; }
+    return AFG_OK;
+}
+
 static int celt_transform_impl(uint32_t n_chan, const uint64_t *d_rec_base, const afg_celt_frame *d_recs, const float *d_coeffs,
                                float *d_out, float *d_states, hipStream_t hip_stream, hipStream_t tail_stream)
 {
@@ -1298,12 +1151,7 @@ static int celt_transform_impl(uint32_t n_chan, const uint64_t *d_rec_base, cons
     const bool forced_walk = path_opt == 3;
     if (forced_walk || (!forced_exact && afg::numeric_mode() == AFG_NUMERIC_TOLERANCE)) {
         if (tail_stream) {                                   // one kernel, all of it beside what the caller queues next
-            hipEvent_t done = nullptr;
-            AFG_HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-            hipError_t e = hipEventRecord(done, hip_stream);
-            if (e == hipSuccess) e = hipStreamWaitEvent(tail_stream, done, 0);
-            (void)hipEventDestroy(done);
-            if (e != hipSuccess) { afg::set_error("afg_celt_transform_streams_hip: %s", hipGetErrorString(e)); return AFG_ERR_HIP; }
+            if (int rc = run_behind(hip_stream, tail_stream, "afg_celt_transform_streams_hip")) return rc;
             hip_stream = tail_stream;
         }
         return afg::celt_walk_launch(n_chan, d_rec_base, d_recs, d_coeffs, d_out, d_states, hip_stream);
@@ -1312,12 +1160,7 @@ static int celt_transform_impl(uint32_t n_chan, const uint64_t *d_rec_base, cons
     const uint32_t pairs = (n_chan + 1) / 2;
     if (use_stream_path(pairs)) {
         if (tail_stream) {                                   // the whole walk is the serial part: all of it behind the event
-            hipEvent_t done = nullptr;
-            AFG_HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-            hipError_t e = hipEventRecord(done, hip_stream);
-            if (e == hipSuccess) e = hipStreamWaitEvent(tail_stream, done, 0);
-            (void)hipEventDestroy(done);
-            if (e != hipSuccess) { afg::set_error("afg_celt_transform_streams_hip: %s", hipGetErrorString(e)); return AFG_ERR_HIP; }
+            if (int rc = run_behind(hip_stream, tail_stream, "afg_celt_transform_streams_hip")) return rc;
             hip_stream = tail_stream;
         }
         // enough streams to fill the device: one pass over the coefficients, one over the PCM
@@ -1344,12 +1187,7 @@ static int celt_transform_impl(uint32_t n_chan, const uint64_t *d_rec_base, cons
     // stream they run there, behind an event, beside whatever the caller queues on hip_stream next.
     hipStream_t serial = (hipStream_t)hip_stream;
     if (tail_stream) {
-        hipEvent_t done = nullptr;
-        AFG_HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-        hipError_t e = hipEventRecord(done, (hipStream_t)hip_stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(tail_stream, done, 0);
-        (void)hipEventDestroy(done);                                        // released once the record has completed
-        if (e != hipSuccess) { afg::set_error("afg_celt_transform_streams_hip: %s", hipGetErrorString(e)); return AFG_ERR_HIP; }
+        if (int rc = run_behind(hip_stream, tail_stream, "afg_celt_transform_streams_hip")) return rc;
         serial = tail_stream;
     }
     hipLaunchKernelGGL(celt_postfilter_kernel, dim3(n_chan), dim3(64), 0, serial, d_rec_base, d_recs, d_out, d_states, n_chan);

@@ -59,6 +59,10 @@ def test_celt_short_period_postfilter(gpu):
 
 
 def test_celt_chunked_with_state_equals_whole(gpu):
+    chunked_with_state_case(gpu)
+
+
+def chunked_with_state_case(gpu):
     rec_base, recs, coeffs, total = synthetic.celt_batch(9, [10], [2], p_postfilter=0.7, p_transient=0.3)
     want = oraclelib.celt_transform(rec_base, recs, coeffs, total)
     states = np.zeros((2, afgpu.CELT_STATE_FLOATS), np.float32)
@@ -102,6 +106,19 @@ def test_celt_deemph_sequences_per_wavefront(gpu, monkeypatch, seq, duo):
 
 def test_celt_padded_output_stride(gpu):
     """out_stride 3 (stereo written into a 3-channel plane) and an unaligned mono row: per-lane path."""
+    padded_output_stride_case(gpu)
+
+
+def check_written(got, want, recs, total):
+    """Bit-exact on every slot a record names; every other slot untouched."""
+    written = np.zeros(total, bool)
+    for r in recs:
+        written[int(r["out_off"]) + np.arange(int(r["frame_size"])) * int(r["out_stride"])] = True
+    assert not np.isnan(got[written]).any() and np.isnan(got[~written]).all()
+    assert np.array_equal(got[written].view(np.uint32), want[written].view(np.uint32))
+
+
+def padded_output_stride_case(gpu):
     rec_base, recs, coeffs, total = synthetic.celt_batch(22, [4, 4], [2, 1])
     stereo = recs["out_stride"] == 2
     recs["out_off"][stereo] = (recs["out_off"][stereo] // 2) * 3 + recs["out_off"][stereo] % 2
@@ -112,11 +129,47 @@ def test_celt_padded_output_stride(gpu):
     total = int(recs["out_off"][mono].max()) + 960
     want = oraclelib.celt_transform(rec_base, recs, coeffs, total)
     got, _ = run_gpu(gpu, rec_base, recs, coeffs, total)
-    written = np.zeros(total, bool)
-    for r in recs:
-        written[int(r["out_off"]) + np.arange(int(r["frame_size"])) * int(r["out_stride"])] = True
-    assert not np.isnan(got[written]).any() and np.isnan(got[~written]).all()
-    assert np.array_equal(got[written].view(np.uint32), want[written].view(np.uint32))
+    check_written(got, want, recs, total)
+
+
+@pytest.mark.parametrize("duo", [0, 1])
+def test_celt_padded_output_stride_both_forms(gpu, monkeypatch, duo):
+    """The strided per-lane path of the de-emphasis walk as one wavefront and as a mover / chainer pair (the host's own
+    choice for three sequences is the pair)."""
+    monkeypatch.setenv("AFG_CELT_DE_DUO", str(duo))
+    padded_output_stride_case(gpu)
+
+
+@pytest.mark.parametrize("duo", [0, 1])
+def test_celt_chunked_with_state_both_forms(gpu, monkeypatch, duo):
+    """The de-emphasis memory carried across calls (state word 2056), read and saved by the single wavefront and by the
+    chainer of a pair."""
+    monkeypatch.setenv("AFG_CELT_DE_DUO", str(duo))
+    chunked_with_state_case(gpu)
+
+
+def empty_sequence_batch():
+    """Three stereo streams of four 960-sample frames; the second stream's second channel has no records (its slots of the
+    interleaved plane stay unwritten)."""
+    rec_base, recs, coeffs, total = synthetic.celt_batch(23, [4, 4, 4], [2, 2, 2])
+    lo, hi = int(rec_base[3]), int(rec_base[4])
+    recs = np.concatenate([recs[:lo], recs[hi:]])
+    rec_base = rec_base.copy()
+    rec_base[4:] -= np.uint64(hi - lo)                       # sequence 3: rec_base[3] == rec_base[4]
+    return rec_base, recs, coeffs, total
+
+
+@pytest.mark.parametrize("duo", [0, 1])
+def test_celt_empty_sequence_inside_wavefront(gpu, monkeypatch, duo):
+    """Four chain lanes per wavefront: in the wavefront of sequences 0 .. 3 lane 2 has a stereo record and its partner lane
+    none, so its frames take the per-lane path, while the wavefront of sequences 4 and 5 walks rows."""
+    monkeypatch.setenv("AFG_CELT_DE_SEQ", "4")
+    monkeypatch.setenv("AFG_CELT_DE_DUO", str(duo))
+    rec_base, recs, coeffs, total = empty_sequence_batch()
+    assert rec_base[3] == rec_base[4] and len(recs) == 20
+    want = oraclelib.celt_transform(rec_base, recs, coeffs, total)
+    got, _ = run_gpu(gpu, rec_base, recs, coeffs, total)
+    check_written(got, want, recs, total)
 
 
 def opus_output_inputs():
