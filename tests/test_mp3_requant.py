@@ -10,56 +10,9 @@ import pytest
 
 import afgpu
 import mp3_bitstream as mb
+from mp3_requant_model import requant_numpy
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "mathjax_invalid_keypress.mp3")
-
-
-def requant_numpy(q, granules, sdesc):
-    """float32 statement of the device kernel: [blocks, 576] spectra."""
-    bol, dst, p43 = afgpu.mp3_qtables()
-    f32 = np.float32
-    out = np.zeros(q.shape, f32)
-    for g in granules:
-        nch, b0 = int(g["nch"]), int(g["q_off"]) // 576
-        x = np.zeros((nch, 576), f32)
-        for c in range(nch):
-            v = q[b0 + c].astype(np.int64)
-            a = np.abs(v)
-            one = g["scale"][c][bol[int(g["table"][c]) & 31]]
-            p = np.zeros(576, f32)
-            small = a < 129
-            p[small] = p43[16 + a[small]]
-            big = ~small
-            if big.any():                                           # L3_pow_43 for x >= 129
-                xb = a[big]
-                mult = np.where(xb < 1024, 16, 256).astype(f32)
-                xb = np.where(xb < 1024, xb << 3, xb)
-                sign = (2 * xb) & 64
-                frac = ((xb & 63) - sign).astype(f32) / ((xb & ~63) + sign).astype(f32)
-                poly = f32(1.0) + frac * (f32(4.0) / f32(3) + frac * (f32(2.0) / f32(9)))
-                p[big] = p43[16 + ((xb + sign) >> 6)] * poly * mult
-            r = one.astype(f32) * p
-            x[c] = np.where(v == 0, f32(0), np.where(v < 0, -r, r))
-        if nch == 2 and g["stereo"]:
-            mode = np.full(576, 1, np.uint8)
-            fl = fr = None
-            if g["stereo"] == 2:
-                sd = sdesc[int(g["sdesc"])]
-                b = bol[int(g["table"][0]) & 31]
-                mode, fl, fr = sd["type"][b], sd["fl"][b], sd["fr"][b]
-            a0, a1 = x[0].copy(), x[1].copy()
-            ms = mode == 1
-            x[0][ms], x[1][ms] = (a0 + a1)[ms], (a0 - a1)[ms]
-            if fl is not None:
-                it = mode == 2
-                x[1][it], x[0][it] = (a0 * fr)[it], (a0 * fl)[it]
-        for c in range(nch):
-            t = int(g["table"][c])
-            if t & 0x80:
-                out[b0 + c][dst[t & 31]] = x[c]
-            else:
-                out[b0 + c] = x[c]
-    return out
 
 
 def check_file(data):

@@ -61,3 +61,27 @@ def test_closed_form_equals_the_reference_loop():
     for seed in (5, 6, 7):
         pk, cv, pt, st, spec = cases.hand_made(seed, trials=80)
         cases.same_floats(kernel_statement(pk, cv, pt, st, spec, tab), oraclelib.vorbis_floor(pk, cv, pt, st, spec))
+
+
+def test_closed_form_at_the_two_smallest_block_sizes():
+    """cases.small_blocks (n2 = 32 and 64 among n2 = 1024): the statement equals the reference loop, the guard floats
+    between the packets stay as they were, and the set holds what it is there for"""
+    tab = inverse_db_table()
+    for seed in (5, 6):
+        pk, cv, pt, st, spec, guard = cases.small_blocks(seed)
+        want = oraclelib.vorbis_floor(pk, cv, pt, st, spec)
+        cases.same_floats(kernel_statement(pk, cv, pt, st, spec, tab), want)
+        assert (want.view(np.uint32)[guard] == cases.GUARD_BITS).all() and guard.sum() >= 4 * (len(pk) + 1)
+        assert (pk["spec_off"] % 4 == 0).all() and set(int(n) for n in pk["n2"]) == {32, 64, 1024}
+        small = pk[pk["n2"] < 1024]
+        assert set(int(c) for c in small["channels"]) == set(range(1, 9))
+        assert (small["n_steps"] == 0).any() and (small["n_steps"] >= 2).any()
+        for k in small[small["n_steps"] >= 2]:                          # one channel in every step of the packet
+            s = st[int(k["step_off"]):int(k["step_off"]) + int(k["n_steps"])]
+            assert any((s == c).any(axis=1).all() for c in range(int(k["channels"])))
+        npts = np.concatenate([cv["n_points"][int(k["curve_index"]):int(k["curve_index"]) + int(k["channels"])] for k in small])
+        n2s = np.concatenate([np.full(int(k["channels"]), int(k["n2"])) for k in small])
+        assert (npts == 0).any() and (npts == 1).any() and (npts == 2).any() and (npts == n2s + 1).any()
+        last_x = np.array([pt[int(c["point_off"]) + int(c["n_points"]) - 1, 0] if c["n_points"] else -1 for c in cv])
+        first = np.concatenate([np.arange(int(k["curve_index"]), int(k["curve_index"]) + int(k["channels"])) for k in small])
+        assert ((last_x[first] > 0) & (last_x[first] < n2s)).any() and (last_x[first] > n2s).any()

@@ -68,6 +68,21 @@ def test_hand_made_curves(gpu):
         assert np.isnan(want).any() or np.isinf(want).any()
 
 
+def test_the_two_smallest_block_sizes(gpu):
+    """Block sizes 64 and 128 (n2 = 32 and 64: 8 and 16 of a workgroup's 256 lanes take bins) next to n2 = 1024 in one launch,
+    guard floats between the packets.  Hand-made records only: tests/vorbis_bitstream.make_file writes a file with
+    bs=(64, 128), but afg_vorbis_parse_r refuses every stream whose short block is below 256 (the transform stage does not
+    take them), so test_records_of_files cannot carry such files and the generator stays as it is."""
+    import vorbis_floor_cases as cases
+    for seed in (5, 6):
+        pk, cv, pt, st, spec, guard = cases.small_blocks(seed)
+        want = oraclelib.vorbis_floor(pk, cv, pt, st, spec)
+        got = run_kernel(gpu, pk, cv, pt, st, spec)
+        assert (got.view(np.uint32)[guard] == cases.GUARD_BITS).all(), np.nonzero(got.view(np.uint32)[guard] != cases.GUARD_BITS)[0][:8]
+        cases.same_floats(got, want)
+        assert not guard.all() and (want.view(np.uint32)[guard] == cases.GUARD_BITS).all()
+
+
 def test_batch_and_stream_equal_the_host_floor(gpu, monkeypatch):
     """the outer surface with the floor on the device (default) and in the host parser: the same PCM, bit for bit"""
     import vorbis_bitstream as vb
