@@ -18,7 +18,9 @@
 //     R = 4  (n = 1024):  4 x 4 x 4 x 4        R = 8  (n = 2048):  8 x 8 x 8        R = 16 (n = 4096): 16 x 4 x 16
 //
 // (tests/vorbis_walk_model.py restates the index algebra of every pass on [64 lanes][R] arrays and checks it against a
-// library FFT, and every LDS access for bank conflicts, on the CPU.)
+// library FFT, and every LDS access for bank conflicts, on the CPU.)  The transform, the window and the carried state are
+// written once over the value type of the channel count, Val<1> = f2 and Val<2> = c2 (a stereo pair channel-packed): the
+// primitives under "one value type per channel count" are all that knows which of the two it is.
 // Window and overlap never see y: output frames j and n/2-1-j of a long block that follows a long block are
 //
 //     out[j]        =  a w[j]        - b w[n/2-1-j]          a = u_cur[n/4+j],  b = u_prev[n/4-1-j]
@@ -47,6 +49,7 @@
 
 #include <mutex>
 #include <type_traits>
+#include <utility>
 
 #include <cmath>
 
@@ -73,58 +76,159 @@ struct Geo {
     static_assert(kTabFloats % 4 == 0, "staged in 16-byte pieces");
 };
 
-// complex product: a pair of packed instructions (round 6; four scalar ones before)
+// ---- one value type per channel count -----------------------------------------------------------------------------------
+// A mono wavefront holds a complex value as f2: (re, im) of its channel.  A stereo wavefront runs the same transform on both
+// channels and holds it channel-packed (round 6) as c2 -- re = (ch0, ch1), im = (ch0, ch1), each a register pair: every real
+// operation of the transform is ONE packed instruction for the two channels (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32:
+// 2 x 64 lanes per issue slot), twiddles and window taps are broadcast through op_sel, multiplications by +-i are register
+// renaming, and the windowed frames come out as (ch0, ch1) pairs: the order of the interleaved PCM.  Against one f2 per
+// channel a stereo long block needs about 410 vector instructions instead of 725 -- the walk was issue-bound, not
+// memory-bound (profiles/r06_pmc_vorbis_walk_kernel.json: VALU busy 0.61 of a SIMD's cycles at two wavefronts, fetch 1.07 x
+// the bytes needed).
+// The transform below is written once over V = Val<CH> and the primitives of this section.  Where a primitive is a sum of
+// TWO products the two types keep an expression each (rot16, window_ola): under -ffp-contract=fast the compiler picks the
+// product the mono form fuses, the stereo form names it, and the PCM of either must not move.
+struct c2 { f2 re, im; };
+template <int CH> struct ValOf { using type = f2; };
+template <> struct ValOf<2> { using type = c2; };
+template <int CH> using Val = typename ValOf<CH>::type;
+template <typename V> constexpr int kChannels = std::is_same_v<V, c2> ? 2 : 1;
+// a real number per channel: float, or (ch0, ch1)
+template <int CH> using Real = std::conditional_t<CH == 2, f2, float>;
+
+__device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ __forceinline__ f2 splat(float v) { return f2{ v, v }; }
+
+__device__ __forceinline__ float re(f2 a) { return a.x; }
+__device__ __forceinline__ float im(f2 a) { return a.y; }
+__device__ __forceinline__ f2 re(c2 a) { return a.re; }
+__device__ __forceinline__ f2 im(c2 a) { return a.im; }
+__device__ __forceinline__ f2 cplx(float r, float i) { return f2{ r, i }; }
+__device__ __forceinline__ c2 cplx(f2 r, f2 i) { return c2{ r, i }; }
+// channel c of a real
+__device__ __forceinline__ float chan_of(float v, int) { return v; }
+__device__ __forceinline__ float chan_of(f2 v, int c) { return c ? v.y : v.x; }
+__device__ __forceinline__ void set_chan(float &d, int, float v) { d = v; }
+__device__ __forceinline__ void set_chan(f2 &d, int c, float v)
+{
+    if (c) d.y = v;
+    else d.x = v;
+}
+
+__device__ __forceinline__ c2 operator+(c2 a, c2 b) { return c2{ a.re + b.re, a.im + b.im }; }
+__device__ __forceinline__ c2 operator-(c2 a, c2 b) { return c2{ a.re - b.re, a.im - b.im }; }
+template <typename V> __device__ __forceinline__ V add_mi(V a, V b) { return cplx(re(a) + im(b), im(a) - re(b)); }   // a + (-i) b
+template <typename V> __device__ __forceinline__ V add_pi(V a, V b) { return cplx(re(a) - im(b), im(a) + re(b)); }   // a + i b
+// d + s x and d - s x, s a real constant (one product: the contraction and the spelled-out fma round alike)
+__device__ __forceinline__ float madd(float d, float s, float x) { return d + s * x; }
+__device__ __forceinline__ float msub(float d, float s, float x) { return d - s * x; }
+__device__ __forceinline__ f2 madd(f2 d, float s, f2 x) { return fma2(x, splat(s), d); }
+__device__ __forceinline__ f2 msub(f2 d, float s, f2 x) { return fma2(-x, splat(s), d); }
+// times one complex factor: a pair of packed instructions (round 6; four scalar ones before); both channels' values: four
 __device__ __forceinline__ f2 cmul(f2 a, f2 w) { return pk_cmul_fused(a, w); }
+__device__ __forceinline__ c2 cmul(c2 a, f2 w)
+{
+    const f2 wr = w.xx, wi = w.yy;
+    return c2{ fma2(-a.im, wi, a.re * wr), fma2(a.im, wr, a.re * wi) };
+}
+// a * exp(-2 pi i M / 16) for M = 1, 3, 9: two products per part
+template <int M>
+__device__ __forceinline__ f2 rot16(f2 a)
+{
+    constexpr float c1 = 0.92387953251128675613f, s1 = 0.38268343236508977173f;
+    if constexpr (M == 1) return f2{ a.x * c1 + a.y * s1, a.y * c1 - a.x * s1 };
+    else if constexpr (M == 3) return f2{ a.x * s1 + a.y * c1, a.y * s1 - a.x * c1 };
+    else return f2{ -(a.x * c1 + a.y * s1), a.x * s1 - a.y * c1 };
+}
+template <int M>
+__device__ __forceinline__ c2 rot16(c2 a)
+{
+    const f2 c1 = splat(0.92387953251128675613f), s1 = splat(0.38268343236508977173f);
+    if constexpr (M == 1) return c2{ fma2(a.im, s1, a.re * c1), fma2(-a.re, s1, a.im * c1) };
+    else if constexpr (M == 3) return c2{ fma2(a.im, c1, a.re * s1), fma2(-a.re, c1, a.im * s1) };
+    else return c2{ -fma2(a.im, s1, a.re * c1), fma2(a.re, s1, -(a.im * c1)) };
+}
+// Window and overlap of frames j0, j0+1 (lo0, lo1) and n/2-2-j0, n/2-1-j0 (hi0, hi1): a0, -a1n the block's own u, b0, b1 the
+// carried ones, w0 = (w[j0], w[j0+1]), w1 = (w[n/2-2-j0], w[n/2-1-j0])
+__device__ __forceinline__ void window_ola(float a0, float a1n, float b0, float b1, f2 w0, f2 w1, float &lo0, float &lo1, float &hi0,
+                                           float &hi1)
+{
+    const float a1 = -a1n;
+    lo0 = a0 * w0.x - b0 * w1.y;
+    lo1 = a1 * w0.y - b1 * w1.x;
+    hi1 = -a0 * w1.y - b0 * w0.x;
+    hi0 = -a1 * w1.x - b1 * w0.y;
+}
+__device__ __forceinline__ void window_ola(f2 a0, f2 a1n, f2 b0, f2 b1, f2 w0, f2 w1, f2 &lo0, f2 &lo1, f2 &hi0, f2 &hi1)
+{
+    lo0 = fma2(-b0, w1.yy, a0 * w0.xx);
+    lo1 = fma2(-b1, w1.xx, -(a1n * w0.yy));
+    hi1 = fma2(-b0, w0.xx, -(a0 * w1.yy));
+    hi0 = fma2(-b1, w0.yy, a1n * w1.xx);
+}
+// The transform area of a wavefront, F complex slots per channel: one channel's values as f2 slots; a stereo pair's as a
+// plane of real parts and a plane of imaginary parts, each slot the two channels' values (8 bytes either way: the slot
+// indices, and so the bank behaviour, are the same, tests/vorbis_walk_model.py)
+template <int F> __device__ __forceinline__ void put(f2 *U, int slot, f2 v) { U[slot] = v; }
+template <int F> __device__ __forceinline__ void put(f2 *U, int slot, c2 v)
+{
+    U[slot] = v.re;
+    (U + F)[slot] = v.im;
+}
+template <int F> __device__ __forceinline__ void get(const f2 *U, int slot, f2 &v) { v = U[slot]; }
+template <int F> __device__ __forceinline__ void get(const f2 *U, int slot, c2 &v) { v = c2{ U[slot], (U + F)[slot] }; }
 
 // 4-point DFT, forward, natural order in and out
-__device__ __forceinline__ void dft4(f2 &a0, f2 &a1, f2 &a2, f2 &a3)
+template <typename V>
+__device__ __forceinline__ void dft4(V &a0, V &a1, V &a2, V &a3)
 {
-    const f2 s02 = a0 + a2, d02 = a0 - a2, s13 = a1 + a3, d13 = a1 - a3;
+    const V s02 = a0 + a2, d02 = a0 - a2, s13 = a1 + a3, d13 = a1 - a3;
     a0 = s02 + s13;
     a2 = s02 - s13;
-    a1 = f2{ d02.x + d13.y, d02.y - d13.x };
-    a3 = f2{ d02.x - d13.y, d02.y + d13.x };
+    a1 = add_mi(d02, d13);
+    a3 = add_pi(d02, d13);
 }
 
 // 8-point DFT, forward (exp(-2 pi i a b / 8)), natural order in and out
-__device__ __forceinline__ void dft8(f2 (&a)[8])
+template <typename V>
+__device__ __forceinline__ void dft8(V (&a)[8])
 {
     constexpr float s = 0.70710678118654752440f;
-    const f2 b0 = a[0] + a[4], b4 = a[0] - a[4], b1 = a[1] + a[5], b5 = a[1] - a[5];
-    const f2 b2 = a[2] + a[6], b6 = a[2] - a[6], b3 = a[3] + a[7], b7 = a[3] - a[7];
-    const f2 c0 = b0 + b2, c2 = b0 - b2, c1 = b1 + b3, c3 = b1 - b3;
+    const V b0 = a[0] + a[4], b4 = a[0] - a[4], b1 = a[1] + a[5], b5 = a[1] - a[5];
+    const V b2 = a[2] + a[6], b6 = a[2] - a[6], b3 = a[3] + a[7], b7 = a[3] - a[7];
+    const V c0 = b0 + b2, c2_ = b0 - b2, c1 = b1 + b3, c3 = b1 - b3;
     a[0] = c0 + c1;
     a[4] = c0 - c1;
-    a[2] = f2{ c2.x + c3.y, c2.y - c3.x };
-    a[6] = f2{ c2.x - c3.y, c2.y + c3.x };
-    const f2 d0 = f2{ b4.x + b6.y, b4.y - b6.x }, d2 = f2{ b4.x - b6.y, b4.y + b6.x };
-    const f2 p5 = f2{ b5.x + b5.y, b5.y - b5.x }, p7 = f2{ b7.y - b7.x, -(b7.x + b7.y) };
-    const f2 D1 = p5 + p7, D3 = p5 - p7;
-    a[1] = f2{ d0.x + s * D1.x, d0.y + s * D1.y };
-    a[5] = f2{ d0.x - s * D1.x, d0.y - s * D1.y };
-    a[3] = f2{ d2.x + s * D3.y, d2.y - s * D3.x };
-    a[7] = f2{ d2.x - s * D3.y, d2.y + s * D3.x };
+    a[2] = add_mi(c2_, c3);
+    a[6] = add_pi(c2_, c3);
+    const V d0 = add_mi(b4, b6), d2 = add_pi(b4, b6);
+    // p5 = b5 (1 - i), p7 = -b7 (1 + i), both without their factor 1/sqrt 2
+    const V p5 = cplx(re(b5) + im(b5), im(b5) - re(b5)), p7 = cplx(im(b7) - re(b7), -(re(b7) + im(b7)));
+    const V D1 = p5 + p7, D3 = p5 - p7;
+    a[1] = cplx(madd(re(d0), s, re(D1)), madd(im(d0), s, im(D1)));
+    a[5] = cplx(msub(re(d0), s, re(D1)), msub(im(d0), s, im(D1)));
+    a[3] = cplx(madd(re(d2), s, im(D3)), msub(im(d2), s, re(D3)));
+    a[7] = cplx(msub(re(d2), s, im(D3)), madd(im(d2), s, re(D3)));
 }
 
 // a * exp(-2 pi i M / 16) for the exponents a 4 x 4 split of 16 points meets (0, 1, 2, 3, 4, 6, 9)
-template <int M>
-__device__ __forceinline__ f2 mul_w16(f2 a)
+template <int M, typename V>
+__device__ __forceinline__ V mul_w16(V a)
 {
-    constexpr float c1 = 0.92387953251128675613f, s1 = 0.38268343236508977173f, h = 0.70710678118654752440f;
+    constexpr float h = 0.70710678118654752440f;
     if constexpr (M == 0) return a;
-    else if constexpr (M == 1) return f2{ a.x * c1 + a.y * s1, a.y * c1 - a.x * s1 };
-    else if constexpr (M == 2) return f2{ (a.x + a.y) * h, (a.y - a.x) * h };
-    else if constexpr (M == 3) return f2{ a.x * s1 + a.y * c1, a.y * s1 - a.x * c1 };
-    else if constexpr (M == 4) return f2{ a.y, -a.x };
-    else if constexpr (M == 6) return f2{ (a.y - a.x) * h, -(a.x + a.y) * h };
+    else if constexpr (M == 2) return cplx((re(a) + im(a)) * h, (im(a) - re(a)) * h);
+    else if constexpr (M == 4) return cplx(im(a), -re(a));
+    else if constexpr (M == 6) return cplx((im(a) - re(a)) * h, -((re(a) + im(a)) * h));
     else {
-        static_assert(M == 9, "exponent");
-        return f2{ -(a.x * c1 + a.y * s1), a.x * s1 - a.y * c1 };
+        static_assert(M == 1 || M == 3 || M == 9, "exponent");
+        return rot16<M>(a);
     }
 }
 
 // 16-point DFT, forward, natural order in and out: index n = nl + 4 nh, four 4-point DFTs over nh, W_16^(nl ka), four over nl
-__device__ __forceinline__ void dft16(f2 (&a)[16])
+template <typename V>
+__device__ __forceinline__ void dft16(V (&a)[16])
 {
 #pragma unroll
     for (int nl = 0; nl < 4; nl++) dft4(a[nl], a[nl + 4], a[nl + 8], a[nl + 12]);       // a[nl + 4 ka]
@@ -138,105 +242,10 @@ __device__ __forceinline__ void dft16(f2 (&a)[16])
     a[11] = mul_w16<6>(a[11]);
     a[15] = mul_w16<9>(a[15]);
     // over nl for each ka: inputs a[nl + 4 ka], outputs k = ka + 4 kb
-    f2 o[16];
+    V o[16];
 #pragma unroll
     for (int ka = 0; ka < 4; ka++) {
-        f2 x0 = a[4 * ka], x1 = a[4 * ka + 1], x2 = a[4 * ka + 2], x3 = a[4 * ka + 3];
-        dft4(x0, x1, x2, x3);
-        o[ka] = x0;
-        o[ka + 4] = x1;
-        o[ka + 8] = x2;
-        o[ka + 12] = x3;
-    }
-#pragma unroll
-    for (int k = 0; k < 16; k++) a[k] = o[k];
-}
-
-// ---- channel-packed arithmetic (round 6) ----------------------------------------------------------------------------------
-// A stereo wavefront runs the same transform on both channels.  Held as c2 -- re = (ch0, ch1), im = (ch0, ch1), each a register
-// pair -- every real operation of the transform is ONE packed instruction for the two channels (v_pk_add_f32 / v_pk_mul_f32 /
-// v_pk_fma_f32: 2 x 64 lanes per issue slot), twiddles and window taps are broadcast through op_sel, multiplications by +-i
-// are register renaming, and the windowed frames come out as (ch0, ch1) pairs: the order of the interleaved PCM.  Against
-// the complex-pair form (re, im of one channel per register pair, above: what a mono stream runs) a stereo long block needs
-// about 410 vector instructions instead of 725 -- the walk was issue-bound, not memory-bound (profiles/r06_pmc_vorbis_walk_kernel.json:
-// VALU busy 0.61 of a SIMD's cycles at two wavefronts, fetch 1.07 x the bytes needed).
-struct c2 { f2 re, im; };
-__device__ __forceinline__ c2 operator+(c2 a, c2 b) { return c2{ a.re + b.re, a.im + b.im }; }
-__device__ __forceinline__ c2 operator-(c2 a, c2 b) { return c2{ a.re - b.re, a.im - b.im }; }
-__device__ __forceinline__ c2 add_mi(c2 a, c2 b) { return c2{ a.re + b.im, a.im - b.re }; }       // a + (-i) b
-__device__ __forceinline__ c2 add_pi(c2 a, c2 b) { return c2{ a.re - b.im, a.im + b.re }; }       // a + i b
-__device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f2 splat(float v) { return f2{ v, v }; }
-// both channels' values times one complex factor
-__device__ __forceinline__ c2 cmulw(c2 a, f2 w)
-{
-    const f2 wr = w.xx, wi = w.yy;
-    return c2{ fma2(-a.im, wi, a.re * wr), fma2(a.im, wr, a.re * wi) };
-}
-
-__device__ __forceinline__ void dft4(c2 &a0, c2 &a1, c2 &a2, c2 &a3)
-{
-    const c2 s02 = a0 + a2, d02 = a0 - a2, s13 = a1 + a3, d13 = a1 - a3;
-    a0 = s02 + s13;
-    a2 = s02 - s13;
-    a1 = add_mi(d02, d13);
-    a3 = add_pi(d02, d13);
-}
-
-__device__ __forceinline__ void dft8(c2 (&a)[8])
-{
-    const f2 S = splat(0.70710678118654752440f);
-    const c2 b0 = a[0] + a[4], b4 = a[0] - a[4], b1 = a[1] + a[5], b5 = a[1] - a[5];
-    const c2 b2 = a[2] + a[6], b6 = a[2] - a[6], b3 = a[3] + a[7], b7 = a[3] - a[7];
-    const c2 c0 = b0 + b2, c2_ = b0 - b2, c1 = b1 + b3, c3 = b1 - b3;
-    a[0] = c0 + c1;
-    a[4] = c0 - c1;
-    a[2] = add_mi(c2_, c3);
-    a[6] = add_pi(c2_, c3);
-    const c2 d0 = add_mi(b4, b6), d2 = add_pi(b4, b6);
-    // p5 = b5 (1 - i), p7 = -b7 (1 + i) (both without their factor 1/sqrt 2): p5 = (b5.re + b5.im, b5.im - b5.re),
-    // p7 = (b7.im - b7.re, -(b7.re + b7.im)); q7 holds p7 with the sign of its imaginary part flipped
-    const c2 p5 = c2{ b5.re + b5.im, b5.im - b5.re }, q7 = c2{ b7.im - b7.re, b7.re + b7.im };
-    const c2 D1 = c2{ p5.re + q7.re, p5.im - q7.im }, D3 = c2{ p5.re - q7.re, p5.im + q7.im };
-    a[1] = c2{ fma2(D1.re, S, d0.re), fma2(D1.im, S, d0.im) };
-    a[5] = c2{ fma2(-D1.re, S, d0.re), fma2(-D1.im, S, d0.im) };
-    a[3] = c2{ fma2(D3.im, S, d2.re), fma2(-D3.re, S, d2.im) };
-    a[7] = c2{ fma2(-D3.im, S, d2.re), fma2(D3.re, S, d2.im) };
-}
-
-template <int M>
-__device__ __forceinline__ c2 mul_w16(c2 a)
-{
-    const f2 c1 = splat(0.92387953251128675613f), s1 = splat(0.38268343236508977173f), h = splat(0.70710678118654752440f);
-    if constexpr (M == 0) return a;
-    else if constexpr (M == 1) return c2{ fma2(a.im, s1, a.re * c1), fma2(-a.re, s1, a.im * c1) };
-    else if constexpr (M == 2) return c2{ (a.re + a.im) * h, (a.im - a.re) * h };
-    else if constexpr (M == 3) return c2{ fma2(a.im, c1, a.re * s1), fma2(-a.re, c1, a.im * s1) };
-    else if constexpr (M == 4) return c2{ a.im, -a.re };
-    else if constexpr (M == 6) return c2{ (a.im - a.re) * h, -((a.re + a.im) * h) };
-    else {
-        static_assert(M == 9, "exponent");
-        return c2{ -fma2(a.im, s1, a.re * c1), fma2(a.re, s1, -(a.im * c1)) };
-    }
-}
-
-__device__ __forceinline__ void dft16(c2 (&a)[16])
-{
-#pragma unroll
-    for (int nl = 0; nl < 4; nl++) dft4(a[nl], a[nl + 4], a[nl + 8], a[nl + 12]);
-    a[5] = mul_w16<1>(a[5]);
-    a[9] = mul_w16<2>(a[9]);
-    a[13] = mul_w16<3>(a[13]);
-    a[6] = mul_w16<2>(a[6]);
-    a[10] = mul_w16<4>(a[10]);
-    a[14] = mul_w16<6>(a[14]);
-    a[7] = mul_w16<3>(a[7]);
-    a[11] = mul_w16<6>(a[11]);
-    a[15] = mul_w16<9>(a[15]);
-    c2 o[16];
-#pragma unroll
-    for (int ka = 0; ka < 4; ka++) {
-        c2 x0 = a[4 * ka], x1 = a[4 * ka + 1], x2 = a[4 * ka + 2], x3 = a[4 * ka + 3];
+        V x0 = a[4 * ka], x1 = a[4 * ka + 1], x2 = a[4 * ka + 2], x3 = a[4 * ka + 3];
         dft4(x0, x1, x2, x3);
         o[ka] = x0;
         o[ka + 4] = x1;
@@ -267,6 +276,20 @@ __device__ __forceinline__ void cross32(float &a, float &b)
     lane_swap32(a, b);
     lane_swap32(b, a);
 }
+// the same for every float of a value
+__device__ __forceinline__ void cross32(f2 &a, f2 &b)
+{
+    float ax = a.x, bx = b.x, ay = a.y, by = b.y;
+    cross32(ax, bx);
+    cross32(ay, by);
+    a = f2{ ax, ay };
+    b = f2{ bx, by };
+}
+__device__ __forceinline__ void cross32(c2 &a, c2 &b)
+{
+    cross32(a.re, b.re);
+    cross32(a.im, b.im);
+}
 
 template <int CH, int R>
 __device__ __forceinline__ void settle(f2 (&x)[CH][R])
@@ -296,169 +319,119 @@ __device__ __forceinline__ int group_of(int lane) { return lane < 32 ? lane : 95
 // 6.99 -> 6.91 ms on one box, the same bits).
 template <int R>
 struct LaneTw {
-    f2 w[R], w1[R - 1], w2[7];
+    f2 w[R], w1[R - 1];
 };
 template <int R>
 __device__ __forceinline__ void load_lane_tw(LaneTw<R> &tw, const f2 *T)
 {
     using G = Geo<R>;
-    const int lane = threadIdx.x & 63, j = group_of(lane);
+    const int j = group_of(threadIdx.x & 63);
 #pragma unroll
     for (int r = 0; r < R; r++) tw.w[r] = T[j + 64 * r];
 #pragma unroll
     for (int k = 1; k < R; k++) tw.w1[k - 1] = T[G::kTw1 + j + 64 * (k - 1)];
-    if constexpr (R == 8) {
-#pragma unroll
-        for (int k = 1; k < 8; k++) tw.w2[k - 1] = T[G::kTw2 + (lane >> 3) + 8 * (k - 1)];
-    }
 }
-// which of them: the pre- / post-twiddle w (R values), the pass-1 twiddles (R - 1), pass 2's (R = 8)
-#ifndef AFG_WALK_TW
-#define AFG_WALK_TW 3       // stereo 2048: which sets live in registers (bit 0: w, bit 1: pass 1's, bit 2: pass 2's)
-#endif
-template <int R, int CH> constexpr bool kTwRegs1 = R == 8 && CH == 2 && (AFG_WALK_TW & 2);
-template <int R, int CH> constexpr bool kTwRegs2 = R == 8 && CH == 2 && (AFG_WALK_TW & 4);
-template <int R, int CH> constexpr bool kTwRegsW = (R == 8 && CH == 2 && (AFG_WALK_TW & 1)) || (R == 16 && CH == 1);   // (mono 4096: 197 -> 245 registers, +0.6 %)
-template <int R, int CH> constexpr bool kTwAny = kTwRegsW<R, CH> || kTwRegs1<R, CH> || kTwRegs2<R, CH>;
+// which of them: the pre- / post-twiddle w (R values) and the pass-1 twiddles (R - 1) of the stereo 2048 kernel (pass 2's
+// seven stay in LDS), w of the mono 4096 kernel (197 -> 245 registers, +0.6 %)
+template <int R, int CH> constexpr bool kTwRegs1 = R == 8 && CH == 2;
+template <int R, int CH> constexpr bool kTwRegsW = (R == 8 && CH == 2) || (R == 16 && CH == 1);
+template <int R, int CH> constexpr bool kTwAny = kTwRegsW<R, CH> || kTwRegs1<R, CH>;
 
-// The passes between the pre- and the post-twiddle: e[c][r] = point j + 64 r in, e[c][s] = bin j + 64 s out (not yet
-// multiplied by w).  U: the wavefront's transform area (channel c at U + c kChanF2); T: the table block.
-template <int R, int CH>
-__device__ __forceinline__ void fft_passes(f2 (&e)[CH][R], f2 *U, const f2 *T, const LaneTw<R> &tw)
+// The passes between the pre- and the post-twiddle: e[r] = point j + 64 r in, e[s] = bin j + 64 s out (not yet multiplied
+// by w), of one channel (V = f2) or of a channel-packed pair (V = c2).  U: the wavefront's transform area (put / get);
+// T: the table block.
+template <int R, typename V>
+__device__ __forceinline__ void fft_passes(V (&e)[R], f2 *U, const f2 *T, const LaneTw<R> &tw)
 {
     using G = Geo<R>;
-    constexpr int F = G::kChanF2;
+    constexpr int F = G::kChanF2, CH = kChannels<V>;
     int j = group_of(fresh_lane());
     if constexpr (R == 8) {
         // pass 1: over r = q >> 6 -> k0; twiddle W512^(j k0)
-#pragma unroll
-        for (int c = 0; c < CH; c++) dft8(e[c]);
+        dft8(e);
         {
             const f2 *W1 = T + G::kTw1 + j;
 #pragma unroll
-            for (int k = 1; k < 8; k++) {
-                const f2 w = kTwRegs1<R, CH> ? tw.w1[k - 1] : W1[64 * (k - 1)];
-#pragma unroll
-                for (int c = 0; c < CH; c++) e[c][k] = cmul(e[c][k], w);
-            }
+            for (int k = 1; k < 8; k++) e[k] = cmul(e[k], kTwRegs1<R, CH> ? tw.w1[k - 1] : W1[64 * (k - 1)]);
         }
 #pragma unroll
-        for (int c = 0; c < CH; c++)
-#pragma unroll
-            for (int k = 0; k < 8; k++) U[c * F + j + 68 * k] = e[c][k];
+        for (int k = 0; k < 8; k++) put<F>(U, j + 68 * k, e[k]);
         wave_lds_sync();
         // pass 2: lane (n0, k0) = (lane >> 3, lane & 7) over n1 -> k1; reads U[n0 + 8 n1 + 68 k0], twiddle W64^(n0 k1),
         // writes V[k0 + 8 k1 + 72 n0] (the same area: all reads are issued before the first write)
         const int l2 = fresh_lane();
         const int n0 = l2 >> 3, r2 = n0 + 68 * (l2 & 7), w2 = (l2 & 7) + 72 * n0;
 #pragma unroll
-        for (int c = 0; c < CH; c++)
-#pragma unroll
-            for (int k = 0; k < 8; k++) e[c][k] = U[c * F + r2 + 8 * k];
+        for (int k = 0; k < 8; k++) get<F>(U, r2 + 8 * k, e[k]);
         wave_lds_sync();
-#pragma unroll
-        for (int c = 0; c < CH; c++) dft8(e[c]);
+        dft8(e);
         {
             const f2 *W2 = T + G::kTw2 + n0;
 #pragma unroll
-            for (int k = 1; k < 8; k++) {
-                const f2 w = kTwRegs2<R, CH> ? tw.w2[k - 1] : W2[8 * (k - 1)];
-#pragma unroll
-                for (int c = 0; c < CH; c++) e[c][k] = cmul(e[c][k], w);
-            }
+            for (int k = 1; k < 8; k++) e[k] = cmul(e[k], W2[8 * (k - 1)]);
         }
 #pragma unroll
-        for (int c = 0; c < CH; c++)
-#pragma unroll
-            for (int k = 0; k < 8; k++) U[c * F + w2 + 8 * k] = e[c][k];
+        for (int k = 0; k < 8; k++) put<F>(U, w2 + 8 * k, e[k]);
         wave_lds_sync();
         // pass 3: lane (k0 + 8 k1 = j) over n0 -> k2
         j = group_of(fresh_lane());
 #pragma unroll
-        for (int c = 0; c < CH; c++)
-#pragma unroll
-            for (int k = 0; k < 8; k++) e[c][k] = U[c * F + j + 72 * k];
+        for (int k = 0; k < 8; k++) get<F>(U, j + 72 * k, e[k]);
         wave_lds_sync();
-#pragma unroll
-        for (int c = 0; c < CH; c++) dft8(e[c]);
+        dft8(e);
     } else if constexpr (R == 16) {
         // 16 x 4 x 16: q = n3 + 16 n2 + 64 n1 -> k = k1 + 16 k2 + 64 k3.  pass 1: over r = n1 -> k1; twiddle W1024^(j k1)
-#pragma unroll
-        for (int c = 0; c < CH; c++) dft16(e[c]);
+        dft16(e);
         {
             const f2 *W1 = T + G::kTw1 + j;
 #pragma unroll
-            for (int k = 1; k < 16; k++) {
-                const f2 w = W1[64 * (k - 1)];
-#pragma unroll
-                for (int c = 0; c < CH; c++) e[c][k] = cmul(e[c][k], w);
-            }
+            for (int k = 1; k < 16; k++) e[k] = cmul(e[k], W1[64 * (k - 1)]);
         }
 #pragma unroll
-        for (int c = 0; c < CH; c++)
-#pragma unroll
-            for (int k = 0; k < 16; k++) U[c * F + j + 72 * k] = e[c][k];
+        for (int k = 0; k < 16; k++) put<F>(U, j + 72 * k, e[k]);
         wave_lds_sync();
         // pass 2: lane (n3, g) = (lane >> 2, lane & 3) takes the items k1 = g + 4 i, each a 4-point DFT over n2 -> k2:
         // reads U[n3 + 16 n2 + 72 k1], twiddle W64^(n3 k2), writes V[k1 + 16 k2 + 68 n3]
         const int l2 = fresh_lane();
         const int n3 = l2 >> 2, r2 = n3 + 72 * (l2 & 3), w2 = (l2 & 3) + 68 * n3;
 #pragma unroll
-        for (int c = 0; c < CH; c++)
+        for (int i = 0; i < 4; i++)
 #pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int n2 = 0; n2 < 4; n2++) e[c][4 * i + n2] = U[c * F + r2 + 16 * n2 + 288 * i];
+            for (int n2 = 0; n2 < 4; n2++) get<F>(U, r2 + 16 * n2 + 288 * i, e[4 * i + n2]);
         wave_lds_sync();
 #pragma unroll
-        for (int c = 0; c < CH; c++)
-#pragma unroll
-            for (int i = 0; i < 4; i++) dft4(e[c][4 * i], e[c][4 * i + 1], e[c][4 * i + 2], e[c][4 * i + 3]);
+        for (int i = 0; i < 4; i++) dft4(e[4 * i], e[4 * i + 1], e[4 * i + 2], e[4 * i + 3]);
         {
             const f2 *W2 = T + G::kTw2 + n3;
 #pragma unroll
             for (int k = 1; k < 4; k++) {
                 const f2 w = W2[16 * (k - 1)];
 #pragma unroll
-                for (int c = 0; c < CH; c++)
-#pragma unroll
-                    for (int i = 0; i < 4; i++) e[c][4 * i + k] = cmul(e[c][4 * i + k], w);
+                for (int i = 0; i < 4; i++) e[4 * i + k] = cmul(e[4 * i + k], w);
             }
         }
 #pragma unroll
-        for (int c = 0; c < CH; c++)
+        for (int i = 0; i < 4; i++)
 #pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int k = 0; k < 4; k++) U[c * F + w2 + 4 * i + 16 * k] = e[c][4 * i + k];
+            for (int k = 0; k < 4; k++) put<F>(U, w2 + 4 * i + 16 * k, e[4 * i + k]);
         wave_lds_sync();
         // pass 3: lane j = k1 + 16 k2 over n3 -> k3
         j = group_of(fresh_lane());
 #pragma unroll
-        for (int c = 0; c < CH; c++)
-#pragma unroll
-            for (int k = 0; k < 16; k++) e[c][k] = U[c * F + j + 68 * k];
+        for (int k = 0; k < 16; k++) get<F>(U, j + 68 * k, e[k]);
         wave_lds_sync();
-#pragma unroll
-        for (int c = 0; c < CH; c++) dft16(e[c]);
+        dft16(e);
     } else {
         static_assert(R == 4, "points per lane");
         // 4 x 4 x 4 x 4: q = n4 + 4 n3 + 16 n2 + 64 n1 -> k = k1 + 4 k2 + 16 k3 + 64 k4.  pass 1: over r = n1 -> k1
-#pragma unroll
-        for (int c = 0; c < CH; c++) dft4(e[c][0], e[c][1], e[c][2], e[c][3]);
+        dft4(e[0], e[1], e[2], e[3]);
         {
             const f2 *W1 = T + G::kTw1 + j;
 #pragma unroll
-            for (int k = 1; k < 4; k++) {
-                const f2 w = W1[64 * (k - 1)];
-#pragma unroll
-                for (int c = 0; c < CH; c++) e[c][k] = cmul(e[c][k], w);
-            }
+            for (int k = 1; k < 4; k++) e[k] = cmul(e[k], W1[64 * (k - 1)]);
         }
 #pragma unroll
-        for (int c = 0; c < CH; c++)
-#pragma unroll
-            for (int k = 0; k < 4; k++) U[c * F + j + 80 * k] = e[c][k];
+        for (int k = 0; k < 4; k++) put<F>(U, j + 80 * k, e[k]);
         wave_lds_sync();
         // pass 2: lane (m, k1) = (lane & 15, lane >> 4), m = n4 + 4 n3, over n2 -> k2: reads U[m + 16 n2 + 80 k1], twiddle
         // W64^(m k2), writes slot m + 16 kk + 4 (kk >> 1) of kk = k1 + 4 k2
@@ -466,23 +439,14 @@ __device__ __forceinline__ void fft_passes(f2 (&e)[CH][R], f2 *U, const f2 *T, c
             const int l2 = fresh_lane();
             const int m = l2 & 15, k1 = l2 >> 4, r2 = m + 80 * k1, w2 = m + 16 * k1 + 4 * (k1 >> 1);
 #pragma unroll
-            for (int c = 0; c < CH; c++)
-#pragma unroll
-                for (int k = 0; k < 4; k++) e[c][k] = U[c * F + r2 + 16 * k];
+            for (int k = 0; k < 4; k++) get<F>(U, r2 + 16 * k, e[k]);
             wave_lds_sync();
-#pragma unroll
-            for (int c = 0; c < CH; c++) dft4(e[c][0], e[c][1], e[c][2], e[c][3]);
+            dft4(e[0], e[1], e[2], e[3]);
             const f2 *W2 = T + G::kTw2 + m;
 #pragma unroll
-            for (int k = 1; k < 4; k++) {
-                const f2 w = W2[16 * (k - 1)];
+            for (int k = 1; k < 4; k++) e[k] = cmul(e[k], W2[16 * (k - 1)]);
 #pragma unroll
-                for (int c = 0; c < CH; c++) e[c][k] = cmul(e[c][k], w);
-            }
-#pragma unroll
-            for (int c = 0; c < CH; c++)
-#pragma unroll
-                for (int k = 0; k < 4; k++) U[c * F + w2 + 72 * k] = e[c][k];
+            for (int k = 0; k < 4; k++) put<F>(U, w2 + 72 * k, e[k]);
             wave_lds_sync();
         }
         // pass 3: lane (n4, kk) = (lane & 3, lane >> 2) over n3 -> k3: twiddle W16^(n4 k3), writes V[kk + 16 k3 + 72 n4]
@@ -490,41 +454,29 @@ __device__ __forceinline__ void fft_passes(f2 (&e)[CH][R], f2 *U, const f2 *T, c
             const int l3 = fresh_lane();
             const int n4 = l3 & 3, kk = l3 >> 2, r3 = n4 + 16 * kk + 4 * (kk >> 1), w3 = kk + 72 * n4;
 #pragma unroll
-            for (int c = 0; c < CH; c++)
-#pragma unroll
-                for (int k = 0; k < 4; k++) e[c][k] = U[c * F + r3 + 4 * k];
+            for (int k = 0; k < 4; k++) get<F>(U, r3 + 4 * k, e[k]);
             wave_lds_sync();
-#pragma unroll
-            for (int c = 0; c < CH; c++) dft4(e[c][0], e[c][1], e[c][2], e[c][3]);
+            dft4(e[0], e[1], e[2], e[3]);
             const f2 *W3 = T + G::kTw3 + n4;
 #pragma unroll
-            for (int k = 1; k < 4; k++) {
-                const f2 w = W3[4 * (k - 1)];
+            for (int k = 1; k < 4; k++) e[k] = cmul(e[k], W3[4 * (k - 1)]);
 #pragma unroll
-                for (int c = 0; c < CH; c++) e[c][k] = cmul(e[c][k], w);
-            }
-#pragma unroll
-            for (int c = 0; c < CH; c++)
-#pragma unroll
-                for (int k = 0; k < 4; k++) U[c * F + w3 + 16 * k] = e[c][k];
+            for (int k = 0; k < 4; k++) put<F>(U, w3 + 16 * k, e[k]);
             wave_lds_sync();
         }
         // pass 4: lane j = kk + 16 k3 over n4 -> k4
         j = group_of(fresh_lane());
 #pragma unroll
-        for (int c = 0; c < CH; c++)
-#pragma unroll
-            for (int k = 0; k < 4; k++) e[c][k] = U[c * F + j + 72 * k];
+        for (int k = 0; k < 4; k++) get<F>(U, j + 72 * k, e[k]);
         wave_lds_sync();
-#pragma unroll
-        for (int c = 0; c < CH; c++) dft4(e[c][0], e[c][1], e[c][2], e[c][3]);
+        dft4(e[0], e[1], e[2], e[3]);
     }
 }
 
-// The N-point FFT of all channels with the pre- and post-twiddle: xin[c][r] = (X[2q], X[2q+1]) at q = j + 64 r in,
-// P[c][s] = c[j + 64 s] out.
+// The N-point FFT of all channels with the pre- and post-twiddle: xin[c][r] = (X[2q], X[2q+1]) at q = j + 64 r in, as loaded
+// (one register pair per channel and point); P[s] = c[j + 64 s] out, a stereo pair channel-packed.
 template <int R, int CH, typename Next>
-__device__ __forceinline__ void fft_lanes(f2 (&xin)[CH][R], f2 (&P)[CH][R], f2 *U, const f2 *T, const LaneTw<R> &tw, Next next)
+__device__ __forceinline__ void fft_lanes(f2 (&xin)[CH][R], Val<CH> (&P)[R], f2 *U, const f2 *T, const LaneTw<R> &tw, Next next)
 {
     int j = group_of(fresh_lane());      // points j + 64 r
     // X[2q+1] is the imaginary part of point N-1 - q = (63 - j) + 64 (R-1 - r): the other half-wave's slot R-1 - r
@@ -537,188 +489,26 @@ __device__ __forceinline__ void fft_lanes(f2 (&xin)[CH][R], f2 (&P)[CH][R], f2 *
             xin[c][r].y = a;
             xin[c][R - 1 - r].y = b;
         }
-    f2 e[CH][R];
+    Val<CH> e[R];
     {
         const f2 *W = T + j;
 #pragma unroll
         for (int r = 0; r < R; r++) {
             const f2 w = kTwRegsW<R, CH> ? tw.w[r] : W[64 * r];
-#pragma unroll
-            for (int c = 0; c < CH; c++) e[c][r] = cmul(xin[c][r], w);
+            if constexpr (CH == 2) e[r] = cmul(c2{ f2{ xin[0][r].x, xin[1][r].x }, f2{ xin[0][r].y, xin[1][r].y } }, w);
+            else e[r] = cmul(xin[0][r], w);
         }
     }
     next();                                          // the spectrum registers are free: fetch the next packet's
-    fft_passes<R, CH>(e, U, T, tw);
+    fft_passes<R>(e, U, T, tw);
     j = group_of(fresh_lane());
     {
         const f2 *W = T + j;
 #pragma unroll
-        for (int k = 0; k < R; k++) {
-            const f2 w = kTwRegsW<R, CH> ? tw.w[k] : W[64 * k];
-#pragma unroll
-            for (int c = 0; c < CH; c++) P[c][k] = cmul(e[c][k], w);
-        }
+        for (int k = 0; k < R; k++) P[k] = cmul(e[k], kTwRegsW<R, CH> ? tw.w[k] : W[64 * k]);
     }
 }
 
-// The same passes for a stereo pair held channel-packed (c2): the transform area holds a plane of real parts and a plane of
-// imaginary parts, each slot the two channels' values (8 bytes: the slot indices, and so the bank behaviour, are those of
-// fft_passes, tests/vorbis_walk_model.py).
-template <int R>
-__device__ __forceinline__ void fft_passes2(c2 (&e)[R], f2 *U, const f2 *T, const LaneTw<R> &tw)
-{
-    using G = Geo<R>;
-    constexpr int F = G::kChanF2;
-    f2 *const Ur = U, *const Ui = U + F;
-    int j = group_of(fresh_lane());
-    if constexpr (R == 8) {
-        dft8(e);
-        {
-            const f2 *W1 = T + G::kTw1 + j;
-#pragma unroll
-            for (int k = 1; k < 8; k++) e[k] = cmulw(e[k], kTwRegs1<R, 2> ? tw.w1[k - 1] : W1[64 * (k - 1)]);
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) { Ur[j + 68 * k] = e[k].re; Ui[j + 68 * k] = e[k].im; }
-        wave_lds_sync();
-        const int l2 = fresh_lane();
-        const int n0 = l2 >> 3, r2 = n0 + 68 * (l2 & 7), w2 = (l2 & 7) + 72 * n0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) e[k] = c2{ Ur[r2 + 8 * k], Ui[r2 + 8 * k] };
-        wave_lds_sync();
-        dft8(e);
-        {
-            const f2 *W2 = T + G::kTw2 + n0;
-#pragma unroll
-            for (int k = 1; k < 8; k++) e[k] = cmulw(e[k], kTwRegs2<R, 2> ? tw.w2[k - 1] : W2[8 * (k - 1)]);
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) { Ur[w2 + 8 * k] = e[k].re; Ui[w2 + 8 * k] = e[k].im; }
-        wave_lds_sync();
-        j = group_of(fresh_lane());
-#pragma unroll
-        for (int k = 0; k < 8; k++) e[k] = c2{ Ur[j + 72 * k], Ui[j + 72 * k] };
-        wave_lds_sync();
-        dft8(e);
-    } else if constexpr (R == 16) {
-        dft16(e);
-        {
-            const f2 *W1 = T + G::kTw1 + j;
-#pragma unroll
-            for (int k = 1; k < 16; k++) e[k] = cmulw(e[k], W1[64 * (k - 1)]);
-        }
-#pragma unroll
-        for (int k = 0; k < 16; k++) { Ur[j + 72 * k] = e[k].re; Ui[j + 72 * k] = e[k].im; }
-        wave_lds_sync();
-        const int l2 = fresh_lane();
-        const int n3 = l2 >> 2, r2 = n3 + 72 * (l2 & 3), w2 = (l2 & 3) + 68 * n3;
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int n2 = 0; n2 < 4; n2++) e[4 * i + n2] = c2{ Ur[r2 + 16 * n2 + 288 * i], Ui[r2 + 16 * n2 + 288 * i] };
-        wave_lds_sync();
-#pragma unroll
-        for (int i = 0; i < 4; i++) dft4(e[4 * i], e[4 * i + 1], e[4 * i + 2], e[4 * i + 3]);
-        {
-            const f2 *W2 = T + G::kTw2 + n3;
-#pragma unroll
-            for (int k = 1; k < 4; k++) {
-                const f2 w = W2[16 * (k - 1)];
-#pragma unroll
-                for (int i = 0; i < 4; i++) e[4 * i + k] = cmulw(e[4 * i + k], w);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int k = 0; k < 4; k++) { Ur[w2 + 4 * i + 16 * k] = e[4 * i + k].re; Ui[w2 + 4 * i + 16 * k] = e[4 * i + k].im; }
-        wave_lds_sync();
-        j = group_of(fresh_lane());
-#pragma unroll
-        for (int k = 0; k < 16; k++) e[k] = c2{ Ur[j + 68 * k], Ui[j + 68 * k] };
-        wave_lds_sync();
-        dft16(e);
-    } else {
-        static_assert(R == 4, "points per lane");
-        dft4(e[0], e[1], e[2], e[3]);
-        {
-            const f2 *W1 = T + G::kTw1 + j;
-#pragma unroll
-            for (int k = 1; k < 4; k++) e[k] = cmulw(e[k], W1[64 * (k - 1)]);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) { Ur[j + 80 * k] = e[k].re; Ui[j + 80 * k] = e[k].im; }
-        wave_lds_sync();
-        {
-            const int l2 = fresh_lane();
-            const int m = l2 & 15, k1 = l2 >> 4, r2 = m + 80 * k1, w2 = m + 16 * k1 + 4 * (k1 >> 1);
-#pragma unroll
-            for (int k = 0; k < 4; k++) e[k] = c2{ Ur[r2 + 16 * k], Ui[r2 + 16 * k] };
-            wave_lds_sync();
-            dft4(e[0], e[1], e[2], e[3]);
-            const f2 *W2 = T + G::kTw2 + m;
-#pragma unroll
-            for (int k = 1; k < 4; k++) e[k] = cmulw(e[k], W2[16 * (k - 1)]);
-#pragma unroll
-            for (int k = 0; k < 4; k++) { Ur[w2 + 72 * k] = e[k].re; Ui[w2 + 72 * k] = e[k].im; }
-            wave_lds_sync();
-        }
-        {
-            const int l3 = fresh_lane();
-            const int n4 = l3 & 3, kk = l3 >> 2, r3 = n4 + 16 * kk + 4 * (kk >> 1), w3 = kk + 72 * n4;
-#pragma unroll
-            for (int k = 0; k < 4; k++) e[k] = c2{ Ur[r3 + 4 * k], Ui[r3 + 4 * k] };
-            wave_lds_sync();
-            dft4(e[0], e[1], e[2], e[3]);
-            const f2 *W3 = T + G::kTw3 + n4;
-#pragma unroll
-            for (int k = 1; k < 4; k++) e[k] = cmulw(e[k], W3[4 * (k - 1)]);
-#pragma unroll
-            for (int k = 0; k < 4; k++) { Ur[w3 + 16 * k] = e[k].re; Ui[w3 + 16 * k] = e[k].im; }
-            wave_lds_sync();
-        }
-        j = group_of(fresh_lane());
-#pragma unroll
-        for (int k = 0; k < 4; k++) e[k] = c2{ Ur[j + 72 * k], Ui[j + 72 * k] };
-        wave_lds_sync();
-        dft4(e[0], e[1], e[2], e[3]);
-    }
-}
-
-// fft_lanes for a stereo pair: xin as loaded (one register pair per channel and point), P channel-packed
-template <int R, typename Next>
-__device__ __forceinline__ void fft_lanes2(f2 (&xin)[2][R], c2 (&P)[R], f2 *U, const f2 *T, const LaneTw<R> &tw, Next next)
-{
-    int j = group_of(fresh_lane());
-#pragma unroll
-    for (int c = 0; c < 2; c++)
-#pragma unroll
-        for (int r = 0; r < R / 2; r++) {
-            float a = xin[c][r].y, b = xin[c][R - 1 - r].y;
-            cross32(a, b);
-            xin[c][r].y = a;
-            xin[c][R - 1 - r].y = b;
-        }
-    c2 e[R];
-    {
-        const f2 *W = T + j;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const f2 w = kTwRegsW<R, 2> ? tw.w[r] : W[64 * r];
-            e[r] = cmulw(c2{ f2{ xin[0][r].x, xin[1][r].x }, f2{ xin[0][r].y, xin[1][r].y } }, w);
-        }
-    }
-    next();                                          // the spectrum registers are free: fetch the next packet's
-#ifndef AFG_WALK_EXP_NOFFT                                // (experiment: the memory floor of the walk -- loads, window, stores, no passes)
-    fft_passes2<R>(e, U, T, tw);
-#endif
-    j = group_of(fresh_lane());
-    {
-        const f2 *W = T + j;
-#pragma unroll
-        for (int k = 0; k < R; k++) P[k] = cmulw(e[k], kTwRegsW<R, 2> ? tw.w[k] : W[64 * k]);
-    }
-}
 
 // y[m] of a long block of n samples from its u (floats at uf[0..n/2)): the odd / even extension of the DCT-IV
 template <int N>
@@ -729,29 +519,12 @@ __device__ __forceinline__ float y_of_u(const float *uf, int m)
     return -uf[m - 3 * N / 4];
 }
 
-// two frames of all channels: 16 bytes of a stereo stream, 8 of a mono one; ST (CH channels of a stream with more than
-// two): these channels' 4- or 8-byte column of the interleaved frames, `stride` floats apart, cached -- the other columns'
-// wavefronts fill the lines in L2
-template <int CH, bool ST>
-__device__ __forceinline__ void store_pair(float *o, int pair, const float (&f0)[CH], const float (&f1)[CH], int stride)
+// two frames of all channels of a mono or stereo stream, f0 and f1 a float or (ch0, ch1) each: 8 or 16 bytes
+template <typename F>
+__device__ __forceinline__ void store_pair(float *o, int pair, F f0, F f1)
 {
-    if constexpr (ST && CH == 2) {
-        *(f2 *)(o + (2 * pair) * stride) = f2{ f0[0], f0[1] };
-        *(f2 *)(o + (2 * pair + 1) * stride) = f2{ f1[0], f1[1] };
-    } else if constexpr (ST) {
-        o[(2 * pair) * stride] = f0[0];
-        o[(2 * pair + 1) * stride] = f1[0];
-    } else if constexpr (CH == 2) __builtin_nontemporal_store((f4{ f0[0], f0[1], f1[0], f1[1] }), (f4 *)o + pair);
-    else __builtin_nontemporal_store((f2{ f0[0], f1[0] }), (f2 *)o + pair);
-}
-// the same from channel-packed values: f0, f1 = (ch0, ch1) of two consecutive frames
-template <bool ST>
-__device__ __forceinline__ void store_pair2(float *o, int pair, f2 f0, f2 f1, int stride)
-{
-    if constexpr (ST) {
-        *(f2 *)(o + (2 * pair) * stride) = f0;
-        *(f2 *)(o + (2 * pair + 1) * stride) = f1;
-    } else __builtin_nontemporal_store((f4{ f0.x, f0.y, f1.x, f1.y }), (f4 *)o + pair);
+    if constexpr (std::is_same_v<F, f2>) __builtin_nontemporal_store((f4{ f0.x, f0.y, f1.x, f1.y }), (f4 *)o + pair);
+    else __builtin_nontemporal_store((f2{ f0, f1 }), (f2 *)o + pair);
 }
 // Streams with more than two channels (round 6): the wavefronts of a workgroup are the channels (or channel pairs) of ONE
 // segment and walk it in step.  A chunk -- 128 consecutive frames and the 128 mirrored ones of a long block, all channels --
@@ -801,21 +574,14 @@ __device__ __forceinline__ void walk_body(
     // Carried state, per channel.  After a long block whose right window is long: cb[c][2 i], cb[c][2 i + 1] =
     // u[n/2-1 - 2k], u[n/2-2 - 2k] for k = j + 64 (R/2 + i) -- the b of frames 2k - n/4 and 2k - n/4 + 1 of the next block.
     // Otherwise previous_window itself (:2641-2643): sample lane + 64 i in cb[c][i] (64 .. 256 samples).
-    // (a stereo pair: channel-packed, cbs[i] = (ch0, ch1))
-    using CB = std::conditional_t<CH == 2, f2, float>;
-    CB cbs[R];
+    // (a stereo pair: channel-packed, cbs[i] = (ch0, ch1); chan_of / set_chan reach one channel's -- through two lambdas, not
+    // called in place: inlined early the stereo 1024 kernel spills six registers instead of two and the stereo 2048 kernel
+    // takes 246 instead of 234)
+    Real<CH> cbs[R];
 #pragma unroll
-    for (int i = 0; i < R; i++) cbs[i] = CB(0.0f);
-    auto cbget = [&](int c, int i) -> float {
-        if constexpr (CH == 2) return c ? cbs[i].y : cbs[i].x;
-        else return cbs[i];
-    };
-    auto cbset = [&](int c, int i, float v) {
-        if constexpr (CH == 2) {
-            if (c) cbs[i].y = v;
-            else cbs[i].x = v;
-        } else cbs[i] = v;
-    };
+    for (int i = 0; i < R; i++) cbs[i] = Real<CH>(0.0f);
+    auto cbget = [&](int c, int i) -> float { return chan_of(cbs[i], c); };
+    auto cbset = [&](int c, int i, float v) { set_chan(cbs[i], c, v); };
 
     int fbase = 0;
     unsigned fl_reg = 0;
@@ -851,21 +617,6 @@ __device__ __forceinline__ void walk_body(
             // AFG_VORBIS_NZ_EIGHTHS: load r of a channel covers bins 128 r .. 128 r + 127 of n/2 = 128 R, so a load whose
             // bins all lie in the declared-empty eighths is a whole instruction that is not issued (a scalar test)
             const int nz = (int)(flp >> 4) ? (int)(flp >> 4) - 1 : 8;
-#if defined(AFG_WALK_EXP_NOFFT) && AFG_WALK_EXP_NOFFT == 2
-            // (experiment, with the passes compiled out: the same bytes fetched 16 per lane -- is the 8-byte load what sets the floor?)
-            {
-                const f4 *src4 = (const f4 *)((const f2 *)(spec + lane64(so_reg, p)) + chan * kPts) + fresh_lane();
-#pragma unroll
-                for (int c = 0; c < CH; c++)
-#pragma unroll
-                    for (int r = 0; r < R; r += 2) {
-                        f4 v = f4{ 0.0f, 0.0f, 0.0f, 0.0f };
-                        if (8 * r < nz * R) v = __builtin_nontemporal_load(src4 + c * (kPts / 2) + 64 * (r / 2));
-                        xin[c][r] = f2{ v.x, v.y };
-                        xin[c][r + 1] = f2{ v.z, v.w };
-                    }
-            }
-#else
 #pragma unroll
             for (int c = 0; c < CH; c++)
 #pragma unroll
@@ -873,7 +624,6 @@ __device__ __forceinline__ void walk_body(
                     xin[c][r] = f2{ 0.0f, 0.0f };
                     if (8 * r < nz * R) xin[c][r] = __builtin_nontemporal_load(src + c * kPts + 64 * r);
                 }
-#endif
         } else {
             // nothing reads xin before the next issue(): say so, or the old values are copied around to survive the branch
 #pragma unroll
@@ -912,24 +662,9 @@ __device__ __forceinline__ void walk_body(
                             if (r == (nz >> 1)) xin[c][r] = low ? xin[c][r] : f2{ 0.0f, 0.0f };
                 }
             }
-            // P: c[j + 64 s] of every channel (a stereo pair: channel-packed); px / py read one channel's parts
-            using PT = std::conditional_t<CH == 2, c2, f2>;
-            PT P[R];
-            auto px = [&](int c, int k) -> float {
-                if constexpr (CH == 2) return c ? P[k].re.y : P[k].re.x;
-                else return P[k].x;
-            };
-            auto py = [&](int c, int k) -> float {
-                if constexpr (CH == 2) return c ? P[k].im.y : P[k].im.x;
-                else return P[k].y;
-            };
-            if constexpr (CH == 2) fft_lanes2<R>(xin, P, U, T, tw, next);
-            else {
-                f2 P1[1][R];
-                fft_lanes<R, 1>(xin, P1, U, T, tw, next);
-#pragma unroll
-                for (int k = 0; k < R; k++) P[k] = P1[0][k];
-            }
+            // P: c[j + 64 s] of every channel (a stereo pair: channel-packed)
+            Val<CH> P[R];
+            fft_lanes<R, CH>(xin, P, U, T, tw, next);
             if (!(wprev && wnext)) {
                 // a short neighbour: u of every channel to LDS in natural order for the y(m) accessor below
                 float *const uf = (float *)U;
@@ -938,31 +673,14 @@ __device__ __forceinline__ void walk_body(
 #pragma unroll
                     for (int k = 0; k < R; k++) {
                         const int kk = group_of(lane) + 64 * k;
-                        uf[c * (2 * kChanF2) + 2 * kk] = px(c, k);
-                        uf[c * (2 * kChanF2) + kN / 2 - 1 - 2 * kk] = -py(c, k);
+                        uf[c * (2 * kChanF2) + 2 * kk] = chan_of(re(P[k]), c);
+                        uf[c * (2 * kChanF2) + kN / 2 - 1 - 2 * kk] = -chan_of(im(P[k]), c);
                     }
                 wave_lds_sync();
             }
             // c[N-1 - k] for k = j + 64 s, s = R/2 .. R-1: slot R-1 - s of lane ^ 32
 #pragma unroll
-            for (int k = 0; k < H; k += 2) {
-                if constexpr (CH == 2) {
-                    float ax0 = P[k].re.x, bx0 = P[k + 1].re.x, ax1 = P[k].re.y, bx1 = P[k + 1].re.y;
-                    float ay0 = P[k].im.x, by0 = P[k + 1].im.x, ay1 = P[k].im.y, by1 = P[k + 1].im.y;
-                    cross32(ax0, bx0);
-                    cross32(ax1, bx1);
-                    cross32(ay0, by0);
-                    cross32(ay1, by1);
-                    P[k] = c2{ f2{ ax0, ax1 }, f2{ ay0, ay1 } };
-                    P[k + 1] = c2{ f2{ bx0, bx1 }, f2{ by0, by1 } };
-                } else {
-                    float ax = P[k].x, bx = P[k + 1].x, ay = P[k].y, by = P[k + 1].y;
-                    cross32(ax, bx);
-                    cross32(ay, by);
-                    P[k] = f2{ ax, ay };
-                    P[k + 1] = f2{ bx, by };
-                }
-            }
+            for (int k = 0; k < H; k += 2) cross32(P[k], P[k + 1]);
             // after the crossing slot k holds lane ^ 32's slot k ^ 1: the mirror of s = R/2 + i, slot R/2-1 - i, is slot mir(i)
             auto mir = [](int i) constexpr { return (H - 1 - i) ^ 1; };
             settle(xin);
@@ -975,44 +693,22 @@ __device__ __forceinline__ void walk_body(
                 for (int i = 0; i < H; i++) {
                     const f2 w0 = wlo[64 * i];                     // w[j0], w[j0+1]
                     const f2 w1 = whi[-64 * i];                    // w[n/2-2-j0], w[n/2-1-j0]
-                    if constexpr (CH == 2) {
-                        // both channels at once: a0 = P.re, a1 = -P.im of the mirror slot, b the carried pair
-                        const f2 a0 = P[H + i].re, a1n = P[mir(i)].im, b0 = cbs[2 * i], b1 = cbs[2 * i + 1];
-                        const f2 lo0 = fma2(-b0, w1.yy, a0 * w0.xx);
-                        const f2 lo1 = fma2(-b1, w1.xx, -(a1n * w0.yy));
-                        const f2 hi1 = fma2(-b0, w0.xx, -(a0 * w1.yy));
-                        const f2 hi0 = fma2(-b1, w0.yy, a1n * w1.xx);
-                        if constexpr (ST) {
-                            // the workgroup's wavefronts -- the channel pairs of this segment -- meet in the staging area:
-                            // frames [128 i, 128 i + 128) and their mirror, whole, then stored 16 bytes per lane
-                            float *const S = stage + (i & 1) * (256 * stride) + chan;
-                            *(f2 *)(S + (2 * j) * stride) = lo0;
-                            *(f2 *)(S + (2 * j + 1) * stride) = lo1;
-                            *(f2 *)(S + (128 + 126 - 2 * j) * stride) = hi0;
-                            *(f2 *)(S + (128 + 127 - 2 * j) * stride) = hi1;
-                            staged_store<kN>(stage + (i & 1) * (256 * stride), o - chan, i, stride);
-                        } else {
-                            store_pair2<ST>(o, j + 64 * i, lo0, lo1, stride);
-                            store_pair2<ST>(o, (kPts - 1) - j - 64 * i, hi0, hi1, stride);
-                        }
+                    // all channels at once: a0 = re P, a1 = -im P of the mirror slot, b the carried values
+                    using F = Real<CH>;
+                    F lo0, lo1, hi0, hi1;
+                    window_ola(re(P[H + i]), im(P[mir(i)]), cbs[2 * i], cbs[2 * i + 1], w0, w1, lo0, lo1, hi0, hi1);
+                    if constexpr (ST) {
+                        // the workgroup's wavefronts -- the channels or channel pairs of this segment -- meet in the staging
+                        // area: frames [128 i, 128 i + 128) and their mirror, whole, then stored 16 bytes per lane
+                        float *const S = stage + (i & 1) * (256 * stride) + chan;
+                        *(F *)(S + (2 * j) * stride) = lo0;
+                        *(F *)(S + (2 * j + 1) * stride) = lo1;
+                        *(F *)(S + (128 + 126 - 2 * j) * stride) = hi0;
+                        *(F *)(S + (128 + 127 - 2 * j) * stride) = hi1;
+                        staged_store<kN>(stage + (i & 1) * (256 * stride), o - chan, i, stride);
                     } else {
-                        float lo0[1], lo1[1], hi0[1], hi1[1];
-                        const float a0 = P[H + i].x, a1 = -P[mir(i)].y, b0 = cbs[2 * i], b1 = cbs[2 * i + 1];
-                        lo0[0] = a0 * w0.x - b0 * w1.y;
-                        lo1[0] = a1 * w0.y - b1 * w1.x;
-                        hi1[0] = -a0 * w1.y - b0 * w0.x;
-                        hi0[0] = -a1 * w1.x - b1 * w0.y;
-                        if constexpr (ST) {
-                            float *const S = stage + (i & 1) * (256 * stride) + chan;
-                            S[(2 * j) * stride] = lo0[0];
-                            S[(2 * j + 1) * stride] = lo1[0];
-                            S[(128 + 126 - 2 * j) * stride] = hi0[0];
-                            S[(128 + 127 - 2 * j) * stride] = hi1[0];
-                            staged_store<kN>(stage + (i & 1) * (256 * stride), o - chan, i, stride);
-                        } else {
-                            store_pair<1, ST>(o, j + 64 * i, lo0, lo1, stride);
-                            store_pair<1, ST>(o, (kPts - 1) - j - 64 * i, hi0, hi1, stride);
-                        }
+                        store_pair(o, j + 64 * i, lo0, lo1);
+                        store_pair(o, (kPts - 1) - j - 64 * i, hi0, hi1);
                     }
                 }
             }
@@ -1062,13 +758,8 @@ __device__ __forceinline__ void walk_body(
             if (wnext) {
 #pragma unroll
                 for (int i = 0; i < H; i++) {
-                    if constexpr (CH == 2) {
-                        cbs[2 * i] = -P[H + i].im;                   // u[n/2-1 - 2k], both channels
-                        cbs[2 * i + 1] = P[mir(i)].re;               // u[2 (N-1 - k)] = u[n/2-2 - 2k]
-                    } else {
-                        cbs[2 * i] = -P[H + i].y;
-                        cbs[2 * i + 1] = P[mir(i)].x;
-                    }
+                    cbs[2 * i] = -im(P[H + i]);                      // u[n/2-1 - 2k], all channels
+                    cbs[2 * i + 1] = re(P[mir(i)]);                  // u[2 (N-1 - k)] = u[n/2-2 - 2k]
                 }
             }
         } else {
@@ -1126,11 +817,8 @@ __device__ __forceinline__ void walk_body(
 // (tables once per workgroup + one transform area per wavefront) at the register budget that pays.  The small shapes
 // have little work per packet beside the fixed cost of a packet (flags, bounds, three or four LDS round trips): four
 // wavefronts per SIMD hide it (mono 1024: 11.5 -> 8.4 ms per C3-sized batch; a handful of spilled registers).
-#ifndef AFG_WALK_W82
-#define AFG_WALK_W82 8      // stereo 2048: wavefronts per workgroup (8: two per SIMD; 12: three, at <= 168 registers)
-#endif
+// (stereo 2048 at 12 wavefronts, three per SIMD at <= 168 registers, lost to the default 8: DESIGN.md)
 template <int R, int CH> struct Shape { static constexpr int kWaves = 8, kPerSimd = 2; };
-template <> struct Shape<8, 2> { static constexpr int kWaves = AFG_WALK_W82, kPerSimd = AFG_WALK_W82 / 4; };
 template <> struct Shape<4, 1> { static constexpr int kWaves = 16, kPerSimd = 4; };
 template <> struct Shape<4, 2> { static constexpr int kWaves = 16, kPerSimd = 4; };
 template <> struct Shape<8, 1> { static constexpr int kWaves = 16, kPerSimd = 4; };
@@ -1176,18 +864,13 @@ __global__ __launch_bounds__(64 * WAVES, (Shape<R, CH>::kPerSimd)) void vorbis_w
     }
 }
 
-// wavefronts per SIMD the multi-channel kernels are compiled for (the register budget): as the mono / stereo kernel of the shape unless
-// overridden -- workgroups of 3-7 wavefronts pack a CU differently than the 16-wavefront groups of the small mono / stereo shapes
-#ifndef AFG_MC_PERSIMD_SMALL
-#define AFG_MC_PERSIMD_SMALL 4
-#endif
-template <int R, int CH> struct McPerSimd { static constexpr int k = Shape<R, CH>::kPerSimd == 4 ? AFG_MC_PERSIMD_SMALL : Shape<R, CH>::kPerSimd; };
-
 // Streams with more than two channels: a workgroup is the nch / CH wavefronts of ONE segment (wavefront w: channels w CH ..),
 // every stream of the launch has the same channel count.  LDS: tables | one transform area per wavefront | two staging chunks
-// of 256 frames (staged_store).  At most 8 wavefronts (512 threads): the register budget of the stereo kernels.
+// of 256 frames (staged_store).  At most 8 wavefronts (512 threads): the register budget of the stereo kernels.  Compiled
+// for the wavefronts per SIMD (the register budget) of the mono / stereo kernel of the shape, the small shapes too, though
+// their workgroups of 3-7 wavefronts pack a CU differently than 16-wavefront groups do.
 template <int R, int CH>
-__global__ __launch_bounds__(512, (McPerSimd<R, CH>::k)) void vorbis_walk_mc_kernel(
+__global__ __launch_bounds__(512, (Shape<R, CH>::kPerSimd)) void vorbis_walk_mc_kernel(
     const VorbisSeg *__restrict__ segs, uint32_t n_segs, const VorbisStream *__restrict__ streams,
     const uint8_t *__restrict__ pflags, const uint64_t *__restrict__ spec_off, const uint64_t *__restrict__ out_off,
     const float *tables, const float *__restrict__ walk_tables, const float *__restrict__ spec, float *__restrict__ out,
@@ -1230,6 +913,24 @@ struct DevShape {
     hipError_t rc = hipSuccess;
     int per_cu[17] = {}, cus = 256;
 };
+// the finding: the kernel's dynamic LDS limit, the CU count, and into per_cu[c], c = c0, c0 + step .. c1, the workgroups a CU
+// holds of the launch form form(c) = { threads, LDS bytes }
+template <typename Form>
+void find_room(DevShape &ds, const void *fn, size_t max_lds, int c0, int c1, int step, Form form)
+{
+    std::call_once(ds.once, [&] {
+        ds.rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds);
+        int n_cu = 256, cur = 0;
+        if (hipGetDevice(&cur) == hipSuccess) (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, cur);
+        ds.cus = n_cu;
+        for (int c = c0; ds.rc == hipSuccess && c <= c1; c += step) {
+            const std::pair<int, size_t> f = form(c);
+            int nb = 1;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, f.first, f.second) != hipSuccess) nb = 1;
+            ds.per_cu[c] = nb < 1 ? 1 : nb;
+        }
+    });
+}
 
 template <int R, int CH, bool ST>
 int launch_shape(const VorbisSeg *segs, uint32_t n_segs, int nch, const VorbisStream *streams, const uint8_t *pflags,
@@ -1248,18 +949,8 @@ int launch_shape(const VorbisSeg *segs, uint32_t n_segs, int nch, const VorbisSt
             afg::set_error("afg_vorbis_transform_hip: %d channels on the %d-channel walk", nch, CH);
             return AFG_ERR_INVALID;
         }
-        const void *fn = (const void *)vorbis_walk_mc_kernel<R, CH>;
-        std::call_once(ds.once, [&] {
-            ds.rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mc_lds<R, CH>(kMcMax));
-            int n_cu = 256, cur = 0;
-            if (hipGetDevice(&cur) == hipSuccess) (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, cur);
-            ds.cus = n_cu;
-            for (int c = CH == 2 ? 4 : 3; ds.rc == hipSuccess && c <= kMcMax; c += CH) {
-                int nb = 1;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * (c / CH), mc_lds<R, CH>(c)) != hipSuccess) nb = 1;
-                ds.per_cu[c] = nb < 1 ? 1 : nb;
-            }
-        });
+        find_room(ds, (const void *)vorbis_walk_mc_kernel<R, CH>, mc_lds<R, CH>(kMcMax), CH == 2 ? 4 : 3, kMcMax, CH,
+                  [](int c) { return std::pair<int, size_t>(64 * (c / CH), mc_lds<R, CH>(c)); });
         AFG_HIP_CHECK(ds.rc);
         const uint32_t room = (uint32_t)(ds.per_cu[nch] * ds.cus);
         const size_t lds_bytes = mc_lds<R, CH>(nch);
@@ -1268,15 +959,8 @@ int launch_shape(const VorbisSeg *segs, uint32_t n_segs, int nch, const VorbisSt
     } else {
         constexpr int kWaves = Shape<R, CH>::kWaves;
         constexpr size_t kLds = shape_lds<R, CH>();
-        const void *fn = (const void *)vorbis_walk_kernel<R, CH, kWaves>;
-        std::call_once(ds.once, [&] {
-            ds.rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds);
-            int nb = 1, n_cu = 256, cur = 0;
-            if (ds.rc == hipSuccess && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * kWaves, kLds) != hipSuccess) nb = 1;
-            if (hipGetDevice(&cur) == hipSuccess) (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, cur);
-            ds.per_cu[0] = nb < 1 ? 1 : nb;
-            ds.cus = n_cu;
-        });
+        find_room(ds, (const void *)vorbis_walk_kernel<R, CH, kWaves>, kLds, 0, 0, 1,
+                  [](int) { return std::pair<int, size_t>(64 * Shape<R, CH>::kWaves, shape_lds<R, CH>()); });
         AFG_HIP_CHECK(ds.rc);
         // persistent wavefronts: as many workgroups as the device holds at once, each drawing segments from the counter
         const uint32_t need = (n_segs + kWaves - 1) / kWaves, room = (uint32_t)(ds.per_cu[0] * ds.cus);

@@ -287,7 +287,10 @@ def test_walk_shape_tdac_reconstruction(gpu, ch, n):
 
 @pytest.mark.parametrize("eighths", [0, 1, 3, 6, 8])
 @pytest.mark.parametrize("ch,bs0,bs1", [(1, 256, 2048), (2, 256, 1024), (1, 256, 1024), (2, 512, 4096), (1, 512, 4096),
-                                        (6, 256, 2048), (3, 256, 1024)])
+                                        (6, 256, 2048), (3, 256, 1024),
+                                        # 1024-sample blocks by pairs through the staged store (an odd count of eighths masks
+                                        # the upper lanes of a load there), and the stereo 4096 kernel
+                                        (4, 256, 1024), (6, 512, 1024), (2, 256, 4096)])
 def test_walk_shape_declared_zero_tail(gpu, ch, bs0, bs1, eighths):
     from afgpu import VORBIS_NZ_EIGHTHS
     import torch
@@ -314,6 +317,37 @@ def test_walk_shape_declared_zero_tail(gpu, ch, bs0, bs1, eighths):
     VorbisPlan(packets, channels, [bs0] * 2, [bs1] * 2, declared, 5).transform(torch.from_numpy(poisoned).to(gpu), d_out)
     torch.cuda.synchronize()
     assert (d_out.cpu().numpy().view(np.uint32) == plain.view(np.uint32)).all()
+
+
+@pytest.mark.parametrize("ch,bs0,bs1", [(2, 256, 2048), (2, 256, 1024), (2, 512, 4096), (4, 256, 2048), (3, 256, 1024)])
+def test_walk_shape_channels_do_not_mix(gpu, ch, bs0, bs1):
+    """A wavefront holds a pair of channels packed into the halves of its registers, and reaches one channel of the carried
+    state through a helper: redraw the spectra of the last channel alone and every other channel's column of the interleaved
+    PCM keeps its bits, while the redrawn one's moves."""
+    import torch
+    packets = [20]
+    pflags, spec = synthetic.vorbis_batch(33, packets, [ch], [bs0], [bs1], p_short_run=0.15)
+    plan = VorbisPlan(packets, [ch], [bs0], [bs1], pflags, 5)
+    so, _ = plan.offsets()
+    redrawn = spec.copy()
+    rng = np.random.default_rng(34)
+    for p, f in enumerate(pflags):
+        n2 = (bs1 if f & VORBIS_LONG else bs0) // 2
+        o = int(so[p]) + n2 * (ch - 1)
+        redrawn[o:o + n2] = rng.standard_normal(n2).astype(np.float32)
+
+    def decode(s):
+        d_out = torch.full((plan.out_floats,), float("nan"), dtype=torch.float32, device=gpu)
+        plan.transform(torch.from_numpy(s).to(gpu), d_out)
+        torch.cuda.synchronize()
+        pcm = d_out.cpu().numpy()
+        assert not np.isnan(pcm).any(), "unwritten output"
+        return pcm.view(np.uint32).reshape(-1, ch)
+
+    a, b = decode(spec), decode(redrawn)
+    for c in range(ch - 1):
+        assert (a[:, c] == b[:, c]).all(), f"channel {c} moved with channel {ch - 1}'s spectra"
+    assert (a[:, ch - 1] != b[:, ch - 1]).any(), "the redrawn channel's samples did not move"
 
 
 def test_walk_every_shape_in_one_plan(gpu):

@@ -10,7 +10,11 @@ per lane, as register passes with LDS transposes between them:
 This file restates the index algebra of those passes (which lane reads which LDS slot, which twiddle) on arrays shaped
 [64 lanes][R], so that it can be checked against numpy's FFT on the CPU and so that the LDS addresses of every access can
 be checked for bank conflicts (ds_read_b64 / ds_write_b64: two halves of 32 lanes, 64 banks of 4 bytes: the 8-byte slot
-indices of a half must differ modulo 32).  tests/test_vorbis_walk_model.py runs it; the HIP code follows it line by line.
+indices of a half must differ modulo 32).  tests/test_vorbis_walk_model.py runs it; the HIP code follows it line by line:
+fft_r4 / fft_r8 / fft_r16 are the three arms of the kernel file's fft_passes<R, V>, which is written once for a mono
+wavefront's values (V = f2, one complex slot each) and a stereo wavefront's channel-packed ones (V = c2); Lds.write / Lds.read
+are its put / get, which for c2 address a plane of real parts and a plane of imaginary parts by the same slot index, so one
+model covers both.  spectrum_to_lanes and the twiddles around FFT[R] are fft_lanes<R, CH>.
 """
 import numpy as np
 
