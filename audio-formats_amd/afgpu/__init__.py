@@ -107,6 +107,9 @@ assert CONV_KERNEL_DTYPE.itemsize == 24 and CONV_ROW_DTYPE.itemsize == 48
 CONV_BLOCK, CONV_MAX_TAPS, CONV_DIRECT_MAX, CONV_DIRECT_TILE, CONV_TABLE_FLOATS, CONV_SPEC_FLOATS = 1024, 65536, 128, 4096, 4096, 2050   # AFG_CONV_*
 LOUDNESS_K = 64                                  # AFG_LOUDNESS_K
 LOUDNESS_UNGATED, LOUDNESS_GAIN_CLAMPED, LOUDNESS_PEAK_CLAMPED = 1, 2, 4     # afg_loudness_stats.flags
+MIX_SNR, MIX_GAIN = 0, 1                         # afg_mix_group.flags
+MIX_SILENT_SIGNAL, MIX_SILENT_NOISE, MIX_ENERGY_NOT_FINITE, MIX_GAIN_NOT_FINITE = 1, 2, 4, 8   # afg_mix_stats.flags
+MIX_TILE = 4096                                  # floats of one row per tile of afg_mix_hip
 
 # every symbol include/afg.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -154,6 +157,7 @@ ABI_SYMBOLS = [
     "afg_pvoc_out_frames", "afg_pvoc_bound", "afg_pvoc_check_rows", "afg_pvoc_hip",
     "afg_convolve_bank_layout", "afg_convolve_bank_check", "afg_convolve_bank_hip", "afg_convolve_layout", "afg_convolve_bound",
     "afg_convolve_check_rows", "afg_convolve_hip",
+    "afg_mix_ratio", "afg_mix_layout", "afg_mix_check_groups", "afg_mix_hip", "afg_batch_decode_mixed",
 ]
 
 
@@ -448,6 +452,30 @@ class LoudnessStats(C.Structure):
 LOUDNESS_GROUP_DTYPE = np.dtype(LoudnessGroup)   # arrays of the records, as the other stages' *_DTYPE
 LOUDNESS_STATS_DTYPE = np.dtype(LoudnessStats)
 assert LOUDNESS_GROUP_DTYPE.itemsize == 64 and LOUDNESS_STATS_DTYPE.itemsize == 40 and C.sizeof(LoudnessParams) == 96 and C.sizeof(LoudnessCounts) == 16
+
+
+class MixGroup(C.Structure):
+    """afg_mix_group: the rows one gain covers and the noise under them (afg_mix_hip)."""
+    _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("stride", C.c_uint64), ("first_tile", C.c_uint64), ("noise_off", C.c_uint64),
+                ("noise_stride", C.c_uint64), ("ratio", C.c_double), ("rows", C.c_uint32), ("valid", C.c_uint32), ("noise_len", C.c_uint32),
+                ("noise_start", C.c_uint32), ("flags", C.c_uint32), ("gain", C.c_float)]
+
+
+class MixStats(C.Structure):
+    """afg_mix_stats: one group's record."""
+    _fields_ = [("signal_energy", C.c_double), ("noise_energy", C.c_double), ("gain", C.c_float), ("flags", C.c_uint32)]
+
+
+class MixNoise(C.Structure):
+    """afg_mix_noise: the noise bank of afg_batch_decode_mixed and what every file takes of it."""
+    _fields_ = [("d_noise", C.c_void_p), ("n_clips", C.c_uint64), ("clip_pitch", C.c_uint32), ("clip_rows", C.c_uint32),
+                ("lengths", C.POINTER(C.c_uint32)), ("index", C.POINTER(C.c_uint32)), ("start", C.POINTER(C.c_uint64)),
+                ("snr_db", C.POINTER(C.c_double))]
+
+
+MIX_GROUP_DTYPE = np.dtype(MixGroup)             # arrays of the records, as the other stages' *_DTYPE
+MIX_STATS_DTYPE = np.dtype(MixStats)
+assert MIX_GROUP_DTYPE.itemsize == 80 and MIX_STATS_DTYPE.itemsize == 24 and C.sizeof(MixNoise) == 56
 
 
 class EncodingOptions(C.Structure):
@@ -754,6 +782,13 @@ def lib():
     L.afg_convolve_bound.restype = C.c_double
     L.afg_convolve_check_rows.argtypes = [vp, u64, u64, vp, u64, C.POINTER(ConvolveParams), u64, u64, u64, u64, u64, C.POINTER(u64)]
     L.afg_convolve_hip.argtypes = [u64, vp, u64, vp, u64, C.POINTER(ConvolveParams), vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, vp]
+    L.afg_mix_ratio.argtypes = [C.c_double]
+    L.afg_mix_ratio.restype = C.c_double
+    L.afg_mix_layout.argtypes = [vp, u64]
+    L.afg_mix_layout.restype = u64
+    L.afg_mix_check_groups.argtypes = [vp, u64, u64, u64, u64, u64, C.POINTER(u64)]
+    L.afg_mix_hip.argtypes = [u64, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, vp]
+    L.afg_batch_decode_mixed.argtypes = [vp, vp, C.c_int, C.POINTER(ResampleOpts), C.POINTER(MixNoise), vp, vp, C.POINTER(BatchResult)]
     _lib = L
     _sync_dev_options(L)
     return L
@@ -2419,6 +2454,176 @@ def batch_decode_tensor_loudnorm(files, frames, channels, samplerate, target_luf
         return L.afg_batch_decode_loudnorm(ptrs, lens, n, C.byref(opts), C.byref(prm), out.data_ptr(), stats.ctypes.data, C.byref(res))
 
     out, meta = _batch_tensor_call("batch_decode_tensor_loudnorm", files, (n, channels, frames), out, first_frame, call)
+    return out, meta, stats[:n].copy()
+
+
+def mix_ratio(snr_db):
+    """afg_mix_ratio: 10^(-snr_db / 10) in double, as the host computes it for an afg_mix_group in MIX_SNR mode."""
+    return float(lib().afg_mix_ratio(float(snr_db)))
+
+
+def mix_layout(groups):
+    """afg_mix_layout: fills first_tile of a MIX_GROUP_DTYPE array in place; returns the launch's tile count."""
+    assert groups.dtype == MIX_GROUP_DTYPE and groups.flags.c_contiguous
+    return int(lib().afg_mix_layout(groups.ctypes.data, len(groups)))
+
+
+def mix_check_groups(groups, n_tiles, in_floats, noise_floats, out_floats, plane_at=None):
+    """afg_mix_check_groups: what afg_mix_hip checks before it launches, on host records.  plane_at: None (three separate
+    planes) or the float indices of the first float of the input, noise and output plane in one address space.  AfgError when
+    a check fails."""
+    assert groups.dtype == MIX_GROUP_DTYPE and groups.flags.c_contiguous
+    at = None if plane_at is None else (C.c_uint64 * 3)(*[int(v) for v in plane_at])
+    check(lib().afg_mix_check_groups(groups.ctypes.data, len(groups), int(n_tiles), int(in_floats), int(noise_floats), int(out_floats), at))
+
+
+def mix(n_groups, d_groups, n_tiles, d_in, in_floats, d_noise, noise_floats, d_out, out_floats, d_partials, d_stats, stream=None):
+    """Enqueue the mixing kernels (afg_mix_hip) on device arrays: both energies and the gain of every group into d_stats
+    (MIX_STATS_DTYPE records) and every valid element plus the gain times the noise under it into d_out (d_in itself for in
+    place).  d_partials: n_tiles * 16 bytes.  The groups are checked first (the call waits for `stream` to read them):
+    AfgError, and nothing written, when one fails."""
+    check(lib().afg_mix_hip(int(n_groups), _ptr(d_groups), int(n_tiles), _ptr(d_in), int(in_floats), _ptr(d_noise), int(noise_floats),
+                            _ptr(d_out), int(out_floats), _ptr(d_partials), _ptr(d_stats), _stream(stream)))
+
+
+def _per_group(who, name, value, n, dtype, default=None):
+    """a scalar or one value per group as an array of n"""
+    if value is None:
+        value = default
+    v = np.asarray(value.cpu() if hasattr(value, "cpu") else value)
+    if v.ndim == 0:
+        v = np.full(n, v)
+    v = v.reshape(-1)
+    if v.size != n:
+        raise ValueError(f"{who}: {name} is a scalar or holds one value per group ({n})")
+    return v.astype(dtype)
+
+
+def _mix_noise_args(who, noise, channels, n, snr_db, gain, noise_lengths, noise_index, noise_start):
+    """What add_noise_tensor and batch_decode_tensor_noisy share: the bank's shape and the per-group clip, start and level,
+    checked.  Returns (K, clip rows, N, lengths[K], index[n], start[n] reduced, snr[n] or None, gain[n] or None)."""
+    import torch
+    if not isinstance(noise, torch.Tensor) or not noise.is_cuda or noise.dtype != torch.float32 or not noise.is_contiguous() or noise.dim() not in (2, 3):
+        raise ValueError(f"{who}: noise is a contiguous float32 device tensor [K, N] or [K, channels, N]")
+    K, N = int(noise.shape[0]), int(noise.shape[-1])
+    clip_rows = 1 if noise.dim() == 2 else int(noise.shape[1])
+    if K < 1 or N < 1 or N >= 1 << 32:
+        raise ValueError(f"{who}: noise holds at least one clip of 1 .. 2^32 - 1 samples")
+    if noise.dim() == 3 and clip_rows != channels:
+        raise ValueError(f"{who}: noise [K, channels, N] has {clip_rows} channels, the signal {channels}")
+    if (snr_db is None) == (gain is None):
+        raise ValueError(f"{who}: exactly one of snr_db and gain")
+    lengths = _per_group(who, "noise_lengths", noise_lengths, K, np.int64, N) if noise_lengths is None or np.ndim(noise_lengths) == 0 else None
+    if lengths is None:
+        lengths = np.asarray(noise_lengths.cpu() if hasattr(noise_lengths, "cpu") else noise_lengths).reshape(-1).astype(np.int64)
+        if lengths.size != K:
+            raise ValueError(f"{who}: noise_lengths holds one length per clip ({K})")
+    if (lengths < 1).any() or (lengths > N).any():
+        raise ValueError(f"{who}: noise_lengths: 1 .. {N}")
+    index = _per_group(who, "noise_index", noise_index, n, np.int64, 0)
+    if (index < 0).any() or (index >= K).any():
+        raise ValueError(f"{who}: noise_index: 0 .. {K - 1}")
+    start = _per_group(who, "noise_start", noise_start, n, np.int64, 0)
+    if (start < 0).any():
+        raise ValueError(f"{who}: noise_start: at least 0")
+    start = start % lengths[index] if n else start
+    snr = g = None
+    if snr_db is not None:
+        snr = _per_group(who, "snr_db", snr_db, n, np.float64)
+        if not np.isfinite(snr).all() or not np.isfinite([mix_ratio(v) for v in snr]).all():
+            raise ValueError(f"{who}: snr_db: finite, with a finite ratio 10^(-snr_db / 10)")
+    else:
+        g = _per_group(who, "gain", gain, n, np.float32)
+        if not np.isfinite(g).all() or (g < 0).any():
+            raise ValueError(f"{who}: gain: finite and at least 0")
+    return K, clip_rows, N, lengths, index, start, snr, g
+
+
+def add_noise_tensor(t, noise, snr_db=None, gain=None, noise_lengths=None, noise_index=None, noise_start=None, valid=None, out=None):
+    """Add noise from a bank of clips to every group of a contiguous float32 device tensor [..., channels, frames] -- the
+    channel axis is one group; the leading axes are flattened -- at a signal-to-noise ratio measured over the group's own
+    valid samples (afg_mix_hip, on the current stream; include/afg.h has the definition; with the gain it reports, the result
+    is torchaudio.functional.add_noise's expression bit for bit).  noise: a contiguous float32 device tensor [K, N] (a clip
+    is shared by a group's channels) or [K, channels, N].  noise_lengths: None (N) or one length per clip; a clip shorter
+    than the row loops.  noise_index, noise_start, and snr_db or gain (exactly one of the two; gain: y = x + gain * n as it
+    is): a scalar or one value per group; noise_start is reduced modulo the clip's length.  valid: None, or one length per
+    group: only that many frames of its rows count and are touched.  out: None (a new tensor, a copy of t behind `valid`),
+    `t` itself (in place) or another contiguous tensor of t's shape that overlaps neither t nor the bank.  Returns
+    (out, stats): stats a MIX_STATS_DTYPE array with one record per group.  ValueError, before any launch, for arguments out
+    of range."""
+    import torch
+    who = "add_noise_tensor"
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 2:
+        raise ValueError(f"{who}: a contiguous float32 device tensor [..., channels, frames]")
+    rows, frames = int(t.shape[-2]), int(t.shape[-1])
+    if rows < 1 or rows > 65535 or frames >= 1 << 32:
+        raise ValueError(f"{who}: 1 .. 65535 channels of fewer than 2^32 frames")
+    n = t.numel() // (rows * frames) if frames else 0
+    K, clip_rows, N, lengths, index, start, snr, g = _mix_noise_args(who, noise, rows, n, snr_db, gain, noise_lengths, noise_index, noise_start)
+    if noise.device != t.device:
+        raise ValueError(f"{who}: noise must live on t's device")
+    if out is None:
+        out = t.clone() if valid is not None else torch.empty_like(t)
+    elif out.shape != t.shape or out.dtype != t.dtype or out.device != t.device or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous tensor of t's shape, dtype and device")
+    groups = np.zeros(n, MIX_GROUP_DTYPE)
+    groups["in_off"] = groups["out_off"] = np.arange(n, dtype=np.uint64) * np.uint64(rows * frames)
+    groups["stride"], groups["rows"], groups["valid"] = frames, rows, frames
+    if valid is not None:
+        v = np.asarray(valid.cpu() if hasattr(valid, "cpu") else valid).reshape(-1)
+        if v.size != n or (v < 0).any() or (v > frames).any():
+            raise ValueError(f"{who}: valid holds one length per group, 0 .. the last axis")
+        groups["valid"] = v
+    if n == 0:
+        return out, np.zeros(0, MIX_STATS_DTYPE)
+    groups["noise_off"] = index.astype(np.uint64) * np.uint64(clip_rows * N)
+    groups["noise_stride"] = 0 if noise.dim() == 2 else N
+    groups["noise_len"], groups["noise_start"] = lengths[index], start
+    if snr is not None:
+        groups["flags"], groups["ratio"] = MIX_SNR, [mix_ratio(v) for v in snr]
+    else:
+        groups["flags"], groups["gain"] = MIX_GAIN, g
+    tiles = mix_layout(groups)
+    L = lib()
+    at = (C.c_uint64 * 3)(t.data_ptr() // 4, noise.data_ptr() // 4, out.data_ptr() // 4)
+    if L.afg_mix_check_groups(groups.ctypes.data, n, tiles, t.numel(), noise.numel(), out.numel(), at) != 0:
+        raise ValueError(f"{who}: {L.afg_last_error().decode()}")
+    with torch.cuda.device(t.device):
+        d_groups = torch.from_numpy(groups.view(np.uint8)).to(t.device)
+        d_partials = torch.empty(max(tiles, 1) * 2, dtype=torch.float64, device=t.device)
+        d_stats = torch.zeros(n * MIX_STATS_DTYPE.itemsize, dtype=torch.uint8, device=t.device)
+        mix(n, d_groups, tiles, t, t.numel(), noise, noise.numel(), out, out.numel(), d_partials, d_stats, torch.cuda.current_stream().cuda_stream)
+        stats = d_stats.cpu().numpy().view(MIX_STATS_DTYPE).copy()
+    return out, stats
+
+
+def batch_decode_tensor_noisy(files, frames, channels, samplerate, noise, snr_db, noise_lengths=None, noise_index=None, noise_start=None,
+                              first_frame=None, mono=False, in_channels=0, max_in_rate=0, lowpass_width=0, out=None, n_threads=0):
+    """afg_batch_decode_mixed: batch_decode_tensor_resampled, then noise from the bank added to every file in place at snr_db
+    over the file's own samples -- its channel rows one group, the rows and lengths of batch_decode_tensor_normalized; the
+    padding is left as it is.  noise, noise_lengths, noise_index, noise_start and snr_db as add_noise_tensor takes them, one
+    value per file where they are no scalars; the bank is at `samplerate` already.  Returns (tensor, meta, stats): stats a
+    MIX_STATS_DTYPE array with one record per file (all zero, gain 0, for a file that failed).  The same device and stream
+    rules as batch_decode_tensor; ValueError for arguments out of range, before any call."""
+    who = "batch_decode_tensor_noisy"
+    frames, channels, samplerate = int(frames), int(channels), int(samplerate)
+    if frames < 1 or channels < 1 or samplerate < 1:
+        raise ValueError(f"{who}: frames, channels and samplerate must be at least 1")
+    if mono and channels != 1:
+        raise ValueError(f"{who}: a mono tensor has one channel")
+    n = len(files)
+    K, clip_rows, N, lengths, index, start, snr, _ = _mix_noise_args(who, noise, channels, n, snr_db, None, noise_lengths, noise_index, noise_start)
+    stats = np.zeros(max(n, 1), MIX_STATS_DTYPE)
+    c_len, c_idx = (C.c_uint32 * K)(*[int(v) for v in lengths]), (C.c_uint32 * max(n, 1))(*[int(v) for v in index])
+    c_start, c_snr = (C.c_uint64 * max(n, 1))(*[int(v) for v in start]), (C.c_double * max(n, 1))(*[float(v) for v in snr])
+    bank = MixNoise(noise.data_ptr(), K, N, clip_rows, c_len, c_idx, c_start, c_snr)
+
+    def call(ptrs, lens, n, ff, out, res):
+        opts = ResampleOpts(C.sizeof(ResampleOpts), int(n_threads), channels, frames, ff, samplerate, 1 if mono else 0, int(in_channels),
+                            int(max_in_rate), int(lowpass_width))
+        return lib().afg_batch_decode_mixed(ptrs, lens, n, C.byref(opts), C.byref(bank), out.data_ptr(), stats.ctypes.data, C.byref(res))
+
+    out, meta = _batch_tensor_call(who, files, (n, channels, frames), out, first_frame, call)
     return out, meta, stats[:n].copy()
 
 

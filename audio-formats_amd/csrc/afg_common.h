@@ -126,6 +126,11 @@ int loudness_launch(const afg_loudness_group *h_groups, uint64_t n_groups, const
                     const afg_loudness_params *params, const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats,
                     double *d_sub, double *d_blocks, afg_loudness_stats *d_stats, hipStream_t stream);
 
+// afg_mix_hip likewise (mix.hip); the planes' addresses give afg_mix_check_groups its plane_at
+int mix_launch(const afg_mix_group *h_groups, uint64_t n_groups, const afg_mix_group *d_groups, uint64_t n_tiles, const float *d_in,
+               uint64_t in_floats, const float *d_noise, uint64_t noise_floats, float *d_out, uint64_t out_floats, void *d_partials,
+               afg_mix_stats *d_stats, hipStream_t stream);
+
 // Owns a device buffer filled from a host array at plan creation.
 struct DeviceArray {
     void *ptr = nullptr;

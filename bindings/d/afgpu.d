@@ -619,6 +619,22 @@ int afg_convolve_hip(ulong n_rows, const(afg_convolve_row)* d_rows, ulong n_tile
                      const(afg_convolve_params)* params, const(float)* d_in, ulong in_floats, const(float)* d_bank, ulong bank_floats,
                      const(float)* d_spec, ulong spec_floats, float* d_work, ulong work_floats, float* d_out, ulong out_floats,
                      void* hip_stream);
+// mixing: noise from a bank of clips added to groups of rows at a signal-to-noise ratio (include/afg.h has the definition)
+enum : uint { AFG_MIX_SNR = 0, AFG_MIX_GAIN = 1 }
+enum : uint { AFG_MIX_SILENT_SIGNAL = 1, AFG_MIX_SILENT_NOISE = 2, AFG_MIX_ENERGY_NOT_FINITE = 4, AFG_MIX_GAIN_NOT_FINITE = 8 }
+struct afg_mix_group { ulong in_off, out_off, stride, first_tile, noise_off, noise_stride; double ratio; uint rows, valid, noise_len, noise_start, flags; float gain; }
+static assert(afg_mix_group.sizeof == 80);
+struct afg_mix_stats { double signal_energy, noise_energy; float gain; uint flags; }
+struct afg_mix_noise { const(float)* d_noise; ulong n_clips; uint clip_pitch, clip_rows; const(uint)* lengths; const(uint)* index; const(ulong)* start; const(double)* snr_db; }
+double afg_mix_ratio(double snr_db);
+ulong afg_mix_layout(afg_mix_group* groups, ulong n_groups);
+int afg_mix_check_groups(const(afg_mix_group)* groups, ulong n_groups, ulong n_tiles, ulong in_floats, ulong noise_floats,
+                         ulong out_floats, const(ulong)* plane_at);
+int afg_mix_hip(ulong n_groups, const(afg_mix_group)* d_groups, ulong n_tiles, const(float)* d_in, ulong in_floats,
+                const(float)* d_noise, ulong noise_floats, float* d_out, ulong out_floats, void* d_partials, afg_mix_stats* d_stats,
+                void* hip_stream);
+int afg_batch_decode_mixed(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_resample_opts)* opts,
+                           const(afg_mix_noise)* noise, float* d_out, afg_mix_stats* stats, afg_batch_result* out_);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

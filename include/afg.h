@@ -2228,6 +2228,124 @@ int afg_convolve_hip(uint64_t n_rows, const afg_convolve_row *d_rows, uint64_t n
                      const float *d_spec, uint64_t spec_floats, float *d_work, uint64_t work_floats, float *d_out, uint64_t out_floats,
                      void *hip_stream);
 
+/* ---- mixing: noise added to waveform rows at a signal-to-noise ratio, per group of rows -------------------------------------
+ * The third waveform augmentation of speech-training recipes beside speed perturbation (the resampler) and reverberation
+ * (afg_convolve_hip): additive noise from a bank of clips at a chosen SNR (MUSAN-style; torchaudio.functional.add_noise).
+ * The reference has no such stage; the definition is this library's own, restated in numpy in tests/mix_model.py, and the
+ * device follows it bit for bit.
+ *
+ * Groups.  A group (afg_mix_group) is what one gain covers -- one file's channel rows: rows 1 .. 65535; row r starts at
+ * float in_off + r * stride of d_in and out_off + r * stride of d_out (4-byte aligned only); only the first `valid` floats
+ * of a row count and are touched.  Tiles are afg_norm_group's: 4096 consecutive floats of one row from its element 0, rows
+ * ascending, then tiles ascending; afg_mix_layout fills first_tile and returns the tile count.  valid == 0: nothing is
+ * read, nothing written, and the record is all zero.
+ *
+ * Noise source.  The group names its noise in the noise plane d_noise: noise_off (floats, any residue mod 4), noise_len
+ * = N >= 1, noise_start < N, noise_stride.  noise_stride 0: one noise row, at noise_off, is shared by all the group's rows;
+ * otherwise row r reads the row at noise_off + r * noise_stride, and noise_stride >= N.  The noise sample under element e
+ * of row r is n[(noise_start + e) mod N]: a clip shorter than the row loops.
+ *
+ * Modes (afg_mix_group.flags).  AFG_MIX_SNR: the group carries `ratio`, a float64 the host computes as 10^(-snr_db / 10)
+ * (afg_mix_ratio(snr_db): host only; there is no pow on the device, so its results can be compared as bits); finite and
+ * >= 0.  AFG_MIX_GAIN: the group carries the float32 `gain` itself, finite and >= 0; the energies are still measured and
+ * reported, the record's flags are 0.  The field of the other mode is ignored.
+ *
+ * Energies, in float64, in the normalisation's order, without atomics.  Es is the sum of x^2 over the valid elements of
+ * all rows; En the sum of the squared noise samples as used under the same elements, wrapped -- a shared noise row is
+ * counted once per row.  Element e of a tile belongs to lane (e / 4) % 256 of 256 lanes; a lane starts from +0.0 and over
+ * its elements in ascending e does q = q + (double)v * (double)v (the product is exact, only the adds round); lanes combine
+ * in a binary tree, step d = 1, 2, 4 .. 128, lane l with l % (2 d) == 0 taking v[l] = v[l] + v[l + d]; a group's tile
+ * results combine one after the other in tile order from +0.0.
+ *
+ * Gain.  AFG_MIX_SNR: g = (float)sqrt((Es / En) * ratio): IEEE double division, product and square root, each rounded,
+ * nothing contracted, then one rounding to float32.  The gain is 0, and the record's flags say why, when Es is 0
+ * (AFG_MIX_SILENT_SIGNAL), En is 0 (AFG_MIX_SILENT_NOISE), Es or En is not finite (AFG_MIX_ENERGY_NOT_FINITE; a NaN
+ * sample propagates through its sum), or -- with none of these -- the float32 gain is not finite
+ * (AFG_MIX_GAIN_NOT_FINITE).  Several of the first three may be set together.
+ *
+ * Output.  y = x + g * n: the float32 product rounded first, the float32 sum after it, no fused multiply-add -- with the
+ * same gain, torchaudio's expression bit for bit.  With g == 0 the output is the input's bits and the noise is not read
+ * (in place: nothing is written).  A NaN in Es, En or the output is always the positive quiet NaN (0x7ff8000000000000,
+ * 0x7fc00000), the normalisation's rule: which NaN an operation returns is the hardware's affair, and the definition leaves
+ * none of that in its results.  No float behind `valid` is read or written, in any plane.  In place (d_out == d_in,
+ * out_off == in_off) is allowed: every element is read and then written by one lane.  Any other meeting of an output row
+ * with an input row or another output row is refused, and so is an output plane that overlaps the noise plane.
+ *
+ * afg_mix_check_groups: host only, needs no device; the checks afg_mix_hip makes before it launches, on a host copy of the
+ * groups: flags AFG_MIX_SNR or AFG_MIX_GAIN; the mode's ratio or gain finite and >= 0; rows 1 .. 65535; first_tile and
+ * n_tiles as afg_mix_layout gives them; at most 2^32 - 1 groups and 2^31 - 1 tiles; and for a group with valid > 0:
+ * stride >= valid when rows > 1; noise_len >= 1, noise_start < noise_len, noise_stride 0 or >= noise_len; its rows inside
+ * [0, in_floats) and [0, out_floats) and its noise rows inside [0, noise_floats), offsets and strides that would wrap
+ * included; no output row meeting another output row.  plane_at: NULL (three separate planes), or the float index of the
+ * first float of the input, noise and output plane (in that order) in one address space: then an output row may meet no
+ * input row but its own at the same address, and the output plane must not overlap the noise plane.  AFG_ERR_INVALID with
+ * afg_last_error set otherwise.
+ *
+ * afg_mix_hip: three launches on hip_stream -- the tiles' partial sums into d_partials (n_tiles * 16 bytes, 16-byte
+ * aligned), the groups' records into d_stats (n_groups of them, 8-byte aligned), and the apply pass.  d_groups (8-byte
+ * aligned) is the device copy of the laid-out groups; the entry fetches it on hip_stream, waits for it and checks every
+ * group as afg_mix_check_groups does with plane_at taken from the pointers: anything but a pass is AFG_ERR_INVALID and
+ * nothing is written.  The planes are 4-byte aligned. */
+#define AFG_MIX_SNR                0u   /* afg_mix_group.flags: the gain follows from the energies and `ratio` */
+#define AFG_MIX_GAIN               1u   /* afg_mix_group.flags: the gain is `gain` */
+#define AFG_MIX_SILENT_SIGNAL      1u   /* afg_mix_stats.flags: Es is 0; gain 0 */
+#define AFG_MIX_SILENT_NOISE       2u   /* afg_mix_stats.flags: En is 0; gain 0 */
+#define AFG_MIX_ENERGY_NOT_FINITE  4u   /* afg_mix_stats.flags: Es or En is an infinity or a NaN; gain 0 */
+#define AFG_MIX_GAIN_NOT_FINITE    8u   /* afg_mix_stats.flags: the float32 gain came out an infinity or a NaN; gain 0 */
+typedef struct afg_mix_group {    /* 80 bytes */
+    uint64_t in_off, out_off;     /* float index of row 0, element 0 in d_in / d_out */
+    uint64_t stride;              /* floats from one row to the next, in both planes; >= valid when rows > 1 */
+    uint64_t first_tile;          /* filled in by afg_mix_layout */
+    uint64_t noise_off;           /* float index of the (first) noise row's sample 0 in d_noise */
+    uint64_t noise_stride;        /* 0: one noise row for all rows; else floats from one noise row to the next, >= noise_len */
+    double   ratio;               /* AFG_MIX_SNR: 10^(-snr_db / 10), afg_mix_ratio */
+    uint32_t rows, valid;
+    uint32_t noise_len;           /* N: samples of a noise row, >= 1 */
+    uint32_t noise_start;         /* the noise sample under element 0, < noise_len */
+    uint32_t flags;               /* AFG_MIX_SNR or AFG_MIX_GAIN */
+    float    gain;                /* AFG_MIX_GAIN */
+} afg_mix_group;
+typedef struct afg_mix_stats {    /* 24 bytes, one per group */
+    double   signal_energy, noise_energy;
+    float    gain;                /* what the apply pass used */
+    uint32_t flags;               /* AFG_MIX_SILENT_SIGNAL .. AFG_MIX_GAIN_NOT_FINITE */
+} afg_mix_stats;
+/* Host only: pow(10, -snr_db / 10) in double. */
+double afg_mix_ratio(double snr_db);
+/* Host: fills first_tile of every group, returns the launch's tile count. */
+uint64_t afg_mix_layout(afg_mix_group *groups, uint64_t n_groups);
+int afg_mix_check_groups(const afg_mix_group *groups, uint64_t n_groups, uint64_t n_tiles, uint64_t in_floats, uint64_t noise_floats,
+                         uint64_t out_floats, const uint64_t *plane_at);
+int afg_mix_hip(uint64_t n_groups, const afg_mix_group *d_groups, uint64_t n_tiles, const float *d_in, uint64_t in_floats,
+                const float *d_noise, uint64_t noise_floats, float *d_out, uint64_t out_floats, void *d_partials, afg_mix_stats *d_stats,
+                void *hip_stream);
+
+/* afg_batch_decode_resampled, then one afg_mix_hip launch in place over the whole tensor, one group per file exactly as
+ * afg_batch_decode_resampled_norm makes them (rows, `valid`); what lies behind `valid`, and the rows a file has no channel
+ * for, stay as afg_batch_decode_resampled leaves them.  The noise bank (afg_mix_noise) is the caller's device memory, at the
+ * tensor's rate already: n_clips clips of clip_rows rows of clip_pitch floats.  clip_rows 1: a clip's one row is shared by
+ * a file's channels; otherwise clip_rows == opts->channels and channel r takes row r.  lengths (host, one per clip, 1 ..
+ * clip_pitch; NULL: clip_pitch), index (host, one per file, below n_clips; NULL: clip 0), start (host, one per file, reduced
+ * modulo the clip's length; NULL: 0), snr_db (host, one per file, finite).  File i's group is in AFG_MIX_SNR mode with ratio
+ * afg_mix_ratio(snr_db[i]).  A failed or refused file is a group with valid == 0: a zero slab, a zero record, gain 0.  stats
+ * (host, n_files records) may be NULL; it is filled when the launch has drained.  Checked before any device call,
+ * AFG_ERR_INVALID with afg_last_error set: everything afg_batch_decode_resampled checks; NULL noise, d_noise or snr_db;
+ * d_noise not 4-byte aligned; n_clips, clip_pitch or clip_rows 0; clip_rows neither 1 nor the tensor's channels; a length,
+ * an index or an snr_db out of range; a bank that overlaps the tensor.  Statuses, messages and items[i] are
+ * afg_batch_decode_resampled's. */
+typedef struct afg_mix_noise {    /* 56 bytes */
+    const float    *d_noise;      /* device: [n_clips, clip_rows, clip_pitch] floats */
+    uint64_t        n_clips;
+    uint32_t        clip_pitch;   /* floats of a clip row */
+    uint32_t        clip_rows;    /* 1, or the tensor's channels */
+    const uint32_t *lengths;      /* host, n_clips, or NULL */
+    const uint32_t *index;        /* host, n_files, or NULL */
+    const uint64_t *start;        /* host, n_files, or NULL */
+    const double   *snr_db;       /* host, n_files */
+} afg_mix_noise;
+int afg_batch_decode_mixed(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
+                           const afg_mix_noise *noise, float *d_out, afg_mix_stats *stats, afg_batch_result *out);
+
 #ifdef __cplusplus
 }
 #endif
