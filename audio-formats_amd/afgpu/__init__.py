@@ -110,6 +110,11 @@ LOUDNESS_UNGATED, LOUDNESS_GAIN_CLAMPED, LOUDNESS_PEAK_CLAMPED = 1, 2, 4     # a
 MIX_SNR, MIX_GAIN = 0, 1                         # afg_mix_group.flags
 MIX_SILENT_SIGNAL, MIX_SILENT_NOISE, MIX_ENERGY_NOT_FINITE, MIX_GAIN_NOT_FINITE = 1, 2, 4, 8   # afg_mix_stats.flags
 MIX_TILE = 4096                                  # floats of one row per tile of afg_mix_hip
+FBANK_FRAMES_MAJOR, FBANK_MEL_MAJOR = 0, 1       # afg_fbank_params.layout
+FBANK_WINDOW_POVEY, FBANK_WINDOW_HAMMING, FBANK_WINDOW_HANNING, FBANK_WINDOW_BLACKMAN, FBANK_WINDOW_RECTANGULAR = range(5)
+FBANK_WINDOW_NAMES = {"povey": FBANK_WINDOW_POVEY, "hamming": FBANK_WINDOW_HAMMING, "hanning": FBANK_WINDOW_HANNING,
+                      "blackman": FBANK_WINDOW_BLACKMAN, "rectangular": FBANK_WINDOW_RECTANGULAR}
+FBANK_TILE = 16                                  # frames of one row per tile of afg_fbank_hip
 
 # every symbol include/afg.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -158,6 +163,8 @@ ABI_SYMBOLS = [
     "afg_convolve_bank_layout", "afg_convolve_bank_check", "afg_convolve_bank_hip", "afg_convolve_layout", "afg_convolve_bound",
     "afg_convolve_check_rows", "afg_convolve_hip",
     "afg_mix_ratio", "afg_mix_layout", "afg_mix_check_groups", "afg_mix_hip", "afg_batch_decode_mixed",
+    "afg_fbank_n_fft", "afg_fbank_frames", "afg_fbank_tables", "afg_fbank_filters", "afg_fbank_layout", "afg_fbank_check_rows", "afg_fbank_hip",
+    "afg_batch_decode_fbank",
 ]
 
 
@@ -338,6 +345,21 @@ class ConvolveParams(C.Structure):
 class StftOpts(C.Structure):
     """afg_stft_opts (afg_batch_decode_stft): afg_resample_opts' fields, n_out, the parameters and a reserved 0."""
     _fields_ = ResampleOpts._fields_ + [("n_out", C.c_uint32), ("stft", StftParams), ("reserved", C.c_uint32)]
+
+
+class FbankParams(C.Structure):
+    """afg_fbank_params (afg_fbank_hip)."""
+    _fields_ = [("win_length", C.c_uint32), ("hop", C.c_uint32), ("n_fft", C.c_uint32), ("n_mels", C.c_uint32), ("snip_edges", C.c_uint32),
+                ("remove_dc", C.c_uint32), ("use_power", C.c_uint32), ("use_log", C.c_uint32), ("use_energy", C.c_uint32),
+                ("raw_energy", C.c_uint32), ("htk_compat", C.c_uint32), ("layout", C.c_uint32), ("preemph", C.c_float),
+                ("energy_floor", C.c_float), ("scale", C.c_float), ("reserved", C.c_uint32)]
+
+
+class FbankOpts(C.Structure):
+    """afg_fbank_opts (afg_batch_decode_fbank): afg_resample_opts' fields, n_out, the parameters, the window type, the bank's
+    arguments, the Blackman coefficient and a reserved 0."""
+    _fields_ = ResampleOpts._fields_ + [("n_out", C.c_uint32), ("fbank", FbankParams), ("window_type", C.c_uint32), ("low_freq", C.c_double),
+                                        ("high_freq", C.c_double), ("blackman_coeff", C.c_double), ("reserved", C.c_uint32)]
 
 
 class NormGroup(C.Structure):
@@ -789,6 +811,19 @@ def lib():
     L.afg_mix_check_groups.argtypes = [vp, u64, u64, u64, u64, u64, C.POINTER(u64)]
     L.afg_mix_hip.argtypes = [u64, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, vp]
     L.afg_batch_decode_mixed.argtypes = [vp, vp, C.c_int, C.POINTER(ResampleOpts), C.POINTER(MixNoise), vp, vp, C.POINTER(BatchResult)]
+    L.afg_fbank_n_fft.argtypes = [u32, u32]
+    L.afg_fbank_n_fft.restype = u32
+    L.afg_fbank_frames.argtypes = [C.POINTER(FbankParams), u32]
+    L.afg_fbank_frames.restype = u32
+    L.afg_fbank_tables.argtypes = [u32, u32, u32, C.c_double, vp, u64]
+    L.afg_fbank_tables.restype = u64
+    L.afg_fbank_filters.argtypes = [u32, u32, u32, C.c_double, C.c_double, vp, u64]
+    L.afg_fbank_filters.restype = u64
+    L.afg_fbank_layout.argtypes = [vp, u64, C.POINTER(FbankParams)]
+    L.afg_fbank_layout.restype = u64
+    L.afg_fbank_check_rows.argtypes = [vp, u64, u64, C.POINTER(FbankParams), u64, u64, u64, u64]
+    L.afg_fbank_hip.argtypes = [u64, vp, u64, C.POINTER(FbankParams), vp, u64, vp, u64, vp, u64, vp, u64, vp]
+    L.afg_batch_decode_fbank.argtypes = [vp, vp, C.c_int, C.POINTER(FbankOpts), vp, vp, C.POINTER(BatchResult)]
     _lib = L
     _sync_dev_options(L)
     return L
@@ -2884,6 +2919,190 @@ def stft_tensor(wave, n_fft=400, hop=160, win_length=None, center=True, pad_mode
             stft(n, d_rows, tiles, prm, wave, wave.numel(), table, table.numel(), out, out.numel(), torch.cuda.current_stream().cuda_stream)
     res = torch.view_as_complex(out) if comps == 2 else out
     return res if valid is None else (res, rows["out_frames"].astype(np.int64))
+
+
+def _fbank_window(who, window_type):
+    if isinstance(window_type, str):
+        if window_type not in FBANK_WINDOW_NAMES:
+            raise ValueError(f"{who}: window_type {window_type!r}: one of {sorted(FBANK_WINDOW_NAMES)}")
+        return FBANK_WINDOW_NAMES[window_type]
+    return int(window_type)
+
+
+def fbank_n_fft(win_length, round_to_power_of_two=True):
+    """afg_fbank_n_fft: Kaldi's transform length for a window -- the next power of two, or the window itself."""
+    n = int(lib().afg_fbank_n_fft(int(win_length), 1 if round_to_power_of_two else 0))
+    if n == 0:
+        raise AfgError(f"afg: {lib().afg_last_error().decode()}")
+    return n
+
+
+def fbank_params(win_length=400, hop=160, n_fft=None, n_mels=23, snip_edges=True, remove_dc=True, preemph=0.97, use_power=True,
+                 use_log=True, use_energy=False, raw_energy=True, htk_compat=False, energy_floor=1.0, scale=0.0, layout=FBANK_FRAMES_MAJOR):
+    """afg_fbank_params with torchaudio.compliance.kaldi.fbank's defaults at 16 kHz (n_fft None: the next power of two)."""
+    n_fft = fbank_n_fft(win_length) if n_fft is None else int(n_fft)
+    return FbankParams(int(win_length), int(hop), n_fft, int(n_mels), 1 if snip_edges else 0, 1 if remove_dc else 0, 1 if use_power else 0,
+                       1 if use_log else 0, 1 if use_energy else 0, 1 if raw_energy else 0, 1 if htk_compat else 0, int(layout),
+                       float(preemph), float(energy_floor), float(scale), 0)
+
+
+def fbank_frames(params, in_frames):
+    """afg_fbank_frames: the frames a row of in_frames samples has (0 also for parameters out of range)."""
+    return int(lib().afg_fbank_frames(C.byref(params), int(in_frames)))
+
+
+def fbank_tables(window_type, win_length, n_fft, blackman_coeff=0.42):
+    """afg_fbank_tables: win_length window values (FBANK_WINDOW_* or its name), then n_fft pairs (cos, -sin) of 2 pi j / n_fft,
+    as one float32 array.  Host only.  AfgError for arguments out of range or an n_fft the transform does not take."""
+    L_ = lib()
+    args = (_fbank_window("fbank_tables", window_type), int(win_length), int(n_fft), float(blackman_coeff))
+    need = int(L_.afg_fbank_tables(*args, None, 0))
+    if need == 0:
+        raise AfgError(f"afg: {L_.afg_last_error().decode()}")
+    out = np.zeros(need, np.float32)
+    L_.afg_fbank_tables(*args, out.ctypes.data, need)
+    return out
+
+
+def fbank_filters(samplerate, n_fft, n_mels, low_freq=20.0, high_freq=0.0):
+    """afg_fbank_filters: the float32 bank [n_mels, n_fft // 2 + 1], triangles on the mel axis (high_freq <= 0: an offset from
+    Nyquist).  Host only.  AfgError for arguments out of range."""
+    L_ = lib()
+    args = (int(samplerate), int(n_fft), int(n_mels), float(low_freq), float(high_freq))
+    need = int(L_.afg_fbank_filters(*args, None, 0))
+    if need == 0:
+        raise AfgError(f"afg: {L_.afg_last_error().decode()}")
+    out = np.zeros(need, np.float32)
+    L_.afg_fbank_filters(*args, out.ctypes.data, need)
+    return out.reshape(int(n_mels), need // int(n_mels))
+
+
+def fbank_layout(rows, params):
+    """afg_fbank_layout: fills first_tile of a MEL_ROW_DTYPE array in place (tiles of 16 frames); returns the launch's tile
+    count, 0 for parameters out of range."""
+    assert rows.dtype == MEL_ROW_DTYPE and rows.flags.c_contiguous
+    return int(lib().afg_fbank_layout(rows.ctypes.data, len(rows), C.byref(params)))
+
+
+def fbank_check_rows(rows, n_tiles, params, in_floats, table_floats, filters_floats, out_floats):
+    """afg_fbank_check_rows: what afg_fbank_hip checks before it launches, on host records.  AfgError when one fails."""
+    assert rows.dtype == MEL_ROW_DTYPE and rows.flags.c_contiguous
+    check(lib().afg_fbank_check_rows(rows.ctypes.data, len(rows), int(n_tiles), C.byref(params), int(in_floats), int(table_floats),
+                                     int(filters_floats), int(out_floats)))
+
+
+def fbank(n_rows, d_rows, n_tiles, params, d_in, in_floats, d_table, table_floats, d_filters, filters_floats, d_out, out_floats, stream=None):
+    """Enqueue the filter-bank kernel (afg_fbank_hip) on device arrays: planar float rows to [rows, out_frames, cols] (or
+    [rows, cols, out_frames] with FBANK_MEL_MAJOR), with fbank_tables' table, a dense bank and rows laid out by fbank_layout.
+    The records are checked first (the call waits for `stream` to read them): AfgError, and nothing written, when one fails."""
+    check(lib().afg_fbank_hip(int(n_rows), _ptr(d_rows), int(n_tiles), C.byref(params), _ptr(d_in), int(in_floats), _ptr(d_table),
+                              int(table_floats), _ptr(d_filters), int(filters_floats), _ptr(d_out), int(out_floats), _stream(stream)))
+
+
+_fbank_tables = {}                                            # (device, window, win_length, n_fft, blackman, rate, n_mels, low, high) -> tensors
+
+
+def _fbank_kaldi_params(who, samplerate, num_mel_bins, frame_length, frame_shift, round_to_power_of_two, snip_edges, remove_dc_offset,
+                        preemphasis_coefficient, use_power, use_log_fbank, use_energy, raw_energy, htk_compat, energy_floor, scale, layout):
+    ws, hop = int(samplerate * frame_length * 0.001), int(samplerate * frame_shift * 0.001)
+    if ws < 2 or hop < 1:
+        raise ValueError(f"{who}: frame_length {frame_length} ms and frame_shift {frame_shift} ms at {samplerate} Hz")
+    return fbank_params(ws, hop, fbank_n_fft(ws, round_to_power_of_two), num_mel_bins, snip_edges, remove_dc_offset, preemphasis_coefficient,
+                        use_power, use_log_fbank, use_energy, raw_energy, htk_compat, energy_floor, scale, layout)
+
+
+def fbank_tensor(wave, samplerate=16000, num_mel_bins=23, frame_length=25.0, frame_shift=10.0, window_type="povey", blackman_coeff=0.42,
+                 low_freq=20.0, high_freq=0.0, round_to_power_of_two=True, snip_edges=True, remove_dc_offset=True,
+                 preemphasis_coefficient=0.97, use_power=True, use_log_fbank=True, use_energy=False, raw_energy=True, htk_compat=False,
+                 energy_floor=1.0, scale=0.0, layout=FBANK_FRAMES_MAJOR, valid=None):
+    """Kaldi-compatible filter-bank features of every row of a contiguous float32 device tensor [..., n] (afg_fbank_hip, one
+    launch on the current stream; include/afg.h has the definition), with torchaudio.compliance.kaldi.fbank's argument names
+    and defaults (no dither, no VTLN, no subtract_mean).  scale 32768 turns a [-1, 1] waveform into what Kaldi reads.  The
+    result is [..., F, cols], or [..., cols, F] with FBANK_MEL_MAJOR, F the frames n samples have.  valid: None, or one sample
+    count per row (the leading axes flattened), 0 .. n: row i is then framed as a row of valid[i] samples (mirrored at its own
+    end), its F_i frames stand at the front of its slab (frames-major; with FBANK_MEL_MAJOR at a pitch of F_i frames), the
+    rest stays zero, and the call returns (tensor, frame counts).  The tables are made once per device and parameter set and
+    kept.  AfgError when a parameter or a record is refused."""
+    import torch
+    samplerate = int(samplerate)
+    prm = _fbank_kaldi_params("fbank_tensor", samplerate, num_mel_bins, frame_length, frame_shift, round_to_power_of_two, snip_edges,
+                              remove_dc_offset, preemphasis_coefficient, use_power, use_log_fbank, use_energy, raw_energy, htk_compat,
+                              energy_floor, scale, layout)
+    wt = _fbank_window("fbank_tensor", window_type)
+    fbank_check_rows(np.zeros(0, MEL_ROW_DTYPE), 0, prm, 0, 0, 0, 0)      # (the parameters: AfgError says which)
+    if not wave.is_cuda or not wave.is_contiguous() or wave.dtype != torch.float32 or wave.dim() < 1:
+        raise ValueError("fbank_tensor: a contiguous float32 device tensor [..., n]")
+    lead, length = tuple(wave.shape[:-1]), int(wave.shape[-1])
+    F = fbank_frames(prm, length)
+    if F == 0:
+        raise ValueError(f"fbank_tensor: {length} samples hold no frame of {prm.win_length} samples")
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    cols = prm.n_mels + prm.use_energy
+    shape = lead + ((F, cols) if prm.layout == FBANK_FRAMES_MAJOR else (cols, F))
+    out = (torch.zeros if valid is not None else torch.empty)(shape, dtype=torch.float32, device=wave.device)
+    rows = np.zeros(n, MEL_ROW_DTYPE)
+    rows["in_off"] = np.arange(n, dtype=np.uint64) * np.uint64(length)
+    rows["out_off"] = np.arange(n, dtype=np.uint64) * np.uint64(cols * F)
+    rows["in_frames"], rows["out_frames"] = length, F
+    if valid is not None:
+        v = np.asarray(valid.cpu() if hasattr(valid, "cpu") else valid).reshape(-1).astype(np.int64)
+        if v.size != n or (v < 0).any() or (v > length).any():
+            raise ValueError("fbank_tensor: valid holds one sample count per row, 0 .. n")
+        rows["in_frames"] = v
+        rows["out_frames"] = [fbank_frames(prm, int(c)) for c in v]
+    if n:
+        tiles = fbank_layout(rows, prm)
+        with torch.cuda.device(wave.device):
+            key = (torch.cuda.current_device(), wt, prm.win_length, prm.n_fft, float(blackman_coeff), samplerate, prm.n_mels, float(low_freq),
+                   float(high_freq))
+            if key not in _fbank_tables:
+                _fbank_tables[key] = (torch.from_numpy(fbank_tables(wt, prm.win_length, prm.n_fft, blackman_coeff)).to(wave.device),
+                                      torch.from_numpy(fbank_filters(samplerate, prm.n_fft, prm.n_mels, low_freq, high_freq).reshape(-1).copy())
+                                      .to(wave.device))
+            table, bank = _fbank_tables[key]
+            d_rows = torch.from_numpy(rows.view(np.uint8)).to(wave.device)
+            fbank(n, d_rows, tiles, prm, wave, wave.numel(), table, table.numel(), bank, bank.numel(), out, out.numel(),
+                  torch.cuda.current_stream().cuda_stream)
+    return out if valid is None else (out, rows["out_frames"].astype(np.int64))
+
+
+def batch_decode_fbank(files, frames, samplerate=16000, num_mel_bins=23, frame_length=25.0, frame_shift=10.0, window_type="povey",
+                       blackman_coeff=0.42, low_freq=20.0, high_freq=0.0, round_to_power_of_two=True, snip_edges=True, remove_dc_offset=True,
+                       preemphasis_coefficient=0.97, use_power=True, use_log_fbank=True, use_energy=False, raw_energy=True, htk_compat=False,
+                       energy_floor=1.0, scale=0.0, layout=FBANK_FRAMES_MAJOR, n_out=0, mono=True, out=None, channels=1, first_frame=None,
+                       in_channels=0, max_in_rate=0, lowpass_width=0, n_threads=0):
+    """afg_batch_decode_fbank: (tensor, meta, lengths).  The tensor [len(files), channels, n_out, cols] (or [..., cols, n_out]
+    with FBANK_MEL_MAJOR) holds the Kaldi-compatible filter-bank features of every row of batch_decode_tensor_resampled's
+    tensor of `frames` samples at `samplerate` (include/afg.h has the definition; the arguments are fbank_tensor's).  n_out 0:
+    every frame `frames` samples have.  lengths: per file, the feature frames its own resampled samples give, capped at n_out
+    (0 for a file that failed) -- what a collation masks by.  The same device and stream rules as batch_decode_tensor."""
+    frames, channels, samplerate = int(frames), int(channels), int(samplerate)
+    if frames < 1 or channels < 1 or samplerate < 1:
+        raise ValueError("batch_decode_fbank: frames, channels and samplerate must be at least 1")
+    if mono and channels != 1:
+        raise ValueError("batch_decode_fbank: a mono tensor has one channel")
+    prm = _fbank_kaldi_params("batch_decode_fbank", samplerate, num_mel_bins, frame_length, frame_shift, round_to_power_of_two, snip_edges,
+                              remove_dc_offset, preemphasis_coefficient, use_power, use_log_fbank, use_energy, raw_energy, htk_compat,
+                              energy_floor, scale, layout)
+    wt = _fbank_window("batch_decode_fbank", window_type)
+    fbank_check_rows(np.zeros(0, MEL_ROW_DTYPE), 0, prm, 0, 0, 0, 0)      # (the parameters: AfgError says which)
+    most = fbank_frames(prm, frames)
+    if most == 0:
+        raise ValueError(f"batch_decode_fbank: {frames} samples hold no frame of {prm.win_length} samples")
+    n_out = int(n_out)
+    if n_out < 0 or n_out > most:
+        raise ValueError(f"batch_decode_fbank: n_out {n_out}, but {frames} samples have {most} frames")
+    F, cols = (n_out if n_out else most), prm.n_mels + prm.use_energy
+    shape = (len(files), channels) + ((F, cols) if prm.layout == FBANK_FRAMES_MAJOR else (cols, F))
+    lengths = np.zeros(max(len(files), 1), np.uint32)
+
+    def call(ptrs, lens, n, ff, out, res):
+        opts = FbankOpts(C.sizeof(FbankOpts), int(n_threads), channels, frames, ff, samplerate, 1 if mono else 0, int(in_channels),
+                         int(max_in_rate), int(lowpass_width), n_out, prm, wt, float(low_freq), float(high_freq), float(blackman_coeff), 0)
+        return lib().afg_batch_decode_fbank(ptrs, lens, n, C.byref(opts), out.data_ptr(), lengths.ctypes.data, C.byref(res))
+
+    out, meta = _batch_tensor_call("batch_decode_fbank", files, shape, out, first_frame, call)
+    return out, meta, lengths[:len(files)].astype(np.int64)
 
 
 def pvoc_params(n_fft=400, hop=160):

@@ -635,6 +635,24 @@ int afg_mix_hip(ulong n_groups, const(afg_mix_group)* d_groups, ulong n_tiles, c
                 void* hip_stream);
 int afg_batch_decode_mixed(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_resample_opts)* opts,
                            const(afg_mix_noise)* noise, float* d_out, afg_mix_stats* stats, afg_batch_result* out_);
+// Kaldi-compatible filter-bank features: snip_edges or mirrored frames, DC removal, pre-emphasis, Povey's window, a bank on the
+// mel axis, natural log, an optional energy column (include/afg.h has the definition and the bound); rows are afg_mel_row
+enum : uint { AFG_FBANK_FRAMES_MAJOR = 0, AFG_FBANK_MEL_MAJOR = 1 }
+enum : uint { AFG_FBANK_WINDOW_POVEY = 0, AFG_FBANK_WINDOW_HAMMING = 1, AFG_FBANK_WINDOW_HANNING = 2, AFG_FBANK_WINDOW_BLACKMAN = 3, AFG_FBANK_WINDOW_RECTANGULAR = 4 }
+struct afg_fbank_params { uint win_length, hop, n_fft, n_mels, snip_edges, remove_dc, use_power, use_log, use_energy, raw_energy, htk_compat, layout; float preemph, energy_floor, scale; uint reserved; }
+struct afg_fbank_opts { uint struct_size; int n_threads; uint channels; uint frames; const(long)* first_frame; uint samplerate, mono, in_channels, max_in_rate, lowpass_width, n_out; afg_fbank_params fbank; uint window_type; double low_freq, high_freq, blackman_coeff; uint reserved; }
+uint afg_fbank_n_fft(uint win_length, uint round_pow2);
+uint afg_fbank_frames(const(afg_fbank_params)* params, uint in_frames);
+ulong afg_fbank_tables(uint window_type, uint win_length, uint n_fft, double blackman_coeff, float* out_, ulong cap);
+ulong afg_fbank_filters(uint samplerate, uint n_fft, uint n_mels, double low_freq, double high_freq, float* out_, ulong cap);
+ulong afg_fbank_layout(afg_mel_row* rows, ulong n_rows, const(afg_fbank_params)* params);
+int afg_fbank_check_rows(const(afg_mel_row)* rows, ulong n_rows, ulong n_tiles, const(afg_fbank_params)* params, ulong in_floats,
+                         ulong table_floats, ulong filters_floats, ulong out_floats);
+int afg_fbank_hip(ulong n_rows, const(afg_mel_row)* d_rows, ulong n_tiles, const(afg_fbank_params)* params, const(float)* d_in,
+                  ulong in_floats, const(float)* d_table, ulong table_floats, const(float)* d_filters, ulong filters_floats,
+                  float* d_out, ulong out_floats, void* hip_stream);
+int afg_batch_decode_fbank(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_fbank_opts)* opts, float* d_out,
+                           uint* n_frames, afg_batch_result* out_);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

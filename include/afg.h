@@ -2346,6 +2346,149 @@ typedef struct afg_mix_noise {    /* 56 bytes */
 int afg_batch_decode_mixed(const uint8_t *const *data, const size_t *length, int n_files, const afg_resample_opts *opts,
                            const afg_mix_noise *noise, float *d_out, afg_mix_stats *stats, afg_batch_result *out);
 
+/* ---- Kaldi-compatible filter-bank features (compute-fbank-feats, torchaudio.compliance.kaldi.fbank) -------------------------
+ * The other family of speech front-ends beside the centred, reflect-padded, Hann-windowed log10 mel stage above: frames with
+ * snip_edges or mirrored with the edge repeated, the DC offset removed per frame, pre-emphasis per frame, Povey's window, zero
+ * padding to a power of two, triangles drawn on the mel axis, a natural log over a float32-epsilon floor, an optional
+ * log-energy column, frames-major output.  The reference has no such stage: the definition below is this library's own, and
+ * tests/fbank_model.py states it again in float64.  There is no dither and no VTLN warp, and subtract_mean (a mean over the
+ * frames of an utterance) is the caller's: one tensor op over the valid frames of the result.
+ *
+ * Parameters (afg_fbank_params), uniform over a launch: win_length ws 2 .. 2048; hop 1 .. 65535 (it may exceed ws); n_fft with
+ * ws <= n_fft <= 2048, and one the FFT mel path takes (16 .. 2048, prime factors 2, 3 and 5 only), any other being
+ * AFG_ERR_UNSUPPORTED -- afg_fbank_n_fft(ws, round_pow2) gives Kaldi's choice, the next power of two >= ws, or ws itself;
+ * n_mels 1 .. 256; snip_edges, remove_dc, use_power, use_log, use_energy, raw_energy, htk_compat each 0 or 1; preemph a finite
+ * float in [0, 1]; energy_floor a finite float >= 0; scale a finite float > 0, 0 meaning 1 (Kaldi reads 16-bit samples as
+ * integers: 32768 turns a [-1, 1] waveform into what Kaldi sees); layout AFG_FBANK_FRAMES_MAJOR (Kaldi's [frames, cols]) or
+ * AFG_FBANK_MEL_MAJOR ([cols, frames], which afg_cepstra_hip consumes); reserved 0.  cols = n_mels + use_energy,
+ * n_bins = n_fft / 2 + 1.
+ *
+ * Frames of a row of N samples (afg_fbank_frames): with snip_edges 0 when N < ws, else 1 + (N - ws) / hop; without,
+ * (N + hop / 2) / hop, which is 0 when N is 0.  A record asks for out_frames <= that.
+ * Sample j of frame f is x[idx(f * hop + j - pad)], pad = 0 with snip_edges and ws / 2 - hop / 2 (integer divisions; it may
+ * be negative) without.  An index outside [0, N) is mirrored with the edge repeated until it lies inside: i < 0 -> -1 - i,
+ * i >= N -> 2 N - 1 - i (Kaldi's loop; the extension has period 2 N).  It equals torchaudio's flipped-copy padding wherever
+ * that is defined.
+ *
+ * Per frame.  s_j = float32(x_i * scale) is the one float32 rounding the definition starts from; from there, in float64:
+ *   mu = mean of the ws values s_j and d_j = s_j - mu (without remove_dc: d_j = s_j);
+ *   e_0 = d_0 - c d_0, e_j = d_j - c d_(j-1), c = preemph;   z_j = e_j w_j for j < ws, 0 up to n_fft;
+ *   X_k = DFT of z, k = 0 .. n_fft / 2;   p_k = |X_k|^2, or |X_k| without use_power;   mel_m = sum_k W[m][k] p_k;
+ *   the output is mel_m, or with use_log logf(fmaxf(mel_m, 2^-23)).  fmaxf: a NaN takes the floor, this library's convention
+ *   (torch.max would hand the NaN on).
+ * Energy column (use_energy): En = sum_j d_j^2 with raw_energy, else sum_j z_j^2; its value is logf(fmaxf(En, 2^-23)), raised
+ * to logf(energy_floor) when energy_floor > 0.  It is column 0, the mels behind it, or the last column with htk_compat.
+ * Output: record r's frame f, column c at out_off + f * cols + c (frames-major) or out_off + c * out_frames + f (mel-major).
+ *
+ * Tables, host only, computed in double and rounded once to float32.  afg_fbank_tables(window_type, ws, n_fft,
+ * blackman_coeff, out, cap) returns ws + 2 * n_fft and with cap >= that fills ws window values, then the n_fft twiddle pairs
+ * exactly as afg_mel_fft_tables gives them.  Windows, all symmetric, a = 2 pi j / (ws - 1): AFG_FBANK_WINDOW_POVEY
+ * (0.5 - 0.5 cos a)^0.85, _HAMMING 0.54 - 0.46 cos a, _HANNING 0.5 - 0.5 cos a, _BLACKMAN b - 0.5 cos a + (0.5 - b) cos 2a
+ * with b = blackman_coeff, _RECTANGULAR 1.  Returns 0 with afg_last_error set for sizes out of range, an unknown window, a
+ * blackman_coeff that is not finite, or an n_fft the transform does not take.
+ * afg_fbank_filters(samplerate, n_fft, n_mels, low_freq, high_freq, out, cap) returns n_mels * n_bins and with cap >= that
+ * fills a dense bank out[m * n_bins + k]: mel(f) = 1127 ln(1 + f / 700); high_freq <= 0 is an offset from Nyquist; n_mels + 2
+ * points equally spaced in mel from mel(low_freq) to mel(high_freq), left, centre, right of filter m being points m, m + 1,
+ * m + 2; bin k lies at mel_k = mel(k * samplerate / n_fft);
+ *   W[m][k] = max(0, min((mel_k - left) / (centre - left), (right - mel_k) / (right - centre))),
+ * and the column of the Nyquist bin (k = n_fft / 2 of an even n_fft) is +0.0f.  Returns 0 with afg_last_error set for
+ * samplerate 0, sizes out of range, or anything but 0 <= low_freq < high_freq <= samplerate / 2.  The kernel entry takes any
+ * dense float32 [n_mels, n_bins] bank of the caller's own instead.
+ *
+ * What the device may do, and the bound.  Only the orders of summation are free.  The frame's sum, the mean and s_j - mu are
+ * formed in float64 and d_j is rounded once to float32 -- required: a waveform at Kaldi's scale with a DC offset loses the
+ * signal in a float32 mean.  Everything after that is float32.  u = 2^-24; A_f = sum_j w_j (|d_j| + c |d_(j-1)|) in float64,
+ * d_(-1) = d_0; B_k = 8 ceil(log2 n_fft) + 12; then |re - re64| and |im - im64| are at most E_f = B_k u A_f.  Derivation: the
+ * value that enters the transform is z_j = fl(fl(d_j - fl(c d_(j-1))) w_j) with d_j itself a rounded value; each of the four
+ * roundings (d, the product, the difference, the window product) moves z_j by at most u w_j (|d_j| + c |d_(j-1)|) to first
+ * order, and the transform hands an input error on with gain at most 1 per bin, so they cost 4 u A_f together.  The FFT mel
+ * path's B = 8 ceil(log2 n_fft) + 8 holds for the transform of these z_j (8 per binary level; its + 8 covers the window
+ * product -- counted again here, as margin -- the split pass and second-order terms), with its A_f = sum |z_j| <= this A_f.
+ * With p_hi = (|re64| + E)^2 + (|im64| + E)^2 and p_lo = max(|re64| - E, 0)^2 + max(|im64| - E, 0)^2 as in the STFT stage, and
+ * a bank without negative weights:
+ *   mel lies in [(1 - (n_bins + 4) u) sum_k W p_lo, (1 + (n_bins + 4) u) sum_k W p_hi];
+ *   without use_power, p lies within 2 float32 ulp of the square roots of [(1 - 4u) p_lo, (1 + 4u) p_hi], and mel in
+ *   [(1 - (n_bins + 4) u) sum_k W m_lo, (1 + (n_bins + 4) u) sum_k W m_hi] of those;
+ *   with use_log the output lies within 3 float32 ulp of the natural log of the interval after the floor.
+ * Energy: raw, En lies within a relative (ws + 12) u of the float64 value (ws products and adds, and the rounding of d, which
+ * moves d^2 by 2 u d^2; the rest is margin); windowed, En lies in (1 -+ (ws + 4) u) sum_j (|z_j| -+ eps_j)^2 with
+ * eps_j = 4 u w_j (|d_j| + c |d_(j-1)|), the lower end clamped at 0 per term.  Its log is within 3 ulp as above.
+ * Locality.  The same row gives the same bits wherever it stands in a launch.  A NaN sample reaches exactly the frames whose
+ * ws samples include it, through the mirror as well, and there every column: NaN, or the floor's log with use_log (the
+ * energy column always).  A row with 0 frames has no tiles and nothing of it is read or written.
+ *
+ * afg_fbank_layout, afg_fbank_check_rows, afg_fbank_hip: as afg_mel_fft_layout, afg_mel_fft_check_rows and
+ * afg_melspec_fft_hip, over the same afg_mel_row records; a tile is 16 frames of one row.  afg_fbank_check_rows is host
+ * only and needs no device: parameters in range (AFG_ERR_UNSUPPORTED for the n_fft, AFG_ERR_INVALID otherwise); table_floats
+ * and filters_floats at least what the tables and the bank need; first_tile and n_tiles as afg_fbank_layout gives them; every
+ * row's in_frames floats inside [0, in_floats); out_frames <= afg_fbank_frames; the record's cols * out_frames floats inside
+ * [0, out_floats).  afg_fbank_hip fetches d_rows on hip_stream, makes the same checks and on anything but a pass writes
+ * nothing.  The kernel writes exactly cols * out_frames floats per record and reads no input float outside the record's row. */
+#define AFG_FBANK_FRAMES_MAJOR 0
+#define AFG_FBANK_MEL_MAJOR    1
+#define AFG_FBANK_WINDOW_POVEY       0
+#define AFG_FBANK_WINDOW_HAMMING     1
+#define AFG_FBANK_WINDOW_HANNING     2
+#define AFG_FBANK_WINDOW_BLACKMAN    3
+#define AFG_FBANK_WINDOW_RECTANGULAR 4
+typedef struct afg_fbank_params {  /* 64 bytes */
+    uint32_t win_length, hop, n_fft, n_mels;
+    uint32_t snip_edges, remove_dc, use_power, use_log;
+    uint32_t use_energy, raw_energy, htk_compat, layout;
+    float    preemph, energy_floor, scale;
+    uint32_t reserved;             /* 0 */
+} afg_fbank_params;
+/* the next power of two >= win_length (round_pow2 != 0) or win_length itself; 0 with afg_last_error set for win_length
+ * outside 2 .. 2048 */
+uint32_t afg_fbank_n_fft(uint32_t win_length, uint32_t round_pow2);
+/* the frames of a row of in_frames samples; 0 for params out of range (afg_last_error set) */
+uint32_t afg_fbank_frames(const afg_fbank_params *params, uint32_t in_frames);
+uint64_t afg_fbank_tables(uint32_t window_type, uint32_t win_length, uint32_t n_fft, double blackman_coeff, float *out, uint64_t cap);
+uint64_t afg_fbank_filters(uint32_t samplerate, uint32_t n_fft, uint32_t n_mels, double low_freq, double high_freq, float *out, uint64_t cap);
+uint64_t afg_fbank_layout(afg_mel_row *rows, uint64_t n_rows, const afg_fbank_params *params);
+int afg_fbank_check_rows(const afg_mel_row *rows, uint64_t n_rows, uint64_t n_tiles, const afg_fbank_params *params, uint64_t in_floats,
+                         uint64_t table_floats, uint64_t filters_floats, uint64_t out_floats);
+int afg_fbank_hip(uint64_t n_rows, const afg_mel_row *d_rows, uint64_t n_tiles, const afg_fbank_params *params, const float *d_in,
+                  uint64_t in_floats, const float *d_table, uint64_t table_floats, const float *d_filters, uint64_t filters_floats,
+                  float *d_out, uint64_t out_floats, void *hip_stream);
+
+/* afg_batch_decode_resampled followed by afg_fbank_hip: d_out is n_files * channels * n_out * cols floats on the current
+ * device -- [files, channels, n_out, cols], or [files, channels, cols, n_out] with AFG_FBANK_MEL_MAJOR -- and slab [i, k] is
+ * the definition above applied to row [i, k] of the tensor afg_batch_decode_resampled makes of the same list with the leading
+ * fields of the options.  n_out == 0 means afg_fbank_frames of T; otherwise n_out <= that.  n_frames (host, n_files entries,
+ * may be NULL) receives per file the feature frames its own resampled samples give -- afg_fbank_frames of the valid length
+ * afg_batch_decode_resampled_norm's groups use -- capped at n_out, 0 for a file that failed: what a collation masks by.  In
+ * every other respect it is afg_batch_decode_mel: the scratch is pooled under afg_dev_option("mel_scratch_bytes") with
+ * sublists of at least one file, the tables and the bank are made once per parameter set -- (window_type, win_length, n_fft,
+ * blackman_coeff) and (samplerate, n_fft, n_mels, low_freq, high_freq) -- and kept for the life of the process, without a
+ * bound: a caller that sweeps the frequencies builds its banks with afg_fbank_filters and calls afg_fbank_hip.  A file that failed or was
+ * refused keeps its status and message and gets the all-zero row's slab, items[i].pcm points at the file's slab (NULL when
+ * it failed or was refused), n_files == 0 is AFG_OK and touches nothing.  Checked before any device call, afg_last_error set:
+ * everything afg_batch_decode_resampled checks, a struct_size below sizeof(afg_fbank_opts), a non-zero `reserved`, the
+ * parameters (AFG_ERR_UNSUPPORTED for the n_fft), the window and the bank's arguments, T without a frame, n_out above the
+ * frames of T. */
+typedef struct afg_fbank_opts {
+    uint32_t         struct_size;   /* sizeof(afg_fbank_opts) */
+    int              n_threads;     /* from here to lowpass_width: as afg_resample_opts */
+    uint32_t         channels;
+    uint32_t         frames;        /* T, samples at `samplerate` */
+    const int64_t   *first_frame;
+    uint32_t         samplerate;
+    uint32_t         mono;
+    uint32_t         in_channels;
+    uint32_t         max_in_rate;
+    uint32_t         lowpass_width;
+    uint32_t         n_out;         /* feature frames per slab; 0 means afg_fbank_frames of T */
+    afg_fbank_params fbank;
+    uint32_t         window_type;   /* AFG_FBANK_WINDOW_* */
+    double           low_freq;      /* Hz */
+    double           high_freq;     /* Hz; <= 0: an offset from samplerate / 2 */
+    double           blackman_coeff;
+    uint32_t         reserved;      /* 0 */
+} afg_fbank_opts;
+int afg_batch_decode_fbank(const uint8_t *const *data, const size_t *length, int n_files, const afg_fbank_opts *opts, float *d_out,
+                           uint32_t *n_frames, afg_batch_result *out);
+
 #ifdef __cplusplus
 }
 #endif
