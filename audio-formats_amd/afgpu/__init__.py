@@ -115,6 +115,7 @@ FBANK_WINDOW_POVEY, FBANK_WINDOW_HAMMING, FBANK_WINDOW_HANNING, FBANK_WINDOW_BLA
 FBANK_WINDOW_NAMES = {"povey": FBANK_WINDOW_POVEY, "hamming": FBANK_WINDOW_HAMMING, "hanning": FBANK_WINDOW_HANNING,
                       "blackman": FBANK_WINDOW_BLACKMAN, "rectangular": FBANK_WINDOW_RECTANGULAR}
 FBANK_TILE = 16                                  # frames of one row per tile of afg_fbank_hip
+YIN_TILE, YIN_CHUNK = 4, 16                      # frames of one row per tile of afg_yin_hip; lags per chunk of its cumulative mean
 
 # every symbol include/afg.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -165,6 +166,7 @@ ABI_SYMBOLS = [
     "afg_mix_ratio", "afg_mix_layout", "afg_mix_check_groups", "afg_mix_hip", "afg_batch_decode_mixed",
     "afg_fbank_n_fft", "afg_fbank_frames", "afg_fbank_tables", "afg_fbank_filters", "afg_fbank_layout", "afg_fbank_check_rows", "afg_fbank_hip",
     "afg_batch_decode_fbank",
+    "afg_yin_lags", "afg_yin_frames", "afg_yin_layout", "afg_yin_hip", "afg_batch_decode_pitch",
 ]
 
 
@@ -360,6 +362,18 @@ class FbankOpts(C.Structure):
     arguments, the Blackman coefficient and a reserved 0."""
     _fields_ = ResampleOpts._fields_ + [("n_out", C.c_uint32), ("fbank", FbankParams), ("window_type", C.c_uint32), ("low_freq", C.c_double),
                                         ("high_freq", C.c_double), ("blackman_coeff", C.c_double), ("reserved", C.c_uint32)]
+
+
+class YinParams(C.Structure):
+    """afg_yin_params (afg_yin_hip)."""
+    _fields_ = [("frame_length", C.c_uint32), ("win_length", C.c_uint32), ("hop", C.c_uint32), ("tau_min", C.c_uint32), ("tau_max", C.c_uint32),
+                ("center", C.c_uint32), ("pad_mode", C.c_uint32), ("threshold", C.c_float), ("samplerate", C.c_double),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class PitchOpts(C.Structure):
+    """afg_pitch_opts (afg_batch_decode_pitch): afg_resample_opts' fields, n_out, the parameters and a reserved 0."""
+    _fields_ = ResampleOpts._fields_ + [("n_out", C.c_uint32), ("yin", YinParams), ("reserved", C.c_uint32)]
 
 
 class NormGroup(C.Structure):
@@ -824,6 +838,13 @@ def lib():
     L.afg_fbank_check_rows.argtypes = [vp, u64, u64, C.POINTER(FbankParams), u64, u64, u64, u64]
     L.afg_fbank_hip.argtypes = [u64, vp, u64, C.POINTER(FbankParams), vp, u64, vp, u64, vp, u64, vp, u64, vp]
     L.afg_batch_decode_fbank.argtypes = [vp, vp, C.c_int, C.POINTER(FbankOpts), vp, vp, C.POINTER(BatchResult)]
+    L.afg_yin_lags.argtypes = [C.c_double, C.c_double, C.c_double, u32, u32, C.POINTER(u32), C.POINTER(u32)]
+    L.afg_yin_frames.argtypes = [C.POINTER(YinParams), u32]
+    L.afg_yin_frames.restype = u32
+    L.afg_yin_layout.argtypes = [vp, u64, C.POINTER(YinParams)]
+    L.afg_yin_layout.restype = u64
+    L.afg_yin_hip.argtypes = [u64, vp, u64, C.POINTER(YinParams), vp, u64, vp, u64, vp]
+    L.afg_batch_decode_pitch.argtypes = [vp, vp, C.c_int, C.POINTER(PitchOpts), vp, vp, C.POINTER(BatchResult)]
     _lib = L
     _sync_dev_options(L)
     return L
@@ -3102,6 +3123,133 @@ def batch_decode_fbank(files, frames, samplerate=16000, num_mel_bins=23, frame_l
         return lib().afg_batch_decode_fbank(ptrs, lens, n, C.byref(opts), out.data_ptr(), lengths.ctypes.data, C.byref(res))
 
     out, meta = _batch_tensor_call("batch_decode_fbank", files, shape, out, first_frame, call)
+    return out, meta, lengths[:len(files)].astype(np.int64)
+
+
+def yin_lags(samplerate, fmin, fmax, frame_length, win_length):
+    """afg_yin_lags: librosa's lag range (tau_min, tau_max) = (floor(sr / fmax), min(ceil(sr / fmin), frame_length -
+    win_length - 1)).  AfgError for an empty range or arguments out of range."""
+    lo, hi = C.c_uint32(0), C.c_uint32(0)
+    check(lib().afg_yin_lags(float(samplerate), float(fmin), float(fmax), int(frame_length), int(win_length), C.byref(lo), C.byref(hi)))
+    return int(lo.value), int(hi.value)
+
+
+def yin_params(samplerate, frame_length=2048, win_length=None, hop=None, tau_min=None, tau_max=None, threshold=0.1, center=True,
+               pad_mode=MEL_PAD_ZERO, fmin=None, fmax=None):
+    """afg_yin_params with librosa.yin's defaults (win_length None: frame_length // 2; hop None: frame_length // 4).  The lag
+    range is given as it is (tau_min, tau_max) or drawn from fmin and fmax by yin_lags."""
+    frame_length = int(frame_length)
+    win_length = frame_length // 2 if win_length is None else int(win_length)
+    hop = frame_length // 4 if hop is None else int(hop)
+    if tau_min is None or tau_max is None:
+        if fmin is None or fmax is None:
+            raise ValueError("yin_params: tau_min and tau_max, or fmin and fmax")
+        tau_min, tau_max = yin_lags(samplerate, fmin, fmax, frame_length, win_length)
+    return YinParams(frame_length, win_length, hop, int(tau_min), int(tau_max), 1 if center else 0, int(pad_mode), float(threshold),
+                     float(samplerate), (C.c_uint32 * 2)(0, 0))
+
+
+def yin_frames(params, in_frames):
+    """afg_yin_frames: the frames a row of in_frames samples has (0 also for parameters out of range)."""
+    return int(lib().afg_yin_frames(C.byref(params), int(in_frames)))
+
+
+def yin_layout(rows, params):
+    """afg_yin_layout: fills first_tile of a MEL_ROW_DTYPE array in place (tiles of YIN_TILE frames); returns the launch's tile
+    count, 0 for parameters out of range."""
+    assert rows.dtype == MEL_ROW_DTYPE and rows.flags.c_contiguous
+    return int(lib().afg_yin_layout(rows.ctypes.data, len(rows), C.byref(params)))
+
+
+def yin(n_rows, d_rows, n_tiles, params, d_in, in_floats, d_out, out_floats, stream=None):
+    """Enqueue the YIN kernel (afg_yin_hip) on device arrays: planar float rows to slabs [2, out_frames] -- f0 in Hz, then
+    d' at the chosen lag (voiced iff below the threshold) -- with rows laid out by yin_layout.  The records are checked first
+    (the call waits for `stream` to read them): AfgError, and nothing written, when one fails."""
+    check(lib().afg_yin_hip(int(n_rows), _ptr(d_rows), int(n_tiles), C.byref(params), _ptr(d_in), int(in_floats), _ptr(d_out), int(out_floats),
+                            _stream(stream)))
+
+
+def _yin_check(params):
+    check(lib().afg_yin_hip(0, None, 0, C.byref(params), None, 0, None, 0, None))      # (the parameters: AfgError says which)
+
+
+def yin_tensor(x, samplerate, fmin, fmax, frame_length=2048, win_length=None, hop=None, threshold=0.1, center=True, pad_mode=MEL_PAD_ZERO,
+               valid=None):
+    """The YIN pitch of every row of a contiguous float32 device tensor [..., n] (afg_yin_hip, one launch on the current
+    stream; include/afg.h has the definition), with librosa.yin's argument names and defaults, except that pad_mode defaults to
+    zeros (librosa's np.pad default is "constant").  The result is [..., 2, F], F the frames n samples have: plane 0 the f0 in
+    Hz, plane 1 d' at the chosen lag; a frame is voiced iff plane 1 < threshold.  valid: None, or one sample count per row (the
+    leading axes flattened), 0 .. n: row i is then framed as a row of valid[i] samples (padded at its own end), its F_i frames
+    stand at the front of both planes, the rest is zero, and the call returns (tensor, frame counts).  AfgError when a
+    parameter or a record is refused."""
+    import torch
+    prm = yin_params(samplerate, frame_length, win_length, hop, threshold=threshold, center=center, pad_mode=pad_mode, fmin=fmin, fmax=fmax)
+    _yin_check(prm)
+    if not x.is_cuda or not x.is_contiguous() or x.dtype != torch.float32 or x.dim() < 1:
+        raise ValueError("yin_tensor: a contiguous float32 device tensor [..., n]")
+    lead, length = tuple(x.shape[:-1]), int(x.shape[-1])
+    F = yin_frames(prm, length)
+    if F == 0:
+        raise ValueError(f"yin_tensor: {length} samples hold no frame of {prm.frame_length} samples")
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    out = torch.empty((n, 2, F), dtype=torch.float32, device=x.device)
+    rows = np.zeros(n, MEL_ROW_DTYPE)
+    rows["in_off"] = np.arange(n, dtype=np.uint64) * np.uint64(length)
+    rows["out_off"] = np.arange(n, dtype=np.uint64) * np.uint64(2 * F)
+    rows["in_frames"], rows["out_frames"] = length, F
+    if valid is not None:
+        v = np.asarray(valid.cpu() if hasattr(valid, "cpu") else valid).reshape(-1).astype(np.int64)
+        if v.size != n or (v < 0).any() or (v > length).any():
+            raise ValueError("yin_tensor: valid holds one sample count per row, 0 .. n")
+        pad = prm.frame_length // 2 if prm.center else 0
+        rows["in_frames"] = v
+        rows["out_frames"] = [0 if c == 0 or (prm.pad_mode == MEL_PAD_REFLECT and c <= pad) else yin_frames(prm, int(c)) for c in v]
+        out.zero_()                                          # the kernel writes slabs [2, F_i]; they are spread to [2, F] below
+    if n:
+        tiles = yin_layout(rows, prm)
+        with torch.cuda.device(x.device):
+            d_rows = torch.from_numpy(rows.view(np.uint8)).to(x.device)
+            yin(n, d_rows, tiles, prm, x, x.numel(), out, out.numel(), torch.cuda.current_stream().cuda_stream)
+        if valid is not None:
+            Fi = torch.from_numpy(rows["out_frames"].astype(np.int64)).to(x.device)
+            f = torch.arange(F, device=x.device)
+            at = (torch.arange(2, device=x.device)[None, :, None] * Fi[:, None, None] + f[None, None, :]).clamp_(max=2 * F - 1)
+            own = (f[None, None, :] < Fi[:, None, None]).expand(n, 2, F)
+            out = torch.where(own, out.reshape(n, 2 * F).gather(1, at.reshape(n, 2 * F)).reshape(n, 2, F), torch.zeros((), device=x.device))
+    out = out.reshape(lead + (2, F))
+    return out if valid is None else (out, rows["out_frames"].astype(np.int64))
+
+
+def batch_decode_pitch(files, frames, samplerate, fmin, fmax, frame_length=2048, win_length=None, hop=None, threshold=0.1, center=True,
+                       pad_mode=MEL_PAD_ZERO, n_out=0, mono=True, out=None, channels=1, first_frame=None, in_channels=0, max_in_rate=0,
+                       lowpass_width=0, n_threads=0):
+    """afg_batch_decode_pitch: (tensor, meta, lengths).  The tensor [len(files), channels, 2, n_out] holds the YIN pitch (plane
+    0: f0 in Hz, plane 1: d' at the chosen lag) of every row of batch_decode_tensor_resampled's tensor of `frames` samples at
+    `samplerate` (include/afg.h has the definition; the arguments are yin_tensor's).  n_out 0: every frame `frames` samples
+    have.  lengths: per file, the frames its own resampled samples give, capped at n_out (0 for a file that failed); the frames
+    past them are zero in both planes.  The same device and stream rules as batch_decode_tensor."""
+    frames, channels, samplerate = int(frames), int(channels), int(samplerate)
+    if frames < 1 or channels < 1 or samplerate < 1:
+        raise ValueError("batch_decode_pitch: frames, channels and samplerate must be at least 1")
+    if mono and channels != 1:
+        raise ValueError("batch_decode_pitch: a mono tensor has one channel")
+    prm = yin_params(samplerate, frame_length, win_length, hop, threshold=threshold, center=center, pad_mode=pad_mode, fmin=fmin, fmax=fmax)
+    _yin_check(prm)
+    most = yin_frames(prm, frames)
+    if most == 0:
+        raise ValueError(f"batch_decode_pitch: {frames} samples hold no frame of {prm.frame_length} samples")
+    n_out = int(n_out)
+    if n_out < 0 or n_out > most:
+        raise ValueError(f"batch_decode_pitch: n_out {n_out}, but {frames} samples have {most} frames")
+    F = n_out if n_out else most
+    lengths = np.zeros(max(len(files), 1), np.uint32)
+
+    def call(ptrs, lens, n, ff, out, res):
+        opts = PitchOpts(C.sizeof(PitchOpts), int(n_threads), channels, frames, ff, samplerate, 1 if mono else 0, int(in_channels),
+                         int(max_in_rate), int(lowpass_width), n_out, prm, 0)
+        return lib().afg_batch_decode_pitch(ptrs, lens, n, C.byref(opts), out.data_ptr(), lengths.ctypes.data, C.byref(res))
+
+    out, meta = _batch_tensor_call("batch_decode_pitch", files, (len(files), channels, 2, F), out, first_frame, call)
     return out, meta, lengths[:len(files)].astype(np.int64)
 
 

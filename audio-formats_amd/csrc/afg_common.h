@@ -97,6 +97,12 @@ int fbank_launch(const afg_mel_row *h_rows, uint64_t n_rows, const afg_mel_row *
                  const float *d_in, uint64_t in_floats, const float *d_table, uint64_t table_floats, const float *d_filters,
                  uint64_t filters_floats, float *d_out, uint64_t out_floats, hipStream_t stream);
 
+// afg_yin_hip likewise (yin.hip), the check of its parameters alone (who: the caller's prefix) and a row's frames
+int yin_check_params(const afg_yin_params *params, const char *who);
+uint32_t yin_frames_of(const afg_yin_params &params, uint32_t in_frames);
+int yin_launch(const afg_mel_row *h_rows, uint64_t n_rows, const afg_mel_row *d_rows, uint64_t n_tiles, const afg_yin_params *params,
+               const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats, hipStream_t stream);
+
 // afg_normalize_hip likewise (normalize.hip)
 int normalize_launch(const afg_norm_group *h_groups, uint64_t n_groups, const afg_norm_group *d_groups, uint64_t n_tiles,
                      const afg_norm_params *params, const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats,

@@ -653,6 +653,17 @@ int afg_fbank_hip(ulong n_rows, const(afg_mel_row)* d_rows, ulong n_tiles, const
                   float* d_out, ulong out_floats, void* hip_stream);
 int afg_batch_decode_fbank(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_fbank_opts)* opts, float* d_out,
                            uint* n_frames, afg_batch_result* out_);
+// YIN pitch per frame: f0 and d' at the chosen lag, two planes per row (include/afg.h has the definition); rows are afg_mel_row
+enum : uint { AFG_YIN_CHUNK = 16, AFG_YIN_TILE = 4 }
+struct afg_yin_params { uint frame_length, win_length, hop, tau_min, tau_max, center, pad_mode; float threshold; double samplerate; uint[2] reserved; }
+struct afg_pitch_opts { uint struct_size; int n_threads; uint channels; uint frames; const(long)* first_frame; uint samplerate, mono, in_channels, max_in_rate, lowpass_width, n_out; afg_yin_params yin; uint reserved; }
+int afg_yin_lags(double samplerate, double fmin, double fmax, uint frame_length, uint win_length, uint* tau_min, uint* tau_max);
+uint afg_yin_frames(const(afg_yin_params)* params, uint in_frames);
+ulong afg_yin_layout(afg_mel_row* rows, ulong n_rows, const(afg_yin_params)* params);
+int afg_yin_hip(ulong n_rows, const(afg_mel_row)* d_rows, ulong n_tiles, const(afg_yin_params)* params, const(float)* d_in,
+                ulong in_floats, float* d_out, ulong out_floats, void* hip_stream);
+int afg_batch_decode_pitch(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_pitch_opts)* opts, float* d_out,
+                           uint* n_frames, afg_batch_result* out_);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

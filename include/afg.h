@@ -2489,6 +2489,102 @@ typedef struct afg_fbank_opts {
 int afg_batch_decode_fbank(const uint8_t *const *data, const size_t *length, int n_files, const afg_fbank_opts *opts, float *d_out,
                            uint32_t *n_frames, afg_batch_result *out);
 
+/* ---- Pitch tracking: the YIN fundamental frequency per frame (de Cheveigne & Kawahara 2002; the algorithm of librosa.yin) ----
+ * The f0 contour that TTS, voice-conversion and "fbank + pitch" front ends want, behind the tensor at one sample rate.  The
+ * reference has no such stage: the definition below is this library's own, every step in a fixed arithmetic order, so that
+ * the device result is bit for bit what tests/yin_model.py restates in numpy, decisions included.
+ *
+ * Parameters of a call (afg_yin_params, 48 bytes), uniform over its rows: frame_length N 4 .. 4096; win_length W 1 .. N - 2;
+ * hop >= 1 (it may exceed N); tau_min and tau_max with 1 <= tau_min <= tau_max <= N - W - 1; center 0 or 1; pad_mode
+ * AFG_MEL_PAD_REFLECT or AFG_MEL_PAD_ZERO; threshold a finite float >= 0; samplerate a finite double > 0; reserved 0.
+ * afg_yin_lags(samplerate, fmin, fmax, N, W, &tau_min, &tau_max) gives librosa's choice, tau_min = floor(samplerate / fmax)
+ * and tau_max = min(ceil(samplerate / fmin), N - W - 1), and refuses (AFG_ERR_INVALID, afg_last_error set, nothing stored)
+ * sizes out of range, anything but finite 0 < fmin < fmax and a finite samplerate > 0, and an empty range: tau_min < 1 or
+ * tau_min > tau_max.
+ *
+ * Framing is the mel stage's: sample n of frame f is x[idx(f * hop + n - pad)], pad = center ? N / 2 : 0; an index outside
+ * [0, in_frames) is reflected without repeating the edge or reads +0.0f, according to pad_mode; reflect needs in_frames > pad,
+ * and a record with output that breaks this is refused before the launch.  The row has afg_mel_frames' count with n_fft = N:
+ * 1 + (in_frames + 2 pad - N) / hop frames, 0 when the numerator is negative, 2^32 - 1 at the most (afg_yin_frames).  A frame reads only its
+ * samples 0 .. W - 1 + tau_max.
+ *
+ * Per frame, with x_n its samples:
+ *   1  difference.  For tau = 1 .. tau_max, d(tau) is the chain over j = 0 .. W - 1, in that order, from +0.0f, of
+ *      fmaf(e, e, acc) with e = x_j - x_(j + tau) rounded to float32: one fmaf per term, nothing wider, no reassociation.
+ *   2  cumulative mean, in float64, in chunks of AFG_YIN_CHUNK = 16 lags: c = (tau - 1) / 16; p(tau) is the sequential
+ *      float64 sum of (double)d over the lags of chunk c up to and including tau; B_0 = +0.0, B_(c+1) = B_c + p(last lag of
+ *      chunk c); s(tau) = B_c + p(tau).  d'(tau) = 1.0f when s(tau) == 0, otherwise float32((double)d(tau) * (double)tau /
+ *      s(tau)): the product is exact, there is one IEEE division and one rounding to float32.
+ *   3  choice.  Over tau in [tau_min, tau_max], trough(tau) is: for tau_min < tau < tau_max, d'(tau) < d'(tau - 1) and
+ *      d'(tau) <= d'(tau + 1); for tau = tau_min, d'(tau_min) < d'(tau_min + 1), and false when tau_min == tau_max; for
+ *      tau = tau_max > tau_min, false.  tau* is the smallest tau with trough(tau) and d'(tau) < threshold; if there is
+ *      none, the smallest tau that attains the minimum of d' over the range.
+ *   4  refinement, in float64 from the float32 values: with a = d'(tau* - 1), b = d'(tau*), c = d'(tau* + 1),
+ *      A = ((double)c + (double)a) - 2.0 * (double)b, B = ((double)c - (double)a) * 0.5, shift = |B| < |A| ? -B / A : 0;
+ *      shift = 0 when tau* is tau_min or tau_max.  f0 = float32(samplerate / ((double)tau* + shift)).
+ *   5  non-finite input.  If any d'(tau), tau = 1 .. tau_max, is a NaN, both outputs of the frame are the word 0x7fc00000.
+ * A silent or constant frame needs no case: every d' is 1.0f, so it delivers f0 = samplerate / tau_min and d' = 1.0f.  A
+ * frame is voiced iff its plane 1 is below the threshold.
+ * Output per record, two planes of out_frames floats, frames contiguous: f0 of frame f at out_off + f, d'(tau*) at
+ * out_off + out_frames + f.
+ *
+ * Records are afg_mel_row; a record's slab is 2 * out_frames floats.  afg_yin_layout gives every row its tiles (first_tile)
+ * and returns the launch's tile count, 0 with afg_last_error set for params out of range; a tile is AFG_YIN_TILE = 4
+ * consecutive frames of one record.  afg_yin_hip fetches d_rows on hip_stream and checks the parameters and every record
+ * before the launch: first_tile and n_tiles as afg_yin_layout gives them; every row's in_frames floats inside
+ * [0, in_floats); out_frames <= afg_yin_frames; reflect with output only with in_frames > pad; the record's 2 * out_frames
+ * floats inside [0, out_floats).  On a failed check it returns AFG_ERR_INVALID with afg_last_error set and writes nothing.
+ * The kernel writes exactly 2 * out_frames floats per record and reads no input float outside the record's row.  n_rows == 0
+ * is AFG_OK.  Locality: the same row gives the same bits wherever it stands, and a NaN sample reaches exactly the frames
+ * whose samples 0 .. W - 1 + tau_max include it. */
+#define AFG_YIN_CHUNK 16
+#define AFG_YIN_TILE  4
+typedef struct afg_yin_params {    /* 48 bytes */
+    uint32_t frame_length, win_length, hop;
+    uint32_t tau_min, tau_max;
+    uint32_t center, pad_mode;     /* AFG_MEL_PAD_* */
+    float    threshold;
+    double   samplerate;           /* Hz, of the rows */
+    uint32_t reserved[2];          /* 0 */
+} afg_yin_params;
+int afg_yin_lags(double samplerate, double fmin, double fmax, uint32_t frame_length, uint32_t win_length, uint32_t *tau_min, uint32_t *tau_max);
+/* the frames of a row of in_frames samples; 0 for params out of range (afg_last_error set) */
+uint32_t afg_yin_frames(const afg_yin_params *params, uint32_t in_frames);
+uint64_t afg_yin_layout(afg_mel_row *rows, uint64_t n_rows, const afg_yin_params *params);
+int afg_yin_hip(uint64_t n_rows, const afg_mel_row *d_rows, uint64_t n_tiles, const afg_yin_params *params, const float *d_in,
+                uint64_t in_floats, float *d_out, uint64_t out_floats, void *hip_stream);
+
+/* afg_batch_decode_resampled followed by afg_yin_hip: d_out is n_files * channels * 2 * n_out floats on the current device,
+ * [files, channels, 2, n_out], and planes [i, k, 0] (f0) and [i, k, 1] (d') are the definition above applied to row [i, k] --
+ * all T samples of it -- of the tensor afg_batch_decode_resampled makes of the same list with the leading fields of the
+ * options.  n_out == 0 means afg_yin_frames of T; otherwise n_out <= that.  A file's own frames are the first
+ * min(n_out, afg_yin_frames(valid)) of them, valid being the length afg_batch_decode_resampled_norm's groups use, and none
+ * for a file that failed or has no sample; the frames past them are +0.0f in both planes.  n_frames (host, n_files entries,
+ * may be NULL) receives that count per file.  yin.samplerate must equal `samplerate`.  The resampled tensor of a sublist
+ * stands in a scratch pooled under afg_dev_option("resample_scratch_bytes"), sublists of at least one file.  A file that
+ * failed or was refused keeps its status and message, items[i].pcm points at the file's slab (NULL when it failed or was
+ * refused), n_files == 0 is AFG_OK and touches nothing.  Checked before any device call, afg_last_error set: everything
+ * afg_batch_decode_resampled checks, a struct_size below sizeof(afg_pitch_opts), a non-zero `reserved`, the parameters, a
+ * yin.samplerate that differs from samplerate, T without a frame, reflect padding with T <= pad, n_out above the frames
+ * of T. */
+typedef struct afg_pitch_opts {
+    uint32_t         struct_size;   /* sizeof(afg_pitch_opts) */
+    int              n_threads;     /* from here to lowpass_width: as afg_resample_opts */
+    uint32_t         channels;
+    uint32_t         frames;        /* T, samples at `samplerate` */
+    const int64_t   *first_frame;
+    uint32_t         samplerate;
+    uint32_t         mono;
+    uint32_t         in_channels;
+    uint32_t         max_in_rate;
+    uint32_t         lowpass_width;
+    uint32_t         n_out;         /* frames per plane; 0 means afg_yin_frames of T */
+    afg_yin_params   yin;
+    uint32_t         reserved;      /* 0 */
+} afg_pitch_opts;
+int afg_batch_decode_pitch(const uint8_t *const *data, const size_t *length, int n_files, const afg_pitch_opts *opts, float *d_out,
+                           uint32_t *n_frames, afg_batch_result *out);
+
 #ifdef __cplusplus
 }
 #endif
