@@ -115,6 +115,9 @@ FBANK_WINDOW_POVEY, FBANK_WINDOW_HAMMING, FBANK_WINDOW_HANNING, FBANK_WINDOW_BLA
 FBANK_WINDOW_NAMES = {"povey": FBANK_WINDOW_POVEY, "hamming": FBANK_WINDOW_HAMMING, "hanning": FBANK_WINDOW_HANNING,
                       "blackman": FBANK_WINDOW_BLACKMAN, "rectangular": FBANK_WINDOW_RECTANGULAR}
 FBANK_TILE = 16                                  # frames of one row per tile of afg_fbank_hip
+CMN_FRAMES_MAJOR, CMN_COL_MAJOR = 0, 1             # afg_cmn_params.layout
+CMN_LAYOUT_NAMES = {"frames": CMN_FRAMES_MAJOR, "cols": CMN_COL_MAJOR}
+CMN_CHUNK = 32                                   # frames of one slab per tile of afg_slide_cmn_hip
 YIN_TILE, YIN_CHUNK = 4, 16                      # frames of one row per tile of afg_yin_hip; lags per chunk of its cumulative mean
 
 # every symbol include/afg.h declares (checked by tests/test_abi.py)
@@ -167,6 +170,7 @@ ABI_SYMBOLS = [
     "afg_fbank_n_fft", "afg_fbank_frames", "afg_fbank_tables", "afg_fbank_filters", "afg_fbank_layout", "afg_fbank_check_rows", "afg_fbank_hip",
     "afg_batch_decode_fbank",
     "afg_yin_lags", "afg_yin_frames", "afg_yin_layout", "afg_yin_hip", "afg_batch_decode_pitch",
+    "afg_cmn_layout", "afg_cmn_work_bytes", "afg_cmn_check_slabs", "afg_slide_cmn_hip", "afg_batch_decode_fbank_cmn",
 ]
 
 
@@ -374,6 +378,21 @@ class YinParams(C.Structure):
 class PitchOpts(C.Structure):
     """afg_pitch_opts (afg_batch_decode_pitch): afg_resample_opts' fields, n_out, the parameters and a reserved 0."""
     _fields_ = ResampleOpts._fields_ + [("n_out", C.c_uint32), ("yin", YinParams), ("reserved", C.c_uint32)]
+
+
+class CmnParams(C.Structure):
+    """afg_cmn_params (afg_slide_cmn_hip)."""
+    _fields_ = [("cmn_window", C.c_uint32), ("min_cmn_window", C.c_uint32), ("center", C.c_uint32), ("norm_vars", C.c_uint32),
+                ("cols", C.c_uint32), ("layout", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class CmnSlab(C.Structure):
+    """afg_cmn_slab: one slab of frames by columns (afg_slide_cmn_hip)."""
+    _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("pitch", C.c_uint64), ("first_tile", C.c_uint64),
+                ("n_frames", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+CMN_SLAB_DTYPE = np.dtype(CmnSlab)               # arrays of the records, as the other stages' *_DTYPE
 
 
 class NormGroup(C.Structure):
@@ -838,6 +857,13 @@ def lib():
     L.afg_fbank_check_rows.argtypes = [vp, u64, u64, C.POINTER(FbankParams), u64, u64, u64, u64]
     L.afg_fbank_hip.argtypes = [u64, vp, u64, C.POINTER(FbankParams), vp, u64, vp, u64, vp, u64, vp, u64, vp]
     L.afg_batch_decode_fbank.argtypes = [vp, vp, C.c_int, C.POINTER(FbankOpts), vp, vp, C.POINTER(BatchResult)]
+    L.afg_cmn_layout.argtypes = [vp, u64]
+    L.afg_cmn_layout.restype = u64
+    L.afg_cmn_work_bytes.argtypes = [u64, u32]
+    L.afg_cmn_work_bytes.restype = u64
+    L.afg_cmn_check_slabs.argtypes = [vp, u64, u64, C.POINTER(CmnParams), u64, u64, C.c_int]
+    L.afg_slide_cmn_hip.argtypes = [u64, vp, u64, C.POINTER(CmnParams), vp, u64, vp, u64, vp, u64, vp]
+    L.afg_batch_decode_fbank_cmn.argtypes = [vp, vp, C.c_int, C.POINTER(FbankOpts), C.POINTER(CmnParams), vp, vp, C.POINTER(BatchResult)]
     L.afg_yin_lags.argtypes = [C.c_double, C.c_double, C.c_double, u32, u32, C.POINTER(u32), C.POINTER(u32)]
     L.afg_yin_frames.argtypes = [C.POINTER(YinParams), u32]
     L.afg_yin_frames.restype = u32
@@ -3123,6 +3149,129 @@ def batch_decode_fbank(files, frames, samplerate=16000, num_mel_bins=23, frame_l
         return lib().afg_batch_decode_fbank(ptrs, lens, n, C.byref(opts), out.data_ptr(), lengths.ctypes.data, C.byref(res))
 
     out, meta = _batch_tensor_call("batch_decode_fbank", files, shape, out, first_frame, call)
+    return out, meta, lengths[:len(files)].astype(np.int64)
+
+
+def _cmn_layout_code(who, layout):
+    if isinstance(layout, str):
+        if layout not in CMN_LAYOUT_NAMES:
+            raise ValueError(f"{who}: layout {layout!r}: one of {sorted(CMN_LAYOUT_NAMES)}")
+        return CMN_LAYOUT_NAMES[layout]
+    return int(layout)
+
+
+def cmn_params(cols, cmn_window=600, min_cmn_window=100, center=False, norm_vars=False, layout=CMN_FRAMES_MAJOR):
+    """afg_cmn_params with Kaldi's (and torchaudio.functional.sliding_window_cmn's) defaults; layout CMN_* or "frames" / "cols"."""
+    return CmnParams(int(cmn_window), int(min_cmn_window), 1 if center else 0, 1 if norm_vars else 0, int(cols),
+                     _cmn_layout_code("cmn_params", layout), (C.c_uint32 * 2)(0, 0))
+
+
+def cmn_layout(slabs):
+    """afg_cmn_layout: fills first_tile of a CMN_SLAB_DTYPE array in place (tiles of 32 frames); returns the launch's tile count."""
+    assert slabs.dtype == CMN_SLAB_DTYPE and slabs.flags.c_contiguous
+    return int(lib().afg_cmn_layout(slabs.ctypes.data, len(slabs)))
+
+
+def cmn_work_bytes(n_tiles, cols):
+    """afg_cmn_work_bytes: the workspace afg_slide_cmn_hip needs for n_tiles tiles of `cols` columns."""
+    return int(lib().afg_cmn_work_bytes(int(n_tiles), int(cols)))
+
+
+def cmn_check_slabs(slabs, n_tiles, params, in_floats, out_floats, same_plane):
+    """afg_cmn_check_slabs: what afg_slide_cmn_hip checks before it launches, on host records.  AfgError when one fails."""
+    assert slabs.dtype == CMN_SLAB_DTYPE and slabs.flags.c_contiguous
+    check(lib().afg_cmn_check_slabs(slabs.ctypes.data, len(slabs), int(n_tiles), C.byref(params), int(in_floats), int(out_floats),
+                                    1 if same_plane else 0))
+
+
+def slide_cmn(n_slabs, d_slabs, n_tiles, params, d_in, in_floats, d_out, out_floats, d_work, work_bytes, stream=None):
+    """Enqueue the sliding-window normalisation (afg_slide_cmn_hip) on device arrays: slab k of d_slabs (CMN_SLAB_DTYPE records
+    laid out by cmn_layout) from d_in to d_out -- the same tensor for in place -- with a workspace of cmn_work_bytes bytes.
+    The records are checked first (the call waits for `stream` to read them): AfgError, and nothing written, when one fails."""
+    check(lib().afg_slide_cmn_hip(int(n_slabs), _ptr(d_slabs), int(n_tiles), C.byref(params), _ptr(d_in), int(in_floats), _ptr(d_out),
+                                  int(out_floats), _ptr(d_work), int(work_bytes), _stream(stream)))
+
+
+def sliding_cmn_tensor(t, cmn_window=600, min_cmn_window=100, center=False, norm_vars=False, layout="frames", valid_frames=None, out=None):
+    """Sliding-window mean (and variance) normalisation of every slab of a contiguous float32 device tensor [..., frames, cols],
+    or [..., cols, frames] with layout "cols" (afg_slide_cmn_hip, two launches on the current stream; include/afg.h has the
+    definition, Kaldi's window; the arguments are torchaudio.functional.sliding_window_cmn's).  valid_frames: None, or one
+    frame count per slab (the leading axes flattened), 0 .. frames: only that many frames of the slab are read and written,
+    and the windows end there.  out: None (a new tensor, zero behind valid_frames), `t` itself (in place) or another
+    contiguous tensor of t's shape that does not overlap it; what lies behind valid_frames in it is left as it is.  Returns
+    out.  AfgError when a parameter is refused."""
+    import torch
+    code = _cmn_layout_code("sliding_cmn_tensor", layout)
+    if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 2:
+        raise ValueError("sliding_cmn_tensor: a contiguous float32 device tensor with at least two axes")
+    frames, cols = (int(t.shape[-1]), int(t.shape[-2])) if code == CMN_COL_MAJOR else (int(t.shape[-2]), int(t.shape[-1]))
+    prm = cmn_params(max(cols, 1), cmn_window, min_cmn_window, center, norm_vars, code)
+    cmn_check_slabs(np.zeros(0, CMN_SLAB_DTYPE), 0, prm, 0, 0, False)      # (the parameters: AfgError says which)
+    if out is None:
+        out = torch.zeros_like(t) if valid_frames is not None else torch.empty_like(t)
+    elif out.shape != t.shape or out.dtype != t.dtype or out.device != t.device or not out.is_contiguous():
+        raise ValueError("sliding_cmn_tensor: out must be a contiguous tensor of t's shape, dtype and device")
+    if frames >= 1 << 31:
+        raise ValueError("sliding_cmn_tensor: slabs of 2^31 frames or more")
+    n = t.numel() // (frames * cols) if frames * cols else 0
+    slabs = np.zeros(n, CMN_SLAB_DTYPE)
+    slabs["in_off"] = slabs["out_off"] = np.arange(n, dtype=np.uint64) * np.uint64(frames * cols)
+    slabs["pitch"] = frames if code == CMN_COL_MAJOR else cols
+    slabs["n_frames"] = frames
+    if valid_frames is not None:
+        v = np.asarray(valid_frames.cpu() if hasattr(valid_frames, "cpu") else valid_frames).reshape(-1)
+        if v.size != n or (v < 0).any() or (v > frames).any():
+            raise ValueError("sliding_cmn_tensor: valid_frames holds one frame count per slab, 0 .. frames")
+        slabs["n_frames"] = v
+    tiles = cmn_layout(slabs) if n else 0
+    if tiles == 0:
+        return out
+    with torch.cuda.device(t.device):
+        nbytes = cmn_work_bytes(tiles, cols)
+        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=t.device)
+        d_slabs = torch.from_numpy(slabs.view(np.uint8)).to(t.device)
+        slide_cmn(n, d_slabs, tiles, prm, t, t.numel(), out, out.numel(), work, nbytes, torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+def batch_decode_fbank_cmn(files, frames, cmn_window=600, min_cmn_window=100, center=False, norm_vars=False, samplerate=16000,
+                           num_mel_bins=23, frame_length=25.0, frame_shift=10.0, window_type="povey", blackman_coeff=0.42, low_freq=20.0,
+                           high_freq=0.0, round_to_power_of_two=True, snip_edges=True, remove_dc_offset=True, preemphasis_coefficient=0.97,
+                           use_power=True, use_log_fbank=True, use_energy=False, raw_energy=True, htk_compat=False, energy_floor=1.0,
+                           scale=0.0, layout=FBANK_FRAMES_MAJOR, n_out=0, mono=True, out=None, channels=1, first_frame=None, in_channels=0,
+                           max_in_rate=0, lowpass_width=0, n_threads=0):
+    """afg_batch_decode_fbank_cmn: batch_decode_fbank, then sliding_cmn_tensor's normalisation in place over every slab's own
+    frames (the returned lengths), in one call: (tensor, meta, lengths).  The frames behind a file's length, and the slabs of
+    failed files, are batch_decode_fbank's.  The four window arguments are sliding_cmn_tensor's, the rest batch_decode_fbank's."""
+    frames, channels, samplerate = int(frames), int(channels), int(samplerate)
+    if frames < 1 or channels < 1 or samplerate < 1:
+        raise ValueError("batch_decode_fbank_cmn: frames, channels and samplerate must be at least 1")
+    if mono and channels != 1:
+        raise ValueError("batch_decode_fbank_cmn: a mono tensor has one channel")
+    prm = _fbank_kaldi_params("batch_decode_fbank_cmn", samplerate, num_mel_bins, frame_length, frame_shift, round_to_power_of_two, snip_edges,
+                              remove_dc_offset, preemphasis_coefficient, use_power, use_log_fbank, use_energy, raw_energy, htk_compat,
+                              energy_floor, scale, layout)
+    wt = _fbank_window("batch_decode_fbank_cmn", window_type)
+    fbank_check_rows(np.zeros(0, MEL_ROW_DTYPE), 0, prm, 0, 0, 0, 0)      # (the parameters: AfgError says which)
+    cols = prm.n_mels + prm.use_energy
+    cmn = cmn_params(cols, cmn_window, min_cmn_window, center, norm_vars, CMN_COL_MAJOR if prm.layout == FBANK_MEL_MAJOR else CMN_FRAMES_MAJOR)
+    cmn_check_slabs(np.zeros(0, CMN_SLAB_DTYPE), 0, cmn, 0, 0, False)
+    most = fbank_frames(prm, frames)
+    if most == 0:
+        raise ValueError(f"batch_decode_fbank_cmn: {frames} samples hold no frame of {prm.win_length} samples")
+    n_out = int(n_out)
+    if n_out < 0 or n_out > most:
+        raise ValueError(f"batch_decode_fbank_cmn: n_out {n_out}, but {frames} samples have {most} frames")
+    F = n_out if n_out else most
+    shape = (len(files), channels) + ((F, cols) if prm.layout == FBANK_FRAMES_MAJOR else (cols, F))
+    lengths = np.zeros(max(len(files), 1), np.uint32)
+
+    def call(ptrs, lens, n, ff, out, res):
+        opts = FbankOpts(C.sizeof(FbankOpts), int(n_threads), channels, frames, ff, samplerate, 1 if mono else 0, int(in_channels),
+                         int(max_in_rate), int(lowpass_width), n_out, prm, wt, float(low_freq), float(high_freq), float(blackman_coeff), 0)
+        return lib().afg_batch_decode_fbank_cmn(ptrs, lens, n, C.byref(opts), C.byref(cmn), out.data_ptr(), lengths.ctypes.data, C.byref(res))
+
+    out, meta = _batch_tensor_call("batch_decode_fbank_cmn", files, shape, out, first_frame, call)
     return out, meta, lengths[:len(files)].astype(np.int64)
 
 

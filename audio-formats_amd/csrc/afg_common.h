@@ -108,6 +108,11 @@ int normalize_launch(const afg_norm_group *h_groups, uint64_t n_groups, const af
                      const afg_norm_params *params, const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats,
                      void *d_partials, afg_norm_stats *d_stats, hipStream_t stream);
 
+// afg_slide_cmn_hip likewise (slidecmn.hip)
+int slide_cmn_launch(const afg_cmn_slab *h_slabs, uint64_t n_slabs, const afg_cmn_slab *d_slabs, uint64_t n_tiles, const afg_cmn_params *params,
+                     const float *d_in, uint64_t in_floats, float *d_out, uint64_t out_floats, void *d_work, uint64_t work_bytes,
+                     hipStream_t stream);
+
 // afg_cepstra_hip likewise (cepstra.hip)
 int cepstra_launch(const afg_cep_row *h_rows, uint64_t n_rows, const afg_cep_row *d_rows, uint64_t n_tiles, const afg_cep_params *params,
                    const float *d_in, uint64_t in_floats, const float *d_dct, uint64_t dct_floats, float *d_out, uint64_t out_floats,

@@ -664,6 +664,18 @@ int afg_yin_hip(ulong n_rows, const(afg_mel_row)* d_rows, ulong n_tiles, const(a
                 ulong in_floats, float* d_out, ulong out_floats, void* hip_stream);
 int afg_batch_decode_pitch(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_pitch_opts)* opts, float* d_out,
                            uint* n_frames, afg_batch_result* out_);
+// sliding-window mean and variance normalisation of feature slabs, Kaldi's window (include/afg.h has the definition)
+enum : uint { AFG_CMN_FRAMES_MAJOR = 0, AFG_CMN_COL_MAJOR = 1, AFG_CMN_CHUNK = 32, AFG_CMN_MAX_WINDOW = 1048576, AFG_CMN_MAX_COLS = 1024 }
+struct afg_cmn_params { uint cmn_window, min_cmn_window, center, norm_vars, cols, layout; uint[2] reserved; }
+struct afg_cmn_slab { ulong in_off, out_off, pitch, first_tile; uint n_frames; uint[3] reserved; }
+ulong afg_cmn_layout(afg_cmn_slab* slabs, ulong n_slabs);
+ulong afg_cmn_work_bytes(ulong n_tiles, uint cols);
+int afg_cmn_check_slabs(const(afg_cmn_slab)* slabs, ulong n_slabs, ulong n_tiles, const(afg_cmn_params)* params, ulong in_floats,
+                        ulong out_floats, int same_plane);
+int afg_slide_cmn_hip(ulong n_slabs, const(afg_cmn_slab)* d_slabs, ulong n_tiles, const(afg_cmn_params)* params, const(float)* d_in,
+                      ulong in_floats, float* d_out, ulong out_floats, void* d_work, ulong work_bytes, void* hip_stream);
+int afg_batch_decode_fbank_cmn(const(ubyte*)* data, const(size_t)* length, int n_files, const(afg_fbank_opts)* opts,
+                               const(afg_cmn_params)* cmn, float* d_out, uint* n_frames, afg_batch_result* out_);
 // the `transcode` example for a batch: every item is a complete WAV file (out_format AFG_FORMAT_WAV; AFG_FORMAT_QOA is refused)
 int afg_batch_transcode(const(ubyte*)* data, const(size_t)* length, int n_files, int out_format, const(afg_encoding_options)* enc,
                         const(afg_batch_opts)* opts, afg_encode_result* result);

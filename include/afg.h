@@ -2585,6 +2585,98 @@ typedef struct afg_pitch_opts {
 int afg_batch_decode_pitch(const uint8_t *const *data, const size_t *length, int n_files, const afg_pitch_opts *opts, float *d_out,
                            uint32_t *n_frames, afg_batch_result *out);
 
+/* ---- Sliding-window cepstral mean and variance normalisation (Kaldi's apply-cmvn-sliding, torchaudio's sliding_window_cmn) --
+ * What the Kaldi recipes put behind fbank and MFCC features instead of one set of statistics per utterance: every frame is
+ * normalised by the mean (and variance) of a window of frames around or in front of it -- 300 frames centred for x-vector and
+ * ECAPA speaker models, 600 causal frames with min_cmn_window 100 for online ASR.  The reference has no such stage: the
+ * definition below is this library's own, tests/slidecmn_model.py states it again in numpy, and the device follows it bit
+ * for bit.
+ *
+ * Slab (afg_cmn_slab): n_frames = N valid frames by `cols` columns of float32; element [t][c] is at in_off + t * pitch + c of
+ * d_in with AFG_CMN_FRAMES_MAJOR (what afg_fbank_hip writes by default; Kaldi's own layout) and at in_off + c * pitch + t
+ * with AFG_CMN_COL_MAJOR (the mel, MFCC and AFG_FBANK_MEL_MAJOR slabs); out_off likewise in d_out, with the same pitch.
+ * Frames at and beyond N are neither read nor written; N == 0 touches nothing.
+ *
+ * Parameters (afg_cmn_params), uniform over a launch: cmn_window 1 .. AFG_CMN_MAX_WINDOW (2^20: nothing a tile holds depends
+ * on the window, but every output adds one pair of chunk totals per 32 frames of it, so the time grows with it);
+ * min_cmn_window 1 .. AFG_CMN_MAX_WINDOW (used only without center); center and norm_vars each 0 or 1; cols
+ * 1 .. AFG_CMN_MAX_COLS (1024); layout AFG_CMN_FRAMES_MAJOR or AFG_CMN_COL_MAJOR; reserved 0.  N is at most 2^31 - 1.
+ *
+ * Window of frame t, in integers -- Kaldi's SlidingWindowCmnInternal, quirks included:
+ *   center:  ws = t - cmn_window / 2, we = ws + cmn_window;   otherwise:  ws = t - cmn_window, we = t + 1 (so the causal window
+ *   holds cmn_window + 1 frames);
+ *   if ws < 0: we -= ws, then ws = 0;
+ *   if not center and we > t (always): we = max(t + 1, min_cmn_window);
+ *   if we > N: ws -= we - N, then we = N, then ws = max(ws, 0);
+ *   n = we - ws, at least 1; the window is frames ws .. we - 1.
+ *
+ * Sums S1 = sum of x and S2 = sum of x * x over the window, per column, in float64, in a fixed order, from the window's own
+ * elements only (no difference of running prefixes: that would carry a NaN or an infinity of frame 0 into every later
+ * window, and lose the low bits on long slabs).  (double)x * (double)x is exact; only the adds round.  Chunks are
+ * AFG_CMN_CHUNK = 32 frames, aligned to frame 0 of the slab; the last may be short.  Inside a chunk pre[j] is the sum from
+ * the chunk's first frame ascending to j inclusive and suf[j] the sum from the chunk's last valid frame descending to j
+ * inclusive, each starting from +0.0; the chunk's total is pre of its last frame.  A window whose first and last frame lie in
+ * different chunks sums as suf[ws], then the totals of the whole chunks strictly between added one after the other ascending,
+ * then pre[we - 1] added last.  A window inside one chunk sums its elements ascending from +0.0.  S2 follows the same order.
+ *
+ * Output, in float64 until the last step, every operation rounded by itself (no fused multiply-add):
+ *   mean = S1 / n;   without norm_vars  y = (float)((double)x - mean);
+ *   with norm_vars and n == 1  y = +0.0f;
+ *   with norm_vars and n > 1   var = S2 / n - mean * mean;  var = var < 1e-10 ? 1e-10 : var (Kaldi's floor; a NaN stays a NaN);
+ *                              y = (float)(((double)x - mean) * (1.0 / sqrt(var))).
+ * A NaN result is always 0x7fc00000, as in the normalise stage.  So a NaN frame makes NaN exactly of the outputs whose window
+ * holds it; an infinite one likewise with norm_vars (var is inf - inf), while without it mean is infinite and finite elements
+ * of such a window come out as the opposite infinity.  torchaudio.functional.sliding_window_cmn has no floor and, with
+ * norm_vars, n == 1 gives 0 there too; away from the floor the two agree to rounding (tests/test_slidecmn_model.py).
+ *
+ * Records, tiles, checks.  A tile is one chunk of one slab, all columns; a slab has ceil(N / 32) of them, a slab's tiles follow
+ * those of the slab before.  afg_cmn_layout fills first_tile and returns the launch's tile count.  The launch needs a
+ * workspace of afg_cmn_work_bytes(n_tiles, cols) = n_tiles * cols * 144 bytes, 16-byte aligned, that overlaps neither plane:
+ * the chunk totals, and a copy of every valid element -- the window of a frame reaches into other tiles, so in place nothing
+ * may read the plane once the first result is written; both placements run through the copy and give the same bits.
+ * afg_cmn_check_slabs is host only and runs every check the entry makes: parameters in range; first_tile and n_tiles as
+ * afg_cmn_layout gives them; reserved 0; N <= 2^31 - 1; and for a slab with N > 0: pitch at least cols (frames-major, when
+ * N > 1) or at least N (col-major, when cols > 1); the slab inside [0, in_floats) and [0, out_floats); no output slab -- its
+ * whole span, the gaps a larger pitch leaves included -- overlapping another output slab, or with same_plane (the entry
+ * passes d_in == d_out) any input slab but its own at the same offset.  AFG_ERR_INVALID with afg_last_error set otherwise;
+ * n_slabs == 0 checks the parameters alone.  afg_slide_cmn_hip fetches d_slabs on hip_stream, waits, makes the same checks
+ * and the workspace's, and on anything but a pass writes nothing; then two launches on hip_stream.  n_slabs == 0 is AFG_OK.
+ * Locality: a slab's result is the same bits wherever it stands in the planes and whatever its neighbours are. */
+#define AFG_CMN_FRAMES_MAJOR 0
+#define AFG_CMN_COL_MAJOR    1
+#define AFG_CMN_CHUNK        32
+#define AFG_CMN_MAX_WINDOW   1048576
+#define AFG_CMN_MAX_COLS     1024
+typedef struct afg_cmn_params {    /* 32 bytes */
+    uint32_t cmn_window, min_cmn_window, center, norm_vars;
+    uint32_t cols, layout;         /* AFG_CMN_* */
+    uint32_t reserved[2];          /* 0 */
+} afg_cmn_params;
+typedef struct afg_cmn_slab {      /* 48 bytes */
+    uint64_t in_off, out_off;      /* float index of element [0][0] in d_in / d_out */
+    uint64_t pitch;                /* floats from one frame (frames-major) or one column (col-major) to the next, in both planes */
+    uint64_t first_tile;           /* filled in by afg_cmn_layout */
+    uint32_t n_frames;             /* N */
+    uint32_t reserved[3];          /* 0 */
+} afg_cmn_slab;
+/* Host: fills first_tile of every slab, returns the launch's tile count. */
+uint64_t afg_cmn_layout(afg_cmn_slab *slabs, uint64_t n_slabs);
+/* Host: the workspace of a launch, n_tiles * cols * 144 bytes. */
+uint64_t afg_cmn_work_bytes(uint64_t n_tiles, uint32_t cols);
+int afg_cmn_check_slabs(const afg_cmn_slab *slabs, uint64_t n_slabs, uint64_t n_tiles, const afg_cmn_params *params, uint64_t in_floats,
+                        uint64_t out_floats, int same_plane);
+int afg_slide_cmn_hip(uint64_t n_slabs, const afg_cmn_slab *d_slabs, uint64_t n_tiles, const afg_cmn_params *params, const float *d_in,
+                      uint64_t in_floats, float *d_out, uint64_t out_floats, void *d_work, uint64_t work_bytes, void *hip_stream);
+
+/* afg_batch_decode_fbank, then afg_slide_cmn_hip in place over the first n_frames[i] frames of every slab [i, k], in the
+ * layout the fbank options name.  cols and layout of `cmn` are filled in from the fbank options (n_mels + use_energy and the
+ * fbank layout), whatever the caller put there; its other fields are the caller's.  Frames behind n_frames[i] stay as
+ * afg_batch_decode_fbank leaves them, and so do the slabs of failed and refused files, whose count is 0.  n_frames (host,
+ * n_files entries) may be NULL.  Statuses, messages and items[i] are afg_batch_decode_fbank's, and so is every check it makes;
+ * NULL or out-of-range cmn is refused before any device call as well.  The workspace is pooled. */
+int afg_batch_decode_fbank_cmn(const uint8_t *const *data, const size_t *length, int n_files, const afg_fbank_opts *opts,
+                               const afg_cmn_params *cmn, float *d_out, uint32_t *n_frames, afg_batch_result *out);
+
 #ifdef __cplusplus
 }
 #endif
